@@ -6,13 +6,21 @@ iteration (train.py:158-161,211): prefilter_voxel -> render(training) -> backwar
 fixed linear loss (sum(image * w), w seeded) -> (N>1) gradient all-reduce over RCCL.
 Workload = BASELINE.json's metric config: 1 M-anchor synthetic scene, 1920x1080,
 step-20000 semantics (context model on all anchors + rate + rasterizer).  The
-raster-only phase (step <= 3000 semantics) is timed too and reported as
+raster-only phase (step <= 3000 semantics) is timed too (--full) and reported as
 `value_raster_only`.  Inputs are resident in HBM before the timed region.
 
 One rank per GPU (torchrun); views shard across ranks (weak scaling: one view per
 rank per step), parameters replicated, one flattened-gradient all-reduce per step.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0
+(`value`, `ms_per_step`).  `--full` adds everything else this file measures: the
+per-kernel table of a second, profiled pass and the rooflines built on it, re-timing of
+disturbed runs, the raster-only / mid-phase / training-loss steps, the heavy-pair scene,
+the codec round trips and the CPU baseline (the `--no-*` options trim that list).
+Re-timing needs the profiled pass's kernel time, so a plain run's `value` is the median
+segment of its one timing attempt: a run disturbed by other load on the host is not
+timed again, and shows only in the spread of `timing.ms_per_step_by_segment`.
+`--dump-outputs DIR` writes what the last timed step handed its caller as .npy files.
 """
 from __future__ import annotations
 
@@ -63,6 +71,10 @@ def parse():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--views", type=int, default=8)
     ap.add_argument("--step-semantics", type=int, default=20000, help="training iteration number passed to render()")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (profiled pass, other phases and scenes, codec, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (render dict, loss, parameter gradients) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-raster-only", action="store_true")
     ap.add_argument("--no-codec", action="store_true")
@@ -91,8 +103,9 @@ class _LinearLoss:
 
 
 def one_step(pc, cam, pipe, bg, w, step_sem, params, sync, gt=None):
-    """prefilter -> render -> backward (-> all-reduce). Returns the render dict.  gt: use the training image loss
-    of train.py:199-209 (L1 + SSIM + scaling / rate / mask regularisers) instead of the fixed linear loss."""
+    """prefilter -> render -> backward (-> all-reduce). Returns the render dict, with the step's loss under "loss".  gt: use
+    the training image loss of train.py:199-209 (L1 + SSIM + scaling / rate / mask regularisers) instead of the fixed linear
+    loss."""
     import torch
     from contextgs_amd.renderer import prefilter_voxel, render
     for p in params:
@@ -107,6 +120,7 @@ def one_step(pc, cam, pipe, bg, w, step_sem, params, sync, gt=None):
         if pkg["bit_per_param"] is not None:
             loss = loss + 0.001 * pkg["bit_per_param"] + 5e-4 * mask_reg(pc._mask)                    # train.py:207-209
     loss.backward()
+    pkg["loss"] = loss.detach()
     if sync is not None:
         sync.finish()        # RCCL over xGMI: per-anchor tensors in place (started from gradient hooks), MLPs as one bucket
     return pkg
@@ -162,6 +176,79 @@ def read_prof():
         if n.value:
             out[L.cgs_prof_name(i).decode()] = (ms.value, n.value)
     return out
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_ROWS = 65536
+
+
+def _sample_rows(n, k):
+    """The k rows of an n-row output that --dump-outputs keeps: a fixed draw seeded by n, sorted (the same rows every run)."""
+    import numpy as np
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng(n).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, pkg, pc):
+    """Write what the timed step hands its caller after the last timed step: every entry of the render dict (the loss
+    among them) and the gradient of every parameter, as out_dir/<name>.npy (float32, or float64 for 64-bit values and
+    Python scalars; gradients as grad.<parameter name>.npy).  Small arrays are written whole; of an output with more rows
+    (per anchor / per Gaussian) than k, only the k rows _sample_rows() picks.  k is DUMP_SAMPLE_ROWS, halved until all
+    of it fits in DUMP_LIMIT_BYTES; an image larger than half the limit is sampled by pixel ([H*W, C] rows) instead of
+    being written whole.  Nothing is written before the whole dump is known to fit."""
+    import numpy as np
+    import torch
+
+    def flat(v):                    # nested lists of numbers / tensors (bpp_per_level: [ratio, bpp, [ratio, bpp], ...])
+        if isinstance(v, (list, tuple)):
+            return [x for e in v for x in flat(e)]
+        if isinstance(v, torch.Tensor):
+            return v.detach().double().flatten().cpu().tolist()
+        return [float(v)]
+
+    def as_array(v):
+        if isinstance(v, torch.Tensor):
+            dt = torch.float64 if v.dtype in (torch.float64, torch.int64) else torch.float32
+            return v.to(dt).cpu().numpy()
+        if isinstance(v, (list, tuple)):
+            return np.array(flat(v), dtype=np.float64)
+        if isinstance(v, (int, float)):
+            return np.array(v, dtype=np.float64)
+        return None
+
+    arrays = {k: pkg[k] for k in sorted(pkg)}
+    arrays.update(("grad." + n, p.grad) for n, p in pc.named_parameters() if p.grad is not None)
+    tensors, small = {}, {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            if name == "render" and v.dim() == 3 and v.numel() * 4 > DUMP_LIMIT_BYTES // 2:
+                v = v.flatten(1).t()                    # too large to write whole: pixels as rows
+            tensors[name] = v
+        elif (a := as_array(v)) is not None:
+            small[name] = a
+
+    def nbytes(k):
+        total = sum(a.nbytes for a in small.values())
+        for v in tensors.values():
+            width = 8 if v.dtype in (torch.float64, torch.int64) else 4
+            total += width * (min(k, v.shape[0]) * (v.numel() // max(1, v.shape[0])) if v.dim() > 0 else 1)
+        return total
+
+    k = DUMP_SAMPLE_ROWS
+    while nbytes(k) > DUMP_LIMIT_BYTES:
+        if k == 1:
+            raise RuntimeError(f"--dump-outputs: the outputs do not fit in {DUMP_LIMIT_BYTES} bytes")
+        k //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in tensors.items():
+        rows = _sample_rows(v.shape[0], k) if v.dim() > 0 else None
+        if rows is not None:
+            v = v[torch.from_numpy(rows).to(v.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), as_array(v))
+    for name, a in small.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -238,27 +325,42 @@ def main():
         if rank == 0:
             print("[bench] process group:", json.dumps(dist_report), file=sys.stderr, flush=True)
 
-    full = lambda i: one_step(pc, cam_of(i), pipe, bg, w, args.step_semantics, params, sync)
+    last_step = {}                          # "at": index of the last timed step, whose render dict is kept for --dump-outputs
+
+    def full(i):
+        pkg = one_step(pc, cam_of(i), pipe, bg, w, args.step_semantics, params, sync)
+        if i == last_step.get("at"):
+            last_step["pkg"] = pkg
+        return pkg
+
     raster = lambda i: one_step(pc, cam_of(i), pipe, bg, w, 1000, params, sync)
 
     pkg_full = None
     for i in range(args.warmup):
         pkg_full = full(i)
-    # `value` is timed with the library's per-kernel event bracketing OFF; the per-kernel table (roofline leg) comes from a
-    # second, separately timed pass over the same K steps with it ON (HIP events on the launch stream around each kernel)
+    # `value` is timed with the library's per-kernel event bracketing OFF; the per-kernel table (roofline leg, --full) comes
+    # from a second, separately timed pass over the same K steps with it ON (HIP events on the launch stream around each kernel)
     L.cgs_prof_enable(0)
     del _HOST_S[:]
     if sync is not None:
         sync.exposure_report()              # (clears the warm-up steps' records)
+    last_step["at"] = args.steps - 1
     dt, seg_s, seg_k = timed_segments(full, args.steps, dist_on)
+    del last_step["at"]
     if sync is not None and dist_report is not None:
         dist_report["allreduce_exposed_ms_per_step"] = sync.exposure_report()
     host_ms = sorted(t / k * 1e3 for t, k in _HOST_S)
     host_ms_per_step = host_ms[len(host_ms) // 2] if host_ms else None
-    L.cgs_prof_enable(1)
-    dt_prof = timed(full, args.steps, dist_on)
-    prof = read_prof()
-    L.cgs_prof_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step.pop("pkg"), pc)
+    last_step.clear()
+    dt_prof = lib_ms_now = None
+    if args.full:
+        L.cgs_prof_enable(1)
+        dt_prof = timed(full, args.steps, dist_on)
+        prof = read_prof()
+        L.cgs_prof_enable(0)
+        lib_ms_now = sum(v[0] for v in prof.values()) / max(1, args.steps)
     views = args.steps * world
     seg_ms = sorted(t / k * 1e3 for t, k in zip(seg_s, seg_k))
     ms_per_step = seg_ms[len(seg_ms) // 2]                     # median segment
@@ -268,12 +370,11 @@ def main():
     # them (how round 5's leak of the fused level node showed up: 14.6 ms steps; HISTORY.md "Round 5").  N = 1 only: when the K
     # timed steps took more than RETIME_RATIO (1.3) x this library's kernel time of the same steps (normally 1.09 x), they are
     # timed again — at most two more attempts, 5 s apart — and `value` is the MEDIAN over every segment of every attempt (not the best one); EVERY attempt is listed
-    # in `timing.attempts`.
-    lib_ms_now = sum(v[0] for v in prof.values()) / max(1, args.steps)
+    # in `timing.attempts`.  (--full only: the kernel time comes from the profiled pass.)
     attempts = [{"ms_per_step": round(ms_per_step, 3), "ms_per_step_by_segment": [round(t / k * 1e3, 3) for t, k in zip(seg_s, seg_k)]}]
     all_seg_ms, all_host = list(seg_ms), list(host_ms)
     last = ms_per_step
-    while world == 1 and last > RETIME_RATIO * lib_ms_now and len(attempts) < 3:
+    while args.full and world == 1 and last > RETIME_RATIO * lib_ms_now and len(attempts) < 3:
         time.sleep(5.0)
         del _HOST_S[:]
         dt2, seg_s2, seg_k2 = timed_segments(full, args.steps, dist_on)
@@ -295,7 +396,7 @@ def main():
     value_all_steps = views / dt
 
     value_raster = value_mid = None
-    if not args.no_raster_only:
+    if args.full and not args.no_raster_only:
         for i in range(max(1, args.warmup // 2)):
             raster(i)
         dt_r = timed(raster, args.steps, dist_on)
@@ -308,7 +409,7 @@ def main():
     # the same step with the training image loss of train.py:199-209 (fused L1 + SSIM) instead
     # of the metric's fixed linear loss
     value_img_loss = None
-    if not args.no_image_loss:
+    if args.full and not args.no_image_loss:
         gt_img = torch.rand(3, H, W, device="cuda", generator=g)
         with_loss = lambda i: one_step(pc, cam_of(i), pipe, bg, w, args.step_semantics, params, sync, gt=gt_img)
         for i in range(max(1, args.warmup // 2)):
@@ -317,7 +418,10 @@ def main():
 
     # ---- workload statistics of one view (rank 0) for the algorithmic-byte accounting ----
     result = None
-    if rank == 0:
+    n_vis = P = R = R_eff = lib_ms = None
+    roofline = blend = mlp_group = ctx_group = codec = cpu = None
+    kernels, extra = {}, {}
+    if rank == 0 and args.full:
         from contextgs_amd.rasterizer import raster_stats
         from contextgs_amd.renderer import _raster_settings, prefilter_voxel, render
         cam = cam_of(0)
@@ -520,6 +624,8 @@ def main():
             if not args.no_cpu_baseline and world == 1:      # reported at N=1 only (torchrun also pins OMP to 1 thread)
                 cpu = cpu_baseline(pc, cam, pipe, bg, w, pkg)
 
+    if rank == 0:
+        r3 = lambda x: None if x is None else round(x, 3)
         result = {
             "metric": "views/sec fwd+bwd @1920\u00d71080, 1M anchors", "value": round(value, 3), "unit": "views/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
@@ -531,7 +637,7 @@ def main():
                        "gaussians_per_view": P, "tile_pairs_per_view": R, "R_eff": R_eff, "parallelism": f"dp{world}"},
             "timing": {"segments": len(seg_s), "steps_per_segment": seg_k, "ms_per_step_by_segment": [round(t / k * 1e3, 3) for t, k in zip(seg_s, seg_k)],
                        "ms_per_step_min": round(seg_ms[0], 3), "ms_per_step_max": round(seg_ms[-1], 3),
-                       "attempts": attempts, "kernel_ms_per_step_of_the_profiled_pass": round(lib_ms_now, 3),
+                       "attempts": attempts, "kernel_ms_per_step_of_the_profiled_pass": r3(lib_ms_now),
                        "value_over_all_steps": round(value_all_steps, 3),
                        "host_ms_per_step": None if host_ms_per_step is None else round(host_ms_per_step, 3),
                        "note": "value / ms_per_step = the median of the separately bracketed segments of the K timed steps; "
@@ -546,8 +652,8 @@ def main():
             "roofline": roofline, "blend_roofline": blend, "mlp_group_roofline": mlp_group, "ctx_group_roofline": ctx_group,
             "kernels": kernels,
             "dist": dist_report,
-            "hip_kernel_ms_per_step": round(lib_ms, 3),
-            "ms_per_step_profiled_pass": round(dt_prof / args.steps * 1e3, 3),
+            "hip_kernel_ms_per_step": r3(lib_ms),
+            "ms_per_step_profiled_pass": None if dt_prof is None else round(dt_prof / args.steps * 1e3, 3),
             "cpu_baseline": cpu,
             "codec": codec,
             "extra": extra,

@@ -50,7 +50,7 @@ def test_bench_two_ranks_prints_one_json_line(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CGS_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--anchors", "100000"]
+           "--anchors", "100000", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     if r.returncode != 0 and ("in use" in r.stderr or "EADDRINUSE" in r.stderr):     # the probed port was taken meanwhile
         cmd[cmd.index("--master-port") + 1] = str(_free_port())

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B: weight gradients launched inline (default on one GPU) vs deferred to the end of the backward
 # (CGS_DEFER_WGRAD=1; what dist.GradientSync switches on for world > 1).  Headline step only.
-F="--no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps"
+F="--full --no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps"
 mkdir -p gpurun_out
 for rep in 1 2; do
   for d in 0 1; do

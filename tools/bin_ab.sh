@@ -3,7 +3,7 @@
 # (CGS_BIN_MODE=1), the two-level binning wherever the grid allows it (2) and the per-view choice (0 = what ships).
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
 timeout -k 5 900 python -m pytest tests/test_raster_gpu.py tests/test_raster_edge_gpu.py tests/test_api_edge_gpu.py -x -q 2>&1 | tail -4 | tee gpurun_out/bin_ab_tests.txt
-F="--no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-eval-fps --steps 60"
+F="--full --no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-eval-fps --steps 60"
 for rep in 1 2; do
  for m in 1 2 0; do
   CGS_BIN_MODE=$m timeout -k 5 400 python bench.py $F 2>gpurun_out/bin_ab_err_$m.txt | python -c "

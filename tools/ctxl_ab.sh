@@ -6,7 +6,7 @@ V=${1:-clpipe0}
 timeout -k 5 900 python -m pytest tests/test_ctx_level_gpu.py tests/test_training_parity_gpu.py tests/test_ctx_ops_gpu.py -x -q 2>&1 | tail -2
 echo "product:"; timeout -k 5 200 python tools/ctxl_micro.py 800000 20 71 2>&1 | grep "us  "
 echo "$V:"; CGS_LIB_PATH=tools/variants/libcgs_$V.so CGS_LIB_ALLOW_STALE=1 timeout -k 5 200 python tools/ctxl_micro.py 800000 20 71 2>&1 | grep "us  "
-F="--no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
+F="--full --no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
 for rep in 1 2; do
  for v in product $V; do
   if [ $v = product ]; then E="X=1"; else E="CGS_LIB_PATH=tools/variants/libcgs_$v.so CGS_LIB_ALLOW_STALE=1"; fi

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
 V=${1:-m3wpipe0}; V2=$2
 timeout -k 5 600 python -m pytest tests/test_mlp_gpu.py tests/test_anchor_gen_gpu.py -x -q 2>&1 | tail -2
-F="--no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
+F="--full --no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
 for rep in 1 2; do
  for v in product $V $V2; do
   if [ $v = product ]; then E="X=1"; else E="CGS_LIB_PATH=tools/variants/libcgs_$v.so CGS_LIB_ALLOW_STALE=1"; fi

@@ -4,7 +4,7 @@ set -x
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-FLAGS="--no-cpu-baseline --no-heavy --no-eval-fps --no-codec --no-raster-only --no-image-loss"
+FLAGS="--full --no-cpu-baseline --no-heavy --no-eval-fps --no-codec --no-raster-only --no-image-loss"
 timeout 600 python bench.py $FLAGS > gpurun_out/bench_profiled_cmd.json 2> gpurun_out/bench_profiled_cmd.err
 rm -rf /tmp/prof_full
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_full -o full -- python bench.py $FLAGS > gpurun_out/prof_full.log 2>&1

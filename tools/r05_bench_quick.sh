@@ -1,7 +1,7 @@
 #!/bin/bash
 # two short headline bench lines with the per-scope kernel averages (no tests)
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-F="--no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
+F="--full --no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
 for rep in 1 2; do
   timeout 300 python bench.py $F 2>gpurun_out/r05_bench_quick_err.txt | python -c "
 import json,sys

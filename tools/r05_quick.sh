@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 timeout 1500 python -m pytest tests/test_ctx_level_gpu.py tests/test_training_parity_gpu.py tests/test_context_gpu.py tests/test_ctx_ops_gpu.py tests/test_training_gpu.py tests/test_edge_cases_gpu.py -x -q 2>&1 | tail -25 | tee gpurun_out/r05_quick_tests.txt
-F="--no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
+F="--full --no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
 for rep in 1 2; do
  for fused in 0 1; do
   CGS_LEVEL_FUSED=$fused timeout 300 python bench.py $F 2>gpurun_out/r05_quick_bench_err_$fused.txt | python -c "

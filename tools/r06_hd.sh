@@ -1,7 +1,7 @@
 # hyper latents' gradient rows written by the level kernels (CGS_HYPER_DIRECT): tests, then same-box A/B on the quick headline bench
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
 (timeout 1500 python -m pytest tests/test_ctx_level_gpu.py tests/test_training_gpu.py tests/test_training_parity_gpu.py tests/test_context_gpu.py tests/test_trajectory_gpu.py tests/test_dist_train_gpu.py tests/test_eb_gpu.py tests/test_rate_sub_gpu.py -x -q 2>&1 | tail -5)
-FLAGS="--no-cpu-baseline --no-heavy --no-eval-fps --no-codec --no-raster-only --no-image-loss --steps 60"
+FLAGS="--full --no-cpu-baseline --no-heavy --no-eval-fps --no-codec --no-raster-only --no-image-loss --steps 60"
 for rep in 1 2; do for e in 1 0; do
 CGS_HYPER_DIRECT=$e timeout 600 python bench.py $FLAGS > gpurun_out/hd.json 2> gpurun_out/bench.err
 python - <<PY

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 (timeout 1500 python -m pytest tests/test_raster_gpu.py tests/test_raster_edge_gpu.py tests/test_edge_cases_gpu.py tests/test_fused_view_gpu.py tests/test_configs_gpu.py -x -q 2>&1 | tail -4) > gpurun_out/r06_tq.log 2>&1; cat gpurun_out/r06_tq.log
-FLAGS="--no-cpu-baseline --no-eval-fps --no-codec --no-raster-only --no-image-loss"
+FLAGS="--full --no-cpu-baseline --no-eval-fps --no-codec --no-raster-only --no-image-loss"
 for rep in 1 2; do
 timeout 900 python bench.py $FLAGS > gpurun_out/r06_bench_q.json 2> gpurun_out/bench.err
 python - <<'PY'

@@ -2,7 +2,7 @@ cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 (timeout 600 python -m pytest tests/test_rate_sub_gpu.py -x -q 2>&1 | tail -3) > gpurun_out/r06_t1.log
 (timeout 300 python tools/rate_sub_micro.py 2>&1 | grep fused) > gpurun_out/r06_micro3.log
-FLAGS="--no-cpu-baseline --no-heavy --no-eval-fps --no-codec --no-raster-only --no-image-loss"
+FLAGS="--full --no-cpu-baseline --no-heavy --no-eval-fps --no-codec --no-raster-only --no-image-loss"
 for rep in 1 2; do
 CGS_RATE_FUSED=0 timeout 600 python bench.py $FLAGS > gpurun_out/r06_bench_ratefused0_$rep.json 2> gpurun_out/bench.err
 timeout 600 python bench.py $FLAGS > gpurun_out/r06_bench_ratefused1_$rep.json 2>> gpurun_out/bench.err

@@ -2,7 +2,7 @@
 # headline scene and heavy-pair scene
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
 (timeout 900 python -m pytest tests/test_raster_gpu.py tests/test_raster_edge_gpu.py tests/test_fused_view_gpu.py -x -q 2>&1 | tail -2)
-FLAGS="--no-cpu-baseline --no-eval-fps --no-codec --no-raster-only --no-image-loss"
+FLAGS="--full --no-cpu-baseline --no-eval-fps --no-codec --no-raster-only --no-image-loss"
 for rep in 1 2; do for v in product rbraster; do
 if [ $v = product ]; then E="X=1"; else E="CGS_LIB_PATH=$GRAFT_REPO_ROOT/tools/variants/libcgs_$v.so CGS_LIB_ALLOW_STALE=1"; fi
 env $E timeout 900 python bench.py $FLAGS > gpurun_out/ab.json 2> gpurun_out/bench.err

@@ -1,6 +1,6 @@
 # blend kernels' tile order: how many list-length classes matter?  TO_TOP = c: every list of >= 2^(c-1) entries in one class
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-FLAGS="--no-cpu-baseline --no-eval-fps --no-codec --no-raster-only --no-image-loss --no-heavy"
+FLAGS="--full --no-cpu-baseline --no-eval-fps --no-codec --no-raster-only --no-image-loss --no-heavy"
 for rep in 1 2; do for v in product top11 top10 top9; do
 if [ $v = product ]; then E="X=1"; else E="CGS_LIB_PATH=$GRAFT_REPO_ROOT/tools/variants/libcgs_$v.so CGS_LIB_ALLOW_STALE=1"; fi
 env $E timeout 900 python bench.py $FLAGS > gpurun_out/ab.json 2> gpurun_out/bench.err

@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT
 for n in 100000 500000 1500000 3000000; do
-  timeout 600 python bench.py --anchors $n --steps 12 --warmup 9 --no-cpu-baseline --no-heavy --no-eval-fps --no-image-loss 2>/dev/null | tail -1 | python -c "
+  timeout 600 python bench.py --full --anchors $n --steps 12 --warmup 9 --no-cpu-baseline --no-heavy --no-eval-fps --no-image-loss 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['codec']; cf=d['config']
 v2=c.get('container_v2',{})

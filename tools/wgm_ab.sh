@@ -1,7 +1,7 @@
 #!/bin/bash
 # rows per workgroup of wgrad_multi_kernel (the level MLPs' weight gradients on the 15 % rate subset: ~60 k rows per level)
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-F="--no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
+F="--full --no-cpu-baseline --no-raster-only --no-codec --no-image-loss --no-heavy --no-eval-fps --steps 60"
 for rep in 1 2; do
  for v in ${VARIANTS:-product wgm512 wgm1024 wgm2048}; do
   if [ $v = product ]; then E="X=1"; else E="CGS_LIB_PATH=tools/variants/libcgs_$v.so CGS_LIB_ALLOW_STALE=1"; fi
