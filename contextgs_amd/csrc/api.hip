@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include "cgs_internal.h"
+#include "raster_forms.h"
 
 static thread_local char g_err[512] = "";
 
@@ -134,6 +135,22 @@ extern "C" int cgs_filter(const cgs_raster_cfg *cfg, int64_t N, const float *mea
                                  (hipStream_t)stream);
 }
 
+// visible_filter(means3D, cov3D_precomp=...): the same projection from the six covariance numbers
+extern "C" int cgs_filter_cov(const cgs_raster_cfg *cfg, int64_t N, const float *means3D, const float *cov3D, int32_t *radii,
+                              void *stream) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (N < 0) { cgs_set_error("N < 0"); return CGS_ERR_ARG; }
+    if (N > 0 && (!means3D || !cov3D || !radii)) {
+        cgs_set_error("cgs_filter_cov: NULL input");
+        return CGS_ERR_ARG;
+    }
+    CgsGeom g;
+    memset(&g, 0, sizeof(g));
+    CgsRasterForms f = {nullptr, 0, 0, 0, cov3D};
+    return cgs_launch_preprocess_form(cfg, N, f, means3D, nullptr, nullptr, nullptr, nullptr, g, radii, true, (hipStream_t)stream);
+}
+
 int cgs_launch_filter_voxel(const cgs_raster_cfg *cfg, int64_t N, const float *means3D, const float *scaling, int64_t ld,
                             int scales_are_log, const float *rot1, uint8_t *visible, hipStream_t stream);
 
@@ -176,10 +193,68 @@ uint64_t cgs_new_ticket(int kind) {
 }
 static int raster_count_tail(int64_t P, CgsGeom &g, RasterCountSlot &sl, hipStream_t stream, bool full_keys = false);
 
+// The argument rules of upstream GaussianRasterizer.forward, checked before anything is enqueued: exactly one of colors / shs,
+// exactly one of (scales + rotations) / cov3D (both only when P > 0: an empty call may pass NULL everywhere), SH of degree
+// 0..3 with (D+1)^2 <= M <= 16 coefficients and a camera position.
+static int check_forms(const char *fn, const cgs_raster_cfg *cfg, int64_t P, const float *colors, const float *shs, int32_t sh_degree,
+                       int32_t sh_coeffs, const float *scales, const float *rotations, const float *cov3D, CgsRasterForms &f) {
+    if (P > 0 && (colors != nullptr) == (shs != nullptr)) {
+        cgs_set_error("%s: please provide exactly one of either SHs or precomputed colors", fn);
+        return CGS_ERR_ARG;
+    }
+    if (P > 0 && ((scales != nullptr || rotations != nullptr) == (cov3D != nullptr) || (!cov3D && (!scales || !rotations)))) {
+        cgs_set_error("%s: please provide exactly one of either scale/rotation pair or precomputed 3D covariance", fn);
+        return CGS_ERR_ARG;
+    }
+    if (shs) {
+        if (sh_degree < 0 || sh_degree > 3) { cgs_set_error("%s: sh_degree %d outside 0..3", fn, sh_degree); return CGS_ERR_ARG; }
+        if (sh_coeffs > 16 || sh_coeffs < (sh_degree + 1) * (sh_degree + 1)) {
+            cgs_set_error("%s: %d SH coefficients per Gaussian: degree %d needs %d..16", fn, sh_coeffs, sh_degree,
+                          (sh_degree + 1) * (sh_degree + 1));
+            return CGS_ERR_ARG;
+        }
+        if (!cfg->campos) { cgs_set_error("%s: SH colours need cfg->campos", fn); return CGS_ERR_ARG; }
+    }
+    f.shs = shs;
+    f.sh_degree = sh_degree;
+    f.sh_coeffs = sh_coeffs;
+    f.sh_vec = shs && sh_coeffs % 4 == 0 && ((uintptr_t)shs & 15u) == 0;
+    f.cov3D = cov3D;
+    return CGS_OK;
+}
+
+static int raster_preprocess_launch_impl(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *colors,
+                                         const float *opacities, const float *scales, const float *rotations,
+                                         const CgsRasterForms *forms, void *geom_ws, size_t geom_bytes, int32_t *radii,
+                                         void *stream_, uint64_t *ticket);
+
 extern "C" int cgs_raster_preprocess_launch(const cgs_raster_cfg *cfg, int64_t P, const float *means3D,
                                             const float *colors, const float *opacities, const float *scales,
                                             const float *rotations, void *geom_ws, size_t geom_bytes, int32_t *radii,
                                             void *stream_, uint64_t *ticket) {
+    return raster_preprocess_launch_impl(cfg, P, means3D, colors, opacities, scales, rotations, nullptr, geom_ws, geom_bytes,
+                                         radii, stream_, ticket);
+}
+
+extern "C" int cgs_raster_preprocess_launch_ex(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *colors,
+                                               const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                               const float *scales, const float *rotations, const float *cov3D, void *geom_ws,
+                                               size_t geom_bytes, int32_t *radii, void *stream_, uint64_t *ticket) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (ticket) *ticket = 0;
+    CgsRasterForms f;
+    if ((rc = check_forms("cgs_raster_preprocess_launch_ex", cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
+        return rc;
+    // the colours_precomp + scales/rotations form is cgs_raster_preprocess_launch itself (same kernel)
+    return raster_preprocess_launch_impl(cfg, P, means3D, colors, opacities, scales, rotations, (shs || cov3D) ? &f : nullptr,
+                                         geom_ws, geom_bytes, radii, stream_, ticket);
+}
+
+static int raster_preprocess_launch_impl(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *colors,
+                                         const float *opacities, const float *scales, const float *rotations,
+                                         const CgsRasterForms *forms, void *geom_ws, size_t geom_bytes, int32_t *radii,
+                                         void *stream_, uint64_t *ticket) {
     hipStream_t stream = (hipStream_t)stream_;
     RasterCountSlot &sl = g_raster_slot;
     int rc = check_cfg(cfg);
@@ -196,7 +271,8 @@ extern "C" int cgs_raster_preprocess_launch(const cgs_raster_cfg *cfg, int64_t P
     sl.ranged = sl.spec_between = sl.resorted = false;
     *ticket = sl.ticket = cgs_new_ticket(1);
     if (P == 0) return CGS_OK;
-    if (!means3D || !colors || !opacities || !scales || !rotations || !radii || !geom_ws) {
+    if (!means3D || !(colors || (forms && forms->shs)) || !opacities || !((scales && rotations) || (forms && forms->cov3D)) ||
+        !radii || !geom_ws) {
         cgs_set_error("cgs_raster_preprocess: NULL input");
         return CGS_ERR_ARG;
     }
@@ -205,8 +281,12 @@ extern "C" int cgs_raster_preprocess_launch(const cgs_raster_cfg *cfg, int64_t P
         cgs_set_error("geometry workspace too small: %zu < %zu", geom_bytes, cgs_raster_geom_bytes(P));
         return CGS_ERR_WORKSPACE;
     }
-    if ((rc = cgs_launch_preprocess(cfg, P, means3D, colors, opacities, scales, rotations, g, radii, false,
-                                    stream)))
+    if (forms) {
+        if ((rc = cgs_launch_preprocess_form(cfg, P, *forms, means3D, colors, opacities, scales, rotations, g, radii, false,
+                                             stream)))
+            return rc;
+    } else if ((rc = cgs_launch_preprocess(cfg, P, means3D, colors, opacities, scales, rotations, g, radii, false,
+                                           stream)))
         return rc;
     sl.P = P; sl.geom_ws = geom_ws; sl.geom_bytes = geom_bytes; sl.stream = stream;
     return raster_count_tail(P, g, sl, stream);
@@ -442,6 +522,44 @@ extern "C" int cgs_raster_render_spec(const cgs_raster_cfg *cfg, int64_t P, int6
 }
 
 // ---- backward -----------------------------------------------------------------------------
+// Everything of the backward before the per-Gaussian kernel: checks, carving, the blend backward into the scratch's
+// dL/d(pixel mean) / dL/d(conic) (and the caller's dL_dcolors / dL_dopacities).
+static int raster_backward_blend(const char *fn, const cgs_raster_cfg *cfg, int64_t P, int64_t R, const int32_t *radii,
+                                 void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws, size_t img_bytes,
+                                 const float *dL_dout, float *dL_dcolors, float *dL_dopacities, void *scratch,
+                                 size_t scratch_bytes, CgsGeom &g, float *&d_mean_px, float *&d_conic, hipStream_t stream) {
+    int rc;
+    if (!dL_dout || !dL_dcolors || !dL_dopacities || !scratch || !radii) {
+        cgs_set_error("%s: NULL input", fn);
+        return CGS_ERR_ARG;
+    }
+    if (scratch_bytes < cgs_raster_bwd_scratch_bytes(P)) {
+        cgs_set_error("backward scratch too small");
+        return CGS_ERR_WORKSPACE;
+    }
+    CgsBin b;
+    CgsImg im;
+    memset(&b, 0, sizeof(b));
+    if (!geom_ws || !img_ws || !cgs_geom_carve(&g, geom_ws, geom_bytes, P) ||
+        !cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
+        cgs_set_error("workspace too small");
+        return CGS_ERR_WORKSPACE;
+    }
+    d_mean_px = (float *)scratch;
+    d_conic = (float *)((char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
+    CGS_CHECK_HIP(hipMemsetAsync(scratch, 0, cgs_raster_bwd_scratch_bytes(P), stream));
+    if (R > 0) {
+        if (!bin_ws || !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
+            cgs_set_error("binning workspace missing or too small");
+            return CGS_ERR_WORKSPACE;
+        }
+        if ((rc = cgs_launch_blend_bwd(cfg, g, b, im, dL_dout, d_mean_px, d_conic, dL_dopacities, dL_dcolors,
+                                       stream)))
+            return rc;
+    }
+    return CGS_OK;
+}
+
 extern "C" int cgs_raster_backward(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D,
                                    const float *colors, const float *opacities, const float *scales,
                                    const float *rotations, const int32_t *radii, void *geom_ws,
@@ -456,38 +574,51 @@ extern "C" int cgs_raster_backward(const cgs_raster_cfg *cfg, int64_t P, int64_t
     int rc = check_cfg(cfg);
     if (rc) return rc;
     if (P == 0) return CGS_OK;
-    if (!dL_dout || !dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacities || !dL_dscales ||
-        !dL_drotations || !scratch || !radii) {
+    if (!dL_dmeans3D || !dL_dmeans2D || !dL_dscales || !dL_drotations) {
         cgs_set_error("cgs_raster_backward: NULL input");
         return CGS_ERR_ARG;
     }
-    if (scratch_bytes < cgs_raster_bwd_scratch_bytes(P)) {
-        cgs_set_error("backward scratch too small");
-        return CGS_ERR_WORKSPACE;
-    }
     CgsGeom g;
-    CgsBin b;
-    CgsImg im;
-    memset(&b, 0, sizeof(b));
-    if (!geom_ws || !img_ws || !cgs_geom_carve(&g, geom_ws, geom_bytes, P) ||
-        !cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
-        cgs_set_error("workspace too small");
-        return CGS_ERR_WORKSPACE;
-    }
-    float *d_mean_px = (float *)scratch;
-    float *d_conic = (float *)((char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
-    CGS_CHECK_HIP(hipMemsetAsync(scratch, 0, cgs_raster_bwd_scratch_bytes(P), stream));
-    if (R > 0) {
-        if (!bin_ws || !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
-            cgs_set_error("binning workspace missing or too small");
-            return CGS_ERR_WORKSPACE;
-        }
-        if ((rc = cgs_launch_blend_bwd(cfg, g, b, im, dL_dout, d_mean_px, d_conic, dL_dopacities, dL_dcolors,
-                                       stream)))
-            return rc;
-    }
+    float *d_mean_px, *d_conic;
+    if ((rc = raster_backward_blend("cgs_raster_backward", cfg, P, R, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws,
+                                    img_bytes, dL_dout, dL_dcolors, dL_dopacities, scratch, scratch_bytes, g, d_mean_px, d_conic,
+                                    stream)))
+        return rc;
     return cgs_launch_preprocess_bwd(cfg, P, CGS_BLEND_BWD_RAW ? (const float4 *)g.rec : nullptr, means3D, scales, rotations, radii,
                                      d_mean_px, d_conic, dL_dmeans3D, dL_dmeans2D, dL_dscales, dL_drotations, stream);
+}
+
+extern "C" int cgs_raster_backward_ex(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                      const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                      const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                      void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                      size_t img_bytes, const float *dL_dout, float *dL_dmeans3D, float *dL_dmeans2D,
+                                      float *dL_dcolors, float *dL_dopacities, float *dL_dshs, float *dL_dscales,
+                                      float *dL_drotations, float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    CgsRasterForms f;
+    if ((rc = check_forms("cgs_raster_backward_ex", cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
+        return rc;
+    if (!shs && !cov3D)
+        return cgs_raster_backward(cfg, P, R, means3D, colors, opacities, scales, rotations, radii, geom_ws, geom_bytes, bin_ws,
+                                   bin_bytes, img_ws, img_bytes, dL_dout, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities,
+                                   dL_dscales, dL_drotations, scratch, scratch_bytes, stream_);
+    if (P == 0) return CGS_OK;
+    if (!means3D || !dL_dmeans3D || !dL_dmeans2D || (shs && !dL_dshs) || (cov3D && !dL_dcov3D) ||
+        (!cov3D && (!dL_dscales || !dL_drotations))) {
+        cgs_set_error("cgs_raster_backward_ex: NULL input");
+        return CGS_ERR_ARG;
+    }
+    CgsGeom g;
+    float *d_mean_px, *d_conic;
+    if ((rc = raster_backward_blend("cgs_raster_backward_ex", cfg, P, R, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws,
+                                    img_bytes, dL_dout, dL_dcolors, dL_dopacities, scratch, scratch_bytes, g, d_mean_px, d_conic,
+                                    stream)))
+        return rc;
+    return cgs_launch_preprocess_bwd_form(cfg, P, f, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dcolors, dL_dmeans3D,
+                                          dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream);
 }
 
 extern "C" int cgs_raster_stats(const cgs_raster_cfg *cfg, void *img_ws, size_t img_bytes, int64_t *stats_out,

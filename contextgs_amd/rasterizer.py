@@ -8,9 +8,16 @@ and `.visible_filter(means3D, scales, rotations, cov3D_precomp) -> radii`.
 All arithmetic runs in libcgs_hip.so (hand-written gfx950 kernels) through the
 C-ABI of include/cgs.h; there is no CPU implementation here.
 
-Only the argument combination the reference uses is implemented
-(shs=None, colors_precomp given, scales+rotations given, cov3D_precomp=None;
-gaussian_renderer/__init__.py:197-205, 280-285); the others raise.
+All four argument forms of upstream are implemented: colours as `colors_precomp`
+[P,3] or as spherical harmonics `shs` [P,M,3] (M <= 16, degree
+`raster_settings.sh_degree` evaluated in the preprocess kernel from the direction
+means3D - campos, clamped at 0), covariances from `scales` + `rotations` or as
+`cov3D_precomp` [P,6] (upper triangle xx, xy, xz, yy, yz, zz, used as given:
+scale_modifier does not apply).  Exactly one of each pair; anything else raises
+ValueError before a device is touched.  The form the reference renders with
+(colors_precomp + scales/rotations, gaussian_renderer/__init__.py:197-205) goes
+through `_RasterizeGaussians`; the others through `_RasterizeGaussiansForms`
+(csrc/raster_forms.hip, same binning and blend).
 """
 from __future__ import annotations
 
@@ -190,6 +197,96 @@ class _RasterizeGaussians(torch.autograd.Function):
         return d_means3D, d_means2D, d_colors, d_opac, d_scales, d_rots, None
 
 
+def check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, sh_degree=None) -> None:
+    """Upstream's argument rules (diff_gaussian_rasterization.GaussianRasterizer.forward) plus the SH shape rules, on shapes
+    only: no device is touched."""
+    if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+        raise ValueError("Please provide excatly one of either SHs or precomputed colors!")
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise ValueError("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+    if shs is not None:
+        D = int(sh_degree)
+        if shs.dim() != 3 or shs.shape[2] != 3:
+            raise ValueError(f"shs must be [P, M, 3], got {tuple(shs.shape)}")
+        if not 0 <= D <= 3:
+            raise ValueError(f"sh_degree {D} outside 0..3")
+        if not (D + 1) ** 2 <= shs.shape[1] <= 16:
+            raise ValueError(f"sh_degree {D} needs {(D + 1) ** 2}..16 SH coefficients per Gaussian, got {shs.shape[1]}")
+    if cov3D_precomp is not None and (cov3D_precomp.dim() != 2 or cov3D_precomp.shape[1] != 6):
+        raise ValueError(f"cov3D_precomp must be [P, 6], got {tuple(cov3D_precomp.shape)}")
+
+
+class _RasterizeGaussiansForms(torch.autograd.Function):
+    """The forms _RasterizeGaussians does not take: shs and / or cov3D_precomp (absent inputs are None)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings):
+        L = _lib.lib()
+        _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D)
+        c = {k: (_f32c(v) if v is not None else None)
+             for k, v in dict(means3D=means3D, shs=shs, colors=colors, opac=opacities, scales=scales, rots=rotations,
+                              cov=cov3D).items()}
+        P = c["means3D"].shape[0]
+        dev = c["means3D"].device
+        cfg = _Cfg(raster_settings)
+        if shs is not None:
+            _lib.require_device(cfg.campos)
+        D = int(raster_settings.sh_degree) if shs is not None else 0
+        M = int(shs.shape[1]) if shs is not None else 0
+        H, W = cfg.c.image_height, cfg.c.image_width
+        stream = _lib.current_stream()
+        ctx.set_materialize_grads(False)
+
+        radii = torch.empty(P, dtype=torch.int32, device=dev)
+        geom = _workspace(L.cgs_raster_geom_bytes(P), dev)
+        img = _workspace(L.cgs_raster_img_bytes(H, W), dev)
+        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+        ticket = C.c_uint64(0)
+        _lib.check(L.cgs_raster_preprocess_launch_ex(
+            cfg.ref, P, _lib.ptr(c["means3D"]), _lib.ptr(c["colors"]), _lib.ptr(c["shs"]), D, M, _lib.ptr(c["opac"]),
+            _lib.ptr(c["scales"]), _lib.ptr(c["rots"]), _lib.ptr(c["cov"]), _lib.ptr(geom), geom.numel(), _lib.ptr(radii),
+            stream, C.byref(ticket)), "cgs_raster_preprocess_launch_ex")
+        binws, bin_R, _num_rendered = bin_and_blend(cfg, P, geom, img, color, stream, ticket)
+        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M = cfg, bin_R, D, M
+        ctx.present = [v is not None for v in (shs, colors, scales, rotations, cov3D)]
+        ctx.save_for_backward(c["means3D"], c["shs"], c["colors"], c["opac"], c["scales"], c["rots"], c["cov"], radii, geom,
+                              binws, img)
+        ctx.mark_non_differentiable(radii)
+        return color, radii
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii):
+        L = _lib.lib()
+        means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img = ctx.saved_tensors
+        cfg = ctx.cfg
+        P = means3D.shape[0]
+        dev = means3D.device
+        if grad_color is None:
+            return (None,) * 9
+        g = _f32c(grad_color)
+        # the blend backward accumulates dL/dcolor (read by the SH backward) and dL/dopacity: one zero fill; the rest is
+        # written for every Gaussian by the preprocess backward
+        acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
+        d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
+        d_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        d_means2D = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        d_shs = torch.empty_like(shs) if shs is not None else None
+        d_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if cov is not None else None
+        d_scales = torch.empty(P, 3, dtype=torch.float32, device=dev) if cov is None else None
+        d_rots = torch.empty(P, 4, dtype=torch.float32, device=dev) if cov is None else None
+        scratch = _workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
+        _lib.check(L.cgs_raster_backward_ex(
+            cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M, _lib.ptr(opac),
+            _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
+            binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(), _lib.ptr(g), _lib.ptr(d_means3D),
+            _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_shs), _lib.ptr(d_scales), _lib.ptr(d_rots),
+            _lib.ptr(d_cov), _lib.ptr(scratch), scratch.numel(), _lib.current_stream()), "cgs_raster_backward_ex")
+        has_shs, has_colors, _, _, _ = ctx.present
+        return (d_means3D, d_means2D, d_shs if has_shs else None, d_colors if has_colors else None, d_opac, d_scales, d_rots,
+                d_cov, None)
+
+
 def rasterize_gaussians(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings):
     return _RasterizeGaussians.apply(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings)
 
@@ -218,10 +315,20 @@ class GaussianRasterizer(nn.Module):
             return z > 0.2
 
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):
-        if cov3D_precomp is not None or scales is None or rotations is None:
-            raise NotImplementedError("visible_filter: only the scales+rotations form is on the hot path "
-                                      "(gaussian_renderer/__init__.py:280-285)")
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise ValueError("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         L = _lib.lib()
+        if cov3D_precomp is not None:
+            _lib.require_device(means3D, cov3D_precomp)
+            with torch.no_grad():
+                m, cv = _f32c(means3D), _f32c(cov3D_precomp)
+                N = m.shape[0]
+                cfg = _Cfg(self.raster_settings)
+                radii = torch.zeros(N, dtype=torch.int32, device=m.device)
+                _lib.check(L.cgs_filter_cov(cfg.ref, N, _lib.ptr(m), _lib.ptr(cv), _lib.ptr(radii), _lib.current_stream()),
+                           "cgs_filter_cov")
+            return radii
         _lib.require_device(means3D, scales, rotations)
         with torch.no_grad():
             m, s, r = _f32c(means3D), _f32c(scales), _f32c(rotations)
@@ -234,11 +341,9 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
-        if shs is not None or colors_precomp is None:
-            raise NotImplementedError("ContextGS renders with precomputed colours (shs=None, "
-                                      "gaussian_renderer/__init__.py:200-201)")
-        if cov3D_precomp is not None or scales is None or rotations is None:
-            raise NotImplementedError("ContextGS passes scales+rotations (cov3D_precomp=None, "
-                                      "gaussian_renderer/__init__.py:203-205)")
+        check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
+        if shs is not None or cov3D_precomp is not None:
+            return _RasterizeGaussiansForms.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                  cov3D_precomp, self.raster_settings)
         return rasterize_gaussians(means3D, means2D, colors_precomp, opacities, scales, rotations,
                                    self.raster_settings)

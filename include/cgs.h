@@ -77,8 +77,9 @@ const char *cgs_last_error(void);
 /* Mirrors GaussianRasterizationSettings (the 12 keyword fields built at
  * gaussian_renderer/__init__.py:179-192).  Matrices are the tensors the
  * reference passes: ROW-vector convention, p_view = [x y z 1] @ viewmatrix,
- * row-major 4x4 fp32 on the device.  sh_degree / campos are accepted for
- * API parity; colours are always precomputed on this path (shs=None). */
+ * row-major 4x4 fp32 on the device.  campos is read by the SH colour form
+ * (cgs_raster_preprocess_launch_ex / cgs_raster_backward_ex with shs) and
+ * unused with precomputed colours; the SH degree travels as an argument. */
 typedef struct cgs_raster_cfg {
     int32_t image_height;
     int32_t image_width;
@@ -89,7 +90,7 @@ typedef struct cgs_raster_cfg {
     int32_t debug;              /* !=0: synchronise + check after each kernel */
     const float *viewmatrix;    /* device, 16 floats */
     const float *projmatrix;    /* device, 16 floats */
-    const float *campos;        /* device, 3 floats (unused: colours precomputed) */
+    const float *campos;        /* device, 3 floats (SH colours only; unused with precomputed colours) */
     const float *bg;            /* device, 3 floats */
 } cgs_raster_cfg;
 
@@ -99,6 +100,10 @@ typedef struct cgs_raster_cfg {
 int cgs_filter(const cgs_raster_cfg *cfg, int64_t N, const float *means3D,
                const float *scales, const float *rotations, int32_t *radii,
                void *stream);
+/* visible_filter(means3D, cov3D_precomp=cov3D): cov3D [N,6] = the upper triangle (xx, xy, xz, yy, yz, zz), used as given
+ * (no scale_modifier); radii as cgs_filter. */
+int cgs_filter_cov(const cgs_raster_cfg *cfg, int64_t N, const float *means3D,
+                   const float *cov3D, int32_t *radii, void *stream);
 /* prefilter_voxel (gaussian_renderer/__init__.py:232-287) in one launch: scaling [N, ld] = the model's RAW scaling rows
  * (columns 0..2 are read; exp is applied when scales_are_log != 0, i.e. the model is not a decoded one), rot1 [4] the
  * normalised rotation row every anchor shares (:283 repeats row 0), visible [N] receives `radii_pure > 0` as bool bytes. */
@@ -181,6 +186,42 @@ int cgs_raster_backward(const cgs_raster_cfg *cfg, int64_t P,
                         float *dL_dcolors, float *dL_dopacities,
                         float *dL_dscales, float *dL_drotations,
                         void *scratch, size_t scratch_bytes, void *stream);
+
+/* The four argument forms of upstream GaussianRasterizer(...)(means3D, means2D, opacities, shs, colors_precomp, scales,
+ * rotations, cov3D_precomp): exactly one of colors [P,3] / shs [P, sh_coeffs, 3], exactly one of scales [P,3] + rotations
+ * [P,4] / cov3D [P,6] (the others NULL).  SH colours: degree sh_degree in 0..3, (sh_degree+1)^2 <= sh_coeffs <= 16,
+ * cfg->campos set; rgb = max(SH(normalize(means3D - campos)) + 0.5, 0) per channel.  cov3D is the upper triangle
+ * (xx, xy, xz, yy, yz, zz), used as given (scale_modifier applies to scales only).  Argument errors return CGS_ERR_ARG
+ * (message in cgs_last_error) before anything is enqueued; the form checks apply when P > 0.
+ * _ex with colors + scales/rotations is cgs_raster_preprocess_launch / cgs_raster_backward (same kernels).  Ticket, _wait2,
+ * render_spec and render follow as for cgs_raster_preprocess_launch. */
+int cgs_raster_preprocess_launch_ex(const cgs_raster_cfg *cfg, int64_t P,
+                                    const float *means3D, const float *colors,
+                                    const float *shs, int32_t sh_degree,
+                                    int32_t sh_coeffs, const float *opacities,
+                                    const float *scales, const float *rotations,
+                                    const float *cov3D, void *geom_ws,
+                                    size_t geom_bytes, int32_t *radii,
+                                    void *stream, uint64_t *ticket);
+/* Backward of the above, the same forms as the forward call.  dL_dcolors [P,3] and dL_dopacities must be zero-initialised
+ * in every form: the blend backward accumulates into dL_dcolors, which the SH form then reads.  dL_dshs [P, sh_coeffs, 3]
+ * (shs given; zeros above (sh_degree+1)^2 and for culled Gaussians), dL_dcov3D [P,6] (cov3D given; an off-diagonal entry
+ * carries dL/dSigma_ij + dL/dSigma_ji), dL_dscales / dL_drotations (scales/rotations given) are written for every Gaussian
+ * and may arrive uninitialised; the ones of absent inputs may be NULL.  No gradient reaches campos. */
+int cgs_raster_backward_ex(const cgs_raster_cfg *cfg, int64_t P,
+                           int64_t num_rendered, const float *means3D,
+                           const float *colors, const float *shs,
+                           int32_t sh_degree, int32_t sh_coeffs,
+                           const float *opacities, const float *scales,
+                           const float *rotations, const float *cov3D,
+                           const int32_t *radii, void *geom_ws, size_t geom_bytes,
+                           void *bin_ws, size_t bin_bytes, void *img_ws,
+                           size_t img_bytes, const float *dL_dout,
+                           float *dL_dmeans3D, float *dL_dmeans2D,
+                           float *dL_dcolors, float *dL_dopacities,
+                           float *dL_dshs, float *dL_dscales,
+                           float *dL_drotations, float *dL_dcov3D,
+                           void *scratch, size_t scratch_bytes, void *stream);
 
 /* ---- the anchor expansion fused with the rasterizer's preprocess stage (csrc/expand_raster.hip) ----
  * Training path of render(): gaussian_renderer/__init__.py:130-145 (generate_neural_gaussians' tail) feeding :179-205.
