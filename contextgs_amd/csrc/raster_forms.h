@@ -210,7 +210,8 @@ __device__ __forceinline__ bool cgs_project_cov(const float3 p, const CgsCov3 &c
     o.con_a = c * inv; o.con_b = -b * inv; o.con_c = a * inv;
     o.cov_a = a; o.cov_b = b; o.cov_c = c;
     const float mid = 0.5f * (a + c);
-    const float disc = sqrtf(fmaxf(0.1f, mid * mid - det));
+    const float hd = 0.5f * (a - c);                       // mid^2 - det without cancellation (raster_math.h)
+    const float disc = sqrtf(fmaxf(0.1f, hd * hd + b * b));
     o.radius = ceilf(3.f * sqrtf(fmaxf(mid + disc, mid - disc)));
     o.px = ((ndcx + 1.f) * (float)W - 1.f) * 0.5f;
     o.py = ((ndcy + 1.f) * (float)H - 1.f) * 0.5f;

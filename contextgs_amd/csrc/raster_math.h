@@ -114,7 +114,10 @@ __device__ __forceinline__ bool cgs_project(const float3 p, const float3 s, cons
     o.con_a = c * inv; o.con_b = -b * inv; o.con_c = a * inv;
     o.cov_a = a; o.cov_b = b; o.cov_c = c;
     const float mid = 0.5f * (a + c);
-    const float disc = sqrtf(fmaxf(0.1f, mid * mid - det));
+    // mid^2 - det = ((a - c) / 2)^2 + b^2: the sum of squares, not the difference of two near-equal squares (that one lost
+    // ~1e-2 absolutely at mid ~ 400 and moved ceil() below on the last ulp - 4K frame: radii off the oracle's)
+    const float hd = 0.5f * (a - c);
+    const float disc = sqrtf(fmaxf(0.1f, hd * hd + b * b));
     o.radius = ceilf(3.f * sqrtf(fmaxf(mid + disc, mid - disc)));
     o.px = ((ndcx + 1.f) * (float)W - 1.f) * 0.5f;
     o.py = ((ndcy + 1.f) * (float)H - 1.f) * 0.5f;

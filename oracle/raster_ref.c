@@ -132,7 +132,8 @@ static void preprocess_one(const ref_cfg *c, const real *p, const real *s, const
     g->cov[0] = ca; g->cov[1] = cb; g->cov[2] = cc;
     g->conic[0] = cc * inv; g->conic[1] = -cb * inv; g->conic[2] = ca * inv;
     real mid = (real)0.5 * (ca + cc);
-    real disc = sqrt(fmax((real)0.1, mid * mid - det));
+    real hd = (real)0.5 * (ca - cc);   /* mid^2 - det = ((a - c) / 2)^2 + b^2, free of cancellation */
+    real disc = sqrt(fmax((real)0.1, hd * hd + cb * cb));
     real lam = fmax(mid + disc, mid - disc);
     real radius = ceil((real)3 * sqrt(lam));
     g->px = ((ndc[0] + 1) * c->W - 1) * (real)0.5;
