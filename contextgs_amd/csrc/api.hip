@@ -621,6 +621,115 @@ extern "C" int cgs_raster_backward_ex(const cgs_raster_cfg *cfg, int64_t P, int6
                                           dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream);
 }
 
+// ---- depth / inverse-depth / alpha maps (csrc/raster_aux.hip) --------------------------------------------------------
+int cgs_launch_aux_fwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, float *out_depth, float *out_invdepth,
+                       float *out_alpha, hipStream_t stream);
+int cgs_launch_aux_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const float *dL_ddepth,
+                       const float *dL_dinvdepth, const float *dL_dalpha, float *dL_dmean2D_px, float *dL_dconic,
+                       float *dL_dopacity, float *dL_dz, hipStream_t stream);
+int cgs_launch_aux_dz_chain(const cgs_raster_cfg *cfg, int64_t P, const int32_t *radii, const float *dL_dz, float *dL_dmeans3D,
+                            hipStream_t stream);
+
+extern "C" size_t cgs_raster_bwd_aux_scratch_bytes(int64_t P) {
+    const size_t n = (size_t)(P > 0 ? P : 1);
+    return cgs_raster_bwd_scratch_bytes(P) + cgs_align_up(n * sizeof(float), 256);
+}
+
+// Enqueued after the view's cgs_raster_render / _render_spec that the caller kept (R = the count its binning workspace was
+// carved with): reads the lists, n_contrib, tile_last and final_T that render left.
+extern "C" int cgs_raster_render_aux(const cgs_raster_cfg *cfg, int64_t P, int64_t R, void *geom_ws, size_t geom_bytes,
+                                     void *bin_ws, size_t bin_bytes, void *img_ws, size_t img_bytes, float *out_depth,
+                                     float *out_invdepth, float *out_alpha, void *stream_) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (P < 0 || R < 0) { cgs_set_error("cgs_raster_render_aux: P < 0 or R < 0"); return CGS_ERR_ARG; }
+    if (!out_depth || !out_invdepth || !out_alpha || !img_ws || (R > 0 && (!geom_ws || !bin_ws))) {
+        cgs_set_error("cgs_raster_render_aux: NULL input");
+        return CGS_ERR_ARG;
+    }
+    CgsGeom g;
+    CgsBin b;
+    CgsImg im;
+    memset(&g, 0, sizeof(g));
+    memset(&b, 0, sizeof(b));
+    if (!cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
+        cgs_set_error("image workspace too small");
+        return CGS_ERR_WORKSPACE;
+    }
+    if (P > 0 && geom_ws && !cgs_geom_carve(&g, geom_ws, geom_bytes, P)) {
+        cgs_set_error("geometry workspace too small");
+        return CGS_ERR_WORKSPACE;
+    }
+    if (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
+        cgs_set_error("binning workspace too small: %zu < %zu", bin_bytes, cgs_raster_bin_bytes(P, R));
+        return CGS_ERR_WORKSPACE;
+    }
+    return cgs_launch_aux_fwd(cfg, g, b, im, out_depth, out_invdepth, out_alpha, (hipStream_t)stream_);
+}
+
+// Backward of the colour image and the three maps together, every argument form of cgs_raster_backward_ex.  Each of the four
+// upstream gradients may be NULL; without dL_dout no colour blend backward runs (dL_dcolors keeps its zeros).
+extern "C" int cgs_raster_backward_aux(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_) {
+    (void)opacities;
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (P < 0 || R < 0) { cgs_set_error("cgs_raster_backward_aux: P < 0 or R < 0"); return CGS_ERR_ARG; }
+    if (CGS_BLEND_BWD_RAW) {      // (experiment builds: the colour blend backward leaves raw sums the aux pass does not add to)
+        cgs_set_error("cgs_raster_backward_aux: not available with CGS_BLEND_BWD_RAW");
+        return CGS_ERR_ARG;
+    }
+    CgsRasterForms f;
+    if ((rc = check_forms("cgs_raster_backward_aux", cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
+        return rc;
+    if (P == 0) return CGS_OK;
+    if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacities || !scratch || (shs && !dL_dshs) ||
+        (cov3D && !dL_dcov3D) || (!cov3D && (!dL_dscales || !dL_drotations)) || !geom_ws || !img_ws || (R > 0 && !bin_ws)) {
+        cgs_set_error("cgs_raster_backward_aux: NULL input");
+        return CGS_ERR_ARG;
+    }
+    if (scratch_bytes < cgs_raster_bwd_aux_scratch_bytes(P)) {
+        cgs_set_error("cgs_raster_backward_aux: scratch too small: %zu < %zu", scratch_bytes, cgs_raster_bwd_aux_scratch_bytes(P));
+        return CGS_ERR_WORKSPACE;
+    }
+    CgsGeom g;
+    CgsBin b;
+    CgsImg im;
+    memset(&b, 0, sizeof(b));
+    if (!cgs_geom_carve(&g, geom_ws, geom_bytes, P) || !cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width) ||
+        (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R))) {
+        cgs_set_error("cgs_raster_backward_aux: workspace too small");
+        return CGS_ERR_WORKSPACE;
+    }
+    const bool aux = dL_ddepth || dL_dinvdepth || dL_dalpha;
+    float *d_mean_px = (float *)scratch;
+    float *d_conic = (float *)((char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
+    float *d_z = (float *)((char *)scratch + cgs_raster_bwd_scratch_bytes(P));
+    CGS_CHECK_HIP(hipMemsetAsync(scratch, 0, cgs_raster_bwd_aux_scratch_bytes(P), stream));
+    if (R > 0) {
+        if (dL_dout && (rc = cgs_launch_blend_bwd(cfg, g, b, im, dL_dout, d_mean_px, d_conic, dL_dopacities, dL_dcolors, stream)))
+            return rc;
+        if (aux && (rc = cgs_launch_aux_bwd(cfg, g, b, im, dL_ddepth, dL_dinvdepth, dL_dalpha, d_mean_px, d_conic, dL_dopacities,
+                                            d_z, stream)))
+            return rc;
+    }
+    if (!shs && !cov3D)
+        rc = cgs_launch_preprocess_bwd(cfg, P, nullptr, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dmeans3D,
+                                       dL_dmeans2D, dL_dscales, dL_drotations, stream);
+    else
+        rc = cgs_launch_preprocess_bwd_form(cfg, P, f, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dcolors,
+                                            dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream);
+    if (rc) return rc;
+    return aux ? cgs_launch_aux_dz_chain(cfg, P, radii, d_z, dL_dmeans3D, stream) : CGS_OK;
+}
+
 extern "C" int cgs_raster_stats(const cgs_raster_cfg *cfg, void *img_ws, size_t img_bytes, int64_t *stats_out,
                                 void *stream) {
     int rc = check_cfg(cfg);

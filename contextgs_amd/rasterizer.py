@@ -18,6 +18,20 @@ ValueError before a device is touched.  The form the reference renders with
 (colors_precomp + scales/rotations, gaussian_renderer/__init__.py:197-205) goes
 through `_RasterizeGaussians`; the others through `_RasterizeGaussiansForms`
 (csrc/raster_forms.hip, same binning and blend).
+
+`forward(..., return_aux=True)` returns `(color, radii, {"depth", "invdepth", "alpha"})`, float32 [1,H,W] each, in all
+four forms (`_RasterizeGaussiansAux`, csrc/raster_aux.hip); without it the call runs exactly the code above.  For pixel p the
+contributors i are exactly those of the colour blend (same order, same alpha = min(0.99, o exp(power)), same skip below
+1/255, same stop at T (1 - alpha) < 1e-4); with w_i = alpha_i T_i and z_i the view-space depth of Gaussian i's centre:
+
+  depth[p]    = sum_i w_i z_i
+  invdepth[p] = sum_i w_i / z_i      (upstream's `invdepths`)
+  alpha[p]    = 1 - T_final[p]       (= sum_i w_i)
+
+The background contributes to none of them; expected depth is depth / alpha.  Each map is the colour blend of a
+per-Gaussian scalar (z, 1/z, 1) with a zero background, and gradients flow accordingly to means3D (also directly through z),
+means2D, opacities, scales, rotations and cov3D_precomp, never to shs / colors_precomp.  means2D.grad (the densification
+statistic) includes the maps' share, as upstream's `invdepths` backward does.
 """
 from __future__ import annotations
 
@@ -287,6 +301,101 @@ class _RasterizeGaussiansForms(torch.autograd.Function):
                 d_cov, None)
 
 
+class _RasterizeGaussiansAux(torch.autograd.Function):
+    """Any of the four argument forms (absent inputs are None) with the depth / inverse-depth / alpha maps as three more
+    outputs (csrc/raster_aux.hip).  The forward is the form's preprocess (cgs_raster_preprocess_launch_ex, which is
+    cgs_raster_preprocess_launch for colors_precomp + scales/rotations), the same binning and colour blend, then one walk of
+    the final per-tile lists for the maps.  The backward calls cgs_raster_backward / _ex unchanged when the maps get no
+    gradient, cgs_raster_backward_aux otherwise (no colour blend backward when the image gets none)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings):
+        L = _lib.lib()
+        _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D)
+        c = {k: (_f32c(v) if v is not None else None)
+             for k, v in dict(means3D=means3D, shs=shs, colors=colors, opac=opacities, scales=scales, rots=rotations,
+                              cov=cov3D).items()}
+        P = c["means3D"].shape[0]
+        dev = c["means3D"].device
+        cfg = _Cfg(raster_settings)
+        if shs is not None:
+            _lib.require_device(cfg.campos)
+        D = int(raster_settings.sh_degree) if shs is not None else 0
+        M = int(shs.shape[1]) if shs is not None else 0
+        H, W = cfg.c.image_height, cfg.c.image_width
+        stream = _lib.current_stream()
+        ctx.set_materialize_grads(False)
+
+        radii = torch.empty(P, dtype=torch.int32, device=dev)
+        geom = _workspace(L.cgs_raster_geom_bytes(P), dev)
+        img = _workspace(L.cgs_raster_img_bytes(H, W), dev)
+        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+        depth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
+        invdepth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
+        alpha = torch.empty(1, H, W, dtype=torch.float32, device=dev)
+        ticket = C.c_uint64(0)
+        _lib.check(L.cgs_raster_preprocess_launch_ex(
+            cfg.ref, P, _lib.ptr(c["means3D"]), _lib.ptr(c["colors"]), _lib.ptr(c["shs"]), D, M, _lib.ptr(c["opac"]),
+            _lib.ptr(c["scales"]), _lib.ptr(c["rots"]), _lib.ptr(c["cov"]), _lib.ptr(geom), geom.numel(), _lib.ptr(radii),
+            stream, C.byref(ticket)), "cgs_raster_preprocess_launch_ex")
+        binws, bin_R, _num_rendered = bin_and_blend(cfg, P, geom, img, color, stream, ticket)
+        # behind the render bin_and_blend kept (a voided speculative render has been redone by now)
+        _lib.check(L.cgs_raster_render_aux(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
+                                           binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(),
+                                           _lib.ptr(depth), _lib.ptr(invdepth), _lib.ptr(alpha), stream),
+                   "cgs_raster_render_aux")
+        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M = cfg, bin_R, D, M
+        ctx.present = [v is not None for v in (shs, colors, scales, rotations, cov3D)]
+        ctx.save_for_backward(c["means3D"], c["shs"], c["colors"], c["opac"], c["scales"], c["rots"], c["cov"], radii, geom,
+                              binws, img)
+        ctx.mark_non_differentiable(radii)
+        return color, radii, depth, invdepth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_invdepth, grad_alpha):
+        L = _lib.lib()
+        means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img = ctx.saved_tensors
+        cfg = ctx.cfg
+        P = means3D.shape[0]
+        dev = means3D.device
+        has_shs, has_colors, _, _, _ = ctx.present
+        maps = [None if t is None else _f32c(t) for t in (grad_depth, grad_invdepth, grad_alpha)]
+        if grad_color is None and all(t is None for t in maps):
+            return (None,) * 9
+        g = _f32c(grad_color) if grad_color is not None else None
+        acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
+        d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
+        d_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        d_means2D = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        d_shs = torch.empty_like(shs) if shs is not None else None
+        d_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if cov is not None else None
+        d_scales = torch.empty(P, 3, dtype=torch.float32, device=dev) if cov is None else None
+        d_rots = torch.empty(P, 4, dtype=torch.float32, device=dev) if cov is None else None
+        stream = _lib.current_stream()
+        bin_bytes = binws.numel() if binws is not None else 0
+        if all(t is None for t in maps):
+            # the colour image alone: exactly the existing backward
+            scratch = _workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
+            _lib.check(L.cgs_raster_backward_ex(
+                cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M,
+                _lib.ptr(opac), _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom),
+                geom.numel(), _lib.ptr(binws), bin_bytes, _lib.ptr(img), img.numel(), _lib.ptr(g), _lib.ptr(d_means3D),
+                _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_shs), _lib.ptr(d_scales),
+                _lib.ptr(d_rots), _lib.ptr(d_cov), _lib.ptr(scratch), scratch.numel(), stream), "cgs_raster_backward_ex")
+        else:
+            scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
+            _lib.check(L.cgs_raster_backward_aux(
+                cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M,
+                _lib.ptr(opac), _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom),
+                geom.numel(), _lib.ptr(binws), bin_bytes, _lib.ptr(img), img.numel(), _lib.ptr(g), _lib.ptr(maps[0]),
+                _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors),
+                _lib.ptr(d_opac), _lib.ptr(d_shs), _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov),
+                _lib.ptr(scratch), scratch.numel(), stream), "cgs_raster_backward_aux")
+        colour = g is not None      # the maps send no gradient to the colour inputs
+        return (d_means3D, d_means2D, d_shs if (has_shs and colour) else None, d_colors if (has_colors and colour) else None,
+                d_opac, d_scales, d_rots, d_cov, None)
+
+
 def rasterize_gaussians(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings):
     return _RasterizeGaussians.apply(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings)
 
@@ -340,8 +449,14 @@ class GaussianRasterizer(nn.Module):
         return radii
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, return_aux=False):
+        """(color [3,H,W], radii int32 [P]); with return_aux=True also {"depth", "invdepth", "alpha"}, float32 [1,H,W]
+        each (see the module docstring)."""
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
+        if return_aux:
+            color, radii, depth, invdepth, alpha = _RasterizeGaussiansAux.apply(
+                means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings)
+            return color, radii, {"depth": depth, "invdepth": invdepth, "alpha": alpha}
         if shs is not None or cov3D_precomp is not None:
             return _RasterizeGaussiansForms.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                   cov3D_precomp, self.raster_settings)

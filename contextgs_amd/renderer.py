@@ -574,8 +574,11 @@ def _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False,
-           step=0):                                                                      # :155-229
-    """Render the scene.  Background tensor (bg_color) must be on the GPU."""
+           step=0, *, return_aux=False):                                                # :155-229
+    """Render the scene.  Background tensor (bg_color) must be on the GPU.
+
+    return_aux=True: the dict also holds the rasterizer's "depth", "invdepth" and "alpha" maps ([1,H,W] each, see
+    contextgs_amd/rasterizer.py).  In training mode such a call takes the unfused path (the one CGS_FUSE_VIEW=0 takes)."""
     is_training = pc.get_color_mlp.training
     view = None
     if is_training:
@@ -584,7 +587,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         view = ViewFusion(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier), retain_grad)
         (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, bit_per_anchor_param,
          bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level) = \
-            generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=True, step=step, _view=view)
+            generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=True, step=step,
+                                      _view=None if return_aux else view)
         if view.done is not None:
             rendered_image, radii, screenspace_points = view.done
             return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
@@ -604,16 +608,25 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
             pass
 
     rasterizer = GaussianRasterizer(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier))
-    rendered_image, radii = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
-                                       opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None)
+    if return_aux:
+        rendered_image, radii, aux = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
+                                                opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None,
+                                                return_aux=True)
+    else:
+        rendered_image, radii = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
+                                           opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None)
     if is_training:
-        return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-                "radii": radii, "selection_mask": mask, "neural_opacity": neural_opacity, "scaling": scaling,
-                "bit_per_param": bit_per_param, "bit_per_anchor_param": bit_per_anchor_param,
-                "bit_per_feat_param": bit_per_feat_param, "bit_per_scaling_param": bit_per_scaling_param,
-                "bit_per_offsets_param": bit_per_offsets_param, "bpp_per_level": bpp_per_level}
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii, "time_sub": time_sub}
+        out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+               "radii": radii, "selection_mask": mask, "neural_opacity": neural_opacity, "scaling": scaling,
+               "bit_per_param": bit_per_param, "bit_per_anchor_param": bit_per_anchor_param,
+               "bit_per_feat_param": bit_per_feat_param, "bit_per_scaling_param": bit_per_scaling_param,
+               "bit_per_offsets_param": bit_per_offsets_param, "bpp_per_level": bpp_per_level}
+    else:
+        out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+               "radii": radii, "time_sub": time_sub}
+    if return_aux:
+        out.update(aux)
+    return out
 
 
 def prefilter_voxel(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None):   # :232-287

@@ -223,6 +223,47 @@ int cgs_raster_backward_ex(const cgs_raster_cfg *cfg, int64_t P,
                            float *dL_drotations, float *dL_dcov3D,
                            void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- per-pixel geometry maps: depth, inverse depth, alpha (csrc/raster_aux.hip) ----
+ * For pixel p the contributors i are exactly those of the colour blend: the same front-to-back order, the same
+ * alpha_i = min(0.99, o_i exp(power)), the same skip below 1/255 and the same stop at T (1 - alpha) < 1e-4.  With
+ * w_i = alpha_i T_i and z_i the view-space depth of Gaussian i's centre (the value of the near cull and the depth sort, > 0.2):
+ *   depth[p] = sum_i w_i z_i,   invdepth[p] = sum_i w_i / z_i,   alpha[p] = 1 - T_final[p] (= sum_i w_i).
+ * The background contributes to none of them; expected depth is depth / alpha (the caller's division).  Each map is the colour
+ * blend of a per-Gaussian scalar (z, 1 / z, 1) with a zero background, and its gradient is that blend's: dL/dalpha_i goes into
+ * the same opacity / 2-D mean / conic sums as the colour image's, and dL/dz_i = sum_p w_i (gD - gI / z_i^2) reaches means3D
+ * through the view matrix column that produces z.  No gradient reaches the colours from the maps; dL_dmeans2D includes the
+ * maps' share.
+ *
+ * cgs_raster_render_aux: enqueue after the cgs_raster_render / cgs_raster_render_spec of the view whose result the caller
+ * keeps (after a voided speculative render: after the re-render), with the workspaces and the count R the backward would get.
+ * out_depth / out_invdepth / out_alpha: [H, W] each.  Any argument form of the view. */
+int cgs_raster_render_aux(const cgs_raster_cfg *cfg, int64_t P, int64_t num_rendered,
+                          void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes,
+                          void *img_ws, size_t img_bytes, float *out_depth,
+                          float *out_invdepth, float *out_alpha, void *stream);
+/* Backward of the colour image and the maps, every argument form (the arguments of cgs_raster_backward_ex).  dL_dout [3,H,W],
+ * dL_ddepth, dL_dinvdepth, dL_dalpha [H,W]: any of them may be NULL (no gradient).  Without dL_dout no colour blend backward
+ * runs; dL_dcolors and dL_dopacities must be zero-initialised as for cgs_raster_backward_ex.  With the three map gradients
+ * NULL the result is that of cgs_raster_backward_ex.  scratch: cgs_raster_bwd_aux_scratch_bytes(P) bytes.  Argument errors
+ * return CGS_ERR_ARG before anything is enqueued. */
+int cgs_raster_backward_aux(const cgs_raster_cfg *cfg, int64_t P,
+                            int64_t num_rendered, const float *means3D,
+                            const float *colors, const float *shs,
+                            int32_t sh_degree, int32_t sh_coeffs,
+                            const float *opacities, const float *scales,
+                            const float *rotations, const float *cov3D,
+                            const int32_t *radii, void *geom_ws, size_t geom_bytes,
+                            void *bin_ws, size_t bin_bytes, void *img_ws,
+                            size_t img_bytes, const float *dL_dout,
+                            const float *dL_ddepth, const float *dL_dinvdepth,
+                            const float *dL_dalpha, float *dL_dmeans3D,
+                            float *dL_dmeans2D, float *dL_dcolors,
+                            float *dL_dopacities, float *dL_dshs,
+                            float *dL_dscales, float *dL_drotations,
+                            float *dL_dcov3D, void *scratch,
+                            size_t scratch_bytes, void *stream);
+size_t cgs_raster_bwd_aux_scratch_bytes(int64_t P);
+
 /* ---- the anchor expansion fused with the rasterizer's preprocess stage (csrc/expand_raster.hip) ----
  * Training path of render(): gaussian_renderer/__init__.py:130-145 (generate_neural_gaussians' tail) feeding :179-205.
  * cgs_raster_preprocess_expand_launch = cgs_raster_preprocess_launch whose Gaussians are the surviving slots of
