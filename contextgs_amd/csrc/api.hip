@@ -226,7 +226,7 @@ static int check_forms(const char *fn, const cgs_raster_cfg *cfg, int64_t P, con
 static int raster_preprocess_launch_impl(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *colors,
                                          const float *opacities, const float *scales, const float *rotations,
                                          const CgsRasterForms *forms, void *geom_ws, size_t geom_bytes, int32_t *radii,
-                                         void *stream_, uint64_t *ticket);
+                                         void *stream_, uint64_t *ticket, bool aa = false);
 
 extern "C" int cgs_raster_preprocess_launch(const cgs_raster_cfg *cfg, int64_t P, const float *means3D,
                                             const float *colors, const float *opacities, const float *scales,
@@ -251,10 +251,35 @@ extern "C" int cgs_raster_preprocess_launch_ex(const cgs_raster_cfg *cfg, int64_
                                          geom_ws, geom_bytes, radii, stream_, ticket);
 }
 
+// The option bits of the *_opt entry points (include/cgs.h); anything else is refused before anything is enqueued
+static int check_opts(const char *fn, uint32_t opts) {
+    if (opts & ~(uint32_t)CGS_RASTER_ANTIALIAS) {
+        cgs_set_error("%s: unknown option bits 0x%x (known: CGS_RASTER_ANTIALIAS = 0x%x)", fn, opts & ~(uint32_t)CGS_RASTER_ANTIALIAS,
+                      (uint32_t)CGS_RASTER_ANTIALIAS);
+        return CGS_ERR_ARG;
+    }
+    return CGS_OK;
+}
+
+extern "C" int cgs_raster_preprocess_launch_opt(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *colors,
+                                                const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                                const float *scales, const float *rotations, const float *cov3D, void *geom_ws,
+                                                size_t geom_bytes, int32_t *radii, void *stream_, uint64_t *ticket, uint32_t opts) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (ticket) *ticket = 0;
+    if ((rc = check_opts("cgs_raster_preprocess_launch_opt", opts))) return rc;
+    CgsRasterForms f;
+    if ((rc = check_forms("cgs_raster_preprocess_launch_opt", cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
+        return rc;
+    return raster_preprocess_launch_impl(cfg, P, means3D, colors, opacities, scales, rotations, (shs || cov3D) ? &f : nullptr,
+                                         geom_ws, geom_bytes, radii, stream_, ticket, (opts & CGS_RASTER_ANTIALIAS) != 0);
+}
+
 static int raster_preprocess_launch_impl(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *colors,
                                          const float *opacities, const float *scales, const float *rotations,
                                          const CgsRasterForms *forms, void *geom_ws, size_t geom_bytes, int32_t *radii,
-                                         void *stream_, uint64_t *ticket) {
+                                         void *stream_, uint64_t *ticket, bool aa) {
     hipStream_t stream = (hipStream_t)stream_;
     RasterCountSlot &sl = g_raster_slot;
     int rc = check_cfg(cfg);
@@ -283,10 +308,10 @@ static int raster_preprocess_launch_impl(const cgs_raster_cfg *cfg, int64_t P, c
     }
     if (forms) {
         if ((rc = cgs_launch_preprocess_form(cfg, P, *forms, means3D, colors, opacities, scales, rotations, g, radii, false,
-                                             stream)))
+                                             stream, aa)))
             return rc;
     } else if ((rc = cgs_launch_preprocess(cfg, P, means3D, colors, opacities, scales, rotations, g, radii, false,
-                                           stream)))
+                                           stream, aa)))
         return rc;
     sl.P = P; sl.geom_ws = geom_ws; sl.geom_bytes = geom_bytes; sl.stream = stream;
     return raster_count_tail(P, g, sl, stream);
@@ -669,34 +694,34 @@ extern "C" int cgs_raster_render_aux(const cgs_raster_cfg *cfg, int64_t P, int64
 
 // Backward of the colour image and the three maps together, every argument form of cgs_raster_backward_ex.  Each of the four
 // upstream gradients may be NULL; without dL_dout no colour blend backward runs (dL_dcolors keeps its zeros).
-extern "C" int cgs_raster_backward_aux(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
-                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
-                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
-                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
-                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
-                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
-                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
-                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_) {
-    (void)opacities;
-    hipStream_t stream = (hipStream_t)stream_;
+// fn: the entry point's name for the messages; aa: antialiasing (cgs_raster_backward_opt), which also reads opacities
+static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D,
+                                    const float *colors, const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                    const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                    void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws, size_t img_bytes,
+                                    const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth, const float *dL_dalpha,
+                                    float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities, float *dL_dshs,
+                                    float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *scratch, size_t scratch_bytes,
+                                    hipStream_t stream, bool aa) {
     int rc = check_cfg(cfg);
     if (rc) return rc;
-    if (P < 0 || R < 0) { cgs_set_error("cgs_raster_backward_aux: P < 0 or R < 0"); return CGS_ERR_ARG; }
+    if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
     if (CGS_BLEND_BWD_RAW) {      // (experiment builds: the colour blend backward leaves raw sums the aux pass does not add to)
-        cgs_set_error("cgs_raster_backward_aux: not available with CGS_BLEND_BWD_RAW");
+        cgs_set_error("%s: not available with CGS_BLEND_BWD_RAW", fn);
         return CGS_ERR_ARG;
     }
     CgsRasterForms f;
-    if ((rc = check_forms("cgs_raster_backward_aux", cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
+    if ((rc = check_forms(fn, cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
         return rc;
     if (P == 0) return CGS_OK;
     if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacities || !scratch || (shs && !dL_dshs) ||
-        (cov3D && !dL_dcov3D) || (!cov3D && (!dL_dscales || !dL_drotations)) || !geom_ws || !img_ws || (R > 0 && !bin_ws)) {
-        cgs_set_error("cgs_raster_backward_aux: NULL input");
+        (cov3D && !dL_dcov3D) || (!cov3D && (!dL_dscales || !dL_drotations)) || !geom_ws || !img_ws || (R > 0 && !bin_ws) ||
+        (aa && !opacities)) {
+        cgs_set_error("%s: NULL input", fn);
         return CGS_ERR_ARG;
     }
     if (scratch_bytes < cgs_raster_bwd_aux_scratch_bytes(P)) {
-        cgs_set_error("cgs_raster_backward_aux: scratch too small: %zu < %zu", scratch_bytes, cgs_raster_bwd_aux_scratch_bytes(P));
+        cgs_set_error("%s: scratch too small: %zu < %zu", fn, scratch_bytes, cgs_raster_bwd_aux_scratch_bytes(P));
         return CGS_ERR_WORKSPACE;
     }
     CgsGeom g;
@@ -705,7 +730,7 @@ extern "C" int cgs_raster_backward_aux(const cgs_raster_cfg *cfg, int64_t P, int
     memset(&b, 0, sizeof(b));
     if (!cgs_geom_carve(&g, geom_ws, geom_bytes, P) || !cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width) ||
         (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R))) {
-        cgs_set_error("cgs_raster_backward_aux: workspace too small");
+        cgs_set_error("%s: workspace too small", fn);
         return CGS_ERR_WORKSPACE;
     }
     const bool aux = dL_ddepth || dL_dinvdepth || dL_dalpha;
@@ -720,14 +745,51 @@ extern "C" int cgs_raster_backward_aux(const cgs_raster_cfg *cfg, int64_t P, int
                                             d_z, stream)))
             return rc;
     }
+    // antialiasing: both blend backwards have summed dL/d(op_eff) into dL_dopacities by now; the per-Gaussian kernel turns it
+    // into dL/d(opacity) in place and chains h's share to the covariance
+    const float *aa_op = aa ? opacities : nullptr;
+    float *aa_dop = aa ? dL_dopacities : nullptr;
     if (!shs && !cov3D)
         rc = cgs_launch_preprocess_bwd(cfg, P, nullptr, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dmeans3D,
-                                       dL_dmeans2D, dL_dscales, dL_drotations, stream);
+                                       dL_dmeans2D, dL_dscales, dL_drotations, stream, aa_op, aa_dop);
     else
         rc = cgs_launch_preprocess_bwd_form(cfg, P, f, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dcolors,
-                                            dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream);
+                                            dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_op,
+                                            aa_dop);
     if (rc) return rc;
     return aux ? cgs_launch_aux_dz_chain(cfg, P, radii, d_z, dL_dmeans3D, stream) : CGS_OK;
+}
+
+extern "C" int cgs_raster_backward_aux(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_) {
+    return raster_backward_aux_impl("cgs_raster_backward_aux", cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities,
+                                    scales, rotations, cov3D, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout,
+                                    dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
+                                    dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_, false);
+}
+
+extern "C" int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if ((rc = check_opts("cgs_raster_backward_opt", opts))) return rc;
+    return raster_backward_aux_impl("cgs_raster_backward_opt", cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities,
+                                    scales, rotations, cov3D, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout,
+                                    dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
+                                    dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_,
+                                    (opts & CGS_RASTER_ANTIALIAS) != 0);
 }
 
 extern "C" int cgs_raster_stats(const cgs_raster_cfg *cfg, void *img_ws, size_t img_bytes, int64_t *stats_out,

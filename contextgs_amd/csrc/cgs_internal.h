@@ -131,7 +131,7 @@ size_t cgs_img_carve(CgsImg *im, void *ws, size_t bytes, int32_t H, int32_t W);
 int cgs_launch_preprocess(const cgs_raster_cfg *cfg, int64_t P, const float *means3D,
                           const float *colors, const float *opacities, const float *scales,
                           const float *rotations, CgsGeom &g, int32_t *radii, bool filter_only,
-                          hipStream_t stream);
+                          hipStream_t stream, bool aa = false);     // aa: antialiasing (not with filter_only)
 int cgs_launch_emit_pairs(const cgs_raster_cfg *cfg, int64_t P, CgsGeom &g, CgsBin &b,
                           hipStream_t stream);
 int cgs_launch_ranges(const cgs_raster_cfg *cfg, int64_t R, CgsBin &b, CgsImg &im,
@@ -163,7 +163,9 @@ int cgs_launch_preprocess_bwd(const cgs_raster_cfg *cfg, int64_t P, const float4
                               const float *scales, const float *rotations,
                               const int32_t *radii, const float *dL_dmean2D_px,
                               const float *dL_dconic, float *dL_dmeans3D, float *dL_dmeans2D,
-                              float *dL_dscales, float *dL_drotations, hipStream_t stream);
+                              float *dL_dscales, float *dL_drotations, hipStream_t stream,
+                              const float *aa_opacities = nullptr, float *aa_dL_dopacities = nullptr);
+// (aa_opacities != NULL: antialiasing; aa_dL_dopacities holds dL/d(op_eff) and is rewritten to dL/d(opacity); not with rec_raw)
 
 // expand_raster.hip: the anchor expansion fused with the rasterizer's preprocess stage
 struct CgsExpandSrc {

@@ -20,12 +20,14 @@ struct CgsRasterForms {
 };
 int cgs_launch_preprocess_form(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForms &f, const float *means3D,
                                const float *colors, const float *opacities, const float *scales, const float *rotations,
-                               CgsGeom &g, int32_t *radii, bool filter_only, hipStream_t stream);
+                               CgsGeom &g, int32_t *radii, bool filter_only, hipStream_t stream, bool aa = false);
 int cgs_launch_preprocess_bwd_form(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForms &f, const float *means3D,
                                    const float *scales, const float *rotations, const int32_t *radii,
                                    const float *dL_dmean2D_px, const float *dL_dconic, const float *dL_dcolors,
                                    float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs, float *dL_dscales,
-                                   float *dL_drotations, float *dL_dcov3D, hipStream_t stream);
+                                   float *dL_drotations, float *dL_dcov3D, hipStream_t stream,
+                                   const float *aa_opacities = nullptr, float *aa_dL_dopacities = nullptr);
+// aa: antialiasing (raster_math.h); aa_opacities != NULL: its backward, as cgs_launch_preprocess_bwd's
 
 // ---- spherical harmonics (the real SH basis of 3DGS / PlenOctrees, same constants and term order) ----------------------
 #define CGS_SH_C0 0.28209479177387814f
@@ -190,6 +192,7 @@ __device__ __forceinline__ float3 cgs_dnormvdv(const float3 v, const float3 dv) 
 }
 
 // ---- projection from a given 3-D covariance: cgs_project (csrc/raster_math.h) without its rotation / scale lines -------
+template <bool AA = false>
 __device__ __forceinline__ bool cgs_project_cov(const float3 p, const CgsCov3 &c3, const float *V, const float *Pm, int W, int H,
                                                 float tanfovx, float tanfovy, CgsProj &o) {
     const float3 t = cgs_to_view(p, V);
@@ -202,6 +205,10 @@ __device__ __forceinline__ bool cgs_project_cov(const float3 p, const CgsCov3 &c
     const CgsJac j = cgs_jacobian(t, V, W, H, tanfovx, tanfovy);
     float a, b, c;
     cgs_cov2d(j.A, c3, a, b, c);
+    if constexpr (AA) {
+        float d1;
+        o.aa_h = cgs_aa_h(cgs_det2_comp(a, b, c), a, c, d1);
+    }
     a += 0.3f;
     c += 0.3f;
     const float det = a * c - b * b;
@@ -221,7 +228,8 @@ __device__ __forceinline__ bool cgs_project_cov(const float3 p, const CgsCov3 &c
 
 // ---- forward: cgs_pre_fwd_one (csrc/raster_pre.h) after its cgs_project call, colour evaluated lazily ------------------
 // color() is called only for a Gaussian that touches a tile (radius > 0), the Gaussians whose colour upstream evaluates.
-template <bool FILTER_ONLY, typename ColorFn>
+// AA: pr.aa_h is set (cgs_project / cgs_project_cov with AA), the record and the tightening take op_in * pr.aa_h.
+template <bool FILTER_ONLY, typename ColorFn, bool AA = false>
 __device__ __forceinline__ void cgs_pre_fwd_form(int64_t i, const bool ok, const CgsProj &pr, float op_in, ColorFn color, int W,
                                                  int H, float4 *__restrict__ rec, uint32_t *__restrict__ depth_key,
                                                  uint32_t *__restrict__ tiles, uint2 *__restrict__ rect,
@@ -240,7 +248,7 @@ __device__ __forceinline__ void cgs_pre_fwd_form(int64_t i, const bool ok, const
         if ((x1 - x0) * (y1 - y0) > 0) {
             radius = (int32_t)r;
             if (!FILTER_ONLY) {
-                const float op = op_in;
+                const float op = AA ? op_in * pr.aa_h : op_in;
                 // output-invariant tightening to the alpha >= 1/255 ellipse: see cgs_pre_fwd_one
                 float hx = -1.f, hy = -1.f;
                 uint32_t diag = 0x7C007C00u;
@@ -293,13 +301,24 @@ __device__ __forceinline__ void cgs_pre_fwd_form(int64_t i, const bool ok, const
 
 // ---- backward: the first half of cgs_pre_bwd_one (csrc/raster_pre.h, RAW = false) from a given covariance -------------
 // Fills o.dp (projection + covariance paths of dL/dmeans3D) and o.dm2; M = dL/dSigma as the full symmetric matrix.
+// AA: o.dop and the h terms as in cgs_pre_bwd_one, with d0 from cgs_det2_comp as cgs_project_cov forms it.
+template <bool AA = false>
 __device__ __forceinline__ void cgs_pre_bwd_cov(const float3 p, const CgsCov3 &c3, float gmean_x, float gmean_y, float gconic_a,
                                                 float gconic_b, float gconic_c, const float *V, const float *Pm, int W, int H,
-                                                float tanfovx, float tanfovy, CgsPreBwd &o, float M[9]) {
+                                                float tanfovx, float tanfovy, CgsPreBwd &o, float M[9], float aa_op = 0.f,
+                                                float aa_g = 0.f) {
     const float3 t = cgs_to_view(p, V);
     const CgsJac j = cgs_jacobian(t, V, W, H, tanfovx, tanfovy);
     float x, y, z;   // dilated cov2D = [[x,y],[y,z]]
     cgs_cov2d(j.A, c3, x, y, z);
+    float aa_gx = 0.f, aa_gy = 0.f, aa_gz = 0.f;
+    if constexpr (AA) {
+        float d1;
+        const float d0 = cgs_det2_comp(x, y, z);
+        const float hh = cgs_aa_h(d0, x, z, d1);
+        o.dop = aa_g * hh;
+        cgs_aa_bwd(d0, d1, hh, x, y, z, aa_g, aa_op, aa_gx, aa_gy, aa_gz);
+    }
     x += 0.3f;
     z += 0.3f;
     const float det = x * z - y * y;
@@ -310,6 +329,11 @@ __device__ __forceinline__ void cgs_pre_bwd_cov(const float3 p, const CgsCov3 &c
         gx = d2 * (-z * z * ga + y * z * gbb - y * y * gc);
         gy = d2 * (2.f * y * z * ga - (x * z + y * y) * gbb + 2.f * x * y * gc);
         gz = d2 * (-y * y * ga + x * y * gbb - x * x * gc);
+    }
+    if constexpr (AA) {
+        gx += aa_gx;
+        gy += aa_gy;
+        gz += aa_gz;
     }
     const float h = 0.5f * gy;
     const float *A = j.A;

@@ -14,6 +14,7 @@ struct CgsProj {
     float con_a, con_b, con_c;   // conic = inverse of the dilated 2-D covariance
     float cov_a, cov_b, cov_c;   // dilated 2-D covariance
     float radius;          // ceil(3 sigma_max)
+    float aa_h;            // antialiasing only (AA = true): the opacity factor of cgs_aa_h
 };
 
 struct CgsCov3 { float xx, xy, xz, yy, yz, zz; };
@@ -87,7 +88,58 @@ __device__ __forceinline__ void cgs_cov2d(const float A[6], const CgsCov3 &c, fl
     cc = A[3] * w0 + A[4] * w1 + A[5] * w2;
 }
 
-template <typename T /*unused, float only*/>
+// ---- antialiasing (upstream's `antialiasing`, the 2-D filter of Mip-Splatting) -------------------------------------------
+// With [[a, b], [b, c]] the 2-D covariance BEFORE the 0.3 px^2 dilation:
+//   d0 = a c - b^2,  d1 = (a + 0.3)(c + 0.3) - b^2 = d0 + 0.3 (a + c) + 0.09,  h = sqrt(max(2.5e-5, d0 / d1))
+// and the blend reads opacity * h: the dilation widens the splat, h keeps its integrated alpha.  The conic and the radius
+// stay those of the dilated covariance.  d0 is formed without the cancellation of a c - b^2 (thin, oblique Gaussians):
+// cgs_det2_rs / cgs_det2_comp below.
+#define CGS_AA_R_MIN 2.5e-5f
+
+// d0 from scales / rotations: cov2D = M M^T with M = A R diag(s) (2x3), so by Cauchy-Binet det = the sum of the squared 2x2
+// minors of M - a sum of squares.  s = the scales with scale_modifier applied.
+__device__ __forceinline__ float cgs_det2_rs(const float A[6], const float R[9], const float3 s) {
+    const float sv[3] = {s.x, s.y, s.z};
+    float m0[3], m1[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        m0[k] = sv[k] * (A[0] * R[k] + A[1] * R[3 + k] + A[2] * R[6 + k]);
+        m1[k] = sv[k] * (A[3] * R[k] + A[4] * R[3 + k] + A[5] * R[6 + k]);
+    }
+    const float n01 = m0[0] * m1[1] - m0[1] * m1[0];
+    const float n02 = m0[0] * m1[2] - m0[2] * m1[0];
+    const float n12 = m0[1] * m1[2] - m0[2] * m1[1];
+    return n01 * n01 + n02 * n02 + n12 * n12;
+}
+
+// d0 from a given covariance: a c - b^2 with the rounding error of b^2 put back (Kahan's fma-compensated difference; an
+// explicit fmaf is fused whatever -ffp-contract says)
+__device__ __forceinline__ float cgs_det2_comp(float a, float b, float c) {
+    const float bb = b * b;
+    const float err = fmaf(b, b, -bb);          // b^2 - bb, exactly
+    return fmaf(a, c, -bb) - err;
+}
+
+// h of the undilated (a, c) and d0; d1 out (the backward's denominator)
+__device__ __forceinline__ float cgs_aa_h(float d0, float a, float c, float &d1) {
+    d1 = d0 + 0.3f * (a + c) + 0.09f;
+    return sqrtf(fmaxf(CGS_AA_R_MIN, d0 / d1));
+}
+
+// dL/d(a, b, c) of h * op with dL/d(op_eff) = g (b as ONE variable, the convention of the conic chain's repeated entry):
+// zero where the clamp holds
+__device__ __forceinline__ void cgs_aa_bwd(float d0, float d1, float h, float a, float b, float c, float g, float op, float &ga,
+                                           float &gb, float &gc) {
+    ga = gb = gc = 0.f;
+    if (d0 / d1 > CGS_AA_R_MIN) {
+        const float k = g * op / (2.f * h * d1 * d1);
+        ga = k * (c * d1 - d0 * (c + 0.3f));
+        gc = k * (a * d1 - d0 * (a + 0.3f));
+        gb = k * (-2.f * b * (d1 - d0));
+    }
+}
+
+template <typename T /*unused, float only*/, bool AA = false>
 __device__ __forceinline__ bool cgs_project(const float3 p, const float3 s, const float4 q, const float *V,
                                             const float *Pm, int W, int H, float tanfovx, float tanfovy,
                                             float scale_modifier, CgsProj &o) {
@@ -106,6 +158,10 @@ __device__ __forceinline__ bool cgs_project(const float3 p, const float3 s, cons
     const CgsJac j = cgs_jacobian(t, V, W, H, tanfovx, tanfovy);
     float a, b, c;
     cgs_cov2d(j.A, c3, a, b, c);
+    if constexpr (AA) {
+        float d1;
+        o.aa_h = cgs_aa_h(cgs_det2_rs(j.A, R, sm), a, c, d1);
+    }
     a += 0.3f;
     c += 0.3f;
     const float det = a * c - b * b;

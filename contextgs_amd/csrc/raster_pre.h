@@ -9,14 +9,15 @@
 // One Gaussian of the rasterizer's preprocess stage (project, cov3D -> conic, radius, tile rectangle, record): the body of
 // preprocess_kernel, shared with the kernel that takes its Gaussians straight from the anchor expansion
 // (csrc/expand_raster.hip).  i = the Gaussian's row in every output array.
-template <bool FILTER_ONLY>
+// AA: antialiasing (raster_math.h, cgs_aa_h) - the record and the alpha >= 1/255 tightening take op_in * h.
+template <bool FILTER_ONLY, bool AA = false>
 __device__ __forceinline__ void cgs_pre_fwd_one(int64_t i, const float3 p, const float3 s, const float4 q, float op_in, float c0,
                                                 float c1, float c2, const float *V, const float *Pm, int W, int H,
                                                 float tanfovx, float tanfovy, float scale_modifier, float4 *__restrict__ rec,
                                                 uint32_t *__restrict__ depth_key, uint32_t *__restrict__ tiles,
                                                 uint2 *__restrict__ rect, int32_t *__restrict__ radii) {
     CgsProj pr;
-    const bool ok = cgs_project<float>(p, s, q, V, Pm, W, H, tanfovx, tanfovy, scale_modifier, pr);
+    const bool ok = cgs_project<float, AA>(p, s, q, V, Pm, W, H, tanfovx, tanfovy, scale_modifier, pr);
 
     int32_t radius = 0;
     uint32_t ntiles = 0;
@@ -33,7 +34,7 @@ __device__ __forceinline__ void cgs_pre_fwd_one(int64_t i, const float3 p, const
         if ((x1 - x0) * (y1 - y0) > 0) {
             radius = (int32_t)r;
             if (!FILTER_ONLY) {
-                const float op = op_in;
+                const float op = AA ? op_in * pr.aa_h : op_in;
                 // Output-invariant tightening: alpha >= 1/255 needs
                 // 0.5 d^T conic d <= tau = ln(255 op); that ellipse's bounding box has
                 // half extents sqrt(2 tau cov_xx), sqrt(2 tau cov_yy).  Pixels outside
@@ -97,12 +98,15 @@ __device__ __forceinline__ void cgs_pre_fwd_one(int64_t i, const float3 p, const
 // sum gx, sum gy, sum gx dx, sum gx dy, sum gy dy over the Gaussian's pixels and raw_op its opacity; the factors that turn
 // them into dL/d(pixel mean) and dL/d(conic) are applied here, from the conic this function recomputes anyway:
 //   dL/dmean = -op (con_a a0 + con_b a1, con_c a1 + con_b a0),  dL/dconic = -op (a2 / 2, a3, a4 / 2)
-struct CgsPreBwd { float dp[3], dm2[3], ds[3], dq[4]; };
-template <bool RAW = false>
+// AA (antialiasing, not with RAW): aa_op = the Gaussian's opacity, aa_g = dL/d(op_eff) as the blend backwards summed it;
+// o.dop = dL/d(opacity) = aa_g h, and dL/d(cov2D) of h joins the conic chain's before it goes on to Sigma and means3D.
+struct CgsPreBwd { float dp[3], dm2[3], ds[3], dq[4], dop; };
+template <bool RAW = false, bool AA = false>
 __device__ __forceinline__ CgsPreBwd cgs_pre_bwd_one(const float3 p, const float3 s_raw, const float4 q, float gmean_x, float gmean_y,
                                                      float gconic_a, float gconic_b, float gconic_c, const float *V, const float *Pm,
                                                      int W, int H, float tanfovx, float tanfovy, float scale_modifier,
-                                                     float raw_op = 0.f) {
+                                                     float raw_op = 0.f, float aa_op = 0.f, float aa_g = 0.f) {
+    static_assert(!(RAW && AA), "antialiasing takes the finished dL/d(conic), not the RAW sums");
     CgsPreBwd o;
     const float3 s = make_float3(s_raw.x * scale_modifier, s_raw.y * scale_modifier, s_raw.z * scale_modifier);
     // ---- recompute forward intermediates ---------------------------------
@@ -113,6 +117,14 @@ __device__ __forceinline__ CgsPreBwd cgs_pre_bwd_one(const float3 p, const float
     const CgsJac j = cgs_jacobian(t, V, W, H, tanfovx, tanfovy);
     float x, y, z;   // dilated cov2D = [[x,y],[y,z]]
     cgs_cov2d(j.A, c3, x, y, z);
+    float aa_gx = 0.f, aa_gy = 0.f, aa_gz = 0.f;
+    if constexpr (AA) {
+        float d1;
+        const float d0 = cgs_det2_rs(j.A, R, s);
+        const float hh = cgs_aa_h(d0, x, z, d1);
+        o.dop = aa_g * hh;
+        cgs_aa_bwd(d0, d1, hh, x, y, z, aa_g, aa_op, aa_gx, aa_gy, aa_gz);
+    }
     x += 0.3f;
     z += 0.3f;
     const float det = x * z - y * y;
@@ -135,6 +147,11 @@ __device__ __forceinline__ CgsPreBwd cgs_pre_bwd_one(const float3 p, const float
         gx = d2 * (-z * z * ga + y * z * gbb - y * y * gc);
         gy = d2 * (2.f * y * z * ga - (x * z + y * y) * gbb + 2.f * x * y * gc);
         gz = d2 * (-y * y * ga + x * y * gbb - x * x * gc);
+    }
+    if constexpr (AA) {
+        gx += aa_gx;
+        gy += aa_gy;
+        gz += aa_gz;
     }
     // symmetric matrix form G2 = [[gx, gy/2],[gy/2, gz]]
     const float h = 0.5f * gy;

@@ -32,6 +32,19 @@ The background contributes to none of them; expected depth is depth / alpha.  Ea
 per-Gaussian scalar (z, 1/z, 1) with a zero background, and gradients flow accordingly to means3D (also directly through z),
 means2D, opacities, scales, rotations and cov3D_precomp, never to shs / colors_precomp.  means2D.grad (the densification
 statistic) includes the maps' share, as upstream's `invdepths` backward does.
+
+`GaussianRasterizationSettings(..., antialiasing=True)` (upstream's last field, default False) is the 2-D filter of
+Mip-Splatting that 3DGS code bases turn on with `--antialiasing`.  With [[a, b], [b, c]] the projected 2-D covariance before
+the fixed 0.3 px^2 dilation:
+
+  h = sqrt(max(2.5e-5, (a c - b^2) / ((a + 0.3)(c + 0.3) - b^2)))
+
+and every blend (colour and maps) reads opacity * h: a sub-pixel Gaussian is still widened, but its integrated alpha no
+longer grows with the widening, so a view rendered below the training resolution does not come out too bright and too thick.
+Conic, radii and visible_filter are those of a call without it.  Gradients: opacities get h dL/d(opacity * h), and h's own
+gradient reaches means3D and scales / rotations or cov3D_precomp (not means2D, shs or colors_precomp).  All four argument
+forms, with and without return_aux, run through `_RasterizeGaussiansAA` (cgs_raster_preprocess_launch_opt /
+cgs_raster_backward_opt with CGS_RASTER_ANTIALIAS); with antialiasing=False exactly the code above runs.
 """
 from __future__ import annotations
 
@@ -45,7 +58,7 @@ import torch.nn as nn
 from . import _lib
 
 
-class GaussianRasterizationSettings(NamedTuple):
+class _SettingsFields(NamedTuple):
     image_height: int
     image_width: int
     tanfovx: float
@@ -58,6 +71,31 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
+
+
+class GaussianRasterizationSettings(_SettingsFields):
+    """The reference fork's twelve fields (`_fields`, gaussian_renderer/__init__.py:179-192) plus upstream's
+    `antialiasing`, its last argument (positional 13th or keyword, default False).  `antialiasing` is an attribute rather
+    than a tuple field so that the twelve-field tuple the fork's code unpacks and compares stays exactly as it was;
+    `_replace`, repr and pickling carry it."""
+    antialiasing = False
+
+    def __new__(cls, *args, antialiasing=False, **kw):
+        if len(args) == len(_SettingsFields._fields) + 1:
+            args, antialiasing = args[:-1], args[-1]
+        self = super().__new__(cls, *args, **kw)
+        self.antialiasing = bool(antialiasing)
+        return self
+
+    def _replace(self, **kw):
+        aa = kw.pop("antialiasing", self.antialiasing)
+        return type(self)(*tuple(super()._replace(**kw)), antialiasing=aa)
+
+    def __reduce__(self):
+        return type(self), tuple(self) + (self.antialiasing,)
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing!r})"
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -396,6 +434,93 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
                 d_opac, d_scales, d_rots, d_cov, None)
 
 
+CGS_RASTER_ANTIALIAS = 1      # include/cgs.h: the option bit of the *_opt entry points
+
+
+class _RasterizeGaussiansAA(torch.autograd.Function):
+    """Any of the four argument forms with antialiasing (see the module docstring), with the depth / inverse-depth / alpha
+    maps as three more outputs when `aux`.  The forward is cgs_raster_preprocess_launch_opt, the same binning and colour
+    blend (and map walk); the backward is cgs_raster_backward_opt, whose per-Gaussian kernel turns the blends' dL/d(opacity * h)
+    into dL/d(opacity) and chains h's gradient to the covariance."""
+
+    @staticmethod
+    def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings):
+        L = _lib.lib()
+        _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D)
+        c = {k: (_f32c(v) if v is not None else None)
+             for k, v in dict(means3D=means3D, shs=shs, colors=colors, opac=opacities, scales=scales, rots=rotations,
+                              cov=cov3D).items()}
+        P = c["means3D"].shape[0]
+        dev = c["means3D"].device
+        cfg = _Cfg(raster_settings)
+        if shs is not None:
+            _lib.require_device(cfg.campos)
+        D = int(raster_settings.sh_degree) if shs is not None else 0
+        M = int(shs.shape[1]) if shs is not None else 0
+        H, W = cfg.c.image_height, cfg.c.image_width
+        stream = _lib.current_stream()
+        ctx.set_materialize_grads(False)
+
+        radii = torch.empty(P, dtype=torch.int32, device=dev)
+        geom = _workspace(L.cgs_raster_geom_bytes(P), dev)
+        img = _workspace(L.cgs_raster_img_bytes(H, W), dev)
+        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+        ticket = C.c_uint64(0)
+        _lib.check(L.cgs_raster_preprocess_launch_opt(
+            cfg.ref, P, _lib.ptr(c["means3D"]), _lib.ptr(c["colors"]), _lib.ptr(c["shs"]), D, M, _lib.ptr(c["opac"]),
+            _lib.ptr(c["scales"]), _lib.ptr(c["rots"]), _lib.ptr(c["cov"]), _lib.ptr(geom), geom.numel(), _lib.ptr(radii),
+            stream, C.byref(ticket), CGS_RASTER_ANTIALIAS), "cgs_raster_preprocess_launch_opt")
+        binws, bin_R, _num_rendered = bin_and_blend(cfg, P, geom, img, color, stream, ticket)
+        outs = (color, radii)
+        if aux:
+            maps = [torch.empty(1, H, W, dtype=torch.float32, device=dev) for _ in range(3)]
+            _lib.check(L.cgs_raster_render_aux(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
+                                               binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(),
+                                               _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), stream),
+                       "cgs_raster_render_aux")
+            outs = outs + tuple(maps)
+        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M = cfg, bin_R, D, M
+        ctx.present = [v is not None for v in (shs, colors, scales, rotations, cov3D)]
+        ctx.save_for_backward(c["means3D"], c["shs"], c["colors"], c["opac"], c["scales"], c["rots"], c["cov"], radii, geom,
+                              binws, img)
+        ctx.mark_non_differentiable(radii)
+        return outs
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, *grad_maps):
+        L = _lib.lib()
+        means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img = ctx.saved_tensors
+        cfg = ctx.cfg
+        P = means3D.shape[0]
+        dev = means3D.device
+        has_shs, has_colors, _, _, _ = ctx.present
+        maps = [None if t is None else _f32c(t) for t in (tuple(grad_maps) + (None,) * 3)[:3]]
+        if grad_color is None and all(t is None for t in maps):
+            return (None,) * 10
+        g = _f32c(grad_color) if grad_color is not None else None
+        # the blends accumulate dL/dcolor and dL/d(opacity * h): one zero fill; the per-Gaussian kernel rewrites the latter
+        acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
+        d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
+        d_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        d_means2D = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        d_shs = torch.empty_like(shs) if shs is not None else None
+        d_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if cov is not None else None
+        d_scales = torch.empty(P, 3, dtype=torch.float32, device=dev) if cov is None else None
+        d_rots = torch.empty(P, 4, dtype=torch.float32, device=dev) if cov is None else None
+        stream = _lib.current_stream()
+        scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
+        _lib.check(L.cgs_raster_backward_opt(
+            cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M,
+            _lib.ptr(opac), _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom),
+            geom.numel(), _lib.ptr(binws), binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(), _lib.ptr(g),
+            _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(d_means3D), _lib.ptr(d_means2D),
+            _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_shs), _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov),
+            _lib.ptr(scratch), scratch.numel(), stream, CGS_RASTER_ANTIALIAS), "cgs_raster_backward_opt")
+        colour = g is not None      # the maps send no gradient to the colour inputs
+        return (None, d_means3D, d_means2D, d_shs if (has_shs and colour) else None,
+                d_colors if (has_colors and colour) else None, d_opac, d_scales, d_rots, d_cov, None)
+
+
 def rasterize_gaussians(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings):
     return _RasterizeGaussians.apply(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings)
 
@@ -453,6 +578,13 @@ class GaussianRasterizer(nn.Module):
         """(color [3,H,W], radii int32 [P]); with return_aux=True also {"depth", "invdepth", "alpha"}, float32 [1,H,W]
         each (see the module docstring)."""
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
+        if getattr(self.raster_settings, "antialiasing", False):
+            out = _RasterizeGaussiansAA.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales,
+                                              rotations, cov3D_precomp, self.raster_settings)
+            if return_aux:
+                color, radii, depth, invdepth, alpha = out
+                return color, radii, {"depth": depth, "invdepth": invdepth, "alpha": alpha}
+            return out
         if return_aux:
             color, radii, depth, invdepth, alpha = _RasterizeGaussiansAux.apply(
                 means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings)

@@ -570,7 +570,8 @@ def _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier):
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
         bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=1, campos=viewpoint_camera.camera_center,
-        prefiltered=False, debug=bool(getattr(pipe, "debug", False)))
+        prefiltered=False, debug=bool(getattr(pipe, "debug", False)),
+        antialiasing=bool(getattr(pipe, "antialiasing", False)))
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False,
@@ -578,7 +579,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
 
     return_aux=True: the dict also holds the rasterizer's "depth", "invdepth" and "alpha" maps ([1,H,W] each, see
-    contextgs_amd/rasterizer.py).  In training mode such a call takes the unfused path (the one CGS_FUSE_VIEW=0 takes)."""
+    contextgs_amd/rasterizer.py).  In training mode such a call takes the unfused path (the one CGS_FUSE_VIEW=0 takes), and so
+    does one with `pipe.antialiasing` set (upstream's --antialiasing, see contextgs_amd/rasterizer.py)."""
     is_training = pc.get_color_mlp.training
     view = None
     if is_training:
@@ -588,7 +590,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, bit_per_anchor_param,
          bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level) = \
             generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=True, step=step,
-                                      _view=None if return_aux else view)
+                                      _view=None if (return_aux or view.raster_settings.antialiasing) else view)
         if view.done is not None:
             rendered_image, radii, screenspace_points = view.done
             return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,

@@ -264,6 +264,48 @@ int cgs_raster_backward_aux(const cgs_raster_cfg *cfg, int64_t P,
                             size_t scratch_bytes, void *stream);
 size_t cgs_raster_bwd_aux_scratch_bytes(int64_t P);
 
+/* ---- options of a view that cgs_raster_cfg does not carry (its layout is fixed) ----
+ * CGS_RASTER_ANTIALIAS: upstream's `antialiasing` (the 2-D filter of Mip-Splatting).  With [[a, b], [b, c]] the 2-D covariance
+ * before the 0.3 px^2 dilation, d0 = a c - b^2, d1 = (a + 0.3)(c + 0.3) - b^2 and h = sqrt(max(2.5e-5, d0 / d1)), the blend
+ * reads opacity * h in place of the opacity: a splat's integrated alpha no longer grows with the dilation.  The conic, the
+ * radius (radii) and the visibility filters are those of a call without it.  d0 is formed without cancellation (the sum of
+ * the squared 2x2 minors of A R diag(s) for scales / rotations, an fma-compensated a c - b^2 for cov3D).  The depth /
+ * inverse-depth / alpha maps read the same opacities.  Backward: dL/d(opacity) = h dL/d(opacity * h), and h's gradient reaches
+ * means3D and scales / rotations or cov3D (not means2D, colours or SH). */
+#define CGS_RASTER_ANTIALIAS 1u
+/* cgs_raster_preprocess_launch_ex with an options word (CGS_RASTER_ANTIALIAS; any other bit: CGS_ERR_ARG before anything is
+ * enqueued).  All four argument forms; the ticket, _wait2, render_spec, render and render_aux follow as for _launch_ex, and
+ * opts == 0 gives _launch_ex's result. */
+int cgs_raster_preprocess_launch_opt(const cgs_raster_cfg *cfg, int64_t P,
+                                     const float *means3D, const float *colors,
+                                     const float *shs, int32_t sh_degree,
+                                     int32_t sh_coeffs, const float *opacities,
+                                     const float *scales, const float *rotations,
+                                     const float *cov3D, void *geom_ws,
+                                     size_t geom_bytes, int32_t *radii,
+                                     void *stream, uint64_t *ticket, uint32_t opts);
+/* cgs_raster_backward_aux with an options word: the backward of a view launched by cgs_raster_preprocess_launch_opt with the
+ * same opts.  Colour and / or map gradients, all four forms; dL_dcolors and dL_dopacities zero-initialised as there, scratch
+ * cgs_raster_bwd_aux_scratch_bytes(P) bytes.  With CGS_RASTER_ANTIALIAS, opacities [P] must be given; dL_dopacities receives
+ * the gradient of the opacity the caller passed.  opts == 0 gives cgs_raster_backward_aux's result; unknown bits: CGS_ERR_ARG
+ * before anything is enqueued.  Not available in CGS_BLEND_BWD_RAW builds. */
+int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P,
+                            int64_t num_rendered, const float *means3D,
+                            const float *colors, const float *shs,
+                            int32_t sh_degree, int32_t sh_coeffs,
+                            const float *opacities, const float *scales,
+                            const float *rotations, const float *cov3D,
+                            const int32_t *radii, void *geom_ws, size_t geom_bytes,
+                            void *bin_ws, size_t bin_bytes, void *img_ws,
+                            size_t img_bytes, const float *dL_dout,
+                            const float *dL_ddepth, const float *dL_dinvdepth,
+                            const float *dL_dalpha, float *dL_dmeans3D,
+                            float *dL_dmeans2D, float *dL_dcolors,
+                            float *dL_dopacities, float *dL_dshs,
+                            float *dL_dscales, float *dL_drotations,
+                            float *dL_dcov3D, void *scratch,
+                            size_t scratch_bytes, void *stream, uint32_t opts);
+
 /* ---- the anchor expansion fused with the rasterizer's preprocess stage (csrc/expand_raster.hip) ----
  * Training path of render(): gaussian_renderer/__init__.py:130-145 (generate_neural_gaussians' tail) feeding :179-205.
  * cgs_raster_preprocess_expand_launch = cgs_raster_preprocess_launch whose Gaussians are the surviving slots of
