@@ -14,13 +14,18 @@ All four argument forms of upstream are implemented: colours as `colors_precomp`
 means3D - campos, clamped at 0), covariances from `scales` + `rotations` or as
 `cov3D_precomp` [P,6] (upper triangle xx, xy, xz, yy, yz, zz, used as given:
 scale_modifier does not apply).  Exactly one of each pair; anything else raises
-ValueError before a device is touched.  The form the reference renders with
-(colors_precomp + scales/rotations, gaussian_renderer/__init__.py:197-205) goes
-through `_RasterizeGaussians`; the others through `_RasterizeGaussiansForms`
-(csrc/raster_forms.hip, same binning and blend).
+ValueError before a device is touched.  Every form, with or without the maps and
+antialiasing below, is ONE autograd node, `_RasterizeGaussians`.  Its forward is
+cgs_raster_preprocess_launch_opt, the binning and the blend; for the form the
+reference renders with (colors_precomp + scales/rotations,
+gaussian_renderer/__init__.py:197-205) that is cgs_raster_preprocess_launch, for
+the others the kernels of csrc/raster_forms.hip.  Its backward is
+cgs_raster_backward_ex (cgs_raster_backward for the reference's form) when only the
+colour image got a gradient and antialiasing is off, cgs_raster_backward_opt when
+antialiasing is on or one of the maps got a gradient.
 
 `forward(..., return_aux=True)` returns `(color, radii, {"depth", "invdepth", "alpha"})`, float32 [1,H,W] each, in all
-four forms (`_RasterizeGaussiansAux`, csrc/raster_aux.hip); without it the call runs exactly the code above.  For pixel p the
+four forms (csrc/raster_aux.hip); without it the call runs exactly the code above.  For pixel p the
 contributors i are exactly those of the colour blend (same order, same alpha = min(0.99, o exp(power)), same skip below
 1/255, same stop at T (1 - alpha) < 1e-4); with w_i = alpha_i T_i and z_i the view-space depth of Gaussian i's centre:
 
@@ -43,8 +48,8 @@ and every blend (colour and maps) reads opacity * h: a sub-pixel Gaussian is sti
 longer grows with the widening, so a view rendered below the training resolution does not come out too bright and too thick.
 Conic, radii and visible_filter are those of a call without it.  Gradients: opacities get h dL/d(opacity * h), and h's own
 gradient reaches means3D and scales / rotations or cov3D_precomp (not means2D, shs or colors_precomp).  All four argument
-forms, with and without return_aux, run through `_RasterizeGaussiansAA` (cgs_raster_preprocess_launch_opt /
-cgs_raster_backward_opt with CGS_RASTER_ANTIALIAS); with antialiasing=False exactly the code above runs.
+forms, with and without return_aux, pass CGS_RASTER_ANTIALIAS to cgs_raster_preprocess_launch_opt / cgs_raster_backward_opt;
+with antialiasing=False exactly the code above runs.
 """
 from __future__ import annotations
 
@@ -192,61 +197,10 @@ def bin_and_blend(cfg, P, geom, img, color, stream, ticket):
     return binws, bin_R, num_rendered
 
 
-class _RasterizeGaussians(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, raster_settings):
-        L = _lib.lib()
-        _lib.require_device(means3D, colors, opacities, scales, rotations)
-        means3D_c, colors_c = _f32c(means3D), _f32c(colors)
-        opac_c, scales_c, rots_c = _f32c(opacities), _f32c(scales), _f32c(rotations)
-        P = means3D_c.shape[0]
-        dev = means3D_c.device
-        cfg = _Cfg(raster_settings)
-        H, W = cfg.c.image_height, cfg.c.image_width
-        stream = _lib.current_stream()
-        ctx.set_materialize_grads(False)        # no zero tensors for the gradient of `radii`
-
-        radii = torch.empty(P, dtype=torch.int32, device=dev)       # the preprocess kernel writes every entry (0 = culled)
-        geom = _workspace(L.cgs_raster_geom_bytes(P), dev)
-        img = _workspace(L.cgs_raster_img_bytes(H, W), dev)
-        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-        ticket = C.c_uint64(0)
-        _lib.check(L.cgs_raster_preprocess_launch(cfg.ref, P, _lib.ptr(means3D_c), _lib.ptr(colors_c), _lib.ptr(opac_c),
-                                                  _lib.ptr(scales_c), _lib.ptr(rots_c), _lib.ptr(geom), geom.numel(),
-                                                  _lib.ptr(radii), stream, C.byref(ticket)), "cgs_raster_preprocess_launch")
-        binws, bin_R, _num_rendered = bin_and_blend(cfg, P, geom, img, color, stream, ticket)
-        ctx.cfg = cfg
-        ctx.num_rendered = bin_R
-        ctx.save_for_backward(means3D_c, colors_c, opac_c, scales_c, rots_c, radii, geom, binws, img)
-        ctx.mark_non_differentiable(radii)
-        return color, radii
-
-    @staticmethod
-    def backward(ctx, grad_color, _grad_radii):
-        L = _lib.lib()
-        means3D, colors, opac, scales, rots, radii, geom, binws, img = ctx.saved_tensors
-        cfg = ctx.cfg
-        P = means3D.shape[0]
-        dev = means3D.device
-        if grad_color is None:
-            return (None,) * 7
-        g = _f32c(grad_color)
-        # colour / opacity gradients are accumulated atomically by the blend backward: one zero fill for both; the other
-        # four arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones)
-        acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
-        d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
-        rest = torch.empty(P * (3 + 3 + 3 + 4), dtype=torch.float32, device=dev)
-        parts = torch.split(rest, [3 * P, 3 * P, 3 * P, 4 * P])
-        d_means3D, d_means2D = parts[0].view(P, 3), parts[1].view(P, 3)
-        d_scales, d_rots = parts[2].view(P, 3), parts[3].view(P, 4)
-        scratch = _workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
-        _lib.check(L.cgs_raster_backward(
-            cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opac), _lib.ptr(scales),
-            _lib.ptr(rots), _lib.ptr(radii), _lib.ptr(geom), geom.numel(), _lib.ptr(binws), binws.numel(),
-            _lib.ptr(img), img.numel(), _lib.ptr(g), _lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors),
-            _lib.ptr(d_opac), _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(scratch), scratch.numel(),
-            _lib.current_stream()), "cgs_raster_backward")
-        return d_means3D, d_means2D, d_colors, d_opac, d_scales, d_rots, None
+def _check_cov_form(scales, rotations, cov3D_precomp) -> None:
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise ValueError("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
 
 
 def check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, sh_degree=None) -> None:
@@ -254,9 +208,7 @@ def check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, sh_degree
     only: no device is touched."""
     if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
         raise ValueError("Please provide excatly one of either SHs or precomputed colors!")
-    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-        raise ValueError("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+    _check_cov_form(scales, rotations, cov3D_precomp)
     if shs is not None:
         D = int(sh_degree)
         if shs.dim() != 3 or shs.shape[2] != 3:
@@ -269,220 +221,55 @@ def check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, sh_degree
         raise ValueError(f"cov3D_precomp must be [P, 6], got {tuple(cov3D_precomp.shape)}")
 
 
-class _RasterizeGaussiansForms(torch.autograd.Function):
-    """The forms _RasterizeGaussians does not take: shs and / or cov3D_precomp (absent inputs are None)."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings):
-        L = _lib.lib()
-        _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D)
-        c = {k: (_f32c(v) if v is not None else None)
-             for k, v in dict(means3D=means3D, shs=shs, colors=colors, opac=opacities, scales=scales, rots=rotations,
-                              cov=cov3D).items()}
-        P = c["means3D"].shape[0]
-        dev = c["means3D"].device
-        cfg = _Cfg(raster_settings)
-        if shs is not None:
-            _lib.require_device(cfg.campos)
-        D = int(raster_settings.sh_degree) if shs is not None else 0
-        M = int(shs.shape[1]) if shs is not None else 0
-        H, W = cfg.c.image_height, cfg.c.image_width
-        stream = _lib.current_stream()
-        ctx.set_materialize_grads(False)
-
-        radii = torch.empty(P, dtype=torch.int32, device=dev)
-        geom = _workspace(L.cgs_raster_geom_bytes(P), dev)
-        img = _workspace(L.cgs_raster_img_bytes(H, W), dev)
-        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-        ticket = C.c_uint64(0)
-        _lib.check(L.cgs_raster_preprocess_launch_ex(
-            cfg.ref, P, _lib.ptr(c["means3D"]), _lib.ptr(c["colors"]), _lib.ptr(c["shs"]), D, M, _lib.ptr(c["opac"]),
-            _lib.ptr(c["scales"]), _lib.ptr(c["rots"]), _lib.ptr(c["cov"]), _lib.ptr(geom), geom.numel(), _lib.ptr(radii),
-            stream, C.byref(ticket)), "cgs_raster_preprocess_launch_ex")
-        binws, bin_R, _num_rendered = bin_and_blend(cfg, P, geom, img, color, stream, ticket)
-        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M = cfg, bin_R, D, M
-        ctx.present = [v is not None for v in (shs, colors, scales, rotations, cov3D)]
-        ctx.save_for_backward(c["means3D"], c["shs"], c["colors"], c["opac"], c["scales"], c["rots"], c["cov"], radii, geom,
-                              binws, img)
-        ctx.mark_non_differentiable(radii)
-        return color, radii
-
-    @staticmethod
-    def backward(ctx, grad_color, _grad_radii):
-        L = _lib.lib()
-        means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img = ctx.saved_tensors
-        cfg = ctx.cfg
-        P = means3D.shape[0]
-        dev = means3D.device
-        if grad_color is None:
-            return (None,) * 9
-        g = _f32c(grad_color)
-        # the blend backward accumulates dL/dcolor (read by the SH backward) and dL/dopacity: one zero fill; the rest is
-        # written for every Gaussian by the preprocess backward
-        acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
-        d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
-        d_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        d_means2D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        d_shs = torch.empty_like(shs) if shs is not None else None
-        d_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if cov is not None else None
-        d_scales = torch.empty(P, 3, dtype=torch.float32, device=dev) if cov is None else None
-        d_rots = torch.empty(P, 4, dtype=torch.float32, device=dev) if cov is None else None
-        scratch = _workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
-        _lib.check(L.cgs_raster_backward_ex(
-            cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M, _lib.ptr(opac),
-            _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
-            binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(), _lib.ptr(g), _lib.ptr(d_means3D),
-            _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_shs), _lib.ptr(d_scales), _lib.ptr(d_rots),
-            _lib.ptr(d_cov), _lib.ptr(scratch), scratch.numel(), _lib.current_stream()), "cgs_raster_backward_ex")
-        has_shs, has_colors, _, _, _ = ctx.present
-        return (d_means3D, d_means2D, d_shs if has_shs else None, d_colors if has_colors else None, d_opac, d_scales, d_rots,
-                d_cov, None)
-
-
-class _RasterizeGaussiansAux(torch.autograd.Function):
-    """Any of the four argument forms (absent inputs are None) with the depth / inverse-depth / alpha maps as three more
-    outputs (csrc/raster_aux.hip).  The forward is the form's preprocess (cgs_raster_preprocess_launch_ex, which is
-    cgs_raster_preprocess_launch for colors_precomp + scales/rotations), the same binning and colour blend, then one walk of
-    the final per-tile lists for the maps.  The backward calls cgs_raster_backward / _ex unchanged when the maps get no
-    gradient, cgs_raster_backward_aux otherwise (no colour blend backward when the image gets none)."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings):
-        L = _lib.lib()
-        _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D)
-        c = {k: (_f32c(v) if v is not None else None)
-             for k, v in dict(means3D=means3D, shs=shs, colors=colors, opac=opacities, scales=scales, rots=rotations,
-                              cov=cov3D).items()}
-        P = c["means3D"].shape[0]
-        dev = c["means3D"].device
-        cfg = _Cfg(raster_settings)
-        if shs is not None:
-            _lib.require_device(cfg.campos)
-        D = int(raster_settings.sh_degree) if shs is not None else 0
-        M = int(shs.shape[1]) if shs is not None else 0
-        H, W = cfg.c.image_height, cfg.c.image_width
-        stream = _lib.current_stream()
-        ctx.set_materialize_grads(False)
-
-        radii = torch.empty(P, dtype=torch.int32, device=dev)
-        geom = _workspace(L.cgs_raster_geom_bytes(P), dev)
-        img = _workspace(L.cgs_raster_img_bytes(H, W), dev)
-        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-        depth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-        invdepth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-        alpha = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-        ticket = C.c_uint64(0)
-        _lib.check(L.cgs_raster_preprocess_launch_ex(
-            cfg.ref, P, _lib.ptr(c["means3D"]), _lib.ptr(c["colors"]), _lib.ptr(c["shs"]), D, M, _lib.ptr(c["opac"]),
-            _lib.ptr(c["scales"]), _lib.ptr(c["rots"]), _lib.ptr(c["cov"]), _lib.ptr(geom), geom.numel(), _lib.ptr(radii),
-            stream, C.byref(ticket)), "cgs_raster_preprocess_launch_ex")
-        binws, bin_R, _num_rendered = bin_and_blend(cfg, P, geom, img, color, stream, ticket)
-        # behind the render bin_and_blend kept (a voided speculative render has been redone by now)
-        _lib.check(L.cgs_raster_render_aux(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
-                                           binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(),
-                                           _lib.ptr(depth), _lib.ptr(invdepth), _lib.ptr(alpha), stream),
-                   "cgs_raster_render_aux")
-        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M = cfg, bin_R, D, M
-        ctx.present = [v is not None for v in (shs, colors, scales, rotations, cov3D)]
-        ctx.save_for_backward(c["means3D"], c["shs"], c["colors"], c["opac"], c["scales"], c["rots"], c["cov"], radii, geom,
-                              binws, img)
-        ctx.mark_non_differentiable(radii)
-        return color, radii, depth, invdepth, alpha
-
-    @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_invdepth, grad_alpha):
-        L = _lib.lib()
-        means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img = ctx.saved_tensors
-        cfg = ctx.cfg
-        P = means3D.shape[0]
-        dev = means3D.device
-        has_shs, has_colors, _, _, _ = ctx.present
-        maps = [None if t is None else _f32c(t) for t in (grad_depth, grad_invdepth, grad_alpha)]
-        if grad_color is None and all(t is None for t in maps):
-            return (None,) * 9
-        g = _f32c(grad_color) if grad_color is not None else None
-        acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
-        d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
-        d_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        d_means2D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        d_shs = torch.empty_like(shs) if shs is not None else None
-        d_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if cov is not None else None
-        d_scales = torch.empty(P, 3, dtype=torch.float32, device=dev) if cov is None else None
-        d_rots = torch.empty(P, 4, dtype=torch.float32, device=dev) if cov is None else None
-        stream = _lib.current_stream()
-        bin_bytes = binws.numel() if binws is not None else 0
-        if all(t is None for t in maps):
-            # the colour image alone: exactly the existing backward
-            scratch = _workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
-            _lib.check(L.cgs_raster_backward_ex(
-                cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M,
-                _lib.ptr(opac), _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom),
-                geom.numel(), _lib.ptr(binws), bin_bytes, _lib.ptr(img), img.numel(), _lib.ptr(g), _lib.ptr(d_means3D),
-                _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_shs), _lib.ptr(d_scales),
-                _lib.ptr(d_rots), _lib.ptr(d_cov), _lib.ptr(scratch), scratch.numel(), stream), "cgs_raster_backward_ex")
-        else:
-            scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
-            _lib.check(L.cgs_raster_backward_aux(
-                cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M,
-                _lib.ptr(opac), _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom),
-                geom.numel(), _lib.ptr(binws), bin_bytes, _lib.ptr(img), img.numel(), _lib.ptr(g), _lib.ptr(maps[0]),
-                _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors),
-                _lib.ptr(d_opac), _lib.ptr(d_shs), _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov),
-                _lib.ptr(scratch), scratch.numel(), stream), "cgs_raster_backward_aux")
-        colour = g is not None      # the maps send no gradient to the colour inputs
-        return (d_means3D, d_means2D, d_shs if (has_shs and colour) else None, d_colors if (has_colors and colour) else None,
-                d_opac, d_scales, d_rots, d_cov, None)
-
-
 CGS_RASTER_ANTIALIAS = 1      # include/cgs.h: the option bit of the *_opt entry points
 
 
-class _RasterizeGaussiansAA(torch.autograd.Function):
-    """Any of the four argument forms with antialiasing (see the module docstring), with the depth / inverse-depth / alpha
-    maps as three more outputs when `aux`.  The forward is cgs_raster_preprocess_launch_opt, the same binning and colour
-    blend (and map walk); the backward is cgs_raster_backward_opt, whose per-Gaussian kernel turns the blends' dL/d(opacity * h)
-    into dL/d(opacity) and chains h's gradient to the covariance."""
+class _RasterizeGaussians(torch.autograd.Function):
+    """The one node of the drop-in: any of the four argument forms (absent inputs are None), antialiasing from
+    `raster_settings.antialiasing`, and the depth / inverse-depth / alpha maps as three more outputs when `aux`.  The forward
+    is cgs_raster_preprocess_launch_opt (with no option bit and neither shs nor cov3D it is cgs_raster_preprocess_launch), the
+    binning and colour blend, then one walk of the final per-tile lists for the maps.  The backward is cgs_raster_backward_ex
+    (cgs_raster_backward for colours + scales / rotations) when only the colour image got a gradient and antialiasing is off,
+    cgs_raster_backward_opt otherwise: it runs no colour blend backward when the image got none, and with antialiasing its
+    per-Gaussian kernel turns the blends' dL/d(opacity * h) into dL/d(opacity) and chains h's gradient to the covariance."""
 
     @staticmethod
     def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings):
         L = _lib.lib()
         _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D)
-        c = {k: (_f32c(v) if v is not None else None)
-             for k, v in dict(means3D=means3D, shs=shs, colors=colors, opac=opacities, scales=scales, rots=rotations,
-                              cov=cov3D).items()}
-        P = c["means3D"].shape[0]
-        dev = c["means3D"].device
+        means3D, shs, colors, opac, scales, rots, cov = (
+            None if t is None else _f32c(t) for t in (means3D, shs, colors, opacities, scales, rotations, cov3D))
+        P = means3D.shape[0]
+        dev = means3D.device
         cfg = _Cfg(raster_settings)
         if shs is not None:
             _lib.require_device(cfg.campos)
         D = int(raster_settings.sh_degree) if shs is not None else 0
         M = int(shs.shape[1]) if shs is not None else 0
+        opts = CGS_RASTER_ANTIALIAS if getattr(raster_settings, "antialiasing", False) else 0
         H, W = cfg.c.image_height, cfg.c.image_width
         stream = _lib.current_stream()
-        ctx.set_materialize_grads(False)
+        ctx.set_materialize_grads(False)        # no zero tensors for the gradients of `radii` and of unused outputs
 
-        radii = torch.empty(P, dtype=torch.int32, device=dev)
+        radii = torch.empty(P, dtype=torch.int32, device=dev)       # the preprocess kernel writes every entry (0 = culled)
         geom = _workspace(L.cgs_raster_geom_bytes(P), dev)
         img = _workspace(L.cgs_raster_img_bytes(H, W), dev)
         color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         ticket = C.c_uint64(0)
         _lib.check(L.cgs_raster_preprocess_launch_opt(
-            cfg.ref, P, _lib.ptr(c["means3D"]), _lib.ptr(c["colors"]), _lib.ptr(c["shs"]), D, M, _lib.ptr(c["opac"]),
-            _lib.ptr(c["scales"]), _lib.ptr(c["rots"]), _lib.ptr(c["cov"]), _lib.ptr(geom), geom.numel(), _lib.ptr(radii),
-            stream, C.byref(ticket), CGS_RASTER_ANTIALIAS), "cgs_raster_preprocess_launch_opt")
+            cfg.ref, P, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), D, M, _lib.ptr(opac), _lib.ptr(scales),
+            _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(geom), geom.numel(), _lib.ptr(radii), stream, C.byref(ticket), opts),
+            "cgs_raster_preprocess_launch_opt")
         binws, bin_R, _num_rendered = bin_and_blend(cfg, P, geom, img, color, stream, ticket)
         outs = (color, radii)
-        if aux:
+        if aux:     # behind the render bin_and_blend kept (a voided speculative render has been redone by now)
             maps = [torch.empty(1, H, W, dtype=torch.float32, device=dev) for _ in range(3)]
             _lib.check(L.cgs_raster_render_aux(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
-                                               binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(),
-                                               _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), stream),
-                       "cgs_raster_render_aux")
-            outs = outs + tuple(maps)
-        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M = cfg, bin_R, D, M
-        ctx.present = [v is not None for v in (shs, colors, scales, rotations, cov3D)]
-        ctx.save_for_backward(c["means3D"], c["shs"], c["colors"], c["opac"], c["scales"], c["rots"], c["cov"], radii, geom,
-                              binws, img)
+                                               binws.numel(), _lib.ptr(img), img.numel(), _lib.ptr(maps[0]),
+                                               _lib.ptr(maps[1]), _lib.ptr(maps[2]), stream), "cgs_raster_render_aux")
+            outs += tuple(maps)
+        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M, ctx.opts = cfg, bin_R, D, M, opts
+        ctx.save_for_backward(means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img)
         ctx.mark_non_differentiable(radii)
         return outs
 
@@ -493,36 +280,43 @@ class _RasterizeGaussiansAA(torch.autograd.Function):
         cfg = ctx.cfg
         P = means3D.shape[0]
         dev = means3D.device
-        has_shs, has_colors, _, _, _ = ctx.present
-        maps = [None if t is None else _f32c(t) for t in (tuple(grad_maps) + (None,) * 3)[:3]]
-        if grad_color is None and all(t is None for t in maps):
+        g, *maps = (None if t is None else _f32c(t) for t in (grad_color, *grad_maps, None, None, None)[:4])
+        if g is None and all(t is None for t in maps):
             return (None,) * 10
-        g = _f32c(grad_color) if grad_color is not None else None
-        # the blends accumulate dL/dcolor and dL/d(opacity * h): one zero fill; the per-Gaussian kernel rewrites the latter
+        # the blends accumulate dL/dcolor (read by the SH backward) and dL/dopacity atomically: one zero fill for both; the
+        # other arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones)
         acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
         d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
-        d_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        d_means2D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        d_shs = torch.empty_like(shs) if shs is not None else None
-        d_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if cov is not None else None
-        d_scales = torch.empty(P, 3, dtype=torch.float32, device=dev) if cov is None else None
-        d_rots = torch.empty(P, 4, dtype=torch.float32, device=dev) if cov is None else None
+        rest = torch.empty(P * (6 + (7 if cov is None else 6)), dtype=torch.float32, device=dev)
+        d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:6 * P].view(P, 3)
+        d_scales = rest[6 * P:9 * P].view(P, 3) if cov is None else None
+        d_rots = rest[9 * P:].view(P, 4) if cov is None else None
+        d_cov = rest[6 * P:].view(P, 6) if cov is not None else None
+        d_shs = torch.empty_like(shs) if shs is not None else None      # of its own: aligned as shs is (vector stores)
+        inputs = (cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M,
+                  _lib.ptr(opac), _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom),
+                  geom.numel(), _lib.ptr(binws), binws.numel(), _lib.ptr(img), img.numel(), _lib.ptr(g))
+        grads = (_lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_shs),
+                 _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov))
         stream = _lib.current_stream()
-        scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
-        _lib.check(L.cgs_raster_backward_opt(
-            cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M,
-            _lib.ptr(opac), _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom),
-            geom.numel(), _lib.ptr(binws), binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(), _lib.ptr(g),
-            _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(d_means3D), _lib.ptr(d_means2D),
-            _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_shs), _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov),
-            _lib.ptr(scratch), scratch.numel(), stream, CGS_RASTER_ANTIALIAS), "cgs_raster_backward_opt")
-        colour = g is not None      # the maps send no gradient to the colour inputs
-        return (None, d_means3D, d_means2D, d_shs if (has_shs and colour) else None,
-                d_colors if (has_colors and colour) else None, d_opac, d_scales, d_rots, d_cov, None)
+        if ctx.opts or any(t is not None for t in maps):
+            scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
+            _lib.check(L.cgs_raster_backward_opt(*inputs, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), *grads,
+                                                 _lib.ptr(scratch), scratch.numel(), stream, ctx.opts),
+                       "cgs_raster_backward_opt")
+        else:       # the colour image alone, no antialiasing (cgs_raster_backward for the form the reference trains with)
+            scratch = _workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
+            _lib.check(L.cgs_raster_backward_ex(*inputs, *grads, _lib.ptr(scratch), scratch.numel(), stream),
+                       "cgs_raster_backward_ex")
+        if g is None:       # the maps send no gradient to the colour inputs
+            d_shs = d_colors = None
+        return (None, d_means3D, d_means2D, d_shs, d_colors if colors is not None else None, d_opac, d_scales, d_rots,
+                d_cov, None)
 
 
 def rasterize_gaussians(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings):
-    return _RasterizeGaussians.apply(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings)
+    return _RasterizeGaussians.apply(False, means3D, means2D, None, colors_precomp, opacities, scales, rotations, None,
+                                     raster_settings)
 
 
 def raster_stats(raster_settings: GaussianRasterizationSettings, img_ws: torch.Tensor) -> torch.Tensor:
@@ -549,28 +343,20 @@ class GaussianRasterizer(nn.Module):
             return z > 0.2
 
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise ValueError("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        _check_cov_form(scales, rotations, cov3D_precomp)
         L = _lib.lib()
-        if cov3D_precomp is not None:
-            _lib.require_device(means3D, cov3D_precomp)
-            with torch.no_grad():
-                m, cv = _f32c(means3D), _f32c(cov3D_precomp)
-                N = m.shape[0]
-                cfg = _Cfg(self.raster_settings)
-                radii = torch.zeros(N, dtype=torch.int32, device=m.device)
-                _lib.check(L.cgs_filter_cov(cfg.ref, N, _lib.ptr(m), _lib.ptr(cv), _lib.ptr(radii), _lib.current_stream()),
-                           "cgs_filter_cov")
-            return radii
-        _lib.require_device(means3D, scales, rotations)
+        _lib.require_device(means3D, scales, rotations, cov3D_precomp)
         with torch.no_grad():
-            m, s, r = _f32c(means3D), _f32c(scales), _f32c(rotations)
+            m = _f32c(means3D)
             N = m.shape[0]
             cfg = _Cfg(self.raster_settings)
             radii = torch.zeros(N, dtype=torch.int32, device=m.device)
-            _lib.check(L.cgs_filter(cfg.ref, N, _lib.ptr(m), _lib.ptr(s), _lib.ptr(r), _lib.ptr(radii),
-                                    _lib.current_stream()), "cgs_filter")
+            if cov3D_precomp is not None:
+                _lib.check(L.cgs_filter_cov(cfg.ref, N, _lib.ptr(m), _lib.ptr(_f32c(cov3D_precomp)), _lib.ptr(radii),
+                                            _lib.current_stream()), "cgs_filter_cov")
+            else:
+                _lib.check(L.cgs_filter(cfg.ref, N, _lib.ptr(m), _lib.ptr(_f32c(scales)), _lib.ptr(_f32c(rotations)),
+                                        _lib.ptr(radii), _lib.current_stream()), "cgs_filter")
         return radii
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -578,19 +364,9 @@ class GaussianRasterizer(nn.Module):
         """(color [3,H,W], radii int32 [P]); with return_aux=True also {"depth", "invdepth", "alpha"}, float32 [1,H,W]
         each (see the module docstring)."""
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
-        if getattr(self.raster_settings, "antialiasing", False):
-            out = _RasterizeGaussiansAA.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales,
-                                              rotations, cov3D_precomp, self.raster_settings)
-            if return_aux:
-                color, radii, depth, invdepth, alpha = out
-                return color, radii, {"depth": depth, "invdepth": invdepth, "alpha": alpha}
+        out = _RasterizeGaussians.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                        cov3D_precomp, self.raster_settings)
+        if not return_aux:
             return out
-        if return_aux:
-            color, radii, depth, invdepth, alpha = _RasterizeGaussiansAux.apply(
-                means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings)
-            return color, radii, {"depth": depth, "invdepth": invdepth, "alpha": alpha}
-        if shs is not None or cov3D_precomp is not None:
-            return _RasterizeGaussiansForms.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                                  cov3D_precomp, self.raster_settings)
-        return rasterize_gaussians(means3D, means2D, colors_precomp, opacities, scales, rotations,
-                                   self.raster_settings)
+        color, radii, depth, invdepth, alpha = out
+        return color, radii, {"depth": depth, "invdepth": invdepth, "alpha": alpha}
