@@ -36,9 +36,7 @@ from .multi_level import torch_unique_with_indices
 
 Q_FEAT0, Q_SCALING0, Q_OFFSETS0 = 1, 0.001, 0.2      # :1564-1566
 import os as _os
-LAZY_MODE = int(_os.environ.get("CGS_LAZY_MODE", "2"))   # tuning knob: 0 gather all, 1 defer feat, 2 defer feat+scaling+offsets
 FUSED_TRAINING = True      # fused HIP stages for the training path (tests flip it to compare with the torch composition)
-HYPER_BLOCKS = _os.environ.get("CGS_HYPER_BLOCKS", "1") != "0"   # the noisy hyper latents leave their node one block per level
 ROW_SOURCE = _os.environ.get("CGS_ROW_SOURCE", "1") != "0"      # A/B knob: 0 = gather into coding order first
 RATE_SIDE = _os.environ.get("CGS_RATE_SIDE", "1") != "0"        # A/B knob: 0 = rate gradients through autograd (dense buffers + adds)
 LEVEL_FUSED = _os.environ.get("CGS_LEVEL_FUSED", "1") != "0"    # A/B knob: 0 = round 4's rowcat -> mlp2 -> noise_quant launches per level
@@ -709,7 +707,7 @@ def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
         hyp_p, likelihood_hyper = pc.latent_codec.training_step_forms(
             hyper, None if c.get("identity") else perm, None if c.get("identity") else c["inv_perm"], c["_nz"],
             pre[2] if pre is not None else _ctx.next_seed(), packed=begun.get("packed") if begun is not None else None,
-            noisy=pre[1] if pre is not None else None, sizes=sizes if (HYPER_BLOCKS and len(sizes) <= 4) else None,
+            noisy=pre[1] if pre is not None else None, sizes=sizes if len(sizes) <= 4 else None,
             rows_orig=chosen_rows)
         hyper_feat = None
     elif FUSED_TRAINING and training and keep_stats and choose_mask is not None and hyper.is_cuda and eb_mine:
@@ -736,6 +734,21 @@ def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
         and all(sizes[j_] == 0 or (_mlp.supported(pc.get_grid_mlp[i_])
                                    and _ctx.level_fused_supported(pc.get_grid_mlp[i_], anchor, hyp_l[j_], row_src))
                 for j_, (i_, _t, _o, _a2) in enumerate(c["plan"])))
+    def level_record(j, i, orig, loc, outs, Q_all, side, **extra):
+        """What rate_model reads of level j when its element-wise stages ran fused (keep_stats)."""
+        # chosen_rows lists the chosen anchors level by level: this level's are [lo, lo + len(loc))
+        span = None
+        if chosen_rows is not None:
+            lo_ = sum(int(l_.shape[0]) for l_ in locs[:j])
+            span = (chosen_rows, lo_, lo_ + int(loc.shape[0]))
+        sm = c.get("_sub_map")
+        lvl0 = sum(sizes[:j])
+        # `rows` (original indices of the chosen anchors) is only read when the subset is not listed level by level (span None):
+        # otherwise the mask rows come from ONE gather over all levels' chosen anchors
+        return dict(level=i, orig=orig, rows=orig[loc] if span is None else None, loc=loc, n_level=sizes[j], fused=True,
+                    yf=outs[0], ys=outs[1], yo=outs[2], Q=Q_all, chosen=span, side=side, side_src=row_src,
+                    sub_map=sm[lvl0:lvl0 + sizes[j]] if (sm is not None and span is not None) else None, **extra)
+
     for j, (i, _tc, orig, _a) in enumerate(c["plan"]):
         n_l = sizes[j]
         if n_l > 0:
@@ -764,16 +777,7 @@ def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
                     (Q_FEAT0, Q_SCALING0, Q_OFFSETS0), seed=seed_j, rate_lazy=rate_lazy and keep_stats, pre=pre_j)
                 row_off += n_l
                 if keep_stats:
-                    span = None
-                    if chosen_rows is not None:
-                        lo_ = sum(int(l_.shape[0]) for l_ in locs[:j])
-                        span = (chosen_rows, lo_, lo_ + int(loc.shape[0]))
-                    sm = c.get("_sub_map")
-                    lvl0 = sum(sizes[:j])
-                    levels.append(dict(level=i, orig=orig, rows=orig[loc] if span is None else None, loc=loc, n_level=n_l,
-                                       fused=True, yf=hf, ys=hs, yo=ho, Q=Q_all, chosen=span, side=side, side_src=row_src,
-                                       sub_map=sm[lvl0:lvl0 + n_l] if (sm is not None and span is not None) else None,
-                                       pred=pred_sub, lazy=rate_lazy))
+                    levels.append(level_record(j, i, orig, loc, (hf, hs, ho), Q_all, side, pred=pred_sub, lazy=rate_lazy))
                 feat_q.append(hf)
                 scal_q.append(hs)
                 off_q.append(ho)
@@ -830,20 +834,7 @@ def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
                                                          (Q_FEAT0, Q_SCALING0, Q_OFFSETS0), outs=outs)
                 row_off += n_l
                 if keep_stats:
-                    # chosen_rows lists the chosen anchors level by level: this level's are [lo, lo + len(loc))
-                    span = None
-                    if chosen_rows is not None:
-                        lo_ = sum(int(l_.shape[0]) for l_ in locs[:j])
-                        span = (chosen_rows, lo_, lo_ + int(loc.shape[0]))
-                    sm = c.get("_sub_map")
-                    lvl0 = sum(sizes[:j])
-                    # `rows` (original indices of the chosen anchors) is only read when the subset is not listed level by
-                    # level (span None): otherwise the mask rows come from ONE gather over all levels' chosen anchors
-                    levels.append(dict(level=i, orig=orig, rows=orig[loc] if span is None else None, loc=loc, n_level=n_l,
-                                       fused=True, yf=hf, ys=hs,
-                                       yo=ho, Q=Q_all, chosen=span, side=side, side_src=row_src,
-                                       sub_map=sm[lvl0:lvl0 + n_l] if (sm is not None and span is not None) else None,
-                                       pred=pred_sub))
+                    levels.append(level_record(j, i, orig, loc, (hf, hs, ho), Q_all, side, pred=pred_sub))
                 feat_q.append(hf)
                 scal_q.append(hs)
                 off_q.append(ho)
@@ -1190,10 +1181,8 @@ def multi_scale_generating_visible(pc, anchor, hyper, feat, grid_offsets, grid_s
         # (the renderer may have formed the rows already, for its early launch of the anchor MLPs: the same tensor is handed on)
         e_pos = begun.get("early_pos") if begun is not None else None
         pos = e_pos[1] if (e_pos is not None and e_pos[0] is vis_idx and e_pos[2] is c) else _index_rows(c["inv_perm"], vis_idx)
-        lazy = defer_feat and feat_p.is_cuda and feat_p.dtype == torch.float32 and LAZY_MODE > 0
-        if lazy and LAZY_MODE == 1:
-            outs = (LazyRows(feat_p, pos), gather_unique(scal_p, pos), gather_unique(off_p, pos))
-        elif lazy:      # the consumers (MLP-input assembly, expansion kernels) gather the rows themselves
+        lazy = defer_feat and feat_p.is_cuda and feat_p.dtype == torch.float32
+        if lazy:        # the consumers (MLP-input assembly, expansion kernels) gather the rows themselves
             outs = (LazyRows(feat_p, pos), LazyRows(scal_p, pos), LazyRows(off_p, pos))
         else:
             outs = tuple(gather_unique(t, pos) for t in (feat_p, scal_p, off_p))
