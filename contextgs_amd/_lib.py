@@ -77,7 +77,11 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                                         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
                                        [c_void_p, c_size_t, c_void_p, C.c_uint32]),
-    "cgs_filter_cov": (c_int, [C.POINTER(RasterCfg), c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cgs_raster_camera_bytes": (c_size_t, [c_int64]),
+    "cgs_raster_camera_backward": (c_int, [C.POINTER(RasterCfg), c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, C.c_uint32,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cgs_filter_cov": (c_int,[C.POINTER(RasterCfg), c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cgs_raster_preprocess_wait": (c_int, [C.c_uint64, C.POINTER(c_int64)]),
     "cgs_raster_preprocess_wait2": (c_int, [C.c_uint64, C.POINTER(c_int64), C.POINTER(c_int)]),
     "cgs_debug_set_depth_keys_full": (c_int, [c_int]),

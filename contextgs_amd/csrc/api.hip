@@ -792,6 +792,84 @@ extern "C" int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P, int
                                     (opts & CGS_RASTER_ANTIALIAS) != 0);
 }
 
+// ---- camera gradients (csrc/raster_camera.hip) ---------------------------------------------------------------------------
+size_t cgs_camera_work_bytes(int64_t P);
+int cgs_launch_camera_bwd(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForms &f, const float *means3D, const float *opacities,
+                          const float *scales, const float *rotations, const int32_t *radii, const float *d_mean_px,
+                          const float *d_conic, const float *d_z, const float *dL_dcolors, const float *d_opacities, bool aa,
+                          float *out_view, float *out_proj, float *out_campos, void *work, hipStream_t stream);
+
+extern "C" size_t cgs_raster_camera_bytes(int64_t P) { return cgs_camera_work_bytes(P); }
+
+extern "C" int cgs_raster_camera_backward(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *shs,
+                                          int32_t sh_degree, int32_t sh_coeffs, const float *opacities, const float *scales,
+                                          const float *rotations, const float *cov3D, const int32_t *radii, const void *scratch,
+                                          size_t scratch_bytes, const float *dL_dcolors, const float *dL_dopacities, uint32_t opts,
+                                          float *dL_dviewmatrix, float *dL_dprojmatrix, float *dL_dcampos, void *work,
+                                          size_t work_bytes, void *stream_) {
+    const char *fn = "cgs_raster_camera_backward";
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (P < 0 || P >= (1ll << 31)) { cgs_set_error("%s: P out of range", fn); return CGS_ERR_ARG; }
+    if (opts & ~(uint32_t)(CGS_RASTER_ANTIALIAS | CGS_RASTER_CAMERA_MAPS)) {
+        cgs_set_error("%s: unknown option bits 0x%x (known: CGS_RASTER_ANTIALIAS = 0x%x, CGS_RASTER_CAMERA_MAPS = 0x%x)", fn,
+                      opts & ~(uint32_t)(CGS_RASTER_ANTIALIAS | CGS_RASTER_CAMERA_MAPS), (uint32_t)CGS_RASTER_ANTIALIAS,
+                      (uint32_t)CGS_RASTER_CAMERA_MAPS);
+        return CGS_ERR_ARG;
+    }
+    if (CGS_BLEND_BWD_RAW) {      // (experiment builds: the scratch holds the blend backward's raw sums, which this kernel does not finish)
+        cgs_set_error("%s: not available with CGS_BLEND_BWD_RAW", fn);
+        return CGS_ERR_ARG;
+    }
+    const bool aa = (opts & CGS_RASTER_ANTIALIAS) != 0, maps = (opts & CGS_RASTER_CAMERA_MAPS) != 0;
+    if (!dL_dviewmatrix && !dL_dprojmatrix && !dL_dcampos) { cgs_set_error("%s: no output given", fn); return CGS_ERR_ARG; }
+    if (dL_dcampos && ((P > 0 && !shs) || !cfg->campos)) {
+        cgs_set_error("%s: dL_dcampos needs shs and cfg->campos (the camera position enters through the SH direction only)", fn);
+        return CGS_ERR_ARG;
+    }
+    if (!work || work_bytes < cgs_camera_work_bytes(P)) {
+        cgs_set_error("%s: work missing or too small: %zu < %zu", fn, work ? work_bytes : (size_t)0, cgs_camera_work_bytes(P));
+        return CGS_ERR_ARG;
+    }
+    CgsRasterForms f = {nullptr, 0, 0, 0, cov3D};
+    if (dL_dcampos) {
+        if (sh_degree < 0 || sh_degree > 3) { cgs_set_error("%s: sh_degree %d outside 0..3", fn, sh_degree); return CGS_ERR_ARG; }
+        if (sh_coeffs > 16 || sh_coeffs < (sh_degree + 1) * (sh_degree + 1)) {
+            cgs_set_error("%s: %d SH coefficients per Gaussian: degree %d needs %d..16", fn, sh_coeffs, sh_degree,
+                          (sh_degree + 1) * (sh_degree + 1));
+            return CGS_ERR_ARG;
+        }
+        f.shs = shs;
+        f.sh_degree = sh_degree;
+        f.sh_coeffs = sh_coeffs;
+        f.sh_vec = sh_coeffs % 4 == 0 && ((uintptr_t)shs & 15u) == 0;
+    }
+    if (P > 0) {
+        if ((scales != nullptr || rotations != nullptr) == (cov3D != nullptr) || (!cov3D && (!scales || !rotations))) {
+            cgs_set_error("%s: please provide exactly one of either scale/rotation pair or precomputed 3D covariance", fn);
+            return CGS_ERR_ARG;
+        }
+        if (!means3D || !radii || !scratch || (dL_dcampos && !dL_dcolors) || (aa && (!opacities || !dL_dopacities))) {
+            cgs_set_error("%s: NULL input", fn);
+            return CGS_ERR_ARG;
+        }
+        const size_t need = maps ? cgs_raster_bwd_aux_scratch_bytes(P) : cgs_raster_bwd_scratch_bytes(P);
+        if (scratch_bytes < need) { cgs_set_error("%s: scratch too small: %zu < %zu", fn, scratch_bytes, need); return CGS_ERR_ARG; }
+    }
+    if (P == 0) {       // no Gaussian: zeros
+        if (dL_dviewmatrix) CGS_CHECK_HIP(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), stream));
+        if (dL_dprojmatrix) CGS_CHECK_HIP(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float), stream));
+        if (dL_dcampos) CGS_CHECK_HIP(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float), stream));
+        return CGS_OK;
+    }
+    const float *d_mean_px = (const float *)scratch;
+    const float *d_conic = (const float *)((const char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
+    const float *d_z = maps ? (const float *)((const char *)scratch + cgs_raster_bwd_scratch_bytes(P)) : nullptr;
+    return cgs_launch_camera_bwd(cfg, P, f, means3D, opacities, scales, rotations, radii, d_mean_px, d_conic, d_z, dL_dcolors,
+                                 dL_dopacities, aa, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, work, stream);
+}
+
 extern "C" int cgs_raster_stats(const cgs_raster_cfg *cfg, void *img_ws, size_t img_bytes, int64_t *stats_out,
                                 void *stream) {
     int rc = check_cfg(cfg);

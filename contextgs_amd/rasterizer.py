@@ -50,6 +50,24 @@ Conic, radii and visible_filter are those of a call without it.  Gradients: opac
 gradient reaches means3D and scales / rotations or cov3D_precomp (not means2D, shs or colors_precomp).  All four argument
 forms, with and without return_aux, pass CGS_RASTER_ANTIALIAS to cgs_raster_preprocess_launch_opt / cgs_raster_backward_opt;
 with antialiasing=False exactly the code above runs.
+
+The camera is differentiable too (csrc/raster_camera.hip, cgs_raster_camera_backward): when `raster_settings.viewmatrix`,
+`.projmatrix` or `.campos` requires a gradient, the node returns dL/dviewmatrix [4,4], dL/dprojmatrix [4,4] and dL/dcampos [3]
+in the tensors' logical shape (a transposed view, as scene/cameras.py builds them, receives its own layout through autograd).
+The rasterizer reads the three tensors independently and each gets the gradient of exactly its uses, summed over all Gaussians
+(row-vector convention, V[c][i]):
+
+  viewmatrix V: t = [p,1] V (the Jacobian J of the projection, the depth z = t_z of the maps and of the sort) and W = V[:3,:3]
+                in cov2D = J W Sigma W^T J^T (with antialiasing also h)
+  projmatrix PM: the pixel mean only, (hx, hy, hw) = [p,1] PM[:, (0,1,3)], ndc = h / (hw + 1e-7)
+  campos: the SH direction means3D - campos only (forms with shs; without shs it is unused and gets None)
+
+so a caller who builds PM = V P and campos = inv(V)[3,:3] in torch gets the pose gradient from autograd
+(contextgs_amd/camera_pose.py).  V[:,3] and PM[:,2] are never read: exactly 0.  Not differentiable, as for the per-Gaussian
+inputs: near-plane culling, radii and tile rectangles, the alpha >= 1/255 skip, the 0.99 cap, the T < 1e-4 stop, and t_x, t_y where
+the 1.3 tanfov clamp of the Jacobian is active (zero, as for means3D).  The kernel runs behind the backward above, only when one
+of the three asks; a call in which none does enqueues exactly what it did before.  No float atomics: at a fixed scratch the
+three gradients are bit-reproducible.
 """
 from __future__ import annotations
 
@@ -222,6 +240,7 @@ def check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, sh_degree
 
 
 CGS_RASTER_ANTIALIAS = 1      # include/cgs.h: the option bit of the *_opt entry points
+CGS_RASTER_CAMERA_MAPS = 2    # include/cgs.h, cgs_raster_camera_backward: the scratch is that of cgs_raster_backward_opt (dL/dz)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -234,7 +253,10 @@ class _RasterizeGaussians(torch.autograd.Function):
     per-Gaussian kernel turns the blends' dL/d(opacity * h) into dL/d(opacity) and chains h's gradient to the covariance."""
 
     @staticmethod
-    def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings):
+    def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings,
+                viewmatrix, projmatrix, campos):
+        # viewmatrix / projmatrix / campos: the settings' three camera tensors once more, as inputs of the node so that autograd
+        # can hand them a gradient; the forward reads them through _Cfg as before
         L = _lib.lib()
         _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D)
         means3D, shs, colors, opac, scales, rots, cov = (
@@ -282,7 +304,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         dev = means3D.device
         g, *maps = (None if t is None else _f32c(t) for t in (grad_color, *grad_maps, None, None, None)[:4])
         if g is None and all(t is None for t in maps):
-            return (None,) * 10
+            return (None,) * 13
         # the blends accumulate dL/dcolor (read by the SH backward) and dL/dopacity atomically: one zero fill for both; the
         # other arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones)
         acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
@@ -300,23 +322,47 @@ class _RasterizeGaussians(torch.autograd.Function):
                  _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov))
         stream = _lib.current_stream()
         if ctx.opts or any(t is not None for t in maps):
+            cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS
             scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
             _lib.check(L.cgs_raster_backward_opt(*inputs, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), *grads,
                                                  _lib.ptr(scratch), scratch.numel(), stream, ctx.opts),
                        "cgs_raster_backward_opt")
         else:       # the colour image alone, no antialiasing (cgs_raster_backward for the form the reference trains with)
+            cam_opts = 0
             scratch = _workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
             _lib.check(L.cgs_raster_backward_ex(*inputs, *grads, _lib.ptr(scratch), scratch.numel(), stream),
                        "cgs_raster_backward_ex")
+        # the camera: only when one of its tensors asks (campos without shs is unused: None), behind the backward above while
+        # its scratch and its dL_dcolors / dL_dopacities are intact
+        need_v, need_p, need_c = ctx.needs_input_grad[10:13]
+        need_c = need_c and shs is not None
+        d_view = d_proj = d_campos = None
+        if need_v or need_p or need_c:
+            cam = torch.empty(35, dtype=torch.float32, device=dev)
+            d_view = cam[:16].view(4, 4) if need_v else None
+            d_proj = cam[16:32].view(4, 4) if need_p else None
+            d_campos = cam[32:] if need_c else None
+            work = _workspace(L.cgs_raster_camera_bytes(P), dev)
+            _lib.check(L.cgs_raster_camera_backward(
+                cfg.ref, P, _lib.ptr(means3D), _lib.ptr(shs) if need_c else None, ctx.D, ctx.M, _lib.ptr(opac), _lib.ptr(scales),
+                _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(scratch), scratch.numel(), _lib.ptr(d_colors),
+                _lib.ptr(d_opac), cam_opts, _lib.ptr(d_view), _lib.ptr(d_proj),
+                _lib.ptr(d_campos), _lib.ptr(work), work.numel(), stream), "cgs_raster_camera_backward")
         if g is None:       # the maps send no gradient to the colour inputs
             d_shs = d_colors = None
         return (None, d_means3D, d_means2D, d_shs, d_colors if colors is not None else None, d_opac, d_scales, d_rots,
-                d_cov, None)
+                d_cov, None, d_view, d_proj, d_campos)
+
+
+def _camera_inputs(rs):
+    """The settings' camera tensors as inputs of the node, in their own layout (a transposed view stays one: autograd hands
+    its base the transposed gradient).  A tensor that requires no gradient is passed all the same; it costs nothing."""
+    return rs.viewmatrix, rs.projmatrix, rs.campos
 
 
 def rasterize_gaussians(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings):
     return _RasterizeGaussians.apply(False, means3D, means2D, None, colors_precomp, opacities, scales, rotations, None,
-                                     raster_settings)
+                                     raster_settings, *_camera_inputs(raster_settings))
 
 
 def raster_stats(raster_settings: GaussianRasterizationSettings, img_ws: torch.Tensor) -> torch.Tensor:
@@ -365,7 +411,7 @@ class GaussianRasterizer(nn.Module):
         each (see the module docstring)."""
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
         out = _RasterizeGaussians.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                        cov3D_precomp, self.raster_settings)
+                                        cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings))
         if not return_aux:
             return out
         color, radii, depth, invdepth, alpha = out

@@ -573,23 +573,47 @@ def _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier):
         antialiasing=bool(getattr(pipe, "antialiasing", False)))
 
 
+class _DetachedCamera:
+    """A camera as the Gaussian generation sees it when its pose is being trained: every attribute of the wrapped camera, the
+    three pose tensors detached (render()'s docstring: the anchor MLPs' input is not differentiated with respect to the camera)."""
+
+    def __init__(self, camera):
+        self._camera = camera
+        self.world_view_transform = camera.world_view_transform.detach()
+        self.full_proj_transform = camera.full_proj_transform.detach()
+        self.camera_center = camera.camera_center.detach()
+
+    def __getattr__(self, name):
+        return getattr(self._camera, name)
+
+
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False,
            step=0, *, return_aux=False):                                                # :155-229
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
 
     return_aux=True: the dict also holds the rasterizer's "depth", "invdepth" and "alpha" maps ([1,H,W] each, see
     contextgs_amd/rasterizer.py).  In training mode such a call takes the unfused path (the one CGS_FUSE_VIEW=0 takes), and so
-    does one with `pipe.antialiasing` set (upstream's --antialiasing, see contextgs_amd/rasterizer.py)."""
+    does one with `pipe.antialiasing` set (upstream's --antialiasing, see contextgs_amd/rasterizer.py).
+
+    A camera whose `world_view_transform`, `full_proj_transform` or `camera_center` requires a gradient (a trainable pose,
+    contextgs_amd/camera_pose.py) takes the unfused path too, in training and in eval mode, and the gradient reaches the three
+    tensors through the rasterizer (rasterizer.py: the projection, the covariance chain, the depth of the maps).  Not
+    differentiated with respect to the camera: the anchor MLPs' input (anchor - camera_center), which is evaluated on the
+    detached position, and the fused expand + raster node, which such a call never takes."""
     is_training = pc.get_color_mlp.training
     view = None
+    cam_grad = torch.is_grad_enabled() and any(
+        isinstance(t, torch.Tensor) and t.requires_grad for t in (
+            viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center))
+    gen_camera = _DetachedCamera(viewpoint_camera) if cam_grad else viewpoint_camera
     if is_training:
         # the expansion may run fused with the rasterizer's per-Gaussian stages (then `view.done` holds the rendered view
         # and xyz / color / opacity / rot are None: they never existed as tensors)
         view = ViewFusion(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier), retain_grad)
         (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, bit_per_anchor_param,
          bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level) = \
-            generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=True, step=step,
-                                      _view=None if (return_aux or view.raster_settings.antialiasing) else view)
+            generate_neural_gaussians(gen_camera, pc, visible_mask, is_training=True, step=step,
+                                      _view=None if (return_aux or view.raster_settings.antialiasing or cam_grad) else view)
         if view.done is not None:
             rendered_image, radii, screenspace_points = view.done
             return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
@@ -599,7 +623,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
                     "bit_per_offsets_param": bit_per_offsets_param, "bpp_per_level": bpp_per_level}
     else:
         xyz, color, opacity, scaling, rot, time_sub = generate_neural_gaussians(
-            viewpoint_camera, pc, visible_mask, is_training=False, step=step)
+            gen_camera, pc, visible_mask, is_training=False, step=step)
 
     screenspace_points = _zero_points(xyz)       # :168 `torch.zeros_like(xyz, requires_grad=True) + 0`
     if retain_grad:

@@ -306,6 +306,42 @@ int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P,
                             float *dL_dcov3D, void *scratch,
                             size_t scratch_bytes, void *stream, uint32_t opts);
 
+/* ---- gradients for the camera: viewmatrix, projmatrix, campos (csrc/raster_camera.hip) ----
+ * The rasterizer reads the three tensors of cgs_raster_cfg independently (row-vector convention, M[4c+i] = row c, column i):
+ *   viewmatrix V: the view-space position t = [p,1] V (the Jacobian of the projection, its 1.3 tanfov clamp, the depth
+ *                 z = t_z of the maps) and W = V[:3,:3] in cov2D = J W Sigma W^T J^T (with antialiasing also h);
+ *   projmatrix PM: the pixel mean only, (hx, hy, hw) = [p,1] PM[:, (0,1,3)], ndc = h / (hw + 1e-7);
+ *   campos: the SH direction means3D - campos only.
+ * cgs_raster_camera_backward returns dL/dV [16], dL/dPM [16], dL/dcampos [3] as the gradients of exactly these uses, each
+ * tensor an independent input, summed over all Gaussians with radii > 0.  A caller who builds PM = V P and campos =
+ * inv(V)[3,:3] chains them itself.  Entries never read (V[:,3], PM[:,2]) get exactly 0.  Not differentiated, as for the
+ * per-Gaussian inputs: near-plane culling, radii and tile rectangles, the alpha >= 1/255 skip, the 0.99 cap, the T < 1e-4 stop,
+ * and t_x, t_y where the 1.3 tanfov clamp is active (zero, as for means3D).
+ *
+ * Call it on the same stream right after the cgs_raster_backward / _ex / _aux / _opt of the view, with that call's inputs and
+ * outputs intact: scratch is the backward's scratch (it holds dL/d(pixel mean), dL/d(conic) and, for _aux / _opt, dL/dz),
+ * dL_dcolors [P,3] its colour gradient (read only with dL_dcampos), dL_dopacities [P] its opacity gradient (read only with
+ * CGS_RASTER_ANTIALIAS, together with opacities [P]: dL/d(opacity h) is taken back out of dL/d(opacity) with the recomputed h).
+ * opts: CGS_RASTER_ANTIALIAS as the backward had it; CGS_RASTER_CAMERA_MAPS when the backward was _aux / _opt (scratch of
+ * cgs_raster_bwd_aux_scratch_bytes(P) bytes; its dL/dz joins dL/dt_z).  Any of the three outputs may be NULL, not all;
+ * dL_dcampos needs shs (without SH colours the camera position is unused).  work: cgs_raster_camera_bytes(P) bytes, any
+ * contents (per-workgroup partial sums + an arrival ticket).  No float atomics: at fixed inputs the result is bit-reproducible.
+ * P == 0 gives zeros.  Argument errors (missing pointer, unknown option bit, short scratch or work, dL_dcampos without shs)
+ * return CGS_ERR_ARG before anything is enqueued.  Not available in CGS_BLEND_BWD_RAW builds. */
+#define CGS_RASTER_CAMERA_MAPS 2u
+size_t cgs_raster_camera_bytes(int64_t P);
+int cgs_raster_camera_backward(const cgs_raster_cfg *cfg, int64_t P,
+                               const float *means3D, const float *shs,
+                               int32_t sh_degree, int32_t sh_coeffs,
+                               const float *opacities, const float *scales,
+                               const float *rotations, const float *cov3D,
+                               const int32_t *radii, const void *scratch,
+                               size_t scratch_bytes, const float *dL_dcolors,
+                               const float *dL_dopacities, uint32_t opts,
+                               float *dL_dviewmatrix, float *dL_dprojmatrix,
+                               float *dL_dcampos, void *work, size_t work_bytes,
+                               void *stream);
+
 /* ---- the anchor expansion fused with the rasterizer's preprocess stage (csrc/expand_raster.hip) ----
  * Training path of render(): gaussian_renderer/__init__.py:130-145 (generate_neural_gaussians' tail) feeding :179-205.
  * cgs_raster_preprocess_expand_launch = cgs_raster_preprocess_launch whose Gaussians are the surviving slots of
