@@ -609,7 +609,7 @@ extern "C" int cgs_raster_backward(const cgs_raster_cfg *cfg, int64_t P, int64_t
                                     img_bytes, dL_dout, dL_dcolors, dL_dopacities, scratch, scratch_bytes, g, d_mean_px, d_conic,
                                     stream)))
         return rc;
-    return cgs_launch_preprocess_bwd(cfg, P, CGS_BLEND_BWD_RAW ? (const float4 *)g.rec : nullptr, means3D, scales, rotations, radii,
+    return cgs_launch_preprocess_bwd(cfg, P, means3D, scales, rotations, radii,
                                      d_mean_px, d_conic, dL_dmeans3D, dL_dmeans2D, dL_dscales, dL_drotations, stream);
 }
 
@@ -706,10 +706,6 @@ static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, i
     int rc = check_cfg(cfg);
     if (rc) return rc;
     if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
-    if (CGS_BLEND_BWD_RAW) {      // (experiment builds: the colour blend backward leaves raw sums the aux pass does not add to)
-        cgs_set_error("%s: not available with CGS_BLEND_BWD_RAW", fn);
-        return CGS_ERR_ARG;
-    }
     CgsRasterForms f;
     if ((rc = check_forms(fn, cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
         return rc;
@@ -750,7 +746,7 @@ static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, i
     const float *aa_op = aa ? opacities : nullptr;
     float *aa_dop = aa ? dL_dopacities : nullptr;
     if (!shs && !cov3D)
-        rc = cgs_launch_preprocess_bwd(cfg, P, nullptr, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dmeans3D,
+        rc = cgs_launch_preprocess_bwd(cfg, P, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dmeans3D,
                                        dL_dmeans2D, dL_dscales, dL_drotations, stream, aa_op, aa_dop);
     else
         rc = cgs_launch_preprocess_bwd_form(cfg, P, f, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dcolors,
@@ -816,10 +812,6 @@ extern "C" int cgs_raster_camera_backward(const cgs_raster_cfg *cfg, int64_t P, 
         cgs_set_error("%s: unknown option bits 0x%x (known: CGS_RASTER_ANTIALIAS = 0x%x, CGS_RASTER_CAMERA_MAPS = 0x%x)", fn,
                       opts & ~(uint32_t)(CGS_RASTER_ANTIALIAS | CGS_RASTER_CAMERA_MAPS), (uint32_t)CGS_RASTER_ANTIALIAS,
                       (uint32_t)CGS_RASTER_CAMERA_MAPS);
-        return CGS_ERR_ARG;
-    }
-    if (CGS_BLEND_BWD_RAW) {      // (experiment builds: the scratch holds the blend backward's raw sums, which this kernel does not finish)
-        cgs_set_error("%s: not available with CGS_BLEND_BWD_RAW", fn);
         return CGS_ERR_ARG;
     }
     const bool aa = (opts & CGS_RASTER_ANTIALIAS) != 0, maps = (opts & CGS_RASTER_CAMERA_MAPS) != 0;

@@ -17,9 +17,6 @@
 
 // ------------------------------------------------------------------------------------------------------------
 #define RC_MAX_SRC 4
-#ifndef RC_LDS
-#define RC_LDS 1          // LDS-staged multi-source rowcat forward (tools/variant_lib.sh ... -DRC_LDS=0 for the A/B)
-#endif
 struct RowcatArgs {
     const float *src[RC_MAX_SRC];
     float *dsrc[RC_MAX_SRC];
@@ -256,7 +253,7 @@ extern "C" int cgs_rowcat_fwd_masked(int nsrc, const void *const *data, const in
         return CGS_OK;
     }
     // wide rows of several sources (the context rows of a level): staged through LDS; single narrow gathers: element-wise
-    if (RC_LDS && nsrc >= 2 && a.W >= 16 && a.W <= 256 && n >= 4 * RC_ROWS && !((uintptr_t)out & 15)) {
+    if (nsrc >= 2 && a.W >= 16 && a.W <= 256 && n >= 4 * RC_ROWS && !((uintptr_t)out & 15)) {
         unsigned pair_mask = 0;
         for (int s = 0; s < nsrc; ++s)
             if (!(a.width[s] & 1) && !(a.ld[s] & 1) && !((uintptr_t)a.src[s] & 7)) pair_mask |= 1u << s;
@@ -517,9 +514,6 @@ extern "C" int cgs_zero_unmarked_rows(const uint32_t *stamp, uint32_t gen, int64
 }
 
 // ------------------------------------------------------------------------------------------------------------
-#ifndef NQ_VEC2
-#define NQ_VEC2 1         // float2 forms of the noise_quant kernels (tools/variant_lib.sh ... -DNQ_VEC2=0 for the A/B)
-#endif
 // 16 lanes per row: a wave instruction touches 4 rows x 64 contiguous bytes of each tensor.
 // sums (may be NULL): double [3], += the sums of the SOURCE values read (features, scaling, offsets): the levels of a
 // step together read every row of the three parameter tensors exactly once, which makes these the numerators of the
@@ -719,7 +713,7 @@ extern "C" int cgs_noise_quant_fwd(const float *xf, const float *xs, const float
     if (n == 0) return CGS_OK;
     if (!xf || !xs || !xo || !qadj || !yf || !ys || !yo || !Q) { cgs_set_error("noise_quant_fwd: NULL"); return CGS_ERR_ARG; }
     CgsProfScope prof(CGS_PROF_CTX_FWD, (hipStream_t)stream);
-    if (NQ_VEC2 && nq_vec2_ok(D, S, O, {xf, xs, xo, yf, ys, yo}))
+    if (nq_vec2_ok(D, S, O, {xf, xs, xo, yf, ys, yo}))
         hipLaunchKernelGGL(noise_quant_fwd2_kernel, dim3(stream_grid(n * 16, 256 * 4)), dim3(256), 0, (hipStream_t)stream, xf, xs,
                            xo, qadj, rows, n, D, S, O, seed, q0f, q0s, q0o, yf, ys, yo, Q, sums3);
     else

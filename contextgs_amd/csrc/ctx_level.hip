@@ -106,7 +106,6 @@ __device__ __forceinline__ void cl_layer1(const float *__restrict__ W1t, const f
     for (int t = 0; t < CL_NT1; ++t) acc1[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // (the eight weights of group k + 1 are read before the seven MFMAs of group k are issued, behind scheduling fences: a read
     //  issued just in time leaves the matrix pipe of a one-wave-per-SIMD kernel idle for its round trip; same products, same order)
-#if CL_PIPE
     {
         const float *wp0 = W1t + ((4 * g) * 16 + c) * 8;
         f32x4 lo = *(const f32x4 *)wp0, hi = *(const f32x4 *)(wp0 + 4);
@@ -128,18 +127,6 @@ __device__ __forceinline__ void cl_layer1(const float *__restrict__ W1t, const f
                 lo = lon; hi = hin;
             }
     }
-#else
-#pragma unroll
-    for (int q = 0; q < ClShape<IN>::NTI; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (16 * q + j >= IN) continue;
-            const float *wp = W1t + ((16 * q + 4 * g + j) * 16 + c) * 8;
-            const f32x4 lo = *(const f32x4 *)wp, hi = *(const f32x4 *)(wp + 4);
-#pragma unroll
-            for (int t = 0; t < CL_NT1; ++t) acc1[t] = frag_mfma(t < 4 ? lo[t] : hi[t - 4], xb[q][j], acc1[t]);
-        }
-#endif
 #pragma unroll
     for (int t = 0; t < CL_NT1; ++t)
 #pragma unroll
@@ -198,19 +185,8 @@ __device__ __forceinline__ void cl_row_noise(ClRow &u, uint32_t kf, uint32_t ks,
 #ifndef CLF_WAVES
 #define CLF_WAVES 8               // waves per workgroup of the forward
 #endif
-#ifndef CLF_OCC
-#define CLF_OCC 0                 // > 0: force this many waves per SIMD (register budget) — tuning knob of tools/variant_lib.sh
-#endif
-#ifndef CLF_LDS_STORE
-#define CLF_LDS_STORE 1           // the forward's outputs (X, yf / ys / yo, Q: tile images contiguous in memory) leave through a per-wave LDS patch
-#endif
 #ifndef CLF_GRID
 #define CLF_GRID 2                // workgroups per CU in the forward's persistent grid
-#endif
-#if CLF_OCC > 0
-#define CLF_ATTR __attribute__((amdgpu_waves_per_eu(CLF_OCC, CLF_OCC)))
-#else
-#define CLF_ATTR
 #endif
 
 struct ClFwdArgs {
@@ -234,14 +210,15 @@ struct ClFwdArgs {
 struct ClfIdx { int64_t arow, ppos, srow; };
 
 template <int IN>
-__global__ void __launch_bounds__(CLF_WAVES * 64) CLF_ATTR ctxl_fwd_kernel(ClFwdArgs a) {
+__global__ void __launch_bounds__(CLF_WAVES * 64) ctxl_fwd_kernel(ClFwdArgs a) {
     constexpr int NTI = ClShape<IN>::NTI, XP = ClShape<IN>::XP;
     __shared__ __attribute__((aligned(16))) float W1s[CL_W1T(XP)];        // cl_stage_w1t
     __shared__ float b1s[CL_HP];
     __shared__ float W2qs[3 * CL_HP];
     __shared__ float b2qs[4];
     __shared__ double part[CLF_WAVES][3];
-    constexpr int PATCH = CLF_LDS_STORE ? (16 * IN > CL_ROW_PATCH ? 16 * IN : CL_ROW_PATCH) : 4;       // floats per wave
+    // the outputs (X, yf / ys / yo, Q: tile images contiguous in memory) leave through a per-wave LDS patch
+    constexpr int PATCH = 16 * IN > CL_ROW_PATCH ? 16 * IN : CL_ROW_PATCH;       // floats per wave
     static_assert(PATCH % 4 == 0, "16-byte aligned patches");
     __shared__ __attribute__((aligned(16))) float patches[CLF_WAVES * PATCH];
     const int tid = threadIdx.x, nthr = CLF_WAVES * 64;
@@ -288,7 +265,6 @@ __global__ void __launch_bounds__(CLF_WAVES * 64) CLF_ATTR ctxl_fwd_kernel(ClFwd
     }
     for (; tile < ntiles; tile += tstride) {
         const int64_t row = tile * 16 + c, rn = row + tstride * 16;
-        const bool valid = row < n;
         asm volatile("" ::: "memory");   // keep the LDS weight reads inside the tile loop (LICM would spill them)
         f32x4 xb[NTI];
         cl_gather_merge<IN>(gw, g, xb);
@@ -300,19 +276,12 @@ __global__ void __launch_bounds__(CLF_WAVES * 64) CLF_ATTR ctxl_fwd_kernel(ClFwd
         cl_row_issue(x, XB, (uint32_t)ix.srow, g, rn < n);
         ix = idx_issue(rn + tstride * 16);
         CLB_FENCE();
-#if CLF_LDS_STORE
         cl_xrow_store_tile<IN>(bX, patch, (uint32_t)(tile * 16), g, c, lane, xb);
-#else
-        cl_xrow_store<IN>(bX, (uint32_t)row * (IN * 4), g, valid, xb);
-#endif
         f32x4 acc1[CL_NT1];
         cl_layer1<IN>(W1s, b1s, xb, g, c, acc1);
         float qa[3];
         cl_qadj(W2qs, b2qs, acc1, g, qa);
         const float qf = ctx_step(a.q0f, qa[0]), qs = ctx_step(a.q0s, qa[1]), qo = ctx_step(a.q0o, qa[2]);
-#if !CLF_LDS_STORE
-        cl_s32(bQ, cl_sel(valid && g < 3, (uint32_t)row * 12 + (uint32_t)g * 4), g == 0 ? qf : (g == 1 ? qs : qo));
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i) pf += cl_sum4(xc.F[i]);
         ps += cl_sum4(xc.S);
@@ -329,11 +298,7 @@ __global__ void __launch_bounds__(CLF_WAVES * 64) CLF_ATTR ctxl_fwd_kernel(ClFwd
             xc.O[0][j] = xc.O[0][j] + u.O[0][j] * qo;
             xc.O[1][j] = xc.O[1][j] + u.O[1][j] * qo;
         }
-#if CLF_LDS_STORE
         cl_row_store_tile(xc, (f32x4){qf, qs, qo, 0.f}, YB, bQ, patch, (uint32_t)(tile * 16), g, c, lane);
-#else
-        cl_row_store(xc, YB, (uint32_t)row, g, valid);
-#endif
     }
     if (a.sums) {        // one atomic per block and quantity, spread over CTX_SUM_SLOTS cache lines
         const double sa = ctx_wave_sum((double)pf), sb = ctx_wave_sum((double)ps), sc = ctx_wave_sum((double)po);
@@ -553,7 +518,7 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
 #pragma unroll
         for (int t = 0; t < CL_NT1; ++t) {
             f32x4 hn = hn_next;
-            if (CL_PIPE && t + 1 < CL_NT1) {          // the next tile of H^T is in flight during this tile's products
+            if (t + 1 < CL_NT1) {          // the next tile of H^T is in flight during this tile's products
                 hn_next = clb_get(patches + (t + 1) * CLB_PATCH, g, c);
                 CLB_FENCE();
             }
@@ -569,7 +534,6 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
                 acc1[t][r] = acc1[t][r] > 0.f ? dz : 0.f;
             }
             clb_put(patches + t * CLB_PATCH, acc1[t], g, c);
-            if (!CL_PIPE && t + 1 < CL_NT1) hn_next = clb_get(patches + (t + 1) * CLB_PATCH, g, c);
         }
         // dX = W1^T dZ1 (+ the subset's mean / scale branch)
         f32x4 adx[NTI];
@@ -591,11 +555,11 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
                         w4n = *(const f32x4 *)(W1n4 + hcn * 4);
                         if (NTI > 4) w1n = W1n1[hcn];
                     }
-                    if (CL_PIPE) CLB_FENCE();
+                    CLB_FENCE();
 #pragma unroll
                     for (int v = 0; v < NTI && v < 4; ++v) adx[v] = frag_mfma(w4[v], acc1[t][r], adx[v]);
                     if (NTI > 4) adx[NTI - 1] = frag_mfma(w1, acc1[t][r], adx[NTI - 1]);
-                    if (CL_PIPE) CLB_FENCE();
+                    CLB_FENCE();
                     w4 = w4n; w1 = w1n;
                 }
         }
@@ -629,12 +593,12 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
         for (int t = 0; t < CL_NT1; ++t) {
             const f32x4 dn = dn_next;
             if (t + 1 < CL_NT1) dn_next = clb_get(patches + (t + 1) * CLB_PATCH, g, c);
-            if (CL_PIPE) CLB_FENCE();
+            CLB_FENCE();
 #pragma unroll
             for (int v = 0; v < NTI; ++v)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) aw1[t][v] = frag_mfma(dn[r], xn[v][r], aw1[t][v]);
-            if (CL_PIPE) CLB_FENCE();
+            CLB_FENCE();
         }
     }
     // ---- the workgroup's image [dW1 100 x IN | db1 100 | dW2q 3 x 100 | db2q 3]: the waves take turns (fixed order) ----

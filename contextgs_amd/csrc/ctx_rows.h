@@ -20,9 +20,6 @@ struct ClShape {
 };
 
 // no IR-level motion of the loads (memory clobber) and no machine-scheduler motion (sched_barrier) across
-#ifndef CL_PIPE
-#define CL_PIPE 1             // LDS operands of the next MFMA group are read before the current group is issued
-#endif
 #define CL_FENCE() CLB_FENCE()
 #define CLB_FENCE()                        \
     do {                                   \

@@ -33,31 +33,15 @@
 #ifndef M3_FWD_RT
 #define M3_FWD_RT 1
 #define M3_FWD_WAVES 16
-#ifndef M3_FWD_LDS_STORE
-#define M3_FWD_LDS_STORE 1     // the forward's row-major outputs (Y_*, X_out) leave through a per-wave LDS patch as contiguous 1 KB stores
 #endif
-#ifndef M3W_ROUTER
-#define M3W_ROUTER 1          // fused backward: weight-gradient MFMAs of a group interleaved over its accumulators
-#endif
-#ifndef M3_TAILMAP
-#define M3_TAILMAP 1           // ROWS forward: inputs 48..53 in tail order (two MFMA k-steps instead of four per hidden tile)
-#endif
+// the forward's row-major outputs (Y_*, X_out) leave through a per-wave LDS patch as contiguous 1 KB stores (direct 64-byte
+// chunk stores lost, profiles/r06_mlp3_tiled.txt)
 #define M3_FWD_PATCH (16 * 70)  // floats per wave: the widest tile image (Y_cov)
-#endif
 #ifndef M3_BWD_RT
 #define M3_BWD_RT 2
 #define M3_BWD_WAVES 8
 #endif
 
-// M3_FUSED_WGRAD: the backward computes the weight gradients in the same launch (mlp3_bwd_wg_kernel); 0 = the round-3 pair
-// mlp3_bwd_kernel + wgrad_multi (kept for the data-only entry of the deferred weight-gradient mode and for A/B builds)
-#ifndef M3_FUSED_WGRAD
-#define M3_FUSED_WGRAD 1
-#endif
-// M3_PIPE: explicit register double-buffering of the LDS weight fragments in the forward kernel
-#ifndef M3_PIPE
-#define M3_PIPE 0
-#endif
 #define M3_FENCE()                         \
     do {                                   \
         asm volatile("" ::: "memory");     \
@@ -108,39 +92,6 @@ __device__ __forceinline__ void m3_head_fwd(const float *lds, const M3Head &h, i
     for (int t = 0; t < M3_NT1; ++t)
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) acc1[t][rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#if M3_PIPE
-    // A fragments of k-group q + 1 are read from LDS before the 16 MFMAs of group q are issued (two register
-    // buffers): the compiler's own schedule reads two values, waits for them and issues two MFMAs, i.e. an exposed LDS
-    // round trip per pair (profiles/r03_mlp_pipeline.txt)
-    float a1[2][4][M3_NT1];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int t = 0; t < M3_NT1; ++t) a1[0][j][t] = W1s[(4 * g + j) * L::S1 + 16 * t + c];
-    // input row of W1 for (q, j): 16 q + 4 g + j — in the last piece of a TM operand 48 + g + 4 j (m3_load_x_rows_b)
-    auto krow = [&](int q, int j) { return (TM && q == M3_NTI - 1) ? 16 * q + g + 4 * j : 16 * q + 4 * g + j; };
-#pragma unroll
-    for (int q = 0; q < M3_NTI; ++q) {
-        if (q + 1 < M3_NTI) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int t = 0; t < M3_NT1; ++t)
-                    a1[(q + 1) & 1][j][t] = W1s[krow(q + 1, j) * L::S1 + 16 * t + c];
-        }
-        M3_FENCE();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (16 * q + j >= M3_IN) continue;
-            if (TM && q == M3_NTI - 1 && 16 * q + 4 * j >= M3_IN) continue;          // tail order: inputs 48 + g + 4 j
-#pragma unroll
-            for (int t = 0; t < M3_NT1; ++t)
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) acc1[t][rt] = frag_mfma(a1[q & 1][j][t], xb[rt][q][j], acc1[t][rt]);
-        }
-        M3_FENCE();
-    }
-#else
 #pragma unroll
     for (int q = 0; q < M3_NTI; ++q)
 #pragma unroll
@@ -154,7 +105,6 @@ __device__ __forceinline__ void m3_head_fwd(const float *lds, const M3Head &h, i
                 for (int rt = 0; rt < RT; ++rt) acc1[t][rt] = frag_mfma(a, xb[rt][q][j], acc1[t][rt]);
             }
         }
-#endif
 #pragma unroll
     for (int t = 0; t < M3_NT1; ++t)
 #pragma unroll
@@ -173,34 +123,6 @@ __device__ __forceinline__ void m3_head_fwd(const float *lds, const M3Head &h, i
     for (int u = 0; u < L::NT2; ++u)
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) acc2[u][rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#if M3_PIPE
-    float a2[2][4][L::NT2];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int u = 0; u < L::NT2; ++u) a2[0][r][u] = W2s[(4 * g + r) * L::S2 + 16 * u + c];
-#pragma unroll
-    for (int t = 0; t < M3_NT1; ++t) {
-        if (t + 1 < M3_NT1) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (16 * (t + 1) + r >= M3_HID) continue;
-#pragma unroll
-                for (int u = 0; u < L::NT2; ++u) a2[(t + 1) & 1][r][u] = W2s[(16 * (t + 1) + 4 * g + r) * L::S2 + 16 * u + c];
-            }
-        }
-        M3_FENCE();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (16 * t + r >= M3_HID) continue;
-#pragma unroll
-            for (int u = 0; u < L::NT2; ++u)
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) acc2[u][rt] = frag_mfma(a2[t & 1][r][u], acc1[t][rt][r], acc2[u][rt]);
-        }
-        M3_FENCE();
-    }
-#else
 #pragma unroll
     for (int t = 0; t < M3_NT1; ++t)
 #pragma unroll
@@ -213,8 +135,6 @@ __device__ __forceinline__ void m3_head_fwd(const float *lds, const M3Head &h, i
                 for (int rt = 0; rt < RT; ++rt) acc2[u][rt] = frag_mfma(a, acc1[t][rt][r], acc2[u][rt]);
             }
         }
-#endif
-#if M3_FWD_LDS_STORE
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
         f32x4 yv[L::NT2];
@@ -224,18 +144,6 @@ __device__ __forceinline__ void m3_head_fwd(const float *lds, const M3Head &h, i
             for (int r = 0; r < 4; ++r) yv[u][r] = frag_act<ACT>(acc2[u][rt][r] + b2s[16 * u + 4 * g + r]);
         frag_tile_store<OUT, L::NT2>(patch, B.Y[head], (uint32_t)(row0 + rt * 16) * (OUT * 4), yv, g, c, 16 * g + c);
     }
-#else
-#pragma unroll
-    for (int u = 0; u < L::NT2; ++u)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            const int64_t row = row0 + rt * 16 + c;
-            f32x4 y;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) y[r] = frag_act<ACT>(acc2[u][rt][r] + b2s[16 * u + 4 * g + r]);
-            frag_bstore4<OUT>(B.Y[head], (uint32_t)row * (OUT * 4), u, g, valid[rt], y);
-        }
-#endif
 }
 
 // Input row assembled on the fly (ROWS variant): [ feat_src[src_row[r], 0:50] | (a - cam)/|a - cam| | |a - cam| ] with a =
@@ -289,10 +197,10 @@ __global__ void __launch_bounds__(WAVES * 64)
                     float *__restrict__ Hcat, int64_t n, M3Rows R) {
     constexpr int WFL = M3FwdLds<O0>::FLOATS + M3FwdLds<O1>::FLOATS + M3FwdLds<O2>::FLOATS;
     static_assert(WFL % 4 == 0 && O0 <= 70 && O1 <= 70 && O2 <= 70 && M3_IN <= 70, "patch: 16-byte aligned, the widest image fits");
-    __shared__ __attribute__((aligned(16))) float lds[WFL + (M3_FWD_LDS_STORE ? WAVES * M3_FWD_PATCH : 0)];
+    __shared__ __attribute__((aligned(16))) float lds[WFL + WAVES * M3_FWD_PATCH];
     float *l0 = lds, *l1 = l0 + M3FwdLds<O0>::FLOATS, *l2 = l1 + M3FwdLds<O1>::FLOATS;
     const int tid = threadIdx.x, nthr = WAVES * 64;
-    float *patch = lds + WFL + (M3_FWD_LDS_STORE ? (tid >> 6) * M3_FWD_PATCH : 0);
+    float *patch = lds + WFL + (tid >> 6) * M3_FWD_PATCH;
     m3_stage_fwd<O0>(l0, h0, tid, nthr);
     m3_stage_fwd<O1>(l1, h1, tid, nthr);
     m3_stage_fwd<O2>(l2, h2, tid, nthr);
@@ -327,7 +235,7 @@ __global__ void __launch_bounds__(WAVES * 64)
         srow_n[rt] = ROWS ? cl_li64(B.src, cl_sel(rown < n, (uint32_t)rown * 8)) : 0;
 #pragma unroll
         for (int q = 0; q < M3_NTI; ++q)
-            xb[rt][q] = ROWS ? m3_load_x_rows_b<M3_TAILMAP>(B, cam0, cam1, cam2, row, srow, q, g, valid[rt])
+            xb[rt][q] = ROWS ? m3_load_x_rows_b<true>(B, cam0, cam1, cam2, row, srow, q, g, valid[rt])
                              : frag_bmask4<M3_IN>(frag_bload4<M3_IN>(B.X, (uint32_t)row * ldx4, q, g, valid[rt]), q, g);
     }
     for (int64_t tile = tile0; tile < ntiles; tile += tstride) {
@@ -340,33 +248,23 @@ __global__ void __launch_bounds__(WAVES * 64)
             srow_nn[rt] = ROWS ? cl_li64(B.src, cl_sel(rownn < n, (uint32_t)rownn * 8)) : 0;
 #pragma unroll
             for (int q = 0; q < M3_NTI; ++q)
-                xn[rt][q] = ROWS ? m3_load_x_rows_b<M3_TAILMAP>(B, cam0, cam1, cam2, row, srow_n[rt], q, g, validn[rt])
+                xn[rt][q] = ROWS ? m3_load_x_rows_b<true>(B, cam0, cam1, cam2, row, srow_n[rt], q, g, validn[rt])
                                  : frag_bmask4<M3_IN>(frag_bload4<M3_IN>(B.X, (uint32_t)row * ldx4, q, g, validn[rt]), q, g);
         }
         if (ROWS) {
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
-#if M3_FWD_LDS_STORE
-                if (R.X_out) {
-                    if (M3_TAILMAP) {       // (the last piece is in tail order: values 48 + g and 52 + g of the row)
+                if (R.X_out) {              // (the last piece is in tail order: values 48 + g and 52 + g of the row)
 #pragma unroll
-                        for (int q = 0; q < M3_NTI - 1; ++q) cl_patch_put4(patch + c * M3_IN + 16 * q + 4 * g, xb[rt][q], 4);
-                        patch[c * M3_IN + 48 + g] = xb[rt][M3_NTI - 1][0];
-                        if (g < 2) patch[c * M3_IN + 52 + g] = xb[rt][M3_NTI - 1][1];
-                        cl_patch_flush<64 * M3_IN>(patch, B.Xo, (uint32_t)(row0 + rt * 16) * (M3_XLD * 4), lane);
-                    } else {
-                        frag_tile_store<M3_IN, M3_NTI>(patch, B.Xo, (uint32_t)(row0 + rt * 16) * (M3_XLD * 4), xb[rt], g, c, lane);
-                    }
+                    for (int q = 0; q < M3_NTI - 1; ++q) cl_patch_put4(patch + c * M3_IN + 16 * q + 4 * g, xb[rt][q], 4);
+                    patch[c * M3_IN + 48 + g] = xb[rt][M3_NTI - 1][0];
+                    if (g < 2) patch[c * M3_IN + 52 + g] = xb[rt][M3_NTI - 1][1];
+                    cl_patch_flush<64 * M3_IN>(patch, B.Xo, (uint32_t)(row0 + rt * 16) * (M3_XLD * 4), lane);
                 }
-#else
-#pragma unroll
-                for (int q = 0; q < M3_NTI; ++q)
-                    frag_bstore4<M3_IN>(B.Xo, (uint32_t)(row0 + rt * 16 + c) * (M3_XLD * 4), q, g, valid[rt], xb[rt][q]);
-#endif
         }
-        m3_head_fwd<O0, A0, RT, TILED, ROWS && M3_TAILMAP>(l0, h0, 0, xb, valid, row0, g, c, Hcat, B, patch);
-        m3_head_fwd<O1, A1, RT, TILED, ROWS && M3_TAILMAP>(l1, h1, 1, xb, valid, row0, g, c, Hcat, B, patch);
-        m3_head_fwd<O2, A2, RT, TILED, ROWS && M3_TAILMAP>(l2, h2, 2, xb, valid, row0, g, c, Hcat, B, patch);
+        m3_head_fwd<O0, A0, RT, TILED, ROWS>(l0, h0, 0, xb, valid, row0, g, c, Hcat, B, patch);
+        m3_head_fwd<O1, A1, RT, TILED, ROWS>(l1, h1, 1, xb, valid, row0, g, c, Hcat, B, patch);
+        m3_head_fwd<O2, A2, RT, TILED, ROWS>(l2, h2, 2, xb, valid, row0, g, c, Hcat, B, patch);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
             valid[rt] = validn[rt];
@@ -549,16 +447,7 @@ __global__ void __launch_bounds__(WAVES * 64)
 // At the end the waves of a workgroup add their tiles into one LDS image [dW | db] per product (wave by wave: a fixed order),
 // the image goes to scratch and cgs_launch_wgrad_reduce sums the workgroups' images in block order: bit-reproducible.
 #define M3W_LD 20
-#ifndef M3W_XPREFETCH
-#define M3W_XPREFETCH 1      // X of the next tile is fetched during the last head of this one
-#endif
 #define M3W_PATCH (16 * M3W_LD)
-#ifndef M3W_PREFETCH_AT
-#define M3W_PREFETCH_AT 2    // where in a head the next head's global operands are requested: 0 after the transposes are written, 1 after dH, 2 after dW2
-#endif
-#ifndef M3W_EARLY
-#define M3W_EARLY 0         // a loop's first LDS operands are requested one loop ahead
-#endif
 #define M3W_NPATCH 13          // per wave: H 0..3, dZ2 4..8, dZ1 9..12 (X uses 0..3 before the first head)
 #define M3W_WAVES 4
 #define M3W_E (M3_GLD * (M3_IN + 1) + (10 + 30 + 70) * (M3_HID + 1))
@@ -614,8 +503,8 @@ __device__ __forceinline__ f32x4 m3w_get(const float *patch, int g, int c) {
 
 // One head of one tile.  Order of issue (one wave per SIMD: nothing else hides a latency): the F -> N transposes of H and
 // dZ2 are written and read back BEFORE the dH products, those of dZ1 before the dW2 products, so every LDS round trip has
-// a block of MFMAs in front of its first use; `prefetch` (the next head's global loads) is issued after the first batch of
-// transposes.
+// a block of MFMAs in front of its first use; `prefetch` (the next head's global loads, and in the last head X of the next
+// tile) is issued after the dW2 products (after the transposes are written or after dH: more spills, HISTORY.md round 5).
 template <int OUT, int ACT, class Prefetch>
 __device__ __forceinline__ void m3w_head(const float *lds, float *patches, M3wOps<OUT, ACT> &op, f32x4 ones, int g, int c,
                                          const f32x4 (&xn)[M3_NTI], f32x4 (&adx)[M3_NTI],
@@ -637,10 +526,9 @@ __device__ __forceinline__ void m3w_head(const float *lds, float *patches, M3wOp
     for (int t = 0; t < M3_NT1; ++t) m3w_put(patches + t * M3W_PATCH, op.h[t], g, c);
 #pragma unroll
     for (int u = 0; u < L::NT2; ++u) m3w_put(patches + (4 + u) * M3W_PATCH, b[u], g, c);
-    if (M3W_PREFETCH_AT == 0) prefetch();
-    // (round 5) Every MFMA group's LDS operands are read one group ahead, behind scheduling fences, and each loop's FIRST
-    // operands one loop ahead (M3W_EARLY): with one wave per SIMD a read issued just in time leaves the matrix pipe idle for
-    // its whole round trip — 375 of the 616 MFMAs of a tile had an lgkmcnt wait right in front of them (1023 -> 880 us).
+    // (round 5) Every MFMA group's LDS operands are read one group ahead, behind scheduling fences: with one wave per SIMD a
+    // read issued just in time leaves the matrix pipe idle for its whole round trip — 375 of the 616 MFMAs of a tile had an
+    // lgkmcnt wait right in front of them (1023 -> 880 us).  Each loop's FIRST operands one loop ahead as well lost (17 spills).
     auto ldw2 = [&](int u, int j) {
         f32x4 w;
 #pragma unroll
@@ -659,11 +547,6 @@ __device__ __forceinline__ void m3w_head(const float *lds, float *patches, M3wOp
     for (int t = 0; t < M3_NT1; ++t) adh[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     {
         f32x4 wc = ldw2(0, 0);
-        if (M3W_EARLY) {                        // the N forms of H and of the first dZ2 tile: needed by the dW2 products
-#pragma unroll
-            for (int t = 0; t < M3_NT1; ++t) hn[t] = m3w_get(patches + t * M3W_PATCH, g, c);
-            zc = m3w_get(patches + 4 * M3W_PATCH, g, c);
-        }
 #pragma unroll
         for (int u = 0; u < L::NT2; ++u)
 #pragma unroll
@@ -679,7 +562,6 @@ __device__ __forceinline__ void m3w_head(const float *lds, float *patches, M3wOp
                 wc = wn;
             }
     }
-    if (M3W_PREFETCH_AT == 1) prefetch();
 #pragma unroll
     for (int t = 0; t < M3_NT1; ++t) {
 #pragma unroll
@@ -687,39 +569,26 @@ __device__ __forceinline__ void m3w_head(const float *lds, float *patches, M3wOp
         m3w_put(patches + (9 + t) * M3W_PATCH, adh[t], g, c);          // patches 9..12: dZ1
     }
     // dW2 += dZ2^T [H | 1] (row contraction, layout N)
-    if (!M3W_EARLY) {
 #pragma unroll
-        for (int t = 0; t < M3_NT1; ++t) hn[t] = m3w_get(patches + t * M3W_PATCH, g, c);
-        zc = m3w_get(patches + 4 * M3W_PATCH, g, c);
-    }
+    for (int t = 0; t < M3_NT1; ++t) hn[t] = m3w_get(patches + t * M3W_PATCH, g, c);
+    zc = m3w_get(patches + 4 * M3W_PATCH, g, c);
     if (c == M3_HID - 48) hn[3] = ones;                         // column 50 of [H | 1]
-    f32x4 wx, dc;
-    if (M3W_EARLY) {                            // first operands of the dX and dW1 loops, in flight during the dW2 products
-        wx = ldw1(0, 0);
-        dc = m3w_get(patches + 9 * M3W_PATCH, g, c);
-    }
 #pragma unroll
     for (int u = 0; u < L::NT2; ++u) {
         f32x4 zn = zc;
         if (u + 1 < L::NT2) zn = m3w_get(patches + (4 + u + 1) * M3W_PATCH, g, c);
         M3_FENCE();
-#if M3W_ROUTER      // r outermost: consecutive MFMAs go to DIFFERENT accumulators (same additions per accumulator, same order)
+        // r outermost: consecutive MFMAs go to DIFFERENT accumulators (same additions per accumulator, same order)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int t = 0; t < M3_NT1; ++t) aw2[u][t] = frag_mfma(zc[r], hn[t][r], aw2[u][t]);
-#else
-#pragma unroll
-        for (int t = 0; t < M3_NT1; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) aw2[u][t] = frag_mfma(zc[r], hn[t][r], aw2[u][t]);
-#endif
         M3_FENCE();
         zc = zn;
     }
-    if (M3W_PREFETCH_AT == 2) prefetch();
+    prefetch();
     // dX += W1^T dZ1
-    if (!M3W_EARLY) wx = ldw1(0, 0);
+    f32x4 wx = ldw1(0, 0);
 #pragma unroll
     for (int t = 0; t < M3_NT1; ++t)
 #pragma unroll
@@ -735,23 +604,16 @@ __device__ __forceinline__ void m3w_head(const float *lds, float *patches, M3wOp
             wx = wn;
         }
     // dW1 += dZ1^T [X | 1]
-    if (!M3W_EARLY) dc = m3w_get(patches + 9 * M3W_PATCH, g, c);
+    f32x4 dc = m3w_get(patches + 9 * M3W_PATCH, g, c);
 #pragma unroll
     for (int t = 0; t < M3_NT1; ++t) {
         f32x4 dn = dc;
         if (t + 1 < M3_NT1) dn = m3w_get(patches + (9 + t + 1) * M3W_PATCH, g, c);
         M3_FENCE();
-#if M3W_ROUTER
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int v = 0; v < M3_NTI; ++v) aw1[t][v] = frag_mfma(dc[r], xn[v][r], aw1[t][v]);
-#else
-#pragma unroll
-        for (int v = 0; v < M3_NTI; ++v)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) aw1[t][v] = frag_mfma(dc[r], xn[v][r], aw1[t][v]);
-#endif
         M3_FENCE();
         dc = dn;
     }
@@ -836,9 +698,6 @@ __global__ void __launch_bounds__(M3W_WAVES * 64) __attribute__((amdgpu_waves_pe
         for (int r = 0; r < 4; ++r) ones[r] = row0 + 4 * g + r < n ? 1.f : 0.f;
         // (ROWS) what the end of the tile needs from memory, issued here: the row's source index and its anchor
         const int64_t srow_pre = ROWS ? cl_li64(bSrc, cl_sel(valid, (uint32_t)(row0 + c) * 8)) : 0;
-#if !M3W_XPREFETCH
-        load_x(xf, row0 + c, srow_pre, valid);
-#endif
         if (regather) srow_next = cl_li64(bSrc, cl_sel(validn, (uint32_t)rown * 8));
         const f32x4 anc_pre = ROWS ? cl_l96(bAnc, cl_sel(valid && g == 0, (uint32_t)(row0 + c) * 12)) : zero;
 #pragma unroll
@@ -853,9 +712,7 @@ __global__ void __launch_bounds__(M3W_WAVES * 64) __attribute__((amdgpu_waves_pe
         m3w_head<30, 2>(l1, patches, op1, ones, g, c, xn, adx, a2_1, a1_1, [&]() { op2.template load<TL>(B, 2, row0 + c, g, valid); });
         m3w_head<70, 0>(l2, patches, op2, ones, g, c, xn, adx, a2_2, a1_2, [&]() {
             op0.template load<TL>(B, 0, rown, g, validn);
-#if M3W_XPREFETCH
             load_x(xf, rown, srow_next, validn);
-#endif
         });
         if (ROWS) {
             const int64_t row = row0 + c;
@@ -1124,7 +981,6 @@ static int m3_backward(const float *X, int64_t ldx, const float *const *W1, cons
     h[0] = M3Head{W1[0], nullptr, W2[0], nullptr, const_cast<float *>(Y_op), dY_op, dZ2_op};
     h[1] = M3Head{W1[1], nullptr, W2[1], nullptr, const_cast<float *>(Y_color), dY_color, dZ2_color};
     h[2] = M3Head{W1[2], nullptr, W2[2], nullptr, nullptr, dY_cov, nullptr};
-#if M3_FUSED_WGRAD
     // (the fused kernel addresses its operands through 32-bit byte offsets: beyond M3_MAX_ROWS rows the two-launch form runs)
     if (!data_only && n <= M3_MAX_ROWS && ldx <= 256) {
         // data AND weight gradients in one launch (mlp3_bwd_wg_kernel): dZ1cat / dZ2_* stay untouched
@@ -1153,7 +1009,7 @@ static int m3_backward(const float *X, int64_t ldx, const float *const *W1, cons
             return cgs_launch_wgrad_reduce((const float *)scratch, gridw, prods, 4, stream);
         }
     }
-#endif
+    // the round-3 pair mlp3_bwd_kernel + wgrad_multi: data-only entry of the deferred weight-gradient mode, > M3_MAX_ROWS rows, no scratch
     if (no_x) { cgs_set_error("anchor_mlp3_backward: X == NULL but the fused weight-gradient form could not run (scratch)"); return CGS_ERR_WORKSPACE; }
     if (tiled) {
         cgs_set_error("anchor_mlp3_backward: the tiled hand-over is read by the fused weight-gradient form only (needs the weight-gradient pointers, "

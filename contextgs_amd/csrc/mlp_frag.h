@@ -63,11 +63,8 @@ constexpr int frag_pad4mod8(int x) { int s = 4; while (s < x) s += 8; return s; 
 // (src row-major [COLS][ROWS], e.g. nn.Linear's weight [out][in] -> [in][out]), zeros in the padding.  The source is read in
 // ITS order — consecutive threads, consecutive addresses — and scattered into LDS; reading it in the destination's order is a
 // 4-byte gather with a row-length stride (64 cache lines per wave load).  Measured (round 4, same-box A/B of the headline
-// step, FRAG_STAGE_COALESCED=0 = the old loop): 129 vs 130-131 us per forward launch — the weights are L2-resident and the
-// gather was ~1 us of a launch, not the ~10 us it was suspected of.
-#ifndef FRAG_STAGE_COALESCED
-#define FRAG_STAGE_COALESCED 1
-#endif
+// step against that gather loop): 129 vs 130-131 us per forward launch — the weights are L2-resident and the gather was
+// ~1 us of a launch, not the ~10 us it was suspected of.
 // A staging loop  for (i = tid; i < n; i += nthr) put(i, ok(i) ? src[index(i)] : 0)  with EIGHT of a thread's loads in flight.
 // As a plain loop the compiler emits load -> s_waitcnt vmcnt(0) -> LDS store per round (it does not unroll a loop of unknown trip
 // count, and a predicated load sits behind an exec-mask branch whose join drains the load queue): one exposed round trip per
@@ -96,19 +93,12 @@ __device__ __forceinline__ void frag_stage_loop(const float *__restrict__ src, i
 
 template <int ROWS, int COLS, int RP, int S>
 __device__ __forceinline__ void frag_stage_transposed(float *__restrict__ dst, const float *__restrict__ src, int tid, int nthr) {
-#if FRAG_STAGE_COALESCED
     for (int i = tid; i < RP * S; i += nthr) {
         const int r = i / S, c = i % S;
         if (r >= ROWS || c >= COLS) dst[i] = 0.f;
     }
     frag_stage_loop(src, COLS * ROWS, tid, nthr, [](int i) { return i; },
                     [&](int i, float v) { const int c = i / ROWS, r = i % ROWS; dst[r * S + c] = v; });
-#else
-    for (int i = tid; i < RP * S; i += nthr) {
-        const int r = i / S, c = i % S;
-        dst[i] = (r < ROWS && c < COLS) ? src[c * ROWS + r] : 0.f;
-    }
-#endif
 }
 
 

@@ -272,9 +272,6 @@ int cgs_launch_wgrad2(const float *P, int64_t ldp, int DA, const float *Q, int64
 // group of Q) pair of every product is a task for one wave, all waves of a workgroup walk the same row range, so a
 // row's cache lines (e.g. the three 200-byte slices of an Hcat row) are pulled from HBM once, and 2-4 launches +
 // reductions become one of each.  Same inner loop and LDS-image / two-pass reduction as wgrad4_kernel.
-#ifndef WGM_NARROW
-#define WGM_NARROW 1         // one-tile tasks for <= 16-feature groups (tools/variant_lib.sh ... -DWGM_NARROW=0 for the A/B)
-#endif
 #define WGM_MAX_TASKS 16
 #define WGM_MAX_PROD 4
 #define WGM_MAX_E 25000      // floats of LDS image: 175x100+175 + 100x71+100 (both layers of mlp_grid) = 24875
@@ -542,16 +539,13 @@ static int launch_wgrad_tail(const CgsWgProduct &p, int64_t n, int num_cus, void
 int cgs_launch_wgrad_multi(const CgsWgProduct *prods, int nprod, int64_t n, int num_cus, void *scratch,
                            size_t scratch_bytes, hipStream_t s) {
     if (n <= 0 || nprod <= 0) return CGS_OK;
-#ifndef WG_NO_TAIL_KERNEL
     if (nprod == 1 && scratch && prods[0].DB > 64 && prods[0].DB <= 80 && prods[0].DA <= 128 && prods[0].db &&
         (size_t)(prods[0].DA * prods[0].DB + prods[0].DA) * sizeof(float) <= scratch_bytes)
         return launch_wgrad_tail(prods[0], n, num_cus, scratch, scratch_bytes, s);
-#endif
-    constexpr bool disabled = false;
     WgmArgs a;
     WgmProducts pr;
     int ntask = 0, E = 0;
-    bool fits = scratch != nullptr && nprod <= WGM_MAX_PROD && !disabled;
+    bool fits = scratch != nullptr && nprod <= WGM_MAX_PROD;
     for (int k = 0; k < nprod && fits; ++k) {
         const CgsWgProduct &p = prods[k];
         const int GA = (p.DA + 63) / 64, GB = (p.DB + 63) / 64;
@@ -559,7 +553,7 @@ int cgs_launch_wgrad_multi(const CgsWgProduct *prods, int nprod, int64_t n, int 
         for (int ga = 0; ga < GA && fits; ++ga)
             for (int gb = 0; gb < GB; ++gb) {
                 if (ntask >= WGM_MAX_TASKS) { fits = false; break; }
-                const int narrow = (WGM_NARROW && p.DA - 64 * ga <= 16 ? 1 : 0) | (WGM_NARROW && p.DB - 64 * gb <= 16 ? 2 : 0);
+                const int narrow = (p.DA - 64 * ga <= 16 ? 1 : 0) | (p.DB - 64 * gb <= 16 ? 2 : 0);        // one-tile tasks for <= 16-feature groups
                 a.t[ntask++] = WgmTask{p.P, p.Q, (int)p.ldp, (int)p.ldq, p.DA, p.DB, ga, gb, E, narrow};
             }
         E += p.DA * p.DB + p.DA;

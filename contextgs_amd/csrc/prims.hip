@@ -247,17 +247,7 @@ __device__ __forceinline__ uint32_t cgs_depth_key27(uint32_t k, uint32_t *overfl
 // the output (a tile's run starts where its predecessor's ends); with tile = workgroup id neighbours always sit on different
 // XCDs (workgroups go to the eight XCDs round robin) and every run is a partial-line write of its own, with the XCD-aware
 // assignment they share an L2 that merges them: three 9-bit passes 192 -> 172 us, four 8-bit passes 214 -> 208 us at 5.8 M keys
-// (tools/sort_micro.py, profiles/r06_depth_sort.txt).  SORT_XCD_MAP 0: tile = workgroup id.
-#ifndef SORT_XCD_MAP
-#define SORT_XCD_MAP 1
-#endif
-__device__ __forceinline__ int64_t sort_tile_of_block(int64_t nb) {
-#if SORT_XCD_MAP
-    return cgs_xcd_item(nb);
-#else
-    return (int64_t)blockIdx.x < nb ? (int64_t)blockIdx.x : -1;
-#endif
-}
+// (tools/sort_micro.py, profiles/r06_depth_sort.txt).
 static unsigned sort_grid(int64_t nb) { return cgs_xcd_grid(nb); }
 
 template <int BITS, bool XF>
@@ -266,7 +256,7 @@ __global__ void __launch_bounds__(SORT_THREADS)
                       int64_t n, int64_t nb, int shift, uint32_t digit_mask, uint32_t *overflow, uint32_t epoch) {
     constexpr int NR = 1 << BITS;
     __shared__ uint32_t h[NR];
-    const int64_t tile = sort_tile_of_block(nb);
+    const int64_t tile = cgs_xcd_item(nb);
     if (tile < 0) return;
     for (int d = threadIdx.x; d < NR; d += SORT_THREADS) h[d] = 0;
     __syncthreads();
@@ -343,7 +333,7 @@ __global__ void __launch_bounds__(SORT_THREADS)
                          int64_t n, int64_t nb, int shift, uint32_t digit_mask) {
     constexpr int NR = 1 << BITS;
     constexpr int DPT = NR / SORT_THREADS;         // digits per thread: thread t owns digits t * DPT .. t * DPT + DPT - 1
-    const int64_t tile = sort_tile_of_block(nb);
+    const int64_t tile = cgs_xcd_item(nb);
     if (tile < 0) return;
     // (16-bit counters and one global-minus-local base per digit: 38 KB of LDS per workgroup at 512 digits = four workgroups
     //  per CU; with 32-bit counters and separate bases it was 44 KB = three, and the pass 40 % slower than the 256-digit one)

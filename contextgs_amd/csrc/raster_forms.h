@@ -299,7 +299,7 @@ __device__ __forceinline__ void cgs_pre_fwd_form(int64_t i, const bool ok, const
     }
 }
 
-// ---- backward: the first half of cgs_pre_bwd_one (csrc/raster_pre.h, RAW = false) from a given covariance -------------
+// ---- backward: the first half of cgs_pre_bwd_one (csrc/raster_pre.h) from a given covariance -------------
 // Fills o.dp (projection + covariance paths of dL/dmeans3D) and o.dm2; M = dL/dSigma as the full symmetric matrix.
 // AA: o.dop and the h terms as in cgs_pre_bwd_one, with d0 from cgs_det2_comp as cgs_project_cov forms it.
 template <bool AA = false>

@@ -14,7 +14,6 @@
 #define PF_THREADS 256
 
 // the backward kernel takes dL/d(pixel mean) / dL/d(conic) as the blend backward finishes them (not its raw sums)
-static_assert(!CGS_BLEND_BWD_RAW, "preprocess_bwd_form_kernel has no RAW variant");
 
 // SHD: -1 = colours precomputed, 0..3 = SH of that degree.  COV6: covariance from cov6 instead of scales / rotations.
 template <bool FILTER_ONLY, int SHD, bool COV6>
@@ -133,8 +132,8 @@ __global__ void __launch_bounds__(PF_THREADS)
     } else {
         const float3 s_raw = make_float3(scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]);
         const float4 q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-        o = cgs_pre_bwd_one<false>(p, s_raw, q, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i],
-                                   dL_dconic[3 * i + 1], dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, scale_modifier);
+        o = cgs_pre_bwd_one(p, s_raw, q, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i],
+                            dL_dconic[3 * i + 1], dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, scale_modifier);
 #pragma unroll
         for (int k = 0; k < 3; ++k) dL_dscales[3 * i + k] = o.ds[k];
 #pragma unroll
@@ -271,9 +270,9 @@ __global__ void __launch_bounds__(PF_THREADS)
     } else {
         const float3 s_raw = make_float3(scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]);
         const float4 q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-        o = cgs_pre_bwd_one<false, true>(p, s_raw, q, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i],
-                                         dL_dconic[3 * i + 1], dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, scale_modifier,
-                                         0.f, opacities[i], dL_dopacities[i]);
+        o = cgs_pre_bwd_one<true>(p, s_raw, q, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i],
+                                  dL_dconic[3 * i + 1], dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, scale_modifier,
+                                  opacities[i], dL_dopacities[i]);
 #pragma unroll
         for (int k = 0; k < 3; ++k) dL_dscales[3 * i + k] = o.ds[k];
 #pragma unroll

@@ -39,9 +39,6 @@
 #ifndef RS_WAVES_B
 #define RS_WAVES_B 8              // backward: two waves per SIMD, 256 registers each
 #endif
-#ifndef RS_STAGGER
-#define RS_STAGGER 0              // > 0: the second wave of every SIMD starts RS_STAGGER x 4096 cycles late (MFMA phase of one wave
-#endif                            //      over the element maths of the other)
 
 // permuted output row o' = 16 (2 b + is_scale) + 4 g + r  ->  row of mlp_grid's second layer, -1 = padding
 __host__ __device__ __forceinline__ int rs_w2row(int op) {
@@ -173,10 +170,6 @@ __global__ void __launch_bounds__((BWD ? RS_WAVES_B : RS_WAVES_F) * 64) rs_main_
 
     const int64_t tstride = (int64_t)gridDim.x * RS_WAVES;
     int64_t tile = (int64_t)blockIdx.x * RS_WAVES + wave;
-#if RS_STAGGER > 0
-    if ((wave >> 2) & 1)
-        for (int i = 0; i < RS_STAGGER; ++i) __builtin_amdgcn_s_sleep(64);
-#endif
     float accb[3] = {0.f, 0.f, 0.f};
     RsOps<IN> opn;
     int64_t rn;

@@ -28,7 +28,9 @@
 #define TB_MAXR 256
 #ifndef TB_XCD_MAP
 #define TB_XCD_MAP 0      // 1: columns dealt to the XCDs in contiguous eighths (cgs_xcd_item) — what wins 10 % in the depth sort LOSES
-                          // 9-10 us per pass here (same-box A/B, profiles/r06_depth_sort.txt); 0: column = workgroup id
+                          // 9-10 us per pass here (same-box A/B, profiles/r06_depth_sort.txt); 0: column = workgroup id.
+                          // Stays a run-time argument of the kernels: without it they left the parent's run-to-run spread
+                          // (profiles/knob_collapse.txt)
 #endif
 
 int cgs_scan_exclusive_u32_total(const uint32_t *in, uint32_t *out, int64_t n, void *scratch, size_t scratch_bytes,
@@ -43,18 +45,12 @@ namespace {
 #ifndef GR_ITEMS
 #define GR_ITEMS 2
 #endif
-#ifndef GR_XCD
-#define GR_XCD 1
-#endif
 __global__ void __launch_bounds__(256)
     gather_rects_kernel(int64_t P, const uint32_t *__restrict__ order, const uint2 *__restrict__ rect,
                         uint32_t *__restrict__ rect_lo, uint32_t *__restrict__ rect_hi, uint32_t *__restrict__ cnt) {
-#if GR_XCD
+    // XCD x takes the x-th eighth of the depth order (cgs_xcd_item): -27 us per view (profiles/r06_xcd_gathers.txt)
     const int64_t blk = cgs_xcd_item((P + 256 * GR_ITEMS - 1) / (256 * GR_ITEMS));
     if (blk < 0) return;
-#else
-    const int64_t blk = blockIdx.x;
-#endif
     const int64_t i0 = blk * (256 * GR_ITEMS) + threadIdx.x;
     uint32_t o[GR_ITEMS];
     uint2 rc[GR_ITEMS];
@@ -191,7 +187,7 @@ __global__ void __launch_bounds__(TB_THREADS)
                    uint32_t *__restrict__ hist /*[rows][ncol]*/, int shift, int nbits, const uint32_t *__restrict__ R_dev,
                    uint32_t ncol, int xcd) {
     // column of this workgroup: its id, or (xcd) the XCD-aware assignment of cgs_xcd_item() — neighbouring columns, whose runs are
-    // adjacent in the output, on the same XCD's L2 (prims.hip: sort_tile_of_block)
+    // adjacent in the output, on the same XCD's L2 (as in prims.hip)
     const int64_t col_ = xcd ? cgs_xcd_item((int64_t)ncol) : (int64_t)blockIdx.x;
     if (col_ < 0) return;
     const uint32_t col = (uint32_t)col_;
@@ -651,7 +647,7 @@ __global__ void __launch_bounds__(BK_THREADS)
 // after the depth sort: rectangles and tile counts in depth order (g.sort_b / g.sort_d / g.sort_a)
 int cgs_launch_gather_rects(int64_t P, CgsGeom &g, hipStream_t stream) {
     if (P == 0) return CGS_OK;
-    hipLaunchKernelGGL(gather_rects_kernel, dim3(GR_XCD ? cgs_xcd_grid((P + 256 * GR_ITEMS - 1) / (256 * GR_ITEMS)) : (unsigned)((P + 256 * GR_ITEMS - 1) / (256 * GR_ITEMS))), dim3(256), 0, stream, P,
+    hipLaunchKernelGGL(gather_rects_kernel, dim3(cgs_xcd_grid((P + 256 * GR_ITEMS - 1) / (256 * GR_ITEMS))), dim3(256), 0, stream, P,
                        (const uint32_t *)g.order, (const uint2 *)g.rect, g.sort_b, g.sort_d, g.sort_a);
     CGS_CHECK_HIP(hipGetLastError());
     return CGS_OK;

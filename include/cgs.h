@@ -288,7 +288,7 @@ int cgs_raster_preprocess_launch_opt(const cgs_raster_cfg *cfg, int64_t P,
  * same opts.  Colour and / or map gradients, all four forms; dL_dcolors and dL_dopacities zero-initialised as there, scratch
  * cgs_raster_bwd_aux_scratch_bytes(P) bytes.  With CGS_RASTER_ANTIALIAS, opacities [P] must be given; dL_dopacities receives
  * the gradient of the opacity the caller passed.  opts == 0 gives cgs_raster_backward_aux's result; unknown bits: CGS_ERR_ARG
- * before anything is enqueued.  Not available in CGS_BLEND_BWD_RAW builds. */
+ * before anything is enqueued. */
 int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P,
                             int64_t num_rendered, const float *means3D,
                             const float *colors, const float *shs,
@@ -327,7 +327,7 @@ int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P,
  * dL_dcampos needs shs (without SH colours the camera position is unused).  work: cgs_raster_camera_bytes(P) bytes, any
  * contents (per-workgroup partial sums + an arrival ticket).  No float atomics: at fixed inputs the result is bit-reproducible.
  * P == 0 gives zeros.  Argument errors (missing pointer, unknown option bit, short scratch or work, dL_dcampos without shs)
- * return CGS_ERR_ARG before anything is enqueued.  Not available in CGS_BLEND_BWD_RAW builds. */
+ * return CGS_ERR_ARG before anything is enqueued. */
 #define CGS_RASTER_CAMERA_MAPS 2u
 size_t cgs_raster_camera_bytes(int64_t P);
 int cgs_raster_camera_backward(const cgs_raster_cfg *cfg, int64_t P,

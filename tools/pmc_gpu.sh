@@ -1,6 +1,6 @@
 # HBM traffic of the dominant kernels via PMC counters, collected in their OWN passes (no trace flags), as
 # MI355X_MICROARCH.md prescribes: FETCH_SIZE and WRITE_SIZE cannot share a pass (TCC slots).
-set -x
+set -ex          # a failed pass ends the script: nothing further is started on the GPU after it
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
