@@ -654,6 +654,12 @@ int cgs_launch_aux_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg 
                        float *dL_dopacity, float *dL_dz, hipStream_t stream);
 int cgs_launch_aux_dz_chain(const cgs_raster_cfg *cfg, int64_t P, const int32_t *radii, const float *dL_dz, float *dL_dmeans3D,
                             hipStream_t stream);
+// ---- N-channel per-Gaussian features (csrc/raster_feat.hip) ---------------------------------------------------------------
+int cgs_launch_feat_fwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const float *features, int C, float *out,
+                        hipStream_t stream);
+int cgs_launch_feat_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const float *features, int C,
+                        const float *dL_dmap, float *dL_dmean2D_px, float *dL_dconic, float *dL_dopacity, float *dL_dfeatures,
+                        hipStream_t stream);
 
 extern "C" size_t cgs_raster_bwd_aux_scratch_bytes(int64_t P) {
     const size_t n = (size_t)(P > 0 ? P : 1);
@@ -692,8 +698,9 @@ extern "C" int cgs_raster_render_aux(const cgs_raster_cfg *cfg, int64_t P, int64
     return cgs_launch_aux_fwd(cfg, g, b, im, out_depth, out_invdepth, out_alpha, (hipStream_t)stream_);
 }
 
-// Backward of the colour image and the three maps together, every argument form of cgs_raster_backward_ex.  Each of the four
-// upstream gradients may be NULL; without dL_dout no colour blend backward runs (dL_dcolors keeps its zeros).
+// Backward of the colour image, the three maps and the feature map together, every argument form of cgs_raster_backward_ex.
+// Each upstream gradient may be NULL; without dL_dout no colour blend backward runs (dL_dcolors keeps its zeros).  The feature
+// blend backward (cgs_raster_backward_feat) adds into the same scratch and dL_dopacities, behind the other two blends.
 // fn: the entry point's name for the messages; aa: antialiasing (cgs_raster_backward_opt), which also reads opacities
 static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D,
                                     const float *colors, const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
@@ -702,10 +709,19 @@ static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, i
                                     const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth, const float *dL_dalpha,
                                     float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities, float *dL_dshs,
                                     float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *scratch, size_t scratch_bytes,
-                                    hipStream_t stream, bool aa) {
+                                    hipStream_t stream, bool aa, const float *features = nullptr, int32_t C = 0,
+                                    const float *dL_dfeatures_map = nullptr, float *dL_dfeatures = nullptr) {
     int rc = check_cfg(cfg);
     if (rc) return rc;
     if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
+    if ((features != nullptr) != (dL_dfeatures != nullptr)) {
+        cgs_set_error("%s: features and dL_dfeatures go together (one of them is NULL)", fn);
+        return CGS_ERR_ARG;
+    }
+    if (features && (C < 1 || C > CGS_RASTER_MAX_FEATURES)) {
+        cgs_set_error("%s: %d feature channels outside 1..%d", fn, C, CGS_RASTER_MAX_FEATURES);
+        return CGS_ERR_ARG;
+    }
     CgsRasterForms f;
     if ((rc = check_forms(fn, cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
         return rc;
@@ -740,8 +756,12 @@ static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, i
         if (aux && (rc = cgs_launch_aux_bwd(cfg, g, b, im, dL_ddepth, dL_dinvdepth, dL_dalpha, d_mean_px, d_conic, dL_dopacities,
                                             d_z, stream)))
             return rc;
+        if (features && dL_dfeatures_map &&
+            (rc = cgs_launch_feat_bwd(cfg, g, b, im, features, C, dL_dfeatures_map, d_mean_px, d_conic, dL_dopacities, dL_dfeatures,
+                                      stream)))
+            return rc;
     }
-    // antialiasing: both blend backwards have summed dL/d(op_eff) into dL_dopacities by now; the per-Gaussian kernel turns it
+    // antialiasing: the blend backwards have summed dL/d(op_eff) into dL_dopacities by now; the per-Gaussian kernel turns it
     // into dL/d(opacity) in place and chains h's share to the covariance
     const float *aa_op = aa ? opacities : nullptr;
     float *aa_dop = aa ? dL_dopacities : nullptr;
@@ -786,6 +806,64 @@ extern "C" int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P, int
                                     dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
                                     dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_,
                                     (opts & CGS_RASTER_ANTIALIAS) != 0);
+}
+
+// The feature map of a view: enqueued after the render the caller kept, exactly as cgs_raster_render_aux.  Every pixel of
+// out_features [C, H, W] is written (zeros where nothing was blended, R == 0 included).
+extern "C" int cgs_raster_render_features(const cgs_raster_cfg *cfg, int64_t P, int64_t R, void *geom_ws, size_t geom_bytes,
+                                          void *bin_ws, size_t bin_bytes, void *img_ws, size_t img_bytes, const float *features,
+                                          int32_t C, float *out_features, void *stream_) {
+    const char *fn = "cgs_raster_render_features";
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
+    if (C < 1 || C > CGS_RASTER_MAX_FEATURES) {
+        cgs_set_error("%s: %d feature channels outside 1..%d", fn, C, CGS_RASTER_MAX_FEATURES);
+        return CGS_ERR_ARG;
+    }
+    if (!out_features || (P > 0 && !features)) {       // (P == 0: there is no table to point at)
+        cgs_set_error("%s: features and out_features go together (one of them is NULL)", fn);
+        return CGS_ERR_ARG;
+    }
+    if (!img_ws || (R > 0 && (!geom_ws || !bin_ws))) { cgs_set_error("%s: NULL workspace", fn); return CGS_ERR_ARG; }
+    CgsGeom g;
+    CgsBin b;
+    CgsImg im;
+    memset(&g, 0, sizeof(g));
+    memset(&b, 0, sizeof(b));
+    if (!cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
+        cgs_set_error("%s: image workspace too small", fn);
+        return CGS_ERR_WORKSPACE;
+    }
+    if (P > 0 && geom_ws && !cgs_geom_carve(&g, geom_ws, geom_bytes, P)) {
+        cgs_set_error("%s: geometry workspace too small", fn);
+        return CGS_ERR_WORKSPACE;
+    }
+    if (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
+        cgs_set_error("%s: binning workspace too small: %zu < %zu", fn, bin_bytes, cgs_raster_bin_bytes(P, R));
+        return CGS_ERR_WORKSPACE;
+    }
+    return cgs_launch_feat_fwd(cfg, g, b, im, features, C, out_features, (hipStream_t)stream_);
+}
+
+// cgs_raster_backward_opt plus the feature map's gradient.  features == NULL: cgs_raster_backward_opt's result.
+extern "C" int cgs_raster_backward_feat(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                        const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                        const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                        void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                        size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                        const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                        float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                        float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts,
+                                        const float *features, int32_t C, const float *dL_dfeatures_map, float *dL_dfeatures) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if ((rc = check_opts("cgs_raster_backward_feat", opts))) return rc;
+    return raster_backward_aux_impl("cgs_raster_backward_feat", cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities,
+                                    scales, rotations, cov3D, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout,
+                                    dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
+                                    dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_,
+                                    (opts & CGS_RASTER_ANTIALIAS) != 0, features, C, dL_dfeatures_map, dL_dfeatures);
 }
 
 // ---- camera gradients (csrc/raster_camera.hip) ---------------------------------------------------------------------------

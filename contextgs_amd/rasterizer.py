@@ -38,6 +38,21 @@ per-Gaussian scalar (z, 1/z, 1) with a zero background, and gradients flow accor
 means2D, opacities, scales, rotations and cov3D_precomp, never to shs / colors_precomp.  means2D.grad (the densification
 statistic) includes the maps' share, as upstream's `invdepths` backward does.
 
+`forward(..., features=F)` with F a float tensor [P, C], 1 <= C <= 32 (semantic or language features, normals, per-anchor
+statistics), blends the rows of F exactly as the colour is blended and returns `(color, radii, extras)` with
+`extras["features"]` float32 [C,H,W] (and the three maps too with return_aux=True):
+
+  features[c, p] = sum_i w_i F[i, c]
+
+over the same contributors and weights as above, each pixel stopping where the colour pass stopped it.  Values are blended as
+given (any sign, nothing clamped) over a zero background; a caller composites one with features + (1 - alpha) bg.  It is one
+more walk of the view's tile lists (csrc/raster_feat.hip, cgs_raster_render_features), not ceil(C/3) renders; without `features`
+the call runs exactly the code above.  When the feature map got a gradient the backward is cgs_raster_backward_feat: gradients
+reach `features`, means2D, opacities, means3D, scales / rotations or cov3D_precomp and the camera tensors that ask, never
+shs / colors_precomp; when only the feature map got one, no colour blend backward runs.  dL/dfeatures is summed with float
+atomics, like dL/dcolors: not bit-reproducible.  Shape errors (not 2-D, rows != P, C outside 1..32) raise ValueError before a
+device is touched.
+
 `GaussianRasterizationSettings(..., antialiasing=True)` (upstream's last field, default False) is the 2-D filter of
 Mip-Splatting that 3DGS code bases turn on with `--antialiasing`.  With [[a, b], [b, c]] the projected 2-D covariance before
 the fixed 0.3 px^2 dilation:
@@ -241,6 +256,19 @@ def check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, sh_degree
 
 CGS_RASTER_ANTIALIAS = 1      # include/cgs.h: the option bit of the *_opt entry points
 CGS_RASTER_CAMERA_MAPS = 2    # include/cgs.h, cgs_raster_camera_backward: the scratch is that of cgs_raster_backward_opt (dL/dz)
+CGS_RASTER_MAX_FEATURES = 32  # include/cgs.h: channels of `features`
+
+
+def check_features(features, P) -> None:
+    """Shape rules of `features` [P, C], on shapes only: no device is touched."""
+    if features is None:
+        return
+    if features.dim() != 2:
+        raise ValueError(f"features must be [P, C], got {tuple(features.shape)}")
+    if features.shape[0] != P:
+        raise ValueError(f"features has {features.shape[0]} rows for {P} Gaussians")
+    if not 1 <= features.shape[1] <= CGS_RASTER_MAX_FEATURES:
+        raise ValueError(f"features has {features.shape[1]} channels, outside 1..{CGS_RASTER_MAX_FEATURES}")
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -250,17 +278,19 @@ class _RasterizeGaussians(torch.autograd.Function):
     binning and colour blend, then one walk of the final per-tile lists for the maps.  The backward is cgs_raster_backward_ex
     (cgs_raster_backward for colours + scales / rotations) when only the colour image got a gradient and antialiasing is off,
     cgs_raster_backward_opt otherwise: it runs no colour blend backward when the image got none, and with antialiasing its
-    per-Gaussian kernel turns the blends' dL/d(opacity * h) into dL/d(opacity) and chains h's gradient to the covariance."""
+    per-Gaussian kernel turns the blends' dL/d(opacity * h) into dL/d(opacity) and chains h's gradient to the covariance.
+    With `features` [P, C] (the last input; None = none of this runs) one more walk of the lists gives the feature map as the
+    last output (cgs_raster_render_features), and when that map got a gradient the backward is cgs_raster_backward_feat."""
 
     @staticmethod
     def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings,
-                viewmatrix, projmatrix, campos):
+                viewmatrix, projmatrix, campos, features=None):
         # viewmatrix / projmatrix / campos: the settings' three camera tensors once more, as inputs of the node so that autograd
         # can hand them a gradient; the forward reads them through _Cfg as before
         L = _lib.lib()
-        _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D)
-        means3D, shs, colors, opac, scales, rots, cov = (
-            None if t is None else _f32c(t) for t in (means3D, shs, colors, opacities, scales, rotations, cov3D))
+        _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D, features)
+        means3D, shs, colors, opac, scales, rots, cov, feat = (
+            None if t is None else _f32c(t) for t in (means3D, shs, colors, opacities, scales, rotations, cov3D, features))
         P = means3D.shape[0]
         dev = means3D.device
         cfg = _Cfg(raster_settings)
@@ -290,21 +320,29 @@ class _RasterizeGaussians(torch.autograd.Function):
                                                binws.numel(), _lib.ptr(img), img.numel(), _lib.ptr(maps[0]),
                                                _lib.ptr(maps[1]), _lib.ptr(maps[2]), stream), "cgs_raster_render_aux")
             outs += tuple(maps)
-        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M, ctx.opts = cfg, bin_R, D, M, opts
-        ctx.save_for_backward(means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img)
+        if feat is not None:    # likewise; every pixel is written
+            fmap = torch.empty(feat.shape[1], H, W, dtype=torch.float32, device=dev)
+            _lib.check(L.cgs_raster_render_features(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
+                                                    binws.numel(), _lib.ptr(img), img.numel(), _lib.ptr(feat), feat.shape[1],
+                                                    _lib.ptr(fmap), stream), "cgs_raster_render_features")
+            outs += (fmap,)
+        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M, ctx.opts, ctx.aux = cfg, bin_R, D, M, opts, bool(aux)
+        ctx.save_for_backward(means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat)
         ctx.mark_non_differentiable(radii)
         return outs
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, *grad_maps):
+    def backward(ctx, grad_color, _grad_radii, *grad_rest):
         L = _lib.lib()
-        means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img = ctx.saved_tensors
+        means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat = ctx.saved_tensors
+        grad_maps = grad_rest[:3] if ctx.aux else ()
+        g_fmap = _f32c(grad_rest[-1]) if (feat is not None and grad_rest[-1] is not None) else None
         cfg = ctx.cfg
         P = means3D.shape[0]
         dev = means3D.device
         g, *maps = (None if t is None else _f32c(t) for t in (grad_color, *grad_maps, None, None, None)[:4])
-        if g is None and all(t is None for t in maps):
-            return (None,) * 13
+        if g is None and g_fmap is None and all(t is None for t in maps):
+            return (None,) * 14
         # the blends accumulate dL/dcolor (read by the SH backward) and dL/dopacity atomically: one zero fill for both; the
         # other arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones)
         acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
@@ -321,7 +359,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         grads = (_lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_shs),
                  _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov))
         stream = _lib.current_stream()
-        if ctx.opts or any(t is not None for t in maps):
+        d_feat = None
+        if g_fmap is not None:      # the feature map got a gradient: the same call with the feature blend backward in it
+            cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS
+            d_feat = torch.zeros_like(feat)         # accumulated atomically, like dL/dcolor
+            scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
+            _lib.check(L.cgs_raster_backward_feat(*inputs, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), *grads,
+                                                  _lib.ptr(scratch), scratch.numel(), stream, ctx.opts, _lib.ptr(feat),
+                                                  feat.shape[1], _lib.ptr(g_fmap), _lib.ptr(d_feat)),
+                       "cgs_raster_backward_feat")
+        elif ctx.opts or any(t is not None for t in maps):
             cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS
             scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
             _lib.check(L.cgs_raster_backward_opt(*inputs, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), *grads,
@@ -348,10 +395,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(scratch), scratch.numel(), _lib.ptr(d_colors),
                 _lib.ptr(d_opac), cam_opts, _lib.ptr(d_view), _lib.ptr(d_proj),
                 _lib.ptr(d_campos), _lib.ptr(work), work.numel(), stream), "cgs_raster_camera_backward")
-        if g is None:       # the maps send no gradient to the colour inputs
+        if g is None:       # the maps and the features send no gradient to the colour inputs
             d_shs = d_colors = None
         return (None, d_means3D, d_means2D, d_shs, d_colors if colors is not None else None, d_opac, d_scales, d_rots,
-                d_cov, None, d_view, d_proj, d_campos)
+                d_cov, None, d_view, d_proj, d_campos, d_feat)
 
 
 def _camera_inputs(rs):
@@ -406,13 +453,19 @@ class GaussianRasterizer(nn.Module):
         return radii
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, return_aux=False):
-        """(color [3,H,W], radii int32 [P]); with return_aux=True also {"depth", "invdepth", "alpha"}, float32 [1,H,W]
-        each (see the module docstring)."""
+                cov3D_precomp=None, features=None, return_aux=False):
+        """(color [3,H,W], radii int32 [P]); with return_aux=True and / or features [P,C] a third value, the dict of
+        {"depth", "invdepth", "alpha"}, float32 [1,H,W] each, and / or {"features"}, float32 [C,H,W] (see the module
+        docstring)."""
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
+        check_features(features, means3D.shape[0])
         out = _RasterizeGaussians.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                        cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings))
-        if not return_aux:
+                                        cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings), features)
+        if not return_aux and features is None:
             return out
-        color, radii, depth, invdepth, alpha = out
-        return color, radii, {"depth": depth, "invdepth": invdepth, "alpha": alpha}
+        extras = {}
+        if return_aux:
+            extras.update(depth=out[2], invdepth=out[3], alpha=out[4])
+        if features is not None:
+            extras["features"] = out[-1]
+        return out[0], out[1], extras

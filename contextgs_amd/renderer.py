@@ -390,7 +390,9 @@ def _generate_unfused(viewpoint_camera, pc, anchor, feat, grid_scaling, grid_off
     return _ExpandGaussians.apply(anchor, grid_scaling, grid_offsets, masks2, op_raw, color_in, cov_in, K, src_row, pre)
 
 
-def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, step=0, _view=None):   # :25-150
+def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, step=0, _view=None,
+                              _rows=None):   # :25-150
+    # _rows: a list that receives, for every Gaussian produced, the row of its anchor in pc.get_anchor (render(anchor_features=))
     time_sub = 0
     if visible_mask is None:
         visible_mask = torch.ones(pc.get_anchor.shape[0], dtype=torch.bool, device=pc.get_anchor.device)
@@ -530,6 +532,8 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
     if rate_out:
         bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level = rate_out
     xyz, color, opacity, scaling, rot, neural_opacity, mask = out
+    if _rows is not None:       # the visible anchor index once per offset, then through the expansion's selection mask
+        _rows.append(vis_idx.repeat_interleave(K)[mask.reshape(-1)])
 
     if is_training:                                                                      # :147-150
         return (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, 16, bit_per_feat_param,
@@ -588,12 +592,17 @@ class _DetachedCamera:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False,
-           step=0, *, return_aux=False):                                                # :155-229
+           step=0, *, return_aux=False, anchor_features=None):                          # :155-229
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
 
     return_aux=True: the dict also holds the rasterizer's "depth", "invdepth" and "alpha" maps ([1,H,W] each, see
     contextgs_amd/rasterizer.py).  In training mode such a call takes the unfused path (the one CGS_FUSE_VIEW=0 takes), and so
     does one with `pipe.antialiasing` set (upstream's --antialiasing, see contextgs_amd/rasterizer.py).
+
+    anchor_features: a float tensor [N, C] over all anchors (pc.get_anchor's row order), 1 <= C <= 32.  Every neural Gaussian
+    carries its anchor's row and the dict gains "features" [C,H,W], the rasterizer's blend of them over a zero background
+    (rasterizer.py).  The gradient reaches `anchor_features` (zero rows for anchors that are not visible) and the geometry.
+    In training mode such a call takes the unfused path, as return_aux does.
 
     A camera whose `world_view_transform`, `full_proj_transform` or `camera_center` requires a gradient (a trainable pose,
     contextgs_amd/camera_pose.py) takes the unfused path too, in training and in eval mode, and the gradient reaches the three
@@ -606,6 +615,10 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         isinstance(t, torch.Tensor) and t.requires_grad for t in (
             viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center))
     gen_camera = _DetachedCamera(viewpoint_camera) if cam_grad else viewpoint_camera
+    rows = [] if anchor_features is not None else None
+    if anchor_features is not None and (anchor_features.dim() != 2 or anchor_features.shape[0] != pc.get_anchor.shape[0]):
+        raise ValueError(f"anchor_features must be [N, C] with N = {pc.get_anchor.shape[0]} anchors, "
+                         f"got {tuple(anchor_features.shape)}")
     if is_training:
         # the expansion may run fused with the rasterizer's per-Gaussian stages (then `view.done` holds the rendered view
         # and xyz / color / opacity / rot are None: they never existed as tensors)
@@ -613,7 +626,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, bit_per_anchor_param,
          bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level) = \
             generate_neural_gaussians(gen_camera, pc, visible_mask, is_training=True, step=step,
-                                      _view=None if (return_aux or view.raster_settings.antialiasing or cam_grad) else view)
+                                      _view=None if (return_aux or view.raster_settings.antialiasing or cam_grad
+                                                     or rows is not None) else view, _rows=rows)
         if view.done is not None:
             rendered_image, radii, screenspace_points = view.done
             return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
@@ -623,7 +637,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
                     "bit_per_offsets_param": bit_per_offsets_param, "bpp_per_level": bpp_per_level}
     else:
         xyz, color, opacity, scaling, rot, time_sub = generate_neural_gaussians(
-            gen_camera, pc, visible_mask, is_training=False, step=step)
+            gen_camera, pc, visible_mask, is_training=False, step=step, _rows=rows)
 
     screenspace_points = _zero_points(xyz)       # :168 `torch.zeros_like(xyz, requires_grad=True) + 0`
     if retain_grad:
@@ -633,10 +647,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
             pass
 
     rasterizer = GaussianRasterizer(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier))
-    if return_aux:
+    if return_aux or rows is not None:
+        features = anchor_features.index_select(0, rows[0]) if rows is not None else None      # plumbing: plain torch
         rendered_image, radii, aux = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
                                                 opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None,
-                                                return_aux=True)
+                                                features=features, return_aux=return_aux)
     else:
         rendered_image, radii = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
                                            opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None)
@@ -649,7 +664,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     else:
         out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
                "radii": radii, "time_sub": time_sub}
-    if return_aux:
+    if return_aux or rows is not None:
         out.update(aux)
     return out
 

@@ -306,6 +306,52 @@ int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P,
                             float *dL_dcov3D, void *scratch,
                             size_t scratch_bytes, void *stream, uint32_t opts);
 
+/* ---- N-channel per-Gaussian features blended like the colour (csrc/raster_feat.hip) ----
+ * features [P, C], 1 <= C <= CGS_RASTER_MAX_FEATURES (C is a runtime argument): semantic or language features, normals,
+ * per-anchor statistics.  For pixel p the contributors i are exactly those of the colour blend (same order, same alpha, same
+ * skip below 1/255, each pixel stopping where the colour pass stopped it) and, with w_i = alpha_i T_i,
+ *   features_map[c, p] = sum_i w_i features[i, c].
+ * Values are blended as given (any sign, finite, nothing clamped) over a zero background: a caller composites one with
+ * features_map + (1 - alpha) bg.  With CGS_RASTER_ANTIALIAS the blend reads opacity * h, as every other blend does.
+ *
+ * cgs_raster_render_features: enqueue after the cgs_raster_render / cgs_raster_render_spec of the view whose result the caller
+ * keeps, exactly as cgs_raster_render_aux (same workspaces, same R).  Every pixel of out_features [C, H, W] is written; with
+ * R == 0 or an empty view the output is zeros.
+ *
+ * cgs_raster_backward_feat: cgs_raster_backward_opt's arguments, then features [P, C], C, dL_dfeatures_map [C, H, W] and
+ * dL_dfeatures [P, C] (zero-initialised by the caller, as dL_dcolors).  The feature blend backward runs behind the colour and
+ * map blend backwards and adds its share into the same dL/d(pixel mean), dL/d(conic) and dL_dopacities sums, so the
+ * per-Gaussian backward, antialiasing's opacity chain and cgs_raster_camera_backward (with CGS_RASTER_CAMERA_MAPS) see it without
+ * knowing of it.  No gradient reaches the colours from the features.  dL_dout, the three map gradients and dL_dfeatures_map may
+ * each be NULL; features == NULL (with dL_dfeatures == NULL) gives cgs_raster_backward_opt's result.  scratch:
+ * cgs_raster_bwd_aux_scratch_bytes(P) bytes.  dL_dfeatures is summed with float atomics, like dL_dcolors: not bit-reproducible.
+ *
+ * CGS_ERR_ARG with a message, before anything is enqueued: C outside 1..CGS_RASTER_MAX_FEATURES, features without
+ * out_features / dL_dfeatures or the reverse, a NULL workspace, P < 0.  A short workspace: CGS_ERR_WORKSPACE. */
+#define CGS_RASTER_MAX_FEATURES 32
+int cgs_raster_render_features(const cgs_raster_cfg *cfg, int64_t P, int64_t num_rendered,
+                               void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes,
+                               void *img_ws, size_t img_bytes, const float *features,
+                               int32_t C, float *out_features, void *stream);
+int cgs_raster_backward_feat(const cgs_raster_cfg *cfg, int64_t P,
+                             int64_t num_rendered, const float *means3D,
+                             const float *colors, const float *shs,
+                             int32_t sh_degree, int32_t sh_coeffs,
+                             const float *opacities, const float *scales,
+                             const float *rotations, const float *cov3D,
+                             const int32_t *radii, void *geom_ws, size_t geom_bytes,
+                             void *bin_ws, size_t bin_bytes, void *img_ws,
+                             size_t img_bytes, const float *dL_dout,
+                             const float *dL_ddepth, const float *dL_dinvdepth,
+                             const float *dL_dalpha, float *dL_dmeans3D,
+                             float *dL_dmeans2D, float *dL_dcolors,
+                             float *dL_dopacities, float *dL_dshs,
+                             float *dL_dscales, float *dL_drotations,
+                             float *dL_dcov3D, void *scratch,
+                             size_t scratch_bytes, void *stream, uint32_t opts,
+                             const float *features, int32_t C,
+                             const float *dL_dfeatures_map, float *dL_dfeatures);
+
 /* ---- gradients for the camera: viewmatrix, projmatrix, campos (csrc/raster_camera.hip) ----
  * The rasterizer reads the three tensors of cgs_raster_cfg independently (row-vector convention, M[4c+i] = row c, column i):
  *   viewmatrix V: the view-space position t = [p,1] V (the Jacobian of the projection, its 1.3 tanfov clamp, the depth
