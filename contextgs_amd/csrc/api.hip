@@ -660,6 +660,10 @@ int cgs_launch_feat_fwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg
 int cgs_launch_feat_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const float *features, int C,
                         const float *dL_dmap, float *dL_dmean2D_px, float *dL_dconic, float *dL_dopacity, float *dL_dfeatures,
                         hipStream_t stream);
+// ---- per-Gaussian contribution statistics and top-contributor maps (csrc/raster_contrib.hip) ------------------------------
+int cgs_launch_contrib(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const int32_t *slot, float *acc_weight,
+                       float *acc_max_weight, int64_t *acc_pixels, int64_t *acc_top_pixels, int32_t *out_top_id,
+                       float *out_top_weight, int32_t *out_count, hipStream_t stream);
 
 extern "C" size_t cgs_raster_bwd_aux_scratch_bytes(int64_t P) {
     const size_t n = (size_t)(P > 0 ? P : 1);
@@ -844,6 +848,49 @@ extern "C" int cgs_raster_render_features(const cgs_raster_cfg *cfg, int64_t P, 
         return CGS_ERR_WORKSPACE;
     }
     return cgs_launch_feat_fwd(cfg, g, b, im, features, C, out_features, (hipStream_t)stream_);
+}
+
+// How much each Gaussian mattered to the view, and which one dominates each pixel: enqueued after the render the caller kept,
+// exactly as cgs_raster_render_aux.  The four accumulators are added into (never zeroed here); the three maps are written for
+// every pixel (-1 / 0 / 0 where nothing was blended, R == 0 included).  Any of the seven may be NULL: not computed.  The values
+// of `slot` are not range-checked on the device: 0 <= slot[i] < n_slots is the caller's contract.
+extern "C" int cgs_raster_contrib(const cgs_raster_cfg *cfg, int64_t P, int64_t R, void *geom_ws, size_t geom_bytes, void *bin_ws,
+                                  size_t bin_bytes, void *img_ws, size_t img_bytes, const int32_t *slot, int64_t n_slots,
+                                  float *acc_weight, float *acc_max_weight, int64_t *acc_pixels, int64_t *acc_top_pixels,
+                                  int32_t *out_top_id, float *out_top_weight, int32_t *out_count, void *stream_) {
+    const char *fn = "cgs_raster_contrib";
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
+    if (!acc_weight && !acc_max_weight && !acc_pixels && !acc_top_pixels && !out_top_id && !out_top_weight && !out_count) {
+        cgs_set_error("%s: no output given (all four accumulators and all three maps are NULL)", fn);
+        return CGS_ERR_ARG;
+    }
+    if (!img_ws || (R > 0 && (!geom_ws || !bin_ws))) { cgs_set_error("%s: NULL workspace", fn); return CGS_ERR_ARG; }
+    if (slot && n_slots <= 0) { cgs_set_error("%s: slot given with n_slots = %lld <= 0", fn, (long long)n_slots); return CGS_ERR_ARG; }
+    if (!slot && n_slots != P) {
+        cgs_set_error("%s: n_slots = %lld != P = %lld without a slot table", fn, (long long)n_slots, (long long)P);
+        return CGS_ERR_ARG;
+    }
+    CgsGeom g;
+    CgsBin b;
+    CgsImg im;
+    memset(&g, 0, sizeof(g));
+    memset(&b, 0, sizeof(b));
+    if (!cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
+        cgs_set_error("%s: image workspace too small", fn);
+        return CGS_ERR_WORKSPACE;
+    }
+    if (P > 0 && geom_ws && !cgs_geom_carve(&g, geom_ws, geom_bytes, P)) {
+        cgs_set_error("%s: geometry workspace too small", fn);
+        return CGS_ERR_WORKSPACE;
+    }
+    if (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
+        cgs_set_error("%s: binning workspace too small: %zu < %zu", fn, bin_bytes, cgs_raster_bin_bytes(P, R));
+        return CGS_ERR_WORKSPACE;
+    }
+    return cgs_launch_contrib(cfg, g, b, im, slot, acc_weight, acc_max_weight, acc_pixels, acc_top_pixels, out_top_id,
+                              out_top_weight, out_count, (hipStream_t)stream_);
 }
 
 // cgs_raster_backward_opt plus the feature map's gradient.  features == NULL: cgs_raster_backward_opt's result.

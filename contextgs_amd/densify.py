@@ -356,3 +356,18 @@ def adjust_anchor(pc, check_interval=100, success_threshold=0.8, grad_threshold=
     pc.max_radii2D = torch.zeros(pc.get_anchor.shape[0], device=dev)
     if _dist.world() > 1:      # what the replicas agree on from here; the next reduce_statistics sums the ranks' additions to it
         pc._stats_base = [getattr(pc, n).clone() for n in _STATS]
+
+
+def anchor_importance(contrib, n_offsets, reduce="max_weight"):
+    """[N] importance of every anchor from a rasterizer.GaussianContrib of N * n_offsets rows accumulated over a set of views
+    (render(contrib=): row a * n_offsets + k is offset k of anchor a): the maximum over the anchor's offsets of `max_weight`,
+    or the sum over them of `weight`, `pixels` or `top_pixels`.  A pruning criterion measured on the rendered views; plain torch,
+    called between training phases, never inside a step."""
+    if reduce not in ("max_weight", "weight", "pixels", "top_pixels"):
+        raise ValueError(f"reduce must be one of max_weight, weight, pixels, top_pixels, got {reduce!r}")
+    t = getattr(contrib, reduce)
+    K = int(n_offsets)
+    if K < 1 or t.dim() != 1 or t.shape[0] % K:
+        raise ValueError(f"contrib has {tuple(t.shape)} rows, not a multiple of n_offsets = {n_offsets}")
+    t = t.view(-1, K)
+    return t.max(dim=1).values if reduce == "max_weight" else t.sum(dim=1)

@@ -83,6 +83,28 @@ inputs: near-plane culling, radii and tile rectangles, the alpha >= 1/255 skip, 
 the 1.3 tanfov clamp of the Jacobian is active (zero, as for means3D).  The kernel runs behind the backward above, only when one
 of the three asks; a call in which none does enqueues exactly what it did before.  No float atomics: at a fixed scratch the
 three gradients are bit-reproducible.
+
+`forward(..., contrib=...)` measures the reverse direction: how much each Gaussian mattered to the view (importance pruning,
+covisibility, picking).  With w_i(p) = alpha_i T_i > 0 for the contributors of pixel p, exactly those of the colour blend as
+above, and 0 otherwise, the call accumulates per Gaussian i into a `GaussianContrib` (four caller-owned tensors, added into
+and never zeroed by the call, so that one object collects a whole set of training views):
+
+  weight     += sum_p w_i(p)                     (float32; LightGaussian's accumulated blending weight)
+  max_weight  = max(max_weight, max_p w_i(p))    (float32, values >= 0; RadSplat's criterion)
+  pixels     += #{p : w_i(p) > 0}                (int64; MonoGS's n_touched)
+  top_pixels += #{p : i has the largest w at p}  (int64; Mini-Splatting's count; an exact tie goes to the front-most)
+
+and returns `(color, radii, extras)` with `extras["contrib"]` the object, `extras["top_id"]` int32 [H,W] (the index of that
+largest contributor in the call's Gaussian order, -1 where the pixel has none), `extras["top_weight"]` float32 [1,H,W] (its w,
+0 where none) and `extras["count"]` int32 [H,W] (the number of contributors).  `contrib=True` allocates a zeroed object of P
+rows; a `GaussianContrib` instance must have P rows.  `contrib_slots`, int32 [P], redirects Gaussian i's four updates to row
+contrib_slots[i] of an object of any length >= 1 (several Gaussians may share a row; values outside [0, len) are the caller's
+error and are not checked on the device); `top_id` stays a Gaussian index.  Culled Gaussians and Gaussians that contributed
+nowhere leave their rows untouched.  It is one more walk of the view's tile lists (csrc/raster_contrib.hip,
+cgs_raster_contrib) behind the render that was kept; it combines freely with return_aux and features, nothing of it is
+differentiable and the backward neither sees nor saves anything of it; without `contrib` the call enqueues exactly what it
+did before.  `weight` is summed with float atomics (not bit-reproducible); the other results are exact.  A wrong length, dtype
+or a non-contiguous tensor, or contrib_slots without contrib, raises ValueError before a device is touched.
 """
 from __future__ import annotations
 
@@ -271,6 +293,69 @@ def check_features(features, P) -> None:
         raise ValueError(f"features has {features.shape[1]} channels, outside 1..{CGS_RASTER_MAX_FEATURES}")
 
 
+class GaussianContrib:
+    """Per-Gaussian (or per-slot) contribution statistics accumulated over views: `weight`, `max_weight` float32 [n], `pixels`,
+    `top_pixels` int64 [n] (module docstring), and `views`, the number of calls accumulated since the last reset."""
+    FIELDS = (("weight", torch.float32), ("max_weight", torch.float32), ("pixels", torch.int64), ("top_pixels", torch.int64))
+
+    def __init__(self, weight, max_weight, pixels, top_pixels, views=0):
+        self.weight, self.max_weight, self.pixels, self.top_pixels = weight, max_weight, pixels, top_pixels
+        self.views = int(views)
+
+    @classmethod
+    def zeros(cls, n, device=None):
+        return cls(*(torch.zeros(int(n), dtype=dt, device=device) for _, dt in cls.FIELDS))
+
+    def tensors(self):
+        return tuple(getattr(self, name) for name, _ in self.FIELDS)
+
+    def __len__(self):
+        return int(self.weight.shape[0])
+
+    def reset(self):
+        for t in self.tensors():
+            t.zero_()
+        self.views = 0
+        return self
+
+
+def check_contrib(contrib, contrib_slots, means3D) -> None:
+    """Rules of `contrib` (None, True or a GaussianContrib) / `contrib_slots`, on shapes, dtypes, strides and the tensors'
+    `.device` attributes only: no device is touched."""
+    P = means3D.shape[0]
+    if contrib is None:
+        if contrib_slots is not None:
+            raise ValueError("contrib_slots given without contrib")
+        return
+    if contrib_slots is not None:
+        if not isinstance(contrib_slots, torch.Tensor) or contrib_slots.dtype != torch.int32:
+            raise ValueError(f"contrib_slots must be an int32 tensor, got {getattr(contrib_slots, 'dtype', type(contrib_slots))}")
+        if contrib_slots.dim() != 1 or contrib_slots.shape[0] != P:
+            raise ValueError(f"contrib_slots must be [P] = [{P}], got {tuple(contrib_slots.shape)}")
+        if not contrib_slots.is_contiguous():
+            raise ValueError("contrib_slots must be contiguous")
+        if contrib_slots.device != means3D.device:
+            raise ValueError(f"contrib_slots is on {contrib_slots.device}, means3D on {means3D.device}")
+    if contrib is True:
+        return
+    if not isinstance(contrib, GaussianContrib):
+        raise ValueError(f"contrib must be a GaussianContrib or True, got {type(contrib).__name__}")
+    n = contrib.weight.shape[0] if contrib.weight.dim() == 1 else -1
+    for (name, dt), t in zip(GaussianContrib.FIELDS, contrib.tensors()):
+        if t.dtype != dt:
+            raise ValueError(f"contrib.{name} must be {dt}, got {t.dtype}")
+        if t.dim() != 1 or t.shape[0] != n:
+            raise ValueError(f"contrib.{name} must be [n] like contrib.weight, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"contrib.{name} must be contiguous")
+        if t.device != means3D.device:      # (the kernel writes through raw pointers in means3D's device context)
+            raise ValueError(f"contrib.{name} is on {t.device}, means3D on {means3D.device}")
+    if contrib_slots is None and n != P:
+        raise ValueError(f"contrib has {n} rows for {P} Gaussians (any length needs contrib_slots)")
+    if contrib_slots is not None and n < 1:
+        raise ValueError("contrib needs at least one row with contrib_slots")
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """The one node of the drop-in: any of the four argument forms (absent inputs are None), antialiasing from
     `raster_settings.antialiasing`, and the depth / inverse-depth / alpha maps as three more outputs when `aux`.  The forward
@@ -280,15 +365,18 @@ class _RasterizeGaussians(torch.autograd.Function):
     cgs_raster_backward_opt otherwise: it runs no colour blend backward when the image got none, and with antialiasing its
     per-Gaussian kernel turns the blends' dL/d(opacity * h) into dL/d(opacity) and chains h's gradient to the covariance.
     With `features` [P, C] (the last input; None = none of this runs) one more walk of the lists gives the feature map as the
-    last output (cgs_raster_render_features), and when that map got a gradient the backward is cgs_raster_backward_feat."""
+    last output (cgs_raster_render_features), and when that map got a gradient the backward is cgs_raster_backward_feat.
+    With `contrib` (a GaussianContrib; None = none of this runs) one more walk accumulates into it and gives the
+    top_id / top_weight / count maps as three non-differentiable outputs behind the aux maps (cgs_raster_contrib)."""
 
     @staticmethod
     def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings,
-                viewmatrix, projmatrix, campos, features=None):
+                viewmatrix, projmatrix, campos, features=None, contrib=None, contrib_slots=None):
         # viewmatrix / projmatrix / campos: the settings' three camera tensors once more, as inputs of the node so that autograd
         # can hand them a gradient; the forward reads them through _Cfg as before
         L = _lib.lib()
-        _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D, features)
+        _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D, features, contrib_slots,
+                            *(contrib.tensors() if isinstance(contrib, GaussianContrib) else ()))
         means3D, shs, colors, opac, scales, rots, cov, feat = (
             None if t is None else _f32c(t) for t in (means3D, shs, colors, opacities, scales, rotations, cov3D, features))
         P = means3D.shape[0]
@@ -314,12 +402,26 @@ class _RasterizeGaussians(torch.autograd.Function):
             "cgs_raster_preprocess_launch_opt")
         binws, bin_R, _num_rendered = bin_and_blend(cfg, P, geom, img, color, stream, ticket)
         outs = (color, radii)
+        nondiff = (radii,)
         if aux:     # behind the render bin_and_blend kept (a voided speculative render has been redone by now)
             maps = [torch.empty(1, H, W, dtype=torch.float32, device=dev) for _ in range(3)]
             _lib.check(L.cgs_raster_render_aux(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
                                                binws.numel(), _lib.ptr(img), img.numel(), _lib.ptr(maps[0]),
                                                _lib.ptr(maps[1]), _lib.ptr(maps[2]), stream), "cgs_raster_render_aux")
             outs += tuple(maps)
+        if contrib is not None:     # likewise; accumulates into the caller's object, every pixel of the maps is written
+            top_id = torch.empty(H, W, dtype=torch.int32, device=dev)
+            top_w = torch.empty(1, H, W, dtype=torch.float32, device=dev)
+            count = torch.empty(H, W, dtype=torch.int32, device=dev)
+            # (P == 0: no row can be touched, and an empty slot table has no pointer to tell it from an absent one)
+            accs = [_lib.ptr(t) for t in contrib.tensors()] if P > 0 else [None] * 4
+            _lib.check(L.cgs_raster_contrib(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws), binws.numel(),
+                                            _lib.ptr(img), img.numel(), _lib.ptr(contrib_slots) if P > 0 else None,
+                                            len(contrib) if P > 0 else 0, *accs, _lib.ptr(top_id), _lib.ptr(top_w),
+                                            _lib.ptr(count), stream), "cgs_raster_contrib")
+            contrib.views += 1
+            outs += (top_id, top_w, count)
+            nondiff += (top_id, top_w, count)
         if feat is not None:    # likewise; every pixel is written
             fmap = torch.empty(feat.shape[1], H, W, dtype=torch.float32, device=dev)
             _lib.check(L.cgs_raster_render_features(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
@@ -328,7 +430,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             outs += (fmap,)
         ctx.cfg, ctx.num_rendered, ctx.D, ctx.M, ctx.opts, ctx.aux = cfg, bin_R, D, M, opts, bool(aux)
         ctx.save_for_backward(means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat)
-        ctx.mark_non_differentiable(radii)
+        ctx.mark_non_differentiable(*nondiff)      # ONE call: torch keeps only the last call's arguments
         return outs
 
     @staticmethod
@@ -342,7 +444,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         dev = means3D.device
         g, *maps = (None if t is None else _f32c(t) for t in (grad_color, *grad_maps, None, None, None)[:4])
         if g is None and g_fmap is None and all(t is None for t in maps):
-            return (None,) * 14
+            return (None,) * 16
         # the blends accumulate dL/dcolor (read by the SH backward) and dL/dopacity atomically: one zero fill for both; the
         # other arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones)
         acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
@@ -398,7 +500,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         if g is None:       # the maps and the features send no gradient to the colour inputs
             d_shs = d_colors = None
         return (None, d_means3D, d_means2D, d_shs, d_colors if colors is not None else None, d_opac, d_scales, d_rots,
-                d_cov, None, d_view, d_proj, d_campos, d_feat)
+                d_cov, None, d_view, d_proj, d_campos, d_feat, None, None)
 
 
 def _camera_inputs(rs):
@@ -453,19 +555,28 @@ class GaussianRasterizer(nn.Module):
         return radii
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, features=None, return_aux=False):
-        """(color [3,H,W], radii int32 [P]); with return_aux=True and / or features [P,C] a third value, the dict of
-        {"depth", "invdepth", "alpha"}, float32 [1,H,W] each, and / or {"features"}, float32 [C,H,W] (see the module
-        docstring)."""
+                cov3D_precomp=None, features=None, return_aux=False, contrib=None, contrib_slots=None):
+        """(color [3,H,W], radii int32 [P]); with return_aux=True, features [P,C] and / or contrib a third value, the dict of
+        {"depth", "invdepth", "alpha"}, float32 [1,H,W] each, {"features"}, float32 [C,H,W], and / or {"contrib", "top_id",
+        "top_weight", "count"} (see the module docstring)."""
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
         check_features(features, means3D.shape[0])
+        if contrib is False:
+            contrib = None
+        check_contrib(contrib, contrib_slots, means3D)
+        if contrib is True:
+            contrib = GaussianContrib.zeros(means3D.shape[0], means3D.device)
         out = _RasterizeGaussians.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                        cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings), features)
-        if not return_aux and features is None:
+                                        cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings), features,
+                                        contrib, contrib_slots)
+        if not return_aux and features is None and contrib is None:
             return out
         extras = {}
         if return_aux:
             extras.update(depth=out[2], invdepth=out[3], alpha=out[4])
+        if contrib is not None:
+            k = 5 if return_aux else 2
+            extras.update(contrib=contrib, top_id=out[k], top_weight=out[k + 1], count=out[k + 2])
         if features is not None:
             extras["features"] = out[-1]
         return out[0], out[1], extras

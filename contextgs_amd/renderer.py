@@ -391,8 +391,9 @@ def _generate_unfused(viewpoint_camera, pc, anchor, feat, grid_scaling, grid_off
 
 
 def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, step=0, _view=None,
-                              _rows=None):   # :25-150
+                              _rows=None, _slots=None):   # :25-150
     # _rows: a list that receives, for every Gaussian produced, the row of its anchor in pc.get_anchor (render(anchor_features=))
+    # _slots: likewise, int32 a * K + k for offset k of anchor a (render(contrib=))
     time_sub = 0
     if visible_mask is None:
         visible_mask = torch.ones(pc.get_anchor.shape[0], dtype=torch.bool, device=pc.get_anchor.device)
@@ -534,6 +535,9 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
     xyz, color, opacity, scaling, rot, neural_opacity, mask = out
     if _rows is not None:       # the visible anchor index once per offset, then through the expansion's selection mask
         _rows.append(vis_idx.repeat_interleave(K)[mask.reshape(-1)])
+    if _slots is not None:      # a * K + k of every (visible anchor, offset), then through the same mask
+        ak = vis_idx.to(torch.int32)[:, None] * K + torch.arange(K, dtype=torch.int32, device=vis_idx.device)
+        _slots.append(ak.reshape(-1)[mask.reshape(-1)])
 
     if is_training:                                                                      # :147-150
         return (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, 16, bit_per_feat_param,
@@ -592,7 +596,7 @@ class _DetachedCamera:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False,
-           step=0, *, return_aux=False, anchor_features=None):                          # :155-229
+           step=0, *, return_aux=False, anchor_features=None, contrib=None):            # :155-229
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
 
     return_aux=True: the dict also holds the rasterizer's "depth", "invdepth" and "alpha" maps ([1,H,W] each, see
@@ -602,6 +606,13 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     anchor_features: a float tensor [N, C] over all anchors (pc.get_anchor's row order), 1 <= C <= 32.  Every neural Gaussian
     carries its anchor's row and the dict gains "features" [C,H,W], the rasterizer's blend of them over a zero background
     (rasterizer.py).  The gradient reaches `anchor_features` (zero rows for anchors that are not visible) and the geometry.
+    In training mode such a call takes the unfused path, as return_aux does.
+
+    contrib: a rasterizer.GaussianContrib of N * K rows (N anchors in pc.get_anchor's order, K = pc.n_offsets; row a * K + k is
+    offset k of anchor a) that the view's per-Gaussian contribution statistics are accumulated into, or True for a fresh one.
+    The dict gains "contrib" (the object), "top_id" int32 [H,W] (the slot a * K + k of the Gaussian with the largest blending
+    weight at each pixel, -1 where there is none), "top_weight" [1,H,W] and "count" int32 [H,W] (rasterizer.py).  Rows of
+    anchors outside `visible_mask` and of offsets the selection mask drops are not touched.  Nothing of it is differentiable.
     In training mode such a call takes the unfused path, as return_aux does.
 
     A camera whose `world_view_transform`, `full_proj_transform` or `camera_center` requires a gradient (a trainable pose,
@@ -619,6 +630,20 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     if anchor_features is not None and (anchor_features.dim() != 2 or anchor_features.shape[0] != pc.get_anchor.shape[0]):
         raise ValueError(f"anchor_features must be [N, C] with N = {pc.get_anchor.shape[0]} anchors, "
                          f"got {tuple(anchor_features.shape)}")
+    slots = None
+    if contrib is not None and contrib is not False:
+        from .rasterizer import GaussianContrib
+        n_rows = pc.get_anchor.shape[0] * pc.n_offsets
+        if contrib is True:
+            contrib = GaussianContrib.zeros(n_rows, pc.get_anchor.device)
+        elif not isinstance(contrib, GaussianContrib):
+            raise ValueError(f"contrib must be a GaussianContrib or True, got {type(contrib).__name__}")
+        if len(contrib) != n_rows:
+            raise ValueError(f"contrib has {len(contrib)} rows for {pc.get_anchor.shape[0]} anchors x {pc.n_offsets} offsets "
+                             f"= {n_rows}")
+        slots = []
+    else:
+        contrib = None
     if is_training:
         # the expansion may run fused with the rasterizer's per-Gaussian stages (then `view.done` holds the rendered view
         # and xyz / color / opacity / rot are None: they never existed as tensors)
@@ -627,7 +652,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
          bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level) = \
             generate_neural_gaussians(gen_camera, pc, visible_mask, is_training=True, step=step,
                                       _view=None if (return_aux or view.raster_settings.antialiasing or cam_grad
-                                                     or rows is not None) else view, _rows=rows)
+                                                     or rows is not None or slots is not None) else view,
+                                      _rows=rows, _slots=slots)
         if view.done is not None:
             rendered_image, radii, screenspace_points = view.done
             return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
@@ -637,7 +663,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
                     "bit_per_offsets_param": bit_per_offsets_param, "bpp_per_level": bpp_per_level}
     else:
         xyz, color, opacity, scaling, rot, time_sub = generate_neural_gaussians(
-            gen_camera, pc, visible_mask, is_training=False, step=step, _rows=rows)
+            gen_camera, pc, visible_mask, is_training=False, step=step, _rows=rows, _slots=slots)
 
     screenspace_points = _zero_points(xyz)       # :168 `torch.zeros_like(xyz, requires_grad=True) + 0`
     if retain_grad:
@@ -647,11 +673,16 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
             pass
 
     rasterizer = GaussianRasterizer(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier))
-    if return_aux or rows is not None:
+    if return_aux or rows is not None or slots is not None:
         features = anchor_features.index_select(0, rows[0]) if rows is not None else None      # plumbing: plain torch
+        more = dict(contrib=contrib, contrib_slots=slots[0]) if slots is not None else {}
         rendered_image, radii, aux = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
                                                 opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None,
-                                                features=features, return_aux=return_aux)
+                                                features=features, return_aux=return_aux, **more)
+        if slots is not None:       # a Gaussian index means nothing outside this call: one gather to slot ids, -1 kept
+            tid = aux["top_id"].long()
+            table = torch.cat([slots[0], slots[0].new_full((1,), -1)])      # (index -1 reads the appended -1)
+            aux["top_id"] = table[tid]
     else:
         rendered_image, radii = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
                                            opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None)
@@ -664,7 +695,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     else:
         out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
                "radii": radii, "time_sub": time_sub}
-    if return_aux or rows is not None:
+    if return_aux or rows is not None or slots is not None:
         out.update(aux)
     return out
 

@@ -352,6 +352,38 @@ int cgs_raster_backward_feat(const cgs_raster_cfg *cfg, int64_t P,
                              const float *features, int32_t C,
                              const float *dL_dfeatures_map, float *dL_dfeatures);
 
+/* ---- per-Gaussian contribution statistics and top-contributor maps (csrc/raster_contrib.hip) ----
+ * The reverse direction of the maps above: how much each Gaussian mattered to the view (importance pruning, covisibility,
+ * picking).  For pixel p the contributors i are exactly those of the colour blend (same order, same alpha, same skip below
+ * 1/255, each pixel stopping where the colour pass stopped it; with CGS_RASTER_ANTIALIAS the records hold opacity * h) and
+ * w_i(p) = alpha_i T_i > 0 for a contributor, 0 otherwise.  Per Gaussian i, ACCUMULATED into caller-owned arrays that the call
+ * never zeroes (one set of arrays collects any number of views):
+ *   acc_weight     float   += sum_p w_i(p)
+ *   acc_max_weight float    = max(old, max_p w_i(p))      the array must hold values >= 0 (compared as bit patterns)
+ *   acc_pixels     int64   += number of pixels i contributed to
+ *   acc_top_pixels int64   += number of pixels where i has the largest w of all contributors (exact tie: the front-most)
+ * Per pixel, written for every pixel: out_top_id int32 [H, W] (index of that largest contributor in the call's Gaussian order,
+ * -1 where the pixel has none), out_top_weight float [H, W] (its w, 0 where none), out_count int32 [H, W] (contributors).
+ * Culled Gaussians and Gaussians that contributed nowhere leave their rows untouched.
+ *
+ * slot, int32 [P] or NULL: Gaussian i's four updates go to row slot[i] of accumulators of length n_slots (NULL: row i, and
+ * n_slots must equal P).  Several Gaussians may share a row; the updates are atomic either way.  out_top_id stays a Gaussian
+ * index.  Slot values are NOT range-checked on the device: 0 <= slot[i] < n_slots is the caller's contract.
+ *
+ * Enqueue after the cgs_raster_render / cgs_raster_render_spec of the view whose result the caller keeps, exactly as
+ * cgs_raster_render_aux (same workspaces, same R).  Any of the four accumulators and of the three maps may be NULL: it is not
+ * computed (with no accumulator among weight / max_weight / pixels the per-entry reduction does not run at all).  With R == 0,
+ * P == 0 or an empty view the maps are -1 / 0 / 0 and the accumulators are untouched.  acc_weight is summed with float atomics
+ * (not bit-reproducible); the other six results are exact.  With cfg->debug the call synchronises and checks after the kernel.
+ *
+ * CGS_ERR_ARG with a message, before anything is enqueued: P < 0 or R < 0, all seven outputs NULL, a NULL workspace, slot given
+ * with n_slots <= 0, n_slots != P without slot.  A short workspace: CGS_ERR_WORKSPACE. */
+int cgs_raster_contrib(const cgs_raster_cfg *cfg, int64_t P, int64_t num_rendered,
+                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws, size_t img_bytes,
+                       const int32_t *slot, int64_t n_slots,
+                       float *acc_weight, float *acc_max_weight, int64_t *acc_pixels, int64_t *acc_top_pixels,
+                       int32_t *out_top_id, float *out_top_weight, int32_t *out_count, void *stream);
+
 /* ---- gradients for the camera: viewmatrix, projmatrix, campos (csrc/raster_camera.hip) ----
  * The rasterizer reads the three tensors of cgs_raster_cfg independently (row-vector convention, M[4c+i] = row c, column i):
  *   viewmatrix V: the view-space position t = [p,1] V (the Jacobian of the projection, its 1.3 tanfov clamp, the depth
