@@ -213,24 +213,8 @@ __global__ void __launch_bounds__(AX_THREADS)
                 v[5] = gG;
                 v[6] = w * fmaf(-gI * r1.w, r1.w, gD);          // w (gD - gI / z^2)
                 v[7] = 0.f;
-                // transposing reduction inside each 16-lane row: lane `sub` < 8 of the row ends with the row's sum of v[sub]
-                const bool b0 = lane & 1, b1 = lane & 2;
-                float a4[4], b2[2];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float keep = b0 ? v[2 * q + 1] : v[2 * q], send = b0 ? v[2 * q] : v[2 * q + 1];
-                    a4[q] = keep + ax_dpp<0xB1>(send);
-                }
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const float keep = b1 ? a4[2 * q + 1] : a4[2 * q], send = b1 ? a4[2 * q] : a4[2 * q + 1];
-                    b2[q] = keep + ax_dpp<0x4E>(send);
-                }
-                b2[0] += ax_dpp<0x124>(b2[0]); b2[0] += ax_dpp<0x128>(b2[0]);
-                b2[1] += ax_dpp<0x124>(b2[1]); b2[1] += ax_dpp<0x128>(b2[1]);
-                asm volatile("" : "+v"(b2[0]), "+v"(b2[1]));
                 const int sub = lane & 15;
-                const float red = sub < 4 ? b2[0] : b2[1];
+                const float red = ax_row_transpose_sum(v, lane, sub);
                 if (has && sub < AX_NGRAD && red != 0.f) atomicAdd(&sacc[e][sub], red);
             }
         }
@@ -240,14 +224,7 @@ __global__ void __launch_bounds__(AX_THREADS)
                         a4 = sacc[tid][4], a5 = sacc[tid][5], a6 = sacc[tid][6];
             if (a0 != 0.f || a1 != 0.f || a2 != 0.f || a3 != 0.f || a4 != 0.f || a5 != 0.f || a6 != 0.f) {
                 const uint32_t g = gid_sorted[range.x + pos];
-                const float4 q0 = srec[tid * 2], q1 = srec[tid * 2 + 1];
-                const float cC = q1.x, op = q1.y;
-                atomicAdd(&dL_dmean2D_px[2 * (size_t)g], op * fmaf(2.f * q0.z, a0, q0.w * a1) * AX_INV_LOG2E);
-                atomicAdd(&dL_dmean2D_px[2 * (size_t)g + 1], op * fmaf(2.f * cC, a1, q0.w * a0) * AX_INV_LOG2E);
-                atomicAdd(&dL_dconic[3 * (size_t)g], -0.5f * op * a2);
-                atomicAdd(&dL_dconic[3 * (size_t)g + 1], -op * a3);
-                atomicAdd(&dL_dconic[3 * (size_t)g + 2], -0.5f * op * a4);
-                atomicAdd(&dL_dopacity[g], a5);
+                ax_flush_geom(g, srec[tid * 2], srec[tid * 2 + 1], a0, a1, a2, a3, a4, a5, dL_dmean2D_px, dL_dconic, dL_dopacity);
                 atomicAdd(&dL_dz[g], a6);
             }
         }

@@ -13,7 +13,7 @@
 // culling and per-row lists (raster_rows.h), run behind the colour pass of the view on what it left (gid_sorted, ranges,
 // tile_order, n_contrib, tile_last).  The records hold opacity * h under antialiasing, so nothing here knows of it.  In place
 // of a per-pixel accumulation, every visited entry is reduced over the 16 lanes (pixels) of its row: the sum and the maximum
-// of w with four DPP steps each, the count from the row's 16 bits of the ballot.  Lane 0 of the row adds the three into the
+// of w with four DPP steps each (ax_row_reduce), the count from the row's 16 bits of the ballot.  Lane 0 of the row adds the three into the
 // batch's LDS accumulator [256] x {float sum, uint max = the bit pattern of a float >= 0, uint count} with LDS atomics (up to
 // 16 rows meet on one entry); after the batch's walk thread `tid` flushes entry `tid` to global memory with one float
 // atomicAdd, one int atomicMax on the bit pattern and one 64-bit atomicAdd, if its count is non-zero.  Each lane also carries
@@ -40,26 +40,6 @@
 #else
 #define CT_NPART 1
 #endif
-
-namespace {
-
-// sum / maximum over the 16 lanes of a row, in every lane of the row (quad swaps, then row rotations by 4 and 8)
-__device__ __forceinline__ float ct_row_sum(float v) {
-    v += ax_dpp<0xB1>(v);
-    v += ax_dpp<0x4E>(v);
-    v += ax_dpp<0x124>(v);
-    v += ax_dpp<0x128>(v);
-    return v;
-}
-__device__ __forceinline__ float ct_row_max(float v) {
-    v = fmaxf(v, ax_dpp<0xB1>(v));
-    v = fmaxf(v, ax_dpp<0x4E>(v));
-    v = fmaxf(v, ax_dpp<0x124>(v));
-    v = fmaxf(v, ax_dpp<0x128>(v));
-    return v;
-}
-
-}  // namespace
 
 // ACC: the per-entry reduction and its flush (weight, max_weight, pixels); without it the walk only tracks each pixel's best.
 template <bool ACC>
@@ -148,7 +128,8 @@ __global__ void __launch_bounds__(AX_THREADS)
                 if (w > best_w) { best_w = w; best_pos = base_pos + e + 1u; }
                 if (ACC) {
                     const uint32_t rc = (uint32_t)__builtin_popcount((uint32_t)(hits >> row_shift) & 0xFFFFu);
-                    const float rs = ct_row_sum(w), rm = ct_row_max(w);
+                    const float rs = ax_row_reduce(w, [](float a, float b) { return a + b; });
+                    const float rm = ax_row_reduce(w, [](float a, float b) { return fmaxf(a, b); });
                     if ((lane & 15) == 0 && rc != 0u) {      // (rc != 0 implies `has`: the row's lanes share i and cnt)
                         atomicAdd(&ssum[part][e], rs);
                         atomicMax(&smax[part][e], __float_as_uint(rm));

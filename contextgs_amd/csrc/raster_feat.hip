@@ -236,27 +236,8 @@ __global__ void __launch_bounds__(AX_THREADS)
                 for (int c = 0; c < FT_BWD_NC; ++c) v[6 + c] = w * gF[c];
                 v[14] = 0.f;
                 v[15] = 0.f;
-                // transposing reduction inside each 16-lane row: lane `sub` of the row ends with the row's sum of v[sub]
-                const bool b0 = lane & 1, b1 = lane & 2;
-                float a8[8], b4[4];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float keep = b0 ? v[2 * q + 1] : v[2 * q], send = b0 ? v[2 * q] : v[2 * q + 1];
-                    a8[q] = keep + ax_dpp<0xB1>(send);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float keep = b1 ? a8[2 * q + 1] : a8[2 * q], send = b1 ? a8[2 * q] : a8[2 * q + 1];
-                    b4[q] = keep + ax_dpp<0x4E>(send);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    b4[q] += ax_dpp<0x124>(b4[q]);
-                    b4[q] += ax_dpp<0x128>(b4[q]);
-                }
-                asm volatile("" : "+v"(b4[0]), "+v"(b4[1]), "+v"(b4[2]), "+v"(b4[3]));
                 const int sub = lane & 15;
-                const float red = sub < 8 ? (sub < 4 ? b4[0] : b4[1]) : (sub < 12 ? b4[2] : b4[3]);
+                const float red = ax_row_transpose_sum(v, lane, sub);
                 if (has && sub < 6 + FT_BWD_NC && red != 0.f) atomicAdd(&sums[e * FT_NSUM + sub], red);
             }
         }
@@ -266,14 +247,7 @@ __global__ void __launch_bounds__(AX_THREADS)
             const float a0 = s0.x, a1 = s0.y, a2 = s0.z, a3 = s0.w, a4 = s1.x, a5 = s1.y;
             const float df[FT_BWD_NC] = {s1.z, s1.w, s2.x, s2.y, s2.z, s2.w, s3.x, s3.y};
             if (a0 != 0.f || a1 != 0.f || a2 != 0.f || a3 != 0.f || a4 != 0.f || a5 != 0.f) {
-                const float4 q0 = srec[tid * 2], q1 = srec[tid * 2 + 1];
-                const float cC = q1.x, op = q1.y;
-                atomicAdd(&dL_dmean2D_px[2 * (size_t)g_cur], op * fmaf(2.f * q0.z, a0, q0.w * a1) * AX_INV_LOG2E);
-                atomicAdd(&dL_dmean2D_px[2 * (size_t)g_cur + 1], op * fmaf(2.f * cC, a1, q0.w * a0) * AX_INV_LOG2E);
-                atomicAdd(&dL_dconic[3 * (size_t)g_cur], -0.5f * op * a2);
-                atomicAdd(&dL_dconic[3 * (size_t)g_cur + 1], -op * a3);
-                atomicAdd(&dL_dconic[3 * (size_t)g_cur + 2], -0.5f * op * a4);
-                atomicAdd(&dL_dopacity[g_cur], a5);
+                ax_flush_geom(g_cur, srec[tid * 2], srec[tid * 2 + 1], a0, a1, a2, a3, a4, a5, dL_dmean2D_px, dL_dconic, dL_dopacity);
             }
 #pragma unroll
             for (int c = 0; c < FT_BWD_NC; ++c)

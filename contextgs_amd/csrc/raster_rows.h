@@ -1,7 +1,8 @@
-// Device helpers of the row-mapped tile walks that run behind the colour pass (raster_aux.hip, raster_feat.hip): the colour
-// blend's alpha, the octagon block culling, the per-row entry lists and the lane -> pixel map.  raster_blend_rows.hip stays
-// byte-identical (hipcc's output for it moved when shared code was factored out of it), so what it defines as rb_* is restated
-// here under ax_* names.
+// Device helpers of the row-mapped tile walks that run behind the colour pass (raster_aux.hip, raster_feat.hip,
+// raster_contrib.hip): the colour blend's alpha, the octagon block culling, the per-row entry lists and the lane -> pixel map;
+// and, written once for the kernels that use them, the row reductions (ax_row_reduce, ax_row_transpose_sum) and the flush of
+// the backward kernels' geometry sums (ax_flush_geom).  raster_blend_rows.hip stays byte-identical (hipcc's output for it moved
+// when shared code was factored out of it), so what it defines as rb_* is restated here under ax_* names.
 #pragma once
 #include <hip/hip_fp16.h>
 #include "cgs_internal.h"
@@ -112,13 +113,66 @@ __device__ __forceinline__ uint32_t ax_list_build(AxLists &S, int blk, int lane,
     return total;
 }
 
-// maximum of n_contrib over the 16 pixels (lanes) of a row
-__device__ __forceinline__ uint32_t ax_row_max(uint32_t v) {
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false));
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false));
+// op over the 16 lanes of a row, in every lane of the row (quad swaps, then row rotations by 4 and 8); V = float or uint32_t
+template <int CTRL, class V>
+__device__ __forceinline__ V ax_row_move(V v) {
+    if constexpr (sizeof(V) == 4 && !__is_same(V, float)) return (V)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+    else return ax_dpp<CTRL>(v);
+}
+template <class V, class Op>
+__device__ __forceinline__ V ax_row_reduce(V v, Op op) {
+    v = op(v, ax_row_move<0xB1>(v));
+    v = op(v, ax_row_move<0x4E>(v));
+    v = op(v, ax_row_move<0x124>(v));
+    v = op(v, ax_row_move<0x128>(v));
     return v;
+}
+__device__ __forceinline__ uint32_t ax_row_max(uint32_t v) {
+    return ax_row_reduce(v, [](uint32_t a, uint32_t b) { return max(a, b); });
+}
+
+// Transposing sum inside each 16-lane row: lane sub = lane & 15 < N of the row returns the row's sum of v[sub] (N = 8 or 16).  Two
+// halving exchanges (lane ^ 1, lane ^ 2) leave N / 4 partials per lane, which the two rotations finish.
+template <int N>
+__device__ __forceinline__ float ax_row_transpose_sum(const float (&v)[N], int lane, int sub) {
+    const bool b0 = lane & 1, b1 = lane & 2;
+    float a[N / 2], b[N / 4];
+#pragma unroll
+    for (int q = 0; q < N / 2; ++q) {
+        const float keep = b0 ? v[2 * q + 1] : v[2 * q], send = b0 ? v[2 * q] : v[2 * q + 1];
+        a[q] = keep + ax_dpp<0xB1>(send);
+    }
+#pragma unroll
+    for (int q = 0; q < N / 4; ++q) {
+        const float keep = b1 ? a[2 * q + 1] : a[2 * q], send = b1 ? a[2 * q] : a[2 * q + 1];
+        b[q] = keep + ax_dpp<0x4E>(send);
+    }
+#pragma unroll
+    for (int q = 0; q < N / 4; ++q) {
+        b[q] += ax_dpp<0x124>(b[q]);
+        b[q] += ax_dpp<0x128>(b[q]);
+    }
+    if constexpr (N == 8) {
+        asm volatile("" : "+v"(b[0]), "+v"(b[1]));
+        return sub < 4 ? b[0] : b[1];
+    } else {
+        asm volatile("" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+        return sub < 8 ? (sub < 4 ? b[0] : b[1]) : (sub < 12 ? b[2] : b[3]);
+    }
+}
+
+// the flush of an entry's six geometry sums (gx, gy, gx dx, gx dy, gy dy, dL/dG) into the colour pass's accumulators;
+// q0, q1 = the entry's staged quads
+__device__ __forceinline__ void ax_flush_geom(uint32_t g, const float4 q0, const float4 q1, float a0, float a1, float a2,
+                                              float a3, float a4, float a5, float *__restrict__ dL_dmean2D_px,
+                                              float *__restrict__ dL_dconic, float *__restrict__ dL_dopacity) {
+    const float cC = q1.x, op = q1.y;
+    atomicAdd(&dL_dmean2D_px[2 * (size_t)g], op * fmaf(2.f * q0.z, a0, q0.w * a1) * AX_INV_LOG2E);
+    atomicAdd(&dL_dmean2D_px[2 * (size_t)g + 1], op * fmaf(2.f * cC, a1, q0.w * a0) * AX_INV_LOG2E);
+    atomicAdd(&dL_dconic[3 * (size_t)g], -0.5f * op * a2);
+    atomicAdd(&dL_dconic[3 * (size_t)g + 1], -op * a3);
+    atomicAdd(&dL_dconic[3 * (size_t)g + 2], -0.5f * op * a4);
+    atomicAdd(&dL_dopacity[g], a5);
 }
 
 }  // namespace

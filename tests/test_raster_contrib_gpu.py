@@ -433,6 +433,32 @@ def test_antialiasing_reads_the_compensated_opacity():
     assert abs(total - want) <= 1e-4 * want
 
 
+# ---- one walk with and without the per-entry reduction -------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["ragged", "long"])
+def test_maps_are_the_same_bits_without_the_accumulators(name):
+    """top_id / top_weight / count of a call that also asks for the accumulators (the kernel instance with the per-entry
+    reduction) against a maps-only call on the same workspaces (the instance without it; only the C entry point can ask for
+    that): bit-identical.  Ragged tiles (40x24), and more than two 256-entry batches in a tile."""
+    from contextgs_amd import _lib, rasterizer
+    cam, g = decomposed_scene(name)
+    P, H, W = g["means3D"].shape[0], cam.image_height, cam.image_width
+    out = _run(_settings(cam), g, contrib=True)
+    assert int(out["count"].sum()) > 0 and int(out["pixels"].sum()) == int(out["count"].sum())
+    lc = dict(rasterizer.last_call)
+    geom, binws, img = lc["geom_ws"], lc["bin_ws"], lc["img_ws"]
+    top_id = torch.full((H, W), -7, dtype=torch.int32, device="cuda")
+    top_w = torch.full((1, H, W), -7.0, device="cuda")
+    count = torch.full((H, W), -7, dtype=torch.int32, device="cuda")
+    _lib.check(_lib.lib().cgs_raster_contrib(lc["cfg"].ref, P, lc["bin_R"], _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
+                                             binws.numel(), _lib.ptr(img), img.numel(), None, P, None, None, None, None,
+                                             _lib.ptr(top_id), _lib.ptr(top_w), _lib.ptr(count), _lib.current_stream()),
+               "cgs_raster_contrib")
+    torch.cuda.synchronize()
+    assert torch.equal(top_id, out["top_id"])
+    assert torch.equal(top_w, out["top_weight"])
+    assert torch.equal(count, out["count"])
+
+
 # ---- empty views -------------------------------------------------------------------------------------------------------------
 def test_empty_view_and_no_gaussians():
     from contextgs_amd.rasterizer import GaussianContrib

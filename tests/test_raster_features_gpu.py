@@ -337,6 +337,27 @@ def test_forward_after_a_voided_speculative_render(oracle32):
     assert torch.equal(again["features"], out["features"])
 
 
+# ---- one walk for every instance ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scene", ["ragged 40x24", "long lists"])
+def test_a_channel_is_the_same_bits_in_every_instance(scene):
+    """One fixed column, blended as channel 0 of tables with C = 1, 5, 9, 17 (the 4-, 8-, 16- and 32-channel instances of the
+    forward kernel) whose other columns are random: channel 0 of the four maps is bit-identical, because every instance walks
+    the same entries in the same order and adds with the same fmaf.  Ragged tiles (40x24 = 3 x 2 tiles, cut right and bottom),
+    and the scene with more than two 256-entry batches per tile."""
+    cam, g = _scene(200, 40, 24, 3, 1.0, (0.02, 0.12)) if scene.startswith("ragged") else _stack_scene("long")
+    P = g["means3D"].shape[0]
+    rs = _settings(cam)
+    f = _table(P, 77, 1)
+    maps = {}
+    for C in (1, 5, 9, 17):
+        F = np.concatenate([f, _table(P, 78 + C, C - 1)], 1) if C > 1 else f
+        maps[C] = _run(rs, g, F=F)["features"]
+        assert maps[C].shape == (C, cam.image_height, cam.image_width)
+    assert float(maps[1].abs().max()) > 0
+    for C in (5, 9, 17):
+        assert torch.equal(maps[C][0], maps[1][0]), C
+
+
 # ---- the four argument forms --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("form", ["shs+scales", "shs+cov", "colors+cov"])
 def test_all_forms_match_colors_precomp_scales_rotations(form):
