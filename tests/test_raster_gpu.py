@@ -364,6 +364,38 @@ def bin_mode(request):
     _lib.check(L.cgs_debug_set_bin_mode(0), "cgs_debug_set_bin_mode")
 
 
+def _lists_three_ways(cam, g, H, W, what, small_cap=None):
+    """Three renders of one scene, each followed by _bin_compare (no differing list entry, no differing range word): with the
+    pair count known on the host, speculative (count read on the device, capacity from the first render), and speculative
+    with a capacity that is too small (the view is rendered again with the true count).  The three images are equal bit for
+    bit and the capacity bookkeeping of rasterizer.bin_and_blend holds.  small_cap: the forced capacity of the third render;
+    None = min(4097, R // 2), which is too small for EVERY scene, and the third render is then asserted to have been redone.
+    Returns (pair count, image of the first render)."""
+    from contextgs_amd import rasterizer as rz
+    rz._pair_capacity.pop((H, W), None)
+    first = _run_gpu(cam, g, (0.0, 0.0, 0.0))["color"]
+    diff, R, R_ws = _bin_compare()
+    assert diff == [0, 0] and R_ws == R, (diff, R, R_ws)
+    again = _run_gpu(cam, g, (0.0, 0.0, 0.0))["color"]              # speculative: the capacity comes from the first render
+    diff, R2, R_ws = _bin_compare()
+    assert diff == [0, 0] and R2 == R and R_ws == rz.pair_capacity_for(R), (diff, R2, R_ws)
+    assert (again == first).all()
+    cap = small_cap
+    if cap is None:
+        assert R >= 2, R
+        cap = min(4097, R // 2)
+    rz._pair_capacity[(H, W)] = cap
+    third = _run_gpu(cam, g, (0.0, 0.0, 0.0))["color"]
+    diff, R3, R_ws = _bin_compare()
+    assert diff == [0, 0] and R3 == R and R_ws == (R if R > cap else cap), (diff, R3, R_ws)
+    if small_cap is None:
+        assert R_ws == R, (R_ws, R)                                  # the speculative render overflowed: rendered again
+    print(f"[binning] {what}: {R} pairs")
+    assert rz._pair_capacity[(H, W)] == (rz.pair_capacity_for(R) if R > cap else cap)
+    assert (third == first).all()
+    return R, first
+
+
 @pytest.mark.parametrize("bin_mode", [1, 2], indirect=True)
 @pytest.mark.parametrize("P,W,H,scale_hi", [(4000, 256, 256, 0.05), (30000, 800, 800, 0.02), (20000, 1920, 1080, 0.08),
                                              (300, 97, 61, 0.4), (60000, 64, 64, 0.3), (50000, 1920, 1080, 0.5),
@@ -381,24 +413,192 @@ def test_tile_lists_equal_the_pair_sort(P, W, H, scale_hi, bin_mode):
     (multi-chunk buckets, masks of all 32 tiles), a 163 x 113 tile grid (more than 256 buckets: mode 2 falls back), odd grids
     (63 x 44, 21 x 49 tiles: partial buckets on both edges), a 128 x 32 grid of exactly 128 buckets with splats across all of it,
     and 200 000 tiny splats (one or two tiles each: bucket lists of a few entries per chunk)."""
-    from contextgs_amd import rasterizer as rz
     cam = look_at_camera((0.3, -3.0, 0.5), (0, 0, 0), W, H, fovx_deg=55.0)
     g = random_gaussians(P, seed=P, extent=1.0, scale_lo=0.003, scale_hi=scale_hi)
     if P == 60000:
         g["means3D"][1::2] = g["means3D"][0::2]
-    rz._pair_capacity.pop((H, W), None)
-    first = _run_gpu(cam, g, (0.0, 0.0, 0.0))["color"]
-    diff, R, R_ws = _bin_compare()
-    assert diff == [0, 0] and R_ws == R, (diff, R, R_ws)
-    again = _run_gpu(cam, g, (0.0, 0.0, 0.0))["color"]              # speculative: the capacity comes from the first render
-    diff, R2, R_ws = _bin_compare()
-    assert diff == [0, 0] and R2 == R and R_ws == rz.pair_capacity_for(R), (diff, R2, R_ws)
-    assert (again == first).all()
-    rz._pair_capacity[(H, W)] = 4097                                 # too small for all but the 28-tile case
-    third = _run_gpu(cam, g, (0.0, 0.0, 0.0))["color"]
-    diff, R3, R_ws = _bin_compare()
-    assert diff == [0, 0] and R3 == R and R_ws == (R if R > 4097 else 4097), (diff, R3, R_ws)
+    R, _ = _lists_three_ways(cam, g, H, W, f"mode {bin_mode}: P {P} {W}x{H}", small_cap=4097)   # too small for all but the 28-tile case
     assert R > 4097 or P == 300
-    print(f"[binning] mode {bin_mode}: P {P} {W}x{H}: {R} pairs")
-    assert rz._pair_capacity[(H, W)] == (rz.pair_capacity_for(R) if R > 4097 else 4097)
-    assert (third == first).all()
+
+
+# ---- every digit width of csrc/tile_bin.hip ----------------------------------------------------------------------------------
+def _ceil_log2(n):
+    bits = 0
+    while (1 << bits) < n:
+        bits += 1
+    return bits
+
+
+def _bin_dispatch(W, H):
+    """The dispatch of cgs_launch_tile_bin16 / cgs_launch_tile_bin_buckets (csrc/tile_bin.hip), restated: (tiles, tile_bits,
+    bits of the low pass, bits of the high pass (0: one pass), buckets of 8 x 4 tiles, bits of the bucket pass (None: more than
+    256 buckets, the two-level path is not taken))."""
+    tx, ty = (W + 15) // 16, (H + 15) // 16
+    tile_bits = _ceil_log2(tx * ty)
+    bits_b = tile_bits // 2 if tile_bits > 8 else 0
+    buckets = ((tx + 7) // 8) * ((ty + 3) // 4)
+    return tx * ty, tile_bits, tile_bits - bits_b, bits_b, buckets, (max(1, _ceil_log2(buckets)) if buckets <= 256 else None)
+
+
+DIGIT_GRIDS = [
+    # W, H (pixels), random Gaussians     tiles          tile_bits (low + high pass)   buckets -> bits of the bucket pass
+    (13, 11, 300),                      # 1 x 1          0  (the 8-bit instantiation)  1 -> 1
+    (27, 9, 300),                       # 2 x 1          1                             1 -> 1
+    (10, 41, 300),                      # 1 x 3          2                             1 -> 1
+    (5, 100, 300),                      # 1 x 7          3                             2 -> 1
+    (70, 40, 300),                      # 5 x 3          4                             1 -> 1
+    (40, 135, 300),                     # 3 x 9          5                             3 -> 2
+    (520, 10, 300),                     # 33 x 1         6  (2^5 + 1 tiles)            5 -> 3
+    (40, 170, 300),                     # 3 x 11         6  (2^5 + 1 tiles)            3 -> 2
+    (37, 630, 300),                     # 3 x 40         7                             10 -> 4
+    (230, 200, 300),                    # 15 x 13        8                             8 -> 3
+    (8000, 16, 300),                    # 500 x 1        9  (5 + 4)                    63 -> 6    rectangles up to 500 wide
+    (16, 8000, 300),                    # 1 x 500        9  (5 + 4)                    125 -> 7   rectangles 1 wide
+    (490, 460, 300),                    # 31 x 29        10 (5 + 5)                    32 -> 5
+    (715, 590, 300),                    # 45 x 37        11 (6 + 5)                    60 -> 6
+    (970, 840, 300),                    # 61 x 53        12 (6 + 6)                    112 -> 7
+    (2048, 1024, 300),                  # 128 x 64       13 (7 + 6)  2^13 tiles        256 -> 8
+    (2048, 2048, 300),                  # 128 x 128      14 (7 + 7)  2^14 tiles        512: radix passes in both modes
+    (2057, 2043, 300),                  # 129 x 128      15 (8 + 7)                    544: radix passes in both modes
+    (4096, 4096, 100),                  # 256 x 256      16 (8 + 8)  2^16 tiles        2048: radix passes in both modes
+]
+
+
+def _check_digit_grid_coverage():
+    """The coverage condition of test_tile_lists_every_digit_width: a grid list that drifts cannot silently drop a case"""
+    d = [_bin_dispatch(W, H) for W, H, _ in DIGIT_GRIDS]
+    assert {x[1] for x in d} == set(range(17)), sorted({x[1] for x in d})
+    assert {(x[2], x[3]) for x in d} == {(b, 0) for b in range(9)} | {(b - b // 2, b // 2) for b in range(9, 17)}
+    assert {x[5] for x in d} == set(range(1, 9)) | {None}, {x[5] for x in d}
+    assert any(x[4] == 1 for x in d)                                    # a grid of exactly one bucket
+    assert {8192, 16384, 65536, 33} <= {x[0] for x in d}                # 2^13, 2^14 (ranges_fix_kernel: per == 16), 2^16, 2^5 + 1
+    assert {(8000, 16), (16, 8000), (4096, 4096)} <= {(W, H) for W, H, _ in DIGIT_GRIDS}
+
+
+_check_digit_grid_coverage()
+
+
+def _long_side_camera(W, H):
+    """look_at_camera of the binning tests with the 55 degrees on the LONGER side of the image, so that a scene also spreads
+    along a 16 x 8000 pixel image"""
+    fovx = 2.0 * math.degrees(math.atan(math.tan(math.radians(27.5)) * W / max(W, H)))
+    return look_at_camera((0.3, -3.0, 0.5), (0, 0, 0), W, H, fovx_deg=fovx)
+
+
+def _splats_at(cam, u, v, depth, sigma_px, opacity, seed):
+    """Isotropic Gaussians whose centres project to the pixels (u, v) at view depths `depth` and whose footprints have a
+    standard deviation of sigma_px pixels (before the rasterizer's 0.3 dilation); arrays broadcast.  Random colours."""
+    W, H = cam.image_width, cam.image_height
+    tx, ty = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
+    u, v, depth, sigma_px, opacity = np.broadcast_arrays(*(np.atleast_1d(np.asarray(a, dtype=np.float64))
+                                                            for a in (u, v, depth, sigma_px, opacity)))
+    n = u.size
+    pc = np.stack([((2 * u + 1) / W - 1) * tx * depth, ((2 * v + 1) / H - 1) * ty * depth, depth, np.ones(n)], axis=1)
+    world = (pc @ np.linalg.inv(np.asarray(cam.world_view_transform, dtype=np.float64)))[:, :3]
+    s = sigma_px * depth * 2 * tx / W
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    return dict(means3D=f(world), scales=f(np.repeat(s[:, None], 3, axis=1)), rotations=f(np.tile([1.0, 0, 0, 0], (n, 1))),
+                colors=f(np.random.default_rng(seed).random((n, 3))), opacities=f(opacity[:, None]))
+
+
+def _join(parts, seed):
+    """the Gaussians of several scenes in ONE random order (ids are not in depth order)"""
+    g = {k: np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]}
+    perm = np.random.default_rng(seed).permutation(g["means3D"].shape[0])
+    return {k: np.ascontiguousarray(v[perm]) for k, v in g.items()}
+
+
+def _view_depth(cam, means3D):
+    wvt = np.asarray(cam.world_view_transform, dtype=np.float64)
+    return means3D.astype(np.float64) @ wvt[:3, 2] + wvt[3, 2]
+
+
+@pytest.mark.parametrize("bin_mode", [1, 2], indirect=True)
+@pytest.mark.parametrize("W,H,P", DIGIT_GRIDS, ids=[f"{W}x{H}" for W, H, _ in DIGIT_GRIDS])
+def test_tile_lists_every_digit_width(oracle32, W, H, P, bin_mode):
+    """One scene per tile_bits value 0 .. 16 (DIGIT_GRIDS: every instantiation of tb_scatter_kernel the two launchers of
+    csrc/tile_bin.hip can reach: one pass of 0 .. 8 bits, where 0 bits runs the 8-bit kernel on a histogram of one row, the
+    low / high passes 5+4 .. 8+8, bucket passes of 1 .. 8 bits), checked three ways by _lists_three_ways under both binnings.
+    A few hundred Gaussians that span several tiles plus three splats that cover the whole frame: every tile has a list, and on
+    grids of more than 4096 tiles those three own more pairs than one 4096-pair block each.  Grids of at most 64 tiles are also
+    compared with the fp32 oracle, so that the two binnings cannot agree on a wrong list there."""
+    nt, tile_bits, bits_a, bits_b, buckets, bucket_bits = _bin_dispatch(W, H)
+    cam = _long_side_camera(W, H)
+    full = _splats_at(cam, (W - 1) / 2, (H - 1) / 2, [2.6, 3.1, 3.6], 10.0 * max(W, H), 0.3, seed=tile_bits)
+    g = _join([random_gaussians(P, seed=1000 + tile_bits, extent=1.0, scale_lo=0.003, scale_hi=0.05), full], seed=tile_bits)
+    R, image = _lists_three_ways(cam, g, H, W, f"mode {bin_mode}: tile_bits {tile_bits} ({bits_a}+{bits_b}), {buckets} buckets "
+                                 f"({bucket_bits} bits), P {P + 3} {W}x{H}")
+    assert R >= 3 * nt, (R, nt)                                          # the three splats do cover every tile
+    if nt <= 64:
+        ref = oracle32.render(cam.oracle_dict(bg=(0.0, 0.0, 0.0)), **_kw(g))
+        _check_image(image, ref["color"], f"digit widths mode {bin_mode} {W}x{H}")
+
+
+# ---- Gaussians without pairs -------------------------------------------------------------------------------------------------
+# (csrc/raster_pre.h gives a Gaussian that touches no tile the depth key of a culled one: wherever such Gaussians lie in
+#  depth, the depth order the binning walks has them behind every Gaussian with pairs.  These scenes pin that the lists do not
+#  depend on where they lie, and the block arithmetic of the pair-generating pass around runs of them.)
+@pytest.mark.parametrize("bin_mode", [1, 2], indirect=True)
+@pytest.mark.parametrize("W,H", [(512, 512), (437, 291)])
+def test_tile_lists_with_zero_pair_runs(oracle32, W, H, bin_mode):
+    """22 000 random Gaussians; runs that are contiguous in view depth get an opacity of 0.003 (255 * opacity < 1: no tile, no
+    pair): 256 at the very front, then 1, 255, 257 and 4096 between stretches of live Gaussians, and 10 000 at the very back.
+    Lists checked three ways under both binnings, the image against the fp32 oracle, and the scene WITHOUT the zero-pair
+    Gaussians has the same pair count and the same image, bit for bit."""
+    P = 22000
+    cam = _long_side_camera(W, H)
+    g = random_gaussians(P, seed=81, extent=1.0, scale_lo=0.003, scale_hi=0.05)
+    z = _view_depth(cam, g["means3D"])
+    order = np.argsort(z, kind="stable")
+    runs = [256, 1, 255, 257, 4096, 10000]
+    gap = (P - sum(runs)) // (len(runs) - 1)
+    dead = np.zeros(P, dtype=bool)                                       # in depth order
+    pos, edges = 0, []
+    for n in runs[:-1]:
+        dead[pos:pos + n] = True
+        edges += [pos, pos + n]
+        pos += n + gap
+    dead[P - runs[-1]:] = True
+    edges += [P - runs[-1]]
+    assert pos <= P - runs[-1] and int(dead.sum()) == sum(runs)
+    zs = z[order]
+    # the runs are what they are meant to be in the rasterizer's fp32 depths too: no near-tie across an end of a run
+    assert all(zs[e] - zs[e - 1] > 1e-5 for e in edges if e > 0), [float(zs[e] - zs[e - 1]) for e in edges if e > 0]
+    g["opacities"][order[dead]] = 0.003
+    R, image = _lists_three_ways(cam, g, H, W, f"mode {bin_mode}: zero-pair runs in depth, P {P} {W}x{H}")
+    assert R > 3 * 4096, R
+    ref = oracle32.render(cam.oracle_dict(bg=(0.0, 0.0, 0.0)), **_kw(g))
+    _check_image(image, ref["color"], f"zero-pair runs mode {bin_mode} {W}x{H}")
+    from contextgs_amd.rasterizer import last_call
+    live = np.sort(order[~dead])
+    only = _run_gpu(cam, {k: np.ascontiguousarray(v[live]) for k, v in g.items()}, (0.0, 0.0, 0.0))["color"]
+    assert int(last_call["num_rendered"]) == R
+    assert (only == image).all()
+
+
+BLOCK_SCENES = [(k, Z, True) for k in (4095, 4096, 4097, 8192) for Z in (1, 300, 5000)] + [(8192, 5000, False), (8193, 5000, False)]
+
+
+@pytest.mark.parametrize("bin_mode", [1, 2], indirect=True)
+@pytest.mark.parametrize("W,H", [(512, 512), (500, 300)])
+@pytest.mark.parametrize("k,Z,cover", BLOCK_SCENES)
+def test_tile_lists_with_zero_pair_runs_at_block_boundaries(k, Z, cover, W, H, bin_mode):
+    """A pair count known exactly, straight-on camera: k splats of ONE tile each nearest the camera (isotropic, sigma 1 pixel, on
+    the centre of a tile that lies fully inside the image: the alpha >= 1/255 box of +-3.8 pixels stays inside the tile; tiles are
+    reused), behind them Z Gaussians without pairs (opacity 0.003), behind those (cover) one splat over all nt tiles: k + nt pairs,
+    the first pair of a Gaussian that owns several 4096-pair blocks one before, on and one after a block boundary.
+    Without the cover: 8192 pairs (an exact multiple of 4096: the last block's walk to P - 1 passes Gaussians without pairs only)
+    and 8193."""
+    cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), W, H, fovx_deg=55.0)
+    nt = ((W + 15) // 16) * ((H + 15) // 16)
+    fx, fy = W // 16, H // 16                                            # tiles fully inside the image
+    rng = np.random.default_rng(k * 7 + Z)
+    t = np.arange(k) % (fx * fy)
+    parts = [_splats_at(cam, 16 * (t % fx) + 7.5, 16 * (t // fx) + 7.5, 1.0 + 1e-4 * np.arange(k), 1.0, 0.9, seed=k),
+             _splats_at(cam, rng.uniform(0, W - 1, Z), rng.uniform(0, H - 1, Z), 2.0 + 1e-4 * np.arange(Z), 1.0, 0.003, seed=Z)]
+    if cover:
+        parts.append(_splats_at(cam, (W - 1) / 2, (H - 1) / 2, 3.0, 10.0 * max(W, H), 0.9, seed=1))
+    g = _join(parts, seed=k + Z)
+    R, _ = _lists_three_ways(cam, g, H, W, f"mode {bin_mode}: {k} one-tile splats, {Z} without pairs, cover {cover}, {W}x{H} "
+                             f"({nt} tiles)")
+    assert R == k + (nt if cover else 0), (R, k, nt)
