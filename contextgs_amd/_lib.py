@@ -83,6 +83,11 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                                          c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
                                         [c_void_p, c_size_t, c_void_p, C.c_uint32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "cgs_raster_bwd_abs_scratch_bytes": (c_size_t, [c_int64]),
+    "cgs_raster_backward_abs": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
+                                       [c_void_p, c_size_t, c_void_p, C.c_uint32, c_void_p, c_int32, c_void_p, c_void_p]),
     "cgs_raster_contrib": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                    c_size_t, c_void_p, c_int64] + [c_void_p] * 8),
     "cgs_raster_camera_bytes": (c_size_t, [c_int64]),
@@ -248,6 +253,7 @@ SIGNATURES = {
     "cgs_prof_name": (C.c_char_p, [c_int]),
     "cgs_prof_read": (c_int, [c_int, C.POINTER(C.c_double), C.POINTER(c_int64)]),
     "cgs_densify_stats": (c_int, [c_int64, c_int] + [c_void_p] * 11),
+    "cgs_densify_stats_ex": (c_int, [c_int64, c_int] + [c_void_p] * 11 + [c_int32, c_int32]),
     "cgs_nonzero_scratch_bytes": (c_size_t, [c_int64]),
     "cgs_nonzero_launch": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p, C.POINTER(C.c_uint64)]),
     "cgs_nonzero_wait": (c_int, [C.c_uint64, C.POINTER(c_int64)]),

@@ -669,6 +669,11 @@ extern "C" size_t cgs_raster_bwd_aux_scratch_bytes(int64_t P) {
     const size_t n = (size_t)(P > 0 ? P : 1);
     return cgs_raster_bwd_scratch_bytes(P) + cgs_align_up(n * sizeof(float), 256);
 }
+// the aux scratch, then the [P, 2] sums of |dL_p/d(pixel mean)| of cgs_raster_backward_abs
+extern "C" size_t cgs_raster_bwd_abs_scratch_bytes(int64_t P) {
+    const size_t n = (size_t)(P > 0 ? P : 1);
+    return cgs_raster_bwd_aux_scratch_bytes(P) + cgs_align_up(2 * n * sizeof(float), 256);
+}
 
 // Enqueued after the view's cgs_raster_render / _render_spec that the caller kept (R = the count its binning workspace was
 // carved with): reads the lists, n_contrib, tile_last and final_T that render left.
@@ -714,7 +719,7 @@ static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, i
                                     float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities, float *dL_dshs,
                                     float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *scratch, size_t scratch_bytes,
                                     hipStream_t stream, bool aa, const float *features = nullptr, int32_t C = 0,
-                                    const float *dL_dfeatures_map = nullptr, float *dL_dfeatures = nullptr) {
+                                    const float *dL_dfeatures_map = nullptr, float *dL_dfeatures = nullptr, bool absgrad = false) {
     int rc = check_cfg(cfg);
     if (rc) return rc;
     if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
@@ -736,8 +741,10 @@ static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, i
         cgs_set_error("%s: NULL input", fn);
         return CGS_ERR_ARG;
     }
-    if (scratch_bytes < cgs_raster_bwd_aux_scratch_bytes(P)) {
-        cgs_set_error("%s: scratch too small: %zu < %zu", fn, scratch_bytes, cgs_raster_bwd_aux_scratch_bytes(P));
+    // absgrad (cgs_raster_backward_abs): dL_dmeans2D is [P, 4] and the scratch carries the absolute accumulator behind dL/dz
+    const size_t scratch_need = absgrad ? cgs_raster_bwd_abs_scratch_bytes(P) : cgs_raster_bwd_aux_scratch_bytes(P);
+    if (scratch_bytes < scratch_need) {
+        cgs_set_error("%s: scratch too small: %zu < %zu", fn, scratch_bytes, scratch_need);
         return CGS_ERR_WORKSPACE;
     }
     CgsGeom g;
@@ -753,9 +760,11 @@ static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, i
     float *d_mean_px = (float *)scratch;
     float *d_conic = (float *)((char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
     float *d_z = (float *)((char *)scratch + cgs_raster_bwd_scratch_bytes(P));
-    CGS_CHECK_HIP(hipMemsetAsync(scratch, 0, cgs_raster_bwd_aux_scratch_bytes(P), stream));
+    float *d_abs = absgrad ? (float *)((char *)scratch + cgs_raster_bwd_aux_scratch_bytes(P)) : nullptr;
+    CGS_CHECK_HIP(hipMemsetAsync(scratch, 0, scratch_need, stream));
     if (R > 0) {
-        if (dL_dout && (rc = cgs_launch_blend_bwd(cfg, g, b, im, dL_dout, d_mean_px, d_conic, dL_dopacities, dL_dcolors, stream)))
+        if (dL_dout &&
+            (rc = cgs_launch_blend_bwd(cfg, g, b, im, dL_dout, d_mean_px, d_conic, dL_dopacities, dL_dcolors, stream, d_abs)))
             return rc;
         if (aux && (rc = cgs_launch_aux_bwd(cfg, g, b, im, dL_ddepth, dL_dinvdepth, dL_dalpha, d_mean_px, d_conic, dL_dopacities,
                                             d_z, stream)))
@@ -771,11 +780,11 @@ static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, i
     float *aa_dop = aa ? dL_dopacities : nullptr;
     if (!shs && !cov3D)
         rc = cgs_launch_preprocess_bwd(cfg, P, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dmeans3D,
-                                       dL_dmeans2D, dL_dscales, dL_drotations, stream, aa_op, aa_dop);
+                                       dL_dmeans2D, dL_dscales, dL_drotations, stream, aa_op, aa_dop, d_abs);
     else
         rc = cgs_launch_preprocess_bwd_form(cfg, P, f, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dcolors,
                                             dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_op,
-                                            aa_dop);
+                                            aa_dop, d_abs);
     if (rc) return rc;
     return aux ? cgs_launch_aux_dz_chain(cfg, P, radii, d_z, dL_dmeans3D, stream) : CGS_OK;
 }
@@ -911,6 +920,27 @@ extern "C" int cgs_raster_backward_feat(const cgs_raster_cfg *cfg, int64_t P, in
                                     dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
                                     dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_,
                                     (opts & CGS_RASTER_ANTIALIAS) != 0, features, C, dL_dfeatures_map, dL_dfeatures);
+}
+
+// cgs_raster_backward_feat with dL_dmeans2D [P, 4]: columns 2:4 are the sums over the pixels of |dL_p/d(2-D mean)| of the colour
+// image (the ABS instance of the blend backward; include/cgs.h).  Every other result is cgs_raster_backward_feat's.
+extern "C" int cgs_raster_backward_abs(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts,
+                                       const float *features, int32_t C, const float *dL_dfeatures_map, float *dL_dfeatures) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if ((rc = check_opts("cgs_raster_backward_abs", opts))) return rc;
+    return raster_backward_aux_impl("cgs_raster_backward_abs", cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities,
+                                    scales, rotations, cov3D, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout,
+                                    dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
+                                    dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_,
+                                    (opts & CGS_RASTER_ANTIALIAS) != 0, features, C, dL_dfeatures_map, dL_dfeatures, true);
 }
 
 // ---- camera gradients (csrc/raster_camera.hip) ---------------------------------------------------------------------------

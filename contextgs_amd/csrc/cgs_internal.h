@@ -145,20 +145,23 @@ int cgs_launch_blend_fwd_rows(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, 
                               hipStream_t stream);
 int cgs_launch_blend_bwd_rows(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const float *dL_dout,
                               float *dL_dmean2D_px, float *dL_dconic, float *dL_dopacity, float *dL_dcolors,
-                              hipStream_t stream);
+                              hipStream_t stream, float *dL_dabs_px = nullptr);
 int cgs_launch_tile_order(const cgs_raster_cfg *cfg, CgsImg &im, hipStream_t stream);      // raster_blend_rows.hip
 int cgs_launch_blend_fwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im,
                          float *out_color, hipStream_t stream);
 int cgs_launch_blend_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im,
                          const float *dL_dout, float *dL_dmean2D_px, float *dL_dconic,
-                         float *dL_dopacity, float *dL_dcolors, hipStream_t stream);
+                         float *dL_dopacity, float *dL_dcolors, hipStream_t stream, float *dL_dabs_px = nullptr);
+// (dL_dabs_px != NULL: the blend backward's ABS instance, which also sums |dL_p/d(pixel mean)| over the pixels into [P, 2])
 int cgs_launch_preprocess_bwd(const cgs_raster_cfg *cfg, int64_t P, const float *means3D,
                               const float *scales, const float *rotations,
                               const int32_t *radii, const float *dL_dmean2D_px,
                               const float *dL_dconic, float *dL_dmeans3D, float *dL_dmeans2D,
                               float *dL_dscales, float *dL_drotations, hipStream_t stream,
-                              const float *aa_opacities = nullptr, float *aa_dL_dopacities = nullptr);
+                              const float *aa_opacities = nullptr, float *aa_dL_dopacities = nullptr,
+                              const float *dL_dabs_px = nullptr);
 // (aa_opacities != NULL: antialiasing; aa_dL_dopacities holds dL/d(op_eff) and is rewritten to dL/d(opacity))
+// (dL_dabs_px != NULL: dL_dmeans2D is [P, 4], columns 2:4 = the absolute sums of dL_dabs_px [P, 2] times 0.5 W, 0.5 H)
 
 // expand_raster.hip: the anchor expansion fused with the rasterizer's preprocess stage
 struct CgsExpandSrc {

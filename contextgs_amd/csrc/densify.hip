@@ -5,12 +5,16 @@
 // element written by exactly one thread (no atomics).
 #include "cgs_internal.h"
 
+// EX (cgs_densify_stats_ex): rows of `grad` are grad_stride floats and the norm is taken over columns grad_col, grad_col + 1;
+// the default instance reads [*, 3] rows, columns 0 and 1, and neither argument.
+template <bool EX>
 __global__ void __launch_bounds__(256)
     densify_stats_kernel(int64_t n_slots, int K, const int64_t *__restrict__ vis_idx, const float *__restrict__ opacity,
                          const uint8_t *__restrict__ sel, const int64_t *__restrict__ sel_pos,
                          const uint8_t *__restrict__ update_filter, const float *__restrict__ grad,
                          float *__restrict__ opacity_accum, float *__restrict__ anchor_demon,
-                         float *__restrict__ offset_gradient_accum, float *__restrict__ offset_denom) {
+                         float *__restrict__ offset_gradient_accum, float *__restrict__ offset_denom, int grad_stride,
+                         int grad_col) {
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= n_slots) return;
     const int64_t a = s / K;
@@ -19,7 +23,8 @@ __global__ void __launch_bounds__(256)
     if (sel[s]) {
         const int64_t j = sel_pos[s];                     // index of this slot's Gaussian among the selected ones
         if (update_filter[j]) {
-            const float gx = grad[3 * j], gy = grad[3 * j + 1];
+            const float *row = EX ? grad + grad_stride * j + grad_col : grad + 3 * j;
+            const float gx = row[0], gy = row[1];
             offset_gradient_accum[anchor * K + k] += sqrtf(gx * gx + gy * gy);      // ||grad[:, :2]||  (:710)
             offset_denom[anchor * K + k] += 1.f;
         }
@@ -32,11 +37,15 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-extern "C" int cgs_densify_stats(int64_t n_vis, int K, const int64_t *vis_idx, const float *opacity, const uint8_t *sel,
-                                 const int64_t *sel_pos, const uint8_t *update_filter, const float *grad,
-                                 float *opacity_accum, float *anchor_demon, float *offset_gradient_accum,
-                                 float *offset_denom, void *stream) {
+static int densify_stats_impl(int64_t n_vis, int K, const int64_t *vis_idx, const float *opacity, const uint8_t *sel,
+                              const int64_t *sel_pos, const uint8_t *update_filter, const float *grad,
+                              float *opacity_accum, float *anchor_demon, float *offset_gradient_accum,
+                              float *offset_denom, void *stream, bool ex, int32_t grad_stride, int32_t grad_col) {
     if (n_vis < 0 || K < 1) { cgs_set_error("densify_stats: bad args"); return CGS_ERR_ARG; }
+    if (ex && (grad_stride < 2 || grad_col < 0 || grad_col + 2 > grad_stride)) {
+        cgs_set_error("densify_stats_ex: columns %d, %d outside rows of %d floats", grad_col, grad_col + 1, grad_stride);
+        return CGS_ERR_ARG;
+    }
     if (n_vis == 0) return CGS_OK;
     if (!vis_idx || !opacity || !sel || !sel_pos || !update_filter || !grad || !opacity_accum || !anchor_demon ||
         !offset_gradient_accum || !offset_denom) {
@@ -44,11 +53,34 @@ extern "C" int cgs_densify_stats(int64_t n_vis, int K, const int64_t *vis_idx, c
         return CGS_ERR_ARG;
     }
     const int64_t n = n_vis * K;
-    hipLaunchKernelGGL(densify_stats_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, K,
-                       vis_idx, opacity, sel, sel_pos, update_filter, grad, opacity_accum, anchor_demon,
-                       offset_gradient_accum, offset_denom);
+    if (ex)
+        hipLaunchKernelGGL(densify_stats_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, K,
+                           vis_idx, opacity, sel, sel_pos, update_filter, grad, opacity_accum, anchor_demon,
+                           offset_gradient_accum, offset_denom, grad_stride, grad_col);
+    else
+        hipLaunchKernelGGL(densify_stats_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, K,
+                           vis_idx, opacity, sel, sel_pos, update_filter, grad, opacity_accum, anchor_demon,
+                           offset_gradient_accum, offset_denom, 3, 0);
     CGS_CHECK_HIP(hipGetLastError());
     return CGS_OK;
+}
+
+extern "C" int cgs_densify_stats(int64_t n_vis, int K, const int64_t *vis_idx, const float *opacity, const uint8_t *sel,
+                                 const int64_t *sel_pos, const uint8_t *update_filter, const float *grad,
+                                 float *opacity_accum, float *anchor_demon, float *offset_gradient_accum,
+                                 float *offset_denom, void *stream) {
+    return densify_stats_impl(n_vis, K, vis_idx, opacity, sel, sel_pos, update_filter, grad, opacity_accum, anchor_demon,
+                              offset_gradient_accum, offset_denom, stream, false, 3, 0);
+}
+
+// cgs_densify_stats on a gradient whose rows are grad_stride floats, the norm over columns grad_col, grad_col + 1 (the
+// absolute columns 2, 3 of cgs_raster_backward_abs's [P, 4] dL_dmeans2D)
+extern "C" int cgs_densify_stats_ex(int64_t n_vis, int K, const int64_t *vis_idx, const float *opacity, const uint8_t *sel,
+                                    const int64_t *sel_pos, const uint8_t *update_filter, const float *grad,
+                                    float *opacity_accum, float *anchor_demon, float *offset_gradient_accum,
+                                    float *offset_denom, void *stream, int32_t grad_stride, int32_t grad_col) {
+    return densify_stats_impl(n_vis, K, vis_idx, opacity, sel, sel_pos, update_filter, grad, opacity_accum, anchor_demon,
+                              offset_gradient_accum, offset_denom, stream, true, grad_stride, grad_col);
 }
 
 // ---- anchor pruning / growing surgery (scene/gaussian_model.py:673-760, `cat_tensors_to_optimizer`,

@@ -73,11 +73,11 @@ int cgs_launch_blend_fwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsIm
 
 int cgs_launch_blend_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const float *dL_dout,
                          float *dL_dmean2D_px, float *dL_dconic, float *dL_dopacity, float *dL_dcolors,
-                         hipStream_t stream) {
+                         hipStream_t stream, float *dL_dabs_px) {
     const int tx = cgs_tiles_x(cfg), ty = cgs_tiles_y(cfg);
     CgsProfScope prof(CGS_PROF_BLEND_BWD, stream);
     (void)tx; (void)ty;
-    return cgs_launch_blend_bwd_rows(cfg, g, b, im, dL_dout, dL_dmean2D_px, dL_dconic, dL_dopacity, dL_dcolors, stream);
+    return cgs_launch_blend_bwd_rows(cfg, g, b, im, dL_dout, dL_dmean2D_px, dL_dconic, dL_dopacity, dL_dcolors, stream, dL_dabs_px);
 }
 
 // R_eff / non-empty tile statistics for the roofline accounting.

@@ -259,6 +259,12 @@ __global__ void __launch_bounds__(RB_THREADS)
     if (tid == 0) tile_last[tile] = max(max(wave_last[0], wave_last[1]), max(wave_last[2], wave_last[3]));
 }
 
+// ABS: the opt-in instance of cgs_raster_backward_abs.  Besides everything the default instance sums it accumulates, per
+// Gaussian, sum_p |dL_p/d(pixel mean x)| and sum_p |dL_p/d(pixel mean y)| over the same (pixel, Gaussian) visits with the
+// same alphas (AbsGS's densification statistic) into dL_dabs_px [P, 2]: two more values per visit in the free places of the
+// reduction's third group, two more accumulator columns (11 x 256 floats: 24.6 KB of LDS, six workgroups per CU).  The default
+// instance never reads dL_dabs_px.
+template <bool ABS>
 __global__ void __launch_bounds__(RB_THREADS)
     blend_bwd_rows_kernel(int W, int H, int tiles_x, const uint2 *__restrict__ ranges,
                           const uint32_t *__restrict__ gid_sorted, const float4 *__restrict__ rec,
@@ -266,13 +272,15 @@ __global__ void __launch_bounds__(RB_THREADS)
                           const uint32_t *__restrict__ n_contrib, const uint32_t *__restrict__ tile_last,
                           const float *__restrict__ dL_dout, float *__restrict__ dL_dmean2D_px,
                           float *__restrict__ dL_dconic, float *__restrict__ dL_dopacity,
-                          float *__restrict__ dL_dcolors, const uint32_t *__restrict__ tile_order) {
+                          float *__restrict__ dL_dcolors, const uint32_t *__restrict__ tile_order,
+                          float *__restrict__ dL_dabs_px) {
+    constexpr int NG = ABS ? RB_NGRAD + 2 : RB_NGRAD;
     // 22.6 KB of LDS per workgroup = seven workgroups per CU: two float4 per record plus its blue component (the third
     // float4 only carries cull extents the staging thread has in registers), no copy of the Gaussian ids (the flush reads
     // gid_sorted again)
     __shared__ float4 srec[RB_THREADS * 2];
     __shared__ float sblue[RB_THREADS];
-    __shared__ float sacc[RB_THREADS][RB_NGRAD];
+    __shared__ float sacc[RB_THREADS][NG];
     __shared__ RbLists S;
 
     const int tile = (int)tile_order[blockIdx.x];        // longest lists first (tile_order_kernel)
@@ -330,7 +338,7 @@ __global__ void __launch_bounds__(RB_THREADS)
             p0 = rec[3 * (size_t)pg]; p1 = rec[3 * (size_t)pg + 1]; p2 = rec[3 * (size_t)pg + 2];
         }
 #pragma unroll
-        for (int k = 0; k < RB_NGRAD; ++k) sacc[tid][k] = 0.f;
+        for (int k = 0; k < NG; ++k) sacc[tid][k] = 0.f;
         S.smask[tid] = (uint16_t)m16;
         __syncthreads();
 
@@ -395,9 +403,20 @@ __global__ void __launch_bounds__(RB_THREADS)
                     const float keep = b1 ? a4[2 * q + 1] : a4[2 * q], send = b1 ? a4[2 * q] : a4[2 * q + 1];
                     b2[q] = keep + rb_dpp<0x4E>(send);
                 }
-                float c8 = v[8];
-                c8 += rb_dpp<0xB1>(c8);
-                c8 += rb_dpp<0x4E>(c8);
+                float c8;
+                if constexpr (ABS) {
+                    // third group of the transposing reduction: v[8], |d/d mean x|, |d/d mean y| and a free place end up
+                    // in lanes 8..11 of the row (A, B, C = r0.z, r0.w, r1.x: the scaled conic of the record)
+                    const float ax = fabsf(fmaf(2.f * r0.z, gx, r0.w * gy)), ay = fabsf(fmaf(2.f * r1.x, gy, r0.w * gx));
+                    const float k0 = b0 ? ax : v[8], s0 = b0 ? v[8] : ax;
+                    const float k1 = b0 ? 0.f : ay, s1 = b0 ? ay : 0.f;
+                    const float t0 = k0 + rb_dpp<0xB1>(s0), t1 = k1 + rb_dpp<0xB1>(s1);
+                    c8 = (b1 ? t1 : t0) + rb_dpp<0x4E>(b1 ? t0 : t1);
+                } else {
+                    c8 = v[8];
+                    c8 += rb_dpp<0xB1>(c8);
+                    c8 += rb_dpp<0x4E>(c8);
+                }
                 b2[0] += rb_dpp<0x124>(b2[0]); b2[0] += rb_dpp<0x128>(b2[0]);
                 b2[1] += rb_dpp<0x124>(b2[1]); b2[1] += rb_dpp<0x128>(b2[1]);
                 c8 += rb_dpp<0x124>(c8); c8 += rb_dpp<0x128>(c8);
@@ -409,7 +428,7 @@ __global__ void __launch_bounds__(RB_THREADS)
                 // (red != 0: a row whose 16 pixels took nothing from its entry — the wave goes on while ANY row has a contribution —
                 //  would add nine zeros through the LDS float-atomic unit, the kernel's second bound: -6 %, same sums bit for bit;
                 //  profiles/r05_blend_bwd_ablations.txt)
-                if (has && sub < RB_NGRAD && red != 0.f) atomicAdd(&sacc[e][sub], red);
+                if (has && sub < NG && red != 0.f) atomicAdd(&sacc[e][sub], red);
             }
         }
         __syncthreads();
@@ -417,8 +436,10 @@ __global__ void __launch_bounds__(RB_THREADS)
             const float a0 = sacc[tid][0], a1 = sacc[tid][1], a2 = sacc[tid][2], a3 = sacc[tid][3],
                         a4 = sacc[tid][4], a5 = sacc[tid][5], a6 = sacc[tid][6], a7 = sacc[tid][7],
                         a8 = sacc[tid][8];
+            float a9 = 0.f, a10 = 0.f;       // the two absolute sums (>= 0)
+            if constexpr (ABS) { a9 = sacc[tid][NG - 2]; a10 = sacc[tid][NG - 1]; }
             if (a0 != 0.f || a1 != 0.f || a2 != 0.f || a3 != 0.f || a4 != 0.f || a5 != 0.f || a6 != 0.f ||
-                a7 != 0.f || a8 != 0.f) {
+                a7 != 0.f || a8 != 0.f || a9 != 0.f || a10 != 0.f) {
                 const uint32_t g = gid_sorted[range.x + pos];
                 const float4 q0 = srec[tid * 2], q1 = srec[tid * 2 + 1];
                 const float cC = q1.x, op = q1.y;
@@ -431,6 +452,10 @@ __global__ void __launch_bounds__(RB_THREADS)
                 atomicAdd(&dL_dcolors[3 * (size_t)g], a6);
                 atomicAdd(&dL_dcolors[3 * (size_t)g + 1], a7);
                 atomicAdd(&dL_dcolors[3 * (size_t)g + 2], a8);
+                if constexpr (ABS) {
+                    if (a9 != 0.f) atomicAdd(&dL_dabs_px[2 * (size_t)g], op * a9 * RB_INV_LOG2E);
+                    if (a10 != 0.f) atomicAdd(&dL_dabs_px[2 * (size_t)g + 1], op * a10 * RB_INV_LOG2E);
+                }
             }
         }
     }
@@ -543,15 +568,24 @@ int cgs_launch_blend_fwd_rows(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, 
     return CGS_OK;
 }
 
+// dL_dabs_px != NULL: the ABS instance, which also adds into dL_dabs_px [P, 2]
 int cgs_launch_blend_bwd_rows(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const float *dL_dout,
                               float *dL_dmean2D_px, float *dL_dconic, float *dL_dopacity, float *dL_dcolors,
-                              hipStream_t stream) {
+                              hipStream_t stream, float *dL_dabs_px) {
     const int tx = cgs_tiles_x(cfg), ty = cgs_tiles_y(cfg);
     const float4 *rec = (const float4 *)g.rec;
-    hipLaunchKernelGGL(blend_bwd_rows_kernel, dim3((unsigned)(tx * ty)), dim3(RB_THREADS), 0, stream, cfg->image_width,
-                       cfg->image_height, tx, (const uint2 *)im.ranges, (const uint32_t *)b.gid_sorted, rec,
-                       cfg->bg, (const float *)im.final_T, (const uint32_t *)im.n_contrib, (const uint32_t *)im.tile_last,
-                       dL_dout, dL_dmean2D_px, dL_dconic, dL_dopacity, dL_dcolors, (const uint32_t *)im.tile_order);
+    if (dL_dabs_px)
+        hipLaunchKernelGGL(blend_bwd_rows_kernel<true>, dim3((unsigned)(tx * ty)), dim3(RB_THREADS), 0, stream, cfg->image_width,
+                           cfg->image_height, tx, (const uint2 *)im.ranges, (const uint32_t *)b.gid_sorted, rec,
+                           cfg->bg, (const float *)im.final_T, (const uint32_t *)im.n_contrib, (const uint32_t *)im.tile_last,
+                           dL_dout, dL_dmean2D_px, dL_dconic, dL_dopacity, dL_dcolors, (const uint32_t *)im.tile_order,
+                           dL_dabs_px);
+    else
+        hipLaunchKernelGGL(blend_bwd_rows_kernel<false>, dim3((unsigned)(tx * ty)), dim3(RB_THREADS), 0, stream, cfg->image_width,
+                           cfg->image_height, tx, (const uint2 *)im.ranges, (const uint32_t *)b.gid_sorted, rec,
+                           cfg->bg, (const float *)im.final_T, (const uint32_t *)im.n_contrib, (const uint32_t *)im.tile_last,
+                           dL_dout, dL_dmean2D_px, dL_dconic, dL_dopacity, dL_dcolors, (const uint32_t *)im.tile_order,
+                           dL_dabs_px);
     CGS_CHECK_LAUNCH(stream, cfg->debug);
     return CGS_OK;
 }

@@ -26,8 +26,9 @@ int cgs_launch_preprocess_bwd_form(const cgs_raster_cfg *cfg, int64_t P, const C
                                    const float *dL_dmean2D_px, const float *dL_dconic, const float *dL_dcolors,
                                    float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs, float *dL_dscales,
                                    float *dL_drotations, float *dL_dcov3D, hipStream_t stream,
-                                   const float *aa_opacities = nullptr, float *aa_dL_dopacities = nullptr);
-// aa: antialiasing (raster_math.h); aa_opacities != NULL: its backward, as cgs_launch_preprocess_bwd's
+                                   const float *aa_opacities = nullptr, float *aa_dL_dopacities = nullptr,
+                                   const float *dL_dabs_px = nullptr);
+// aa: antialiasing (raster_math.h); aa_opacities != NULL: its backward, as cgs_launch_preprocess_bwd's; dL_dabs_px likewise
 
 // ---- spherical harmonics (the real SH basis of 3DGS / PlenOctrees, same constants and term order) ----------------------
 #define CGS_SH_C0 0.28209479177387814f

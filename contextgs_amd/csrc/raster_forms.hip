@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(PF_THREADS)
 
 // Per-Gaussian backward of the forms above (the blend backward's dL/d(pixel mean), dL/d(conic) and, for SH, dL/dcolor in,
 // as preprocess_bwd_kernel<false> takes them).  Every output row is written, zeros for culled Gaussians.
-template <int SHD, bool COV6>
+template <int SHD, bool COV6, bool ABS>
 __global__ void __launch_bounds__(PF_THREADS)
     preprocess_bwd_form_kernel(int64_t P, int W, int H, float tanfovx, float tanfovy, float scale_modifier,
                                const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix,
@@ -72,12 +72,14 @@ __global__ void __launch_bounds__(PF_THREADS)
                                const int32_t *__restrict__ radii, const float *__restrict__ dL_dmean2D_px,
                                const float *__restrict__ dL_dconic, const float *__restrict__ dL_dcolors,
                                float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dmeans2D, float *__restrict__ dL_dshs,
-                               float *__restrict__ dL_dscales, float *__restrict__ dL_drotations, float *__restrict__ dL_dcov6) {
+                               float *__restrict__ dL_dscales, float *__restrict__ dL_drotations, float *__restrict__ dL_dcov6,
+                               const float *__restrict__ dL_dabs_px) {
     const int64_t i = (int64_t)blockIdx.x * PF_THREADS + threadIdx.x;
     if (i >= P) return;
     if (radii[i] <= 0) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = 0.f; dL_dmeans2D[3 * i + k] = 0.f; }
+        for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = 0.f; if constexpr (!ABS) dL_dmeans2D[3 * i + k] = 0.f; }
+        if constexpr (ABS) cgs_store_dm2_abs(dL_dmeans2D, i, nullptr, dL_dabs_px, W, H);
         if (COV6) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) dL_dcov6[6 * i + k] = 0.f;
@@ -146,7 +148,8 @@ __global__ void __launch_bounds__(PF_THREADS)
         o.dp[2] += gsh.z;
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = o.dp[k]; dL_dmeans2D[3 * i + k] = o.dm2[k]; }
+    for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = o.dp[k]; if constexpr (!ABS) dL_dmeans2D[3 * i + k] = o.dm2[k]; }
+    if constexpr (ABS) cgs_store_dm2_abs(dL_dmeans2D, i, o.dm2, dL_dabs_px, W, H);
 }
 
 // preprocess_form_kernel<false, SHD, COV6> with antialiasing (raster_math.h, cgs_aa_h): the record's opacity is opacity * h.
@@ -199,7 +202,7 @@ __global__ void __launch_bounds__(PF_THREADS)
 // preprocess_bwd_form_kernel with antialiasing (restated, as the forward): also reads opacities[i] and dL_dopacities[i]
 // (dL/d(op_eff), the blend backwards' sum), writes dL/d(opacity) = dL/d(op_eff) h over it and adds h's dL/d(cov2D) to the
 // conic chain (raster_pre.h / raster_forms.h).  Culled Gaussians: no blend list holds them, dL_dopacities[i] stays 0.
-template <int SHD, bool COV6>
+template <int SHD, bool COV6, bool ABS>
 __global__ void __launch_bounds__(PF_THREADS)
     preprocess_bwd_form_aa_kernel(int64_t P, int W, int H, float tanfovx, float tanfovy, float scale_modifier,
                                const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix,
@@ -210,12 +213,14 @@ __global__ void __launch_bounds__(PF_THREADS)
                                const float *__restrict__ dL_dconic, const float *__restrict__ dL_dcolors,
                                float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dmeans2D, float *__restrict__ dL_dshs,
                                float *__restrict__ dL_dscales, float *__restrict__ dL_drotations, float *__restrict__ dL_dcov6,
-                                  const float *__restrict__ opacities, float *__restrict__ dL_dopacities) {
+                                  const float *__restrict__ opacities, float *__restrict__ dL_dopacities,
+                                  const float *__restrict__ dL_dabs_px) {
     const int64_t i = (int64_t)blockIdx.x * PF_THREADS + threadIdx.x;
     if (i >= P) return;
     if (radii[i] <= 0) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = 0.f; dL_dmeans2D[3 * i + k] = 0.f; }
+        for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = 0.f; if constexpr (!ABS) dL_dmeans2D[3 * i + k] = 0.f; }
+        if constexpr (ABS) cgs_store_dm2_abs(dL_dmeans2D, i, nullptr, dL_dabs_px, W, H);
         if (COV6) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) dL_dcov6[6 * i + k] = 0.f;
@@ -285,7 +290,8 @@ __global__ void __launch_bounds__(PF_THREADS)
         o.dp[2] += gsh.z;
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = o.dp[k]; dL_dmeans2D[3 * i + k] = o.dm2[k]; }
+    for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = o.dp[k]; if constexpr (!ABS) dL_dmeans2D[3 * i + k] = o.dm2[k]; }
+    if constexpr (ABS) cgs_store_dm2_abs(dL_dmeans2D, i, o.dm2, dL_dabs_px, W, H);
     dL_dopacities[i] = o.dop;
 }
 
@@ -305,24 +311,41 @@ static void launch_fwd(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForm
                            f.sh_vec, opacities, scales, rotations, f.cov3D, g.rec, g.depth_key, g.tiles, g.rect, radii);
 }
 
+template <int SHD, bool COV6, bool ABS>
+static void launch_bwd_abs(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForms &f, const float *means3D, const float *scales,
+                       const float *rotations, const int32_t *radii, const float *dL_dmean2D_px, const float *dL_dconic,
+                       const float *dL_dcolors, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs, float *dL_dscales,
+                       float *dL_drotations, float *dL_dcov3D, hipStream_t stream, const float *aa_opacities,
+                       float *aa_dL_dopacities, const float *dL_dabs_px) {
+    if (aa_opacities)
+        hipLaunchKernelGGL((preprocess_bwd_form_aa_kernel<SHD, COV6, ABS>), dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)),
+                           dim3(PF_THREADS), 0, stream, P, cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
+                           cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, cfg->campos, means3D, f.shs, f.sh_coeffs,
+                           f.sh_vec, scales, rotations, f.cov3D, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
+                           dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, aa_opacities, aa_dL_dopacities, dL_dabs_px);
+    else
+        hipLaunchKernelGGL((preprocess_bwd_form_kernel<SHD, COV6, ABS>), dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)),
+                           dim3(PF_THREADS), 0, stream, P, cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
+                           cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, cfg->campos, means3D, f.shs, f.sh_coeffs,
+                           f.sh_vec, scales, rotations, f.cov3D, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
+                           dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, dL_dabs_px);
+}
+
+// dL_dabs_px != NULL: dL_dmeans2D is [P, 4] (cgs_store_dm2_abs)
 template <int SHD, bool COV6>
 static void launch_bwd(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForms &f, const float *means3D, const float *scales,
                        const float *rotations, const int32_t *radii, const float *dL_dmean2D_px, const float *dL_dconic,
                        const float *dL_dcolors, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs, float *dL_dscales,
                        float *dL_drotations, float *dL_dcov3D, hipStream_t stream, const float *aa_opacities,
-                       float *aa_dL_dopacities) {
-    if (aa_opacities)
-        hipLaunchKernelGGL((preprocess_bwd_form_aa_kernel<SHD, COV6>), dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)),
-                           dim3(PF_THREADS), 0, stream, P, cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
-                           cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, cfg->campos, means3D, f.shs, f.sh_coeffs,
-                           f.sh_vec, scales, rotations, f.cov3D, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
-                           dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, aa_opacities, aa_dL_dopacities);
+                       float *aa_dL_dopacities, const float *dL_dabs_px) {
+    if (dL_dabs_px)
+        launch_bwd_abs<SHD, COV6, true>(cfg, P, f, means3D, scales, rotations, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
+                                        dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_opacities,
+                                        aa_dL_dopacities, dL_dabs_px);
     else
-        hipLaunchKernelGGL((preprocess_bwd_form_kernel<SHD, COV6>), dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)),
-                           dim3(PF_THREADS), 0, stream, P, cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
-                           cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, cfg->campos, means3D, f.shs, f.sh_coeffs,
-                           f.sh_vec, scales, rotations, f.cov3D, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
-                           dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D);
+        launch_bwd_abs<SHD, COV6, false>(cfg, P, f, means3D, scales, rotations, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
+                                         dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_opacities,
+                                         aa_dL_dopacities, dL_dabs_px);
 }
 
 // f.shs == NULL: colours precomputed; f.cov3D == NULL: scales / rotations.  Not both NULL (that form is
@@ -360,12 +383,12 @@ int cgs_launch_preprocess_bwd_form(const cgs_raster_cfg *cfg, int64_t P, const C
                                    const float *dL_dmean2D_px, const float *dL_dconic, const float *dL_dcolors,
                                    float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs, float *dL_dscales,
                                    float *dL_drotations, float *dL_dcov3D, hipStream_t stream, const float *aa_opacities,
-                                   float *aa_dL_dopacities) {
+                                   float *aa_dL_dopacities, const float *dL_dabs_px) {
     if (P == 0) return CGS_OK;
     CgsProfScope prof(CGS_PROF_PREPROCESS_BWD, stream);
     const int d = f.shs ? f.sh_degree : -1;
 #define CGS_BWD_ARGS cfg, P, f, means3D, scales, rotations, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D, dL_dmeans2D, \
-                     dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_opacities, aa_dL_dopacities
+                     dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_opacities, aa_dL_dopacities, dL_dabs_px
     if (f.cov3D) {
         switch (d) {
             case -1: launch_bwd<-1, true>(CGS_BWD_ARGS); break;

@@ -97,6 +97,15 @@ __device__ __forceinline__ void cgs_pre_fwd_one(int64_t i, const float3 p, const
 // AA (antialiasing): aa_op = the Gaussian's opacity, aa_g = dL/d(op_eff) as the blend backwards summed it;
 // o.dop = dL/d(opacity) = aa_g h, and dL/d(cov2D) of h joins the conic chain's before it goes on to Sigma and means3D.
 struct CgsPreBwd { float dp[3], dm2[3], ds[3], dq[4], dop; };
+// Row i of a FOUR-column dL_dmeans2D (cgs_raster_backward_abs): (gnx, gny, 0.5 W abs_x, 0.5 H abs_y), the blend backward's
+// absolute sums abs_px [P, 2] in the convention of the signed columns; dm2 == NULL: a culled Gaussian, four zeros.
+__device__ __forceinline__ void cgs_store_dm2_abs(float *__restrict__ dL_dmeans2D, int64_t i, const float *dm2,
+                                                  const float *__restrict__ abs_px, int W, int H) {
+    dL_dmeans2D[4 * i] = dm2 ? dm2[0] : 0.f;
+    dL_dmeans2D[4 * i + 1] = dm2 ? dm2[1] : 0.f;
+    dL_dmeans2D[4 * i + 2] = dm2 ? abs_px[2 * i] * 0.5f * (float)W : 0.f;
+    dL_dmeans2D[4 * i + 3] = dm2 ? abs_px[2 * i + 1] * 0.5f * (float)H : 0.f;
+}
 template <bool AA = false>
 __device__ __forceinline__ CgsPreBwd cgs_pre_bwd_one(const float3 p, const float3 s_raw, const float4 q, float gmean_x, float gmean_y,
                                                      float gconic_a, float gconic_b, float gconic_c, const float *V, const float *Pm,

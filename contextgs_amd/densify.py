@@ -5,7 +5,8 @@
 `contextgs_amd.model.GaussianModel` densifies on its own (round 3).
 
 * training_statis: one HIP pass over the visible slots (`cgs_densify_stats`, csrc/densify.hip) instead of ~15
-  launches with three boolean-mask index_puts over all N*K offsets.
+  launches with three boolean-mask index_puts over all N*K offsets.  A [P,4] gradient (render(absgrad=True): signed x, y |
+  absolute x, y) accumulates ||grad[:, 2:4]||, AbsGS's statistic, through `cgs_densify_stats_ex`; a [P,3] one ||grad[:, :2]||.
 * prune / adjust_anchor: the eight per-anchor parameters, their Adam moments and the four statistics buffers are
   compacted by ONE `cgs_compact_rows` launch over one `nonzero` of the keep mask (the reference boolean-indexes each of
   the ~28 tensors separately: a mask scan + gather pair per tensor).
@@ -29,6 +30,10 @@ from .encodings import Quantize_anchor
 @torch.no_grad()
 def training_statis(pc, viewspace_point_tensor, opacity, update_filter, offset_selection_mask, anchor_visible_mask):
     K = int(pc.n_offsets)
+    grad = viewspace_point_tensor.grad
+    if grad.dim() != 2 or grad.shape[1] not in (3, 4):
+        raise ValueError(f"training_statis: viewspace_point_tensor.grad must be [P,3] or, from render(absgrad=True), [P,4]; "
+                         f"got {tuple(grad.shape)}")
     _lib.require_device(opacity, pc.opacity_accum)
     vis_idx = torch.nonzero(anchor_visible_mask)[:, 0]
     n_vis = int(vis_idx.shape[0])
@@ -39,13 +44,18 @@ def training_statis(pc, viewspace_point_tensor, opacity, update_filter, offset_s
     sel = offset_selection_mask.reshape(-1).to(torch.uint8).contiguous()
     sel_pos = (torch.cumsum(sel, 0, dtype=torch.int64) - sel).contiguous()
     uf = update_filter.reshape(-1).to(torch.uint8).contiguous()
-    grad = viewspace_point_tensor.grad
     grad = grad if (grad.dtype == torch.float32 and grad.is_contiguous()) else grad.float().contiguous()
-    if grad.dim() != 2 or grad.shape[1] != 3 or grad.shape[0] != uf.shape[0]:
-        raise ValueError("training_statis: viewspace_point_tensor.grad must be [P,3] with P = len(update_filter)")
+    if grad.shape[0] != uf.shape[0]:
+        raise ValueError("training_statis: viewspace_point_tensor.grad must have P = len(update_filter) rows")
     for t in (pc.opacity_accum, pc.anchor_demon, pc.offset_gradient_accum, pc.offset_denom):
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError("training_statis: accumulators must be contiguous fp32")
+    if grad.shape[1] == 4:      # the absolute columns
+        _lib.check(_lib.lib().cgs_densify_stats_ex(n_vis, K, _lib.ptr(vis_idx), _lib.ptr(op), _lib.ptr(sel), _lib.ptr(sel_pos),
+                                                   _lib.ptr(uf), _lib.ptr(grad), _lib.ptr(pc.opacity_accum),
+                                                   _lib.ptr(pc.anchor_demon), _lib.ptr(pc.offset_gradient_accum),
+                                                   _lib.ptr(pc.offset_denom), _lib.current_stream(), 4, 2), "cgs_densify_stats_ex")
+        return
     _lib.check(_lib.lib().cgs_densify_stats(n_vis, K, _lib.ptr(vis_idx), _lib.ptr(op), _lib.ptr(sel), _lib.ptr(sel_pos),
                                             _lib.ptr(uf), _lib.ptr(grad), _lib.ptr(pc.opacity_accum), _lib.ptr(pc.anchor_demon),
                                             _lib.ptr(pc.offset_gradient_accum), _lib.ptr(pc.offset_denom),

@@ -105,6 +105,27 @@ cgs_raster_contrib) behind the render that was kept; it combines freely with ret
 differentiable and the backward neither sees nor saves anything of it; without `contrib` the call enqueues exactly what it
 did before.  `weight` is summed with float atomics (not bit-reproducible); the other results are exact.  A wrong length, dtype
 or a non-contiguous tensor, or contrib_slots without contrib, raises ValueError before a device is touched.
+
+`forward(..., absgrad=True)` returns AbsGS's densification statistic (gsplat's `absgrad`) next to the signed gradient.
+means2D.grad is a SIGNED sum over the pixels a Gaussian covers: a large Gaussian that straddles an over-reconstructed region
+gets per-pixel pulls in opposite directions, they cancel, and the Gaussians that most need splitting score lowest.  With the
+flag `means2D` must be [P,4] and its gradient holds, with L = sum_p L_p the loss on the colour image, (mx_i, my_i) Gaussian
+i's pixel mean and W, H the image size:
+
+  grad[:, 0:2] = the signed gradient exactly as without the flag (0.5 W dL/dmx_i, 0.5 H dL/dmy_i)
+  grad[:, 2]   = 0.5 W sum_p |dL_p / dmx_i|          grad[:, 3] = 0.5 H sum_p |dL_p / dmy_i|
+
+in the same convention (pixel-mean gradient x 0.5 W, x 0.5 H), summed over exactly the contributors the colour backward walks
+with the same alphas: the same 1/255 skip, the same 0.99 cap, the same stop where the forward stopped the pixel, and with
+antialiasing the same opacity * h.  Culled Gaussians get four exact zeros.  The absolute columns hold the COLOUR image's share
+only: gradients that arrive through the depth / inverse-depth / alpha maps or the feature map keep flowing into the signed
+columns and are not part of the absolute ones (their blends are separate kernels, and |a| + |b| per blend is not a quantity
+anyone densifies on); a backward in which the colour image got no gradient leaves them zero.  The per-pixel terms exist only
+inside the blend backward, whose ABS instance (csrc/raster_blend_rows.hip) reduces the two extra values with the others;
+the backward is then cgs_raster_backward_abs in every form, with return_aux, features, contrib, antialiasing and camera
+gradients as before.  Summed with float atomics like the signed gradient: not bit-reproducible.  A [P,4] means2D without the
+keyword, or the keyword with any other shape, raises ValueError before a device is touched; without the flag the call enqueues
+exactly what it did before.  densify.training_statis accumulates ||grad[:, 2:4]|| when it is handed a [P,4] gradient.
 """
 from __future__ import annotations
 
@@ -293,6 +314,16 @@ def check_features(features, P) -> None:
         raise ValueError(f"features has {features.shape[1]} channels, outside 1..{CGS_RASTER_MAX_FEATURES}")
 
 
+def check_absgrad(means2D, absgrad, P) -> None:
+    """`absgrad` and the width of means2D go together ([P,4] with it, never without), on shapes only: no device is touched."""
+    shape = tuple(means2D.shape) if means2D is not None else None
+    if absgrad:
+        if shape != (P, 4):
+            raise ValueError(f"absgrad=True needs means2D [P, 4] = [{P}, 4] (signed x, y | absolute x, y), got {shape}")
+    elif shape is not None and len(shape) == 2 and shape[1] == 4:
+        raise ValueError(f"means2D is {shape}: four columns are the layout of absgrad=True, which was not given")
+
+
 class GaussianContrib:
     """Per-Gaussian (or per-slot) contribution statistics accumulated over views: `weight`, `max_weight` float32 [n], `pixels`,
     `top_pixels` int64 [n] (module docstring), and `views`, the number of calls accumulated since the last reset."""
@@ -367,11 +398,13 @@ class _RasterizeGaussians(torch.autograd.Function):
     With `features` [P, C] (the last input; None = none of this runs) one more walk of the lists gives the feature map as the
     last output (cgs_raster_render_features), and when that map got a gradient the backward is cgs_raster_backward_feat.
     With `contrib` (a GaussianContrib; None = none of this runs) one more walk accumulates into it and gives the
-    top_id / top_weight / count maps as three non-differentiable outputs behind the aux maps (cgs_raster_contrib)."""
+    top_id / top_weight / count maps as three non-differentiable outputs behind the aux maps (cgs_raster_contrib).
+    With `absgrad` the forward is unchanged and the backward is cgs_raster_backward_abs whatever got a gradient: means2D's
+    gradient is [P,4], the signed columns and the absolute sums of the colour image's per-pixel terms (module docstring)."""
 
     @staticmethod
     def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings,
-                viewmatrix, projmatrix, campos, features=None, contrib=None, contrib_slots=None):
+                viewmatrix, projmatrix, campos, features=None, contrib=None, contrib_slots=None, absgrad=False):
         # viewmatrix / projmatrix / campos: the settings' three camera tensors once more, as inputs of the node so that autograd
         # can hand them a gradient; the forward reads them through _Cfg as before
         L = _lib.lib()
@@ -429,6 +462,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                                                     _lib.ptr(fmap), stream), "cgs_raster_render_features")
             outs += (fmap,)
         ctx.cfg, ctx.num_rendered, ctx.D, ctx.M, ctx.opts, ctx.aux = cfg, bin_R, D, M, opts, bool(aux)
+        ctx.absgrad = bool(absgrad)
         ctx.save_for_backward(means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat)
         ctx.mark_non_differentiable(*nondiff)      # ONE call: torch keeps only the last call's arguments
         return outs
@@ -444,16 +478,17 @@ class _RasterizeGaussians(torch.autograd.Function):
         dev = means3D.device
         g, *maps = (None if t is None else _f32c(t) for t in (grad_color, *grad_maps, None, None, None)[:4])
         if g is None and g_fmap is None and all(t is None for t in maps):
-            return (None,) * 16
+            return (None,) * 17
         # the blends accumulate dL/dcolor (read by the SH backward) and dL/dopacity atomically: one zero fill for both; the
         # other arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones)
         acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
         d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
-        rest = torch.empty(P * (6 + (7 if cov is None else 6)), dtype=torch.float32, device=dev)
-        d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:6 * P].view(P, 3)
-        d_scales = rest[6 * P:9 * P].view(P, 3) if cov is None else None
-        d_rots = rest[9 * P:].view(P, 4) if cov is None else None
-        d_cov = rest[6 * P:].view(P, 6) if cov is not None else None
+        m2 = 4 if ctx.absgrad else 3        # columns of dL/dmeans2D
+        rest = torch.empty(P * (3 + m2 + (7 if cov is None else 6)), dtype=torch.float32, device=dev)
+        d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:(3 + m2) * P].view(P, m2)
+        d_scales = rest[(3 + m2) * P:(6 + m2) * P].view(P, 3) if cov is None else None
+        d_rots = rest[(6 + m2) * P:].view(P, 4) if cov is None else None
+        d_cov = rest[(3 + m2) * P:].view(P, 6) if cov is not None else None
         d_shs = torch.empty_like(shs) if shs is not None else None      # of its own: aligned as shs is (vector stores)
         inputs = (cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M,
                   _lib.ptr(opac), _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom),
@@ -462,7 +497,16 @@ class _RasterizeGaussians(torch.autograd.Function):
                  _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov))
         stream = _lib.current_stream()
         d_feat = None
-        if g_fmap is not None:      # the feature map got a gradient: the same call with the feature blend backward in it
+        if ctx.absgrad:             # one entry point for every combination: NULL for what got no gradient
+            cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS        # (its scratch begins with cgs_raster_backward_opt's)
+            d_feat = torch.zeros_like(feat) if g_fmap is not None else None
+            scratch = _workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
+            with_feat = g_fmap is not None
+            _lib.check(L.cgs_raster_backward_abs(*inputs, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), *grads,
+                                                 _lib.ptr(scratch), scratch.numel(), stream, ctx.opts,
+                                                 _lib.ptr(feat) if with_feat else None, feat.shape[1] if with_feat else 0,
+                                                 _lib.ptr(g_fmap), _lib.ptr(d_feat)), "cgs_raster_backward_abs")
+        elif g_fmap is not None:    # the feature map got a gradient: the same call with the feature blend backward in it
             cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS
             d_feat = torch.zeros_like(feat)         # accumulated atomically, like dL/dcolor
             scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
@@ -500,7 +544,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         if g is None:       # the maps and the features send no gradient to the colour inputs
             d_shs = d_colors = None
         return (None, d_means3D, d_means2D, d_shs, d_colors if colors is not None else None, d_opac, d_scales, d_rots,
-                d_cov, None, d_view, d_proj, d_campos, d_feat, None, None)
+                d_cov, None, d_view, d_proj, d_campos, d_feat, None, None, None)
 
 
 def _camera_inputs(rs):
@@ -555,11 +599,13 @@ class GaussianRasterizer(nn.Module):
         return radii
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, features=None, return_aux=False, contrib=None, contrib_slots=None):
+                cov3D_precomp=None, features=None, return_aux=False, contrib=None, contrib_slots=None, absgrad=False):
         """(color [3,H,W], radii int32 [P]); with return_aux=True, features [P,C] and / or contrib a third value, the dict of
         {"depth", "invdepth", "alpha"}, float32 [1,H,W] each, {"features"}, float32 [C,H,W], and / or {"contrib", "top_id",
-        "top_weight", "count"} (see the module docstring)."""
+        "top_weight", "count"} (see the module docstring).  absgrad=True: means2D is [P,4] and its gradient's columns 2:4 are
+        the sums over the pixels of the absolute per-pixel gradients of the colour image (module docstring)."""
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
+        check_absgrad(means2D, absgrad, means3D.shape[0])
         check_features(features, means3D.shape[0])
         if contrib is False:
             contrib = None
@@ -568,7 +614,7 @@ class GaussianRasterizer(nn.Module):
             contrib = GaussianContrib.zeros(means3D.shape[0], means3D.device)
         out = _RasterizeGaussians.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                         cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings), features,
-                                        contrib, contrib_slots)
+                                        contrib, contrib_slots, *((True,) if absgrad else ()))
         if not return_aux and features is None and contrib is None:
             return out
         extras = {}

@@ -196,8 +196,9 @@ class ViewFusion:
     """What render() hands to generate_neural_gaussians when the expansion may run fused with the rasterizer: the view's
     raster settings in, the rendered view out (`done`: (image, radii, screenspace_points))."""
 
-    def __init__(self, raster_settings, retain_grad):
+    def __init__(self, raster_settings, retain_grad, absgrad=False):
         self.raster_settings, self.retain_grad, self.done = raster_settings, retain_grad, None
+        self.absgrad = bool(absgrad)       # screenspace_points is [P,4] and the backward is cgs_raster_backward_abs
 
 
 class _ExpandRasterize(torch.autograd.Function):
@@ -207,10 +208,12 @@ class _ExpandRasterize(torch.autograd.Function):
     nodes' backward launches (cgs_raster_backward, cgs_expand_backward) with their hand-over buffers kept inside the node.
     Same device functions on the same values as the two nodes: bit-identical image, radii and scaling
     (tests/test_fused_view_gpu.py).  means2D: the view's screenspace_points (its gradient is the only thing it
-    carries), created by the caller once the survivor count P is known."""
+    carries), created by the caller once the survivor count P is known.  absgrad: means2D is [P,4] and the rasterizer's
+    backward launch is cgs_raster_backward_abs with the same arguments (rasterizer.py: the absolute sums in columns 2:4)."""
 
     @staticmethod
-    def forward(ctx, anchor, gscaling, offsets, masks, op_raw, color_in, cov_in, means2D, K, src_row, pre, raster_settings):
+    def forward(ctx, anchor, gscaling, offsets, masks, op_raw, color_in, cov_in, means2D, K, src_row, pre, raster_settings,
+                absgrad=False):
         from . import rasterizer as rz
         L = _lib.lib()
         _lib.require_device(anchor, gscaling, offsets, masks, op_raw, color_in, cov_in)
@@ -222,7 +225,8 @@ class _ExpandRasterize(torch.autograd.Function):
         assert pre.n == n and pre.K == K
         ctx.set_materialize_grads(False)
         P = pre.wait()
-        assert means2D.shape[0] == P
+        assert means2D.shape[0] == P and means2D.shape[1] == (4 if absgrad else 3)
+        ctx.absgrad = bool(absgrad)
         neural_opacity, mask_out, flags, pos = pre.neural_opacity, pre.mask_out, pre.flags, pre.pos
         cfg = rz._Cfg(raster_settings)
         H, W = cfg.c.image_height, cfg.c.image_width
@@ -255,10 +259,22 @@ class _ExpandRasterize(torch.autograd.Function):
         # ---- the rasterizer's backward (as _RasterizeGaussians.backward) into buffers that stay inside this node
         acc = torch.zeros(max(P, 1) * 4, dtype=torch.float32, device=dev)      # atomically accumulated: dL/d colour | opacity
         d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:4 * P].view(P, 1)
-        rest = torch.empty(max(P, 1) * 13, dtype=torch.float32, device=dev)
-        d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:6 * P].view(P, 3)
-        d_scales, d_rots = rest[6 * P:9 * P].view(P, 3), rest[9 * P:13 * P].view(P, 4)
-        if g_img is not None and P > 0:
+        m2 = 4 if ctx.absgrad else 3        # columns of dL/dmeans2D
+        rest = torch.empty(max(P, 1) * (10 + m2), dtype=torch.float32, device=dev)
+        d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:(3 + m2) * P].view(P, m2)
+        d_scales, d_rots = rest[(3 + m2) * P:(6 + m2) * P].view(P, 3), rest[(6 + m2) * P:(10 + m2) * P].view(P, 4)
+        if g_img is not None and P > 0 and ctx.absgrad:
+            # the plain form's arguments; the colours never existed as a tensor and the backward of this form does not read
+            # them (the pointer only says "colours, not SH": include/cgs.h), so the gradient buffer stands in
+            scratch = rz._workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
+            _lib.check(L.cgs_raster_backward_abs(
+                cfg.ref, P, ctx.num_rendered, _lib.ptr(xyz), _lib.ptr(d_colors), None, 0, 0, None, _lib.ptr(scaling),
+                _lib.ptr(rot), None, _lib.ptr(radii), _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
+                binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(), _lib.ptr(rz._f32c(g_img)), None, None,
+                None, _lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), None, _lib.ptr(d_scales),
+                _lib.ptr(d_rots), None, _lib.ptr(scratch), scratch.numel(), stream, 0, None, 0, None, None),
+                "cgs_raster_backward_abs")
+        elif g_img is not None and P > 0:
             scratch = rz._workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
             _lib.check(L.cgs_raster_backward(
                 cfg.ref, P, ctx.num_rendered, _lib.ptr(xyz), None, None, _lib.ptr(scaling), _lib.ptr(rot), _lib.ptr(radii),
@@ -291,7 +307,7 @@ class _ExpandRasterize(torch.autograd.Function):
             _lib.ptr(cov_in), _lib.ptr(d_means3D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_scales), _lib.ptr(d_rots),
             _lib.ptr(g_no), _lib.ptr(d_anchor), _lib.ptr(d_gs), _lib.ptr(d_off), _lib.ptr(d_op), _lib.ptr(d_mask),
             _lib.ptr(d_color), _lib.ptr(d_cov), _lib.ptr(src_row), stream), "cgs_expand_backward")
-        return d_anchor, d_gs, d_off, d_mask, d_op, d_color, d_cov, d_means2D, None, None, None, None
+        return d_anchor, d_gs, d_off, d_mask, d_op, d_color, d_cov, d_means2D, None, None, None, None, None
 
 
 def _anchor_mlps(pc, x):
@@ -376,7 +392,7 @@ def _generate_unfused(viewpoint_camera, pc, anchor, feat, grid_scaling, grid_off
         # the expansion and the rasterizer as one node (csrc/expand_raster.hip); the survivor count is read here, after
         # `between` has put the rate model in the queue, so that screenspace_points can be an INPUT of the node
         P = pre.wait()
-        screenspace_points = _zero_points(torch.empty(P, 0, device=anchor.device))
+        screenspace_points = _zero_points(torch.empty(P, 0, device=anchor.device), 4 if view.absgrad else 3)
         if view.retain_grad:
             try:
                 screenspace_points.retain_grad()
@@ -384,7 +400,7 @@ def _generate_unfused(viewpoint_camera, pc, anchor, feat, grid_scaling, grid_off
                 pass
         image, radii, scaling, neural_opacity, mask = _ExpandRasterize.apply(
             anchor, grid_scaling, grid_offsets, masks2, op_raw, color_in, cov_in, screenspace_points, K, src_row, pre,
-            view.raster_settings)
+            view.raster_settings, *((True,) if view.absgrad else ()))
         view.done = (image, radii, screenspace_points)
         return None, None, None, scaling, None, neural_opacity, mask
     return _ExpandGaussians.apply(anchor, grid_scaling, grid_offsets, masks2, op_raw, color_in, cov_in, K, src_row, pre)
@@ -550,25 +566,25 @@ class _ZeroPoints(torch.autograd.Function):
     receives the 2-D position gradients): a FRESH zero tensor per view, as in the reference — independent storage, so a caller
     that writes into one view's tensor does not touch another's (rounds 3-4 handed every view a slice of one pooled zero
     buffer, "read-only by contract") — wrapped in an autograd node so that it is a non-leaf tensor that requires
-    grad without the reference's `+ 0` launch.  One fill of 12 B per Gaussian per view."""
+    grad without the reference's `+ 0` launch.  One fill of 12 B per Gaussian per view ([P,4], 16 B, with render(absgrad=True))."""
 
     @staticmethod
-    def forward(ctx, like, token):
-        return torch.zeros(int(like.shape[0]), 3, dtype=torch.float32, device=like.device)
+    def forward(ctx, like, token, cols=3):
+        return torch.zeros(int(like.shape[0]), cols, dtype=torch.float32, device=like.device)
 
     @staticmethod
     def backward(ctx, _g):
-        return None, None
+        return None, None, None
 
 
 _GRAD_TOKEN = {}
 
 
-def _zero_points(xyz):
+def _zero_points(xyz, cols=3):
     tok = _GRAD_TOKEN.get(xyz.device)
     if tok is None:
         tok = _GRAD_TOKEN[xyz.device] = torch.zeros(1, device=xyz.device, requires_grad=True)
-    return _ZeroPoints.apply(xyz.detach(), tok)
+    return _ZeroPoints.apply(xyz.detach(), tok, cols)
 
 
 def _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier):
@@ -596,7 +612,7 @@ class _DetachedCamera:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False,
-           step=0, *, return_aux=False, anchor_features=None, contrib=None):            # :155-229
+           step=0, *, return_aux=False, anchor_features=None, contrib=None, absgrad=False):            # :155-229
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
 
     return_aux=True: the dict also holds the rasterizer's "depth", "invdepth" and "alpha" maps ([1,H,W] each, see
@@ -614,6 +630,12 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     weight at each pixel, -1 where there is none), "top_weight" [1,H,W] and "count" int32 [H,W] (rasterizer.py).  Rows of
     anchors outside `visible_mask` and of offsets the selection mask drops are not touched.  Nothing of it is differentiable.
     In training mode such a call takes the unfused path, as return_aux does.
+
+    absgrad=True: "viewspace_points" is created [P,4] and its gradient holds the signed 2-D position gradient in columns 0:2,
+    as without the flag, and in columns 2:4 the sums over the pixels of the ABSOLUTE per-pixel gradients of the colour image
+    (AbsGS's densification statistic; contextgs_amd/rasterizer.py has the definition and what it excludes).  Training-mode
+    calls stay on the fused expand + raster node; every other path hands the keyword to the rasterizer.
+    densify.training_statis (GaussianModel.training_statis) accumulates ||grad[:, 2:4]|| when the gradient has four columns.
 
     A camera whose `world_view_transform`, `full_proj_transform` or `camera_center` requires a gradient (a trainable pose,
     contextgs_amd/camera_pose.py) takes the unfused path too, in training and in eval mode, and the gradient reaches the three
@@ -647,7 +669,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     if is_training:
         # the expansion may run fused with the rasterizer's per-Gaussian stages (then `view.done` holds the rendered view
         # and xyz / color / opacity / rot are None: they never existed as tensors)
-        view = ViewFusion(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier), retain_grad)
+        view = ViewFusion(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier), retain_grad, absgrad)
         (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, bit_per_anchor_param,
          bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level) = \
             generate_neural_gaussians(gen_camera, pc, visible_mask, is_training=True, step=step,
@@ -665,7 +687,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         xyz, color, opacity, scaling, rot, time_sub = generate_neural_gaussians(
             gen_camera, pc, visible_mask, is_training=False, step=step, _rows=rows, _slots=slots)
 
-    screenspace_points = _zero_points(xyz)       # :168 `torch.zeros_like(xyz, requires_grad=True) + 0`
+    screenspace_points = _zero_points(xyz, 4 if absgrad else 3)       # :168 `torch.zeros_like(xyz, requires_grad=True) + 0`
     if retain_grad:
         try:
             screenspace_points.retain_grad()
@@ -673,9 +695,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
             pass
 
     rasterizer = GaussianRasterizer(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier))
+    abs_kw = dict(absgrad=True) if absgrad else {}
     if return_aux or rows is not None or slots is not None:
         features = anchor_features.index_select(0, rows[0]) if rows is not None else None      # plumbing: plain torch
         more = dict(contrib=contrib, contrib_slots=slots[0]) if slots is not None else {}
+        more.update(abs_kw)
         rendered_image, radii, aux = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
                                                 opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None,
                                                 features=features, return_aux=return_aux, **more)
@@ -685,7 +709,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
             aux["top_id"] = table[tid]
     else:
         rendered_image, radii = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
-                                           opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None)
+                                           opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None, **abs_kw)
     if is_training:
         out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
                "radii": radii, "selection_mask": mask, "neural_opacity": neural_opacity, "scaling": scaling,

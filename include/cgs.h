@@ -352,6 +352,45 @@ int cgs_raster_backward_feat(const cgs_raster_cfg *cfg, int64_t P,
                              const float *features, int32_t C,
                              const float *dL_dfeatures_map, float *dL_dfeatures);
 
+/* ---- absolute screen-space gradients for densification (csrc/raster_blend_rows.hip, the ABS instance) ----
+ * dL_dmeans2D of every backward above is a SIGNED sum over the pixels a Gaussian covers: per-pixel pulls in opposite
+ * directions cancel, and the large Gaussians that most need splitting score lowest.  With L = sum_p L_p the colour loss, i a
+ * Gaussian, (mx_i, my_i) its pixel mean and W, H the image size, cgs_raster_backward_abs also returns (AbsGS; gsplat's `absgrad`)
+ *   abs_x[i] = 0.5 W sum_p |dL_p / d mx_i|,     abs_y[i] = 0.5 H sum_p |dL_p / d my_i|
+ * in the convention of the signed columns (pixel-mean gradient x 0.5 W, x 0.5 H).  The sum runs over exactly the (pixel,
+ * Gaussian) visits of the colour blend backward with the same alphas: the same skip below 1/255, the same 0.99 cap, the same
+ * stop at n_contrib; with CGS_RASTER_ANTIALIAS the same opacity * h.  The colour image's share ONLY: gradients that arrive
+ * through the depth / inverse-depth / alpha maps or the feature map flow into the signed columns as before and are not part of
+ * the absolute ones (their blends are separate kernels, and |a| + |b| per blend is not a quantity anyone densifies on).
+ * Without dL_dout the absolute columns are zero.  Summed with float atomics, like the signed gradient: not bit-reproducible.
+ *
+ * cgs_raster_backward_abs: the argument list, the checks and the results of cgs_raster_backward_feat (features, the three map
+ * gradients and dL_dout may each be NULL; opts as there), except that dL_dmeans2D is [P, 4]: (gnx, gny, abs_x, abs_y), every
+ * row written, four exact zeros for a culled Gaussian.  scratch: cgs_raster_bwd_abs_scratch_bytes(P) bytes = the scratch of
+ * cgs_raster_backward_feat with the [P, 2] absolute accumulator appended, so cgs_raster_camera_backward (CGS_RASTER_CAMERA_MAPS)
+ * reads it as it reads that one.  A short scratch: CGS_ERR_WORKSPACE; P == 0: CGS_OK, nothing enqueued.  As in the backwards
+ * above, `colors` is not dereferenced (which of colors / shs is given names the form), so a caller whose colours never existed
+ * as an array (the fused expand + raster node) passes any non-NULL pointer. */
+size_t cgs_raster_bwd_abs_scratch_bytes(int64_t P);
+int cgs_raster_backward_abs(const cgs_raster_cfg *cfg, int64_t P,
+                            int64_t num_rendered, const float *means3D,
+                            const float *colors, const float *shs,
+                            int32_t sh_degree, int32_t sh_coeffs,
+                            const float *opacities, const float *scales,
+                            const float *rotations, const float *cov3D,
+                            const int32_t *radii, void *geom_ws, size_t geom_bytes,
+                            void *bin_ws, size_t bin_bytes, void *img_ws,
+                            size_t img_bytes, const float *dL_dout,
+                            const float *dL_ddepth, const float *dL_dinvdepth,
+                            const float *dL_dalpha, float *dL_dmeans3D,
+                            float *dL_dmeans2D, float *dL_dcolors,
+                            float *dL_dopacities, float *dL_dshs,
+                            float *dL_dscales, float *dL_drotations,
+                            float *dL_dcov3D, void *scratch,
+                            size_t scratch_bytes, void *stream, uint32_t opts,
+                            const float *features, int32_t C,
+                            const float *dL_dfeatures_map, float *dL_dfeatures);
+
 /* ---- per-Gaussian contribution statistics and top-contributor maps (csrc/raster_contrib.hip) ----
  * The reverse direction of the maps above: how much each Gaussian mattered to the view (importance pruning, covisibility,
  * picking).  For pixel p the contributors i are exactly those of the colour blend (same order, same alpha, same skip below
@@ -1269,6 +1308,15 @@ int cgs_densify_stats(int64_t n_vis, int K, const int64_t *vis_idx,
                       const float *grad, float *opacity_accum, float *anchor_demon,
                       float *offset_gradient_accum, float *offset_denom,
                       void *stream);
+/* cgs_densify_stats on a gradient whose rows are grad_stride floats, with the norm taken over columns grad_col, grad_col + 1:
+ * grad_stride = 4, grad_col = 2 accumulates the absolute columns of cgs_raster_backward_abs's [P,4] dL_dmeans2D; 3, 0 is
+ * cgs_densify_stats.  Columns outside the row: CGS_ERR_ARG. */
+int cgs_densify_stats_ex(int64_t n_vis, int K, const int64_t *vis_idx,
+                         const float *opacity, const uint8_t *sel,
+                         const int64_t *sel_pos, const uint8_t *update_filter,
+                         const float *grad, float *opacity_accum, float *anchor_demon,
+                         float *offset_gradient_accum, float *offset_denom,
+                         void *stream, int32_t grad_stride, int32_t grad_col);
 
 /* ---- anchor pruning surgery (scene/gaussian_model.py:715-760, `_prune_anchor_optimizer` / `prune_anchor`, and the
  * statistics compaction of `adjust_anchor` :883-903) ----
