@@ -163,27 +163,45 @@ struct M3Rows {
 // TM (the forward's own operand): the last piece in TAIL ORDER — lane g, slot j holds input 48 + g + 4 j instead of 48 + 4 g + j, so
 // that the six inputs 48..53 fill the k-slots of TWO MFMA steps (j = 0: 48..51, j = 1: 52, 53) instead of being spread over four;
 // the matching rows of W1 are read in m3_head_fwd.  Free here: the tail is assembled in registers.
-template <bool TM = false>
-__device__ __forceinline__ f32x4 m3_load_x_rows_b(const M3FwdBufs &B, float cam0, float cam1, float cam2, int64_t row, int64_t srow,
-                                                  int q, int g, bool valid) {
+// The last piece (q = 3) in two halves: m3_x_tail_issue only REQUESTS what it is made of (features 48, 49 and the anchor),
+// m3_x_tail_finish forms it.  A caller with nobody to cover a round trip to memory (mlp3_bwd_wg_kernel: one wave per SIMD)
+// issues a tile ahead and finishes at the use; the divisions behind the loads otherwise wait for them on the spot.
+struct M3XTail { f32x4 f2, a; };
+template <bool TM>
+__device__ __forceinline__ M3XTail m3_x_tail_issue(const M3FwdBufs &B, int64_t row, int64_t srow, int g, bool valid) {
     const uint32_t fo = (uint32_t)srow * (M3_HID * 4);
-    if (q < 3) return cl_l128(B.feat, cl_sel(valid, fo + (uint32_t)(16 * q + 4 * g) * 4));
+    M3XTail t;
     if (TM) {
-        const f32x4 f2 = cl_l64(B.feat, cl_sel(valid && g < 2, fo + 48 * 4));                 // features 48, 49
-        const f32x4 a = cl_l96(B.anc, cl_sel(valid, (uint32_t)row * 12));
+        t.f2 = cl_l64(B.feat, cl_sel(valid && g < 2, fo + 48 * 4));                 // features 48, 49
+        t.a = cl_l96(B.anc, cl_sel(valid, (uint32_t)row * 12));
+    } else {
+        t.f2 = cl_l64(B.feat, cl_sel(valid && g == 0, fo + 48 * 4));                // features 48, 49
+        t.a = cl_l96(B.anc, cl_sel(valid && g < 2, (uint32_t)row * 12));
+    }
+    return t;
+}
+template <bool TM>
+__device__ __forceinline__ f32x4 m3_x_tail_finish(const M3XTail &t, float cam0, float cam1, float cam2, int g, bool valid) {
+    const f32x4 f2 = t.f2, a = t.a;
+    if (TM) {
         const float ux = a[0] - cam0, uy = a[1] - cam1, uz = a[2] - cam2;
         const float dist = sqrtf(ux * ux + uy * uy + uz * uz);
         const float s0 = g == 0 ? f2[0] : (g == 1 ? f2[1] : (g == 2 ? ux / dist : uy / dist));
         const float s1 = g == 0 ? uz / dist : (g == 1 ? dist : 0.f);
         return valid ? (f32x4){s0, s1, 0.f, 0.f} : (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-    const f32x4 f2 = cl_l64(B.feat, cl_sel(valid && g == 0, fo + 48 * 4));                    // features 48, 49
-    const f32x4 a = cl_l96(B.anc, cl_sel(valid && g < 2, (uint32_t)row * 12));
     const float ux = a[0] - cam0, uy = a[1] - cam1, uz = a[2] - cam2;
     const float dist = sqrtf(ux * ux + uy * uy + uz * uz);
     const f32x4 v0 = (f32x4){f2[0], f2[1], ux / dist, uy / dist}, v1 = (f32x4){uz / dist, dist, 0.f, 0.f};
     const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
     return !valid ? z : (g == 0 ? v0 : (g == 1 ? v1 : z));
+}
+template <bool TM = false>
+__device__ __forceinline__ f32x4 m3_load_x_rows_b(const M3FwdBufs &B, float cam0, float cam1, float cam2, int64_t row, int64_t srow,
+                                                  int q, int g, bool valid) {
+    const uint32_t fo = (uint32_t)srow * (M3_HID * 4);
+    if (q < 3) return cl_l128(B.feat, cl_sel(valid, fo + (uint32_t)(16 * q + 4 * g) * 4));
+    return m3_x_tail_finish<TM>(m3_x_tail_issue<TM>(B, row, srow, g, valid), cam0, cam1, cam2, g, valid);
 }
 
 // TILED (ROWS only): Hcat — a buffer only the fused backward reads, 600 of the 1256 bytes per anchor this kernel stores — leaves
@@ -479,8 +497,15 @@ struct M3wOps {
             if (ACT != FRAG_ACT_NONE) y[u] = frag_bload4<OUT>(B.Y[head], ro, u, g, valid);
         }
 #pragma unroll
-        for (int t = 0; t < M3_NT1; ++t)
+        for (int t = 0; t < M3_NT1 - 1; ++t)
             h[t] = TILED ? frag_tload4<M3_HID>(B.H, th, t, g, (int)(row & 15), valid) : frag_bload4<M3_HID>(B.H, rh, t, g, valid);
+        // the last piece holds columns 48, 49 and nothing else: a 64-bit load of the same address.  As a 128-bit load its upper
+        // half is dead from the start (mask() zeroes it in every lane), the register allocator hands those two registers to the
+        // next LDS read, and the write-after-write hazard puts an `s_waitcnt vmcnt(0)` right behind the prefetch: a full round
+        // trip to memory per head with nobody to cover it (798 -> 737 us at 1 M anchors, profiles/mlp3_bwd_pipeline.txt).
+        static_assert(M3_HID % 16 == 2, "the 64-bit tail load");
+        constexpr int tl = M3_NT1 - 1;
+        h[tl] = cl_l64(B.H, cl_sel(valid && g == 0, TILED ? th + frag_toff<M3_HID>(tl, g, (int)(row & 15)) : rh + (uint32_t)(16 * tl + 4 * g) * 4));
     }
     __device__ __forceinline__ void mask(int g) {
 #pragma unroll
@@ -501,16 +526,54 @@ __device__ __forceinline__ f32x4 m3w_get(const float *patch, int g, int c) {
     return o;
 }
 
-// One head of one tile.  Order of issue (one wave per SIMD: nothing else hides a latency): the F -> N transposes of H and
-// dZ2 are written and read back BEFORE the dH products, those of dZ1 before the dW2 products, so every LDS round trip has
-// a block of MFMAs in front of its first use; `prefetch` (the next head's global loads, and in the last head X of the next
-// tile) is issued after the dW2 products (after the transposes are written or after dH: more spills, HISTORY.md round 5).
-template <int OUT, int ACT, class Prefetch>
+// ---- LDS weight images of the fused backward: one 16-byte read per MFMA group --------------------------------------------
+// A group of the two data-gradient chains is four MFMAs that take weights (row, 16 t + c), t = 0..3, of one image row.  In
+// M3BwdLds' row-major image those are four dwords 16 apart: two ds_read2_b32 and, with one wave per SIMD, two `s_waitcnt
+// lgkmcnt` per group.  Here the image is stored [row][c][t] — the four weights of a lane are 16 contiguous bytes, ONE
+// ds_read_b128 per group and one counted wait — with 64-float rows: the lane groups of a ds_read_b128 ({0-3, 12-15, 20-27}, ...)
+// take c = 0..3, 12..15 from row 4g + j and c = 4..11 from row 4(g + 1) + j: 256-byte rows keep their 16 pieces on 64
+// distinct banks.  The same values reach the same MFMAs.
+template <int OUT>
+struct M3wLds {
+    static constexpr int NT2 = (OUT + 15) / 16, OP = NT2 * 16;
+    static constexpr int FLOATS = OP * 64 + M3_HP * 64;
+};
+template <int OUT>
+__device__ __forceinline__ void m3w_stage(float *lds, const M3Head &h, int tid, int nthr) {
+    using L = M3wLds<OUT>;
+    float *W2i = lds, *W1i = W2i + L::OP * 64;
+    frag_stage_loop(h.W2, L::OP * 64, tid, nthr,                                         // W2i[o][c][t] = W2[o][16 t + c]
+                    [](int i) { const int o = i >> 6, hh = 16 * (i & 3) + ((i >> 2) & 15); return (o < OUT && hh < M3_HID) ? o * M3_HID + hh : -1; },
+                    [&](int i, float v) { W2i[i] = v; });
+    frag_stage_loop(h.W1, M3_HP * 64, tid, nthr,                                         // W1i[h][c][v] = W1[h][16 v + c]
+                    [](int i) { const int hh = i >> 6, k = 16 * (i & 3) + ((i >> 2) & 15); return (hh < M3_HID && k < M3_IN) ? hh * M3_IN + k : -1; },
+                    [&](int i, float v) { W1i[i] = v; });
+}
+
+// One head of one tile.  One wave per SIMD: nothing else hides a latency, so every LDS operand is requested ahead of the MFMA
+// group that takes it, and held in place by scheduling fences (M3_FENCE):
+//   dH and dX chains (groups of 4 MFMAs, 128 cycles): the weights of group k + 2 are requested before group k is issued — one
+//     group of lead (round 5) is about one LDS round trip, two cover it.  The first two groups of a chain come from the phase
+//     before it: dH's from the previous head's last dW1 group (`wq`; across the tile boundary for the first head: `nextw` reads
+//     the NEXT head's image), dX's before the last dW2 group.
+//   dW2 and dW1 (groups of 16 MFMAs, 512 cycles): the transposed tile of group k + 1 before group k, the first tiles (H, dZ2[0],
+//     dZ1[0]) inside the last two groups of the chain in front — the F -> N transposes are written before that chain starts
+//     (H, dZ2) or right behind dH (dZ1), so every LDS round trip has MFMAs in front of its first use.
+// `prefetch` (the next head's global loads, and in the last head X of the next tile) is issued after the dW2 products (after
+// the transposes are written or after dH: more spills, HISTORY.md round 5).
+// The MFMAs, their operands and the order in which an accumulator receives its products are those of rounds 4-6: same bits.
+// Per tile 616 MFMAs as before, 146 LDS reads (240) behind 129 `s_waitcnt` (206); 874 -> 798 us at 1 M anchors, 723 with the
+// memory waits below gone, matrix pipe busy 59 -> 71 % of the wave cycles (profiles/mlp3_bwd_pipeline.txt).
+template <int OUT, int ACT, class Prefetch, class NextW>
 __device__ __forceinline__ void m3w_head(const float *lds, float *patches, M3wOps<OUT, ACT> &op, f32x4 ones, int g, int c,
                                          const f32x4 (&xn)[M3_NTI], f32x4 (&adx)[M3_NTI],
-                                         f32x4 (&aw2)[(OUT + 15) / 16][M3_NT1], f32x4 (&aw1)[M3_NT1][M3_NTI], Prefetch prefetch) {
-    using L = M3BwdLds<OUT>;
-    const float *W2n = lds, *W1n = W2n + L::OP * L::SA;
+                                         f32x4 (&aw2)[(OUT + 15) / 16][M3_NT1], f32x4 (&aw1)[M3_NT1][M3_NTI], f32x4 (&wq)[2],
+                                         Prefetch prefetch, NextW nextw) {
+    using L = M3wLds<OUT>;
+    const float *W2i = lds, *W1i = W2i + L::OP * 64;
+    constexpr int NG2 = 4 * L::NT2;                                   // dH groups (u, j) = (k / 4, k % 4)
+    constexpr int NGX = 4 * (M3_HID / 16) + M3_HID % 16;              // dX groups (t, r) = (k / 4, k % 4): 16 t + r < M3_HID
+    static_assert(16 * (L::NT2 - 1) + 3 < OUT && M3_HID % 16 <= 4 && NG2 >= 4 && NGX >= 4, "every (k / 4, k % 4) below is a valid k-step");
     op.mask(g);
     f32x4 b[L::NT2];
 #pragma unroll
@@ -526,41 +589,26 @@ __device__ __forceinline__ void m3w_head(const float *lds, float *patches, M3wOp
     for (int t = 0; t < M3_NT1; ++t) m3w_put(patches + t * M3W_PATCH, op.h[t], g, c);
 #pragma unroll
     for (int u = 0; u < L::NT2; ++u) m3w_put(patches + (4 + u) * M3W_PATCH, b[u], g, c);
-    // (round 5) Every MFMA group's LDS operands are read one group ahead, behind scheduling fences: with one wave per SIMD a
-    // read issued just in time leaves the matrix pipe idle for its whole round trip — 375 of the 616 MFMAs of a tile had an
-    // lgkmcnt wait right in front of them (1023 -> 880 us).  Each loop's FIRST operands one loop ahead as well lost (17 spills).
-    auto ldw2 = [&](int u, int j) {
-        f32x4 w;
-#pragma unroll
-        for (int t = 0; t < M3_NT1; ++t) w[t] = W2n[(16 * u + 4 * g + j) * L::SA + 16 * t + c];
-        return w;
-    };
-    auto ldw1 = [&](int t, int r) {
-        f32x4 w;
-#pragma unroll
-        for (int v = 0; v < M3_NTI; ++v) w[v] = W1n[(16 * t + 4 * g + r) * L::SB + 16 * v + c];
-        return w;
-    };
+    auto ldw2 = [&](int k) { return *(const f32x4 *)(W2i + (16 * (k / 4) + 4 * g + k % 4) * 64 + 4 * c); };    // [t]
+    auto ldw1 = [&](int k) { return *(const f32x4 *)(W1i + (16 * (k / 4) + 4 * g + k % 4) * 64 + 4 * c); };    // [v]
     // dH = W2^T dZ2 (transposed chain, layout F)
-    f32x4 adh[M3_NT1], hn[M3_NT1], zc;
+    f32x4 adh[M3_NT1], hn[M3_NT1], z[L::NT2], w2[NG2], wx[NGX], d[M3_NT1];
 #pragma unroll
     for (int t = 0; t < M3_NT1; ++t) adh[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    {
-        f32x4 wc = ldw2(0, 0);
+    w2[0] = wq[0];
+    w2[1] = wq[1];
 #pragma unroll
-        for (int u = 0; u < L::NT2; ++u)
+    for (int k = 0; k < NG2; ++k) {
+        if (k + 2 < NG2) w2[k + 2] = ldw2(k + 2);
+        if (k == NG2 - 2) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (16 * u + j >= OUT) continue;
-                const int un = j == 3 ? u + 1 : u, jn = j == 3 ? 0 : j + 1;
-                f32x4 wn = wc;
-                if (un < L::NT2 && 16 * un + jn < OUT) wn = ldw2(un, jn);
-                M3_FENCE();
+            for (int t = 0; t < M3_NT1; ++t) hn[t] = m3w_get(patches + t * M3W_PATCH, g, c);
+        }
+        if (k == NG2 - 1) z[0] = m3w_get(patches + 4 * M3W_PATCH, g, c);
+        M3_FENCE();
 #pragma unroll
-                for (int t = 0; t < M3_NT1; ++t) adh[t] = frag_mfma(wc[t], b[u][j], adh[t]);
-                M3_FENCE();
-                wc = wn;
-            }
+        for (int t = 0; t < M3_NT1; ++t) adh[t] = frag_mfma(w2[k][t], b[k / 4][k % 4], adh[t]);
+        M3_FENCE();
     }
 #pragma unroll
     for (int t = 0; t < M3_NT1; ++t) {
@@ -569,70 +617,64 @@ __device__ __forceinline__ void m3w_head(const float *lds, float *patches, M3wOp
         m3w_put(patches + (9 + t) * M3W_PATCH, adh[t], g, c);          // patches 9..12: dZ1
     }
     // dW2 += dZ2^T [H | 1] (row contraction, layout N)
-#pragma unroll
-    for (int t = 0; t < M3_NT1; ++t) hn[t] = m3w_get(patches + t * M3W_PATCH, g, c);
-    zc = m3w_get(patches + 4 * M3W_PATCH, g, c);
     if (c == M3_HID - 48) hn[3] = ones;                         // column 50 of [H | 1]
 #pragma unroll
     for (int u = 0; u < L::NT2; ++u) {
-        f32x4 zn = zc;
-        if (u + 1 < L::NT2) zn = m3w_get(patches + (4 + u + 1) * M3W_PATCH, g, c);
+        if (u + 1 < L::NT2) z[u + 1] = m3w_get(patches + (4 + u + 1) * M3W_PATCH, g, c);
+        if (u == L::NT2 - 1) {
+            wx[0] = ldw1(0);
+            wx[1] = ldw1(1);
+        }
         M3_FENCE();
         // r outermost: consecutive MFMAs go to DIFFERENT accumulators (same additions per accumulator, same order)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int t = 0; t < M3_NT1; ++t) aw2[u][t] = frag_mfma(zc[r], hn[t][r], aw2[u][t]);
+            for (int t = 0; t < M3_NT1; ++t) aw2[u][t] = frag_mfma(z[u][r], hn[t][r], aw2[u][t]);
         M3_FENCE();
-        zc = zn;
     }
     prefetch();
     // dX += W1^T dZ1
-    f32x4 wx = ldw1(0, 0);
 #pragma unroll
-    for (int t = 0; t < M3_NT1; ++t)
+    for (int k = 0; k < NGX; ++k) {
+        if (k + 2 < NGX) wx[k + 2] = ldw1(k + 2);
+        if (k == NGX - 2) d[0] = m3w_get(patches + 9 * M3W_PATCH, g, c);
+        M3_FENCE();
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (16 * t + r >= M3_HID) continue;
-            const int tn = r == 3 ? t + 1 : t, rn = r == 3 ? 0 : r + 1;
-            f32x4 wn = wx;
-            if (tn < M3_NT1 && 16 * tn + rn < M3_HID) wn = ldw1(tn, rn);
-            M3_FENCE();
-#pragma unroll
-            for (int v = 0; v < M3_NTI; ++v) adx[v] = frag_mfma(wx[v], adh[t][r], adx[v]);
-            M3_FENCE();
-            wx = wn;
-        }
+        for (int v = 0; v < M3_NTI; ++v) adx[v] = frag_mfma(wx[k][v], adh[k / 4][k % 4], adx[v]);
+        M3_FENCE();
+    }
     // dW1 += dZ1^T [X | 1]
-    f32x4 dc = m3w_get(patches + 9 * M3W_PATCH, g, c);
 #pragma unroll
     for (int t = 0; t < M3_NT1; ++t) {
-        f32x4 dn = dc;
-        if (t + 1 < M3_NT1) dn = m3w_get(patches + (9 + t + 1) * M3W_PATCH, g, c);
+        if (t + 1 < M3_NT1) d[t + 1] = m3w_get(patches + (9 + t + 1) * M3W_PATCH, g, c);
+        if (t == M3_NT1 - 1) nextw(wq);
         M3_FENCE();
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int v = 0; v < M3_NTI; ++v) aw1[t][v] = frag_mfma(dc[r], xn[v][r], aw1[t][v]);
+            for (int v = 0; v < M3_NTI; ++v) aw1[t][v] = frag_mfma(d[t][r], xn[v][r], aw1[t][v]);
         M3_FENCE();
-        dc = dn;
     }
 }
 
-template <bool ROWS, bool TL = false>         // TL: Hcat is the TILED forward's (fragment-major: one contiguous KB per load)
+// TL: Hcat is the TILED forward's (fragment-major: one contiguous KB per load).  RG: X == NULL, the input rows are assembled
+// again (below) — a template parameter, not a run-time flag: the two loaders behind a uniform branch in the middle of the last
+// head's prefetch left the compiler two `s_waitcnt vmcnt(0)` at the joins (737 -> 723 us with X kept, the shipped mode).
+template <bool ROWS, bool TL = false, bool RG = false>
 __global__ void __launch_bounds__(M3W_WAVES * 64) __attribute__((amdgpu_waves_per_eu(1, 1)))
     mlp3_bwd_wg_kernel(M3Head h0, M3Head h1, M3Head h2, const float *__restrict__ X, int64_t ldx,
                        const float *__restrict__ Hcat, float *__restrict__ dX, int64_t lddx, int64_t n, M3Rows R,
                        float *__restrict__ partial) {
-    constexpr int WF = M3BwdLds<10>::FLOATS + M3BwdLds<30>::FLOATS + M3BwdLds<70>::FLOATS;
+    constexpr int WF = M3wLds<10>::FLOATS + M3wLds<30>::FLOATS + M3wLds<70>::FLOATS;
     constexpr int PF = M3W_WAVES * M3W_NPATCH * M3W_PATCH;
     static_assert(WF + PF >= M3W_E, "the LDS image of the weight gradients reuses the weight region");
     __shared__ __attribute__((aligned(16))) float lds[WF + PF];
-    float *l0 = lds, *l1 = l0 + M3BwdLds<10>::FLOATS, *l2 = l1 + M3BwdLds<30>::FLOATS;
+    float *l0 = lds, *l1 = l0 + M3wLds<10>::FLOATS, *l2 = l1 + M3wLds<30>::FLOATS;
     const int tid = threadIdx.x, nthr = M3W_WAVES * 64;
-    m3_stage_bwd<10>(l0, h0, tid, nthr);
-    m3_stage_bwd<30>(l1, h1, tid, nthr);
-    m3_stage_bwd<70>(l2, h2, tid, nthr);
+    m3w_stage<10>(l0, h0, tid, nthr);
+    m3w_stage<30>(l1, h1, tid, nthr);
+    m3w_stage<70>(l2, h2, tid, nthr);
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
     float *patches = lds + WF + wave * M3W_NPATCH * M3W_PATCH;
@@ -655,7 +697,7 @@ __global__ void __launch_bounds__(M3W_WAVES * 64) __attribute__((amdgpu_waves_pe
     M3wBufs B;
     B.dY[0] = cl_buf(h0.dY, nb * 40); B.dY[1] = cl_buf(h1.dY, nb * 120); B.dY[2] = cl_buf(h2.dY, nb * 280);
     B.Y[0] = cl_buf(h0.Y, nb * 40); B.Y[1] = cl_buf(h1.Y, nb * 120); B.Y[2] = cl_buf(h2.Y, nb * 280);
-    static_assert(ROWS || !TL, "the tiled hand-over belongs to the ROWS pair");
+    static_assert(ROWS || !(TL || RG), "the tiled hand-over and the re-assembled rows belong to the ROWS pair");
     B.H = cl_buf(Hcat, (TL ? (nb + 15) / 16 * 16 : nb) * (M3_HLD * 4));
     B.X = cl_buf(X, nb > 0 ? ((nb - 1) * (uint64_t)ldx + M3_IN) * 4 : 0);
     const ClBuf bSrc = cl_buf(ROWS ? R.src_row : nullptr, nb * 8), bAnc = cl_buf(ROWS ? R.anchor : nullptr, nb * 12);
@@ -664,15 +706,24 @@ __global__ void __launch_bounds__(M3W_WAVES * 64) __attribute__((amdgpu_waves_pe
     // (round 6) X == NULL (ROWS): the forward did not keep its assembled input rows (216 of the 1256 bytes per anchor it
     // stores: the forward is bound by exactly those stores) — the rows are assembled again here, by the forward's own loader
     // from the same operands: the same bits
-    const bool regather = ROWS && X == nullptr;
+    // The last piece of such a row (view direction, distance) is divisions behind two loads: only the loads are issued a tile
+    // ahead (load_x), the piece is formed where the tile starts (finish_x).  Formed inside the prefetch, it waited there for its
+    // loads, and with them for every load of the prefetch in front of them.
+    constexpr bool regather = RG;
     M3FwdBufs FB;
     FB.feat = cl_buf(regather ? R.feat_src : nullptr, CL_MAX_BYTES);
     FB.anc = bAnc;
+    M3XTail xt;
     auto load_x = [&](f32x4 (&x)[M3_NTI], int64_t row, int64_t srow, bool v) {
 #pragma unroll
-        for (int q = 0; q < M3_NTI; ++q)
-            x[q] = regather ? m3_load_x_rows_b(FB, cam0, cam1, cam2, row, srow, q, g, v)
-                            : frag_bload4<M3_IN>(B.X, (uint32_t)row * ldx4, q, g, v);
+        for (int q = 0; q < M3_NTI; ++q) {
+            if (regather && q == M3_NTI - 1) xt = m3_x_tail_issue<false>(FB, row, srow, g, v);
+            else x[q] = regather ? m3_load_x_rows_b(FB, cam0, cam1, cam2, row, srow, q, g, v)
+                                 : frag_bload4<M3_IN>(B.X, (uint32_t)row * ldx4, q, g, v);
+        }
+    };
+    auto finish_x = [&](f32x4 (&x)[M3_NTI], bool v) {
+        if (regather) x[M3_NTI - 1] = m3_x_tail_finish<false>(xt, cam0, cam1, cam2, g, v);
     };
     M3wOps<10, 1> op0;
     M3wOps<30, 2> op1;
@@ -686,6 +737,13 @@ __global__ void __launch_bounds__(M3W_WAVES * 64) __attribute__((amdgpu_waves_pe
         const int64_t s0 = regather ? cl_li64(bSrc, cl_sel(v0, (uint32_t)row * 8)) : 0;
         load_x(xf, row, s0, v0);
     }
+    // the first two dH weight groups of a head (rows 4g, 4g + 1 of its W2 image), requested by the head in front of it
+    auto ldw2_first = [&](const float *img, f32x4 (&w)[2]) {
+        w[0] = *(const f32x4 *)(img + (4 * g) * 64 + 4 * c);
+        w[1] = *(const f32x4 *)(img + (4 * g + 1) * 64 + 4 * c);
+    };
+    f32x4 wq[2];
+    ldw2_first(l0, wq);
     for (; tile < ntiles; tile += tstride) {
         const int64_t row0 = tile * 16;
         asm volatile("" ::: "memory");   // keep the LDS weight reads inside the tile loop (LICM would spill them)
@@ -700,6 +758,7 @@ __global__ void __launch_bounds__(M3W_WAVES * 64) __attribute__((amdgpu_waves_pe
         const int64_t srow_pre = ROWS ? cl_li64(bSrc, cl_sel(valid, (uint32_t)(row0 + c) * 8)) : 0;
         if (regather) srow_next = cl_li64(bSrc, cl_sel(validn, (uint32_t)rown * 8));
         const f32x4 anc_pre = ROWS ? cl_l96(bAnc, cl_sel(valid && g == 0, (uint32_t)(row0 + c) * 12)) : zero;
+        finish_x(xf, valid);
 #pragma unroll
         for (int q = 0; q < M3_NTI; ++q) m3w_put(patches + q * M3W_PATCH, frag_bmask4<M3_IN>(xf[q], q, g), g, c);
 #pragma unroll
@@ -708,12 +767,18 @@ __global__ void __launch_bounds__(M3W_WAVES * 64) __attribute__((amdgpu_waves_pe
         f32x4 adx[M3_NTI];
 #pragma unroll
         for (int v = 0; v < M3_NTI; ++v) adx[v] = zero;
-        m3w_head<10, 1>(l0, patches, op0, ones, g, c, xn, adx, a2_0, a1_0, [&]() { op1.template load<TL>(B, 1, row0 + c, g, valid); });
-        m3w_head<30, 2>(l1, patches, op1, ones, g, c, xn, adx, a2_1, a1_1, [&]() { op2.template load<TL>(B, 2, row0 + c, g, valid); });
-        m3w_head<70, 0>(l2, patches, op2, ones, g, c, xn, adx, a2_2, a1_2, [&]() {
-            op0.template load<TL>(B, 0, rown, g, validn);
-            load_x(xf, rown, srow_next, validn);
-        });
+        m3w_head<10, 1>(l0, patches, op0, ones, g, c, xn, adx, a2_0, a1_0, wq,
+                        [&]() { op1.template load<TL>(B, 1, row0 + c, g, valid); }, [&](f32x4 (&w)[2]) { ldw2_first(l1, w); });
+        m3w_head<30, 2>(l1, patches, op1, ones, g, c, xn, adx, a2_1, a1_1, wq,
+                        [&]() { op2.template load<TL>(B, 2, row0 + c, g, valid); }, [&](f32x4 (&w)[2]) { ldw2_first(l2, w); });
+        // (the last head hands over to the NEXT tile: its operands from memory, and the first head's first weights — the tile
+        //  boundary is not a drain; a wave's last tile reads them for nothing)
+        m3w_head<70, 0>(l2, patches, op2, ones, g, c, xn, adx, a2_2, a1_2, wq,
+                        [&]() {
+                            op0.template load<TL>(B, 0, rown, g, validn);
+                            load_x(xf, rown, srow_next, validn);
+                        },
+                        [&](f32x4 (&w)[2]) { ldw2_first(l0, w); });
         if (ROWS) {
             const int64_t row = row0 + c;
             const int64_t srow = valid ? srow_pre : 0;
@@ -990,15 +1055,17 @@ static int m3_backward(const float *X, int64_t ldx, const float *const *W1, cons
         if (scratch && scratch_bytes >= (size_t)gridw * M3W_E * sizeof(float)) {
             {
                 CgsProfScope prof(CGS_PROF_MLP_BWD, stream);
-                if (rows && tiled)
-                    hipLaunchKernelGGL((mlp3_bwd_wg_kernel<true, true>), dim3(gridw), dim3(M3W_WAVES * 64), 0, stream, h[0], h[1], h[2], X,
-                                       ldx, Hcat, nullptr, 0, n, *rows, (float *)scratch);
-                else if (rows)
-                    hipLaunchKernelGGL((mlp3_bwd_wg_kernel<true>), dim3(gridw), dim3(M3W_WAVES * 64), 0, stream, h[0], h[1], h[2], X,
-                                       ldx, Hcat, nullptr, 0, n, *rows, (float *)scratch);
-                else
+#define M3W_LAUNCH_ROWS(TL_, RG_)                                                                                                   \
+                hipLaunchKernelGGL((mlp3_bwd_wg_kernel<true, TL_, RG_>), dim3(gridw), dim3(M3W_WAVES * 64), 0, stream, h[0], h[1], h[2], X, \
+                                   ldx, Hcat, nullptr, 0, n, *rows, (float *)scratch)
+                if (rows && tiled) {
+                    if (no_x) M3W_LAUNCH_ROWS(true, true); else M3W_LAUNCH_ROWS(true, false);
+                } else if (rows) {
+                    if (no_x) M3W_LAUNCH_ROWS(false, true); else M3W_LAUNCH_ROWS(false, false);
+                } else
                     hipLaunchKernelGGL((mlp3_bwd_wg_kernel<false>), dim3(gridw), dim3(M3W_WAVES * 64), 0, stream, h[0], h[1], h[2], X,
                                        ldx, Hcat, dX, lddx, n, M3Rows{}, (float *)scratch);
+#undef M3W_LAUNCH_ROWS
                 CGS_CHECK_HIP(hipGetLastError());
             }
             CgsProfScope prof(CGS_PROF_MLP_WGRAD, stream);
