@@ -41,6 +41,24 @@ class RasterCfg(C.Structure):
     ]
 
 
+class AdamTensor(C.Structure):
+    """struct cgs_adam_tensor — one tensor of a cgs_adam_step launch (optim.py)."""
+    _fields_ = [
+        ("p", c_void_p),
+        ("g", c_void_p),
+        ("m", c_void_p),
+        ("v", c_void_p),
+        ("numel", c_int64),
+        ("beta1", C.c_double),
+        ("beta2", C.c_double),
+        ("width", c_int32),
+        ("step_size", c_float),
+        ("bias2_sqrt", c_float),
+        ("eps", c_float),
+        ("weight_decay", c_float),
+    ]
+
+
 # name -> (restype, argtypes); the authoritative list of exported symbols.
 # tests/test_abi.py checks it against include/cgs.h.
 SIGNATURES = {
@@ -262,6 +280,7 @@ SIGNATURES = {
     "cgs_level_unique": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  C.POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
     "cgs_compact_rows": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
+    "cgs_adam_step": (c_int, [c_int, C.POINTER(AdamTensor), c_void_p, c_int64, c_void_p]),
     "cgs_l1_ssim_partials": (c_size_t, [c_int, c_int, c_int]),
     "cgs_l1_ssim_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cgs_l1_ssim_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -131,12 +131,19 @@ _OPEN_SYNC = None          # weakref to the GradientSync that currently owns the
 # which only visible anchors are differentiated (step <= 10 000: no context model over all anchors); None = every row.
 # GradientSync(sparse="auto") reads it: the decision to take the touched-rows path is the PHASE (the same on every rank),
 # whether the compact exchange pays is decided on the UNION of the ranks' rows (also the same on every rank).
-_TOUCHED = {"rows": None, "n": 0}
+_TOUCHED = {"rows": None, "n": 0, "count": 0}
 
 
 def note_touched_rows(mask, n_rows: int = 0):
     """mask: bool [N] of the anchors whose per-anchor gradients this view can touch, or None for "all of them"."""
     _TOUCHED["rows"], _TOUCHED["n"] = mask, int(n_rows)
+    _TOUCHED["count"] += 1
+
+
+def touched_rows():
+    """(mask, count): the last note_touched_rows mask (None = every row) and how many notes have been made so far — a reader
+    that remembers the count knows whether exactly one view was rendered since it last looked (optim.FusedAdam's "auto")."""
+    return _TOUCHED["rows"], _TOUCHED["count"]
 
 
 def _auto_rows(p):

@@ -234,7 +234,21 @@ class GaussianModel(nn.Module):
             {"params": self.latent_codec.parameters(), "lr": a.latent_codec_lr_init, "name": "latent_codec"},
             {"params": self.mlp_grid.parameters(), "lr": a.mlp_grid_lr_init, "name": "mlp_grid"},
         ]
-        self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        # CGS_OPTIMIZER: lets the reference's unmodified train.py opt in (its argument parser has no optimizer_type)
+        optimizer_type = os.environ.get("CGS_OPTIMIZER") or getattr(training_args, "optimizer_type", "default")
+        if optimizer_type == "default":
+            self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        elif optimizer_type in ("fused_adam", "sparse_adam"):
+            from .optim import FusedAdam
+            if optimizer_type == "sparse_adam":
+                # the tensors whose gradients reach only the anchors a view sees.  Not `mask`: train.py:209's regulariser puts
+                # gradient on every row of _mask (dist.GradientSync handles the same fact for the all-reduce)
+                for g in groups:
+                    if g["name"] in ("anchor", "offset", "anchor_feat", "hyper_latent", "scaling", "rotation"):
+                        g["row_sparse"] = True
+            self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)
+        else:
+            raise ValueError(f"optimizer_type {optimizer_type!r}: expected 'default', 'fused_adam' or 'sparse_adam'")
         late = 0 if self.ste_binary else 10000
         sched = lambda pre, scale=1.0, step_sub=0: expon_lr_func(
             getattr(a, pre + "_lr_init") * scale, getattr(a, pre + "_lr_final") * scale,

@@ -1397,6 +1397,37 @@ int cgs_scaling_reg_bwd(const float *scaling, const float *g, int64_t P, float *
 int cgs_sigmoid_mean_fwd(const float *x, int64_t n, float *partials, void *stream);
 int cgs_sigmoid_mean_bwd(const float *x, const float *g, int64_t n, float *dx, void *stream);
 
+/* ---- the optimizer step (scene/gaussian_model.py:475 `torch.optim.Adam(l, lr=0.0, eps=1e-15)` and train.py:255
+ * `gaussians.optimizer.step()`): Adam without amsgrad for up to CGS_ADAM_MAX fp32 tensors in ONE launch ----
+ * Per element, in fp32 (torch's `_single_tensor_adam`):
+ *   g' = g + weight_decay * p                 (only when weight_decay != 0)
+ *   m  = m + (g' - m) * (1 - beta1)
+ *   v  = v * beta2 + g' * g' * (1 - beta2)
+ *   p  = p - step_size * (m / (sqrt(v) / bias2_sqrt + eps))
+ * step_size = lr / (1 - beta1^t) and bias2_sqrt = sqrt(1 - beta2^t) are the caller's, computed in double as torch does.
+ * beta1 / beta2 are doubles: the kernel uses float(beta) and float(1 - beta) like torch, and 1 - float(0.999) is 1.3e-5
+ * away from float(0.001).
+ * width == 0: a dense tensor.  width > 0: numel == n_rows * width, element e belongs to row e / width, and an element
+ * whose byte of `rows` [n_rows] (device) is 0 has none of p, m, v read or written.  rows == NULL (then n_rows must be 0
+ * if any width > 0): every tensor is dense.  `tensors` is a HOST array (it travels in the kernel arguments); pointers
+ * need 4-byte alignment only, a tensor whose four pointers are 16-byte aligned takes the vector path.  No atomics: the
+ * result of a tensor does not depend on which tensors share its launch.  No host read-back.  nt == 0 or all numel == 0
+ * launches nothing.  CGS_ERR_ARG (before the device is touched): nt outside [0, CGS_ADAM_MAX], tensors == NULL, a
+ * NULL pointer with numel > 0, numel < 0, width < 0, n_rows < 0, width > 0 with numel != n_rows * width, width > 0
+ * with rows == NULL and n_rows != 0. */
+#define CGS_ADAM_MAX 32
+typedef struct cgs_adam_tensor {
+    float *p;
+    const float *g;
+    float *m;
+    float *v;
+    int64_t numel;
+    double beta1, beta2;
+    int32_t width;
+    float step_size, bias2_sqrt, eps, weight_decay;
+} cgs_adam_tensor;
+int cgs_adam_step(int nt, const cgs_adam_tensor *tensors, const uint8_t *rows, int64_t n_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
