@@ -931,6 +931,181 @@ def table_decode_lanes(blob, lens, C_, N, cdf, cdf_len, offset, medians, block):
     return out
 
 
+# ---- anchor positions in Morton order (container version 3: anchor.b) ---------------------------------------------------
+# Byte format ("anchor.b"), little endian: magic, N, B, symbols per class-coder block (4 x uint32), the class
+# CDF (50 x uint32), then per anchor block its first key (6 bytes) and its mantissa byte length (uint16), the byte lengths of the
+# class stream's coder blocks (uint32), the class stream and the mantissa blocks.
+_ANCHOR_MAGIC = int.from_bytes(b"CGA3", "little")
+_ANCHOR_BLOCK = 1024                     # anchors per block (stored; the decoder honours the stored value)
+_ANCHOR_CLS_BLOCK = 64 * 512             # class symbols per block of the lane-parallel table coder
+_ANCHOR_CLASSES = 49                     # bit lengths 0..48 of a gap between 48-bit keys
+_ANCHOR_FIXED = 16 + 4 * (_ANCHOR_CLASSES + 1)
+
+
+def _anchor_cdf(hist):
+    """Class counts [49] -> integer CDF [50] totalling 2^16 in which every class that occurs keeps at least one count."""
+    hist = np.asarray(hist, dtype=np.int64)
+    total = int(hist.sum())
+    freq = np.zeros(_ANCHOR_CLASSES, dtype=np.int64)
+    if total == 0:
+        freq[0] = 1 << 16
+    else:
+        freq = np.where(hist > 0, np.maximum(1, (hist * (2 << 16) + total) // (2 * total)), 0)
+        freq[int(np.argmax(hist))] += (1 << 16) - int(freq.sum())      # (the largest class holds >= 2^16 / 49: it stays positive)
+    cdf = np.zeros(_ANCHOR_CLASSES + 1, dtype=np.int64)
+    np.cumsum(freq, out=cdf[1:])
+    return cdf
+
+
+def _anchor_tables(cdf, dev):
+    """The stored CDF as the one-channel tables of the lane-parallel table coder (its last slot, the escape, gets no mass)."""
+    tab = np.concatenate([np.asarray(cdf, dtype=np.int32), [1 << 16]]).astype(np.int32)[None]
+    return _upload_small([tab, np.array([tab.shape[1]], np.int32), np.zeros(1, np.int32), np.zeros(1, np.float32)], dev)
+
+
+def _anchor_header(head, total):
+    """Host validation of an anchor.b stream of `total` bytes from its leading bytes `head` (all of it, or the fixed part first and
+    then the whole header: a staged stream stays on the device).  -> dict of the header's fields; RuntimeError on anything wrong."""
+    bad = lambda why: RuntimeError("anchor.b: " + why)
+    if total < _ANCHOR_FIXED or len(head) < _ANCHOR_FIXED:
+        raise bad(f"{total} bytes are shorter than the fixed header")
+    magic, N, B, cls_block = (int(v) for v in np.frombuffer(head, dtype="<u4", count=4))
+    if magic != _ANCHOR_MAGIC:
+        raise bad("wrong magic number")
+    if not 64 <= B <= 4096:
+        raise bad(f"block size {B} outside [64, 4096]")
+    if N >= 1 << 31 or not 64 <= cls_block <= 1 << 24:
+        raise bad("anchor count or class block size out of range")
+    cdf = np.frombuffer(head, dtype="<u4", count=_ANCHOR_CLASSES + 1, offset=16).astype(np.int64)
+    if cdf[0] != 0 or cdf[-1] != 1 << 16 or np.any(np.diff(cdf) < 0):
+        raise bad("the class CDF is not non-decreasing from 0 to 2^16")
+    nb = (N + B - 1) // B
+    n_cls = N - nb
+    ncb = (n_cls + cls_block - 1) // cls_block
+    hdr = _ANCHOR_FIXED + nb * 8 + ncb * 4
+    out = {"N": N, "B": B, "cls_block": cls_block, "cdf": cdf, "n_blocks": nb, "n_cls": n_cls, "header_bytes": hdr}
+    if total < hdr:
+        raise bad("shorter than its header tables")
+    if len(head) < hdr:
+        return out                                   # the caller comes back with the tables
+    first = np.zeros((nb, 8), dtype=np.uint8)
+    first[:, :6] = np.frombuffer(head, dtype=np.uint8, count=nb * 6, offset=_ANCHOR_FIXED).reshape(nb, 6)
+    mant_len = np.frombuffer(head, dtype="<u2", count=nb, offset=_ANCHOR_FIXED + nb * 6).astype(np.int64)
+    cls_len = np.frombuffer(head, dtype="<u4", count=ncb, offset=_ANCHOR_FIXED + nb * 8).astype(np.int64)
+    if hdr + int(cls_len.sum()) + int(mant_len.sum()) != total:
+        raise bad(f"header {hdr} + class stream {int(cls_len.sum())} + mantissas {int(mant_len.sum())} bytes do not add up to "
+                  f"the stream's {total}")
+    out.update(first_key=first.view("<u8").reshape(nb), mant_len=mant_len, cls_len=cls_len)
+    return out
+
+
+def anchor_encode(q):
+    """q int32 [N, 3] device tensor of quantised anchor indices, each in [0, 65535] -> (order int64 [N] device, stream bytes):
+    `order` is the stable ascending sort of the 48-bit Morton keys and the stream (anchor.b of container version 3) codes
+    q[order] without loss: per block of 1024 anchors a raw first key, then gap classes through the lane-parallel table coder
+    under a static CDF stored in the header, and the gaps' low bits bit-packed (csrc/anchor_code.hip)."""
+    L = _lib.lib()
+    _lib.require_device(q)
+    if q.dim() != 2 or q.shape[1] != 3 or q.dtype != torch.int32:
+        raise ValueError("anchor_encode: q must be an int32 tensor [N, 3]")
+    dev = q.device
+    q = q.contiguous()
+    N, B, cls_block = int(q.shape[0]), _ANCHOR_BLOCK, _ANCHOR_CLS_BLOCK
+    nb = (N + B - 1) // B
+    n_cls = N - nb
+    fixed = np.array([_ANCHOR_MAGIC, N, B, cls_block], dtype="<u4").tobytes()
+    order = torch.empty(N, dtype=torch.int64, device=dev)
+    if N == 0:
+        return order, fixed + _anchor_cdf(np.zeros(_ANCHOR_CLASSES)).astype("<u4").tobytes()
+    stream = _lib.current_stream()
+    keys = torch.empty(N, dtype=torch.int64, device=dev)                  # (uint64 keys below 2^48)
+    st_hist = torch.zeros(1 + _ANCHOR_CLASSES, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(L.cgs_anchor_order_scratch_bytes(N)), dtype=torch.uint8, device=dev)
+    _lib.check(L.cgs_anchor_order(_lib.ptr(q), N, _lib.ptr(order), _lib.ptr(keys), _lib.ptr(st_hist[:1]), _lib.ptr(scratch),
+                                  scratch.numel(), stream), "cgs_anchor_order")
+    slot = int(L.cgs_anchor_pack_slot_bytes(B))
+    cls = torch.empty(max(n_cls, 1), dtype=torch.int32, device=dev)
+    first_len = torch.empty(nb * 3, dtype=torch.int32, device=dev)        # [first keys uint64 | mantissa byte lengths uint32]
+    first, mant_len = first_len[:2 * nb], first_len[2 * nb:]
+    slots = torch.empty(nb * slot + 16, dtype=torch.uint8, device=dev)
+    _lib.check(L.cgs_anchor_pack(_lib.ptr(keys), N, B, _lib.ptr(cls), _lib.ptr(first), _lib.ptr(slots), _lib.ptr(mant_len),
+                                 _lib.ptr(st_hist[1:]), stream), "cgs_anchor_pack")
+    # (an index out of range left key 0: everything queued so far ran on valid keys, and the one read below reports it)
+    src_off = torch.arange(nb + 1, dtype=torch.int64, device=dev) * slot
+    dst_off = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(mant_len, 0, out=dst_off[1:])
+    packed = torch.empty(nb * slot + 16, dtype=torch.uint8, device=dev)
+    _lib.check(L.cgs_streams_compact(_lib.ptr(slots), _lib.ptr(src_off), _lib.ptr(mant_len), _lib.ptr(dst_off), nb, _lib.ptr(packed),
+                                     stream), "cgs_streams_compact")
+    st_hist_h = st_hist.cpu().numpy()
+    if int(st_hist_h[0]) != 0:
+        raise RuntimeError("anchor_encode: an anchor index lies outside [0, 65535]")
+    cdf = _anchor_cdf(st_hist_h[1:])
+    if n_cls > 0:
+        tab, tab_len, tab_off, _ = _anchor_tables(cdf, dev)
+        cls_blob, cls_lens = table_encode_lanes(cls[:n_cls].view(1, n_cls), tab, tab_len, tab_off, cls_block)
+    else:
+        cls_blob, cls_lens = np.zeros(0, np.uint8), np.zeros(0, np.int64)
+    first_len_h = first_len.cpu().numpy()
+    first_h = first_len_h[:2 * nb].view("<u8")
+    mant_len_h = first_len_h[2 * nb:].astype(np.int64)
+    mant = packed[:int(mant_len_h.sum())].cpu().numpy()
+    header = b"".join([fixed, cdf.astype("<u4").tobytes(),
+                       np.ascontiguousarray(first_h.view(np.uint8).reshape(nb, 8)[:, :6]).tobytes(),
+                       mant_len_h.astype("<u2").tobytes(), np.asarray(cls_lens).astype("<u4").tobytes()])
+    return order, header + cls_blob.tobytes() + mant.tobytes()
+
+
+def anchor_decode(stream, device=None):
+    """Inverse of anchor_encode: anchor.b as bytes / uint8 ndarray, or as a staged uint8 device tensor followed by >= 16 readable
+    bytes (StagedFiles.get), -> q int32 [N, 3] on the device, rows in the encoder's sorted order.  The header is validated on the
+    host BEFORE anything is launched (RuntimeError: wrong magic, lengths that do not add up to the stream's size, a CDF that is
+    not non-decreasing up to 2^16, a block size outside [64, 4096]); the kernels bound every read by the stored block lengths
+    and report a malformed payload, which raises RuntimeError too."""
+    L = _lib.lib()
+    if isinstance(stream, torch.Tensor) and stream.is_cuda:
+        dev, in_d, total = stream.device, stream.reshape(-1), int(stream.numel())
+        if in_d.dtype != torch.uint8:
+            raise RuntimeError("anchor.b: a staged stream must be a uint8 tensor")
+        head = in_d[:min(total, _ANCHOR_FIXED)].cpu().numpy().tobytes()
+        h = _anchor_header(head, total)
+        if "mant_len" not in h:
+            h = _anchor_header(in_d[:h["header_bytes"]].cpu().numpy().tobytes(), total)
+    else:
+        dev = torch.device(device if device is not None else "cuda")
+        buf = np.frombuffer(stream, dtype=np.uint8) if not isinstance(stream, np.ndarray) else stream.reshape(-1).view(np.uint8)
+        total = int(buf.size)
+        h = _anchor_header(buf.tobytes(), total)
+        in_d = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
+        in_d[:total].copy_(torch.from_numpy(buf.copy()))
+    N, B, nb, n_cls, hdr = h["N"], h["B"], h["n_blocks"], h["n_cls"], h["header_bytes"]
+    q = torch.empty(N, 3, dtype=torch.int32, device=dev)
+    if N == 0:
+        return q
+    cls_bytes = int(h["cls_len"].sum())
+    if n_cls > 0:
+        tab, tab_len, tab_off, med = _anchor_tables(h["cdf"], dev)
+        cls = table_decode_lanes(in_d[hdr:], h["cls_len"], 1, n_cls, tab, tab_len, tab_off, med, h["cls_block"])
+    else:
+        cls = torch.zeros(1, 1, dtype=torch.float32, device=dev)
+    mant_off_h = np.zeros(nb + 1, dtype=np.int64)
+    np.cumsum(h["mant_len"], out=mant_off_h[1:])
+    first, mant_off = _upload_small([h["first_key"].astype(np.int64), mant_off_h], dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    mant = in_d[hdr + cls_bytes:]
+    _lib.check(L.cgs_anchor_unpack(_lib.ptr(cls), N, B, _lib.ptr(first), _lib.ptr(mant) if mant.numel() else _lib.ptr(in_d),
+                                   _lib.ptr(mant_off), _lib.ptr(q), _lib.ptr(status), _lib.current_stream()), "cgs_anchor_unpack")
+    bad = int(status.item())
+    if n_cls > 0:
+        try:
+            decode_status_check(dev)                 # the class stream's lane decoder
+        except ValueError as e:
+            raise RuntimeError("anchor.b: " + str(e)) from e
+    if bad:
+        raise RuntimeError(f"anchor.b: block {bad - 1} holds a gap class above 48 or a mantissa past its stored byte length")
+    return q
+
+
 def gaussian_cdf_table(mean, scale, Q, min_v, max_v, q_div=1):
     """uint16 [n, max-min+2] integer CDF table of one stream (test hook)."""
     L = _lib.lib()

@@ -17,6 +17,10 @@ one wave per stream (codec.gaussian_encode_groups / gaussian_decode_groups):
   * the format's serial host streams (the mask stream, the 10 000-anchor hyper rANS
     strings) run on host threads next to the device work (codec.host_pool).
 
+Container version 3 (opt-in) is version 2 with the anchors coded: anchor.b (codec.anchor_encode: Morton-ordered positions, gap
+classes through the table coder, raw low bits) replaces anchor.npy, and every per-anchor tensor is coded in that sorted order, so
+the decoded model's rows come back sorted by Morton key.
+
 Deliberate deviation: the reference's decoder raises IndexError when fewer
 than 10 000 anchors are valid (:1322-1331); this one decodes any size.
 """
@@ -48,6 +52,11 @@ MAX_BATCH = 1_000                                              # :1071
 # "Lane-parallel Gaussian codec": the coder arithmetic runs 64-wide in vector registers instead of one serial chain per
 # wave on the scalar unit).  meta.b gets a 15th item {"version": 2, "block_symbols": ..., "chunk": {"masks": ...},
 # "bit_masks": [...]}; the per-stream lists of the header (bits, min, max) are per block; a 14-item list is version 1.
+# 3 = version 2 with the anchor positions coded without loss: anchor.b (codec.anchor_encode / anchor_decode, csrc/anchor_code.hip;
+# byte format in INTEGRATION.md) instead of anchor.npy.  The valid anchors are coded in the stable ascending order of their
+# 48-bit Morton keys — the selection of every per-anchor tensor is nonzero(mask)[order] instead of [mask] — so the level plan,
+# the contexts and every other stream live in that order, and so do the rows of the decoded model.  meta.b's 15th item says
+# "version": 3 and adds "anchor": {"scheme": "morton-gap", "block": B, "bytes": len(anchor.b)}.  One rank only.
 CONTAINER_VERSION = 1
 V2_BLOCK = 64 * 512                      # symbols per block: 512 per lane stream
 V2_CHUNK = {"masks": 1000}               # anchors per mask chunk stream
@@ -351,8 +360,13 @@ def _tracer(name):
 @torch.no_grad()
 def conduct_encoding(pc, pre_path_name, container_version=None):   # :1007-1295
     version = default_container_version() if container_version is None else int(container_version)
-    if version not in (1, 2):
-        raise ValueError(f"container version {version}: 1 (the reference's container) or 2")
+    if version not in (1, 2, 3):
+        raise ValueError(f"container version {version}: 1 (the reference's container), 2 or 3")
+    if version == 3 and mgpu.world() > 1:
+        raise NotImplementedError("container version 3 (anchors coded in Morton order) is written by one rank only")
+    anchors_coded = version == 3
+    if anchors_coded:
+        version = 2                   # everything but the anchor file and the order of the rows is version 2
     chunk = dict(V2_CHUNK) if version == 2 else {"masks": MAX_BATCH}
     lanes = version == 2
     torch.cuda.synchronize(); t1 = time.time()
@@ -366,6 +380,13 @@ def conduct_encoding(pc, pre_path_name, container_version=None):   # :1007-1295
     # the mask stream (:1265-1269) is ONE serial arithmetic-coded stream and the longest chain of the encoder (10 M symbols on
     # a host thread): it is started FIRST, before the prior tables and the other per-anchor gathers
     mask_anchor = pc.get_mask_anchor
+    if anchors_coded:
+        # version 3: the valid anchors in the stable ascending order of their Morton keys (an index selection; the model itself
+        # is neither permuted nor modified).  Everything below is defined on whatever order this selection produces.
+        _q = Quantize_anchor.apply(pc._anchor[mask_anchor], pc.x_bound_min, pc.x_bound_max)[1]
+        anchor_order, anchor_stream = codec.anchor_encode(_q.to(torch.int32))
+        mask_anchor = torch.nonzero(mask_anchor.reshape(-1))[:, 0][anchor_order]
+        tr("anchors ordered and coded (device)")
     _mask = pc.get_mask[mask_anchor]
     prob_masks = (_mask.sum() / _mask.numel()).item() if _mask.numel() else 0.5
     if root and version == 2:
@@ -402,7 +423,9 @@ def conduct_encoding(pc, pre_path_name, container_version=None):   # :1007-1295
     grid_scaling_after_Q = torch.zeros_like(_scaling)
     already_coded = torch.zeros(_feat.shape[0], dtype=torch.bool, device=_feat.device)
     writes = []                       # file writes run on host threads while the device predicts / codes
-    if root:
+    if root and anchors_coded:
+        writes += codec.write_file(path("anchor.b"), anchor_stream)
+    elif root:
         anchor_u16 = quantized_anchor.cpu().numpy().astype(np.uint16)                       # :1100-1101
         writes.append(codec.host_pool().submit(np.save, path("anchor.npy"), anchor_u16))
 
@@ -503,7 +526,7 @@ def conduct_encoding(pc, pre_path_name, container_version=None):   # :1007-1295
         bit_hyper_list = [len(b) * 8 for b in hyper_bytes]
         with open(path("hyper.b"), "wb") as f:
             f.write(b"".join(hyper_bytes))
-    bit_anchor = _anchor.numel() * 16
+    bit_anchor = len(anchor_stream) * 8 if anchors_coded else _anchor.numel() * 16
     bit_hyper = int(np.sum(bit_hyper_list))
     bit_feat = sum(int(np.sum(v)) for v in bit_d["feat"].values())
     bit_scaling = sum(int(np.sum(v)) for v in bit_d["scaling"].values())
@@ -533,6 +556,8 @@ def conduct_encoding(pc, pre_path_name, container_version=None):   # :1007-1295
     if version == 2:
         meta.append({"version": 2, "block_symbols": V2_BLOCK, "block_policy": V2_BLOCK_POLICY, "hyper_block": V2_HYPER_BLOCK, "chunk": chunk,
                      "bit_masks": mask_lens * 8})
+        if anchors_coded:
+            meta[-1].update(version=3, anchor={"scheme": "morton-gap", "block": codec._ANCHOR_BLOCK, "bytes": len(anchor_stream)})
     torch.save(meta, meta_path)
     bit_meta = os.path.getsize(meta_path) * 8
     mlp = pc.get_mlp_size()[0]
@@ -553,6 +578,8 @@ def conduct_decoding(pc, pre_path_name):                       # :1299-1539
     # anchor.npy (12 MB at 1 M anchors) is read and converted on a host thread while this one loads the header, the MLPs and
     # the prior tables: the level plan — the first thing the device chain waits for — needs nothing else from the files
     def read_anchors():
+        if not os.path.exists(path("anchor.npy")):
+            return None                                   # container version 3: anchor.b, staged and decoded on the device
         a = np.load(path("anchor.npy"))
         pinned = codec._pinned_staging(a.size * 4, "anchors")[:a.size * 4].view(torch.int32).view(a.shape)
         np.copyto(pinned.numpy(), a, casting="unsafe")
@@ -564,20 +591,27 @@ def conduct_decoding(pc, pre_path_name):                       # :1299-1539
      bit_hyper_list, bit_feat_d, bit_scaling_d, bit_offsets_d, N_levels_list) = meta[:14]
     extra = meta[14] if len(meta) > 14 else {"version": 1}
     version = int(extra.get("version", 1))
-    if version not in (1, 2):
-        raise RuntimeError(f"meta.b: container version {version} is newer than this decoder (1, 2)")
+    if version not in (1, 2, 3):
+        raise RuntimeError(f"meta.b: container version {version} is newer than this decoder (1, 2, 3)")
+    if version == 3 and mgpu.world() > 1:
+        raise NotImplementedError("container version 3 (anchors coded in Morton order) is decoded by one rank only")
+    anchors_coded = version == 3
+    if anchors_coded:
+        version = 2                   # everything but the anchor file is version 2
     # all coded streams: file -> pinned buffer -> device by the staging threads on a side stream, in the order the coder
     # launches consume them; started before anything else is loaded (reading ~120 MB is the longest chain of the prologue)
     dev = pc.x_bound_min.device
     n_lv = len(N_levels_list)
     if version == 2:       # masks first (their launch runs beside the prologue), then level by level incl. the offsets
-        order = ["masks.b", "hyper.b"] + [f"{a}{l}.b" for l in reversed(range(n_lv)) for a in ("feat", "scaling", "offsets")]
+        # (version 3: anchor.b in front of them, because the anchors gate the level plan)
+        order = (["anchor.b"] if anchors_coded else []) + ["masks.b", "hyper.b"] + [f"{a}{l}.b" for l in reversed(range(n_lv)) for a in ("feat", "scaling", "offsets")]
     else:
         order = [f"{a}{l}.b" for l in reversed(range(n_lv)) for a in ("feat", "scaling")] + \
                 [f"offsets{l}.b" for l in reversed(range(n_lv))]
     # (only masks.b starts now: the checkpoint is read first, on a quiet interpreter — beside eight reader threads that read
     #  took 4-8 ms instead of 0.3; the other files are released right after it and are still early for the first level)
-    staged = codec.StagedFiles([path(f_) for f_ in order if os.path.exists(path(f_))], dev, start=1 if version == 2 else 0)
+    staged = codec.StagedFiles([path(f_) for f_ in order if os.path.exists(path(f_))], dev,
+                               start=(2 if anchors_coded else 1) if version == 2 else 0)
     codec.decode_status(dev, reset=True)     # the lane decoders report a malformed block here (read once, after the last launch)
     tr("file staging prepared")
     chunk = extra["chunk"] if version == 2 else {"masks": max_batch}
@@ -619,7 +653,13 @@ def conduct_decoding(pc, pre_path_name):                       # :1299-1539
     load_mlp_checkpoints(pc, path("mlp.pt"), ck=ck, tr=tr, stored_tables=version == 2)     # (incl. the hyper prior's CDF tables)
     # the level plan (sorts and compactions: milliseconds of device work) needs the anchors and the checkpoint's bounds only:
     # queued now, it runs while the host goes on with the mask / hyper launches
-    q = anchor_job.result().to(dev, non_blocking=True)           # :1340-1342 (pinned: the copy is queued, not waited for)
+    if anchors_coded:
+        q = codec.anchor_decode(staged.get(path("anchor.b")))    # int32 [N_valid, 3], rows in Morton order
+        if int(q.shape[0]) != N_valid:
+            raise RuntimeError(f"anchor.b holds {int(q.shape[0])} anchors, meta.b's levels {N_valid}")
+        tr("anchor.b decoded (device)")
+    else:
+        q = anchor_job.result().to(dev, non_blocking=True)       # :1340-1342 (pinned: the copy is queued, not waited for)
     interval = (pc.x_bound_max - pc.x_bound_min) * Q_anchor + 1e-6
     anchor_decoded = q * interval + pc.x_bound_min
     tr("anchors on the device")

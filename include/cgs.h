@@ -41,6 +41,10 @@
  *   cgs_bernoulli_ac_*         encoder / decoder of the offset masks
  *                              (utils/encodings.py:147-180) as chunk streams
  *                              on the device (container version 2)
+ *   cgs_anchor_order, _pack,
+ *   cgs_anchor_unpack          no counterpart: the anchor positions coded in Morton
+ *                              order (container version 3; the reference stores
+ *                              them raw, scene/gaussian_model.py:1100-1101)
  *   cgs_pread_ranges,
  *   cgs_pwrite_ranges          the container's file reads / writes
  *                              (scene/gaussian_model.py:1235-1238, 1455-1481)
@@ -1138,6 +1142,46 @@ int cgs_bernoulli_ac_decode(uint32_t c1, const int64_t *stream_off,
 int cgs_gaussian_cdf_table(const float *mean, const float *scale,
                            const float *Q, int64_t q_div, int64_t n, int min_v,
                            int max_v, uint16_t *table, void *stream);
+
+/* Container version 3, anchor.b: the quantised anchor positions coded without
+ * loss in Morton order (byte format: INTEGRATION.md).  A position (qx, qy, qz),
+ * each index in [0, 65535], has the 48-bit key whose bit 3b+2 / 3b+1 / 3b is bit
+ * b of qx / qy / qz.
+ * cgs_anchor_order: q int32 [n, 3] (device) -> order int64 [n], the STABLE
+ * ascending sort of the keys (equal keys keep their input order), and
+ * keys_sorted uint64 [n] = key[order[i]]: two cgs_sort_pairs_u32 sorts, the low
+ * 24 bits and then the high 24 bits, carrying the permutation.  An index
+ * outside [0, 65535] makes *status (device int32, zeroed by the caller) 1; its
+ * key is then 0, nothing is clamped.  scratch from
+ * cgs_anchor_order_scratch_bytes(n). */
+size_t cgs_anchor_order_scratch_bytes(int64_t n);
+int cgs_anchor_order(const int32_t *q, int64_t n, int64_t *order,
+                     uint64_t *keys_sorted, int32_t *status, void *scratch,
+                     size_t scratch_bytes, void *stream);
+/* cgs_anchor_pack: the sorted keys in blocks of `block` anchors (64..4096), one
+ * workgroup each.  first_key[b] = the block's first key; every other key is the
+ * gap d >= 0 to its predecessor, sent as the class c = bit length of d (0..48)
+ * and the c - 1 low bits of d.  cls int32 [n - n_blocks] receives the classes
+ * block after block (the symbols of cgs_table_ac_encode_lanes), hist uint32 [49]
+ * (zeroed by the caller) their counts; block b's mantissa bits, packed LSB
+ * first from a byte boundary, land at slots + b * cgs_anchor_pack_slot_bytes(block)
+ * (16-byte aligned; mant_len[b] bytes, for cgs_streams_compact). */
+size_t cgs_anchor_pack_slot_bytes(int block);
+int cgs_anchor_pack(const uint64_t *keys_sorted, int64_t n, int block,
+                    int32_t *cls, uint64_t *first_key, uint8_t *slots,
+                    uint32_t *mant_len, uint32_t *hist, void *stream);
+/* cgs_anchor_unpack: the inverse, one workgroup per block.  cls float
+ * [n - n_blocks]: the classes as cgs_table_ac_decode_lanes leaves them (one
+ * channel, medians 0); block b's mantissa bytes are mant + mant_off[b] ..
+ * mant_off[b + 1] (int64 [n_blocks + 1], device; `mant` readable to the end of
+ * the 4-byte word holding its last byte); -> q int32 [n, 3] in sorted order.
+ * Reads stay inside a block's bytes: a class outside 0..48 or a mantissa that
+ * would end past them is not read and *status (device int32, zeroed by the
+ * caller) becomes 1 + b. */
+int cgs_anchor_unpack(const float *cls, int64_t n, int block,
+                      const uint64_t *first_key, const uint8_t *mant,
+                      const int64_t *mant_off, int32_t *q, int32_t *status,
+                      void *stream);
 
 /* --- range-ANS for the hyper-prior symbols on the HOST
  * (EntropyBottleneck.compress / decompress, scene/gaussian_model.py:1088,
