@@ -675,6 +675,30 @@ extern "C" size_t cgs_raster_bwd_abs_scratch_bytes(int64_t P) {
     return cgs_raster_bwd_aux_scratch_bytes(P) + cgs_align_up(2 * n * sizeof(float), 256);
 }
 
+// The workspaces of a render the caller kept, for the passes enqueued behind it (cgs_raster_render_aux, _render_features,
+// cgs_raster_contrib): g and b zeroed, then carved where there is something to carve.  fn: the entry point's name in front of
+// the message; NULL for cgs_raster_render_aux, whose messages carry none.
+static int carve_kept_render(const char *fn, const cgs_raster_cfg *cfg, int64_t P, int64_t R, void *geom_ws, size_t geom_bytes,
+                             void *bin_ws, size_t bin_bytes, void *img_ws, size_t img_bytes, CgsGeom &g, CgsBin &b, CgsImg &im) {
+    const char *sep = fn ? ": " : "";
+    if (!fn) fn = "";
+    memset(&g, 0, sizeof(g));
+    memset(&b, 0, sizeof(b));
+    if (!cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
+        cgs_set_error("%s%simage workspace too small", fn, sep);
+        return CGS_ERR_WORKSPACE;
+    }
+    if (P > 0 && geom_ws && !cgs_geom_carve(&g, geom_ws, geom_bytes, P)) {
+        cgs_set_error("%s%sgeometry workspace too small", fn, sep);
+        return CGS_ERR_WORKSPACE;
+    }
+    if (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
+        cgs_set_error("%s%sbinning workspace too small: %zu < %zu", fn, sep, bin_bytes, cgs_raster_bin_bytes(P, R));
+        return CGS_ERR_WORKSPACE;
+    }
+    return CGS_OK;
+}
+
 // Enqueued after the view's cgs_raster_render / _render_spec that the caller kept (R = the count its binning workspace was
 // carved with): reads the lists, n_contrib, tile_last and final_T that render left.
 extern "C" int cgs_raster_render_aux(const cgs_raster_cfg *cfg, int64_t P, int64_t R, void *geom_ws, size_t geom_bytes,
@@ -690,20 +714,7 @@ extern "C" int cgs_raster_render_aux(const cgs_raster_cfg *cfg, int64_t P, int64
     CgsGeom g;
     CgsBin b;
     CgsImg im;
-    memset(&g, 0, sizeof(g));
-    memset(&b, 0, sizeof(b));
-    if (!cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
-        cgs_set_error("image workspace too small");
-        return CGS_ERR_WORKSPACE;
-    }
-    if (P > 0 && geom_ws && !cgs_geom_carve(&g, geom_ws, geom_bytes, P)) {
-        cgs_set_error("geometry workspace too small");
-        return CGS_ERR_WORKSPACE;
-    }
-    if (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
-        cgs_set_error("binning workspace too small: %zu < %zu", bin_bytes, cgs_raster_bin_bytes(P, R));
-        return CGS_ERR_WORKSPACE;
-    }
+    if ((rc = carve_kept_render(nullptr, cfg, P, R, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, g, b, im))) return rc;
     return cgs_launch_aux_fwd(cfg, g, b, im, out_depth, out_invdepth, out_alpha, (hipStream_t)stream_);
 }
 
@@ -842,20 +853,7 @@ extern "C" int cgs_raster_render_features(const cgs_raster_cfg *cfg, int64_t P, 
     CgsGeom g;
     CgsBin b;
     CgsImg im;
-    memset(&g, 0, sizeof(g));
-    memset(&b, 0, sizeof(b));
-    if (!cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
-        cgs_set_error("%s: image workspace too small", fn);
-        return CGS_ERR_WORKSPACE;
-    }
-    if (P > 0 && geom_ws && !cgs_geom_carve(&g, geom_ws, geom_bytes, P)) {
-        cgs_set_error("%s: geometry workspace too small", fn);
-        return CGS_ERR_WORKSPACE;
-    }
-    if (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
-        cgs_set_error("%s: binning workspace too small: %zu < %zu", fn, bin_bytes, cgs_raster_bin_bytes(P, R));
-        return CGS_ERR_WORKSPACE;
-    }
+    if ((rc = carve_kept_render(fn, cfg, P, R, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, g, b, im))) return rc;
     return cgs_launch_feat_fwd(cfg, g, b, im, features, C, out_features, (hipStream_t)stream_);
 }
 
@@ -884,20 +882,7 @@ extern "C" int cgs_raster_contrib(const cgs_raster_cfg *cfg, int64_t P, int64_t 
     CgsGeom g;
     CgsBin b;
     CgsImg im;
-    memset(&g, 0, sizeof(g));
-    memset(&b, 0, sizeof(b));
-    if (!cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
-        cgs_set_error("%s: image workspace too small", fn);
-        return CGS_ERR_WORKSPACE;
-    }
-    if (P > 0 && geom_ws && !cgs_geom_carve(&g, geom_ws, geom_bytes, P)) {
-        cgs_set_error("%s: geometry workspace too small", fn);
-        return CGS_ERR_WORKSPACE;
-    }
-    if (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
-        cgs_set_error("%s: binning workspace too small: %zu < %zu", fn, bin_bytes, cgs_raster_bin_bytes(P, R));
-        return CGS_ERR_WORKSPACE;
-    }
+    if ((rc = carve_kept_render(fn, cfg, P, R, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, g, b, im))) return rc;
     return cgs_launch_contrib(cfg, g, b, im, slot, acc_weight, acc_max_weight, acc_pixels, acc_top_pixels, out_top_id,
                               out_top_weight, out_count, (hipStream_t)stream_);
 }

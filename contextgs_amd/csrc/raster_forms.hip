@@ -7,16 +7,20 @@
 // SH rows are [M, 3] fp32 per Gaussian (M <= 16); only the (D+1)^2 active coefficients are read, as dwordx4 when the rows
 // are 16-byte aligned (M % 4 == 0).  The backward recomputes the colour and its clamp bits with the forward's device
 // function (-ffp-contract=off: the same bits) instead of storing a mask, and writes the whole dL/dshs row, zeros above
-// (D+1)^2 and for culled Gaussians included.
+// (D+1)^2 and for culled Gaussians included.  It takes dL/d(pixel mean) / dL/d(conic) as the blend backward finishes them
+// (not its raw sums).
+//
+// Two kernel templates, forward and backward.  The form (SHD, COV6) and the options (AA: antialiasing, ABS: absolute
+// screen-space gradients) are template flags of the kernels themselves; launch_fwd / launch_bwd pick the instance, and the
+// switches at the bottom instantiate only the forms that reach this file.
 #include "cgs_internal.h"
 #include "raster_forms.h"
 
 #define PF_THREADS 256
 
-// the backward kernel takes dL/d(pixel mean) / dL/d(conic) as the blend backward finishes them (not its raw sums)
-
 // SHD: -1 = colours precomputed, 0..3 = SH of that degree.  COV6: covariance from cov6 instead of scales / rotations.
-template <bool FILTER_ONLY, int SHD, bool COV6>
+// AA: antialiasing (raster_math.h, cgs_aa_h), the record's opacity is opacity * h.  Never with FILTER_ONLY.
+template <bool FILTER_ONLY, int SHD, bool COV6, bool AA>
 __global__ void __launch_bounds__(PF_THREADS)
     preprocess_form_kernel(int64_t P, int W, int H, float tanfovx, float tanfovy, float scale_modifier,
                            const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix,
@@ -38,11 +42,11 @@ __global__ void __launch_bounds__(PF_THREADS)
     bool ok;
     if (COV6) {
         const CgsCov3 c3 = {cov6[6 * i], cov6[6 * i + 1], cov6[6 * i + 2], cov6[6 * i + 3], cov6[6 * i + 4], cov6[6 * i + 5]};
-        ok = cgs_project_cov(p, c3, V, Pm, W, H, tanfovx, tanfovy, pr);
+        ok = cgs_project_cov<AA>(p, c3, V, Pm, W, H, tanfovx, tanfovy, pr);
     } else {
         const float3 s = make_float3(scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]);
         const float4 q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-        ok = cgs_project<float>(p, s, q, V, Pm, W, H, tanfovx, tanfovy, scale_modifier, pr);
+        ok = cgs_project<float, AA>(p, s, q, V, Pm, W, H, tanfovx, tanfovy, scale_modifier, pr);
     }
     auto color = [&]() -> float3 {
         if constexpr (SHD < 0) {
@@ -57,12 +61,16 @@ __global__ void __launch_bounds__(PF_THREADS)
             return make_float3(fmaxf(c.x, 0.f), fmaxf(c.y, 0.f), fmaxf(c.z, 0.f));
         }
     };
-    cgs_pre_fwd_form<FILTER_ONLY>(i, ok, pr, FILTER_ONLY ? 0.f : opacities[i], color, W, H, rec, depth_key, tiles, rect, radii);
+    cgs_pre_fwd_form<FILTER_ONLY, decltype(color), AA>(i, ok, pr, FILTER_ONLY ? 0.f : opacities[i], color, W, H, rec, depth_key, tiles,
+                                                       rect, radii);
 }
 
 // Per-Gaussian backward of the forms above (the blend backward's dL/d(pixel mean), dL/d(conic) and, for SH, dL/dcolor in,
-// as preprocess_bwd_kernel<false> takes them).  Every output row is written, zeros for culled Gaussians.
-template <int SHD, bool COV6, bool ABS>
+// as preprocess_bwd_kernel takes them).  Every output row is written, zeros for culled Gaussians.
+// AA (antialiasing): also reads opacities[i] and dL_dopacities[i] (dL/d(op_eff), the blend backwards' sum), writes
+// dL/d(opacity) = dL/d(op_eff) h over it and adds h's dL/d(cov2D) to the conic chain (raster_pre.h / raster_forms.h); the other
+// instances never touch the two pointers.  Culled Gaussians: no blend list holds them, dL_dopacities[i] stays 0.
+template <int SHD, bool COV6, bool ABS, bool AA>
 __global__ void __launch_bounds__(PF_THREADS)
     preprocess_bwd_form_kernel(int64_t P, int W, int H, float tanfovx, float tanfovy, float scale_modifier,
                                const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix,
@@ -73,7 +81,8 @@ __global__ void __launch_bounds__(PF_THREADS)
                                const float *__restrict__ dL_dconic, const float *__restrict__ dL_dcolors,
                                float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dmeans2D, float *__restrict__ dL_dshs,
                                float *__restrict__ dL_dscales, float *__restrict__ dL_drotations, float *__restrict__ dL_dcov6,
-                               const float *__restrict__ dL_dabs_px) {
+                               const float *__restrict__ dL_dabs_px, const float *__restrict__ opacities,
+                               float *__restrict__ dL_dopacities) {
     const int64_t i = (int64_t)blockIdx.x * PF_THREADS + threadIdx.x;
     if (i >= P) return;
     if (radii[i] <= 0) {
@@ -122,8 +131,9 @@ __global__ void __launch_bounds__(PF_THREADS)
     if (COV6) {
         const CgsCov3 c3 = {cov6[6 * i], cov6[6 * i + 1], cov6[6 * i + 2], cov6[6 * i + 3], cov6[6 * i + 4], cov6[6 * i + 5]};
         float M[9];
-        cgs_pre_bwd_cov(p, c3, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i], dL_dconic[3 * i + 1],
-                        dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, o, M);
+        cgs_pre_bwd_cov<AA>(p, c3, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i], dL_dconic[3 * i + 1],
+                            dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, o, M, AA ? opacities[i] : 0.f,
+                            AA ? dL_dopacities[i] : 0.f);
         // an off-diagonal number of the six stands for both symmetric entries
         dL_dcov6[6 * i + 0] = M[0];
         dL_dcov6[6 * i + 1] = M[1] + M[3];
@@ -134,8 +144,9 @@ __global__ void __launch_bounds__(PF_THREADS)
     } else {
         const float3 s_raw = make_float3(scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]);
         const float4 q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-        o = cgs_pre_bwd_one(p, s_raw, q, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i],
-                            dL_dconic[3 * i + 1], dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, scale_modifier);
+        o = cgs_pre_bwd_one<AA>(p, s_raw, q, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i],
+                                dL_dconic[3 * i + 1], dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, scale_modifier,
+                                AA ? opacities[i] : 0.f, AA ? dL_dopacities[i] : 0.f);
 #pragma unroll
         for (int k = 0; k < 3; ++k) dL_dscales[3 * i + k] = o.ds[k];
 #pragma unroll
@@ -150,202 +161,43 @@ __global__ void __launch_bounds__(PF_THREADS)
 #pragma unroll
     for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = o.dp[k]; if constexpr (!ABS) dL_dmeans2D[3 * i + k] = o.dm2[k]; }
     if constexpr (ABS) cgs_store_dm2_abs(dL_dmeans2D, i, o.dm2, dL_dabs_px, W, H);
-}
-
-// preprocess_form_kernel<false, SHD, COV6> with antialiasing (raster_math.h, cgs_aa_h): the record's opacity is opacity * h.
-// (Restated, not a shared body: routing the kernel above through a device function changed the instructions hipcc emits
-// for it.  The two are edited together.)
-template <int SHD, bool COV6>
-__global__ void __launch_bounds__(PF_THREADS)
-    preprocess_form_aa_kernel(int64_t P, int W, int H, float tanfovx, float tanfovy, float scale_modifier,
-                           const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix,
-                           const float *__restrict__ campos, const float *__restrict__ means3D,
-                           const float *__restrict__ colors, const float *__restrict__ shs, int sh_m, int sh_vec,
-                           const float *__restrict__ opacities, const float *__restrict__ scales,
-                           const float *__restrict__ rotations, const float *__restrict__ cov6, float4 *__restrict__ rec,
-                           uint32_t *__restrict__ depth_key, uint32_t *__restrict__ tiles, uint2 *__restrict__ rect,
-                           int32_t *__restrict__ radii) {
-    const int64_t i = (int64_t)blockIdx.x * PF_THREADS + threadIdx.x;
-    if (i >= P) return;
-
-    float V[16], Pm[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { V[k] = viewmatrix[k]; Pm[k] = projmatrix[k]; }
-    const float3 p = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
-
-    CgsProj pr;
-    bool ok;
-    if (COV6) {
-        const CgsCov3 c3 = {cov6[6 * i], cov6[6 * i + 1], cov6[6 * i + 2], cov6[6 * i + 3], cov6[6 * i + 4], cov6[6 * i + 5]};
-        ok = cgs_project_cov<true>(p, c3, V, Pm, W, H, tanfovx, tanfovy, pr);
-    } else {
-        const float3 s = make_float3(scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]);
-        const float4 q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-        ok = cgs_project<float, true>(p, s, q, V, Pm, W, H, tanfovx, tanfovy, scale_modifier, pr);
-    }
-    auto color = [&]() -> float3 {
-        if constexpr (SHD < 0) {
-            return make_float3(colors[3 * i], colors[3 * i + 1], colors[3 * i + 2]);
-        } else {
-            constexpr int N = 3 * (SHD + 1) * (SHD + 1);
-            float sh[N];
-            cgs_load_row<N>(shs + i * 3 * (int64_t)sh_m, sh_vec != 0, sh);
-            float3 d;
-            const float3 u = cgs_sh_dir(p, make_float3(campos[0], campos[1], campos[2]), d);
-            const float3 c = cgs_sh_rgb<SHD>(sh, u.x, u.y, u.z);
-            return make_float3(fmaxf(c.x, 0.f), fmaxf(c.y, 0.f), fmaxf(c.z, 0.f));
-        }
-    };
-    cgs_pre_fwd_form<false, decltype(color), true>(i, ok, pr, opacities[i], color, W, H, rec, depth_key, tiles, rect, radii);
-}
-
-// preprocess_bwd_form_kernel with antialiasing (restated, as the forward): also reads opacities[i] and dL_dopacities[i]
-// (dL/d(op_eff), the blend backwards' sum), writes dL/d(opacity) = dL/d(op_eff) h over it and adds h's dL/d(cov2D) to the
-// conic chain (raster_pre.h / raster_forms.h).  Culled Gaussians: no blend list holds them, dL_dopacities[i] stays 0.
-template <int SHD, bool COV6, bool ABS>
-__global__ void __launch_bounds__(PF_THREADS)
-    preprocess_bwd_form_aa_kernel(int64_t P, int W, int H, float tanfovx, float tanfovy, float scale_modifier,
-                               const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix,
-                               const float *__restrict__ campos, const float *__restrict__ means3D,
-                               const float *__restrict__ shs, int sh_m, int sh_vec, const float *__restrict__ scales,
-                               const float *__restrict__ rotations, const float *__restrict__ cov6,
-                               const int32_t *__restrict__ radii, const float *__restrict__ dL_dmean2D_px,
-                               const float *__restrict__ dL_dconic, const float *__restrict__ dL_dcolors,
-                               float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dmeans2D, float *__restrict__ dL_dshs,
-                               float *__restrict__ dL_dscales, float *__restrict__ dL_drotations, float *__restrict__ dL_dcov6,
-                                  const float *__restrict__ opacities, float *__restrict__ dL_dopacities,
-                                  const float *__restrict__ dL_dabs_px) {
-    const int64_t i = (int64_t)blockIdx.x * PF_THREADS + threadIdx.x;
-    if (i >= P) return;
-    if (radii[i] <= 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = 0.f; if constexpr (!ABS) dL_dmeans2D[3 * i + k] = 0.f; }
-        if constexpr (ABS) cgs_store_dm2_abs(dL_dmeans2D, i, nullptr, dL_dabs_px, W, H);
-        if (COV6) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) dL_dcov6[6 * i + k] = 0.f;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) dL_dscales[3 * i + k] = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) dL_drotations[4 * i + k] = 0.f;
-        }
-        if (SHD >= 0) cgs_zero_row(dL_dshs + i * 3 * (int64_t)sh_m, sh_vec != 0, sh_m);
-        return;
-    }
-
-    float V[16], Pm[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { V[k] = viewmatrix[k]; Pm[k] = projmatrix[k]; }
-    const float3 p = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
-
-    // SH first: its row (up to 48 floats) is dead before the geometry chain needs its registers
-    float3 gsh = make_float3(0.f, 0.f, 0.f);      // dL/dmeans3D through the view direction
-    if constexpr (SHD >= 0) {
-        constexpr int N = 3 * (SHD + 1) * (SHD + 1);
-        constexpr int K = (SHD + 1) * (SHD + 1);
-        float sh[N];
-        cgs_load_row<N>(shs + i * 3 * (int64_t)sh_m, sh_vec != 0, sh);
-        float3 d;
-        const float3 u = cgs_sh_dir(p, make_float3(campos[0], campos[1], campos[2]), d);
-        const float3 c = cgs_sh_rgb<SHD>(sh, u.x, u.y, u.z);         // the forward's colour: its clamp bits
-        const float g[3] = {c.x < 0.f ? 0.f : dL_dcolors[3 * i], c.y < 0.f ? 0.f : dL_dcolors[3 * i + 1],
-                            c.z < 0.f ? 0.f : dL_dcolors[3 * i + 2]};
-        float w[K], b[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) w[k] = sh[3 * k] * g[0] + sh[3 * k + 1] * g[1] + sh[3 * k + 2] * g[2];
-        const float3 gdir = cgs_sh_ddir<SHD>(w, u.x, u.y, u.z);
-        cgs_sh_basis<SHD>(u.x, u.y, u.z, b);
-        cgs_store_row<N>(dL_dshs + i * 3 * (int64_t)sh_m, sh_vec != 0, sh_m, [&](int j) { return b[j / 3] * g[j % 3]; });
-        if (SHD > 0) gsh = cgs_dnormvdv(d, gdir);
-    }
-    CgsPreBwd o;
-    if (COV6) {
-        const CgsCov3 c3 = {cov6[6 * i], cov6[6 * i + 1], cov6[6 * i + 2], cov6[6 * i + 3], cov6[6 * i + 4], cov6[6 * i + 5]};
-        float M[9];
-        cgs_pre_bwd_cov<true>(p, c3, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i], dL_dconic[3 * i + 1],
-                              dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, o, M, opacities[i], dL_dopacities[i]);
-        // an off-diagonal number of the six stands for both symmetric entries
-        dL_dcov6[6 * i + 0] = M[0];
-        dL_dcov6[6 * i + 1] = M[1] + M[3];
-        dL_dcov6[6 * i + 2] = M[2] + M[6];
-        dL_dcov6[6 * i + 3] = M[4];
-        dL_dcov6[6 * i + 4] = M[5] + M[7];
-        dL_dcov6[6 * i + 5] = M[8];
-    } else {
-        const float3 s_raw = make_float3(scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]);
-        const float4 q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-        o = cgs_pre_bwd_one<true>(p, s_raw, q, dL_dmean2D_px[2 * i], dL_dmean2D_px[2 * i + 1], dL_dconic[3 * i],
-                                  dL_dconic[3 * i + 1], dL_dconic[3 * i + 2], V, Pm, W, H, tanfovx, tanfovy, scale_modifier,
-                                  opacities[i], dL_dopacities[i]);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) dL_dscales[3 * i + k] = o.ds[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dL_drotations[4 * i + k] = o.dq[k];
-    }
-
-    if (SHD > 0) {
-        o.dp[0] += gsh.x;
-        o.dp[1] += gsh.y;
-        o.dp[2] += gsh.z;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { dL_dmeans3D[3 * i + k] = o.dp[k]; if constexpr (!ABS) dL_dmeans2D[3 * i + k] = o.dm2[k]; }
-    if constexpr (ABS) cgs_store_dm2_abs(dL_dmeans2D, i, o.dm2, dL_dabs_px, W, H);
-    dL_dopacities[i] = o.dop;
+    if constexpr (AA) dL_dopacities[i] = o.dop;
 }
 
 template <bool FILTER_ONLY, int SHD, bool COV6>
 static void launch_fwd(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForms &f, const float *means3D, const float *colors,
                        const float *opacities, const float *scales, const float *rotations, CgsGeom &g, int32_t *radii,
                        hipStream_t stream, bool aa) {
-    if (!FILTER_ONLY && aa)
-        hipLaunchKernelGGL((preprocess_form_aa_kernel<SHD, COV6>), dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)),
-                           dim3(PF_THREADS), 0, stream, P, cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
-                           cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, cfg->campos, means3D, colors, f.shs, f.sh_coeffs,
-                           f.sh_vec, opacities, scales, rotations, f.cov3D, g.rec, g.depth_key, g.tiles, g.rect, radii);
-    else
-        hipLaunchKernelGGL((preprocess_form_kernel<FILTER_ONLY, SHD, COV6>), dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)),
-                           dim3(PF_THREADS), 0, stream, P, cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
-                           cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, cfg->campos, means3D, colors, f.shs, f.sh_coeffs,
-                           f.sh_vec, opacities, scales, rotations, f.cov3D, g.rec, g.depth_key, g.tiles, g.rect, radii);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, stream, P,
+                           cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy, cfg->scale_modifier, cfg->viewmatrix,
+                           cfg->projmatrix, cfg->campos, means3D, colors, f.shs, f.sh_coeffs, f.sh_vec, opacities, scales, rotations,
+                           f.cov3D, g.rec, g.depth_key, g.tiles, g.rect, radii);
+    };
+    if constexpr (!FILTER_ONLY) {
+        if (aa) return go(preprocess_form_kernel<false, SHD, COV6, true>);
+    }
+    go(preprocess_form_kernel<FILTER_ONLY, SHD, COV6, false>);
 }
 
-template <int SHD, bool COV6, bool ABS>
-static void launch_bwd_abs(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForms &f, const float *means3D, const float *scales,
-                       const float *rotations, const int32_t *radii, const float *dL_dmean2D_px, const float *dL_dconic,
-                       const float *dL_dcolors, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs, float *dL_dscales,
-                       float *dL_drotations, float *dL_dcov3D, hipStream_t stream, const float *aa_opacities,
-                       float *aa_dL_dopacities, const float *dL_dabs_px) {
-    if (aa_opacities)
-        hipLaunchKernelGGL((preprocess_bwd_form_aa_kernel<SHD, COV6, ABS>), dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)),
-                           dim3(PF_THREADS), 0, stream, P, cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
-                           cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, cfg->campos, means3D, f.shs, f.sh_coeffs,
-                           f.sh_vec, scales, rotations, f.cov3D, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
-                           dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, aa_opacities, aa_dL_dopacities, dL_dabs_px);
-    else
-        hipLaunchKernelGGL((preprocess_bwd_form_kernel<SHD, COV6, ABS>), dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)),
-                           dim3(PF_THREADS), 0, stream, P, cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
-                           cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, cfg->campos, means3D, f.shs, f.sh_coeffs,
-                           f.sh_vec, scales, rotations, f.cov3D, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
-                           dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, dL_dabs_px);
-}
-
-// dL_dabs_px != NULL: dL_dmeans2D is [P, 4] (cgs_store_dm2_abs)
+// dL_dabs_px != NULL: dL_dmeans2D is [P, 4] (cgs_store_dm2_abs); aa_opacities != NULL: antialiasing
 template <int SHD, bool COV6>
 static void launch_bwd(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForms &f, const float *means3D, const float *scales,
                        const float *rotations, const int32_t *radii, const float *dL_dmean2D_px, const float *dL_dconic,
                        const float *dL_dcolors, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dshs, float *dL_dscales,
                        float *dL_drotations, float *dL_dcov3D, hipStream_t stream, const float *aa_opacities,
                        float *aa_dL_dopacities, const float *dL_dabs_px) {
-    if (dL_dabs_px)
-        launch_bwd_abs<SHD, COV6, true>(cfg, P, f, means3D, scales, rotations, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
-                                        dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_opacities,
-                                        aa_dL_dopacities, dL_dabs_px);
-    else
-        launch_bwd_abs<SHD, COV6, false>(cfg, P, f, means3D, scales, rotations, radii, dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D,
-                                         dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_opacities,
-                                         aa_dL_dopacities, dL_dabs_px);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((P + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, stream, P,
+                           cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy, cfg->scale_modifier, cfg->viewmatrix,
+                           cfg->projmatrix, cfg->campos, means3D, f.shs, f.sh_coeffs, f.sh_vec, scales, rotations, f.cov3D, radii,
+                           dL_dmean2D_px, dL_dconic, dL_dcolors, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations,
+                           dL_dcov3D, dL_dabs_px, aa_opacities, aa_dL_dopacities);
+    };
+    if (aa_opacities && dL_dabs_px) go(preprocess_bwd_form_kernel<SHD, COV6, true, true>);
+    else if (aa_opacities) go(preprocess_bwd_form_kernel<SHD, COV6, false, true>);
+    else if (dL_dabs_px) go(preprocess_bwd_form_kernel<SHD, COV6, true, false>);
+    else go(preprocess_bwd_form_kernel<SHD, COV6, false, false>);
 }
 
 // f.shs == NULL: colours precomputed; f.cov3D == NULL: scales / rotations.  Not both NULL (that form is

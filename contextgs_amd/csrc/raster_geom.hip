@@ -13,7 +13,8 @@
 
 #define PRE_THREADS 256
 
-template <bool FILTER_ONLY>
+// AA: antialiasing (upstream's `antialiasing`), the record's opacity is opacity * h (raster_math.h).  Never with FILTER_ONLY.
+template <bool FILTER_ONLY, bool AA>
 __global__ void __launch_bounds__(PRE_THREADS)
     preprocess_kernel(int64_t P, int W, int H, float tanfovx, float tanfovy, float scale_modifier,
                       const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix,
@@ -34,34 +35,9 @@ __global__ void __launch_bounds__(PRE_THREADS)
     const float4 q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2],
                                  rotations[4 * i + 3]);
 
-    cgs_pre_fwd_one<FILTER_ONLY>(i, p, s, q, FILTER_ONLY ? 0.f : opacities[i], FILTER_ONLY ? 0.f : colors[3 * i],
-                                 FILTER_ONLY ? 0.f : colors[3 * i + 1], FILTER_ONLY ? 0.f : colors[3 * i + 2], V, Pm, W, H, tanfovx,
-                                 tanfovy, scale_modifier, rec, depth_key, tiles, rect, radii);
-}
-
-// preprocess_kernel<false> with antialiasing (upstream's `antialiasing`): the record's opacity is opacity * h (raster_math.h)
-__global__ void __launch_bounds__(PRE_THREADS)
-    preprocess_aa_kernel(int64_t P, int W, int H, float tanfovx, float tanfovy, float scale_modifier,
-                         const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix,
-                         const float *__restrict__ means3D, const float *__restrict__ colors,
-                         const float *__restrict__ opacities, const float *__restrict__ scales,
-                         const float *__restrict__ rotations, float4 *__restrict__ rec,
-                         uint32_t *__restrict__ depth_key, uint32_t *__restrict__ tiles,
-                         uint2 *__restrict__ rect, int32_t *__restrict__ radii) {
-    const int64_t i = (int64_t)blockIdx.x * PRE_THREADS + threadIdx.x;
-    if (i >= P) return;
-
-    float V[16], Pm[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { V[k] = viewmatrix[k]; Pm[k] = projmatrix[k]; }
-
-    const float3 p = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
-    const float3 s = make_float3(scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]);
-    const float4 q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2],
-                                 rotations[4 * i + 3]);
-
-    cgs_pre_fwd_one<false, true>(i, p, s, q, opacities[i], colors[3 * i], colors[3 * i + 1], colors[3 * i + 2], V, Pm, W, H, tanfovx,
-                                 tanfovy, scale_modifier, rec, depth_key, tiles, rect, radii);
+    cgs_pre_fwd_one<FILTER_ONLY, AA>(i, p, s, q, FILTER_ONLY ? 0.f : opacities[i], FILTER_ONLY ? 0.f : colors[3 * i],
+                                     FILTER_ONLY ? 0.f : colors[3 * i + 1], FILTER_ONLY ? 0.f : colors[3 * i + 2], V, Pm, W, H, tanfovx,
+                                     tanfovy, scale_modifier, rec, depth_key, tiles, rect, radii);
 }
 
 // prefilter_voxel (gaussian_renderer/__init__.py:232-287) in one launch: the reference evaluates get_scaling /
@@ -115,19 +91,15 @@ int cgs_launch_preprocess(const cgs_raster_cfg *cfg, int64_t P, const float *mea
     if (P == 0) return CGS_OK;
     const unsigned nb = (unsigned)((P + PRE_THREADS - 1) / PRE_THREADS);
     CgsProfScope prof(filter_only ? CGS_PROF_FILTER : CGS_PROF_PREPROCESS, stream);
-    if (aa && !filter_only) {
-        hipLaunchKernelGGL(preprocess_aa_kernel, dim3(nb), dim3(PRE_THREADS), 0, stream, P, cfg->image_width, cfg->image_height,
-                           cfg->tanfovx, cfg->tanfovy, cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, means3D, colors,
-                           opacities, scales, rotations, g.rec, g.depth_key, g.tiles, g.rect, radii);
-    } else if (filter_only) {
-        hipLaunchKernelGGL(preprocess_kernel<true>, dim3(nb), dim3(PRE_THREADS), 0, stream, P,
+    if (filter_only) {
+        hipLaunchKernelGGL((preprocess_kernel<true, false>), dim3(nb), dim3(PRE_THREADS), 0, stream, P,
                            cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
                            cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, means3D,
                            (const float *)nullptr, (const float *)nullptr, scales, rotations,
                            (float4 *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint2 *)nullptr, radii);
     } else {
-        hipLaunchKernelGGL(preprocess_kernel<false>, dim3(nb), dim3(PRE_THREADS), 0, stream, P,
-                           cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
+        hipLaunchKernelGGL((aa ? preprocess_kernel<false, true> : preprocess_kernel<false, false>), dim3(nb), dim3(PRE_THREADS), 0,
+                           stream, P, cfg->image_width, cfg->image_height, cfg->tanfovx, cfg->tanfovy,
                            cfg->scale_modifier, cfg->viewmatrix, cfg->projmatrix, means3D, colors, opacities,
                            scales, rotations, g.rec, g.depth_key, g.tiles, g.rect, radii);
     }

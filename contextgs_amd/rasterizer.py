@@ -21,8 +21,9 @@ reference renders with (colors_precomp + scales/rotations,
 gaussian_renderer/__init__.py:197-205) that is cgs_raster_preprocess_launch, for
 the others the kernels of csrc/raster_forms.hip.  Its backward is
 cgs_raster_backward_ex (cgs_raster_backward for the reference's form) when only the
-colour image got a gradient and antialiasing is off, cgs_raster_backward_opt when
-antialiasing is on or one of the maps got a gradient.
+colour image got a gradient and antialiasing is off, cgs_raster_backward_feat without
+features (which is cgs_raster_backward_opt) when antialiasing is on or one of the maps
+got a gradient.
 
 `forward(..., return_aux=True)` returns `(color, radii, {"depth", "invdepth", "alpha"})`, float32 [1,H,W] each, in all
 four forms (csrc/raster_aux.hip); without it the call runs exactly the code above.  For pixel p the
@@ -63,7 +64,7 @@ and every blend (colour and maps) reads opacity * h: a sub-pixel Gaussian is sti
 longer grows with the widening, so a view rendered below the training resolution does not come out too bright and too thick.
 Conic, radii and visible_filter are those of a call without it.  Gradients: opacities get h dL/d(opacity * h), and h's own
 gradient reaches means3D and scales / rotations or cov3D_precomp (not means2D, shs or colors_precomp).  All four argument
-forms, with and without return_aux, pass CGS_RASTER_ANTIALIAS to cgs_raster_preprocess_launch_opt / cgs_raster_backward_opt;
+forms, with and without return_aux, pass CGS_RASTER_ANTIALIAS to cgs_raster_preprocess_launch_opt / cgs_raster_backward_feat;
 with antialiasing=False exactly the code above runs.
 
 The camera is differentiable too (csrc/raster_camera.hip, cgs_raster_camera_backward): when `raster_settings.viewmatrix`,
@@ -393,10 +394,11 @@ class _RasterizeGaussians(torch.autograd.Function):
     is cgs_raster_preprocess_launch_opt (with no option bit and neither shs nor cov3D it is cgs_raster_preprocess_launch), the
     binning and colour blend, then one walk of the final per-tile lists for the maps.  The backward is cgs_raster_backward_ex
     (cgs_raster_backward for colours + scales / rotations) when only the colour image got a gradient and antialiasing is off,
-    cgs_raster_backward_opt otherwise: it runs no colour blend backward when the image got none, and with antialiasing its
-    per-Gaussian kernel turns the blends' dL/d(opacity * h) into dL/d(opacity) and chains h's gradient to the covariance.
-    With `features` [P, C] (the last input; None = none of this runs) one more walk of the lists gives the feature map as the
-    last output (cgs_raster_render_features), and when that map got a gradient the backward is cgs_raster_backward_feat.
+    cgs_raster_backward_feat otherwise (without features it is cgs_raster_backward_opt): it runs no colour blend backward when
+    the image got none, and with antialiasing its per-Gaussian kernel turns the blends' dL/d(opacity * h) into dL/d(opacity) and
+    chains h's gradient to the covariance.  With `features` [P, C] (the last input; None = none of this runs) one more walk of
+    the lists gives the feature map as the last output (cgs_raster_render_features), and when that map got a gradient the same
+    backward call runs the feature blend backward too.
     With `contrib` (a GaussianContrib; None = none of this runs) one more walk accumulates into it and gives the
     top_id / top_weight / count maps as three non-differentiable outputs behind the aux maps (cgs_raster_contrib).
     With `absgrad` the forward is unchanged and the backward is cgs_raster_backward_abs whatever got a gradient: means2D's
@@ -506,20 +508,17 @@ class _RasterizeGaussians(torch.autograd.Function):
                                                  _lib.ptr(scratch), scratch.numel(), stream, ctx.opts,
                                                  _lib.ptr(feat) if with_feat else None, feat.shape[1] if with_feat else 0,
                                                  _lib.ptr(g_fmap), _lib.ptr(d_feat)), "cgs_raster_backward_abs")
-        elif g_fmap is not None:    # the feature map got a gradient: the same call with the feature blend backward in it
+        elif g_fmap is not None or ctx.opts or any(t is not None for t in maps):
+            # maps, antialiasing or a gradient on the feature map (then with the feature blend backward in it): one call,
+            # which without features is cgs_raster_backward_opt's
             cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS
-            d_feat = torch.zeros_like(feat)         # accumulated atomically, like dL/dcolor
+            with_feat = g_fmap is not None
+            d_feat = torch.zeros_like(feat) if with_feat else None          # accumulated atomically, like dL/dcolor
             scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
             _lib.check(L.cgs_raster_backward_feat(*inputs, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), *grads,
-                                                  _lib.ptr(scratch), scratch.numel(), stream, ctx.opts, _lib.ptr(feat),
-                                                  feat.shape[1], _lib.ptr(g_fmap), _lib.ptr(d_feat)),
-                       "cgs_raster_backward_feat")
-        elif ctx.opts or any(t is not None for t in maps):
-            cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS
-            scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
-            _lib.check(L.cgs_raster_backward_opt(*inputs, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), *grads,
-                                                 _lib.ptr(scratch), scratch.numel(), stream, ctx.opts),
-                       "cgs_raster_backward_opt")
+                                                  _lib.ptr(scratch), scratch.numel(), stream, ctx.opts,
+                                                  _lib.ptr(feat) if with_feat else None, feat.shape[1] if with_feat else 0,
+                                                  _lib.ptr(g_fmap), _lib.ptr(d_feat)), "cgs_raster_backward_feat")
         else:       # the colour image alone, no antialiasing (cgs_raster_backward for the form the reference trains with)
             cam_opts = 0
             scratch = _workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)

@@ -197,14 +197,16 @@ def test_one_pixel_has_nothing_to_cancel(oracle32):
 
 
 # ---- 3: forms and options -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("form", ["shs+scales", "shs+cov", "colors+cov"])
-def test_all_forms_match_colors_precomp_scales_rotations(form):
+@pytest.mark.parametrize("form, aa", [pytest.param(f, a, id=f + ("-aa" if a else "")) for a in (False, True)
+                                      for f in ("shs+scales", "shs+cov", "colors+cov")])
+def test_all_forms_match_colors_precomp_scales_rotations(form, aa):
+    """aa: both sides with antialiasing, the ABS and AA instances of the form kernels against those of the plain kernel."""
     from contextgs_amd.rasterizer import GaussianRasterizer
     from test_raster_sh_cov_gpu import _shs, cov6_torch, sh_eval_torch
     P, W, H, D, M = 2000, 128, 96, 2, 9
     cam, g = _scene(P, W, H, P + 3)
     sh = _shs(P, M, seed=P)
-    rs = _settings(cam, D=D)
+    rs = _settings(cam, D=D, aa=aa)
     campos = rs.campos.float()
     w = torch.tensor(np.random.default_rng(5).normal(size=(3, H, W)).astype(np.float32), device="cuda")
 
@@ -233,8 +235,8 @@ def test_all_forms_match_colors_precomp_scales_rotations(form):
     assert float(same.float().mean()) >= 1 - 1e-4
     rows = same.numpy()
     a, b = new["m2"].cpu().numpy()[rows], ref["m2"].cpu().numpy()[rows]
-    _check_grad(a[:, 2:4], b[:, 2:4], f"absolute columns {form}")
-    _check_grad(a[:, 0:2], b[:, 0:2], f"signed columns {form}")
+    _check_grad(a[:, 2:4], b[:, 2:4], f"absolute columns {form}{' aa' if aa else ''}")
+    _check_grad(a[:, 0:2], b[:, 0:2], f"signed columns {form}{' aa' if aa else ''}")
     assert bool((new["m2"][new["radii"] <= 0] == 0).all())
 
 
