@@ -106,6 +106,11 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                                         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
                                        [c_void_p, c_size_t, c_void_p, C.c_uint32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "cgs_raster_bwd_det_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "cgs_raster_backward_det": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
+                                       [c_void_p, c_size_t, c_void_p, C.c_uint32, c_int32, c_void_p, c_size_t]),
     "cgs_raster_contrib": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                    c_size_t, c_void_p, c_int64] + [c_void_p] * 8),
     "cgs_raster_camera_bytes": (c_size_t, [c_int64]),

@@ -928,6 +928,108 @@ extern "C" int cgs_raster_backward_abs(const cgs_raster_cfg *cfg, int64_t P, int
                                     (opts & CGS_RASTER_ANTIALIAS) != 0, features, C, dL_dfeatures_map, dL_dfeatures, true);
 }
 
+// ---- bit-reproducible backward (csrc/raster_blend_rows.hip, the DET instances) ---------------------------------------------
+// det_ws: base [P] (exclusive scan of geom.tiles in id order) | the scan's scratch | the slot array, 48 B per pair
+static const size_t DET_SLOT_BYTES = 48;
+struct DetLayout { size_t scan_off, scan_bytes, slots_off; };
+static DetLayout det_layout(int64_t P) {
+    const size_t n = (size_t)(P > 0 ? P : 1);
+    DetLayout l;
+    l.scan_bytes = cgs_scan_scratch_bytes((int64_t)n);
+    l.scan_off = cgs_align_up(n * sizeof(uint32_t), 256);
+    l.slots_off = l.scan_off + cgs_align_up(l.scan_bytes, 256);
+    return l;
+}
+extern "C" size_t cgs_raster_bwd_det_bytes(int64_t P, int64_t num_rendered, int32_t means2D_cols) {
+    (void)means2D_cols;         // (one slot layout for both widths: columns 9, 10 are the absolute sums)
+    return det_layout(P).slots_off + cgs_align_up((size_t)(num_rendered > 0 ? num_rendered : 1) * DET_SLOT_BYTES, 256);
+}
+
+int cgs_launch_blend_bwd_det(const cgs_raster_cfg *cfg, int64_t P, int64_t R, CgsGeom &g, CgsBin &b, CgsImg &im,
+                             const float *dL_dout, const uint32_t *slot_base, void *slots, float *dL_dmean2D_px, float *dL_dconic,
+                             float *dL_dopacity, float *dL_dcolors, float *dL_dz, float *dL_dabs_px, hipStream_t stream);
+
+// cgs_raster_backward_abs's colour path with every float-atomic sum replaced by the store-and-sum form (include/cgs.h): base =
+// scan of geom.tiles, [zero fill of the slots, DET blend backward,] per-Gaussian sum INTO the scratch layout of
+// cgs_raster_backward_abs, then the unchanged per-Gaussian backward.
+extern "C" int cgs_raster_backward_det(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts,
+                                       int32_t means2D_cols, void *det_ws, size_t det_bytes) {
+    const char *fn = "cgs_raster_backward_det";
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if ((rc = check_opts(fn, opts))) return rc;
+    if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
+    if (means2D_cols != 3 && means2D_cols != 4) {
+        cgs_set_error("%s: means2D_cols = %d, must be 3 or 4", fn, means2D_cols);
+        return CGS_ERR_ARG;
+    }
+    if (dL_ddepth || dL_dinvdepth || dL_dalpha) {
+        cgs_set_error("%s: dL_ddepth, dL_dinvdepth and dL_dalpha must be NULL (the map blends' backward sums with float atomics "
+                      "and is not covered by the deterministic mode)", fn);
+        return CGS_ERR_ARG;
+    }
+    const bool aa = (opts & CGS_RASTER_ANTIALIAS) != 0, absgrad = means2D_cols == 4;
+    CgsRasterForms f;
+    if ((rc = check_forms(fn, cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f))) return rc;
+    if (P == 0) return CGS_OK;
+    if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacities || !scratch || !det_ws ||
+        (shs && !dL_dshs) || (cov3D && !dL_dcov3D) || (!cov3D && (!dL_dscales || !dL_drotations)) || !geom_ws || !img_ws ||
+        (R > 0 && !bin_ws) || (aa && !opacities)) {
+        cgs_set_error("%s: NULL input", fn);
+        return CGS_ERR_ARG;
+    }
+    const size_t scratch_need = cgs_raster_bwd_abs_scratch_bytes(P), det_need = cgs_raster_bwd_det_bytes(P, R, means2D_cols);
+    if (scratch_bytes < scratch_need) {
+        cgs_set_error("%s: scratch too small: %zu < %zu", fn, scratch_bytes, scratch_need);
+        return CGS_ERR_WORKSPACE;
+    }
+    if (det_bytes < det_need) {
+        cgs_set_error("%s: det_ws too small: %zu < %zu", fn, det_bytes, det_need);
+        return CGS_ERR_WORKSPACE;
+    }
+    CgsGeom g;
+    CgsBin b;
+    CgsImg im;
+    memset(&b, 0, sizeof(b));
+    if (!cgs_geom_carve(&g, geom_ws, geom_bytes, P) || !cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width) ||
+        (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R))) {
+        cgs_set_error("%s: workspace too small", fn);
+        return CGS_ERR_WORKSPACE;
+    }
+    float *d_mean_px = (float *)scratch;
+    float *d_conic = (float *)((char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
+    float *d_z = (float *)((char *)scratch + cgs_raster_bwd_scratch_bytes(P));
+    float *d_abs = absgrad ? (float *)((char *)scratch + cgs_raster_bwd_aux_scratch_bytes(P)) : nullptr;
+    const DetLayout dl = det_layout(P);
+    uint32_t *base = (uint32_t *)det_ws;
+    char *scan = (char *)det_ws + dl.scan_off, *slots = (char *)det_ws + dl.slots_off;
+    const size_t scan_bytes = dl.scan_bytes;
+    const bool blend = R > 0 && dL_dout;
+    if (blend) {
+        if ((rc = cgs_scan_exclusive_u32_total(g.tiles, base, P, scan, scan_bytes, nullptr, stream))) return rc;
+        if (cfg->debug) CGS_CHECK_HIP(hipStreamSynchronize(stream));
+    }
+    // (without a blend the sum kernel reads neither base nor a slot: every row is written zero)
+    if ((rc = cgs_launch_blend_bwd_det(cfg, P, R, g, b, im, dL_dout, base, slots, d_mean_px, d_conic, dL_dopacities, dL_dcolors,
+                                       d_z, d_abs, stream)))
+        return rc;
+    const float *aa_op = aa ? opacities : nullptr;
+    float *aa_dop = aa ? dL_dopacities : nullptr;
+    if (!shs && !cov3D)
+        return cgs_launch_preprocess_bwd(cfg, P, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dmeans3D, dL_dmeans2D,
+                                         dL_dscales, dL_drotations, stream, aa_op, aa_dop, d_abs);
+    return cgs_launch_preprocess_bwd_form(cfg, P, f, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dcolors, dL_dmeans3D,
+                                          dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_op, aa_dop, d_abs);
+}
+
 // ---- camera gradients (csrc/raster_camera.hip) ---------------------------------------------------------------------------
 size_t cgs_camera_work_bytes(int64_t P);
 int cgs_launch_camera_bwd(const cgs_raster_cfg *cfg, int64_t P, const CgsRasterForms &f, const float *means3D, const float *opacities,

@@ -147,6 +147,11 @@ int cgs_launch_blend_bwd_rows(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, 
                               float *dL_dmean2D_px, float *dL_dconic, float *dL_dopacity, float *dL_dcolors,
                               hipStream_t stream, float *dL_dabs_px = nullptr);
 int cgs_launch_tile_order(const cgs_raster_cfg *cfg, CgsImg &im, hipStream_t stream);      // raster_blend_rows.hip
+// the DET instances + the per-Gaussian sum of their slots (cgs_raster_backward_det): every row of the five outputs and dL_dz written
+int cgs_launch_blend_bwd_rows_det(const cgs_raster_cfg *cfg, int64_t P, int64_t R, CgsGeom &g, CgsBin &b, CgsImg &im,
+                                  const float *dL_dout, const uint32_t *slot_base, void *slots, float *dL_dmean2D_px,
+                                  float *dL_dconic, float *dL_dopacity, float *dL_dcolors, float *dL_dz, float *dL_dabs_px,
+                                  hipStream_t stream);
 int cgs_launch_blend_fwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im,
                          float *out_color, hipStream_t stream);
 int cgs_launch_blend_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im,

@@ -80,6 +80,15 @@ int cgs_launch_blend_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsIm
     return cgs_launch_blend_bwd_rows(cfg, g, b, im, dL_dout, dL_dmean2D_px, dL_dconic, dL_dopacity, dL_dcolors, stream, dL_dabs_px);
 }
 
+// The store-and-sum blend backward of cgs_raster_backward_det (raster_blend_rows.hip: the DET instances and det_sum_kernel).
+int cgs_launch_blend_bwd_det(const cgs_raster_cfg *cfg, int64_t P, int64_t R, CgsGeom &g, CgsBin &b, CgsImg &im,
+                             const float *dL_dout, const uint32_t *slot_base, void *slots, float *dL_dmean2D_px, float *dL_dconic,
+                             float *dL_dopacity, float *dL_dcolors, float *dL_dz, float *dL_dabs_px, hipStream_t stream) {
+    CgsProfScope prof(CGS_PROF_BLEND_BWD, stream);
+    return cgs_launch_blend_bwd_rows_det(cfg, P, R, g, b, im, dL_dout, slot_base, slots, dL_dmean2D_px, dL_dconic, dL_dopacity,
+                                         dL_dcolors, dL_dz, dL_dabs_px, stream);
+}
+
 // R_eff / non-empty tile statistics for the roofline accounting.
 __global__ void __launch_bounds__(256) raster_stats_kernel(int ntiles, const uint32_t *__restrict__ tile_last,
                                                            unsigned long long *__restrict__ out) {

@@ -264,6 +264,19 @@ __global__ void __launch_bounds__(RB_THREADS)
 // same alphas (AbsGS's densification statistic) into dL_dabs_px [P, 2]: two more values per visit in the free places of the
 // reduction's third group, two more accumulator columns (11 x 256 floats: 24.6 KB of LDS, six workgroups per CU).  The default
 // instance never reads dL_dabs_px.
+//
+// DET: the opt-in instance of cgs_raster_backward_det (blend_bwd_rows_det_kernel below): the same walk and the same per-visit
+// arithmetic, but no sum whose order depends on timing.
+//   Inside the tile: one accumulator plane per WAVE, sacc[wave][entry][k] (4 x 256 x NG floats: 36.9 / 45.1 KB; with the records
+//   and the lists 50.7 / 58.9 KB of LDS, three / two workgroups per CU).  A wave's iterations run in the order of its rows' lists
+//   (a function of the masks, n_contrib and the list alone), and inside an iteration rows 0, 1, 2, 3 add IN TURN with plain LDS
+//   read-add-writes, each behind a wave-scope fence + wave_barrier (two rows often hold the same entry: the next row's read must
+//   see the previous row's write, and the compiler must not merge the four predicated blocks).  No other wave touches the plane.
+//   The flush adds planes 0, 1, 2, 3 in that order.
+//   Across tiles: the flush STORES the entry's converted sums (12 floats: mean x, y | conic a, b, c | opacity | r, g, b | abs x,
+//   y | spare) into slot(g, tile) = base[g] + (ty - y0_g) (x1_g - x0_g) + (tx - x0_g) of `slots`, exactly one writer per slot;
+//   det_sum_kernel adds a Gaussian's slots in an order that depends on tiles[g] alone.  Slots nobody writes (entries behind
+//   tile_last, all-zero sums, occluded Gaussians) keep the zeros of the caller's fill.
 template <bool ABS>
 __global__ void __launch_bounds__(RB_THREADS)
     blend_bwd_rows_kernel(int W, int H, int tiles_x, const uint2 *__restrict__ ranges,
@@ -274,191 +287,93 @@ __global__ void __launch_bounds__(RB_THREADS)
                           float *__restrict__ dL_dconic, float *__restrict__ dL_dopacity,
                           float *__restrict__ dL_dcolors, const uint32_t *__restrict__ tile_order,
                           float *__restrict__ dL_dabs_px) {
-    constexpr int NG = ABS ? RB_NGRAD + 2 : RB_NGRAD;
-    // 22.6 KB of LDS per workgroup = seven workgroups per CU: two float4 per record plus its blue component (the third
-    // float4 only carries cull extents the staging thread has in registers), no copy of the Gaussian ids (the flush reads
-    // gid_sorted again)
-    __shared__ float4 srec[RB_THREADS * 2];
-    __shared__ float sblue[RB_THREADS];
-    __shared__ float sacc[RB_THREADS][NG];
-    __shared__ RbLists S;
+    constexpr bool DET = false;
+    const uint2 *const rect = nullptr;             // (the DET instances' arguments: named in discarded statements only)
+    const uint32_t *const slot_base = nullptr;
+    float4 *const slots = nullptr;
+    const uint64_t slot_cap = 0;
+#include "raster_blend_rows_bwd.h"
+}
 
-    const int tile = (int)tile_order[blockIdx.x];        // longest lists first (tile_order_kernel)
-    const uint32_t tlast = tile_last[tile];
-    if (tlast == 0) return;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const RbLane L = rb_lane(tx, ty, wave, lane);
-    const bool inside = L.px < W && L.py < H;
-    const float pxf = (float)L.px, pyf = (float)L.py;
-    const uint2 range = ranges[tile];
-    const size_t pix = (size_t)L.py * W + L.px, hw = (size_t)H * W;
+// The DET instances (comment above blend_bwd_rows_kernel): nothing is added to global memory, every entry's sums are stored
+// to the slot of its (Gaussian, tile) pair.
+template <bool ABS>
+__global__ void __launch_bounds__(RB_THREADS)
+    blend_bwd_rows_det_kernel(int W, int H, int tiles_x, const uint2 *__restrict__ ranges,
+                              const uint32_t *__restrict__ gid_sorted, const float4 *__restrict__ rec,
+                              const float *__restrict__ bg, const float *__restrict__ final_T,
+                              const uint32_t *__restrict__ n_contrib, const uint32_t *__restrict__ tile_last,
+                              const float *__restrict__ dL_dout, const uint32_t *__restrict__ tile_order,
+                              const uint2 *__restrict__ rect, const uint32_t *__restrict__ slot_base,
+                              float4 *__restrict__ slots, uint64_t slot_cap) {
+    constexpr bool DET = true;
+    float *const dL_dmean2D_px = nullptr, *const dL_dconic = nullptr, *const dL_dopacity = nullptr, *const dL_dcolors = nullptr,
+                 *const dL_dabs_px = nullptr;      // (the default instances' arguments: named in discarded statements only)
+#include "raster_blend_rows_bwd.h"
+}
 
-    const float T_final = inside ? final_T[pix] : 0.f;
-    const uint32_t my_last = inside ? n_contrib[pix] : 0u;
-    uint32_t blk_last = my_last;       // maximum over the 16 lanes (pixels) of the row
-    blk_last = max(blk_last, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)blk_last, 0xB1, 0xF, 0xF, false));
-    blk_last = max(blk_last, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)blk_last, 0x4E, 0xF, 0xF, false));
-    blk_last = max(blk_last, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)blk_last, 0x124, 0xF, 0xF, false));
-    blk_last = max(blk_last, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)blk_last, 0x128, 0xF, 0xF, false));
-    float T = T_final;
-    float gr = 0.f, gg = 0.f, gb = 0.f;
-    if (inside) { gr = dL_dout[pix]; gg = dL_dout[hw + pix]; gb = dL_dout[2 * hw + pix]; }
-    const float bg_dot = bg[0] * gr + bg[1] * gg + bg[2] * gb;
-    const float neg_bg_T = -T_final * bg_dot;
-    float acc_dot = 0.f, last_cdot = 0.f, last_alpha = 0.f;       // scalar colour recurrence (see raster_blend.hip)
-
-    const int nbatch = (int)((tlast + RB_THREADS - 1) / RB_THREADS);
-    // the batch after the one being walked is fetched into registers before the walk starts (see the forward)
-    float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0;
-    uint32_t pg = 0;
-    {
-        const uint32_t pos0 = (uint32_t)(nbatch - 1) * RB_THREADS + tid;
-        if (pos0 < tlast) {
-            pg = gid_sorted[range.x + pos0];
-            p0 = rec[3 * (size_t)pg]; p1 = rec[3 * (size_t)pg + 1]; p2 = rec[3 * (size_t)pg + 2];
+// Per-Gaussian sum of the DET instances' slots: Gaussian g owns slots base[g] .. base[g] + tiles[g] - 1 (its rectangle, row-major)
+// and every output row is WRITTEN (exact zeros for a Gaussian without tiles; dL/dz of the map blends, which this mode does not
+// run, is written zero too so that the camera backward reads a defined scratch).  Order of the additions, a function of tiles[g]
+// alone: up to DS_SMALL slots, one thread adds them in ascending order (the headline view: 1.2 slots per Gaussian); above, the
+// 64 lanes of the Gaussian's wave add slots lane, lane + 64, ... in ascending order each and the 64 partial sums meet in the xor
+// butterfly 32, 16, .., 1 (a + b = b + a bit for bit, so every lane holds the same sum) - a screen-filling Gaussian's thousands
+// of slots are read as contiguous 3 KB lines by the wave.
+#define DS_SMALL 32u
+template <bool ABS>
+__global__ void __launch_bounds__(256)
+    det_sum_kernel(int64_t P, const uint32_t *__restrict__ tiles, const uint32_t *__restrict__ slot_base,
+                   const float4 *__restrict__ slots, uint64_t slot_cap, float *__restrict__ dL_dmean2D_px,
+                   float *__restrict__ dL_dconic, float *__restrict__ dL_dopacity, float *__restrict__ dL_dcolors,
+                   float *__restrict__ dL_dz, float *__restrict__ dL_dabs_px) {
+    constexpr int NV = ABS ? 11 : 9;
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    uint32_t n = 0, b = 0;
+    if (g < P) { n = tiles[g]; b = slot_base[g]; }
+    // (never with the view's own counts and a capacity >= its pair count: no read past the slot array whatever the inputs)
+    if ((uint64_t)b + n > slot_cap) n = (uint64_t)b < slot_cap ? (uint32_t)(slot_cap - b) : 0u;
+    float a[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) a[k] = 0.f;
+    const bool big = n > DS_SMALL;
+    if (!big)
+        for (uint32_t j = 0; j < n; ++j) {
+            const float4 *const s = slots + 3 * ((uint64_t)b + j);
+            const float4 s0 = s[0], s1 = s[1], s2 = s[2];
+            a[0] += s0.x; a[1] += s0.y; a[2] += s0.z; a[3] += s0.w; a[4] += s1.x; a[5] += s1.y; a[6] += s1.z; a[7] += s1.w;
+            a[8] += s2.x;
+            if constexpr (ABS) { a[9] += s2.y; a[10] += s2.z; }
+        }
+    uint64_t todo = rb_ballot(big);
+    while (todo) {
+        const int src = __builtin_ctzll(todo);
+        todo &= todo - 1ull;
+        const uint32_t nn = (uint32_t)__shfl((int)n, src, 64), bb = (uint32_t)__shfl((int)b, src, 64);
+        float p[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) p[k] = 0.f;
+        for (uint32_t j = (uint32_t)lane; j < nn; j += 64u) {
+            const float4 *const s = slots + 3 * ((uint64_t)bb + j);
+            const float4 s0 = s[0], s1 = s[1], s2 = s[2];
+            p[0] += s0.x; p[1] += s0.y; p[2] += s0.z; p[3] += s0.w; p[4] += s1.x; p[5] += s1.y; p[6] += s1.z; p[7] += s1.w;
+            p[8] += s2.x;
+            if constexpr (ABS) { p[9] += s2.y; p[10] += s2.z; }
+        }
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) p[k] += __shfl_xor(p[k], d, 64);
+            a[k] = lane == src ? p[k] : a[k];
         }
     }
-    for (int bi = nbatch - 1; bi >= 0; --bi) {
-        const uint32_t base_pos = (uint32_t)bi * RB_THREADS;
-        const uint32_t pos = base_pos + tid;
-        uint32_t m16 = 0;
-        __syncthreads();   // previous batch fully flushed before LDS is reused
-        if (pos < tlast) {
-            srec[tid * 2] = p0;
-            srec[tid * 2 + 1] = p1;
-            sblue[tid] = p2.x;
-            m16 = rb_block_mask(p0.x, p0.y, p2.y, p2.z, p2.w, tx * CGS_TILE, ty * CGS_TILE);
-        } else {
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            srec[tid * 2] = z; srec[tid * 2 + 1] = z; sblue[tid] = 0.f;
-        }
-        if (bi > 0) {      // every position of an earlier batch is < tlast
-            pg = gid_sorted[range.x + pos - RB_THREADS];
-            p0 = rec[3 * (size_t)pg]; p1 = rec[3 * (size_t)pg + 1]; p2 = rec[3 * (size_t)pg + 2];
-        }
-#pragma unroll
-        for (int k = 0; k < NG; ++k) sacc[tid][k] = 0.f;
-        S.smask[tid] = (uint16_t)m16;
-        __syncthreads();
-
-        {
-            // entries behind the LAST contribution of every pixel of this 4x4 block (n_contrib: where the forward stopped)
-            // cannot contribute to it: they never enter the block's list (the tile-wide bound `tlast` is the maximum over
-            // 256 pixels, a block's own bound over 16)
-            int i = (int)rb_list_build(S, L.blk, lane, (int)blk_last - (int)base_pos - 1) - 1;
-            uint32_t e_next = S.list[L.blk][max(i, 0)];
-            while (rb_ballot(i >= 0) != 0ull) {
-                const bool has = i >= 0;
-                const uint32_t e = e_next;
-                i -= has ? 1 : 0;
-                e_next = S.list[L.blk][max(i, 0)];                   // next entry's index: in flight during this iteration
-                const uint32_t position = base_pos + e + 1u;         // 1-based
-                const float4 r0 = srec[e * 2], r1 = srec[e * 2 + 1];
-                const float blue = sblue[e];
-                const RbEval ev = rb_eval(r0, r1, pxf, pyf);
-                const bool act = has && (position <= my_last) && ev.hit;
-                if (rb_ballot(act) == 0ull) continue;
-                // Branch-free: a lane whose pixel takes no contribution runs the same updates on alpha = 0, G = 0, for which
-                // every one of them is an exact no-op (T / 1 = T, w = 0, the colour recurrence with alpha = 0 hands on
-                // the value the next contributing step would have computed) — two selects instead of a divergent block,
-                // nine zero-initialisations and the moves that merge its results (the kernel is VALU-issue bound).
-                const float alpha = act ? ev.alpha : 0.f, Gm = act ? ev.g : 0.f;
-                const float om = 1.f - alpha;
-                // 1/(1 - alpha), alpha <= 0.99: v_rcp_f32 + one Newton step (3 instructions, <= 1 ulp) for the background
-                // term; T itself by the IEEE division: T is rebuilt over the whole list, and T * rcp (two roundings per
-                // entry) drifted 5-8x further from fp64 than the oracle over 300+ entry lists
-                float inv_om = __builtin_amdgcn_rcpf(om);
-                inv_om = inv_om * fmaf(-om, inv_om, 2.f);
-                T = T / om;
-                const float w = alpha * T;
-                acc_dot = fmaf(last_alpha, last_cdot, (1.f - last_alpha) * acc_dot);
-                last_cdot = fmaf(r1.z, gr, fmaf(r1.w, gg, blue * gb));
-                float dL_dalpha = (last_cdot - acc_dot) * T;
-                last_alpha = alpha;
-                dL_dalpha = fmaf(neg_bg_T, inv_om, dL_dalpha);
-                const float gG = Gm * dL_dalpha;
-                const float gx = gG * ev.dx, gy = gG * ev.dy;
-                float v[RB_NGRAD];
-                v[0] = gx;
-                v[1] = gy;
-                v[2] = gx * ev.dx;
-                v[3] = gx * ev.dy;
-                v[4] = gy * ev.dy;
-                v[5] = gG;
-                v[6] = w * gr;
-                v[7] = w * gg;
-                v[8] = w * gb;
-                // transposing reduction inside each 16-lane row (identical to raster_blend.hip); every row then adds
-                // into the accumulator of ITS OWN Gaussian
-                const bool b0 = lane & 1, b1 = lane & 2;
-                float a4[4], b2[2];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float keep = b0 ? v[2 * q + 1] : v[2 * q], send = b0 ? v[2 * q] : v[2 * q + 1];
-                    a4[q] = keep + rb_dpp<0xB1>(send);
-                }
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const float keep = b1 ? a4[2 * q + 1] : a4[2 * q], send = b1 ? a4[2 * q] : a4[2 * q + 1];
-                    b2[q] = keep + rb_dpp<0x4E>(send);
-                }
-                float c8;
-                if constexpr (ABS) {
-                    // third group of the transposing reduction: v[8], |d/d mean x|, |d/d mean y| and a free place end up
-                    // in lanes 8..11 of the row (A, B, C = r0.z, r0.w, r1.x: the scaled conic of the record)
-                    const float ax = fabsf(fmaf(2.f * r0.z, gx, r0.w * gy)), ay = fabsf(fmaf(2.f * r1.x, gy, r0.w * gx));
-                    const float k0 = b0 ? ax : v[8], s0 = b0 ? v[8] : ax;
-                    const float k1 = b0 ? 0.f : ay, s1 = b0 ? ay : 0.f;
-                    const float t0 = k0 + rb_dpp<0xB1>(s0), t1 = k1 + rb_dpp<0xB1>(s1);
-                    c8 = (b1 ? t1 : t0) + rb_dpp<0x4E>(b1 ? t0 : t1);
-                } else {
-                    c8 = v[8];
-                    c8 += rb_dpp<0xB1>(c8);
-                    c8 += rb_dpp<0x4E>(c8);
-                }
-                b2[0] += rb_dpp<0x124>(b2[0]); b2[0] += rb_dpp<0x128>(b2[0]);
-                b2[1] += rb_dpp<0x124>(b2[1]); b2[1] += rb_dpp<0x128>(b2[1]);
-                c8 += rb_dpp<0x124>(c8); c8 += rb_dpp<0x128>(c8);
-                // keep the last three DPP additions in front of the predicated store: sunk into its exec-masked block
-                // they split into a full-exec v_mov_dpp plus an add each (and a zero for the mov's `old` operand)
-                asm volatile("" : "+v"(b2[0]), "+v"(b2[1]), "+v"(c8));
-                const int sub = lane & 15;
-                const float red = sub < 4 ? b2[0] : (sub < 8 ? b2[1] : c8);
-                // (red != 0: a row whose 16 pixels took nothing from its entry — the wave goes on while ANY row has a contribution —
-                //  would add nine zeros through the LDS float-atomic unit, the kernel's second bound: -6 %, same sums bit for bit;
-                //  profiles/r05_blend_bwd_ablations.txt)
-                if (has && sub < NG && red != 0.f) atomicAdd(&sacc[e][sub], red);
-            }
-        }
-        __syncthreads();
-        if (pos < tlast) {
-            const float a0 = sacc[tid][0], a1 = sacc[tid][1], a2 = sacc[tid][2], a3 = sacc[tid][3],
-                        a4 = sacc[tid][4], a5 = sacc[tid][5], a6 = sacc[tid][6], a7 = sacc[tid][7],
-                        a8 = sacc[tid][8];
-            float a9 = 0.f, a10 = 0.f;       // the two absolute sums (>= 0)
-            if constexpr (ABS) { a9 = sacc[tid][NG - 2]; a10 = sacc[tid][NG - 1]; }
-            if (a0 != 0.f || a1 != 0.f || a2 != 0.f || a3 != 0.f || a4 != 0.f || a5 != 0.f || a6 != 0.f ||
-                a7 != 0.f || a8 != 0.f || a9 != 0.f || a10 != 0.f) {
-                const uint32_t g = gid_sorted[range.x + pos];
-                const float4 q0 = srec[tid * 2], q1 = srec[tid * 2 + 1];
-                const float cC = q1.x, op = q1.y;
-                atomicAdd(&dL_dmean2D_px[2 * (size_t)g], op * fmaf(2.f * q0.z, a0, q0.w * a1) * RB_INV_LOG2E);
-                atomicAdd(&dL_dmean2D_px[2 * (size_t)g + 1], op * fmaf(2.f * cC, a1, q0.w * a0) * RB_INV_LOG2E);
-                atomicAdd(&dL_dconic[3 * (size_t)g], -0.5f * op * a2);
-                atomicAdd(&dL_dconic[3 * (size_t)g + 1], -op * a3);
-                atomicAdd(&dL_dconic[3 * (size_t)g + 2], -0.5f * op * a4);
-                atomicAdd(&dL_dopacity[g], a5);
-                atomicAdd(&dL_dcolors[3 * (size_t)g], a6);
-                atomicAdd(&dL_dcolors[3 * (size_t)g + 1], a7);
-                atomicAdd(&dL_dcolors[3 * (size_t)g + 2], a8);
-                if constexpr (ABS) {
-                    if (a9 != 0.f) atomicAdd(&dL_dabs_px[2 * (size_t)g], op * a9 * RB_INV_LOG2E);
-                    if (a10 != 0.f) atomicAdd(&dL_dabs_px[2 * (size_t)g + 1], op * a10 * RB_INV_LOG2E);
-                }
-            }
-        }
-    }
+    if (g >= P) return;
+    dL_dmean2D_px[2 * g] = a[0]; dL_dmean2D_px[2 * g + 1] = a[1];
+    dL_dconic[3 * g] = a[2]; dL_dconic[3 * g + 1] = a[3]; dL_dconic[3 * g + 2] = a[4];
+    dL_dopacity[g] = a[5];
+    dL_dcolors[3 * g] = a[6]; dL_dcolors[3 * g + 1] = a[7]; dL_dcolors[3 * g + 2] = a[8];
+    dL_dz[g] = 0.f;
+    if constexpr (ABS) { dL_dabs_px[2 * g] = a[9]; dL_dabs_px[2 * g + 1] = a[10]; }
 }
 
 
@@ -586,6 +501,43 @@ int cgs_launch_blend_bwd_rows(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, 
                            cfg->bg, (const float *)im.final_T, (const uint32_t *)im.n_contrib, (const uint32_t *)im.tile_last,
                            dL_dout, dL_dmean2D_px, dL_dconic, dL_dopacity, dL_dcolors, (const uint32_t *)im.tile_order,
                            dL_dabs_px);
+    CGS_CHECK_LAUNCH(stream, cfg->debug);
+    return CGS_OK;
+}
+
+// The blend backward of cgs_raster_backward_det: zero fill of the slot array, the DET instance, the per-Gaussian sum.  slot_base:
+// the exclusive scan of g.tiles in id order (the caller's); slot_cap: slots the array holds (>= the view's pair count); R == 0
+// or no upstream gradient: only the sum kernel runs, over no slots (every row zero).  dL_dabs_px != NULL: the ABS instances.
+int cgs_launch_blend_bwd_rows_det(const cgs_raster_cfg *cfg, int64_t P, int64_t R, CgsGeom &g, CgsBin &b, CgsImg &im,
+                                  const float *dL_dout, const uint32_t *slot_base, void *slots, float *dL_dmean2D_px,
+                                  float *dL_dconic, float *dL_dopacity, float *dL_dcolors, float *dL_dz, float *dL_dabs_px,
+                                  hipStream_t stream) {
+    const int tx = cgs_tiles_x(cfg), ty = cgs_tiles_y(cfg);
+    const bool blend = R > 0 && dL_dout;
+    const uint64_t cap = blend ? (uint64_t)R : 0ull;
+    if (blend) {
+        CGS_CHECK_HIP(hipMemsetAsync(slots, 0, (size_t)R * 48u, stream));
+        if (dL_dabs_px)
+            hipLaunchKernelGGL(blend_bwd_rows_det_kernel<true>, dim3((unsigned)(tx * ty)), dim3(RB_THREADS), 0, stream,
+                               cfg->image_width, cfg->image_height, tx, (const uint2 *)im.ranges, (const uint32_t *)b.gid_sorted,
+                               (const float4 *)g.rec, cfg->bg, (const float *)im.final_T, (const uint32_t *)im.n_contrib,
+                               (const uint32_t *)im.tile_last, dL_dout, (const uint32_t *)im.tile_order, (const uint2 *)g.rect,
+                               slot_base, (float4 *)slots, cap);
+        else
+            hipLaunchKernelGGL(blend_bwd_rows_det_kernel<false>, dim3((unsigned)(tx * ty)), dim3(RB_THREADS), 0, stream,
+                               cfg->image_width, cfg->image_height, tx, (const uint2 *)im.ranges, (const uint32_t *)b.gid_sorted,
+                               (const float4 *)g.rec, cfg->bg, (const float *)im.final_T, (const uint32_t *)im.n_contrib,
+                               (const uint32_t *)im.tile_last, dL_dout, (const uint32_t *)im.tile_order, (const uint2 *)g.rect,
+                               slot_base, (float4 *)slots, cap);
+        CGS_CHECK_LAUNCH(stream, cfg->debug);
+    }
+    const dim3 grid((unsigned)((P + 255) / 256));
+    if (dL_dabs_px)
+        hipLaunchKernelGGL(det_sum_kernel<true>, grid, dim3(256), 0, stream, P, (const uint32_t *)g.tiles, slot_base,
+                           (const float4 *)slots, cap, dL_dmean2D_px, dL_dconic, dL_dopacity, dL_dcolors, dL_dz, dL_dabs_px);
+    else
+        hipLaunchKernelGGL(det_sum_kernel<false>, grid, dim3(256), 0, stream, P, (const uint32_t *)g.tiles, slot_base,
+                           (const float4 *)slots, cap, dL_dmean2D_px, dL_dconic, dL_dopacity, dL_dcolors, dL_dz, dL_dabs_px);
     CGS_CHECK_LAUNCH(stream, cfg->debug);
     return CGS_OK;
 }

@@ -127,6 +127,22 @@ the backward is then cgs_raster_backward_abs in every form, with return_aux, fea
 gradients as before.  Summed with float atomics like the signed gradient: not bit-reproducible.  A [P,4] means2D without the
 keyword, or the keyword with any other shape, raises ValueError before a device is touched; without the flag the call enqueues
 exactly what it did before.  densify.training_statis accumulates ||grad[:, 2:4]|| when it is handed a [P,4] gradient.
+
+`forward(..., deterministic=True)` makes the backward bit-reproducible.  The forward already is (no atomics in the blend, a
+stable depth sort, binnings that leave the same lists); the default backward sums every Gaussian's partial gradients with float
+atomics, in LDS inside a tile and in global memory across tiles, in the order of arrival.  With the flag the backward is
+cgs_raster_backward_det (include/cgs.h has the contract and the slot formula): inside a tile every wave sums into a plane of its
+own in a fixed order, every (Gaussian, tile) pair stores its sums to a slot of its own, and a per-Gaussian kernel adds a
+Gaussian's slots in an order that depends on its tile count only.  Every gradient the node returns (means3D, means2D with 3 or
+4 columns, shs / colors_precomp, opacities, scales / rotations or cov3D_precomp, the three camera tensors) is then bit-identical
+from call to call for the same input bits, library build and device model, whichever binning ran, with or without pair-count
+speculation, whatever else the device does; the values are the default backward's up to the order of the sums.  All four
+argument forms, antialiasing, absgrad and camera gradients are covered; the forward is untouched.  NOT covered, and refused with
+ValueError before a device is touched: return_aux, features and contrib (the map and feature blends' backward and
+GaussianContrib.weight are separate kernels that sum with float atomics).  `deterministic=None` (the default) reads the
+environment variable CGS_RASTER_DETERMINISTIC (1 = on), so that a training script that never heard of the keyword can be
+switched; without the flag the call enqueues exactly what it did before.  The mode costs a workspace of 48 bytes per
+(Gaussian, tile) pair and time (DESIGN.md sections 4 and 7 have the numbers).
 """
 from __future__ import annotations
 
@@ -325,6 +341,22 @@ def check_absgrad(means2D, absgrad, P) -> None:
         raise ValueError(f"means2D is {shape}: four columns are the layout of absgrad=True, which was not given")
 
 
+def check_deterministic(deterministic, return_aux=False, features=None, contrib=None) -> bool:
+    """The resolved `deterministic` flag (None: the environment variable CGS_RASTER_DETERMINISTIC, 1 = on).  With the flag on,
+    the keywords whose backward or accumulation still sums with float atomics are refused; no device is touched.  With the flag
+    off nothing is checked."""
+    if deterministic is None:
+        deterministic = os.environ.get("CGS_RASTER_DETERMINISTIC", "0") == "1"
+    if not deterministic:
+        return False
+    for name, given in (("return_aux", bool(return_aux)), ("features", features is not None),
+                        ("contrib", contrib is not None and contrib is not False)):
+        if given:
+            raise ValueError(f"deterministic=True does not cover {name}: the depth / alpha map blends, the feature blend and "
+                             f"GaussianContrib.weight sum with float atomics (not covered: return_aux, features, contrib)")
+    return True
+
+
 class GaussianContrib:
     """Per-Gaussian (or per-slot) contribution statistics accumulated over views: `weight`, `max_weight` float32 [n], `pixels`,
     `top_pixels` int64 [n] (module docstring), and `views`, the number of calls accumulated since the last reset."""
@@ -402,11 +434,14 @@ class _RasterizeGaussians(torch.autograd.Function):
     With `contrib` (a GaussianContrib; None = none of this runs) one more walk accumulates into it and gives the
     top_id / top_weight / count maps as three non-differentiable outputs behind the aux maps (cgs_raster_contrib).
     With `absgrad` the forward is unchanged and the backward is cgs_raster_backward_abs whatever got a gradient: means2D's
-    gradient is [P,4], the signed columns and the absolute sums of the colour image's per-pixel terms (module docstring)."""
+    gradient is [P,4], the signed columns and the absolute sums of the colour image's per-pixel terms (module docstring).
+    With `deterministic` (never together with aux, features or contrib) the forward is unchanged and the backward is
+    cgs_raster_backward_det: no float atomics, bit-reproducible gradients (module docstring)."""
 
     @staticmethod
     def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings,
-                viewmatrix, projmatrix, campos, features=None, contrib=None, contrib_slots=None, absgrad=False):
+                viewmatrix, projmatrix, campos, features=None, contrib=None, contrib_slots=None, absgrad=False,
+                deterministic=False):
         # viewmatrix / projmatrix / campos: the settings' three camera tensors once more, as inputs of the node so that autograd
         # can hand them a gradient; the forward reads them through _Cfg as before
         L = _lib.lib()
@@ -465,6 +500,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             outs += (fmap,)
         ctx.cfg, ctx.num_rendered, ctx.D, ctx.M, ctx.opts, ctx.aux = cfg, bin_R, D, M, opts, bool(aux)
         ctx.absgrad = bool(absgrad)
+        ctx.deterministic = bool(deterministic)
         ctx.save_for_backward(means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat)
         ctx.mark_non_differentiable(*nondiff)      # ONE call: torch keeps only the last call's arguments
         return outs
@@ -480,10 +516,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         dev = means3D.device
         g, *maps = (None if t is None else _f32c(t) for t in (grad_color, *grad_maps, None, None, None)[:4])
         if g is None and g_fmap is None and all(t is None for t in maps):
-            return (None,) * 17
+            return (None,) * 18
         # the blends accumulate dL/dcolor (read by the SH backward) and dL/dopacity atomically: one zero fill for both; the
-        # other arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones)
-        acc = torch.zeros(P * 4, dtype=torch.float32, device=dev)
+        # other arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones).  The deterministic
+        # backward writes every row of both itself.
+        acc = (torch.empty if ctx.deterministic else torch.zeros)(P * 4, dtype=torch.float32, device=dev)
         d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
         m2 = 4 if ctx.absgrad else 3        # columns of dL/dmeans2D
         rest = torch.empty(P * (3 + m2 + (7 if cov is None else 6)), dtype=torch.float32, device=dev)
@@ -499,7 +536,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                  _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov))
         stream = _lib.current_stream()
         d_feat = None
-        if ctx.absgrad:             # one entry point for every combination: NULL for what got no gradient
+        if ctx.deterministic:       # the colour image alone (the forward refused everything else), every form and option
+            cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS        # (the scratch is cgs_raster_backward_abs's, dL/dz written zero)
+            scratch = _workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
+            det_ws = _workspace(L.cgs_raster_bwd_det_bytes(P, ctx.num_rendered, m2), dev)
+            _lib.check(L.cgs_raster_backward_det(*inputs, None, None, None, *grads, _lib.ptr(scratch), scratch.numel(), stream,
+                                                 ctx.opts, m2, _lib.ptr(det_ws), det_ws.numel()), "cgs_raster_backward_det")
+        elif ctx.absgrad:           # one entry point for every combination: NULL for what got no gradient
             cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS        # (its scratch begins with cgs_raster_backward_opt's)
             d_feat = torch.zeros_like(feat) if g_fmap is not None else None
             scratch = _workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
@@ -543,7 +586,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         if g is None:       # the maps and the features send no gradient to the colour inputs
             d_shs = d_colors = None
         return (None, d_means3D, d_means2D, d_shs, d_colors if colors is not None else None, d_opac, d_scales, d_rots,
-                d_cov, None, d_view, d_proj, d_campos, d_feat, None, None, None)
+                d_cov, None, d_view, d_proj, d_campos, d_feat, None, None, None, None)
 
 
 def _camera_inputs(rs):
@@ -598,11 +641,15 @@ class GaussianRasterizer(nn.Module):
         return radii
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, features=None, return_aux=False, contrib=None, contrib_slots=None, absgrad=False):
+                cov3D_precomp=None, features=None, return_aux=False, contrib=None, contrib_slots=None, absgrad=False,
+                deterministic=None):
         """(color [3,H,W], radii int32 [P]); with return_aux=True, features [P,C] and / or contrib a third value, the dict of
         {"depth", "invdepth", "alpha"}, float32 [1,H,W] each, {"features"}, float32 [C,H,W], and / or {"contrib", "top_id",
         "top_weight", "count"} (see the module docstring).  absgrad=True: means2D is [P,4] and its gradient's columns 2:4 are
-        the sums over the pixels of the absolute per-pixel gradients of the colour image (module docstring)."""
+        the sums over the pixels of the absolute per-pixel gradients of the colour image (module docstring).
+        deterministic=True (None: CGS_RASTER_DETERMINISTIC=1): a bit-reproducible backward without float atomics; not with
+        return_aux, features or contrib (module docstring)."""
+        deterministic = check_deterministic(deterministic, return_aux, features, contrib)
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
         check_absgrad(means2D, absgrad, means3D.shape[0])
         check_features(features, means3D.shape[0])
@@ -613,7 +660,8 @@ class GaussianRasterizer(nn.Module):
             contrib = GaussianContrib.zeros(means3D.shape[0], means3D.device)
         out = _RasterizeGaussians.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                         cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings), features,
-                                        contrib, contrib_slots, *((True,) if absgrad else ()))
+                                        contrib, contrib_slots,
+                                        *((bool(absgrad), True) if deterministic else (True,) if absgrad else ()))
         if not return_aux and features is None and contrib is None:
             return out
         extras = {}

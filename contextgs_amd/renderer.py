@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from . import _lib, anchor_gen, mlp
 from .context_model import LazyRows, begin_step, gather_unique, multi_scale_generating, multi_scale_generating_visible
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, check_deterministic
 
 Q_FEAT, Q_SCALING, Q_OFFSETS = 1, 0.001, 0.2      # :40-42
 
@@ -196,9 +196,10 @@ class ViewFusion:
     """What render() hands to generate_neural_gaussians when the expansion may run fused with the rasterizer: the view's
     raster settings in, the rendered view out (`done`: (image, radii, screenspace_points))."""
 
-    def __init__(self, raster_settings, retain_grad, absgrad=False):
+    def __init__(self, raster_settings, retain_grad, absgrad=False, deterministic=False):
         self.raster_settings, self.retain_grad, self.done = raster_settings, retain_grad, None
         self.absgrad = bool(absgrad)       # screenspace_points is [P,4] and the backward is cgs_raster_backward_abs
+        self.deterministic = bool(deterministic)       # the rasterizer's backward is cgs_raster_backward_det (3 or 4 columns)
 
 
 class _ExpandRasterize(torch.autograd.Function):
@@ -209,11 +210,13 @@ class _ExpandRasterize(torch.autograd.Function):
     Same device functions on the same values as the two nodes: bit-identical image, radii and scaling
     (tests/test_fused_view_gpu.py).  means2D: the view's screenspace_points (its gradient is the only thing it
     carries), created by the caller once the survivor count P is known.  absgrad: means2D is [P,4] and the rasterizer's
-    backward launch is cgs_raster_backward_abs with the same arguments (rasterizer.py: the absolute sums in columns 2:4)."""
+    backward launch is cgs_raster_backward_abs with the same arguments (rasterizer.py: the absolute sums in columns 2:4).
+    deterministic: the rasterizer's backward launch is cgs_raster_backward_det with the plain form's arguments (rasterizer.py:
+    no float atomics; same records and same lists as the unfused node, so the same bits)."""
 
     @staticmethod
     def forward(ctx, anchor, gscaling, offsets, masks, op_raw, color_in, cov_in, means2D, K, src_row, pre, raster_settings,
-                absgrad=False):
+                absgrad=False, deterministic=False):
         from . import rasterizer as rz
         L = _lib.lib()
         _lib.require_device(anchor, gscaling, offsets, masks, op_raw, color_in, cov_in)
@@ -227,6 +230,7 @@ class _ExpandRasterize(torch.autograd.Function):
         P = pre.wait()
         assert means2D.shape[0] == P and means2D.shape[1] == (4 if absgrad else 3)
         ctx.absgrad = bool(absgrad)
+        ctx.deterministic = bool(deterministic)
         neural_opacity, mask_out, flags, pos = pre.neural_opacity, pre.mask_out, pre.flags, pre.pos
         cfg = rz._Cfg(raster_settings)
         H, W = cfg.c.image_height, cfg.c.image_width
@@ -257,13 +261,25 @@ class _ExpandRasterize(torch.autograd.Function):
         dev = gscaling.device
         stream = _lib.current_stream()
         # ---- the rasterizer's backward (as _RasterizeGaussians.backward) into buffers that stay inside this node
-        acc = torch.zeros(max(P, 1) * 4, dtype=torch.float32, device=dev)      # atomically accumulated: dL/d colour | opacity
+        use_det = g_img is not None and P > 0 and ctx.deterministic
+        # atomically accumulated: dL/d colour | opacity (the deterministic backward writes every row of both itself)
+        acc = (torch.empty if use_det else torch.zeros)(max(P, 1) * 4, dtype=torch.float32, device=dev)
         d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:4 * P].view(P, 1)
         m2 = 4 if ctx.absgrad else 3        # columns of dL/dmeans2D
         rest = torch.empty(max(P, 1) * (10 + m2), dtype=torch.float32, device=dev)
         d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:(3 + m2) * P].view(P, m2)
         d_scales, d_rots = rest[(3 + m2) * P:(6 + m2) * P].view(P, 3), rest[(6 + m2) * P:(10 + m2) * P].view(P, 4)
-        if g_img is not None and P > 0 and ctx.absgrad:
+        if use_det:         # the plain form's arguments, as the absgrad branch below
+            scratch = rz._workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
+            det_ws = rz._workspace(L.cgs_raster_bwd_det_bytes(P, ctx.num_rendered, m2), dev)
+            _lib.check(L.cgs_raster_backward_det(
+                cfg.ref, P, ctx.num_rendered, _lib.ptr(xyz), _lib.ptr(d_colors), None, 0, 0, None, _lib.ptr(scaling),
+                _lib.ptr(rot), None, _lib.ptr(radii), _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
+                binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(), _lib.ptr(rz._f32c(g_img)), None, None,
+                None, _lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), None, _lib.ptr(d_scales),
+                _lib.ptr(d_rots), None, _lib.ptr(scratch), scratch.numel(), stream, 0, m2, _lib.ptr(det_ws), det_ws.numel()),
+                "cgs_raster_backward_det")
+        elif g_img is not None and P > 0 and ctx.absgrad:
             # the plain form's arguments; the colours never existed as a tensor and the backward of this form does not read
             # them (the pointer only says "colours, not SH": include/cgs.h), so the gradient buffer stands in
             scratch = rz._workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
@@ -307,7 +323,7 @@ class _ExpandRasterize(torch.autograd.Function):
             _lib.ptr(cov_in), _lib.ptr(d_means3D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_scales), _lib.ptr(d_rots),
             _lib.ptr(g_no), _lib.ptr(d_anchor), _lib.ptr(d_gs), _lib.ptr(d_off), _lib.ptr(d_op), _lib.ptr(d_mask),
             _lib.ptr(d_color), _lib.ptr(d_cov), _lib.ptr(src_row), stream), "cgs_expand_backward")
-        return d_anchor, d_gs, d_off, d_mask, d_op, d_color, d_cov, d_means2D, None, None, None, None, None
+        return d_anchor, d_gs, d_off, d_mask, d_op, d_color, d_cov, d_means2D, None, None, None, None, None, None
 
 
 def _anchor_mlps(pc, x):
@@ -400,7 +416,7 @@ def _generate_unfused(viewpoint_camera, pc, anchor, feat, grid_scaling, grid_off
                 pass
         image, radii, scaling, neural_opacity, mask = _ExpandRasterize.apply(
             anchor, grid_scaling, grid_offsets, masks2, op_raw, color_in, cov_in, screenspace_points, K, src_row, pre,
-            view.raster_settings, *((True,) if view.absgrad else ()))
+            view.raster_settings, *((view.absgrad, True) if view.deterministic else (True,) if view.absgrad else ()))
         view.done = (image, radii, screenspace_points)
         return None, None, None, scaling, None, neural_opacity, mask
     return _ExpandGaussians.apply(anchor, grid_scaling, grid_offsets, masks2, op_raw, color_in, cov_in, K, src_row, pre)
@@ -612,7 +628,7 @@ class _DetachedCamera:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False,
-           step=0, *, return_aux=False, anchor_features=None, contrib=None, absgrad=False):            # :155-229
+           step=0, *, return_aux=False, anchor_features=None, contrib=None, absgrad=False, deterministic=None):   # :155-229
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
 
     return_aux=True: the dict also holds the rasterizer's "depth", "invdepth" and "alpha" maps ([1,H,W] each, see
@@ -637,11 +653,19 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     calls stay on the fused expand + raster node; every other path hands the keyword to the rasterizer.
     densify.training_statis (GaussianModel.training_statis) accumulates ||grad[:, 2:4]|| when the gradient has four columns.
 
+    deterministic=True (None, the default: the environment variable CGS_RASTER_DETERMINISTIC=1): the rasterizer's backward runs
+    without float atomics and its gradients are bit-reproducible (contextgs_amd/rasterizer.py has the contract).  Training-mode
+    calls stay on the fused expand + raster node, whose backward launch is then cgs_raster_backward_det; every other path hands
+    the keyword to the rasterizer; fused and unfused give the same bits.  Not covered, ValueError before a device is touched:
+    return_aux, anchor_features, contrib.  The rasterizer's gradients only: other launches of a training step still sum with
+    float atomics (DESIGN.md section 8 lists them).
+
     A camera whose `world_view_transform`, `full_proj_transform` or `camera_center` requires a gradient (a trainable pose,
     contextgs_amd/camera_pose.py) takes the unfused path too, in training and in eval mode, and the gradient reaches the three
     tensors through the rasterizer (rasterizer.py: the projection, the covariance chain, the depth of the maps).  Not
     differentiated with respect to the camera: the anchor MLPs' input (anchor - camera_center), which is evaluated on the
     detached position, and the fused expand + raster node, which such a call never takes."""
+    deterministic = check_deterministic(deterministic, return_aux, anchor_features, contrib)
     is_training = pc.get_color_mlp.training
     view = None
     cam_grad = torch.is_grad_enabled() and any(
@@ -669,7 +693,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     if is_training:
         # the expansion may run fused with the rasterizer's per-Gaussian stages (then `view.done` holds the rendered view
         # and xyz / color / opacity / rot are None: they never existed as tensors)
-        view = ViewFusion(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier), retain_grad, absgrad)
+        view = ViewFusion(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier), retain_grad, absgrad,
+                          deterministic)
         (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, bit_per_anchor_param,
          bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level) = \
             generate_neural_gaussians(gen_camera, pc, visible_mask, is_training=True, step=step,
@@ -696,6 +721,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
 
     rasterizer = GaussianRasterizer(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier))
     abs_kw = dict(absgrad=True) if absgrad else {}
+    abs_kw.update(deterministic=deterministic)      # (resolved above: the rasterizer does not read the environment again)
     if return_aux or rows is not None or slots is not None:
         features = anchor_features.index_select(0, rows[0]) if rows is not None else None      # plumbing: plain torch
         more = dict(contrib=contrib, contrib_slots=slots[0]) if slots is not None else {}

@@ -366,7 +366,8 @@ int cgs_raster_backward_feat(const cgs_raster_cfg *cfg, int64_t P,
  * stop at n_contrib; with CGS_RASTER_ANTIALIAS the same opacity * h.  The colour image's share ONLY: gradients that arrive
  * through the depth / inverse-depth / alpha maps or the feature map flow into the signed columns as before and are not part of
  * the absolute ones (their blends are separate kernels, and |a| + |b| per blend is not a quantity anyone densifies on).
- * Without dL_dout the absolute columns are zero.  Summed with float atomics, like the signed gradient: not bit-reproducible.
+ * Without dL_dout the absolute columns are zero.  Summed with float atomics, like the signed gradient: not bit-reproducible
+ * (cgs_raster_backward_det below is).
  *
  * cgs_raster_backward_abs: the argument list, the checks and the results of cgs_raster_backward_feat (features, the three map
  * gradients and dL_dout may each be NULL; opts as there), except that dL_dmeans2D is [P, 4]: (gnx, gny, abs_x, abs_y), every
@@ -394,6 +395,56 @@ int cgs_raster_backward_abs(const cgs_raster_cfg *cfg, int64_t P,
                             size_t scratch_bytes, void *stream, uint32_t opts,
                             const float *features, int32_t C,
                             const float *dL_dfeatures_map, float *dL_dfeatures);
+
+/* ---- bit-reproducible backward (csrc/raster_blend_rows.hip, the DET instances + det_sum_kernel) ----
+ * Every backward above sums each Gaussian's partial gradients with float atomics, in LDS inside a tile and in global memory
+ * across the tiles it touches: the order is the order of arrival and two backwards of one view differ in the last bits.
+ * cgs_raster_backward_det computes the colour image's backward without a float atomic.
+ *
+ * Contract: given the same input bits, the same library build and the same device model, every gradient it returns (means3D,
+ * means2D with 3 or 4 columns, colours or SH, opacities, scales / rotations or cov3D, and through cgs_raster_camera_backward
+ * behind it the three camera tensors) is bit-identical from call to call, whichever binning ran, whether num_rendered is the
+ * view's pair count or a larger speculative capacity, whatever the workgroup -> tile order, whatever else runs on the device
+ * and whatever the workspaces held before.  No summation order depends on timing; every sum's order is a function of the
+ * view's lists and rectangles alone.  Values: those of cgs_raster_backward_abs up to the order of the sums.
+ *
+ * How: a Gaussian's pairs are exactly the tiles of its rectangle (x0, y0) .. (x1, y1) (exclusive), row-major, so pair
+ * (g, tile (tx, ty)) owns slot
+ *   slot(g, tx, ty) = base[g] + (ty - y0_g) (x1_g - x0_g) + (tx - x0_g),   base = exclusive scan of tiles[] in id order
+ * (a Gaussian's slots are contiguous, the total is the pair count).  Inside a tile each wave sums into an LDS plane of its own,
+ * its four rows in turn, and the planes are added in wave order; the tile then STORES its twelve floats (9 sums, the two
+ * absolute sums, one spare) to its slot with plain vector stores; a per-Gaussian kernel adds the tiles[g] slots of Gaussian g
+ * in an order that depends on tiles[g] only and WRITES every row of the scratch of cgs_raster_backward_abs, dL_dcolors and
+ * dL_dopacities (exact zeros for culled Gaussians), behind which the per-Gaussian backward runs unchanged.
+ *
+ * cgs_raster_backward_det: the arguments of cgs_raster_backward_abs up to and including `opts` (no features), then
+ * means2D_cols (3: dL_dmeans2D is [P, 3]; 4: [P, 4] with the absolute sums as there), det_ws and its size.  dL_ddepth,
+ * dL_dinvdepth and dL_dalpha must be NULL (the map blends and the feature blend are not covered: CGS_ERR_ARG before anything is
+ * enqueued).  scratch: cgs_raster_bwd_abs_scratch_bytes(P) bytes, in that layout for either width (dL/dz is written zero), so
+ * cgs_raster_camera_backward (CGS_RASTER_CAMERA_MAPS) runs behind it.  dL_dcolors and dL_dopacities are OVERWRITTEN: the caller
+ * need not zero them, and nothing the call reads may be uninitialised but what the render left.  det_ws:
+ * cgs_raster_bwd_det_bytes(P, num_rendered, means2D_cols) bytes = base (4 B x P), the scan's scratch and the slot array (48 B x
+ * num_rendered, zero-filled by the call); num_rendered may be the speculative capacity the binning workspace was carved with.
+ * A short scratch or det_ws: CGS_ERR_WORKSPACE.  P == 0: CGS_OK, nothing enqueued.  num_rendered == 0, an empty view or
+ * dL_dout == NULL: every row zero.  cfg->debug synchronises and checks after each kernel. */
+size_t cgs_raster_bwd_det_bytes(int64_t P, int64_t num_rendered, int32_t means2D_cols);
+int cgs_raster_backward_det(const cgs_raster_cfg *cfg, int64_t P,
+                            int64_t num_rendered, const float *means3D,
+                            const float *colors, const float *shs,
+                            int32_t sh_degree, int32_t sh_coeffs,
+                            const float *opacities, const float *scales,
+                            const float *rotations, const float *cov3D,
+                            const int32_t *radii, void *geom_ws, size_t geom_bytes,
+                            void *bin_ws, size_t bin_bytes, void *img_ws,
+                            size_t img_bytes, const float *dL_dout,
+                            const float *dL_ddepth, const float *dL_dinvdepth,
+                            const float *dL_dalpha, float *dL_dmeans3D,
+                            float *dL_dmeans2D, float *dL_dcolors,
+                            float *dL_dopacities, float *dL_dshs,
+                            float *dL_dscales, float *dL_drotations,
+                            float *dL_dcov3D, void *scratch,
+                            size_t scratch_bytes, void *stream, uint32_t opts,
+                            int32_t means2D_cols, void *det_ws, size_t det_bytes);
 
 /* ---- per-Gaussian contribution statistics and top-contributor maps (csrc/raster_contrib.hip) ----
  * The reverse direction of the maps above: how much each Gaussian mattered to the view (importance pruning, covisibility,
