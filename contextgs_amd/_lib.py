@@ -59,6 +59,18 @@ class AdamTensor(C.Structure):
     ]
 
 
+# The seven cgs_raster_backward* signatures (include/cgs.h), from their common pieces: cfg, P, R | the inputs | the three
+# workspaces, pointer and bytes each | dL_dout [| the three map gradients] | the output gradients | scratch, its bytes, the stream
+# [| opts [| features, C, dL_dfeatures_map, dL_dfeatures] or [| means2D_cols, det_ws, det_bytes]]
+_BWD_HEAD = [C.POINTER(RasterCfg), c_int64, c_int64]
+_BWD_WS = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+_BWD_TAIL = [c_void_p, c_size_t, c_void_p]
+# means3D, colors, shs, sh_degree, sh_coeffs, opacities, scales, rotations, cov3D, radii, the workspaces, dL_dout
+_BWD_FORMS = _BWD_HEAD + [c_void_p] * 3 + [c_int32] * 2 + [c_void_p] * 5 + _BWD_WS + [c_void_p]
+_BWD_MAPS = _BWD_FORMS + [c_void_p] * 3
+_BWD_OUT = [c_void_p] * 8 + _BWD_TAIL       # dL_dmeans3D, _means2D, _colors, _opacities, _shs, _scales, _rotations, _cov3D
+_BWD_FEAT = [c_void_p, c_int32, c_void_p, c_void_p]
+
 # name -> (restype, argtypes); the authoritative list of exported symbols.
 # tests/test_abi.py checks it against include/cgs.h.
 SIGNATURES = {
@@ -77,40 +89,22 @@ SIGNATURES = {
     "cgs_raster_preprocess_launch_ex": (c_int, [C.POINTER(RasterCfg), c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                                 C.POINTER(C.c_uint64)]),
-    "cgs_raster_backward_ex": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                       c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cgs_raster_backward_ex": (c_int, _BWD_FORMS + _BWD_OUT),
     "cgs_raster_render_aux": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_size_t,
                                       c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "cgs_raster_backward_aux": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
-                                       [c_void_p, c_size_t, c_void_p]),
+    "cgs_raster_backward_aux": (c_int, _BWD_MAPS + _BWD_OUT),
     "cgs_raster_bwd_aux_scratch_bytes": (c_size_t, [c_int64]),
     "cgs_raster_preprocess_launch_opt": (c_int, [C.POINTER(RasterCfg), c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                                  C.POINTER(C.c_uint64), C.c_uint32]),
-    "cgs_raster_backward_opt": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
-                                       [c_void_p, c_size_t, c_void_p, C.c_uint32]),
+    "cgs_raster_backward_opt": (c_int, _BWD_MAPS + _BWD_OUT + [C.c_uint32]),
     "cgs_raster_render_features": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_size_t,
                                            c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p]),
-    "cgs_raster_backward_feat": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
-                                        [c_void_p, c_size_t, c_void_p, C.c_uint32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "cgs_raster_backward_feat": (c_int, _BWD_MAPS + _BWD_OUT + [C.c_uint32] + _BWD_FEAT),
     "cgs_raster_bwd_abs_scratch_bytes": (c_size_t, [c_int64]),
-    "cgs_raster_backward_abs": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
-                                       [c_void_p, c_size_t, c_void_p, C.c_uint32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "cgs_raster_backward_abs": (c_int, _BWD_MAPS + _BWD_OUT + [C.c_uint32] + _BWD_FEAT),
     "cgs_raster_bwd_det_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
-    "cgs_raster_backward_det": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
-                                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p] + [c_void_p] * 8 +
-                                       [c_void_p, c_size_t, c_void_p, C.c_uint32, c_int32, c_void_p, c_size_t]),
+    "cgs_raster_backward_det": (c_int, _BWD_MAPS + _BWD_OUT + [C.c_uint32, c_int32, c_void_p, c_size_t]),
     "cgs_raster_contrib": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                    c_size_t, c_void_p, c_int64] + [c_void_p] * 8),
     "cgs_raster_camera_bytes": (c_size_t, [c_int64]),
@@ -127,10 +121,7 @@ SIGNATURES = {
                                        c_void_p, c_size_t, c_void_p, c_void_p]),
     "cgs_raster_render": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_size_t,
                                   c_void_p, c_size_t, c_void_p, c_void_p]),
-    "cgs_raster_backward": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_size_t, c_void_p]),
+    "cgs_raster_backward": (c_int, _BWD_HEAD + [c_void_p] * 6 + _BWD_WS + [c_void_p] * 7 + _BWD_TAIL),
     "cgs_raster_preprocess_expand_launch": (c_int, [C.POINTER(RasterCfg), c_int64, c_int] + [c_void_p] * 9 + [c_int64, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, C.POINTER(C.c_uint64)]),
     "cgs_raster_stats": (c_int, [C.POINTER(RasterCfg), c_void_p, c_size_t, c_void_p, c_void_p]),

@@ -100,9 +100,32 @@ extern "C" size_t cgs_raster_img_bytes(int32_t H, int32_t W) {
     CgsImg im;
     return cgs_img_carve(&im, nullptr, 0, H, W);
 }
-extern "C" size_t cgs_raster_bwd_scratch_bytes(int64_t P) {
+// The backward's scratch: d_mean_px [P, 2] | d_conic [P, 3] | d_z [P] | d_abs [P, 2], each 256-byte aligned.  Every entry point
+// takes a prefix of it: the colour image alone, + dL/dz of the maps, + the absolute sums.  The one place that knows the layout:
+// the three size queries, the backward's driver and cgs_raster_camera_backward all carve here.  Returns the prefix's bytes.
+enum CgsBwdScratchPart { BWD_SCRATCH_COLOUR = 2, BWD_SCRATCH_MAPS = 3, BWD_SCRATCH_ABS = 4 };
+struct CgsBwdScratch { float *d_mean_px, *d_conic, *d_z, *d_abs; };     // (d_z / d_abs: NULL outside the prefix)
+static size_t cgs_bwd_scratch_carve(CgsBwdScratch *s, void *ws, int64_t P, CgsBwdScratchPart part) {
+    CgsCarver c(ws, (size_t)-1);
     const size_t n = (size_t)(P > 0 ? P : 1);
-    return cgs_align_up(2 * n * sizeof(float), 256) + cgs_align_up(3 * n * sizeof(float), 256);
+    s->d_mean_px = c.take<float>(2 * n);
+    s->d_conic = c.take<float>(3 * n);
+    s->d_z = part >= BWD_SCRATCH_MAPS ? c.take<float>(n) : nullptr;
+    s->d_abs = part >= BWD_SCRATCH_ABS ? c.take<float>(2 * n) : nullptr;
+    return c.used();
+}
+extern "C" size_t cgs_raster_bwd_scratch_bytes(int64_t P) {
+    CgsBwdScratch s;
+    return cgs_bwd_scratch_carve(&s, nullptr, P, BWD_SCRATCH_COLOUR);
+}
+extern "C" size_t cgs_raster_bwd_aux_scratch_bytes(int64_t P) {
+    CgsBwdScratch s;
+    return cgs_bwd_scratch_carve(&s, nullptr, P, BWD_SCRATCH_MAPS);
+}
+// the aux scratch, then the [P, 2] sums of |dL_p/d(pixel mean)| of cgs_raster_backward_abs
+extern "C" size_t cgs_raster_bwd_abs_scratch_bytes(int64_t P) {
+    CgsBwdScratch s;
+    return cgs_bwd_scratch_carve(&s, nullptr, P, BWD_SCRATCH_ABS);
 }
 
 static int check_cfg(const cgs_raster_cfg *cfg) {
@@ -546,106 +569,6 @@ extern "C" int cgs_raster_render_spec(const cgs_raster_cfg *cfg, int64_t P, int6
                               (hipStream_t)stream_);
 }
 
-// ---- backward -----------------------------------------------------------------------------
-// Everything of the backward before the per-Gaussian kernel: checks, carving, the blend backward into the scratch's
-// dL/d(pixel mean) / dL/d(conic) (and the caller's dL_dcolors / dL_dopacities).
-static int raster_backward_blend(const char *fn, const cgs_raster_cfg *cfg, int64_t P, int64_t R, const int32_t *radii,
-                                 void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws, size_t img_bytes,
-                                 const float *dL_dout, float *dL_dcolors, float *dL_dopacities, void *scratch,
-                                 size_t scratch_bytes, CgsGeom &g, float *&d_mean_px, float *&d_conic, hipStream_t stream) {
-    int rc;
-    if (!dL_dout || !dL_dcolors || !dL_dopacities || !scratch || !radii) {
-        cgs_set_error("%s: NULL input", fn);
-        return CGS_ERR_ARG;
-    }
-    if (scratch_bytes < cgs_raster_bwd_scratch_bytes(P)) {
-        cgs_set_error("backward scratch too small");
-        return CGS_ERR_WORKSPACE;
-    }
-    CgsBin b;
-    CgsImg im;
-    memset(&b, 0, sizeof(b));
-    if (!geom_ws || !img_ws || !cgs_geom_carve(&g, geom_ws, geom_bytes, P) ||
-        !cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width)) {
-        cgs_set_error("workspace too small");
-        return CGS_ERR_WORKSPACE;
-    }
-    d_mean_px = (float *)scratch;
-    d_conic = (float *)((char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
-    CGS_CHECK_HIP(hipMemsetAsync(scratch, 0, cgs_raster_bwd_scratch_bytes(P), stream));
-    if (R > 0) {
-        if (!bin_ws || !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R)) {
-            cgs_set_error("binning workspace missing or too small");
-            return CGS_ERR_WORKSPACE;
-        }
-        if ((rc = cgs_launch_blend_bwd(cfg, g, b, im, dL_dout, d_mean_px, d_conic, dL_dopacities, dL_dcolors,
-                                       stream)))
-            return rc;
-    }
-    return CGS_OK;
-}
-
-extern "C" int cgs_raster_backward(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D,
-                                   const float *colors, const float *opacities, const float *scales,
-                                   const float *rotations, const int32_t *radii, void *geom_ws,
-                                   size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
-                                   size_t img_bytes, const float *dL_dout, float *dL_dmeans3D,
-                                   float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
-                                   float *dL_dscales, float *dL_drotations, void *scratch,
-                                   size_t scratch_bytes, void *stream_) {
-    (void)colors;
-    (void)opacities;
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_cfg(cfg);
-    if (rc) return rc;
-    if (P == 0) return CGS_OK;
-    if (!dL_dmeans3D || !dL_dmeans2D || !dL_dscales || !dL_drotations) {
-        cgs_set_error("cgs_raster_backward: NULL input");
-        return CGS_ERR_ARG;
-    }
-    CgsGeom g;
-    float *d_mean_px, *d_conic;
-    if ((rc = raster_backward_blend("cgs_raster_backward", cfg, P, R, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws,
-                                    img_bytes, dL_dout, dL_dcolors, dL_dopacities, scratch, scratch_bytes, g, d_mean_px, d_conic,
-                                    stream)))
-        return rc;
-    return cgs_launch_preprocess_bwd(cfg, P, means3D, scales, rotations, radii,
-                                     d_mean_px, d_conic, dL_dmeans3D, dL_dmeans2D, dL_dscales, dL_drotations, stream);
-}
-
-extern "C" int cgs_raster_backward_ex(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
-                                      const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
-                                      const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
-                                      void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
-                                      size_t img_bytes, const float *dL_dout, float *dL_dmeans3D, float *dL_dmeans2D,
-                                      float *dL_dcolors, float *dL_dopacities, float *dL_dshs, float *dL_dscales,
-                                      float *dL_drotations, float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_cfg(cfg);
-    if (rc) return rc;
-    CgsRasterForms f;
-    if ((rc = check_forms("cgs_raster_backward_ex", cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
-        return rc;
-    if (!shs && !cov3D)
-        return cgs_raster_backward(cfg, P, R, means3D, colors, opacities, scales, rotations, radii, geom_ws, geom_bytes, bin_ws,
-                                   bin_bytes, img_ws, img_bytes, dL_dout, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities,
-                                   dL_dscales, dL_drotations, scratch, scratch_bytes, stream_);
-    if (P == 0) return CGS_OK;
-    if (!means3D || !dL_dmeans3D || !dL_dmeans2D || (shs && !dL_dshs) || (cov3D && !dL_dcov3D) ||
-        (!cov3D && (!dL_dscales || !dL_drotations))) {
-        cgs_set_error("cgs_raster_backward_ex: NULL input");
-        return CGS_ERR_ARG;
-    }
-    CgsGeom g;
-    float *d_mean_px, *d_conic;
-    if ((rc = raster_backward_blend("cgs_raster_backward_ex", cfg, P, R, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws,
-                                    img_bytes, dL_dout, dL_dcolors, dL_dopacities, scratch, scratch_bytes, g, d_mean_px, d_conic,
-                                    stream)))
-        return rc;
-    return cgs_launch_preprocess_bwd_form(cfg, P, f, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dcolors, dL_dmeans3D,
-                                          dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream);
-}
-
 // ---- depth / inverse-depth / alpha maps (csrc/raster_aux.hip) --------------------------------------------------------
 int cgs_launch_aux_fwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, float *out_depth, float *out_invdepth,
                        float *out_alpha, hipStream_t stream);
@@ -664,16 +587,6 @@ int cgs_launch_feat_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg
 int cgs_launch_contrib(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const int32_t *slot, float *acc_weight,
                        float *acc_max_weight, int64_t *acc_pixels, int64_t *acc_top_pixels, int32_t *out_top_id,
                        float *out_top_weight, int32_t *out_count, hipStream_t stream);
-
-extern "C" size_t cgs_raster_bwd_aux_scratch_bytes(int64_t P) {
-    const size_t n = (size_t)(P > 0 ? P : 1);
-    return cgs_raster_bwd_scratch_bytes(P) + cgs_align_up(n * sizeof(float), 256);
-}
-// the aux scratch, then the [P, 2] sums of |dL_p/d(pixel mean)| of cgs_raster_backward_abs
-extern "C" size_t cgs_raster_bwd_abs_scratch_bytes(int64_t P) {
-    const size_t n = (size_t)(P > 0 ? P : 1);
-    return cgs_raster_bwd_aux_scratch_bytes(P) + cgs_align_up(2 * n * sizeof(float), 256);
-}
 
 // The workspaces of a render the caller kept, for the passes enqueued behind it (cgs_raster_render_aux, _render_features,
 // cgs_raster_contrib): g and b zeroed, then carved where there is something to carve.  fn: the entry point's name in front of
@@ -716,120 +629,6 @@ extern "C" int cgs_raster_render_aux(const cgs_raster_cfg *cfg, int64_t P, int64
     CgsImg im;
     if ((rc = carve_kept_render(nullptr, cfg, P, R, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, g, b, im))) return rc;
     return cgs_launch_aux_fwd(cfg, g, b, im, out_depth, out_invdepth, out_alpha, (hipStream_t)stream_);
-}
-
-// Backward of the colour image, the three maps and the feature map together, every argument form of cgs_raster_backward_ex.
-// Each upstream gradient may be NULL; without dL_dout no colour blend backward runs (dL_dcolors keeps its zeros).  The feature
-// blend backward (cgs_raster_backward_feat) adds into the same scratch and dL_dopacities, behind the other two blends.
-// fn: the entry point's name for the messages; aa: antialiasing (cgs_raster_backward_opt), which also reads opacities
-static int raster_backward_aux_impl(const char *fn, const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D,
-                                    const float *colors, const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
-                                    const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
-                                    void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws, size_t img_bytes,
-                                    const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth, const float *dL_dalpha,
-                                    float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities, float *dL_dshs,
-                                    float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *scratch, size_t scratch_bytes,
-                                    hipStream_t stream, bool aa, const float *features = nullptr, int32_t C = 0,
-                                    const float *dL_dfeatures_map = nullptr, float *dL_dfeatures = nullptr, bool absgrad = false) {
-    int rc = check_cfg(cfg);
-    if (rc) return rc;
-    if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
-    if ((features != nullptr) != (dL_dfeatures != nullptr)) {
-        cgs_set_error("%s: features and dL_dfeatures go together (one of them is NULL)", fn);
-        return CGS_ERR_ARG;
-    }
-    if (features && (C < 1 || C > CGS_RASTER_MAX_FEATURES)) {
-        cgs_set_error("%s: %d feature channels outside 1..%d", fn, C, CGS_RASTER_MAX_FEATURES);
-        return CGS_ERR_ARG;
-    }
-    CgsRasterForms f;
-    if ((rc = check_forms(fn, cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f)))
-        return rc;
-    if (P == 0) return CGS_OK;
-    if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacities || !scratch || (shs && !dL_dshs) ||
-        (cov3D && !dL_dcov3D) || (!cov3D && (!dL_dscales || !dL_drotations)) || !geom_ws || !img_ws || (R > 0 && !bin_ws) ||
-        (aa && !opacities)) {
-        cgs_set_error("%s: NULL input", fn);
-        return CGS_ERR_ARG;
-    }
-    // absgrad (cgs_raster_backward_abs): dL_dmeans2D is [P, 4] and the scratch carries the absolute accumulator behind dL/dz
-    const size_t scratch_need = absgrad ? cgs_raster_bwd_abs_scratch_bytes(P) : cgs_raster_bwd_aux_scratch_bytes(P);
-    if (scratch_bytes < scratch_need) {
-        cgs_set_error("%s: scratch too small: %zu < %zu", fn, scratch_bytes, scratch_need);
-        return CGS_ERR_WORKSPACE;
-    }
-    CgsGeom g;
-    CgsBin b;
-    CgsImg im;
-    memset(&b, 0, sizeof(b));
-    if (!cgs_geom_carve(&g, geom_ws, geom_bytes, P) || !cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width) ||
-        (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R))) {
-        cgs_set_error("%s: workspace too small", fn);
-        return CGS_ERR_WORKSPACE;
-    }
-    const bool aux = dL_ddepth || dL_dinvdepth || dL_dalpha;
-    float *d_mean_px = (float *)scratch;
-    float *d_conic = (float *)((char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
-    float *d_z = (float *)((char *)scratch + cgs_raster_bwd_scratch_bytes(P));
-    float *d_abs = absgrad ? (float *)((char *)scratch + cgs_raster_bwd_aux_scratch_bytes(P)) : nullptr;
-    CGS_CHECK_HIP(hipMemsetAsync(scratch, 0, scratch_need, stream));
-    if (R > 0) {
-        if (dL_dout &&
-            (rc = cgs_launch_blend_bwd(cfg, g, b, im, dL_dout, d_mean_px, d_conic, dL_dopacities, dL_dcolors, stream, d_abs)))
-            return rc;
-        if (aux && (rc = cgs_launch_aux_bwd(cfg, g, b, im, dL_ddepth, dL_dinvdepth, dL_dalpha, d_mean_px, d_conic, dL_dopacities,
-                                            d_z, stream)))
-            return rc;
-        if (features && dL_dfeatures_map &&
-            (rc = cgs_launch_feat_bwd(cfg, g, b, im, features, C, dL_dfeatures_map, d_mean_px, d_conic, dL_dopacities, dL_dfeatures,
-                                      stream)))
-            return rc;
-    }
-    // antialiasing: the blend backwards have summed dL/d(op_eff) into dL_dopacities by now; the per-Gaussian kernel turns it
-    // into dL/d(opacity) in place and chains h's share to the covariance
-    const float *aa_op = aa ? opacities : nullptr;
-    float *aa_dop = aa ? dL_dopacities : nullptr;
-    if (!shs && !cov3D)
-        rc = cgs_launch_preprocess_bwd(cfg, P, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dmeans3D,
-                                       dL_dmeans2D, dL_dscales, dL_drotations, stream, aa_op, aa_dop, d_abs);
-    else
-        rc = cgs_launch_preprocess_bwd_form(cfg, P, f, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dcolors,
-                                            dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_op,
-                                            aa_dop, d_abs);
-    if (rc) return rc;
-    return aux ? cgs_launch_aux_dz_chain(cfg, P, radii, d_z, dL_dmeans3D, stream) : CGS_OK;
-}
-
-extern "C" int cgs_raster_backward_aux(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
-                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
-                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
-                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
-                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
-                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
-                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
-                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_) {
-    return raster_backward_aux_impl("cgs_raster_backward_aux", cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities,
-                                    scales, rotations, cov3D, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout,
-                                    dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
-                                    dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_, false);
-}
-
-extern "C" int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
-                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
-                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
-                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
-                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
-                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
-                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
-                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts) {
-    int rc = check_cfg(cfg);
-    if (rc) return rc;
-    if ((rc = check_opts("cgs_raster_backward_opt", opts))) return rc;
-    return raster_backward_aux_impl("cgs_raster_backward_opt", cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities,
-                                    scales, rotations, cov3D, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout,
-                                    dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
-                                    dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_,
-                                    (opts & CGS_RASTER_ANTIALIAS) != 0);
 }
 
 // The feature map of a view: enqueued after the render the caller kept, exactly as cgs_raster_render_aux.  Every pixel of
@@ -887,49 +686,12 @@ extern "C" int cgs_raster_contrib(const cgs_raster_cfg *cfg, int64_t P, int64_t 
                               out_top_weight, out_count, (hipStream_t)stream_);
 }
 
-// cgs_raster_backward_opt plus the feature map's gradient.  features == NULL: cgs_raster_backward_opt's result.
-extern "C" int cgs_raster_backward_feat(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
-                                        const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
-                                        const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
-                                        void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
-                                        size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
-                                        const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
-                                        float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
-                                        float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts,
-                                        const float *features, int32_t C, const float *dL_dfeatures_map, float *dL_dfeatures) {
-    int rc = check_cfg(cfg);
-    if (rc) return rc;
-    if ((rc = check_opts("cgs_raster_backward_feat", opts))) return rc;
-    return raster_backward_aux_impl("cgs_raster_backward_feat", cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities,
-                                    scales, rotations, cov3D, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout,
-                                    dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
-                                    dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_,
-                                    (opts & CGS_RASTER_ANTIALIAS) != 0, features, C, dL_dfeatures_map, dL_dfeatures);
-}
+// ---- backward -----------------------------------------------------------------------------
+// One driver, raster_backward_run, behind the seven exported cgs_raster_backward* entry points (include/cgs.h): each of them
+// fills a RasterBwdCall and calls it.  Nothing is enqueued on a path that returns an error.
 
-// cgs_raster_backward_feat with dL_dmeans2D [P, 4]: columns 2:4 are the sums over the pixels of |dL_p/d(2-D mean)| of the colour
-// image (the ABS instance of the blend backward; include/cgs.h).  Every other result is cgs_raster_backward_feat's.
-extern "C" int cgs_raster_backward_abs(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
-                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
-                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
-                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
-                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
-                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
-                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
-                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts,
-                                       const float *features, int32_t C, const float *dL_dfeatures_map, float *dL_dfeatures) {
-    int rc = check_cfg(cfg);
-    if (rc) return rc;
-    if ((rc = check_opts("cgs_raster_backward_abs", opts))) return rc;
-    return raster_backward_aux_impl("cgs_raster_backward_abs", cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities,
-                                    scales, rotations, cov3D, radii, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout,
-                                    dL_ddepth, dL_dinvdepth, dL_dalpha, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs,
-                                    dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, (hipStream_t)stream_,
-                                    (opts & CGS_RASTER_ANTIALIAS) != 0, features, C, dL_dfeatures_map, dL_dfeatures, true);
-}
-
-// ---- bit-reproducible backward (csrc/raster_blend_rows.hip, the DET instances) ---------------------------------------------
-// det_ws: base [P] (exclusive scan of geom.tiles in id order) | the scan's scratch | the slot array, 48 B per pair
+// The workspace of the bit-reproducible backward (csrc/raster_blend_rows.hip, the DET instances): base [P] (exclusive scan of
+// geom.tiles in id order) | the scan's scratch | the slot array, 48 B per pair
 static const size_t DET_SLOT_BYTES = 48;
 struct DetLayout { size_t scan_off, scan_bytes, slots_off; };
 static DetLayout det_layout(int64_t P) {
@@ -949,9 +711,250 @@ int cgs_launch_blend_bwd_det(const cgs_raster_cfg *cfg, int64_t P, int64_t R, Cg
                              const float *dL_dout, const uint32_t *slot_base, void *slots, float *dL_dmean2D_px, float *dL_dconic,
                              float *dL_dopacity, float *dL_dcolors, float *dL_dz, float *dL_dabs_px, hipStream_t stream);
 
-// cgs_raster_backward_abs's colour path with every float-atomic sum replaced by the store-and-sum form (include/cgs.h): base =
-// scan of geom.tiles, [zero fill of the slots, DET blend backward,] per-Gaussian sum INTO the scratch layout of
-// cgs_raster_backward_abs, then the unchanged per-Gaussian backward.
+// What an entry point allows (the first six fields; the table in DESIGN.md), then its arguments in the order of the longest
+// signature.  An entry point without an argument leaves it zero: no map gradients, opts == 0, no features, no det_ws.
+struct RasterBwdCall {
+    const char *fn;         // the entry point's name in front of the messages
+    bool oldest;            // cgs_raster_backward / _ex: dL_dout is required, the forms are checked before P and R, and a NULL
+                            // workspace is CGS_ERR_WORKSPACE (the later entry points: CGS_ERR_ARG with the other NULL inputs)
+    bool any_form;          // check_forms applies; false for cgs_raster_backward, whose signature is the plain form itself
+    bool det;               // cgs_raster_backward_det: no map gradients, det_ws, nothing zero-filled (every row is written)
+    CgsBwdScratchPart scratch;      // the layout the scratch must hold; zero-filled unless `det`
+    int32_t means2D_cols;   // columns of dL_dmeans2D: 3, or 4 with the absolute sums
+    const cgs_raster_cfg *cfg;
+    int64_t P, R;
+    const float *means3D, *colors, *shs;
+    int32_t sh_degree, sh_coeffs;
+    const float *opacities, *scales, *rotations, *cov3D;
+    const int32_t *radii;
+    void *geom_ws; size_t geom_bytes;
+    void *bin_ws; size_t bin_bytes;
+    void *img_ws; size_t img_bytes;
+    const float *dL_dout, *dL_ddepth, *dL_dinvdepth, *dL_dalpha;
+    float *dL_dmeans3D, *dL_dmeans2D, *dL_dcolors, *dL_dopacities, *dL_dshs, *dL_dscales, *dL_drotations, *dL_dcov3D;
+    void *scratch_ws; size_t scratch_bytes;
+    void *stream;
+    uint32_t opts;
+    const float *features; int32_t C; const float *dL_dfeatures_map; float *dL_dfeatures;
+    void *det_ws; size_t det_bytes;
+};
+
+// Checks, carving, [zero fill | scan of geom.tiles], the blend backwards (colour, maps, features) into the scratch's
+// dL/d(pixel mean) / dL/d(conic) / dL/dz (and the caller's dL_dcolors / dL_dopacities), the per-Gaussian backward, dL/dz's chain.
+static int raster_backward_run(const RasterBwdCall &c) {
+    const char *fn = c.fn;
+    const cgs_raster_cfg *cfg = c.cfg;
+    const int64_t P = c.P, R = c.R;
+    hipStream_t stream = (hipStream_t)c.stream;
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if ((rc = check_opts(fn, c.opts))) return rc;
+    const bool aa = (c.opts & CGS_RASTER_ANTIALIAS) != 0, aux = c.dL_ddepth || c.dL_dinvdepth || c.dL_dalpha;
+    const bool plain = !c.shs && !c.cov3D;      // colours + scales / rotations: cgs_launch_preprocess_bwd
+    if (!c.oldest && (P < 0 || R < 0)) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
+    if (c.means2D_cols != 3 && c.means2D_cols != 4) {
+        cgs_set_error("%s: means2D_cols = %d, must be 3 or 4", fn, c.means2D_cols);
+        return CGS_ERR_ARG;
+    }
+    if (c.det && aux) {
+        cgs_set_error("%s: dL_ddepth, dL_dinvdepth and dL_dalpha must be NULL (the map blends' backward sums with float atomics "
+                      "and is not covered by the deterministic mode)", fn);
+        return CGS_ERR_ARG;
+    }
+    if ((c.features != nullptr) != (c.dL_dfeatures != nullptr)) {
+        cgs_set_error("%s: features and dL_dfeatures go together (one of them is NULL)", fn);
+        return CGS_ERR_ARG;
+    }
+    if (c.features && (c.C < 1 || c.C > CGS_RASTER_MAX_FEATURES)) {
+        cgs_set_error("%s: %d feature channels outside 1..%d", fn, c.C, CGS_RASTER_MAX_FEATURES);
+        return CGS_ERR_ARG;
+    }
+    CgsRasterForms f = {nullptr, 0, 0, 0, nullptr};
+    if (c.any_form && (rc = check_forms(fn, cfg, P, c.colors, c.shs, c.sh_degree, c.sh_coeffs, c.scales, c.rotations, c.cov3D, f)))
+        return rc;
+    if (c.oldest) {
+        if (plain) fn = "cgs_raster_backward";      // (cgs_raster_backward_ex with the plain form is that entry point)
+        if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
+    }
+    if (P == 0) return CGS_OK;
+    if (!c.radii || !c.dL_dmeans3D || !c.dL_dmeans2D || !c.dL_dcolors || !c.dL_dopacities || !c.scratch_ws ||
+        (c.shs && !c.dL_dshs) || (c.cov3D && !c.dL_dcov3D) || (!c.cov3D && (!c.dL_dscales || !c.dL_drotations)) ||
+        (c.oldest ? !c.dL_dout || (!plain && !c.means3D)
+                  : !c.means3D || !c.geom_ws || !c.img_ws || (R > 0 && !c.bin_ws) || (aa && !c.opacities) || (c.det && !c.det_ws))) {
+        cgs_set_error("%s: NULL input", fn);
+        return CGS_ERR_ARG;
+    }
+    CgsBwdScratch s;
+    const size_t scratch_need = cgs_bwd_scratch_carve(&s, c.scratch_ws, P, c.scratch);
+    if (c.scratch_bytes < scratch_need) {
+        cgs_set_error("%s: scratch too small: %zu < %zu", fn, c.scratch_bytes, scratch_need);
+        return CGS_ERR_WORKSPACE;
+    }
+    if (c.det && c.det_bytes < cgs_raster_bwd_det_bytes(P, R, c.means2D_cols)) {
+        cgs_set_error("%s: det_ws too small: %zu < %zu", fn, c.det_bytes, cgs_raster_bwd_det_bytes(P, R, c.means2D_cols));
+        return CGS_ERR_WORKSPACE;
+    }
+    CgsGeom g;
+    CgsBin b;
+    CgsImg im;
+    memset(&b, 0, sizeof(b));
+    if (!c.geom_ws || !c.img_ws || !cgs_geom_carve(&g, c.geom_ws, c.geom_bytes, P) ||
+        !cgs_img_carve(&im, c.img_ws, c.img_bytes, cfg->image_height, cfg->image_width) ||
+        (R > 0 && (!c.bin_ws || !cgs_bin_carve(&b, c.bin_ws, c.bin_bytes, P, R)))) {
+        cgs_set_error("%s: workspace too small", fn);
+        return CGS_ERR_WORKSPACE;
+    }
+    // four columns: dL_dmeans2D is [P, 4] and the blend backward sums the absolute accumulator behind dL/dz
+    float *d_abs = c.means2D_cols == 4 ? s.d_abs : nullptr;
+    if (c.det) {
+        // store-and-sum instead of float atomics (include/cgs.h): base = scan of geom.tiles, [zero fill of the slots, DET blend
+        // backward,] per-Gaussian sum INTO the scratch; without a blend the sum kernel reads neither base nor a slot
+        const DetLayout dl = det_layout(P);
+        uint32_t *base = (uint32_t *)c.det_ws;
+        if (R > 0 && c.dL_dout) {
+            if ((rc = cgs_scan_exclusive_u32_total(g.tiles, base, P, (char *)c.det_ws + dl.scan_off, dl.scan_bytes, nullptr, stream)))
+                return rc;
+            if (cfg->debug) CGS_CHECK_HIP(hipStreamSynchronize(stream));
+        }
+        if ((rc = cgs_launch_blend_bwd_det(cfg, P, R, g, b, im, c.dL_dout, base, (char *)c.det_ws + dl.slots_off, s.d_mean_px,
+                                           s.d_conic, c.dL_dopacities, c.dL_dcolors, s.d_z, d_abs, stream)))
+            return rc;
+    } else {
+        CGS_CHECK_HIP(hipMemsetAsync(c.scratch_ws, 0, scratch_need, stream));
+        if (R > 0) {
+            if (c.dL_dout && (rc = cgs_launch_blend_bwd(cfg, g, b, im, c.dL_dout, s.d_mean_px, s.d_conic, c.dL_dopacities,
+                                                        c.dL_dcolors, stream, d_abs)))
+                return rc;
+            if (aux && (rc = cgs_launch_aux_bwd(cfg, g, b, im, c.dL_ddepth, c.dL_dinvdepth, c.dL_dalpha, s.d_mean_px, s.d_conic,
+                                                c.dL_dopacities, s.d_z, stream)))
+                return rc;
+            if (c.features && c.dL_dfeatures_map &&
+                (rc = cgs_launch_feat_bwd(cfg, g, b, im, c.features, c.C, c.dL_dfeatures_map, s.d_mean_px, s.d_conic,
+                                          c.dL_dopacities, c.dL_dfeatures, stream)))
+                return rc;
+        }
+    }
+    // antialiasing: the blend backwards have summed dL/d(op_eff) into dL_dopacities by now; the per-Gaussian kernel turns it
+    // into dL/d(opacity) in place and chains h's share to the covariance
+    const float *aa_op = aa ? c.opacities : nullptr;
+    float *aa_dop = aa ? c.dL_dopacities : nullptr;
+    if (plain)
+        rc = cgs_launch_preprocess_bwd(cfg, P, c.means3D, c.scales, c.rotations, c.radii, s.d_mean_px, s.d_conic, c.dL_dmeans3D,
+                                       c.dL_dmeans2D, c.dL_dscales, c.dL_drotations, stream, aa_op, aa_dop, d_abs);
+    else
+        rc = cgs_launch_preprocess_bwd_form(cfg, P, f, c.means3D, c.scales, c.rotations, c.radii, s.d_mean_px, s.d_conic,
+                                            c.dL_dcolors, c.dL_dmeans3D, c.dL_dmeans2D, c.dL_dshs, c.dL_dscales, c.dL_drotations,
+                                            c.dL_dcov3D, stream, aa_op, aa_dop, d_abs);
+    if (rc) return rc;
+    return aux ? cgs_launch_aux_dz_chain(cfg, P, c.radii, s.d_z, c.dL_dmeans3D, stream) : CGS_OK;
+}
+
+extern "C" int cgs_raster_backward(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D,
+                                   const float *colors, const float *opacities, const float *scales,
+                                   const float *rotations, const int32_t *radii, void *geom_ws,
+                                   size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                   size_t img_bytes, const float *dL_dout, float *dL_dmeans3D,
+                                   float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
+                                   float *dL_dscales, float *dL_drotations, void *scratch,
+                                   size_t scratch_bytes, void *stream_) {
+    const RasterBwdCall c = {"cgs_raster_backward", true, false, false, BWD_SCRATCH_COLOUR, 3,
+                             cfg, P, R, means3D, colors, nullptr, 0, 0, opacities, scales, rotations, nullptr, radii,
+                             geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout, nullptr, nullptr, nullptr,
+                             dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, nullptr, dL_dscales, dL_drotations, nullptr,
+                             scratch, scratch_bytes, stream_};
+    return raster_backward_run(c);
+}
+
+extern "C" int cgs_raster_backward_ex(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                      const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                      const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                      void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                      size_t img_bytes, const float *dL_dout, float *dL_dmeans3D, float *dL_dmeans2D,
+                                      float *dL_dcolors, float *dL_dopacities, float *dL_dshs, float *dL_dscales,
+                                      float *dL_drotations, float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_) {
+    const RasterBwdCall c = {"cgs_raster_backward_ex", true, true, false, BWD_SCRATCH_COLOUR, 3,
+                             cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities, scales, rotations, cov3D, radii,
+                             geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout, nullptr, nullptr, nullptr,
+                             dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D,
+                             scratch, scratch_bytes, stream_};
+    return raster_backward_run(c);
+}
+
+// Backward of the colour image and the three maps together, every argument form of cgs_raster_backward_ex.  Each upstream
+// gradient may be NULL; without dL_dout no colour blend backward runs (dL_dcolors keeps its zeros).
+extern "C" int cgs_raster_backward_aux(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_) {
+    const RasterBwdCall c = {"cgs_raster_backward_aux", false, true, false, BWD_SCRATCH_MAPS, 3,
+                             cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities, scales, rotations, cov3D, radii,
+                             geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout, dL_ddepth, dL_dinvdepth, dL_dalpha,
+                             dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D,
+                             scratch, scratch_bytes, stream_};
+    return raster_backward_run(c);
+}
+
+// cgs_raster_backward_aux with the options word: CGS_RASTER_ANTIALIAS also reads opacities
+extern "C" int cgs_raster_backward_opt(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts) {
+    const RasterBwdCall c = {"cgs_raster_backward_opt", false, true, false, BWD_SCRATCH_MAPS, 3,
+                             cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities, scales, rotations, cov3D, radii,
+                             geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout, dL_ddepth, dL_dinvdepth, dL_dalpha,
+                             dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D,
+                             scratch, scratch_bytes, stream_, opts};
+    return raster_backward_run(c);
+}
+
+// cgs_raster_backward_opt plus the feature map's gradient: the feature blend backward adds into the same scratch and
+// dL_dopacities, behind the other two blends.  features == NULL: cgs_raster_backward_opt's result.
+extern "C" int cgs_raster_backward_feat(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                        const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                        const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                        void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                        size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                        const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                        float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                        float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts,
+                                        const float *features, int32_t C, const float *dL_dfeatures_map, float *dL_dfeatures) {
+    const RasterBwdCall c = {"cgs_raster_backward_feat", false, true, false, BWD_SCRATCH_MAPS, 3,
+                             cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities, scales, rotations, cov3D, radii,
+                             geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout, dL_ddepth, dL_dinvdepth, dL_dalpha,
+                             dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D,
+                             scratch, scratch_bytes, stream_, opts, features, C, dL_dfeatures_map, dL_dfeatures};
+    return raster_backward_run(c);
+}
+
+// cgs_raster_backward_feat with dL_dmeans2D [P, 4]: columns 2:4 are the sums over the pixels of |dL_p/d(2-D mean)| of the colour
+// image (the ABS instance of the blend backward; include/cgs.h).  Every other result is cgs_raster_backward_feat's.
+extern "C" int cgs_raster_backward_abs(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                       const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                       const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                       void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                       size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                       const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                       float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                       float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts,
+                                       const float *features, int32_t C, const float *dL_dfeatures_map, float *dL_dfeatures) {
+    const RasterBwdCall c = {"cgs_raster_backward_abs", false, true, false, BWD_SCRATCH_ABS, 4,
+                             cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities, scales, rotations, cov3D, radii,
+                             geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout, dL_ddepth, dL_dinvdepth, dL_dalpha,
+                             dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D,
+                             scratch, scratch_bytes, stream_, opts, features, C, dL_dfeatures_map, dL_dfeatures};
+    return raster_backward_run(c);
+}
+
+// cgs_raster_backward_abs's colour path with every float-atomic sum replaced by the store-and-sum form (include/cgs.h), into the
+// scratch layout of cgs_raster_backward_abs for either width of dL_dmeans2D, then the unchanged per-Gaussian backward.
 extern "C" int cgs_raster_backward_det(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
                                        const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
                                        const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
@@ -961,73 +964,12 @@ extern "C" int cgs_raster_backward_det(const cgs_raster_cfg *cfg, int64_t P, int
                                        float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
                                        float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts,
                                        int32_t means2D_cols, void *det_ws, size_t det_bytes) {
-    const char *fn = "cgs_raster_backward_det";
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_cfg(cfg);
-    if (rc) return rc;
-    if ((rc = check_opts(fn, opts))) return rc;
-    if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
-    if (means2D_cols != 3 && means2D_cols != 4) {
-        cgs_set_error("%s: means2D_cols = %d, must be 3 or 4", fn, means2D_cols);
-        return CGS_ERR_ARG;
-    }
-    if (dL_ddepth || dL_dinvdepth || dL_dalpha) {
-        cgs_set_error("%s: dL_ddepth, dL_dinvdepth and dL_dalpha must be NULL (the map blends' backward sums with float atomics "
-                      "and is not covered by the deterministic mode)", fn);
-        return CGS_ERR_ARG;
-    }
-    const bool aa = (opts & CGS_RASTER_ANTIALIAS) != 0, absgrad = means2D_cols == 4;
-    CgsRasterForms f;
-    if ((rc = check_forms(fn, cfg, P, colors, shs, sh_degree, sh_coeffs, scales, rotations, cov3D, f))) return rc;
-    if (P == 0) return CGS_OK;
-    if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dcolors || !dL_dopacities || !scratch || !det_ws ||
-        (shs && !dL_dshs) || (cov3D && !dL_dcov3D) || (!cov3D && (!dL_dscales || !dL_drotations)) || !geom_ws || !img_ws ||
-        (R > 0 && !bin_ws) || (aa && !opacities)) {
-        cgs_set_error("%s: NULL input", fn);
-        return CGS_ERR_ARG;
-    }
-    const size_t scratch_need = cgs_raster_bwd_abs_scratch_bytes(P), det_need = cgs_raster_bwd_det_bytes(P, R, means2D_cols);
-    if (scratch_bytes < scratch_need) {
-        cgs_set_error("%s: scratch too small: %zu < %zu", fn, scratch_bytes, scratch_need);
-        return CGS_ERR_WORKSPACE;
-    }
-    if (det_bytes < det_need) {
-        cgs_set_error("%s: det_ws too small: %zu < %zu", fn, det_bytes, det_need);
-        return CGS_ERR_WORKSPACE;
-    }
-    CgsGeom g;
-    CgsBin b;
-    CgsImg im;
-    memset(&b, 0, sizeof(b));
-    if (!cgs_geom_carve(&g, geom_ws, geom_bytes, P) || !cgs_img_carve(&im, img_ws, img_bytes, cfg->image_height, cfg->image_width) ||
-        (R > 0 && !cgs_bin_carve(&b, bin_ws, bin_bytes, P, R))) {
-        cgs_set_error("%s: workspace too small", fn);
-        return CGS_ERR_WORKSPACE;
-    }
-    float *d_mean_px = (float *)scratch;
-    float *d_conic = (float *)((char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
-    float *d_z = (float *)((char *)scratch + cgs_raster_bwd_scratch_bytes(P));
-    float *d_abs = absgrad ? (float *)((char *)scratch + cgs_raster_bwd_aux_scratch_bytes(P)) : nullptr;
-    const DetLayout dl = det_layout(P);
-    uint32_t *base = (uint32_t *)det_ws;
-    char *scan = (char *)det_ws + dl.scan_off, *slots = (char *)det_ws + dl.slots_off;
-    const size_t scan_bytes = dl.scan_bytes;
-    const bool blend = R > 0 && dL_dout;
-    if (blend) {
-        if ((rc = cgs_scan_exclusive_u32_total(g.tiles, base, P, scan, scan_bytes, nullptr, stream))) return rc;
-        if (cfg->debug) CGS_CHECK_HIP(hipStreamSynchronize(stream));
-    }
-    // (without a blend the sum kernel reads neither base nor a slot: every row is written zero)
-    if ((rc = cgs_launch_blend_bwd_det(cfg, P, R, g, b, im, dL_dout, base, slots, d_mean_px, d_conic, dL_dopacities, dL_dcolors,
-                                       d_z, d_abs, stream)))
-        return rc;
-    const float *aa_op = aa ? opacities : nullptr;
-    float *aa_dop = aa ? dL_dopacities : nullptr;
-    if (!shs && !cov3D)
-        return cgs_launch_preprocess_bwd(cfg, P, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dmeans3D, dL_dmeans2D,
-                                         dL_dscales, dL_drotations, stream, aa_op, aa_dop, d_abs);
-    return cgs_launch_preprocess_bwd_form(cfg, P, f, means3D, scales, rotations, radii, d_mean_px, d_conic, dL_dcolors, dL_dmeans3D,
-                                          dL_dmeans2D, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D, stream, aa_op, aa_dop, d_abs);
+    const RasterBwdCall c = {"cgs_raster_backward_det", false, true, true, BWD_SCRATCH_ABS, means2D_cols,
+                             cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities, scales, rotations, cov3D, radii,
+                             geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout, dL_ddepth, dL_dinvdepth, dL_dalpha,
+                             dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D,
+                             scratch, scratch_bytes, stream_, opts, nullptr, 0, nullptr, nullptr, det_ws, det_bytes};
+    return raster_backward_run(c);
 }
 
 // ---- camera gradients (csrc/raster_camera.hip) ---------------------------------------------------------------------------
@@ -1066,6 +1008,8 @@ extern "C" int cgs_raster_camera_backward(const cgs_raster_cfg *cfg, int64_t P, 
         cgs_set_error("%s: work missing or too small: %zu < %zu", fn, work ? work_bytes : (size_t)0, cgs_camera_work_bytes(P));
         return CGS_ERR_ARG;
     }
+    CgsBwdScratch s;       // (read only; d_z: NULL without the maps)
+    const size_t need = cgs_bwd_scratch_carve(&s, const_cast<void *>(scratch), P, maps ? BWD_SCRATCH_MAPS : BWD_SCRATCH_COLOUR);
     CgsRasterForms f = {nullptr, 0, 0, 0, cov3D};
     if (dL_dcampos) {
         if (sh_degree < 0 || sh_degree > 3) { cgs_set_error("%s: sh_degree %d outside 0..3", fn, sh_degree); return CGS_ERR_ARG; }
@@ -1088,7 +1032,6 @@ extern "C" int cgs_raster_camera_backward(const cgs_raster_cfg *cfg, int64_t P, 
             cgs_set_error("%s: NULL input", fn);
             return CGS_ERR_ARG;
         }
-        const size_t need = maps ? cgs_raster_bwd_aux_scratch_bytes(P) : cgs_raster_bwd_scratch_bytes(P);
         if (scratch_bytes < need) { cgs_set_error("%s: scratch too small: %zu < %zu", fn, scratch_bytes, need); return CGS_ERR_ARG; }
     }
     if (P == 0) {       // no Gaussian: zeros
@@ -1097,10 +1040,7 @@ extern "C" int cgs_raster_camera_backward(const cgs_raster_cfg *cfg, int64_t P, 
         if (dL_dcampos) CGS_CHECK_HIP(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float), stream));
         return CGS_OK;
     }
-    const float *d_mean_px = (const float *)scratch;
-    const float *d_conic = (const float *)((const char *)scratch + cgs_align_up(2 * (size_t)P * sizeof(float), 256));
-    const float *d_z = maps ? (const float *)((const char *)scratch + cgs_raster_bwd_scratch_bytes(P)) : nullptr;
-    return cgs_launch_camera_bwd(cfg, P, f, means3D, opacities, scales, rotations, radii, d_mean_px, d_conic, d_z, dL_dcolors,
+    return cgs_launch_camera_bwd(cfg, P, f, means3D, opacities, scales, rotations, radii, s.d_mean_px, s.d_conic, s.d_z, dL_dcolors,
                                  dL_dopacities, aa, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, work, stream);
 }
 

@@ -420,6 +420,48 @@ def check_contrib(contrib, contrib_slots, means3D) -> None:
         raise ValueError("contrib needs at least one row with contrib_slots")
 
 
+def launch_backward(cfg, P, R, inputs, D, M, workspaces, g, maps, grads, stream, opts=0, absgrad=False, deterministic=False,
+                    features=None):
+    """The one cgs_raster_backward* call of a view, for both autograd nodes (_RasterizeGaussians, renderer._ExpandRasterize).
+    inputs: (means3D, colors, shs, opacities, scales, rotations, cov3D, radii), None for what the form does not have;
+    workspaces: (geom, binning or None, img) and R the count the binning workspace was carved with; g, maps: the upstream
+    gradients of the colour image and of the depth / inverse-depth / alpha maps (None: no gradient); grads: (dL_dmeans3D,
+    dL_dmeans2D [P, 4 with absgrad else 3], dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D), the
+    caller's buffers (dL_dcolors / dL_dopacities zero-filled unless `deterministic`); features: (features, the feature map's
+    gradient, dL_dfeatures zero-filled) or None.  The entry point: deterministic -> _det (the colour image alone); absgrad ->
+    _abs, whatever got a gradient; maps, an option bit or a feature-map gradient -> _feat (without features it is
+    cgs_raster_backward_opt's); otherwise the colour image alone -> _ex (cgs_raster_backward for colours + scales / rotations).
+    Returns the scratch, which cgs_raster_camera_backward reads, and the `opts` to call that with."""
+    L = _lib.lib()
+    p = _lib.ptr
+    means3D, colors, shs, opac, scales, rots, cov, radii = inputs
+    geom, binws, img = workspaces
+    dev = means3D.device
+    feat, g_fmap, d_feat = features if features is not None else (None, None, None)
+    m2 = 4 if absgrad else 3        # columns of dL/dmeans2D
+    map_ptrs = tuple(p(t) for t in maps)
+    tail = (opts, p(feat), feat.shape[1] if feat is not None else 0, p(g_fmap), p(d_feat))
+    # (every scratch but _ex's begins with cgs_raster_backward_opt's; _det writes its dL/dz zero)
+    cam_opts = opts | CGS_RASTER_CAMERA_MAPS
+    if deterministic:
+        name, scratch_bytes = "cgs_raster_backward_det", L.cgs_raster_bwd_abs_scratch_bytes(P)
+    elif absgrad:
+        name, scratch_bytes = "cgs_raster_backward_abs", L.cgs_raster_bwd_abs_scratch_bytes(P)
+    elif features is not None or opts or any(t is not None for t in maps):
+        name, scratch_bytes = "cgs_raster_backward_feat", L.cgs_raster_bwd_aux_scratch_bytes(P)
+    else:
+        name, scratch_bytes, map_ptrs, tail, cam_opts = "cgs_raster_backward_ex", L.cgs_raster_bwd_scratch_bytes(P), (), (), 0
+    scratch = _workspace(scratch_bytes, dev)
+    if deterministic:
+        det_ws = _workspace(L.cgs_raster_bwd_det_bytes(P, R, m2), dev)
+        tail = (opts, m2, p(det_ws), det_ws.numel())
+    _lib.check(getattr(L, name)(
+        cfg.ref, P, R, p(means3D), p(colors), p(shs), D, M, p(opac), p(scales), p(rots), p(cov), p(radii), p(geom), geom.numel(),
+        p(binws), binws.numel() if binws is not None else 0, p(img), img.numel(), p(g), *map_ptrs, *(p(t) for t in grads),
+        p(scratch), scratch.numel(), stream, *tail), name)
+    return scratch, cam_opts
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """The one node of the drop-in: any of the four argument forms (absent inputs are None), antialiasing from
     `raster_settings.antialiasing`, and the depth / inverse-depth / alpha maps as three more outputs when `aux`.  The forward
@@ -529,44 +571,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         d_rots = rest[(6 + m2) * P:].view(P, 4) if cov is None else None
         d_cov = rest[(3 + m2) * P:].view(P, 6) if cov is not None else None
         d_shs = torch.empty_like(shs) if shs is not None else None      # of its own: aligned as shs is (vector stores)
-        inputs = (cfg.ref, P, ctx.num_rendered, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(shs), ctx.D, ctx.M,
-                  _lib.ptr(opac), _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(geom),
-                  geom.numel(), _lib.ptr(binws), binws.numel(), _lib.ptr(img), img.numel(), _lib.ptr(g))
-        grads = (_lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_shs),
-                 _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(d_cov))
+        with_feat = g_fmap is not None
+        d_feat = torch.zeros_like(feat) if with_feat else None          # accumulated atomically, like dL/dcolor
         stream = _lib.current_stream()
-        d_feat = None
-        if ctx.deterministic:       # the colour image alone (the forward refused everything else), every form and option
-            cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS        # (the scratch is cgs_raster_backward_abs's, dL/dz written zero)
-            scratch = _workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
-            det_ws = _workspace(L.cgs_raster_bwd_det_bytes(P, ctx.num_rendered, m2), dev)
-            _lib.check(L.cgs_raster_backward_det(*inputs, None, None, None, *grads, _lib.ptr(scratch), scratch.numel(), stream,
-                                                 ctx.opts, m2, _lib.ptr(det_ws), det_ws.numel()), "cgs_raster_backward_det")
-        elif ctx.absgrad:           # one entry point for every combination: NULL for what got no gradient
-            cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS        # (its scratch begins with cgs_raster_backward_opt's)
-            d_feat = torch.zeros_like(feat) if g_fmap is not None else None
-            scratch = _workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
-            with_feat = g_fmap is not None
-            _lib.check(L.cgs_raster_backward_abs(*inputs, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), *grads,
-                                                 _lib.ptr(scratch), scratch.numel(), stream, ctx.opts,
-                                                 _lib.ptr(feat) if with_feat else None, feat.shape[1] if with_feat else 0,
-                                                 _lib.ptr(g_fmap), _lib.ptr(d_feat)), "cgs_raster_backward_abs")
-        elif g_fmap is not None or ctx.opts or any(t is not None for t in maps):
-            # maps, antialiasing or a gradient on the feature map (then with the feature blend backward in it): one call,
-            # which without features is cgs_raster_backward_opt's
-            cam_opts = ctx.opts | CGS_RASTER_CAMERA_MAPS
-            with_feat = g_fmap is not None
-            d_feat = torch.zeros_like(feat) if with_feat else None          # accumulated atomically, like dL/dcolor
-            scratch = _workspace(L.cgs_raster_bwd_aux_scratch_bytes(P), dev)
-            _lib.check(L.cgs_raster_backward_feat(*inputs, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), *grads,
-                                                  _lib.ptr(scratch), scratch.numel(), stream, ctx.opts,
-                                                  _lib.ptr(feat) if with_feat else None, feat.shape[1] if with_feat else 0,
-                                                  _lib.ptr(g_fmap), _lib.ptr(d_feat)), "cgs_raster_backward_feat")
-        else:       # the colour image alone, no antialiasing (cgs_raster_backward for the form the reference trains with)
-            cam_opts = 0
-            scratch = _workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
-            _lib.check(L.cgs_raster_backward_ex(*inputs, *grads, _lib.ptr(scratch), scratch.numel(), stream),
-                       "cgs_raster_backward_ex")
+        scratch, cam_opts = launch_backward(
+            cfg, P, ctx.num_rendered, (means3D, colors, shs, opac, scales, rots, cov, radii), ctx.D, ctx.M, (geom, binws, img),
+            g, maps, (d_means3D, d_means2D, d_colors, d_opac, d_shs, d_scales, d_rots, d_cov), stream, ctx.opts, ctx.absgrad,
+            ctx.deterministic, (feat, g_fmap, d_feat) if with_feat else None)
         # the camera: only when one of its tensors asks (campos without shs is unused: None), behind the backward above while
         # its scratch and its dL_dcolors / dL_dopacities are intact
         need_v, need_p, need_c = ctx.needs_input_grad[10:13]

@@ -260,7 +260,7 @@ class _ExpandRasterize(torch.autograd.Function):
         cfg, K, n, src_row, P = ctx.cfg, ctx.K, ctx.n, ctx.src_row, ctx.P
         dev = gscaling.device
         stream = _lib.current_stream()
-        # ---- the rasterizer's backward (as _RasterizeGaussians.backward) into buffers that stay inside this node
+        # ---- the rasterizer's backward (rasterizer.launch_backward) into buffers that stay inside this node
         use_det = g_img is not None and P > 0 and ctx.deterministic
         # atomically accumulated: dL/d colour | opacity (the deterministic backward writes every row of both itself)
         acc = (torch.empty if use_det else torch.zeros)(max(P, 1) * 4, dtype=torch.float32, device=dev)
@@ -269,35 +269,13 @@ class _ExpandRasterize(torch.autograd.Function):
         rest = torch.empty(max(P, 1) * (10 + m2), dtype=torch.float32, device=dev)
         d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:(3 + m2) * P].view(P, m2)
         d_scales, d_rots = rest[(3 + m2) * P:(6 + m2) * P].view(P, 3), rest[(6 + m2) * P:(10 + m2) * P].view(P, 4)
-        if use_det:         # the plain form's arguments, as the absgrad branch below
-            scratch = rz._workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
-            det_ws = rz._workspace(L.cgs_raster_bwd_det_bytes(P, ctx.num_rendered, m2), dev)
-            _lib.check(L.cgs_raster_backward_det(
-                cfg.ref, P, ctx.num_rendered, _lib.ptr(xyz), _lib.ptr(d_colors), None, 0, 0, None, _lib.ptr(scaling),
-                _lib.ptr(rot), None, _lib.ptr(radii), _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
-                binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(), _lib.ptr(rz._f32c(g_img)), None, None,
-                None, _lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), None, _lib.ptr(d_scales),
-                _lib.ptr(d_rots), None, _lib.ptr(scratch), scratch.numel(), stream, 0, m2, _lib.ptr(det_ws), det_ws.numel()),
-                "cgs_raster_backward_det")
-        elif g_img is not None and P > 0 and ctx.absgrad:
+        if g_img is not None and P > 0:
             # the plain form's arguments; the colours never existed as a tensor and the backward of this form does not read
             # them (the pointer only says "colours, not SH": include/cgs.h), so the gradient buffer stands in
-            scratch = rz._workspace(L.cgs_raster_bwd_abs_scratch_bytes(P), dev)
-            _lib.check(L.cgs_raster_backward_abs(
-                cfg.ref, P, ctx.num_rendered, _lib.ptr(xyz), _lib.ptr(d_colors), None, 0, 0, None, _lib.ptr(scaling),
-                _lib.ptr(rot), None, _lib.ptr(radii), _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
-                binws.numel() if binws is not None else 0, _lib.ptr(img), img.numel(), _lib.ptr(rz._f32c(g_img)), None, None,
-                None, _lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors), _lib.ptr(d_opac), None, _lib.ptr(d_scales),
-                _lib.ptr(d_rots), None, _lib.ptr(scratch), scratch.numel(), stream, 0, None, 0, None, None),
-                "cgs_raster_backward_abs")
-        elif g_img is not None and P > 0:
-            scratch = rz._workspace(L.cgs_raster_bwd_scratch_bytes(P), dev)
-            _lib.check(L.cgs_raster_backward(
-                cfg.ref, P, ctx.num_rendered, _lib.ptr(xyz), None, None, _lib.ptr(scaling), _lib.ptr(rot), _lib.ptr(radii),
-                _lib.ptr(geom), geom.numel(), _lib.ptr(binws), binws.numel() if binws is not None else 0, _lib.ptr(img),
-                img.numel(), _lib.ptr(rz._f32c(g_img)), _lib.ptr(d_means3D), _lib.ptr(d_means2D), _lib.ptr(d_colors),
-                _lib.ptr(d_opac), _lib.ptr(d_scales), _lib.ptr(d_rots), _lib.ptr(scratch), scratch.numel(), stream),
-                "cgs_raster_backward")
+            rz.launch_backward(cfg, P, ctx.num_rendered, (xyz, d_colors, None, None, scaling, rot, None, radii), 0, 0,
+                               (geom, binws, img), rz._f32c(g_img), (None, None, None),
+                               (d_means3D, d_means2D, d_colors, d_opac, None, d_scales, d_rots, None), stream, 0, ctx.absgrad,
+                               ctx.deterministic)
         else:
             rest.zero_()
         if g_scaling is not None:            # the loss reads `scaling` too (train.py:204): what autograd would have summed
