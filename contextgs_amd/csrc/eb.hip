@@ -10,6 +10,7 @@
 // DPP network and keeps them in registers across the whole row loop, so the kernel ends with
 // 58 atomics per wave.
 #include "cgs_internal.h"
+#include <cfloat>
 
 #define EB_P 58          // packed parameters per channel
 // layout: [M0 3 | B0 3 | F0 3 | M1 9 | B1 3 | F1 3 | M2 9 | B2 3 | F2 3 | M3 9 | B3 3 | F3 3 | M4 3 | B4 1]
@@ -28,7 +29,10 @@ __device__ __forceinline__ float eb_rcp(float d) {          // 1 / d: hardware r
     const float r = __builtin_amdgcn_rcpf(d);
     return fmaf(fmaf(-d, r, 1.f), r, r);
 }
-__device__ __forceinline__ float sigmoidf(float x) { return eb_rcp(1.f + __expf(-x)); }
+// finite for every finite x: below x ~ -88.7 __expf(-x) is +inf and eb_rcp(inf) = fma(fma(-inf, 0, 1), 0, 0) is NaN, which the
+// backward's s (1 - s) would add into the parameter gradients of the whole channel (latents of a diverging run get there); the
+// clamp leaves every finite exponential, i.e. every result for |x| < 87, bit for bit as it is
+__device__ __forceinline__ float sigmoidf(float x) { return eb_rcp(1.f + fminf(__expf(-x), FLT_MAX)); }
 // tanh of the density's hidden units (24 per element and evaluation pair: the library's tanhf, a 38-instruction divergent
 // routine, WAS this file's kernels — round 6): 1 - 2 / (1 + exp(2 z)) with one v_exp_f32; absolute error ~1e-7, which is what
 // enters y = z + f tanh(z) (the relative error near z = 0 does not: nothing divides by it); |z| clamped where tanh is +-1 in fp32
