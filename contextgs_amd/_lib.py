@@ -59,9 +59,10 @@ class AdamTensor(C.Structure):
     ]
 
 
-# The seven cgs_raster_backward* signatures (include/cgs.h), from their common pieces: cfg, P, R | the inputs | the three
+# The eight cgs_raster_backward* signatures (include/cgs.h), from their common pieces: cfg, P, R | the inputs | the three
 # workspaces, pointer and bytes each | dL_dout [| the three map gradients] | the output gradients | scratch, its bytes, the stream
-# [| opts [| features, C, dL_dfeatures_map, dL_dfeatures] or [| means2D_cols, det_ws, det_bytes]]
+# [| opts [| features, C, dL_dfeatures_map, dL_dfeatures [| moments, median_id, dL_ddistortion, dL_dmedian_depth]] or
+# [| means2D_cols, det_ws, det_bytes]]
 _BWD_HEAD = [C.POINTER(RasterCfg), c_int64, c_int64]
 _BWD_WS = [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
 _BWD_TAIL = [c_void_p, c_size_t, c_void_p]
@@ -105,6 +106,9 @@ SIGNATURES = {
     "cgs_raster_backward_abs": (c_int, _BWD_MAPS + _BWD_OUT + [C.c_uint32] + _BWD_FEAT),
     "cgs_raster_bwd_det_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
     "cgs_raster_backward_det": (c_int, _BWD_MAPS + _BWD_OUT + [C.c_uint32, c_int32, c_void_p, c_size_t]),
+    "cgs_raster_render_geom": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_size_t,
+                                       c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cgs_raster_backward_geom": (c_int, _BWD_MAPS + _BWD_OUT + [C.c_uint32] + _BWD_FEAT + [c_void_p] * 4),
     "cgs_raster_contrib": (c_int, [C.POINTER(RasterCfg), c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                    c_size_t, c_void_p, c_int64] + [c_void_p] * 8),
     "cgs_raster_camera_bytes": (c_size_t, [c_int64]),

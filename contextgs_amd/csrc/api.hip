@@ -588,6 +588,13 @@ int cgs_launch_contrib(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg 
                        float *acc_max_weight, int64_t *acc_pixels, int64_t *acc_top_pixels, int32_t *out_top_id,
                        float *out_top_weight, int32_t *out_count, hipStream_t stream);
 
+// ---- depth-distortion and median-depth maps (csrc/raster_geom_maps.hip) -----------------------------------------------------
+int cgs_launch_geom_maps_fwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, float *out_distortion,
+                             float *out_median_depth, int32_t *out_median_id, float *out_moments, hipStream_t stream);
+int cgs_launch_geom_maps_bwd(const cgs_raster_cfg *cfg, CgsGeom &g, CgsBin &b, CgsImg &im, const float *moments,
+                             const int32_t *median_id, const float *dL_ddistortion, const float *dL_dmedian_depth,
+                             float *dL_dmean2D_px, float *dL_dconic, float *dL_dopacity, float *dL_dz, hipStream_t stream);
+
 // The workspaces of a render the caller kept, for the passes enqueued behind it (cgs_raster_render_aux, _render_features,
 // cgs_raster_contrib): g and b zeroed, then carved where there is something to carve.  fn: the entry point's name in front of
 // the message; NULL for cgs_raster_render_aux, whose messages carry none.
@@ -686,8 +693,32 @@ extern "C" int cgs_raster_contrib(const cgs_raster_cfg *cfg, int64_t P, int64_t 
                               out_top_weight, out_count, (hipStream_t)stream_);
 }
 
+// The depth-distortion map, the median depth and its Gaussian: enqueued after the render the caller kept, exactly as
+// cgs_raster_render_aux.  Every pixel of the three maps and of out_moments [2, H, W] (what the backward needs of the forward's
+// sums) is written; zeros / -1 where nothing was blended, R == 0 included.  P == 0: nothing is enqueued.
+extern "C" int cgs_raster_render_geom(const cgs_raster_cfg *cfg, int64_t P, int64_t R, void *geom_ws, size_t geom_bytes,
+                                      void *bin_ws, size_t bin_bytes, void *img_ws, size_t img_bytes, float *out_distortion,
+                                      float *out_median_depth, int32_t *out_median_id, float *out_moments, void *stream_) {
+    const char *fn = "cgs_raster_render_geom";
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (P < 0 || R < 0) { cgs_set_error("%s: P < 0 or R < 0", fn); return CGS_ERR_ARG; }
+    if (!out_distortion || !out_median_depth || !out_median_id || !out_moments) {
+        cgs_set_error("%s: NULL output (distortion, median_depth, median_id and moments are all written)", fn);
+        return CGS_ERR_ARG;
+    }
+    if (!img_ws || (R > 0 && (!geom_ws || !bin_ws))) { cgs_set_error("%s: NULL workspace", fn); return CGS_ERR_ARG; }
+    if (P == 0) return CGS_OK;
+    CgsGeom g;
+    CgsBin b;
+    CgsImg im;
+    if ((rc = carve_kept_render(fn, cfg, P, R, geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, g, b, im))) return rc;
+    return cgs_launch_geom_maps_fwd(cfg, g, b, im, out_distortion, out_median_depth, out_median_id, out_moments,
+                                    (hipStream_t)stream_);
+}
+
 // ---- backward -----------------------------------------------------------------------------
-// One driver, raster_backward_run, behind the seven exported cgs_raster_backward* entry points (include/cgs.h): each of them
+// One driver, raster_backward_run, behind the eight exported cgs_raster_backward* entry points (include/cgs.h): each of them
 // fills a RasterBwdCall and calls it.  Nothing is enqueued on a path that returns an error.
 
 // The workspace of the bit-reproducible backward (csrc/raster_blend_rows.hip, the DET instances): base [P] (exclusive scan of
@@ -712,7 +743,8 @@ int cgs_launch_blend_bwd_det(const cgs_raster_cfg *cfg, int64_t P, int64_t R, Cg
                              float *dL_dopacity, float *dL_dcolors, float *dL_dz, float *dL_dabs_px, hipStream_t stream);
 
 // What an entry point allows (the first six fields; the table in DESIGN.md), then its arguments in the order of the longest
-// signature.  An entry point without an argument leaves it zero: no map gradients, opts == 0, no features, no det_ws.
+// signature.  An entry point without an argument leaves it zero: no map gradients, opts == 0, no features, no det_ws, no
+// distortion / median-depth gradients.
 struct RasterBwdCall {
     const char *fn;         // the entry point's name in front of the messages
     bool oldest;            // cgs_raster_backward / _ex: dL_dout is required, the forms are checked before P and R, and a NULL
@@ -737,6 +769,7 @@ struct RasterBwdCall {
     uint32_t opts;
     const float *features; int32_t C; const float *dL_dfeatures_map; float *dL_dfeatures;
     void *det_ws; size_t det_bytes;
+    const float *moments; const int32_t *median_id; const float *dL_ddistortion, *dL_dmedian_depth;    // cgs_raster_backward_geom
 };
 
 // Checks, carving, [zero fill | scan of geom.tiles], the blend backwards (colour, maps, features) into the scratch's
@@ -767,6 +800,12 @@ static int raster_backward_run(const RasterBwdCall &c) {
     }
     if (c.features && (c.C < 1 || c.C > CGS_RASTER_MAX_FEATURES)) {
         cgs_set_error("%s: %d feature channels outside 1..%d", fn, c.C, CGS_RASTER_MAX_FEATURES);
+        return CGS_ERR_ARG;
+    }
+    const bool geomaps = c.dL_ddistortion || c.dL_dmedian_depth;      // (with both NULL the two saved maps are not looked at)
+    if ((c.dL_ddistortion && !c.moments) || (c.dL_dmedian_depth && !c.median_id)) {
+        cgs_set_error("%s: dL_ddistortion needs moments and dL_dmedian_depth needs median_id (what cgs_raster_render_geom "
+                      "wrote; the one a given gradient needs is NULL)", fn);
         return CGS_ERR_ARG;
     }
     CgsRasterForms f = {nullptr, 0, 0, 0, nullptr};
@@ -832,6 +871,10 @@ static int raster_backward_run(const RasterBwdCall &c) {
                 (rc = cgs_launch_feat_bwd(cfg, g, b, im, c.features, c.C, c.dL_dfeatures_map, s.d_mean_px, s.d_conic,
                                           c.dL_dopacities, c.dL_dfeatures, stream)))
                 return rc;
+            if (geomaps && (rc = cgs_launch_geom_maps_bwd(cfg, g, b, im, c.moments, c.median_id, c.dL_ddistortion,
+                                                          c.dL_dmedian_depth, s.d_mean_px, s.d_conic, c.dL_dopacities, s.d_z,
+                                                          stream)))
+                return rc;
         }
     }
     // antialiasing: the blend backwards have summed dL/d(op_eff) into dL_dopacities by now; the per-Gaussian kernel turns it
@@ -846,7 +889,7 @@ static int raster_backward_run(const RasterBwdCall &c) {
                                             c.dL_dcolors, c.dL_dmeans3D, c.dL_dmeans2D, c.dL_dshs, c.dL_dscales, c.dL_drotations,
                                             c.dL_dcov3D, stream, aa_op, aa_dop, d_abs);
     if (rc) return rc;
-    return aux ? cgs_launch_aux_dz_chain(cfg, P, c.radii, s.d_z, c.dL_dmeans3D, stream) : CGS_OK;
+    return (aux || geomaps) ? cgs_launch_aux_dz_chain(cfg, P, c.radii, s.d_z, c.dL_dmeans3D, stream) : CGS_OK;
 }
 
 extern "C" int cgs_raster_backward(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D,
@@ -950,6 +993,29 @@ extern "C" int cgs_raster_backward_abs(const cgs_raster_cfg *cfg, int64_t P, int
                              geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout, dL_ddepth, dL_dinvdepth, dL_dalpha,
                              dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D,
                              scratch, scratch_bytes, stream_, opts, features, C, dL_dfeatures_map, dL_dfeatures};
+    return raster_backward_run(c);
+}
+
+// cgs_raster_backward_abs plus the gradients of the distortion and median-depth maps: their blend backward
+// (csrc/raster_geom_maps.hip) adds into the same scratch, dL_dopacities and dL/dz behind the other blends.  With both gradients
+// NULL: cgs_raster_backward_abs's result.
+extern "C" int cgs_raster_backward_geom(const cgs_raster_cfg *cfg, int64_t P, int64_t R, const float *means3D, const float *colors,
+                                        const float *shs, int32_t sh_degree, int32_t sh_coeffs, const float *opacities,
+                                        const float *scales, const float *rotations, const float *cov3D, const int32_t *radii,
+                                        void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes, void *img_ws,
+                                        size_t img_bytes, const float *dL_dout, const float *dL_ddepth, const float *dL_dinvdepth,
+                                        const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                        float *dL_dopacities, float *dL_dshs, float *dL_dscales, float *dL_drotations,
+                                        float *dL_dcov3D, void *scratch, size_t scratch_bytes, void *stream_, uint32_t opts,
+                                        const float *features, int32_t C, const float *dL_dfeatures_map, float *dL_dfeatures,
+                                        const float *moments, const int32_t *median_id, const float *dL_ddistortion,
+                                        const float *dL_dmedian_depth) {
+    const RasterBwdCall c = {"cgs_raster_backward_geom", false, true, false, BWD_SCRATCH_ABS, 4,
+                             cfg, P, R, means3D, colors, shs, sh_degree, sh_coeffs, opacities, scales, rotations, cov3D, radii,
+                             geom_ws, geom_bytes, bin_ws, bin_bytes, img_ws, img_bytes, dL_dout, dL_ddepth, dL_dinvdepth, dL_dalpha,
+                             dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D,
+                             scratch, scratch_bytes, stream_, opts, features, C, dL_dfeatures_map, dL_dfeatures, nullptr, 0,
+                             moments, median_id, dL_ddistortion, dL_dmedian_depth};
     return raster_backward_run(c);
 }
 

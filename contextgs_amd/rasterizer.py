@@ -128,6 +128,35 @@ gradients as before.  Summed with float atomics like the signed gradient: not bi
 keyword, or the keyword with any other shape, raises ValueError before a device is touched; without the flag the call enqueues
 exactly what it did before.  densify.training_statis accumulates ||grad[:, 2:4]|| when it is handed a [P,4] gradient.
 
+`forward(..., return_geometry=True)` returns the two maps people regularise and measure geometry with, `(color, radii, extras)`
+with `extras["distortion"]` and `extras["median_depth"]` float32 [1,H,W] and `extras["median_id"]` int32 [H,W]
+(csrc/raster_geom_maps.hip, cgs_raster_render_geom: one more walk of the view's tile lists).  For pixel p the contributors
+i = 1..n are exactly those of the colour blend, front to back: the same order, the same alpha_i = min(0.99, o_i exp(power)), the
+same skip below 1/255, each pixel stopping where the colour pass stopped it (n_contrib), with antialiasing the same opacity * h.
+Let T_1 = 1, T_{i+1} = T_i (1 - alpha_i), w_i = alpha_i T_i, z_i the view-space depth of Gaussian i's centre (the value
+`return_aux` blends), A_i = sum_{k<=i} w_k and D_i = sum_{k<=i} w_k z_k:
+
+  distortion[p]   = 2 sum_i w_i (z_i A_{i-1} - D_{i-1})
+  median_depth[p] = z_m,  m = the first contributor with T_m (1 - alpha_m) < 0.5;   0 where no contributor crosses
+  median_id[p]    = index of m in the call's Gaussian order (int32), -1 where none
+
+The distortion is Mip-NeRF 360's distortion loss as 2DGS, gsplat (`distloss`), GOF and RaDe-GS render it, defined by this running
+sum as gsplat defines it; the lists are sorted by the float bits of z, so z is non-decreasing along a list and the sum equals
+sum_{i,j} w_i w_j |z_i - z_j|.  It is in depth units, homogeneous of degree 1 in z, not normalised (divide by a scene scale if
+you want) and the background contributes nothing.  The median depth is the depth mesh extraction and depth evaluation use: the
+expected depth depth / alpha smears across occlusion edges.  Gradients of the distortion, with
+e_i = 2 [z_i A_{i-1} - D_{i-1} + (D_n - D_i) - z_i (A_n - A_i)]: through the weights it is the colour blend's backward with the
+per-pixel scalar "colour" e_i over a zero background, d/dalpha_i = T_i e_i - (sum_{k>i} e_k w_k) / (1 - alpha_i), reaching
+means2D, opacities, means3D and scales / rotations or cov3D_precomp; directly through z, d/dz_i = 2 w_i (A_{i-1} - (A_n - A_i)),
+chained to means3D through the view matrix as the maps' dL/dz; shs and colors_precomp get none.  The median depth sends
+dL/dz_m += g[p] to the chosen Gaussian and nothing else (the choice is not differentiable); median_id is not differentiable.
+The keyword combines with all four argument forms, antialiasing, return_aux, features, contrib, absgrad (the new share goes to
+the signed columns only, as for the other maps) and camera gradients, and stays the one autograd node: the forward's sums the
+backward needs (`moments` [2,H,W]) are saved and not returned, and the backward is cgs_raster_backward_geom when one of the two
+maps got a gradient; when neither did, no geometry backward kernel runs and the backward is the one of a call without the
+keyword.  Float atomics like the other side passes: not bit-reproducible.  Without the keyword the call enqueues exactly what it
+did before.
+
 `forward(..., deterministic=True)` makes the backward bit-reproducible.  The forward already is (no atomics in the blend, a
 stable depth sort, binnings that leave the same lists); the default backward sums every Gaussian's partial gradients with float
 atomics, in LDS inside a tile and in global memory across tiles, in the order of arrival.  With the flag the backward is
@@ -138,8 +167,8 @@ Gaussian's slots in an order that depends on its tile count only.  Every gradien
 from call to call for the same input bits, library build and device model, whichever binning ran, with or without pair-count
 speculation, whatever else the device does; the values are the default backward's up to the order of the sums.  All four
 argument forms, antialiasing, absgrad and camera gradients are covered; the forward is untouched.  NOT covered, and refused with
-ValueError before a device is touched: return_aux, features and contrib (the map and feature blends' backward and
-GaussianContrib.weight are separate kernels that sum with float atomics).  `deterministic=None` (the default) reads the
+ValueError before a device is touched: return_aux, features, contrib and return_geometry (the map, feature and geometry blends'
+backward and GaussianContrib.weight are separate kernels that sum with float atomics).  `deterministic=None` (the default) reads the
 environment variable CGS_RASTER_DETERMINISTIC (1 = on), so that a training script that never heard of the keyword can be
 switched; without the flag the call enqueues exactly what it did before.  The mode costs a workspace of 48 bytes per
 (Gaussian, tile) pair and time (DESIGN.md sections 4 and 7 have the numbers).
@@ -341,7 +370,7 @@ def check_absgrad(means2D, absgrad, P) -> None:
         raise ValueError(f"means2D is {shape}: four columns are the layout of absgrad=True, which was not given")
 
 
-def check_deterministic(deterministic, return_aux=False, features=None, contrib=None) -> bool:
+def check_deterministic(deterministic, return_aux=False, features=None, contrib=None, return_geometry=False) -> bool:
     """The resolved `deterministic` flag (None: the environment variable CGS_RASTER_DETERMINISTIC, 1 = on).  With the flag on,
     the keywords whose backward or accumulation still sums with float atomics are refused; no device is touched.  With the flag
     off nothing is checked."""
@@ -354,6 +383,9 @@ def check_deterministic(deterministic, return_aux=False, features=None, contrib=
         if given:
             raise ValueError(f"deterministic=True does not cover {name}: the depth / alpha map blends, the feature blend and "
                              f"GaussianContrib.weight sum with float atomics (not covered: return_aux, features, contrib)")
+    if return_geometry:
+        raise ValueError("deterministic=True does not cover return_geometry: the distortion / median-depth blend's backward sums "
+                         "with float atomics (not covered: return_aux, features, contrib, return_geometry)")
     return True
 
 
@@ -421,14 +453,16 @@ def check_contrib(contrib, contrib_slots, means3D) -> None:
 
 
 def launch_backward(cfg, P, R, inputs, D, M, workspaces, g, maps, grads, stream, opts=0, absgrad=False, deterministic=False,
-                    features=None):
+                    features=None, geometry=None):
     """The one cgs_raster_backward* call of a view, for both autograd nodes (_RasterizeGaussians, renderer._ExpandRasterize).
     inputs: (means3D, colors, shs, opacities, scales, rotations, cov3D, radii), None for what the form does not have;
     workspaces: (geom, binning or None, img) and R the count the binning workspace was carved with; g, maps: the upstream
     gradients of the colour image and of the depth / inverse-depth / alpha maps (None: no gradient); grads: (dL_dmeans3D,
     dL_dmeans2D [P, 4 with absgrad else 3], dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D), the
     caller's buffers (dL_dcolors / dL_dopacities zero-filled unless `deterministic`); features: (features, the feature map's
-    gradient, dL_dfeatures zero-filled) or None.  The entry point: deterministic -> _det (the colour image alone); absgrad ->
+    gradient, dL_dfeatures zero-filled) or None; geometry: (moments, median_id, the distortion map's gradient, the median-depth
+    map's gradient) when one of the two got a gradient, else None (dL_dmeans2D is then [P, 4] whatever `absgrad`).  The entry
+    point: geometry -> _geom; deterministic -> _det (the colour image alone); absgrad ->
     _abs, whatever got a gradient; maps, an option bit or a feature-map gradient -> _feat (without features it is
     cgs_raster_backward_opt's); otherwise the colour image alone -> _ex (cgs_raster_backward for colours + scales / rotations).
     Returns the scratch, which cgs_raster_camera_backward reads, and the `opts` to call that with."""
@@ -443,7 +477,10 @@ def launch_backward(cfg, P, R, inputs, D, M, workspaces, g, maps, grads, stream,
     tail = (opts, p(feat), feat.shape[1] if feat is not None else 0, p(g_fmap), p(d_feat))
     # (every scratch but _ex's begins with cgs_raster_backward_opt's; _det writes its dL/dz zero)
     cam_opts = opts | CGS_RASTER_CAMERA_MAPS
-    if deterministic:
+    if geometry is not None:
+        name, scratch_bytes = "cgs_raster_backward_geom", L.cgs_raster_bwd_abs_scratch_bytes(P)
+        tail += tuple(p(t) for t in geometry)
+    elif deterministic:
         name, scratch_bytes = "cgs_raster_backward_det", L.cgs_raster_bwd_abs_scratch_bytes(P)
     elif absgrad:
         name, scratch_bytes = "cgs_raster_backward_abs", L.cgs_raster_bwd_abs_scratch_bytes(P)
@@ -477,13 +514,16 @@ class _RasterizeGaussians(torch.autograd.Function):
     top_id / top_weight / count maps as three non-differentiable outputs behind the aux maps (cgs_raster_contrib).
     With `absgrad` the forward is unchanged and the backward is cgs_raster_backward_abs whatever got a gradient: means2D's
     gradient is [P,4], the signed columns and the absolute sums of the colour image's per-pixel terms (module docstring).
-    With `deterministic` (never together with aux, features or contrib) the forward is unchanged and the backward is
-    cgs_raster_backward_det: no float atomics, bit-reproducible gradients (module docstring)."""
+    With `deterministic` (never together with aux, features, contrib or geometry) the forward is unchanged and the backward is
+    cgs_raster_backward_det: no float atomics, bit-reproducible gradients (module docstring).
+    With `geometry` one more walk gives the distortion and median-depth maps and the non-differentiable median_id behind the
+    contrib maps (cgs_raster_render_geom); its moments and median_id are saved, and when one of the two maps got a gradient the
+    backward is cgs_raster_backward_geom (module docstring)."""
 
     @staticmethod
     def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings,
                 viewmatrix, projmatrix, campos, features=None, contrib=None, contrib_slots=None, absgrad=False,
-                deterministic=False):
+                deterministic=False, geometry=False):
         # viewmatrix / projmatrix / campos: the settings' three camera tensors once more, as inputs of the node so that autograd
         # can hand them a gradient; the forward reads them through _Cfg as before
         L = _lib.lib()
@@ -534,6 +574,19 @@ class _RasterizeGaussians(torch.autograd.Function):
             contrib.views += 1
             outs += (top_id, top_w, count)
             nondiff += (top_id, top_w, count)
+        geom_saved = ()
+        if geometry:    # likewise; every pixel is written (P == 0: the call enqueues nothing, the fills below stand)
+            new = torch.empty if P > 0 else torch.zeros
+            gmaps = [new(1, H, W, dtype=torch.float32, device=dev) for _ in range(2)]
+            med_id = new(H, W, dtype=torch.int32, device=dev) if P > 0 else torch.full((H, W), -1, dtype=torch.int32, device=dev)
+            moments = new(2, H, W, dtype=torch.float32, device=dev)
+            _lib.check(L.cgs_raster_render_geom(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws), binws.numel(),
+                                                _lib.ptr(img), img.numel(), _lib.ptr(gmaps[0]), _lib.ptr(gmaps[1]),
+                                                _lib.ptr(med_id), _lib.ptr(moments), stream), "cgs_raster_render_geom")
+            ctx.geom_at = len(outs) - 2       # where the two maps' gradients sit in the backward's *grad_rest
+            outs += (gmaps[0], gmaps[1], med_id)
+            nondiff += (med_id,)
+            geom_saved = (moments, med_id)
         if feat is not None:    # likewise; every pixel is written
             fmap = torch.empty(feat.shape[1], H, W, dtype=torch.float32, device=dev)
             _lib.check(L.cgs_raster_render_features(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
@@ -543,28 +596,31 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.cfg, ctx.num_rendered, ctx.D, ctx.M, ctx.opts, ctx.aux = cfg, bin_R, D, M, opts, bool(aux)
         ctx.absgrad = bool(absgrad)
         ctx.deterministic = bool(deterministic)
-        ctx.save_for_backward(means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat)
+        ctx.geometry = bool(geometry)
+        ctx.save_for_backward(means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat, *geom_saved)
         ctx.mark_non_differentiable(*nondiff)      # ONE call: torch keeps only the last call's arguments
         return outs
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, *grad_rest):
         L = _lib.lib()
-        means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat = ctx.saved_tensors
+        means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat, *geom_saved = ctx.saved_tensors
         grad_maps = grad_rest[:3] if ctx.aux else ()
+        g_geom = [None if t is None else _f32c(t) for t in grad_rest[ctx.geom_at:ctx.geom_at + 2]] if ctx.geometry else []
+        with_geom = any(t is not None for t in g_geom)       # (neither map got a gradient: the backward of a call without them)
         g_fmap = _f32c(grad_rest[-1]) if (feat is not None and grad_rest[-1] is not None) else None
         cfg = ctx.cfg
         P = means3D.shape[0]
         dev = means3D.device
         g, *maps = (None if t is None else _f32c(t) for t in (grad_color, *grad_maps, None, None, None)[:4])
-        if g is None and g_fmap is None and all(t is None for t in maps):
-            return (None,) * 18
+        if g is None and g_fmap is None and all(t is None for t in maps) and not with_geom:
+            return (None,) * 19
         # the blends accumulate dL/dcolor (read by the SH backward) and dL/dopacity atomically: one zero fill for both; the
         # other arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones).  The deterministic
         # backward writes every row of both itself.
         acc = (torch.empty if ctx.deterministic else torch.zeros)(P * 4, dtype=torch.float32, device=dev)
         d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
-        m2 = 4 if ctx.absgrad else 3        # columns of dL/dmeans2D
+        m2 = 4 if (ctx.absgrad or with_geom) else 3     # columns of dL/dmeans2D (cgs_raster_backward_geom: always four)
         rest = torch.empty(P * (3 + m2 + (7 if cov is None else 6)), dtype=torch.float32, device=dev)
         d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:(3 + m2) * P].view(P, m2)
         d_scales = rest[(3 + m2) * P:(6 + m2) * P].view(P, 3) if cov is None else None
@@ -577,7 +633,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         scratch, cam_opts = launch_backward(
             cfg, P, ctx.num_rendered, (means3D, colors, shs, opac, scales, rots, cov, radii), ctx.D, ctx.M, (geom, binws, img),
             g, maps, (d_means3D, d_means2D, d_colors, d_opac, d_shs, d_scales, d_rots, d_cov), stream, ctx.opts, ctx.absgrad,
-            ctx.deterministic, (feat, g_fmap, d_feat) if with_feat else None)
+            ctx.deterministic, (feat, g_fmap, d_feat) if with_feat else None, (*geom_saved, *g_geom) if with_geom else None)
         # the camera: only when one of its tensors asks (campos without shs is unused: None), behind the backward above while
         # its scratch and its dL_dcolors / dL_dopacities are intact
         need_v, need_p, need_c = ctx.needs_input_grad[10:13]
@@ -596,8 +652,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _lib.ptr(d_campos), _lib.ptr(work), work.numel(), stream), "cgs_raster_camera_backward")
         if g is None:       # the maps and the features send no gradient to the colour inputs
             d_shs = d_colors = None
+        if with_geom and not ctx.absgrad:       # means2D is [P, 3]: the signed columns and the zero every [P, 3] backward writes
+            d_means2D = torch.nn.functional.pad(d_means2D[:, :2], (0, 1))
         return (None, d_means3D, d_means2D, d_shs, d_colors if colors is not None else None, d_opac, d_scales, d_rots,
-                d_cov, None, d_view, d_proj, d_campos, d_feat, None, None, None, None)
+                d_cov, None, d_view, d_proj, d_campos, d_feat, None, None, None, None, None)
 
 
 def _camera_inputs(rs):
@@ -653,14 +711,15 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, features=None, return_aux=False, contrib=None, contrib_slots=None, absgrad=False,
-                deterministic=None):
+                deterministic=None, return_geometry=False):
         """(color [3,H,W], radii int32 [P]); with return_aux=True, features [P,C] and / or contrib a third value, the dict of
         {"depth", "invdepth", "alpha"}, float32 [1,H,W] each, {"features"}, float32 [C,H,W], and / or {"contrib", "top_id",
         "top_weight", "count"} (see the module docstring).  absgrad=True: means2D is [P,4] and its gradient's columns 2:4 are
         the sums over the pixels of the absolute per-pixel gradients of the colour image (module docstring).
         deterministic=True (None: CGS_RASTER_DETERMINISTIC=1): a bit-reproducible backward without float atomics; not with
-        return_aux, features or contrib (module docstring)."""
-        deterministic = check_deterministic(deterministic, return_aux, features, contrib)
+        return_aux, features, contrib or return_geometry (module docstring).  return_geometry=True: the dict gains
+        {"distortion", "median_depth"}, float32 [1,H,W], and {"median_id"}, int32 [H,W] (module docstring)."""
+        deterministic = check_deterministic(deterministic, return_aux, features, contrib, return_geometry)
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
         check_absgrad(means2D, absgrad, means3D.shape[0])
         check_features(features, means3D.shape[0])
@@ -672,8 +731,9 @@ class GaussianRasterizer(nn.Module):
         out = _RasterizeGaussians.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                         cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings), features,
                                         contrib, contrib_slots,
-                                        *((bool(absgrad), True) if deterministic else (True,) if absgrad else ()))
-        if not return_aux and features is None and contrib is None:
+                                        *((bool(absgrad), False, True) if return_geometry else (bool(absgrad), True) if deterministic
+                                          else (True,) if absgrad else ()))
+        if not return_aux and features is None and contrib is None and not return_geometry:
             return out
         extras = {}
         if return_aux:
@@ -681,6 +741,9 @@ class GaussianRasterizer(nn.Module):
         if contrib is not None:
             k = 5 if return_aux else 2
             extras.update(contrib=contrib, top_id=out[k], top_weight=out[k + 1], count=out[k + 2])
+        if return_geometry:
+            k = 2 + (3 if return_aux else 0) + (3 if contrib is not None else 0)
+            extras.update(distortion=out[k], median_depth=out[k + 1], median_id=out[k + 2])
         if features is not None:
             extras["features"] = out[-1]
         return out[0], out[1], extras

@@ -606,7 +606,8 @@ class _DetachedCamera:
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False,
-           step=0, *, return_aux=False, anchor_features=None, contrib=None, absgrad=False, deterministic=None):   # :155-229
+           step=0, *, return_aux=False, anchor_features=None, contrib=None, absgrad=False, deterministic=None,
+           return_geometry=False):   # :155-229
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
 
     return_aux=True: the dict also holds the rasterizer's "depth", "invdepth" and "alpha" maps ([1,H,W] each, see
@@ -625,6 +626,12 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     anchors outside `visible_mask` and of offsets the selection mask drops are not touched.  Nothing of it is differentiable.
     In training mode such a call takes the unfused path, as return_aux does.
 
+    return_geometry=True: the dict also holds the rasterizer's "distortion" and "median_depth" maps ([1,H,W] each; the
+    depth-distortion regulariser and the depth at which a ray's accumulated opacity crosses one half) and "median_id" int32
+    [H,W], the index of that Gaussian among the view's neural Gaussians (the order of "radii"), -1 where there is none
+    (rasterizer.py has the definitions and the gradients).  In training mode such a call takes the unfused path, as return_aux
+    does.
+
     absgrad=True: "viewspace_points" is created [P,4] and its gradient holds the signed 2-D position gradient in columns 0:2,
     as without the flag, and in columns 2:4 the sums over the pixels of the ABSOLUTE per-pixel gradients of the colour image
     (AbsGS's densification statistic; contextgs_amd/rasterizer.py has the definition and what it excludes).  Training-mode
@@ -635,7 +642,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     without float atomics and its gradients are bit-reproducible (contextgs_amd/rasterizer.py has the contract).  Training-mode
     calls stay on the fused expand + raster node, whose backward launch is then cgs_raster_backward_det; every other path hands
     the keyword to the rasterizer; fused and unfused give the same bits.  Not covered, ValueError before a device is touched:
-    return_aux, anchor_features, contrib.  The rasterizer's gradients only: other launches of a training step still sum with
+    return_aux, anchor_features, contrib, return_geometry.  The rasterizer's gradients only: other launches of a training step still sum with
     float atomics (DESIGN.md section 8 lists them).
 
     A camera whose `world_view_transform`, `full_proj_transform` or `camera_center` requires a gradient (a trainable pose,
@@ -643,7 +650,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     tensors through the rasterizer (rasterizer.py: the projection, the covariance chain, the depth of the maps).  Not
     differentiated with respect to the camera: the anchor MLPs' input (anchor - camera_center), which is evaluated on the
     detached position, and the fused expand + raster node, which such a call never takes."""
-    deterministic = check_deterministic(deterministic, return_aux, anchor_features, contrib)
+    deterministic = check_deterministic(deterministic, return_aux, anchor_features, contrib, return_geometry)
+    return_geometry = bool(return_geometry)
     is_training = pc.get_color_mlp.training
     view = None
     cam_grad = torch.is_grad_enabled() and any(
@@ -676,8 +684,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, bit_per_anchor_param,
          bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level) = \
             generate_neural_gaussians(gen_camera, pc, visible_mask, is_training=True, step=step,
-                                      _view=None if (return_aux or view.raster_settings.antialiasing or cam_grad
-                                                     or rows is not None or slots is not None) else view,
+                                      _view=None if (return_aux or return_geometry or view.raster_settings.antialiasing
+                                                     or cam_grad or rows is not None or slots is not None) else view,
                                       _rows=rows, _slots=slots)
         if view.done is not None:
             rendered_image, radii, screenspace_points = view.done
@@ -700,10 +708,12 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     rasterizer = GaussianRasterizer(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier))
     abs_kw = dict(absgrad=True) if absgrad else {}
     abs_kw.update(deterministic=deterministic)      # (resolved above: the rasterizer does not read the environment again)
-    if return_aux or rows is not None or slots is not None:
+    if return_aux or return_geometry or rows is not None or slots is not None:
         features = anchor_features.index_select(0, rows[0]) if rows is not None else None      # plumbing: plain torch
         more = dict(contrib=contrib, contrib_slots=slots[0]) if slots is not None else {}
         more.update(abs_kw)
+        if return_geometry:
+            more.update(return_geometry=True)
         rendered_image, radii, aux = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
                                                 opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None,
                                                 features=features, return_aux=return_aux, **more)
@@ -723,7 +733,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     else:
         out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
                "radii": radii, "time_sub": time_sub}
-    if return_aux or rows is not None or slots is not None:
+    if return_aux or return_geometry or rows is not None or slots is not None:
         out.update(aux)
     return out
 

@@ -446,6 +446,72 @@ int cgs_raster_backward_det(const cgs_raster_cfg *cfg, int64_t P,
                             size_t scratch_bytes, void *stream, uint32_t opts,
                             int32_t means2D_cols, void *det_ws, size_t det_bytes);
 
+/* ---- depth-distortion and median-depth maps (csrc/raster_geom_maps.hip) ----
+ * For pixel p the contributors i = 1..n are exactly those of the colour blend, front to back: the same order, the same
+ * alpha_i = min(0.99, o_i exp(power)), the same skip below 1/255, each pixel stopping where the colour pass stopped it
+ * (n_contrib); with CGS_RASTER_ANTIALIAS the same opacity * h.  Let T_1 = 1, T_{i+1} = T_i (1 - alpha_i), w_i = alpha_i T_i,
+ * z_i the view-space depth of Gaussian i's centre (the value cgs_raster_render_aux blends), A_i = sum_{k<=i} w_k and
+ * D_i = sum_{k<=i} w_k z_k.  Then
+ *   distortion[p]   = 2 sum_i w_i (z_i A_{i-1} - D_{i-1})
+ *   median_depth[p] = z_m,  m = the first contributor with T_m (1 - alpha_m) < 0.5;   0 where no contributor crosses
+ *   median_id[p]    = index of m in the call's Gaussian order (int32), -1 where none
+ * The distortion is Mip-NeRF 360's distortion loss as 2DGS and gsplat (`distloss`) render it, DEFINED by this running sum.  The
+ * lists are sorted by the float bits of z, so z is non-decreasing along a list and the sum equals sum_{i,j} w_i w_j |z_i - z_j|.
+ * It is in depth units, homogeneous of degree 1 in z, not normalised (callers divide by a scene scale if they want), and the
+ * background contributes nothing.  The median depth is the depth mesh extraction and depth evaluation use: the expected depth
+ * depth / alpha smears across occlusion edges.
+ *
+ * Gradients of the distortion, with e_i = 2 [z_i A_{i-1} - D_{i-1} + (D_n - D_i) - z_i (A_n - A_i)] = d distortion / d w_i:
+ *   through the weights: the colour blend's backward with the per-pixel scalar "colour" e_i over a zero background,
+ *     d/dalpha_i = T_i e_i - (sum_{k>i} e_k w_k) / (1 - alpha_i), into the same opacity / 2-D mean / conic sums as the colour's;
+ *   directly through z: d/dz_i = 2 w_i (A_{i-1} - (A_n - A_i)), chained to means3D through the view matrix as the maps' dL/dz.
+ * Gradient of the median depth: dL/dz_m += g[p] for the chosen Gaussian and nothing else (the choice is not differentiable).
+ * No gradient reaches the colours or SH from either map.
+ *
+ * cgs_raster_render_geom: enqueue after the cgs_raster_render / cgs_raster_render_spec of the view whose result the caller
+ * keeps, exactly as cgs_raster_render_aux (same workspaces, same R).  Every pixel of out_distortion, out_median_depth (float
+ * [H, W]), out_median_id (int32 [H, W]) and out_moments (float [2, H, W]) is written; with R == 0 or an empty view the maps are
+ * zeros / -1.  out_moments is what the backward needs of the forward's sums and is opaque to the caller: plane 0 holds A_n,
+ * plane 1 holds D_n taken relative to the depth of the front-most entry of the pixel's tile list, D_n - z_ref A_n (the
+ * distortion does not change under a shift of z, and both kernels work on z - z_ref so that z A - D does not cancel).
+ *
+ * cgs_raster_backward_geom: the arguments, the checks and the results of cgs_raster_backward_abs (dL_dmeans2D is [P, 4]; the
+ * scratch is cgs_raster_bwd_abs_scratch_bytes(P) bytes), then moments and median_id as cgs_raster_render_geom wrote them and
+ * dL_ddistortion, dL_dmedian_depth [H, W], each of which may be NULL.  The maps' blend backward runs behind the colour, map and
+ * feature blend backwards and adds its share into the same dL/d(pixel mean), dL/d(conic), dL_dopacities and dL/dz sums, so the
+ * per-Gaussian backward, antialiasing's opacity chain and cgs_raster_camera_backward (CGS_RASTER_CAMERA_MAPS) see it without
+ * knowing of it; the share goes to the signed columns of dL_dmeans2D only.  With both gradients NULL the result is
+ * cgs_raster_backward_abs's and neither moments nor median_id is read.  Summed with float atomics: not bit-reproducible.
+ *
+ * CGS_ERR_ARG with a message that names the function, before anything is enqueued: a NULL workspace or output, P < 0 or R < 0,
+ * dL_ddistortion without moments, dL_dmedian_depth without median_id.  A short workspace: CGS_ERR_WORKSPACE.  P == 0: CGS_OK,
+ * nothing enqueued (cgs_raster_render_geom then leaves its outputs to the caller). */
+int cgs_raster_render_geom(const cgs_raster_cfg *cfg, int64_t P, int64_t num_rendered,
+                           void *geom_ws, size_t geom_bytes, void *bin_ws, size_t bin_bytes,
+                           void *img_ws, size_t img_bytes, float *out_distortion,
+                           float *out_median_depth, int32_t *out_median_id,
+                           float *out_moments, void *stream);
+int cgs_raster_backward_geom(const cgs_raster_cfg *cfg, int64_t P,
+                             int64_t num_rendered, const float *means3D,
+                             const float *colors, const float *shs,
+                             int32_t sh_degree, int32_t sh_coeffs,
+                             const float *opacities, const float *scales,
+                             const float *rotations, const float *cov3D,
+                             const int32_t *radii, void *geom_ws, size_t geom_bytes,
+                             void *bin_ws, size_t bin_bytes, void *img_ws,
+                             size_t img_bytes, const float *dL_dout,
+                             const float *dL_ddepth, const float *dL_dinvdepth,
+                             const float *dL_dalpha, float *dL_dmeans3D,
+                             float *dL_dmeans2D, float *dL_dcolors,
+                             float *dL_dopacities, float *dL_dshs,
+                             float *dL_dscales, float *dL_drotations,
+                             float *dL_dcov3D, void *scratch,
+                             size_t scratch_bytes, void *stream, uint32_t opts,
+                             const float *features, int32_t C,
+                             const float *dL_dfeatures_map, float *dL_dfeatures,
+                             const float *moments, const int32_t *median_id,
+                             const float *dL_ddistortion, const float *dL_dmedian_depth);
+
 /* ---- per-Gaussian contribution statistics and top-contributor maps (csrc/raster_contrib.hip) ----
  * The reverse direction of the maps above: how much each Gaussian mattered to the view (importance pruning, covisibility,
  * picking).  For pixel p the contributors i are exactly those of the colour blend (same order, same alpha, same skip below
