@@ -13,6 +13,12 @@
 //                     weight gradients dW1 = dZ1^T [X | 1] (row contraction on the matrix cores, 140 accumulator registers
 //                     per lane) and dW2[step rows] = [H | 1]^T d qadj (28 more): one wave per SIMD, the unified 512-register file —
 //                     the shape of mlp3_bwd_wg_kernel (mlp3.hip).  dZ1 never exists in memory.
+//   <., HS = true>    the hidden layer's hand-over: the forward also writes H = relu(W1 X + b1) and tanh(qadj) as they stand in its
+//                     registers (fragment-major, 416 B per row), the backward reads them instead of running the forward's chain again:
+//                     308 instead of 448 MFMAs per tile, no step-size head.  The forward is bound by its bytes and pays for the
+//                     stores, the backward hides the loads: -84 / +44 us per launch at IN 71 in the step, a wash at IN 15
+//                     (profiles/ctxl_hidden_handover.txt).  cgs_ctx_level_fwd_h / _bwd_h; the HS = false instances are the kernels
+//                     as they were.
 //
 // Every global operand goes through RAW BUFFER loads / stores (hardware bounds check): a lane that has nothing to load — a row
 // past the end, a piece another lane group owns, a row outside the rate subset — issues the same instruction with an
@@ -26,6 +32,7 @@
 #include "buf_access.h"
 #include "ctx_rows.h"
 #include "ctx_noise.h"
+#include <type_traits>
 
 
 // ---- the MLP input row ---------------------------------------------------------------------------------------
@@ -206,11 +213,21 @@ struct ClFwdArgs {
     float *yf, *ys, *yo, *Q;                 // [n,50] [n,6] [n,30] [n,3]
     double *sums;                            // may be NULL (ctx_noise.h)
 };
+struct ClFwdArgsH : ClFwdArgs { float *H; };  // HS: + the hidden layer's hand-over to the backward (CL_HT_BYTES per 16-row tile)
 
 struct ClfIdx { int64_t arow, ppos, srow; };
 
-template <int IN>
-__global__ void __launch_bounds__(CLF_WAVES * 64) ctxl_fwd_kernel(ClFwdArgs a) {
+// The hidden layer's hand-over from the forward to the backward (private to this file), fragment-major like mlp3's Hcat: per 16-row
+// tile the hidden tiles t = 0..5 as six 1 KB fragments in LANE order (lane 16 g + c -> its acc1[t], 16 bytes: one contiguous store /
+// load instruction per fragment), then 512 bytes of tile 6: units 96..99 of row c from lane (0, c) at 16 c, and (tanh(qadj 0..2), 0)
+// of row c from lane (1, c) at 256 + 16 c.  WHOLE tiles: the rows past n of the last tile hold what their zero input rows give (the
+// backward multiplies them by d qadj = 0 inside an MFMA, where 0 x NaN would be NaN).
+#define CL_HT_BYTES (6 * 1024 + 512)
+
+// HS: + the hidden layer's hand-over (a.H).  A template parameter, not a NULL test or a zero-size buffer: the seven dropped store
+// instructions and their registers cost the plain forward 24 us per launch at 500 k rows (profiles/ctxl_hidden_handover.txt).
+template <int IN, bool HS>
+__global__ void __launch_bounds__(CLF_WAVES * 64) ctxl_fwd_kernel(typename std::conditional<HS, ClFwdArgsH, ClFwdArgs>::type a) {
     constexpr int NTI = ClShape<IN>::NTI, XP = ClShape<IN>::XP;
     __shared__ __attribute__((aligned(16))) float W1s[CL_W1T(XP)];        // cl_stage_w1t
     __shared__ float b1s[CL_HP];
@@ -237,6 +254,8 @@ __global__ void __launch_bounds__(CLF_WAVES * 64) ctxl_fwd_kernel(ClFwdArgs a) {
     const ClRowBufs XB = {cl_buf(a.xf, NA * CL_D * 4), cl_buf(a.xs, NA * CL_S * 4), cl_buf(a.xo, NA * CL_O * 4)};
     const ClRowBufs YB = {cl_buf(a.yf, nb * CL_D * 4), cl_buf(a.ys, nb * CL_S * 4), cl_buf(a.yo, nb * CL_O * 4)};
     const ClBuf bX = cl_buf(a.X, nb * IN * 4), bQ = cl_buf(a.Q, nb * 12);
+    ClBuf bH = bX;
+    if constexpr (HS) bH = cl_buf(a.H, (uint64_t)ntiles * CL_HT_BYTES);
     const ClBuf bAr = cl_buf(a.a_rows, nb * 8), bPos = cl_buf(a.pos, nb * 8), bRows = cl_buf(a.rows, nb * 8);
     const uint32_t kf = ctx_noise_key(a.seed, 0), ks = ctx_noise_key(a.seed, 1), ko = ctx_noise_key(a.seed, 2);
     const int64_t tstride = (int64_t)gridDim.x * CLF_WAVES;
@@ -279,9 +298,24 @@ __global__ void __launch_bounds__(CLF_WAVES * 64) ctxl_fwd_kernel(ClFwdArgs a) {
         cl_xrow_store_tile<IN>(bX, patch, (uint32_t)(tile * 16), g, c, lane, xb);
         f32x4 acc1[CL_NT1];
         cl_layer1<IN>(W1s, b1s, xb, g, c, acc1);
+        const uint32_t hb = (uint32_t)tile * CL_HT_BYTES + (uint32_t)lane * 16;
+        if constexpr (HS) {       // the hand-over: H as it stands in the registers (tile 6 with the tanh values below)
+#pragma unroll
+            for (int t = 0; t < CL_NT1 - 1; ++t) cl_s128(bH, hb + (uint32_t)t * 1024, acc1[t]);
+            CL_FENCE();
+        }
         float qa[3];
         cl_qadj(W2qs, b2qs, acc1, g, qa);
-        const float qf = ctx_step(a.q0f, qa[0]), qs = ctx_step(a.q0s, qa[1]), qo = ctx_step(a.q0o, qa[2]);
+        float qf, qs, qo;
+        if constexpr (!HS) {
+            qf = ctx_step(a.q0f, qa[0]); qs = ctx_step(a.q0s, qa[1]); qo = ctx_step(a.q0o, qa[2]);
+        } else {
+            // ctx_step (ctx_noise.h) with its tanh taken once: the backward wants the same value
+            const f32x4 tq = (f32x4){tanhf(qa[0]), tanhf(qa[1]), tanhf(qa[2]), 0.f};
+            qf = fmaxf(a.q0f * (1.f + tq[0]), 1e-9f); qs = fmaxf(a.q0s * (1.f + tq[1]), 1e-9f); qo = fmaxf(a.q0o * (1.f + tq[2]), 1e-9f);
+            cl_s128(bH, cl_sel(g < 2, hb + (CL_NT1 - 1) * 1024), g == 0 ? acc1[CL_NT1 - 1] : tq);
+            CL_FENCE();
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) pf += cl_sum4(xc.F[i]);
         ps += cl_sum4(xc.S);
@@ -334,6 +368,7 @@ struct ClBwdArgs {
     uint64_t seed;
     float q0f, q0s, q0o;
 };
+struct ClBwdArgsH : ClBwdArgs { const float *H; };   // HS: + the forward's hand-over (CL_HT_BYTES per tile)
 
 __device__ __forceinline__ void clb_put(float *patch, f32x4 v, int g, int c) { *(f32x4 *)(patch + c * CLB_LD + 4 * g) = v; }
 __device__ __forceinline__ f32x4 clb_get(const float *patch, int g, int c) {
@@ -399,8 +434,13 @@ __device__ __forceinline__ void clb_dx_and_sums(const ClRow &dy, const ClRow &sd
     af += __shfl_xor(af, 32); as += __shfl_xor(as, 32); ao += __shfl_xor(ao, 32);
 }
 
-template <int IN>
-__global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_per_eu(1, 1))) ctxl_bwd_kernel(ClBwdArgs a) {
+// HS = false: the hidden layer and the step-size head are recomputed from X (the forward's chain, the forward's bits).
+// HS = true: they come from the forward's hand-over buffer — no cl_layer1, no cl_qadj, no tanhf, no W1t image; the H fragments of
+// the next tile are requested with its dy (before the dW1 products), X — now wanted by the dW1 product alone — at the top of its
+// own tile.  Every remaining product and sum is the same instruction sequence on the same bits.
+template <int IN, bool HS>
+__global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+ctxl_bwd_kernel(typename std::conditional<HS, ClBwdArgsH, ClBwdArgs>::type a) {
     constexpr int NTI = ClShape<IN>::NTI, XP = ClShape<IN>::XP;
     constexpr int NPATCH = CL_NT1 + NTI;                     // per wave: H, then dZ1 0..6, X 7..
     // LDS: W1t (layer 1, cl_stage_w1t) | W1n4 [h][c][4]: W1[h][16 v + c], v < 4 | W1n1 [h][c]: W1[h][64 + c] | b1 | W2q | b2q
@@ -413,15 +453,17 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
     __shared__ __attribute__((aligned(16))) float lds[WF + PF];
     float *W1s = lds, *W1n4 = W1s + CL_W1T(XP), *W1n1 = W1n4 + N4, *b1s = W1n1 + N1, *W2qs = b1s + CL_HP, *b2qs = W2qs + 3 * CL_HP;
     const int tid = threadIdx.x, nthr = CLB_WAVES * 64;
-    cl_stage_w1t<IN>(W1s, a.W1, tid, nthr);
+    if constexpr (!HS) cl_stage_w1t<IN>(W1s, a.W1, tid, nthr);
     frag_stage_loop(a.W1, N4, tid, nthr,
                     [](int i) { const int h = i >> 6, c_ = (i >> 2) & 15, v = i & 3, k = 16 * v + c_; return (h < CL_HID && k < IN) ? h * IN + k : -1; },
                     [&](int i, float v) { W1n4[i] = v; });
     frag_stage_loop(a.W1, N1, tid, nthr, [](int i) { const int h = i >> 4, k = 64 + (i & 15); return (h < CL_HID && k < IN) ? h * IN + k : -1; },
                     [&](int i, float v) { W1n1[i] = v; });
-    for (int i = tid; i < CL_HP; i += nthr) b1s[i] = i < CL_HID ? a.b1[i] : 0.f;
+    if constexpr (!HS)
+        for (int i = tid; i < CL_HP; i += nthr) b1s[i] = i < CL_HID ? a.b1[i] : 0.f;
     for (int i = tid; i < 3 * CL_HP; i += nthr) W2qs[i] = (i % CL_HP) < CL_HID ? a.W2q[(i / CL_HP) * CL_HID + (i % CL_HP)] : 0.f;
-    if (tid < 4) b2qs[tid] = tid < 3 ? a.b2q[tid] : 0.f;
+    if constexpr (!HS)
+        if (tid < 4) b2qs[tid] = tid < 3 ? a.b2q[tid] : 0.f;
     __syncthreads();
 
     const int lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
@@ -436,6 +478,8 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
     const ClRowBufs SDB = {cl_buf(a.side_f, M * CL_D * 4), cl_buf(a.side_s, M * CL_S * 4), cl_buf(a.side_o, M * CL_O * 4)};
     const ClBuf bSQ = cl_buf(a.side_Q, M * 12), bQe = cl_buf(a.dQ_ext, nb * 12), bRows = cl_buf(a.rows, nb * 8),
                 bMap = cl_buf(a.side_map, nb * 4), bDH = cl_buf(a.dhyp, NA * 48);
+    ClBuf bH = bX;
+    if constexpr (HS) bH = cl_buf(a.H, (uint64_t)ntiles * CL_HT_BYTES);
     const uint32_t kf = ctx_noise_key(a.seed, 0), ks = ctx_noise_key(a.seed, 1), ko = ctx_noise_key(a.seed, 2);
     const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
     // accumulators held for the whole launch (matrix-core outputs: AGPRs)
@@ -452,17 +496,27 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
     // products (its registers are those the dX chain has just released)
     auto op_issue_x = [&](ClbOps<IN> &op, int64_t row) {
         const bool v = row < n;
-        cl_xrow_load<IN>(bX, (uint32_t)row * (IN * 4), g, v, op.xb);
+        if constexpr (!HS) cl_xrow_load<IN>(bX, (uint32_t)row * (IN * 4), g, v, op.xb);
         op.srow = cl_li64(bRows, cl_sel(v, (uint32_t)row * 8));
         op.sm = __builtin_amdgcn_raw_buffer_load_b32(bMap, (int)cl_sel(v, (uint32_t)row * 4), 0, 0);
         op.dq_ext = cl_l32(bQe, cl_sel(v && g < 3, (uint32_t)row * 12 + (uint32_t)g * 4));
     };
     auto op_issue_dy = [&](ClbOps<IN> &op, int64_t row) { cl_row_issue(op.dy, DYB, (uint32_t)row, g, row < n); };
+    // HS: the lane's fragments of tile t_ of the hand-over; of tile 6, lanes g == 0 take units 96..99, the others the row's tanh values
+    f32x4 hpre[CL_NT1];
+    auto op_issue_h = [&](int64_t t_) {
+        const bool v = t_ < ntiles;
+        const uint32_t tb = (uint32_t)t_ * CL_HT_BYTES;
+#pragma unroll
+        for (int t = 0; t < CL_NT1 - 1; ++t) hpre[t] = cl_l128(bH, cl_sel(v, tb + (uint32_t)(t * 1024 + lane * 16)));
+        hpre[CL_NT1 - 1] = cl_l128(bH, cl_sel(v, tb + (uint32_t)((CL_NT1 - 1) * 1024 + (g == 0 ? 0 : 256) + c * 16)));
+    };
 
     const int64_t tstride = (int64_t)gridDim.x * CLB_WAVES;
     int64_t tile = (int64_t)blockIdx.x * CLB_WAVES + wave;
     ClbOps<IN> op;
     op_issue_x(op, tile < ntiles ? tile * 16 + c : n);
+    if constexpr (HS) op_issue_h(tile);
     op_issue_dy(op, tile < ntiles ? tile * 16 + c : n);
     for (; tile < ntiles; tile += tstride) {
         const int64_t row0 = tile * 16, row = row0 + c;
@@ -470,20 +524,30 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
         asm volatile("" ::: "memory");   // keep the LDS weight reads inside the tile loop (LICM would spill them)
         const bool chosen = has_side && valid && op.sm >= 0;
         const uint32_t sm = chosen ? (uint32_t)op.sm : 0u;
+        if constexpr (HS) cl_xrow_load<IN>(bX, (uint32_t)row * (IN * 4), g, valid, op.xb);      // wanted at the end of the tile
         // the rate subset's compact gradients of this row (needed after the first block of MFMAs)
         ClRow sd;
         cl_row_issue(sd, SDB, sm, g, chosen);
         const float sq = cl_l32(bSQ, cl_sel(chosen && g < 3, sm * 12 + (uint32_t)g * 4));
         // [X | 1] towards layout N; H^T = relu(W1 X^T + b1) (the forward's chain, the forward's bits), H towards layout N
-        cl_xrow_mask<IN>(g, op.xb);
-#pragma unroll
-        for (int q = 0; q < NTI; ++q) clb_put(patches + (CL_NT1 + q) * CLB_PATCH, op.xb[q], g, c);
         f32x4 acc1[CL_NT1];
-        cl_layer1<IN>(W1s, b1s, op.xb, g, c, acc1);
+        float qa[3], th[3];
+        if constexpr (!HS) {
+            cl_xrow_mask<IN>(g, op.xb);
+#pragma unroll
+            for (int q = 0; q < NTI; ++q) clb_put(patches + (CL_NT1 + q) * CLB_PATCH, op.xb[q], g, c);
+            cl_layer1<IN>(W1s, b1s, op.xb, g, c, acc1);
+        } else {
+            // (hidden units 100..111 of lanes g > 0: relu(0 + 0) in the recompute)
+#pragma unroll
+            for (int t = 0; t < CL_NT1 - 1; ++t) acc1[t] = hpre[t];
+            acc1[CL_NT1 - 1] = g == 0 ? hpre[CL_NT1 - 1] : zero;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) th[k] = __shfl(hpre[CL_NT1 - 1][k], 16 + c, 64);
+        }
 #pragma unroll
         for (int t = 0; t < CL_NT1; ++t) clb_put(patches + t * CLB_PATCH, acc1[t], g, c);
-        float qa[3];
-        cl_qadj(W2qs, b2qs, acc1, g, qa);
+        if constexpr (!HS) cl_qadj(W2qs, b2qs, acc1, g, qa);
         // dx = dy (+ rate side), scattered to the parameter rows; sum_c dx u per tensor
         float af, as, ao;
         clb_dx_and_sums(op.dy, sd, DXB, (uint32_t)op.srow, kf, ks, ko, row, g, valid, af, as, ao);
@@ -492,12 +556,19 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
         const float e0 = __shfl(ext, c, 64), e1 = __shfl(ext, 16 + c, 64), e2 = __shfl(ext, 32 + c, 64);
         float dq[3];
         {
-            const float t0 = tanhf(qa[0]), t1 = tanhf(qa[1]), t2 = tanhf(qa[2]);
+            float t0, t1, t2;
+            if constexpr (!HS) { t0 = tanhf(qa[0]); t1 = tanhf(qa[1]); t2 = tanhf(qa[2]); }
+            else { t0 = th[0]; t1 = th[1]; t2 = th[2]; }
             dq[0] = (valid && a.q0f * (1.f + t0) >= 1e-9f) ? (af + e0) * a.q0f * (1.f - t0 * t0) : 0.f;
             dq[1] = (valid && a.q0s * (1.f + t1) >= 1e-9f) ? (as + e1) * a.q0s * (1.f - t1 * t1) : 0.f;
             dq[2] = (valid && a.q0o * (1.f + t2) >= 1e-9f) ? (ao + e2) * a.q0o * (1.f - t2 * t2) : 0.f;
         }
         if (g == 0) *(f32x4 *)(dqp + 4 * c) = (f32x4){dq[0], dq[1], dq[2], 0.f};
+        if constexpr (HS) {       // X has arrived with the side rows (issued in front of them): towards layout N, its registers are free again
+            cl_xrow_mask<IN>(g, op.xb);
+#pragma unroll
+            for (int q = 0; q < NTI; ++q) clb_put(patches + (CL_NT1 + q) * CLB_PATCH, op.xb[q], g, c);
+        }
         // this tile's global operands are consumed: the next tile's are fetched behind ~300 MFMAs
         CLB_FENCE();
         f32x4 dxs[NTI];
@@ -587,6 +658,7 @@ __global__ void __launch_bounds__(CLB_WAVES * 64) __attribute__((amdgpu_waves_pe
         if (c == IN - 16 * (NTI - 1)) xn[NTI - 1] = ones;                 // column IN of [X | 1]
         CLB_FENCE();
         op_issue_dy(op, row + tstride * 16);
+        if constexpr (HS) op_issue_h(tile + tstride);
         CLB_FENCE();
         f32x4 dn_next = clb_get(patches, g, c);
 #pragma unroll
@@ -653,11 +725,16 @@ static bool cl_fits(int64_t rows, int64_t row_bytes) { return rows >= 0 && (uint
 // Forward of one level, every row (see the head of this file).  in_dim 71: context level — X[r] = [anchor[a_rows[r]] |
 // base_f[pos[r]] | base_s[pos[r]] | hyp[r]]; in_dim 15: first level — X[r] = [anchor[a_rows[r]] (* a_mask) | hyp[r]].
 // W2q / b2q: the LAST three rows of mlp_grid's second layer (the step-size adjustments, :1603-1608).
-extern "C" int cgs_ctx_level_fwd(int in_dim, const float *anchor, int64_t n_anchor, const int64_t *a_rows, const uint8_t *a_mask,
-                                 const float *base_f, const float *base_s, int64_t n_par, const int64_t *pos, const float *hyp,
-                                 int64_t n, const float *W1, const float *b1, const float *W2q, const float *b2q, const float *xf,
-                                 const float *xs, const float *xo, const int64_t *rows, uint64_t seed, float q0f, float q0s,
-                                 float q0o, float *X, float *yf, float *ys, float *yo, float *Q, double *sums3, void *stream) {
+// cgs_ctx_level_fwd_h: + H (may be NULL = cgs_ctx_level_fwd), cgs_ctx_level_hidden_bytes(n) bytes: the hidden layer and tanh(step-size
+// outputs) of every 16-row tile in a layout private to this file, for cgs_ctx_level_bwd_h.  Whole tiles are written.
+extern "C" size_t cgs_ctx_level_hidden_bytes(int64_t n) { return n > 0 ? (size_t)((n + 15) / 16) * CL_HT_BYTES : 0; }
+
+extern "C" int cgs_ctx_level_fwd_h(int in_dim, const float *anchor, int64_t n_anchor, const int64_t *a_rows, const uint8_t *a_mask,
+                                   const float *base_f, const float *base_s, int64_t n_par, const int64_t *pos, const float *hyp,
+                                   int64_t n, const float *W1, const float *b1, const float *W2q, const float *b2q, const float *xf,
+                                   const float *xs, const float *xo, const int64_t *rows, uint64_t seed, float q0f, float q0s,
+                                   float q0o, float *X, float *yf, float *ys, float *yo, float *Q, double *sums3, float *H,
+                                   void *stream) {
     if (n < 0 || n_anchor < 0 || n_par < 0 || (in_dim != 71 && in_dim != 15)) { cgs_set_error("ctx_level_fwd: bad args (in_dim 71 or 15)"); return CGS_ERR_ARG; }
     if (n == 0) return CGS_OK;
     if (!anchor || !a_rows || !hyp || !W1 || !b1 || !W2q || !b2q || !xf || !xs || !xo || !rows || !X || !yf || !ys || !yo || !Q ||
@@ -666,24 +743,39 @@ extern "C" int cgs_ctx_level_fwd(int in_dim, const float *anchor, int64_t n_anch
         return CGS_ERR_ARG;
     }
     // 32-bit buffer offsets (raw buffer instructions): every operand must stay below 4 GB
-    if (!cl_fits(n, in_dim * 4) || !cl_fits(n, CL_D * 4) || !cl_fits(n_anchor, CL_D * 4) || !cl_fits(n_par, CL_D * 4)) {
+    if (!cl_fits(n, in_dim * 4) || !cl_fits(n, CL_D * 4) || !cl_fits(n_anchor, CL_D * 4) || !cl_fits(n_par, CL_D * 4) ||
+        (H && !cl_fits((n + 15) / 16, CL_HT_BYTES))) {
         cgs_set_error("ctx_level_fwd: an operand exceeds 4 GB (n %lld, n_anchor %lld)", (long long)n, (long long)n_anchor);
         return CGS_ERR_ARG;
     }
-    ClFwdArgs a;
+    ClFwdArgsH a;
     a.anchor = anchor; a.a_rows = a_rows; a.a_mask = in_dim == 15 ? a_mask : nullptr; a.base_f = base_f; a.base_s = base_s; a.pos = pos;
     a.hyp = hyp; a.W1 = W1; a.b1 = b1; a.W2q = W2q; a.b2q = b2q;
     a.xf = xf; a.xs = xs; a.xo = xo; a.rows = rows; a.n = n; a.n_anchor = n_anchor; a.n_par = n_par; a.seed = seed;
     a.q0f = q0f; a.q0s = q0s; a.q0o = q0o;
-    a.X = X; a.yf = yf; a.ys = ys; a.yo = yo; a.Q = Q; a.sums = sums3;
+    a.X = X; a.yf = yf; a.ys = ys; a.yo = yo; a.Q = Q; a.sums = sums3; a.H = H;
     const int64_t tiles = (n + 15) / 16, want = (tiles + CLF_WAVES - 1) / CLF_WAVES;
     const int64_t cap = (int64_t)CLF_GRID * cl_cus();
     const unsigned grid = (unsigned)(want < cap ? want : cap);
     CgsProfScope prof(CGS_PROF_CTX_FWD, (hipStream_t)stream);
-    if (in_dim == 71) hipLaunchKernelGGL((ctxl_fwd_kernel<71>), dim3(grid), dim3(CLF_WAVES * 64), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((ctxl_fwd_kernel<15>), dim3(grid), dim3(CLF_WAVES * 64), 0, (hipStream_t)stream, a);
+    const dim3 gr(grid), bl(CLF_WAVES * 64);
+    const ClFwdArgs &a0 = a;
+    if (H) {
+        if (in_dim == 71) hipLaunchKernelGGL((ctxl_fwd_kernel<71, true>), gr, bl, 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((ctxl_fwd_kernel<15, true>), gr, bl, 0, (hipStream_t)stream, a);
+    } else if (in_dim == 71) hipLaunchKernelGGL((ctxl_fwd_kernel<71, false>), gr, bl, 0, (hipStream_t)stream, a0);
+    else hipLaunchKernelGGL((ctxl_fwd_kernel<15, false>), gr, bl, 0, (hipStream_t)stream, a0);
     CGS_CHECK_HIP(hipGetLastError());
     return CGS_OK;
+}
+
+extern "C" int cgs_ctx_level_fwd(int in_dim, const float *anchor, int64_t n_anchor, const int64_t *a_rows, const uint8_t *a_mask,
+                                 const float *base_f, const float *base_s, int64_t n_par, const int64_t *pos, const float *hyp,
+                                 int64_t n, const float *W1, const float *b1, const float *W2q, const float *b2q, const float *xf,
+                                 const float *xs, const float *xo, const int64_t *rows, uint64_t seed, float q0f, float q0s,
+                                 float q0o, float *X, float *yf, float *ys, float *yo, float *Q, double *sums3, void *stream) {
+    return cgs_ctx_level_fwd_h(in_dim, anchor, n_anchor, a_rows, a_mask, base_f, base_s, n_par, pos, hyp, n, W1, b1, W2q, b2q, xf, xs, xo,
+                               rows, seed, q0f, q0s, q0o, X, yf, ys, yo, Q, sums3, nullptr, stream);
 }
 
 extern "C" size_t cgs_ctx_level_bwd_scratch_bytes(void) { return (size_t)cl_cus() * (CL_HID * 71 + CL_HID + 3 * CL_HID + 3) * sizeof(float); }
@@ -701,6 +793,15 @@ extern "C" int cgs_ctx_level_bwd2(int in_dim, const float *X, const float *W1, c
                                   const float *side_s, const float *side_o, const float *side_Q, const float *dx_sub, float *dX,
                                   float *d_hyp_rows, float *dW1, float *db1, float *dW2q, float *db2q, void *scratch,
                                   size_t scratch_bytes, void *stream);
+// cgs_ctx_level_bwd_h: cgs_ctx_level_bwd2 + H, the hand-over cgs_ctx_level_fwd_h wrote for these rows and weights: the hidden layer
+// and the step-size head are read, not recomputed (every output has the recompute's bits).  H == NULL: cgs_ctx_level_bwd2.
+extern "C" int cgs_ctx_level_bwd_h(int in_dim, const float *X, const float *W1, const float *b1, const float *W2q,
+                                   const float *b2q, const float *dyf, const float *dys, const float *dyo, const float *dQ_ext,
+                                   int64_t n, uint64_t seed, float q0f, float q0s, float q0o, const int64_t *rows, int64_t n_anchor,
+                                   float *dxf, float *dxs, float *dxo, const int32_t *side_map, int64_t m_side, const float *side_f,
+                                   const float *side_s, const float *side_o, const float *side_Q, const float *dx_sub, float *dX,
+                                   float *d_hyp_rows, float *dW1, float *db1, float *dW2q, float *db2q, const float *H, void *scratch,
+                                   size_t scratch_bytes, void *stream);
 extern "C" int cgs_ctx_level_bwd(int in_dim, const float *X, const float *W1, const float *b1, const float *W2q,
                                  const float *b2q, const float *dyf, const float *dys, const float *dyo, const float *dQ_ext,
                                  int64_t n, uint64_t seed, float q0f, float q0s, float q0o, const int64_t *rows, int64_t n_anchor,
@@ -719,6 +820,18 @@ extern "C" int cgs_ctx_level_bwd2(int in_dim, const float *X, const float *W1, c
                                   const float *side_s, const float *side_o, const float *side_Q, const float *dx_sub, float *dX,
                                   float *d_hyp_rows, float *dW1, float *db1, float *dW2q, float *db2q, void *scratch,
                                   size_t scratch_bytes, void *stream) {
+    return cgs_ctx_level_bwd_h(in_dim, X, W1, b1, W2q, b2q, dyf, dys, dyo, dQ_ext, n, seed, q0f, q0s, q0o, rows, n_anchor, dxf, dxs, dxo,
+                               side_map, m_side, side_f, side_s, side_o, side_Q, dx_sub, dX, d_hyp_rows, dW1, db1, dW2q, db2q, nullptr,
+                               scratch, scratch_bytes, stream);
+}
+
+extern "C" int cgs_ctx_level_bwd_h(int in_dim, const float *X, const float *W1, const float *b1, const float *W2q,
+                                   const float *b2q, const float *dyf, const float *dys, const float *dyo, const float *dQ_ext,
+                                   int64_t n, uint64_t seed, float q0f, float q0s, float q0o, const int64_t *rows, int64_t n_anchor,
+                                   float *dxf, float *dxs, float *dxo, const int32_t *side_map, int64_t m_side, const float *side_f,
+                                   const float *side_s, const float *side_o, const float *side_Q, const float *dx_sub, float *dX,
+                                   float *d_hyp_rows, float *dW1, float *db1, float *dW2q, float *db2q, const float *H, void *scratch,
+                                   size_t scratch_bytes, void *stream) {
     if (n < 0 || n_anchor < 0 || m_side < 0 || (in_dim != 71 && in_dim != 15)) { cgs_set_error("ctx_level_bwd: bad args (in_dim 71 or 15)"); return CGS_ERR_ARG; }
     if (n == 0) return CGS_OK;
     if (!X || !W1 || !b1 || !W2q || !b2q || !rows || !dxf || !dxs || !dxo || !dX || !dW1 || !db1 || !dW2q || !db2q || !scratch) {
@@ -726,7 +839,8 @@ extern "C" int cgs_ctx_level_bwd2(int in_dim, const float *X, const float *W1, c
         return CGS_ERR_ARG;
     }
     if (side_map && m_side > 0 && (!side_f || !side_s || !side_o || !side_Q)) { cgs_set_error("ctx_level_bwd: side_map needs the four side arrays"); return CGS_ERR_ARG; }
-    if (!cl_fits(n, in_dim * 4) || !cl_fits(n, CL_D * 4) || !cl_fits(n_anchor, CL_D * 4) || !cl_fits(m_side, in_dim * 4)) {
+    if (!cl_fits(n, in_dim * 4) || !cl_fits(n, CL_D * 4) || !cl_fits(n_anchor, CL_D * 4) || !cl_fits(m_side, in_dim * 4) ||
+        (H && !cl_fits((n + 15) / 16, CL_HT_BYTES))) {
         cgs_set_error("ctx_level_bwd: an operand exceeds 4 GB (n %lld, n_anchor %lld)", (long long)n, (long long)n_anchor);
         return CGS_ERR_ARG;
     }
@@ -734,17 +848,22 @@ extern "C" int cgs_ctx_level_bwd2(int in_dim, const float *X, const float *W1, c
     const int64_t tiles = (n + 15) / 16, want = (tiles + CLB_WAVES - 1) / CLB_WAVES;
     int64_t grid = want < cl_cus() ? want : cl_cus();
     if ((size_t)grid * E * sizeof(float) > scratch_bytes) { cgs_set_error("ctx_level_bwd: scratch too small"); return CGS_ERR_WORKSPACE; }
-    ClBwdArgs a;
+    ClBwdArgsH a;
     const bool side = side_map != nullptr && m_side > 0;
     a.X = X; a.W1 = W1; a.b1 = b1; a.W2q = W2q; a.b2q = b2q; a.dyf = dyf; a.dys = dys; a.dyo = dyo; a.dQ_ext = dQ_ext;
     a.rows = rows; a.dxf = dxf; a.dxs = dxs; a.dxo = dxo; a.side_map = side ? side_map : nullptr; a.side_f = side ? side_f : nullptr;
     a.side_s = side ? side_s : nullptr; a.side_o = side ? side_o : nullptr; a.side_Q = side ? side_Q : nullptr;
     a.dx_sub = side ? dx_sub : nullptr; a.dX = dX; a.dhyp = d_hyp_rows; a.partial = (float *)scratch;
-    a.n = n; a.n_anchor = n_anchor; a.m = side ? m_side : 0; a.seed = seed; a.q0f = q0f; a.q0s = q0s; a.q0o = q0o;
+    a.n = n; a.n_anchor = n_anchor; a.m = side ? m_side : 0; a.seed = seed; a.q0f = q0f; a.q0s = q0s; a.q0o = q0o; a.H = H;
     {
         CgsProfScope prof(CGS_PROF_CTX_BWD, (hipStream_t)stream);
-        if (in_dim == 71) hipLaunchKernelGGL((ctxl_bwd_kernel<71>), dim3((unsigned)grid), dim3(CLB_WAVES * 64), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((ctxl_bwd_kernel<15>), dim3((unsigned)grid), dim3(CLB_WAVES * 64), 0, (hipStream_t)stream, a);
+        const dim3 gr((unsigned)grid), bl(CLB_WAVES * 64);
+        const ClBwdArgs &a0 = a;
+        if (H) {
+            if (in_dim == 71) hipLaunchKernelGGL((ctxl_bwd_kernel<71, true>), gr, bl, 0, (hipStream_t)stream, a);
+            else hipLaunchKernelGGL((ctxl_bwd_kernel<15, true>), gr, bl, 0, (hipStream_t)stream, a);
+        } else if (in_dim == 71) hipLaunchKernelGGL((ctxl_bwd_kernel<71, false>), gr, bl, 0, (hipStream_t)stream, a0);
+        else hipLaunchKernelGGL((ctxl_bwd_kernel<15, false>), gr, bl, 0, (hipStream_t)stream, a0);
         CGS_CHECK_HIP(hipGetLastError());
     }
     CgsProfScope prof(CGS_PROF_LMLP_WGRAD, (hipStream_t)stream);

@@ -815,6 +815,10 @@ def choose_rows(perm, n, mask, given, seed, thresh, anchor, anchor_ref, mask_ref
 ANCHOR_SHARED = os.environ.get("CGS_ANCHOR_SHARED", "1") != "0"      # A/B knob: 0 = one zero-filled [N,3] anchor gradient per level (rounds 5)
 HYPER_DIRECT = os.environ.get("CGS_HYPER_DIRECT", "1") != "0"        # A/B knob: 0 = the hyper latents' gradient leaves the levels as column slices of dX (gather_rows_segmented)
 PREFIX_INPLACE = os.environ.get("CGS_PREFIX_INPLACE", "1") != "0"    # A/B knob: 0 = the coded prefix's gradient as its own tensors, summed by autograd
+# A/B knob, default: the context levels' forward (in_dim 71) hands its hidden layer to the backward (cgs_ctx_level_fwd_h / _bwd_h,
+# +416 B per row kept between the two).  CGS_CTXL_KEEP_H=0: the backward recomputes it from X (cgs_ctx_level_bwd2).  The first level
+# (in_dim 15) always recomputes: its 28 layer-1 MFMAs per tile cost what the hand-over's bytes do — profiles/ctxl_hidden_handover.txt
+KEEP_H = os.environ.get("CGS_CTXL_KEEP_H", "1") != "0"
 
 
 _JOINED_GRADS = {}       # data pointer -> (rows, width) of the gradients _JoinRows' backward split this step (cleared per forward)
@@ -869,7 +873,8 @@ class _LevelFused(torch.autograd.Function):
 
     @staticmethod
     def launch(anchor, base_f, base_s, hyp, W1, b1, W2, b2, cfg):
-        """The forward's launch on plain values (no autograd): (X, Q, (W1c, b1c, W2c, b2c)).  Called by forward(), or EARLIER by
+        """The forward's launch on plain values (no autograd): (X, Q, (W1c, b1c, W2c, b2c), H) — H: the hidden layer's hand-over to
+        the backward (a private byte buffer; None when cfg["need_grad"] is false or KEEP_H is off).  Called by forward(), or EARLIER by
         level_fused_launch() — the level kernels of a step need nothing the host has to wait for, so context_model enqueues them in
         front of the rate subset's read-back and hands the result to forward() through cfg["pre"]."""
         from . import mlp as _mlp
@@ -897,14 +902,17 @@ class _LevelFused(torch.autograd.Function):
         assert yf.is_contiguous() and ys.is_contiguous() and yo.is_contiguous()
         X = torch.empty(n, in_f, dtype=_f32, device=dev)
         Q = torch.empty(n, 3, dtype=_f32, device=dev)
+        H = None
+        if KEEP_H and cfg.get("need_grad") and n > 0 and in_f == 71:
+            H = torch.empty(int(L.cgs_ctx_level_hidden_bytes(n)), dtype=torch.uint8, device=dev)
         stream = _lib.current_stream()
         seed, q0 = int(cfg["seed"]), cfg["q0"]
-        _lib.check(L.cgs_ctx_level_fwd(
+        _lib.check(L.cgs_ctx_level_fwd_h(
             in_f, _lib.ptr(anchor_c), int(anchor_c.shape[0]), _lib.ptr(a_rows), _lib.ptr(a_mask), _lib.ptr(bf), _lib.ptr(bs),
             int(bf.shape[0]) if ctxlevel else 0, _lib.ptr(pos), _lib.ptr(hyp_c), n, _lib.ptr(W1c), _lib.ptr(b1c), W2c.data_ptr() + 4 * n_stat * hid, b2c.data_ptr() + 4 * n_stat, _lib.ptr(src.f),
             _lib.ptr(src.s), _lib.ptr(src.o), _lib.ptr(rows), seed, q0[0], q0[1], q0[2], _lib.ptr(X), _lib.ptr(yf), _lib.ptr(ys),
-            _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(src.sums_buffer()), stream), "cgs_ctx_level_fwd")
-        return X, Q, (W1c, b1c, W2c, b2c)
+            _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(src.sums_buffer()), _lib.ptr(H), stream), "cgs_ctx_level_fwd_h")
+        return X, Q, (W1c, b1c, W2c, b2c), H
 
     @staticmethod
     def forward(ctx, anchor, base_f, base_s, hyp, W1, b1, W2, b2, _token, cfg):
@@ -912,7 +920,9 @@ class _LevelFused(torch.autograd.Function):
         L = _lib.lib()
         src, rows, loc = cfg["src"], cfg["rows"], cfg["loc"]
         pre = cfg.get("pre")
-        X, Q, (W1c, b1c, W2c, b2c) = pre if pre is not None else _LevelFused.launch(anchor, base_f, base_s, hyp, W1, b1, W2, b2, cfg)
+        if pre is None:
+            pre = _LevelFused.launch(anchor, base_f, base_s, hyp, W1, b1, W2, b2, dict(cfg, need_grad=any(ctx.needs_input_grad)))
+        X, Q, (W1c, b1c, W2c, b2c), H = pre
         n, in_f = int(rows.shape[0]), int(W1c.shape[1])
         hid, out, n_stat = int(W1c.shape[0]), int(W2c.shape[0]), int(cfg["n_stat"])
         ctxlevel = base_f is not None
@@ -934,7 +944,7 @@ class _LevelFused(torch.autograd.Function):
             _lib.check(L.cgs_mlp2_forward(in_f, hid, out, 0, _lib.ptr(x_sub), in_f, _lib.ptr(W1c), _lib.ptr(b1c), _lib.ptr(W2c),
                                           _lib.ptr(b2c), _lib.ptr(pred), out, _lib.ptr(h_sub), m, stream), "cgs_mlp2_forward")
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(X, x_sub, h_sub, W1c, b1c, W2c, b2c)
+        ctx.save_for_backward(X, x_sub, h_sub, W1c, b1c, W2c, b2c, H)      # (H is no output of this node: no cycle, see below)
         # (without "outs": they are this node's OUTPUTS — an output kept on its own ctx is a reference cycle through the C++
         #  node that Python's collector cannot see: every step's level nodes, RowSource and ~350 MB of level tensors stayed
         #  alive for the life of the process, found in round 5 when the device filled up — tools/leak_probe.py)
@@ -952,7 +962,7 @@ class _LevelFused(torch.autograd.Function):
     def backward(ctx, gf, gs, go, gQ, d_pred):
         from . import mlp as _mlp
         L = _lib.lib()
-        X, x_sub, h_sub, W1, b1, W2, b2 = ctx.saved_tensors
+        X, x_sub, h_sub, W1, b1, W2, b2, H = ctx.saved_tensors
         cfg = ctx.cfg
         n, in_f, hid, out, n_stat, m = ctx.dims
         src, rows, loc = cfg["src"], cfg["rows"], cfg["loc"]
@@ -999,13 +1009,20 @@ class _LevelFused(torch.autograd.Function):
         hd, d_hyp_rows = cfg.get("hyp_direct"), None
         if hd is not None and ctx.needs_input_grad[3] and hd[0].n == int(dxf.shape[0]) and hd[0].c == 12 and hd[0].sizes[hd[1]] == n:
             d_hyp_rows = hd[0].buffer(dev)
-        _lib.check(L.cgs_ctx_level_bwd2(
+        # with the forward's hidden layer when it was kept (the recompute's bits, a third fewer matrix products), else from X alone
+        bwd_args = (
             in_f, _lib.ptr(X), _lib.ptr(W1), _lib.ptr(b1), W2.data_ptr() + 4 * n_stat * hid, b2.data_ptr() + 4 * n_stat,
             _lib.ptr(gf), _lib.ptr(gs), _lib.ptr(go), _lib.ptr(gQ), n, int(cfg["seed"]), cfg["q0"][0], cfg["q0"][1], cfg["q0"][2],
             _lib.ptr(rows), int(dxf.shape[0]), _lib.ptr(dxf), _lib.ptr(dxs), _lib.ptr(dxo), _lib.ptr(smap),
             int(sd[0].shape[0]) if sd[0] is not None else 0, *[_lib.ptr(t) for t in sd],
             _lib.ptr(dx_sub), _lib.ptr(dX), _lib.ptr(d_hyp_rows), _lib.ptr(dW1), _lib.ptr(db1), dW2.data_ptr() + 4 * n_stat * hid,
-            db2.data_ptr() + 4 * n_stat, _lib.ptr(ws2), ws2.numel(), stream), "cgs_ctx_level_bwd")
+            db2.data_ptr() + 4 * n_stat)
+        # (an instrumented cgs_ctx_level_bwd2 — a caller that wrapped the entry to see the level backward start, as the multi-rank
+        #  sequence test does — is honoured: the recompute path, the same bits)
+        if H is not None and type(L.cgs_ctx_level_bwd2) is type(L.cgs_ctx_level_bwd_h):
+            _lib.check(L.cgs_ctx_level_bwd_h(*bwd_args, _lib.ptr(H), _lib.ptr(ws2), ws2.numel(), stream), "cgs_ctx_level_bwd_h")
+        else:
+            _lib.check(L.cgs_ctx_level_bwd2(*bwd_args, _lib.ptr(ws2), ws2.numel(), stream), "cgs_ctx_level_bwd")
         if d_hyp_rows is not None:
             hd[0].done.add(hd[1])
         if side is not None:
@@ -1063,7 +1080,7 @@ def level_fused_launch(anchor, base_f, base_s, hyp, seq, n_stat, a_rows, a_mask,
     (same arguments, same seed).  base_f / base_s: the coded prefix's VALUES (the buffers the earlier levels' launches wrote)."""
     l1, l2 = seq[0], seq[2]
     cfg = dict(a_rows=a_rows, a_mask=a_mask, pos=pos, n_stat=int(n_stat), src=src, rows=rows, seed=int(seed),
-               q0=tuple(float(v) for v in q0), outs=outs)
+               q0=tuple(float(v) for v in q0), outs=outs, need_grad=torch.is_grad_enabled())
     return _LevelFused.launch(anchor, base_f, base_s, hyp, l1.weight, l1.bias, l2.weight, l2.bias, cfg)
 
 

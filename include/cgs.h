@@ -1011,6 +1011,26 @@ int cgs_ctx_level_bwd2(int in_dim, const float *X, const float *W1, const float 
                        const int32_t *side_map, int64_t m_side, const float *side_f, const float *side_s, const float *side_o, const float *side_Q,
                        const float *dx_sub, float *dX, float *d_hyp_rows, float *dW1, float *db1, float *dW2q, float *db2q,
                        void *scratch, size_t scratch_bytes, void *stream);
+/* The hidden layer's hand-over: cgs_ctx_level_fwd_h = cgs_ctx_level_fwd + H (may be NULL = cgs_ctx_level_fwd), a buffer of
+ * cgs_ctx_level_hidden_bytes(n) bytes that receives relu(W1 X + b1) and tanh of the three step-size outputs of every row, in a
+ * layout private to csrc/ctx_level.hip (whole 16-row tiles: every byte of the buffer is written).  cgs_ctx_level_bwd_h =
+ * cgs_ctx_level_bwd2 + that buffer (same rows, same weights; NULL = cgs_ctx_level_bwd2): the backward reads the hidden layer
+ * instead of recomputing it from X — a third fewer matrix products, no step-size head; every output has the bits of
+ * cgs_ctx_level_bwd2. */
+size_t cgs_ctx_level_hidden_bytes(int64_t n);
+int cgs_ctx_level_fwd_h(int in_dim, const float *anchor, int64_t n_anchor, const int64_t *a_rows,
+                        const uint8_t *a_mask, const float *base_f, const float *base_s, int64_t n_par,
+                        const int64_t *pos, const float *hyp, int64_t n, const float *W1, const float *b1, const float *W2q, const float *b2q,
+                        const float *xf, const float *xs, const float *xo, const int64_t *rows, uint64_t seed,
+                        float q0f, float q0s, float q0o, float *X, float *yf, float *ys, float *yo, float *Q,
+                        double *sums3, float *H, void *stream);
+int cgs_ctx_level_bwd_h(int in_dim, const float *X, const float *W1, const float *b1, const float *W2q,
+                        const float *b2q, const float *dyf, const float *dys, const float *dyo,
+                        const float *dQ_ext, int64_t n, uint64_t seed, float q0f, float q0s, float q0o,
+                        const int64_t *rows, int64_t n_anchor, float *dxf, float *dxs, float *dxo,
+                        const int32_t *side_map, int64_t m_side, const float *side_f, const float *side_s, const float *side_o, const float *side_Q,
+                        const float *dx_sub, float *dX, float *d_hyp_rows, float *dW1, float *db1, float *dW2q, float *db2q,
+                        const float *H, void *scratch, size_t scratch_bytes, void *stream);
 
 /* Row strides (floats) of the buffers the anchor-MLP forward and backward hand to each other, so that callers size them:
  * out4 = {row stride of Hcat (150: head h in columns 50 h .. 50 h + 49), row stride of X_out of the _rows variant (54),

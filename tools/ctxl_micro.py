@@ -1,5 +1,6 @@
 """Micro-benchmark of the fused level kernels (csrc/ctx_level.hip) on level-0-sized operands: cgs_ctx_level_fwd / _bwd at
-n rows of in_dim 71 (and the round-4 launches they replace, for the same rows).  python tools/ctxl_micro.py [n] [iters]"""
+n rows of in_dim 71 (and the round-4 launches they replace, for the same rows).  python tools/ctxl_micro.py [n] [iters] [in_dim] [h]
+h = 1: also the hidden layer's hand-over (cgs_ctx_level_fwd_h / _bwd_h), alternating with the recompute pair, from the same build."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -8,6 +9,7 @@ from contextgs_amd import _lib
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 800_000
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 in_dim = int(sys.argv[3]) if len(sys.argv) > 3 else 71
+with_h = len(sys.argv) > 4 and sys.argv[4] == "1"
 L = _lib.lib()
 dev = "cuda"
 p = _lib.ptr
@@ -52,6 +54,21 @@ def bwd():
                                    p(dW2q), p(db2q), p(ws), ws.numel(), st), "bwd")
 
 
+H = torch.empty(int(L.cgs_ctx_level_hidden_bytes(n)), dtype=torch.uint8, device=dev) if with_h else None
+
+
+def fwd_h():
+    _lib.check(L.cgs_ctx_level_fwd_h(in_dim, p(anchor), N, p(a_rows), None, p(base_f) if ctxl else None, p(base_s) if ctxl else None,
+                                     n_par if ctxl else 0, p(pos) if ctxl else None, p(hyp), n, p(W1), p(b1), p(W2q), p(b2q), p(xf), p(xs), p(xo), p(rows), seed,
+                                     *q0, p(X), p(yf), p(ys), p(yo), p(Q), p(sums), p(H), st), "fwd_h")
+
+
+def bwd_h():
+    _lib.check(L.cgs_ctx_level_bwd_h(in_dim, p(X), p(W1), p(b1), p(W2q), p(b2q), p(dyf), p(dys), p(dyo), None, n, seed, *q0, p(rows),
+                                     N, p(dxf), p(dxs), p(dxo), p(smap), m, p(sf), p(ss), p(so), p(sQ), p(dxsub), p(dX), None, p(dW1), p(db1),
+                                     p(dW2q), p(db2q), p(H), p(ws), ws.numel(), st), "bwd_h")
+
+
 def timeit(f, name):
     for _ in range(3):
         f()
@@ -69,6 +86,11 @@ def timeit(f, name):
 
 t_f = timeit(fwd, "ctx_level_fwd")
 t_b = timeit(bwd, "ctx_level_bwd (+reduce)")
+if with_h:
+    for rnd in range(3):      # alternating: the pair with the hand-over, the pair without
+        hf, hb = timeit(fwd_h, "ctx_level_fwd_h"), timeit(bwd_h, "ctx_level_bwd_h (+reduce)")
+        rf, rb = timeit(fwd, "ctx_level_fwd"), timeit(bwd, "ctx_level_bwd (+reduce)")
+        print(f"round {rnd}: pair with H {hf + hb:9.1f} us, recompute {rf + rb:9.1f} us, difference {hf + hb - rf - rb:+9.1f} us")
 tiles = (n + 15) // 16
 mf_f = 140 if ctxl else 28
 mf_b = 420 if ctxl else 84

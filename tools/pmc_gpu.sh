@@ -51,7 +51,7 @@ tot_ctx, steps_ctx = 0.0, 0
 for k, (n, tot) in rd.items():
     if any(s_ in k for s_ in ctx_keys) and k in wr:
         tot_ctx += (2 * tot + wr[k][1]) * 1024
-    if "ctxl_bwd_kernel<71>" in k:
+    if "ctxl_bwd_kernel<71" in k:          # (<71> before the hand-over, <71, true | false> since)
         steps_ctx = n // 2
 import hashlib, os
 csrc = os.path.join(os.environ.get("GRAFT_REPO_ROOT", "."), "contextgs_amd", "csrc")
