@@ -14,9 +14,16 @@ import torch
 from . import _lib
 
 
+def _refuse_target_grad(ctx, who):
+    if ctx.needs_input_grad[1]:
+        raise NotImplementedError(f"{who}: `gt` (the second image) requires grad, but the fused loss differentiates the first image "
+                                  "only; detach the target, or pass the image to optimise first")
+
+
 class _L1Ssim(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, gt):
+        _refuse_target_grad(ctx, "l1_ssim")
         _lib.require_device(img, gt)
         x = img if (img.dtype == torch.float32 and img.is_contiguous()) else img.float().contiguous()
         y = gt if (gt.dtype == torch.float32 and gt.is_contiguous()) else gt.float().contiguous()
@@ -76,6 +83,7 @@ class _TrainImageLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, gt, lam):
+        _refuse_target_grad(ctx, "training_image_loss")
         _lib.require_device(img, gt)
         x = img if (img.dtype == torch.float32 and img.is_contiguous()) else img.float().contiguous()
         y = gt if (gt.dtype == torch.float32 and gt.is_contiguous()) else gt.float().contiguous()

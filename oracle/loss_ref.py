@@ -6,6 +6,8 @@ Follows utils/loss_utils.py of the reference:
   gaussian :23-25   11 taps, sigma 1.5, normalised
   _ssim    :43-63   zero-padded per-channel 11x11 filtering of x, y, x^2, y^2, xy; C1 = 0.01^2, C2 = 0.03^2;
                     ssim_map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)); mean
+`l1_ssim_terms` / `l1_ssim_grads` are the same expressions with everything the fused kernel exposes returned: the per-pixel maps and
+the per-tile sums of a tile size given by the caller (tests/loss_cases.py); `l1_ssim` is their composition.
 Pinned by tests/golden/loss.npz (values and gradients produced by the reference's own functions,
 tools/make_loss_golden.py).  The gradient below is the analytic adjoint of the same expressions.
 
@@ -39,14 +41,27 @@ def _filt(a, w):
     return o
 
 
-def l1_ssim(img, gt, dtype=np.float32):
-    """(l1 mean, ssim mean, dl1/dimg, dssim/dimg) for [C,H,W] arrays."""
+def _tile_sums(a, tile):
+    """sums of a [C,H,W] array over tile[0] x tile[1] pixel tiles, [C, tile rows, tile columns], in a's dtype."""
+    th, tw = (tile, tile) if np.isscalar(tile) else tile
+    C, H, W = a.shape
+    ny, nx = -(-H // th), -(-W // tw)
+    p = np.zeros((C, ny * th, nx * tw), dtype=a.dtype)
+    p[:, :H, :W] = a
+    return p.reshape(C, ny, th, nx, tw).sum(axis=(2, 4), dtype=a.dtype)
+
+
+def l1_ssim_terms(img, gt, dtype=np.float32, tile=32, filt=None):
+    """What the fused forward exposes, per pixel and per tile, for [C,H,W] arrays in `dtype`:
+      absdiff |x - y|, ssim (the SSIM map), dmu1 / ds1 / ds12 (d ssim / d mu1, d sigma1^2, d sigma12: what the backward filters),
+      tile_l1 / tile_ssim [C, tile rows, tile columns]: sums of absdiff and ssim over `tile` (rows, columns or one int) pixels.
+    `filt` replaces the window filtering (tests state wrong filters with it)."""
+    filt = filt or _filt
     x, y = img.astype(dtype), gt.astype(dtype)
     w = window(dtype)
-    n = x.size
     C1, C2 = dtype(0.01 ** 2), dtype(0.03 ** 2)
-    mu1, mu2 = _filt(x, w), _filt(y, w)
-    e11, e22, e12 = _filt(x * x, w), _filt(y * y, w), _filt(x * y, w)
+    mu1, mu2 = filt(x, w), filt(y, w)
+    e11, e22, e12 = filt(x * x, w), filt(y * y, w), filt(x * y, w)
     s1, s2, s12 = e11 - mu1 * mu1, e22 - mu2 * mu2, e12 - mu1 * mu2
     a1, a2 = 2 * mu1 * mu2 + C1, 2 * s12 + C2
     b1, b2 = mu1 * mu1 + mu2 * mu2 + C1, s1 + s2 + C2
@@ -54,9 +69,27 @@ def l1_ssim(img, gt, dtype=np.float32):
     dm_ds1 = -(a1 * a2) / (b1 * b2 * b2)
     dm_ds12 = 2 * a1 / (b1 * b2)
     dm_dmu1 = (2 * mu2 * a2 * b1 - 2 * mu1 * a1 * a2) / (b1 * b1 * b2) - 2 * mu1 * dm_ds1 - mu2 * dm_ds12
-    g_ssim = (_filt(dm_dmu1, w) + 2 * x * _filt(dm_ds1, w) + y * _filt(dm_ds12, w)) / dtype(n)
+    d = np.abs(x - y)
+    return {"absdiff": d, "ssim": m, "dmu1": dm_dmu1, "ds1": dm_ds1, "ds12": dm_ds12,
+            "tile_l1": _tile_sums(d, tile), "tile_ssim": _tile_sums(m, tile)}
+
+
+def l1_ssim_grads(img, gt, dmu1, ds1, ds12, dtype=np.float32, filt=None):
+    """(dl1/dimg, dssim/dimg) of the two means from the three derivative maps: the backward on its own."""
+    filt = filt or _filt
+    x, y = img.astype(dtype), gt.astype(dtype)
+    w = window(dtype)
+    n = x.size
+    g_ssim = (filt(dmu1.astype(dtype), w) + 2 * x * filt(ds1.astype(dtype), w) + y * filt(ds12.astype(dtype), w)) / dtype(n)
     g_l1 = np.sign(x - y) / dtype(n)
-    return float(np.abs(x - y).mean(dtype=np.float64)), float(m.mean(dtype=np.float64)), g_l1, g_ssim
+    return g_l1, g_ssim
+
+
+def l1_ssim(img, gt, dtype=np.float32):
+    """(l1 mean, ssim mean, dl1/dimg, dssim/dimg) for [C,H,W] arrays."""
+    t = l1_ssim_terms(img, gt, dtype)
+    g_l1, g_ssim = l1_ssim_grads(img, gt, t["dmu1"], t["ds1"], t["ds12"], dtype)
+    return float(t["absdiff"].mean(dtype=np.float64)), float(t["ssim"].mean(dtype=np.float64)), g_l1, g_ssim
 
 
 def scaling_reg(scaling):

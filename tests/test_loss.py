@@ -72,12 +72,15 @@ def test_hip_full_hd_properties_and_torch_reference():
 
 # ---- the two regularisers train.py:203,209 adds to the image terms ----------------------------------------------------
 
-def _reg_inputs(P, seed):
+REG_P_TWO_TRIPS = 2_097_152 + 5       # 524 289 quads: one more than 2048 workgroups of 256 hold, and a tail row
+
+
+def _reg_inputs(P, seed, mask_rows=None):
     r = np.random.default_rng(seed)
     scaling = np.exp(r.normal(-3.0, 1.0, size=(P, 3))).astype(np.float32)
     if P > 2:
         scaling[1, 1] = 0.0           # torch's prod backward has a separate zero-safe path: d/d(that entry) = product of the others
-    mask = r.normal(0.5, 2.0, size=(P, 10, 1)).astype(np.float32)
+    mask = r.normal(0.5, 2.0, size=(P if mask_rows is None else mask_rows, 10, 1)).astype(np.float32)
     return scaling, mask
 
 
@@ -98,12 +101,13 @@ def test_reg_oracle_matches_the_reference_expressions(P):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("P", [1, 3, 4, 5, 1001, 1_000_003])
+@pytest.mark.parametrize("P", [1, 3, 4, 5, 1001, 1_000_003, REG_P_TWO_TRIPS])
 def test_hip_regularisers_match_oracle(P):
     import torch
     from contextgs_amd.loss_utils import scaling_reg, mask_reg
     from oracle import loss_ref
-    scaling, mask = _reg_inputs(P, 7 + P)
+    # (the two-trip case is about scaling_reg's grid-stride loop: its mask stays at 1001 rows)
+    scaling, mask = _reg_inputs(P, 7 + P, mask_rows=1001 if P == REG_P_TWO_TRIPS else None)
     for x_np, op, ref in ((scaling, scaling_reg, loss_ref.scaling_reg), (mask, mask_reg, loss_ref.mask_reg)):
         v_ref, d_ref = ref(x_np)
         for misaligned in (False, True):
@@ -165,6 +169,62 @@ def test_weighted_image_sum_matches_torch_fp64(n, with_rate):
     assert torch.equal(weighted_image_sum(img, w, rate, 0.001), out)
     (2.0 * out).backward()
     assert torch.equal(img.grad, 2.0 * w)
+    if with_rate:
+        assert abs(float(rate.grad) - 0.002) < 1e-9
+
+
+def _off_by_four_bytes(t):
+    """The same values in a view that starts 4 bytes into its storage: not 16-byte aligned."""
+    import torch
+    buf = torch.zeros(t.numel() + 1, dtype=t.dtype, device=t.device)
+    buf[1:] = t
+    v = buf[1:]
+    assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+    return v
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["img", "w", "both"])
+@pytest.mark.parametrize("n", [5, 1027, 3 * 180 * 320])
+def test_weighted_image_sum_misaligned_operands(n, which):
+    """An operand that is not 16-byte aligned sends cgs_weighted_sum_* down the element-wise path (n4 = 0), forward (img or w)
+    and backward (w): the assertions of the aligned cases."""
+    import torch
+    from contextgs_amd.loss_utils import weighted_image_sum
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    img = torch.rand(n, device="cuda", generator=gen)
+    w = torch.randn(n, device="cuda", generator=gen)
+    if which in ("img", "both"):
+        img = _off_by_four_bytes(img)
+    if which in ("w", "both"):
+        w = _off_by_four_bytes(w)
+    img.requires_grad_(True)
+    rate = torch.tensor(3.25, device="cuda", requires_grad=True)
+    out = weighted_image_sum(img, w, rate, 0.001)
+    ref = (img.detach().double() * w.double()).sum() + 0.001 * 3.25
+    assert abs(float(out) - float(ref)) <= 1e-6 * float((img.detach().double() * w.double()).abs().sum()) + 1e-7
+    assert torch.equal(weighted_image_sum(img, w, rate, 0.001), out)
+    aligned = weighted_image_sum(img.detach().clone(), w.clone(), rate, 0.001)            # the vector path on the same values
+    assert abs(float(out) - float(aligned)) <= 1e-6 * float((img.detach().double() * w.double()).abs().sum()) + 1e-7
+    (2.0 * out).backward()
+    assert img.grad.shape == img.shape and torch.equal(img.grad, 2.0 * w)
+    assert abs(float(rate.grad) - 0.002) < 1e-9
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_rate", [False, True])
+def test_weighted_image_sum_of_nothing(with_rate):
+    """n = 0: the value is lam * rate (or 0), the image gradient is empty."""
+    import torch
+    from contextgs_amd.loss_utils import weighted_image_sum
+    img = torch.zeros(0, device="cuda", requires_grad=True)
+    w = torch.zeros(0, device="cuda")
+    rate = torch.tensor(3.25, device="cuda", requires_grad=True) if with_rate else None
+    out = weighted_image_sum(img, w, rate, 0.001)
+    assert abs(float(out) - (0.001 * 3.25 if with_rate else 0.0)) < 1e-9
+    assert torch.equal(weighted_image_sum(img, w, rate, 0.001), out)
+    (2.0 * out).backward()
+    assert img.grad is not None and img.grad.shape == (0,)
     if with_rate:
         assert abs(float(rate.grad) - 0.002) < 1e-9
 
