@@ -3,6 +3,8 @@ expansion) against the REFERENCE's outputs in tests/golden/*.npz, through the dr
 modules of contextgs_amd (which call libcgs_hip.so via the C-ABI).
 
 Bit-exact: Quantize_anchor, STE_*, level indices.  Floating point: tolerances stated inline.
+The expansion's goldens here are whole-model, strided fixtures judged against the tensor's maximum; its kernels are pinned
+element by element against float64 in tests/test_expand_gpu.py (reference and error units: tests/expand_ref.py).
 """
 import os
 import types
