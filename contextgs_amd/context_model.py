@@ -24,6 +24,9 @@ Cited lines are scene/gaussian_model.py unless stated otherwise.
 """
 from __future__ import annotations
 
+import collections
+import types
+
 import torch
 
 from . import _lib
@@ -35,6 +38,7 @@ from .entropy_bottleneck import EntropyBottleneck as _EntropyBottleneck
 from .multi_level import torch_unique_with_indices
 
 Q_FEAT0, Q_SCALING0, Q_OFFSETS0 = 1, 0.001, 0.2      # :1564-1566
+_Q0 = (Q_FEAT0, Q_SCALING0, Q_OFFSETS0)
 import os as _os
 FUSED_TRAINING = True      # fused HIP stages for the training path (tests flip it to compare with the torch composition)
 ROW_SOURCE = _os.environ.get("CGS_ROW_SOURCE", "1") != "0"      # A/B knob: 0 = gather into coding order first
@@ -166,8 +170,7 @@ def level_plan(pc, anchor, mask_anchor_bool):
 
 
 def _cached_plan(pc, anchor, mask_anchor_bool):
-    key = (float(pc.voxel_size), tuple(float(v) for v in pc.level_scale), int(pc.level_num),
-           tuple(anchor.shape), mask_anchor_bool is None)
+    key = _plan_key(pc, anchor, mask_anchor_bool)
     cache = getattr(pc, "_level_cache", None)
     if cache is not None and cache["key"] == key:
         same = (anchor == cache["anchor"]).all()
@@ -272,7 +275,7 @@ def begin_step(pc, anchor, mask_anchor_bool, predict_bpp):
         packed = pc.latent_codec._packed_params()      # a cat launch the step needs anyway: queued before the read-back
     hyper_pre = None
     hl = getattr(pc, "_hyper_latent", None)
-    if (packed is not None and FUSED_TRAINING and hl is not None and hl.is_cuda and hl.dtype == torch.float32 and hl.dim() == 2
+    if (packed is not None and hl is not None and _fused_step(True, hl) and hl.dtype == torch.float32 and hl.dim() == 2
             and hl.is_contiguous() and hl.shape[0] == a["n"]):
         # the noisy hyper latents in coding order depend on the plan only, not on the rate subset: launched here, in front
         # of the read-back, instead of behind it where the GPU would wait for the host to issue them (a 30 us gap)
@@ -345,32 +348,30 @@ def _level_plan_uncached(pc, anchor, mask_anchor_bool):
             orig = mapping_to_orign(mapping_list, i, to_code)
         else:
             orig = torch.arange(n, device=dev)[to_code]
-        plan.append((i, to_code, orig, None))     # level anchors are re-gathered from the live tensor: level_anchors()
+        plan.append((i, to_code, orig, None))     # level anchors are re-gathered from the live tensor: _level_inputs()
     return plan, inverse_indices_list, mapping_list
 
 
-def level_anchors(anchor, mask_anchor_bool, level, orig):
-    """hybrid_anchor_list[level][to_code] of the reference (:1594): the rows `orig` of the anchors the level
-    was built from (masked anchors are zeroed from level 1 up, :1758-1759)."""
-    if level >= 1 and mask_anchor_bool is not None:
-        anchor = anchor * mask_anchor_bool.unsqueeze(1)
-    return gather_unique(anchor, orig)
+def _grid_mlp_fused(pc, level):
+    """mlp_grid[level] has an instance of the fused fp32-MFMA kernels (mlp.hip)."""
+    return _mlp.supported(pc.get_grid_mlp[level])
 
 
 def grid_mlp(pc, level, feat_in):
     """mlp_grid[level](feat_in) (:1600) on the fused fp32-MFMA kernels when the shape has an instance."""
     seq = pc.get_grid_mlp[level]
-    return _mlp.mlp2(feat_in, seq) if _mlp.supported(seq) else seq(feat_in)
+    return _mlp.mlp2(feat_in, seq) if _grid_mlp_fused(pc, level) else seq(feat_in)
 
 
 def split_prediction(pc, predicted):                                    # :1603-1608
     D, K = pc.feat_dim, pc.n_offsets
-    (mean_feat, scale_feat, mean_scaling, scale_scaling, mean_offsets, scale_offsets, qf, qs, qo) = torch.split(
-        predicted, [D, D, 6, 6, 3 * K, 3 * K, 1, 1, 1], dim=-1)
-    Q_feat = (Q_FEAT0 * (1 + torch.tanh(qf))).clamp(1e-9)
-    Q_scaling = (Q_SCALING0 * (1 + torch.tanh(qs))).clamp(1e-9)
-    Q_offsets = (Q_OFFSETS0 * (1 + torch.tanh(qo))).clamp(1e-9)
-    return mean_feat, scale_feat, mean_scaling, scale_scaling, mean_offsets, scale_offsets, Q_feat, Q_scaling, Q_offsets
+    stats_and_q = torch.split(predicted, [D, D, 6, 6, 3 * K, 3 * K, 1, 1, 1], dim=-1)
+    return (*stats_and_q[:6], *_step_sizes(*stats_and_q[6:]))
+
+
+def _step_sizes(qf, qs, qo):
+    """(Q_feat, Q_scaling, Q_offsets) from mlp_grid's three step-size outputs (:1606-1608)."""
+    return tuple((q0 * (1 + torch.tanh(q))).clamp(1e-9) for q0, q in zip(_Q0, (qf, qs, qo)))
 
 
 def _index_rows(x, idx):
@@ -542,9 +543,98 @@ def gather_rows(x, idx):
     return _GatherRows.apply(x, idx) if x.requires_grad else x.index_select(0, idx)
 
 
+def _fused_step(training, t):
+    """The fused HIP stages of the training path apply to a step on the device tensor `t` (the one reader of FUSED_TRAINING)."""
+    return bool(FUSED_TRAINING and training and t.is_cuda)
+
+
+# What one step of the context model runs, decided once per step by _route():
+#   fused        the levels' element-wise stages run as HIP kernels (ctx_ops): training, on the device
+#   row_source   the levels read features / scaling / offsets through perm[lo:hi] (ctx_ops.RowSource), nothing is gathered
+#   hyper        "forms": EntropyBottleneck.training_step_forms; "rows": the likelihood of the rate subset's rows; "plain"
+#   tiers        per plan entry "kernel" (ctx_ops.level_fused), "launches" (round 4's separate launches), "torch", None = empty level
+#   subset       per plan entry: mlp_grid's mean / scale outputs are formed on the rate subset's rows only (see _level_launches)
+#   rate_side    the rate gradients reach the levels in compact form (ctx_ops.RateSide)
+#   rate_lazy    the rate subset's mean / scale outputs stay inside the rate kernels (cgs_rate_sub_*)
+#   levels_fused every level record rate_model gets is a fused one (_level_record)
+_Route = collections.namedtuple("_Route", "fused row_source hyper tiers subset rate_side rate_lazy levels_fused")
+
+
+def _route(pc, c, anchor, hyper, feat, grid_offsets, grid_scaling, training, keep_stats, has_choose, has_chosen, allow_rate_lazy):
+    """The step's route (_Route) on the plan `c`: the ONE place that reads the A/B knobs and asks which shapes have kernels.
+    has_choose: a rate subset exists (a mask, or the list the bookkeeping kernel compacted); has_chosen: that list exists, level
+    by level, with the live count (_plan_and_chosen's full path).  _early_levels asks before the read-back, with what the step
+    will have if its data does not change; the level loop asks with what came back.  `hyper` (the latents) stands for the levels'
+    blocks of noisy latents, which do not exist yet: a latent codec returns them in its input's width, dtype and device."""
+    plan, sizes = c["plan"], c["sizes"]
+    fused = _fused_step(training, anchor) and not pc.adaptQ_per_channel
+    subset = tuple(_grid_mlp_fused(pc, i_) and (not keep_stats or has_choose) for (i_, _t, _o, _a) in plan)
+    # When every level takes the fused path, features / scaling / offsets are not gathered at all: the level kernels
+    # read their rows of the parameter tensors through perm[lo:hi] and scatter the gradients back (ctx_ops.RowSource)
+    row_source = bool(fused and ROW_SOURCE and not c.get("identity") and all(subset) and grid_offsets.dim() == 3
+                      and (feat.requires_grad or grid_scaling.requires_grad or grid_offsets.requires_grad))
+    # :1556.  Only the rate subset's hyper likelihood is ever read (:1662), and only as a sum of bits: on the fused
+    # training path the bottleneck returns the noisy latents already in coding order plus that sum (two launches);
+    # otherwise the likelihood of the chosen rows / of all rows as a tensor
+    hyper_step = "plain"
+    if (_fused_step(training, hyper) and keep_stats and has_choose and isinstance(pc.latent_codec, _EntropyBottleneck)
+            and pc.latent_codec.filters == (3, 3, 3, 3)):
+        forms = not pc.disable_hyper and has_chosen and c["covers_all"] and hyper.dtype == torch.float32
+        hyper_step = "forms" if forms else "rows"
+    src_like = types.SimpleNamespace(f=feat, s=grid_scaling, o=grid_offsets.detach().flatten(1)) if row_source else None
+    tiers, joined = [], fused
+    for j, (i, _tc, _orig, _a) in enumerate(plan):
+        if sizes[j] <= 0:
+            tiers.append(None)
+        elif not (fused and subset[j]):
+            tiers.append("torch")
+            joined = False          # (the levels' outputs no longer lie side by side: no later level takes the kernel tier)
+        elif LEVEL_FUSED and joined and _ctx.level_fused_supported(pc.get_grid_mlp[i], anchor, hyper, src_like):
+            tiers.append("kernel")
+        else:
+            tiers.append("launches")
+    coded = [t for t in tiers if t is not None]
+    rate_side = bool(keep_stats and RATE_SIDE)
+    # The mean / scale outputs of the rate subset can stay INSIDE the rate kernels (cgs_rate_sub_*, round 6) when the rate model
+    # will take its one-node path (rate_model: every level on the kernel tier, the subset listed level by level, the live
+    # fraction a host number)
+    rate_lazy = bool(allow_rate_lazy and RATE_FUSED and rate_side and has_chosen and row_source and pc._anchor_feat.is_cuda
+                     and all(t == "kernel" for t in coded))
+    return _Route(fused, row_source, hyper_step, tuple(tiers), subset, rate_side, rate_lazy,
+                  bool(keep_stats and coded and "torch" not in coded))
+
+
 class _EarlyMismatch(Exception):
     """The level kernels were enqueued ahead of the rate subset's read-back and what came back does not fit them (the plan was
-    rebuilt, or a level left the fused path): the caller runs the step's context model again the plain way."""
+    rebuilt, or the rate subset's rows are missing): the caller runs the step's context model again the plain way."""
+
+
+def _level_inputs(ctx_src, level, orig, mask_anchor_bool):
+    """(a_rows, a_mask, pos, base_f, base_s, csr): what the rows of mlp_grid's input are assembled from.  The first level coded
+    reads its own anchors `orig` (:1596-1599); a context level reads its parents' anchors a_rows and their rows `pos` of the coded
+    prefix base_f / base_s (ctx_src = _next_context(...), :1711-1724; csr: the parents' children lists for the backward)."""
+    if ctx_src is None:
+        # (masked anchors sit at the origin from level 1 up, :1758-1759: a_mask multiplies the gathered rows)
+        return orig, (mask_anchor_bool if level >= 1 else None), None, None, None, None
+    a_rows, pos, base_f, base_s, csr = ctx_src
+    return a_rows, None, pos, base_f, base_s, csr
+
+
+def _level_kernel_args(pc, c, j, anchor, hyp, ctx_src, mask_anchor_bool, row_src, big, row_off):
+    """(the arguments ctx_ops.level_fused_launch and ctx_ops.level_fused share, csr) of plan entry j, whose rows start at row_off
+    of the coding order: the early launch and the node created around it later get the same arguments from here."""
+    i, _tc, orig, _a = c["plan"][j]
+    a_rows, a_mask, pos, base_f, base_s, csr = _level_inputs(ctx_src, i, orig, mask_anchor_bool)
+    sl = slice(row_off, row_off + c["sizes"][j])
+    return dict(anchor=anchor, base_f=base_f, base_s=base_s, hyp=hyp, seq=pc.get_grid_mlp[i],
+                n_stat=2 * (pc.feat_dim + 6 + 3 * pc.n_offsets), a_rows=a_rows, a_mask=a_mask, pos=pos, src=row_src,
+                rows=c["perm"][sl], outs=tuple(b[sl] for b in big), q0=_Q0), csr
+
+
+def _level_outputs(c, feat, grid_scaling, K, dev):
+    """The buffers the fused levels write their outputs into, side by side in coding order (no cat at the end)."""
+    n_tot = int(c["perm"].shape[0])
+    return tuple(torch.empty(n_tot, w, dtype=torch.float32, device=dev) for w in (feat.shape[1], grid_scaling.shape[1], 3 * K))
 
 
 def _early_levels(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, begun):
@@ -554,51 +644,32 @@ def _early_levels(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anch
     back from the read-back, prepared them one after the other (profiles/r06_gpu_idle_gaps.txt).  The autograd nodes are created
     later, by the level loop, around these results (ctx_ops.level_fused(pre=)).  None when the step is not the all-fused one."""
     c = begun["cache"]
-    K, D = pc.n_offsets, pc.feat_dim
     if (begun.get("used") or c is not getattr(pc, "_level_cache", None) or pc.level_scale is None
-            or c["key"] != _plan_key(pc, anchor, mask_anchor_bool) or not c["covers_all"] or c.get("identity")
+            or c["key"] != _plan_key(pc, anchor, mask_anchor_bool) or not c["covers_all"]
             or begun["anchor"] is not anchor or begun["mask"] is not mask_anchor_bool):
         return None
-    if not (FUSED_TRAINING and ROW_SOURCE and LEVEL_FUSED and RATE_FUSED and RATE_SIDE and not pc.adaptQ_per_channel):
-        return None
     pre = begun.get("hyper_pre")
-    if (pre is None or pre[0] is not hyper or pc.disable_hyper or hyper.dtype != torch.float32
-            or not (isinstance(pc.latent_codec, _EntropyBottleneck) and pc.latent_codec.filters == (3, 3, 3, 3))):
+    if pre is None or pre[0] is not hyper or any(n_ <= 0 for n_ in c["sizes"]):
         return None
-    if not (grid_offsets.dim() == 3 and pc._anchor_feat.is_cuda
-            and (feat.requires_grad or grid_scaling.requires_grad or grid_offsets.requires_grad)):
+    # the route of the step the renderer runs (statistics kept, on the rate subset the bookkeeping kernel lists)
+    route = _route(pc, c, anchor, hyper, feat, grid_offsets, grid_scaling, training=True, keep_stats=True, has_choose=True,
+                   has_chosen=True, allow_rate_lazy=True)
+    if not (route.rate_lazy and route.hyper == "forms"):       # (rate_lazy: every level on the kernel tier)
         return None
-    sizes, perm, plan = c["sizes"], c["perm"], c["plan"]
-    if any(n_ <= 0 for n_ in sizes) or not all(_mlp.supported(pc.get_grid_mlp[i_]) for (i_, _t, _o, _a) in plan):
-        return None
-    v_blocks = torch.split(pre[1], sizes)
+    v_blocks = torch.split(pre[1], c["sizes"])
     row_src = _ctx.RowSource(feat, grid_scaling, grid_offsets, True)
-    if not all(_ctx.level_fused_supported(pc.get_grid_mlp[i_], anchor, v_blocks[j_], row_src) for j_, (i_, _t, _o, _a) in enumerate(plan)):
-        return None
     row_src.sums_buffer()
-    n_tot = int(perm.shape[0])
-    dev = anchor.device
-    big_f = torch.empty(n_tot, feat.shape[1], dtype=torch.float32, device=dev)
-    big_s = torch.empty(n_tot, grid_scaling.shape[1], dtype=torch.float32, device=dev)
-    big_o = torch.empty(n_tot, 3 * K, dtype=torch.float32, device=dev)
-    out, row_off, src_vals = [], 0, None
-    for j, (i, _tc, orig, _a) in enumerate(plan):
-        n_l = sizes[j]
-        sl = slice(row_off, row_off + n_l)
-        if src_vals is None:
-            a_rows, pos_, bf, bs = orig, None, None, None
-            a_mask = mask_anchor_bool if (i >= 1 and mask_anchor_bool is not None) else None
-        else:
-            (a_rows, pos_, bf, bs), a_mask = src_vals, None
+    big = _level_outputs(c, feat, grid_scaling, pc.n_offsets, anchor.device)
+    out, row_off, ctx_src = [], 0, None
+    for j, (i, _tc, _orig, _a) in enumerate(c["plan"]):
+        args, _csr = _level_kernel_args(pc, c, j, anchor, v_blocks[j], ctx_src, mask_anchor_bool, row_src, big, row_off)
         seed = _ctx.next_seed()
-        res = _ctx.level_fused_launch(anchor, bf, bs, v_blocks[j], pc.get_grid_mlp[i], 2 * (D + 6 + 3 * K), a_rows, a_mask, pos_,
-                                      row_src, perm[row_off:row_off + n_l], (big_f[sl], big_s[sl], big_o[sl]),
-                                      (Q_FEAT0, Q_SCALING0, Q_OFFSETS0), seed)
-        out.append((res, seed))
-        row_off += n_l
+        out.append((_ctx.level_fused_launch(**args, seed=seed), seed))
+        row_off += c["sizes"][j]
         if i != 0:          # (what _next_context hands the next level, as values: the coded prefix lies at the front of the buffers)
-            src_vals = (c["ctx_idx"][i], c["ctx_pos"][i], big_f[:row_off], big_s[:row_off])
-    return dict(cache=c, row_src=row_src, big=(big_f, big_s, big_o), levels=out, inputs=(hyper, feat, grid_offsets, grid_scaling))
+            ctx_src = (c["ctx_idx"][i], c["ctx_pos"][i], big[0][:row_off], big[1][:row_off], c["ctx_csr"][i])
+    return dict(cache=c, route=route, row_src=row_src, big=big, levels=out,
+                inputs=(anchor, mask_anchor_bool, hyper, feat, grid_offsets, grid_scaling))
 
 
 def early_levels_begin(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, begun):
@@ -609,27 +680,136 @@ def early_levels_begin(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
         begun["early"] = _early_levels(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, begun)
 
 
-def context_model_coding_order(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, training,
-                               keep_stats, choose_mask=None, draw_choose=False, begun=None, allow_rate_lazy=False):
-    """_coding_order_impl with the level kernels enqueued ahead of the rate subset's read-back when the step allows it
-    (_early_levels); if what comes back does not fit them, once more the plain way."""
-    args = (pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, training, keep_stats)
+def context_model_coding_order(*args, begun=None, **kwargs):
+    """_coding_order_impl (same arguments) with the level kernels enqueued ahead of the rate subset's read-back when the step allows
+    it (_early_levels); if what comes back does not fit them, once more the plain way (begun is used up: nothing is enqueued early)."""
     try:
-        return _coding_order_impl(*args, choose_mask=choose_mask, draw_choose=draw_choose, begun=begun,
-                                  allow_rate_lazy=allow_rate_lazy, early_ok=EARLY_LEVELS)
+        return _coding_order_impl(*args, begun=begun, **kwargs)
     except _EarlyMismatch:
-        if begun is not None:
-            begun["used"] = True
-        return _coding_order_impl(*args, choose_mask=choose_mask, draw_choose=draw_choose, begun=begun,
-                                  allow_rate_lazy=allow_rate_lazy, early_ok=False)
+        begun["used"] = True
+        return _coding_order_impl(*args, begun=begun, **kwargs)
+
+
+def _level_record(st, j, loc, outs, Q_all, side, **extra):
+    """What rate_model reads of level j when its element-wise stages ran fused (keep_stats)."""
+    c, sizes, chosen_rows = st.c, st.c["sizes"], st.chosen_rows
+    i, _tc, orig, _a = c["plan"][j]
+    # chosen_rows lists the chosen anchors level by level: this level's are [lo, lo + len(loc))
+    span = None
+    if chosen_rows is not None:
+        lo_ = sum(int(l_.shape[0]) for l_ in st.locs[:j])
+        span = (chosen_rows, lo_, lo_ + int(loc.shape[0]))
+    sm = c.get("_sub_map")
+    lvl0 = sum(sizes[:j])
+    # `rows` (original indices of the chosen anchors) is only read when the subset is not listed level by level (span None):
+    # otherwise the mask rows come from ONE gather over all levels' chosen anchors
+    return dict(level=i, orig=orig, rows=orig[loc] if span is None else None, loc=loc, n_level=sizes[j], fused=True,
+                yf=outs[0], ys=outs[1], yo=outs[2], Q=Q_all, chosen=span, side=side, side_src=st.row_src,
+                sub_map=sm[lvl0:lvl0 + sizes[j]] if (sm is not None and span is not None) else None, **extra)
+
+
+def _level_kernel(st, j, hyp, loc, ctx_src, row_off):
+    """Kernel tier: input-row assembly + hidden layer + step sizes + noisy values of every row in one launch each way
+    (csrc/ctx_level.hip); the mean / scale outputs only on the rate subset's rows.  -> (hf, hs, ho, record or None)"""
+    args, csr = _level_kernel_args(st.pc, st.c, j, st.anchor, hyp, ctx_src, st.mask, st.row_src, st.big, row_off)
+    side = _ctx.RateSide() if st.route.rate_side else None
+    pre, seed = st.early["levels"][j] if st.early is not None else (None, None)
+    hf, hs, ho, Q_all, pred_sub = _ctx.level_fused(**args, loc=loc, csr=csr, side=side, seed=seed, rate_lazy=st.route.rate_lazy,
+                                                   pre=pre)
+    rec = _level_record(st, j, loc, (hf, hs, ho), Q_all, side, pred=pred_sub, lazy=st.route.rate_lazy) if st.keep_stats else None
+    return hf, hs, ho, rec
+
+
+def _level_launches(st, j, hyp, loc, ctx_src, row_off, joined):
+    """Separate-launch tier (round 4): rowcat / ctx_assemble -> level_mlp / mlp2_weights -> noise_quant, on the RowSource or on
+    the level's slices of the gathered parameters (st.params).  joined: the outputs go into st.big.  -> (hf, hs, ho, record or None)"""
+    pc, c, anchor = st.pc, st.c, st.anchor
+    i, _tc, orig, _a = c["plan"][j]
+    n_l, K = c["sizes"][j], pc.n_offsets
+    a_rows, a_mask, pos, base_f, base_s, csr = _level_inputs(ctx_src, i, orig, st.mask)
+    if base_f is None:                                                             # :1596-1600
+        feat_in = _ctx.rowcat([(anchor, a_rows, True, a_mask), (hyp, None, True)])
+    else:
+        feat_in = _ctx.ctx_assemble(anchor, base_f, base_s, hyp, a_rows, pos, csr)
+    # Only the three step-size outputs of mlp_grid are needed for EVERY row (they scale the noise /
+    # the rounding); the 172 mean/scale outputs are consumed by the rate model alone, i.e. by the
+    # `choose_mask` rows (15 % in training, :1658-1669; none at all when predict_bpp is off).  The
+    # reference evaluates all 175 outputs for all rows and throws 85-100 % of them away; here the
+    # second layer runs with its 3 step-size rows on every anchor and with all rows on the chosen
+    # anchors only (identical values: the same fp32 fma chains).
+    seq = pc.get_grid_mlp[i]
+    n_stat = 2 * (pc.feat_dim + 6 + 3 * K)
+    pred_sub = None
+    if st.keep_stats:
+        # mlp_grid has two consumers, the step sizes on every row and all outputs on the chosen rows: ONE
+        # autograd node serves both (weight gradients of the module filled once, the subset's input
+        # gradient merged row-wise into the full one)
+        qadj, pred_sub = _mlp.level_mlp(feat_in, loc, seq, n_stat)
+    else:
+        qadj = _mlp.mlp2_weights(feat_in, seq[0].weight, seq[0].bias, seq[2].weight[n_stat:], seq[2].bias[n_stat:])
+    # step sizes + noise (:1603-1616) in one launch; the rate of the chosen rows is one more (rate_model)
+    sl = slice(row_off, row_off + n_l)
+    outs = tuple(b[sl] for b in st.big) if joined else None
+    side = None
+    if st.row_src is not None:
+        side = _ctx.RateSide() if st.route.rate_side else None
+        hf, hs, ho, Q_all = _ctx.noise_quant(None, None, None, qadj, _Q0, outs=outs, src=st.row_src, rows=c["perm"][sl], side=side)
+    else:
+        feat_l, scal_l, off_l = st.params
+        hf, hs, ho, Q_all = _ctx.noise_quant(feat_l[j], scal_l[j], off_l[j].reshape(n_l, 3 * K), qadj, _Q0, outs=outs)
+    rec = _level_record(st, j, loc, (hf, hs, ho), Q_all, side, pred=pred_sub) if st.keep_stats else None
+    return hf, hs, ho, rec
+
+
+def _level_torch(st, j, hyp, loc, ctx_src):
+    """Torch tier: the reference's composition (:1594-1625) on the level's slices of the gathered parameters (st.params) — every
+    step off the device, evaluation, and shapes without kernels.  -> (hf, hs, ho, record or None)"""
+    pc, c, anchor, keep_stats = st.pc, st.c, st.anchor, st.keep_stats
+    i, _tc, orig, _a = c["plan"][j]
+    n_l, K = c["sizes"][j], pc.n_offsets
+    a_rows, a_mask, pos, base_f, base_s, _csr = _level_inputs(ctx_src, i, orig, st.mask)
+    if base_f is None:                                                             # :1596-1600
+        level_anchor = gather_unique(anchor if a_mask is None else anchor * a_mask.unsqueeze(1), a_rows)
+        feat_in = torch.cat([level_anchor, hyp.float()], dim=1)
+    else:
+        feat_in = torch.cat([gather_rows(anchor, a_rows), gather_rows(base_f, pos), gather_rows(base_s, pos), hyp], dim=1)
+    subset_mode = st.route.subset[j]        # (the step sizes on every row, the other outputs on the rate subset: see _level_launches)
+    if subset_mode:
+        seq = pc.get_grid_mlp[i]
+        n_stat = 2 * (pc.feat_dim + 6 + 3 * K)
+        qadj = _mlp.mlp2_weights(feat_in, seq[0].weight, seq[0].bias, seq[2].weight[n_stat:], seq[2].bias[n_stat:])
+        Q_feat, Q_scaling, Q_offsets = _step_sizes(qadj[:, 0:1], qadj[:, 1:2], qadj[:, 2:3])
+    else:
+        *pred, Q_feat, Q_scaling, Q_offsets = split_prediction(pc, grid_mlp(pc, i, feat_in))
+    hf, hs, ho = (t[j] for t in st.params)
+    qo = Q_offsets.view(n_l, K, -1) if pc.adaptQ_per_channel else Q_offsets.unsqueeze(1)
+    if st.training:                                                                # :1610-1616
+        hf = hf + torch.empty_like(hf).uniform_(-0.5, 0.5) * Q_feat
+        hs = hs + torch.empty_like(hs).uniform_(-0.5, 0.5) * Q_scaling
+        ho = ho + torch.empty_like(ho).uniform_(-0.5, 0.5) * qo
+    else:                                                                          # :1617-1625
+        hf = STE_multistep.apply(hf, Q_feat).detach()
+        hs = STE_multistep.apply(hs, Q_scaling).detach()
+        ho = STE_multistep.apply(ho, qo).detach()
+    ho = ho.reshape(-1, 3 * K)
+    if not keep_stats:
+        return hf, hs, ho, None
+    # the record of an unfused level: values, (mean, scale) x (feat, scaling, offsets) and step sizes, on the rate subset's rows
+    # (selected) or on every row of the level, for rate_model to pick the subset from
+    g = (lambda t: gather_unique(t, loc)) if subset_mode else (lambda t: t)
+    if subset_mode:
+        pred = split_prediction(pc, grid_mlp(pc, i, g(feat_in)))[:6]
+    rec = dict(level=i, orig=orig, rows=orig[loc] if subset_mode else None, n_level=n_l, selected=subset_mode,
+               vals=(g(hf), g(hs), g(ho)), pred=tuple(pred), Q=(g(Q_feat), g(Q_scaling), g(Q_offsets)))
+    return hf, hs, ho, rec
 
 
 def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, training,
-                       keep_stats, choose_mask=None, draw_choose=False, begun=None, allow_rate_lazy=False, early_ok=False):
+                       keep_stats, choose_mask=None, draw_choose=False, begun=None, allow_rate_lazy=False):
     """The level loop of multi_scale_generating (:1556-1652) in coding order.
 
     Returns (cache, feat_Q, scaling_Q, offsets_Q [rows in coding order: row r is anchor cache['perm'][r]],
-    likelihood_hyper [N-ordered], levels) where `levels` holds, per coded level, the slices the rate model
+    likelihood_hyper [N-ordered], levels, route) where `levels` holds, per coded level, the slices the rate model
     needs (only when keep_stats)."""
     K = pc.n_offsets
     _ctx._JOINED_GRADS.clear()
@@ -637,18 +817,19 @@ def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
         sel = anchor[mask_anchor_bool] if mask_anchor_bool is not None else anchor
         pc.level_scale = find_divide_scale(pc, sel, pc.target_ratio, pc.level_num)
     early = None
-    if (early_ok and begun is not None and training and keep_stats and allow_rate_lazy and anchor.is_cuda
-            and (draw_choose or choose_mask is not None)):
+    if begun is not None and training and keep_stats and allow_rate_lazy and (draw_choose or choose_mask is not None):
         early = begun.pop("early", None)
-        if early is not None and not all(a_ is b_ for a_, b_ in zip(early["inputs"], (hyper, feat, grid_offsets, grid_scaling))):
+        if early is not None and not all(a_ is b_ for a_, b_ in zip(
+                early["inputs"], (anchor, mask_anchor_bool, hyper, feat, grid_offsets, grid_scaling))):
             early = None                    # (launched for other tensors: its buffers are simply dropped)
         if early is None:
-            early = _early_levels(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, begun)
+            early_levels_begin(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, begun)
+            early = begun.pop("early", None)
     # level plan (cached) + the rate subset's rows per level, with one host read for both
     c, locs, chosen_rows = _plan_and_chosen(pc, anchor, mask_anchor_bool,
                                             choose_mask if (keep_stats and anchor.is_cuda) else None,
                                             draw=draw_choose and keep_stats and choose_mask is None, begun=begun)
-    if early is not None and (c is not early["cache"] or locs is None or chosen_rows is None):
+    if early is not None and (c is not early["cache"] or chosen_rows is None):
         raise _EarlyMismatch()
     if draw_choose and keep_stats and choose_mask is None:
         # the kernels drew the subset: keep a bool mask around for the (rare) level that does not take the fused path
@@ -661,46 +842,27 @@ def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
     # (host work that launches nothing — the row source, the level outputs' buffers, the path predicates — comes BEFORE the hyper
     #  step's launches: the device is idle behind the rate subset's read-back at this point and whatever the host still has to do
     #  between the hyper step's ~95 us kernel and the first level kernel shows as a gap; profiles/r06_gpu_idle_gaps.txt)
+    route = _route(pc, c, anchor, hyper, feat, grid_offsets, grid_scaling, training, keep_stats,
+                   has_choose=choose_mask is not None, has_chosen=chosen_rows is not None, allow_rate_lazy=allow_rate_lazy)
+    # (the same predicates on the same plan and the rate subset the early launch counted on: only the data could differ, above)
+    assert early is None or route == early["route"]
     # one gather per tensor into coding order, then contiguous per-level slices (split backward = one cat)
     full = c["covers_all"]
     if c.get("identity"):       # parameters are stored in coding order: the level slices are views, nothing moves
         in_order = lambda t: t
     else:
         in_order = lambda t: gather_unique(t, perm, full)
-    # training path on the device: the level's element-wise stages run as fused HIP kernels (ctx_ops)
-    fused = FUSED_TRAINING and training and anchor.is_cuda and not pc.adaptQ_per_channel
-    # When every level takes the fused path, features / scaling / offsets are not gathered at all: the level kernels
-    # read their rows of the parameter tensors through perm[lo:hi] and scatter the gradients back (ctx_ops.RowSource)
-    row_src = None
-    if (fused and ROW_SOURCE and not c.get("identity") and (not keep_stats or choose_mask is not None)
-            and all(_mlp.supported(pc.get_grid_mlp[i_]) for (i_, _t, _o, _a) in c["plan"])
-            and grid_offsets.dim() == 3 and (feat.requires_grad or grid_scaling.requires_grad or grid_offsets.requires_grad)):
-        if early is not None:
-            row_src = early["row_src"]
-        else:
-            row_src = _ctx.RowSource(feat, grid_scaling, grid_offsets, full)
-            row_src.sums_buffer()            # (its zero fill is queued here, in front of the hyper step's kernel)
-        feat_l = scal_l = off_l = None
-    else:
-        if early is not None:
-            raise _EarlyMismatch()
-        feat_l = torch.split(in_order(feat), sizes)
-        scal_l = torch.split(in_order(grid_scaling), sizes)
-        off_l = torch.split(in_order(grid_offsets), sizes)
-    n_tot = int(perm.shape[0])
+    row_src = params = big = None
     if early is not None:
-        big_f, big_s, big_o = early["big"]
-    elif fused:
-        big_f = torch.empty(n_tot, feat.shape[1], dtype=torch.float32, device=anchor.device)
-        big_s = torch.empty(n_tot, grid_scaling.shape[1], dtype=torch.float32, device=anchor.device)
-        big_o = torch.empty(n_tot, 3 * K, dtype=torch.float32, device=anchor.device)
-    # :1556.  Only the rate subset's hyper likelihood is ever read (:1662), and only as a sum of bits: on the fused
-    # training path the bottleneck returns the noisy latents already in coding order plus that sum (two launches);
-    # otherwise the likelihood of the chosen rows / of all rows as a tensor
-    hyp_p = None
-    eb_mine = isinstance(pc.latent_codec, _EntropyBottleneck) and pc.latent_codec.filters == (3, 3, 3, 3)
-    if (FUSED_TRAINING and training and keep_stats and choose_mask is not None and hyper.is_cuda and eb_mine
-            and not pc.disable_hyper and c.get("_nz") is not None and c["covers_all"] and hyper.dtype == torch.float32):
+        row_src, big = early["row_src"], early["big"]
+    elif route.row_source:
+        row_src = _ctx.RowSource(feat, grid_scaling, grid_offsets, full)
+        row_src.sums_buffer()            # (its zero fill is queued here, in front of the hyper step's kernel)
+    else:
+        params = tuple(torch.split(in_order(t), sizes) for t in (feat, grid_scaling, grid_offsets))
+    if big is None and route.fused:
+        big = _level_outputs(c, feat, grid_scaling, K, anchor.device)
+    if route.hyper == "forms":
         pre = begun.get("hyper_pre") if (begun is not None and begun.get("cache") is c) else None
         if pre is not None and pre[0] is not hyper:
             pre = None
@@ -709,184 +871,58 @@ def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
             pre[2] if pre is not None else _ctx.next_seed(), packed=begun.get("packed") if begun is not None else None,
             noisy=pre[1] if pre is not None else None, sizes=sizes if len(sizes) <= 4 else None,
             rows_orig=chosen_rows)
-        hyper_feat = None
-    elif FUSED_TRAINING and training and keep_stats and choose_mask is not None and hyper.is_cuda and eb_mine:
-        rows_h = chosen_rows if chosen_rows is not None else torch.nonzero(_as_mask(choose_mask))[:, 0]
-        hyper_feat, likelihood_hyper = pc.latent_codec(hyper, training=training, rows=rows_h)
     else:
-        hyper_feat, likelihood_hyper = pc.latent_codec(hyper, training=training)
-    if pc.disable_hyper and hyper_feat is not None:
-        hyper_feat = hyper_feat * 0
-
-    hyp_l = hyp_p if isinstance(hyp_p, tuple) else torch.split(hyp_p if hyp_p is not None else in_order(hyper_feat), sizes)
-
+        if route.hyper == "rows":
+            rows_h = chosen_rows if chosen_rows is not None else torch.nonzero(_as_mask(choose_mask))[:, 0]
+            hyper_feat, likelihood_hyper = pc.latent_codec(hyper, training=training, rows=rows_h)
+        else:
+            hyper_feat, likelihood_hyper = pc.latent_codec(hyper, training=training)
+        if pc.disable_hyper:
+            hyper_feat = hyper_feat * 0
+        hyp_p = in_order(hyper_feat)
+    hyp_l = hyp_p if isinstance(hyp_p, tuple) else torch.split(hyp_p, sizes)
+    # (what _route took for granted of the latent codec when it asked for the level kernels)
+    assert "kernel" not in route.tiers or (hyp_l[0].shape[1:], hyp_l[0].dtype, hyp_l[0].device) == (hyper.shape[1:], hyper.dtype,
+                                                                                                    hyper.device)
+    st = types.SimpleNamespace(pc=pc, c=c, anchor=anchor, mask=mask_anchor_bool, route=route, training=training,
+                               keep_stats=keep_stats, row_src=row_src, big=big, params=params, early=early, locs=locs,
+                               chosen_rows=chosen_rows)
     feat_q, scal_q, off_q, levels = [], [], [], []
-    ctx_src = None                      # (idx, pos, base_f, base_s): the coded context of the next level
-    # the fused levels write their outputs side by side into these (coding order), so no cat is needed at the end
-    row_off, joined = 0, fused
-    # The mean / scale outputs of the rate subset can stay INSIDE the rate kernels (cgs_rate_sub_*, round 6) when the rate model
-    # will take its one-node path (rate_model: every level fused, the subset listed level by level, the live fraction a host
-    # number) — decided here, before the first level runs, from the same predicates the loop and rate_model use
-    rate_lazy = bool(
-        allow_rate_lazy and RATE_FUSED and fused and LEVEL_FUSED and RATE_SIDE and keep_stats and choose_mask is not None
-        and chosen_rows is not None and locs is not None and row_src is not None
-        and (mask_anchor_bool is None or c.get("live_count") is not None) and pc._anchor_feat.is_cuda
-        and all(sizes[j_] == 0 or (_mlp.supported(pc.get_grid_mlp[i_])
-                                   and _ctx.level_fused_supported(pc.get_grid_mlp[i_], anchor, hyp_l[j_], row_src))
-                for j_, (i_, _t, _o, _a2) in enumerate(c["plan"])))
-    def level_record(j, i, orig, loc, outs, Q_all, side, **extra):
-        """What rate_model reads of level j when its element-wise stages ran fused (keep_stats)."""
-        # chosen_rows lists the chosen anchors level by level: this level's are [lo, lo + len(loc))
-        span = None
-        if chosen_rows is not None:
-            lo_ = sum(int(l_.shape[0]) for l_ in locs[:j])
-            span = (chosen_rows, lo_, lo_ + int(loc.shape[0]))
-        sm = c.get("_sub_map")
-        lvl0 = sum(sizes[:j])
-        # `rows` (original indices of the chosen anchors) is only read when the subset is not listed level by level (span None):
-        # otherwise the mask rows come from ONE gather over all levels' chosen anchors
-        return dict(level=i, orig=orig, rows=orig[loc] if span is None else None, loc=loc, n_level=sizes[j], fused=True,
-                    yf=outs[0], ys=outs[1], yo=outs[2], Q=Q_all, chosen=span, side=side, side_src=row_src,
-                    sub_map=sm[lvl0:lvl0 + sizes[j]] if (sm is not None and span is not None) else None, **extra)
-
+    ctx_src = None                      # (idx, pos, base_f, base_s, csr): the coded context of the next level
+    # the fused levels write their outputs side by side into st.big (coding order), so no cat is needed at the end
+    row_off, joined = 0, route.fused
     for j, (i, _tc, orig, _a) in enumerate(c["plan"]):
-        n_l = sizes[j]
-        if n_l > 0:
+        tier, rec = route.tiers[j], None
+        if tier is None:
+            if params is not None:
+                hf, hs, ho = params[0][j], params[1][j], params[2][j].reshape(-1, 3 * K)
+            else:       # an EMPTY level on the row-source path (tiny scenes): the per-level slices were never materialised
+                hf, hs, ho = (anchor.new_zeros(0, w, dtype=torch.float32) for w in (pc.feat_dim, 6, 3 * K))
+        else:
             loc = None
             if keep_stats and choose_mask is not None:
                 loc = locs[j] if locs is not None else torch.nonzero(choose_mask[orig])[:, 0]
-            subset_mode = _mlp.supported(pc.get_grid_mlp[i]) and (not keep_stats or loc is not None)
-            use_fused = fused and subset_mode
-            if (use_fused and LEVEL_FUSED and row_src is not None and joined
-                    and _ctx.level_fused_supported(pc.get_grid_mlp[i], anchor, hyp_l[j], row_src)):
-                # input-row assembly + hidden layer + step sizes + noisy values of every row: one launch each way
-                # (csrc/ctx_level.hip); the mean / scale outputs only on the rate subset's rows
-                sl = slice(row_off, row_off + n_l)
-                side = _ctx.RateSide() if (keep_stats and RATE_SIDE) else None
-                if ctx_src is None:
-                    # (masked anchors sit at the origin from level 1 up, :1758-1759: the product is folded into the gather)
-                    a_rows, pos_, base_f, base_s, csr = orig, None, None, None, None
-                    a_mask = mask_anchor_bool if (i >= 1 and mask_anchor_bool is not None) else None
-                else:
-                    a_rows, pos_, base_f, base_s, csr = ctx_src
-                    a_mask = None
-                pre_j, seed_j = early["levels"][j] if early is not None else (None, None)
-                hf, hs, ho, Q_all, pred_sub = _ctx.level_fused(
-                    anchor, base_f, base_s, hyp_l[j], pc.get_grid_mlp[i], 2 * (pc.feat_dim + 6 + 3 * K), loc if keep_stats else None,
-                    a_rows, a_mask, pos_, csr, row_src, perm[row_off:row_off + n_l], (big_f[sl], big_s[sl], big_o[sl]), side,
-                    (Q_FEAT0, Q_SCALING0, Q_OFFSETS0), seed=seed_j, rate_lazy=rate_lazy and keep_stats, pre=pre_j)
-                row_off += n_l
-                if keep_stats:
-                    levels.append(level_record(j, i, orig, loc, (hf, hs, ho), Q_all, side, pred=pred_sub, lazy=rate_lazy))
-                feat_q.append(hf)
-                scal_q.append(hs)
-                off_q.append(ho)
-                if i != 0:
-                    ctx_src = _next_context(c, i, feat_q, scal_q, (big_f, big_s, row_off))
-                continue
-            if early is not None:
-                raise _EarlyMismatch()
-            if rate_lazy:
-                raise RuntimeError("context model: a level left the fused path after the rate subset was made lazy")
-            if ctx_src is None:                                                        # :1596-1600
-                if use_fused:
-                    # (masked anchors sit at the origin from level 1 up, :1758-1759: the product is folded into the gather)
-                    a_mask = mask_anchor_bool if (i >= 1 and mask_anchor_bool is not None) else None
-                    feat_in = _ctx.rowcat([(anchor, orig, True, a_mask), (hyp_l[j], None, True)])
-                else:
-                    feat_in = torch.cat([level_anchors(anchor, mask_anchor_bool, i, orig), hyp_l[j].float()], dim=1)
+            if tier == "kernel":
+                hf, hs, ho, rec = _level_kernel(st, j, hyp_l[j], loc, ctx_src, row_off)
+            elif tier == "launches":
+                hf, hs, ho, rec = _level_launches(st, j, hyp_l[j], loc, ctx_src, row_off, joined)
             else:
-                idx, pos, base_f, base_s, csr = ctx_src
-                if use_fused:
-                    feat_in = _ctx.ctx_assemble(anchor, base_f, base_s, hyp_l[j], idx, pos, csr)
-                else:
-                    feat_in = torch.cat([gather_rows(anchor, idx), gather_rows(base_f, pos), gather_rows(base_s, pos),
-                                         hyp_l[j]], dim=1)
-            # Only the three step-size outputs of mlp_grid are needed for EVERY row (they scale the noise /
-            # the rounding); the 172 mean/scale outputs are consumed by the rate model alone, i.e. by the
-            # `choose_mask` rows (15 % in training, :1658-1669; none at all when predict_bpp is off).  The
-            # reference evaluates all 175 outputs for all rows and throws 85-100 % of them away; here the
-            # second layer runs with its 3 step-size rows on every anchor and with all rows on the chosen
-            # anchors only (identical values: the same fp32 fma chains).
-            feat_sub = pred_sub = None
-            if subset_mode:
-                seq = pc.get_grid_mlp[i]
-                D_ = pc.feat_dim
-                n_stat = 2 * (D_ + 6 + 3 * K)
-                if use_fused and keep_stats:
-                    # mlp_grid has two consumers, the step sizes on every row and all outputs on the chosen rows: ONE
-                    # autograd node serves both (weight gradients of the module filled once, the subset's input
-                    # gradient merged row-wise into the full one)
-                    qadj, pred_sub = _mlp.level_mlp(feat_in, loc, seq, n_stat)
-                else:
-                    qadj = _mlp.mlp2_weights(feat_in, seq[0].weight, seq[0].bias, seq[2].weight[n_stat:], seq[2].bias[n_stat:])
-            if use_fused:
-                # step sizes + noise (:1603-1616) in one launch; the rate of the chosen rows is one more (rate_model)
-                sl = slice(row_off, row_off + n_l)
-                outs = (big_f[sl], big_s[sl], big_o[sl]) if joined else None
-                side = None
-                if row_src is not None:
-                    side = _ctx.RateSide() if (keep_stats and RATE_SIDE) else None
-                    hf, hs, ho, Q_all = _ctx.noise_quant(None, None, None, qadj, (Q_FEAT0, Q_SCALING0, Q_OFFSETS0),
-                                                         outs=outs, src=row_src, rows=perm[row_off:row_off + n_l], side=side)
-                else:
-                    hf, hs, ho, Q_all = _ctx.noise_quant(feat_l[j], scal_l[j], off_l[j].reshape(n_l, 3 * K), qadj,
-                                                         (Q_FEAT0, Q_SCALING0, Q_OFFSETS0), outs=outs)
-                row_off += n_l
-                if keep_stats:
-                    levels.append(level_record(j, i, orig, loc, (hf, hs, ho), Q_all, side, pred=pred_sub))
-                feat_q.append(hf)
-                scal_q.append(hs)
-                off_q.append(ho)
-                if i != 0:
-                    ctx_src = _next_context(c, i, feat_q, scal_q, (big_f, big_s, row_off) if joined else None)
-                continue
-            joined = False
-            if subset_mode:
-                Q_feat = (Q_FEAT0 * (1 + torch.tanh(qadj[:, 0:1]))).clamp(1e-9)
-                Q_scaling = (Q_SCALING0 * (1 + torch.tanh(qadj[:, 1:2]))).clamp(1e-9)
-                Q_offsets = (Q_OFFSETS0 * (1 + torch.tanh(qadj[:, 2:3]))).clamp(1e-9)
-            else:
-                (mean_feat, scale_feat, mean_scaling, scale_scaling, mean_offsets, scale_offsets, Q_feat, Q_scaling,
-                 Q_offsets) = split_prediction(pc, grid_mlp(pc, i, feat_in))
-            hf, hs, ho = feat_l[j], scal_l[j], off_l[j]
-            qo = Q_offsets.view(n_l, K, -1) if pc.adaptQ_per_channel else Q_offsets.unsqueeze(1)
-            if training:                                                               # :1610-1616
-                hf = hf + torch.empty_like(hf).uniform_(-0.5, 0.5) * Q_feat
-                hs = hs + torch.empty_like(hs).uniform_(-0.5, 0.5) * Q_scaling
-                ho = ho + torch.empty_like(ho).uniform_(-0.5, 0.5) * qo
-            else:                                                                      # :1617-1625
-                hf = STE_multistep.apply(hf, Q_feat).detach()
-                hs = STE_multistep.apply(hs, Q_scaling).detach()
-                ho = STE_multistep.apply(ho, qo).detach()
-            ho = ho.reshape(-1, 3 * K)
-            if keep_stats and subset_mode:
-                g = lambda t: gather_unique(t, loc)
-                (mean_feat, scale_feat, mean_scaling, scale_scaling, mean_offsets, scale_offsets, _qf, _qs, _qo) = \
-                    split_prediction(pc, grid_mlp(pc, i, g(feat_in)))
-                levels.append(dict(level=i, orig=orig, rows=orig[loc], n_level=n_l, selected=True, feat=g(hf), scaling=g(hs),
-                                   offsets=g(ho), mf=mean_feat, sf=scale_feat, qf=g(Q_feat), ms=mean_scaling,
-                                   ss=scale_scaling, qs=g(Q_scaling), mo=mean_offsets, so=scale_offsets, qo=g(Q_offsets)))
-            elif keep_stats:
-                levels.append(dict(level=i, orig=orig, n_level=n_l, selected=False, feat=hf, scaling=hs, offsets=ho,
-                                   mf=mean_feat, sf=scale_feat, qf=Q_feat, ms=mean_scaling, ss=scale_scaling,
-                                   qs=Q_scaling, mo=mean_offsets, so=scale_offsets, qo=Q_offsets))
-        else:
-            if feat_l is not None:
-                hf, hs, ho = feat_l[j], scal_l[j], off_l[j].reshape(-1, 3 * K)
-            else:       # an EMPTY level on the row-source path (tiny scenes): the per-level slices were never materialised
-                hf, hs, ho = (anchor.new_zeros(0, w, dtype=torch.float32) for w in (pc.feat_dim, 6, 3 * K))
-            joined = joined and n_l == 0
+                hf, hs, ho, rec = _level_torch(st, j, hyp_l[j], loc, ctx_src)
+                joined = False
+        if rec is not None:
+            levels.append(rec)
         feat_q.append(hf)
         scal_q.append(hs)
         off_q.append(ho)
+        row_off += sizes[j]
         if i != 0:
-            ctx_src = _next_context(c, i, feat_q, scal_q)
-    if joined and row_off == n_tot:
-        return (c, _JoinRows.apply(big_f, *feat_q), _JoinRows.apply(big_s, *scal_q),
-                _JoinRows.apply(big_o, *off_q).view(-1, K, 3), likelihood_hyper, levels)
+            in_big = joined and tier in ("kernel", "launches")
+            ctx_src = _next_context(c, i, feat_q, scal_q, (big[0], big[1], row_off) if in_big else None)
+    if joined:
+        return (c, _JoinRows.apply(big[0], *feat_q), _JoinRows.apply(big[1], *scal_q),
+                _JoinRows.apply(big[2], *off_q).view(-1, K, 3), likelihood_hyper, levels, route)
     cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
-    return c, cat(feat_q), cat(scal_q), cat(off_q).view(-1, K, 3), likelihood_hyper, levels
+    return c, cat(feat_q), cat(scal_q), cat(off_q).view(-1, K, 3), likelihood_hyper, levels, route
 
 
 def _next_context(c, i, feat_q, scal_q, joined=None):
@@ -911,104 +947,84 @@ def draw_choose_mask(anchor, mask_anchor_bool, return_sum_bits):
     return choose_mask
 
 
-def rate_model(pc, anchor, binary_grid_masks, mask_anchor_bool, likelihood_hyper, levels, return_sum_bits,
-               choose_mask=None, live_count=None, masks_chosen_given=None):
-    """:1657-1707 — bits of a random 15 % subset (all anchors for return_sum_bits), per level on the level's rows.
-    masks_chosen_given: binary_grid_masks.reshape(n, K)[levels[0]["chosen"][0]] gathered by the caller (one node with the
-    visible rows' gather, _GatherUniquePair), or None."""
+def _bpp_report(pc, n, levels, raw, n_hyper=None, level_rows=None):
+    """each_level_bpp (:1697-1705) from the device values raw = [dead fraction, hyper, level...]; with level_rows (the rate
+    subset's rows per level) raw holds bit SUMS and the normalisations are done on the host when the report is read."""
+    divisors = None
+    if level_rows is not None:
+        width = pc.feat_dim + 6 + 3 * pc.n_offsets
+        divisors = [1.0, float(max(1, n_hyper))] + [float(max(1, r) * width) for r in level_rows]
+    return LevelBppReport(raw, [L["n_level"] / n for L in levels], divisors)
+
+
+def _rate_one_node(pc, n, levels, masks_chosen, hyper_sum, x_means, mask_anchor_rate, dead, counts):
+    """Every level on the fused rate kernel, the subset listed level after level, the live fraction a host number: the whole
+    of :1658-1705 is ONE autograd node (a launch per level + one for the scalar tail, each way).  -> (four 0-dim tensors, raw)"""
+    tensors, spans = [], []
+    for L in levels:
+        tensors += [L["yf"], L["ys"], L["yo"], L["Q"], L["pred"], L["loc"]]
+        spans.append((L["chosen"][1], L["chosen"][2]))
+    src0 = levels[0]["side_src"]
+    meta = dict(use_clamp=_enc.use_clamp, K=pc.n_offsets, spans=spans, sides=[L.get("side") for L in levels],
+                maps=[L.get("sub_map") for L in levels], finish=(float(mask_anchor_rate), *map(float, counts), float(dead)),
+                sum_table=src0.rate_sum_table(len(levels)) if src0 is not None else None)
+    return _ctx.rate_all(hyper_sum, masks_chosen, x_means, meta, tensors)
+
+
+def _rate_level_sums(pc, n, records, binary_grid_masks, masks_chosen_given, x_means, table):
+    """One launch per fused level record: gathers of the chosen rows + the three rate terms + their sums (ctx_ops.level_rate);
+    table: a zeroed [len(records), 3] the sums are written into (rate_finish reads it whole), or None.  -> the sums per record"""
     K = pc.n_offsets
-    n = anchor.shape[0]
-    dev = anchor.device
-    if choose_mask is None:
-        choose_mask = draw_choose_mask(anchor, mask_anchor_bool, return_sum_bits)
-    if mask_anchor_bool is None:
-        mask_anchor_rate = 1
-    elif live_count is not None:                # counted by the step's bookkeeping kernel: no reduction, a host scalar
-        mask_anchor_rate = live_count / mask_anchor_bool.numel()
-    else:
-        mask_anchor_rate = (mask_anchor_bool.sum() / mask_anchor_bool.numel()).detach()
-    from .entropy_bottleneck import HyperBitSum
-    hyper_sum = bit_hyper = None
-    if isinstance(likelihood_hyper, HyperBitSum):       # the fused training path already summed the bits
-        hyper_sum, n_hyper = likelihood_hyper.total, likelihood_hyper.numel
-    elif likelihood_hyper.shape[0] != n:        # already restricted to the chosen rows (context_model_coding_order)
-        bit_hyper = -torch.log2(likelihood_hyper)
-    else:
-        bit_hyper = -torch.log2(gather_unique(likelihood_hyper, torch.nonzero(_as_mask(choose_mask))[:, 0]))
-    if bit_hyper is not None:
-        hyper_sum, n_hyper = torch.sum(bit_hyper).reshape(1), bit_hyper.numel()
-    eg = pc.entropy_gaussian
-    all_fused = bool(levels) and all(L.get("fused") for L in levels) and pc._anchor_feat.is_cuda
-    if all_fused:
-        # every level goes through the fused rate kernel, which takes the three clamp centres as constants: one
-        # launch over the three parameter tensors (exp of the scaling logits on the fly) instead of exp + 3 reductions
-        xm_feat = xm_scaling = xm_offsets = None
-        src0 = next((L["side_src"] for L in levels if L.get("side_src") is not None), None)
-        # (valid when the level kernels read exactly pc's parameters: multi_scale_generating is also callable on other tensors)
-        s_is_pc = src0 is not None and ((pc.decoded_version and src0.s_orig is pc._scaling)
-                                        or getattr(src0.s_orig, "_cgs_exp_of", None) is pc._scaling)
-        if (src0 is not None and src0.rows_read == n and src0.f.data_ptr() == pc._anchor_feat.data_ptr()
-                and src0.o.data_ptr() == pc._offset.data_ptr() and s_is_pc):
-            x_means_fused = src0.means()        # accumulated by the level kernels while they read the rows
+    masks_chosen, sums = None, []
+    for L in records:
+        # (a lazy mean / scale branch lives in rate_all's kernels: _route only makes a level lazy when the step's rate model is
+        #  _rate_one_node, and the callers hand rate_model the live count such a step has)
+        assert not L.get("lazy")
+        if L.get("chosen") is not None:
+            # the mask rows of ALL levels' chosen anchors in one gather (one scatter + one zero fill on the way
+            # back instead of an [N,K] gradient buffer and an accumulation per level)
+            if masks_chosen is None:
+                masks_chosen = (masks_chosen_given if masks_chosen_given is not None
+                                else gather_unique(binary_grid_masks.reshape(n, K), L["chosen"][0]))
+            m_rows, g_rows = masks_chosen[L["chosen"][1]:L["chosen"][2]], None
         else:
-            x_means_fused = _ctx.means3(pc._anchor_feat, pc._scaling, pc._offset, exp_b=not pc.decoded_version)
-    else:
-        xm_feat, xm_scaling, xm_offsets = pc._anchor_feat.mean(), pc.get_scaling.mean(), pc._offset.mean()
-    if (all_fused and not return_sum_bits and all(L.get("chosen") is not None for L in levels)
-            and (mask_anchor_bool is None or live_count is not None)):
-        # every level on the fused rate kernel, the subset listed level after level, the live fraction a host number:
-        # the whole of :1658-1705 is ONE autograd node (a launch per level + one for the scalar tail, each way)
-        chosen_all = levels[0]["chosen"][0]
-        masks_chosen = (masks_chosen_given if masks_chosen_given is not None
-                        else gather_unique(binary_grid_masks.reshape(n, K), chosen_all))
-        tensors, spans, sides, maps, level_rows = [], [], [], [], []
-        n_feat = n_scaling = n_offsets = 0
-        for L in levels:
-            n_sub = int(L["loc"].shape[0])
-            tensors += [L["yf"], L["ys"], L["yo"], L["Q"], L["pred"], L["loc"]]
-            spans.append((L["chosen"][1], L["chosen"][2]))
-            sides.append(L.get("side"))
-            maps.append(L.get("sub_map"))
-            n_feat, n_scaling, n_offsets = n_feat + n_sub * pc.feat_dim, n_scaling + n_sub * 6, n_offsets + n_sub * 3 * K
-            level_rows.append(n_sub)
-        dead = 0.0 if mask_anchor_bool is None else 1.0 - live_count / mask_anchor_bool.numel()
-        meta = dict(use_clamp=_enc.use_clamp, K=K, spans=spans, sides=sides, maps=maps,
-                    finish=(float(mask_anchor_rate), float(n_feat), float(n_scaling), float(n_offsets), float(dead)),
-                    sum_table=src0.rate_sum_table(len(levels)) if src0 is not None else None)
-        out4, raw = _ctx.rate_all(hyper_sum, masks_chosen, x_means_fused, meta, tensors)      # (out4: four 0-dim tensors)
-        feat_dim = pc.feat_dim + 6 + 3 * K
-        divisors = [1.0, float(max(1, n_hyper))] + [float(max(1, r) * feat_dim) for r in level_rows]
-        each_level_bpp = LevelBppReport(raw, [L["n_level"] / n for L in levels], divisors)
-        return out4[0], out4[1], out4[2], out4[3], each_level_bpp
-    if any(L.get("lazy") for L in levels):
-        raise RuntimeError("rate_model: levels with a lazy mean / scale branch need the one-node rate path")
+            m_rows, g_rows = binary_grid_masks.reshape(n, K), L["rows"]
+        sums.append(_ctx.level_rate(L["yf"], L["ys"], L["yo"], L["Q"], L["pred"], L["loc"], m_rows, g_rows, x_means,
+                                    _enc.use_clamp, K, side=L.get("side"), out=table[len(sums)] if table is not None else None))
+    return sums
+
+
+def _rate_vector_tail(sums, hyper_sum, mask_anchor_bool, mask_anchor_rate, counts):
+    """The scalar tail of :1687-1705 over the fused levels' sums as a handful of [3]-vector ops (the element-by-element version
+    is ~60 one-element launches per step).  -> (four 0-dim tensors, raw)"""
+    n_feat, n_scaling, n_offsets = counts
+    S = torch.stack(sums)                                     # [levels, 3] = (feat, scaling, offsets) bits
+    tot = S.sum(dim=0) * mask_anchor_rate
+    s_hyper = hyper_sum.reshape(()) * mask_anchor_rate
+    bit_per_feat_param = tot[0] / max(1, n_feat)
+    bit_per_scaling_param = tot[1] / max(1, n_scaling)
+    bit_per_offsets_param = tot[2] / max(1, n_offsets)
+    bit_per_param = (tot.sum() + s_hyper) / max(1, n_feat + n_scaling + n_offsets)
+    with torch.no_grad():
+        raw = torch.cat([(1 - mask_anchor_bool.float().mean()).reshape(1) if mask_anchor_bool is not None
+                         else torch.zeros(1, device=S.device), s_hyper.detach().reshape(1), S.detach().sum(dim=1)])
+    return (bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param), raw
+
+
+def _rate_elementwise(pc, n, levels, binary_grid_masks, mask_anchor_bool, choose_mask, hyper_sum, n_hyper, bit_hyper,
+                      mask_anchor_rate, x_means3, fused_sums, return_sum_bits):
+    """:1664-1705 level by level in torch — the levels of the torch tier, mixed fused / unfused levels, return_sum_bits;
+    fused_sums: _rate_level_sums of the fused records among `levels`, x_means3: the three clamp centres (unfused levels)."""
+    K, eg = pc.n_offsets, pc.entropy_gaussian
+    dev = hyper_sum.device
     masks30 = None                              # [N, 3K] mask weights, only the unfused levels read it
     zero = torch.zeros((), device=dev)
     s_feat, s_scaling, s_offsets = zero, zero, zero
     n_feat = n_scaling = n_offsets = 0
     level_bpp_sums, level_rows = [], []
-    x_means = masks_chosen = None
-    fused_sums = []
-    # the fused levels write their three sums into consecutive rows of one zeroed table (rate_finish reads it whole)
-    S_table = torch.zeros(len(levels), 3, dtype=torch.float32, device=dev) if all_fused else None
     for L in levels:
-        if L.get("fused"):                      # one launch: gathers of the chosen rows + the three rate terms + sums
-            if x_means is None:
-                x_means = x_means_fused if all_fused else torch.stack([xm_feat, xm_scaling, xm_offsets]).detach()
+        if L.get("fused"):
             n_sub = int(L["loc"].shape[0])
-            if L.get("chosen") is not None:
-                # the mask rows of ALL levels' chosen anchors in one gather (one scatter + one zero fill on the way
-                # back instead of an [N,K] gradient buffer and an accumulation per level)
-                if masks_chosen is None:
-                    masks_chosen = (masks_chosen_given if masks_chosen_given is not None
-                                    else gather_unique(binary_grid_masks.reshape(n, K), L["chosen"][0]))
-                m_rows, g_rows = masks_chosen[L["chosen"][1]:L["chosen"][2]], None
-            else:
-                m_rows, g_rows = binary_grid_masks.reshape(n, K), L["rows"]
-            sums = _ctx.level_rate(L["yf"], L["ys"], L["yo"], L["Q"], L["pred"], L["loc"], m_rows, g_rows, x_means,
-                                   _enc.use_clamp, K, side=L.get("side"),
-                                   out=S_table[len(fused_sums)] if S_table is not None else None)
-            fused_sums.append(sums)
             n_feat, n_scaling, n_offsets = n_feat + n_sub * pc.feat_dim, n_scaling + n_sub * 6, n_offsets + n_sub * 3 * K
             level_rows.append(n_sub)
             continue
@@ -1019,40 +1035,15 @@ def rate_model(pc, anchor, binary_grid_masks, mask_anchor_bool, likelihood_hyper
             loc = torch.nonzero(choose_mask[L["orig"]])[:, 0]
             rows = L["orig"][loc]
             g = lambda t, loc=loc: gather_unique(t, loc)
-        bf = eg(g(L["feat"]), g(L["mf"]), g(L["sf"]), g(L["qf"]), xm_feat)
-        bs = eg(g(L["scaling"]), g(L["ms"]), g(L["ss"]), g(L["qs"]), xm_scaling)
+        bf, bs, bo = (eg(g(L["vals"][k]), g(L["pred"][2 * k]), g(L["pred"][2 * k + 1]), g(L["Q"][k]), x_means3[k]) for k in range(3))
         if masks30 is None:
             masks30 = binary_grid_masks.repeat(1, 1, 3).view(-1, 3 * K)
-        bo = eg(g(L["offsets"]), g(L["mo"]), g(L["so"]), g(L["qo"]), xm_offsets) * gather_unique(masks30, rows)
+        bo = bo * gather_unique(masks30, rows)
         s_feat, s_scaling, s_offsets = s_feat + bf.sum(), s_scaling + bs.sum(), s_offsets + bo.sum()
         n_feat, n_scaling, n_offsets = n_feat + bf.numel(), n_scaling + bs.numel(), n_offsets + bo.numel()
         level_rows.append(int(rows.shape[0]))
         level_bpp_sums.append((bf.detach().sum() + bs.detach().sum() + bo.detach().sum()))
-
-    if fused_sums and len(fused_sums) == len(levels) and not return_sum_bits:
-        feat_dim = pc.feat_dim + 6 + 3 * K
-        divisors = [1.0, float(max(1, n_hyper))] + [float(max(1, r) * feat_dim) for r in level_rows]
-        if S_table is not None and (mask_anchor_bool is None or live_count is not None):
-            # all levels came from the fused rate kernel and the live fraction is a host number: the whole scalar tail
-            # of :1687-1705 is one launch (forward) / one launch (backward)
-            dead = 0.0 if mask_anchor_bool is None else 1.0 - live_count / mask_anchor_bool.numel()
-            out4, raw = _ctx.rate_finish(fused_sums, hyper_sum, mask_anchor_rate, n_feat, n_scaling, n_offsets, dead)
-            each_level_bpp = LevelBppReport(raw, [L["n_level"] / n for L in levels], divisors)
-            return out4[0], out4[1], out4[2], out4[3], each_level_bpp
-        # the same as a handful of [3]-vector ops (the element-by-element version is ~60 one-element launches per step)
-        S = torch.stack(fused_sums)                               # [levels, 3] = (feat, scaling, offsets) bits
-        tot = S.sum(dim=0) * mask_anchor_rate
-        s_hyper = hyper_sum.reshape(()) * mask_anchor_rate
-        bit_per_feat_param = tot[0] / max(1, n_feat)
-        bit_per_scaling_param = tot[1] / max(1, n_scaling)
-        bit_per_offsets_param = tot[2] / max(1, n_offsets)
-        bit_per_param = (tot.sum() + s_hyper) / max(1, n_feat + n_scaling + n_offsets)
-        with torch.no_grad():
-            raw = torch.cat([(1 - mask_anchor_bool.float().mean()).reshape(1) if mask_anchor_bool is not None
-                             else torch.zeros(1, device=dev), s_hyper.detach().reshape(1), S.detach().sum(dim=1)])
-        each_level_bpp = LevelBppReport(raw, [L["n_level"] / n for L in levels], divisors)
-        return bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, each_level_bpp
-    for sums in fused_sums:                     # mixed fused / unfused levels: element-wise bookkeeping
+    for sums in fused_sums:
         s_feat, s_scaling, s_offsets = s_feat + sums[0], s_scaling + sums[1], s_offsets + sums[2]
         level_bpp_sums.append(sums.detach().sum())
 
@@ -1076,8 +1067,78 @@ def rate_model(pc, anchor, binary_grid_masks, mask_anchor_bool, likelihood_hyper
                  bit_per_hyper_param.detach()]
         stats += [s / max(1, r) / feat_dim for s, r in zip(level_bpp_sums, level_rows)]
         dev_stats = torch.stack([t.reshape(()).float() for t in stats])
-    each_level_bpp = LevelBppReport(dev_stats, [L["n_level"] / n for L in levels])
-    return bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, each_level_bpp
+    return (bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param,
+            _bpp_report(pc, n, levels, dev_stats))
+
+
+def rate_model(pc, anchor, binary_grid_masks, mask_anchor_bool, likelihood_hyper, levels, return_sum_bits,
+               choose_mask=None, live_count=None, masks_chosen_given=None, levels_fused=False):
+    """:1657-1707 — bits of a random 15 % subset (all anchors for return_sum_bits), per level on the level's rows.
+    masks_chosen_given: binary_grid_masks.reshape(n, K)[levels[0]["chosen"][0]] gathered by the caller (one node with the
+    visible rows' gather, _GatherUniquePair), or None.  levels_fused: the step's _Route.levels_fused.
+    Four tails: _rate_one_node; a launch per level (_rate_level_sums) + ctx_ops.rate_finish, or + _rate_vector_tail where the live
+    fraction is a device value or pc's own parameters are not on the device; _rate_elementwise for everything else."""
+    K = pc.n_offsets
+    n = anchor.shape[0]
+    dev = anchor.device
+    if choose_mask is None:
+        choose_mask = draw_choose_mask(anchor, mask_anchor_bool, return_sum_bits)
+    live_known = mask_anchor_bool is None or live_count is not None
+    if mask_anchor_bool is None:
+        mask_anchor_rate = 1
+    elif live_count is not None:                # counted by the step's bookkeeping kernel: no reduction, a host scalar
+        mask_anchor_rate = live_count / mask_anchor_bool.numel()
+    else:
+        mask_anchor_rate = (mask_anchor_bool.sum() / mask_anchor_bool.numel()).detach()
+    from .entropy_bottleneck import HyperBitSum
+    hyper_sum = bit_hyper = None
+    if isinstance(likelihood_hyper, HyperBitSum):       # the fused training path already summed the bits
+        hyper_sum, n_hyper = likelihood_hyper.total, likelihood_hyper.numel
+    elif likelihood_hyper.shape[0] != n:        # already restricted to the chosen rows (context_model_coding_order)
+        bit_hyper = -torch.log2(likelihood_hyper)
+    else:
+        bit_hyper = -torch.log2(gather_unique(likelihood_hyper, torch.nonzero(_as_mask(choose_mask))[:, 0]))
+    if bit_hyper is not None:
+        hyper_sum, n_hyper = torch.sum(bit_hyper).reshape(1), bit_hyper.numel()
+    on_dev = levels_fused and pc._anchor_feat.is_cuda
+    x_means3 = None
+    if on_dev:
+        # every level goes through the fused rate kernel, which takes the three clamp centres as constants: one
+        # launch over the three parameter tensors (exp of the scaling logits on the fly) instead of exp + 3 reductions
+        src0 = next((L["side_src"] for L in levels if L.get("side_src") is not None), None)
+        # (valid when the level kernels read exactly pc's parameters: multi_scale_generating is also callable on other tensors)
+        s_is_pc = src0 is not None and ((pc.decoded_version and src0.s_orig is pc._scaling)
+                                        or getattr(src0.s_orig, "_cgs_exp_of", None) is pc._scaling)
+        if (src0 is not None and src0.rows_read == n and src0.f.data_ptr() == pc._anchor_feat.data_ptr()
+                and src0.o.data_ptr() == pc._offset.data_ptr() and s_is_pc):
+            x_means = src0.means()        # accumulated by the level kernels while they read the rows
+        else:
+            x_means = _ctx.means3(pc._anchor_feat, pc._scaling, pc._offset, exp_b=not pc.decoded_version)
+    else:
+        x_means3 = (pc._anchor_feat.mean(), pc.get_scaling.mean(), pc._offset.mean())
+        x_means = torch.stack(x_means3).detach() if any(L.get("fused") for L in levels) else None
+    scalar_tail = levels_fused and not return_sum_bits          # the four rates from the fused levels' sums alone
+    if scalar_tail:
+        level_rows = [int(L["loc"].shape[0]) for L in levels]
+        counts = tuple(sum(level_rows) * w for w in (pc.feat_dim, 6, 3 * K))
+        dead = (0.0 if mask_anchor_bool is None else 1.0 - live_count / mask_anchor_bool.numel()) if live_known else None
+    if scalar_tail and on_dev and live_known and levels[0]["chosen"] is not None:
+        masks_chosen = (masks_chosen_given if masks_chosen_given is not None
+                        else gather_unique(binary_grid_masks.reshape(n, K), levels[0]["chosen"][0]))
+        out4, raw = _rate_one_node(pc, n, levels, masks_chosen, hyper_sum, x_means, mask_anchor_rate, dead, counts)
+    else:
+        # the fused levels write their three sums into consecutive rows of one zeroed table (rate_finish reads it whole)
+        table = torch.zeros(len(levels), 3, dtype=torch.float32, device=dev) if on_dev else None
+        sums = _rate_level_sums(pc, n, [L for L in levels if L.get("fused")], binary_grid_masks, masks_chosen_given, x_means, table)
+        if not scalar_tail:
+            return _rate_elementwise(pc, n, levels, binary_grid_masks, mask_anchor_bool, choose_mask, hyper_sum, n_hyper, bit_hyper,
+                                     mask_anchor_rate, x_means3, sums, return_sum_bits)
+        if on_dev and live_known:
+            # the live fraction is a host number: the whole scalar tail of :1687-1705 is one launch each way
+            out4, raw = _ctx.rate_finish(sums, hyper_sum, mask_anchor_rate, *counts, dead)
+        else:
+            out4, raw = _rate_vector_tail(sums, hyper_sum, mask_anchor_bool, mask_anchor_rate, counts)
+    return out4[0], out4[1], out4[2], out4[3], _bpp_report(pc, n, levels, raw, n_hyper, level_rows)
 
 
 class LevelBppReport(list):
@@ -1125,18 +1186,18 @@ def multi_scale_generating(pc, anchor, hyper, feat, grid_offsets, grid_scaling, 
     if predict_bpp:
         choose_mask = (choose_mask_provider(anchor, mask_anchor_bool) if (choose_mask_provider is not None and not return_sum_bits)
                        else draw_choose_mask(anchor, mask_anchor_bool, return_sum_bits))
-    c, feat_p, scal_p, off_p, likelihood_hyper, levels = context_model_coding_order(
+    c, feat_p, scal_p, off_p, likelihood_hyper, levels, route = context_model_coding_order(
         pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, training, keep_stats=predict_bpp,
         choose_mask=choose_mask, allow_rate_lazy=not return_sum_bits)
     if predict_bpp and return_sum_bits:
-        return rate_model(pc, anchor, binary_grid_masks, mask_anchor_bool, likelihood_hyper, levels, True, choose_mask)
+        return rate_model(pc, anchor, binary_grid_masks, mask_anchor_bool, likelihood_hyper, levels, True, choose_mask,
+                          levels_fused=route.levels_fused)
     feat_after_Q, grid_scaling_after_Q, grid_offsets_after_Q = (_unpermute(c, t) for t in (feat_p, scal_p, off_p))
     if not predict_bpp:
         return feat_after_Q, grid_scaling_after_Q, grid_offsets_after_Q
     # (levels whose mean / scale branch lives in the rate kernels need the one-node rate path, i.e. the live count as a host number)
-    lazy = any(L.get("lazy") for L in levels)
     rates = rate_model(pc, anchor, binary_grid_masks, mask_anchor_bool, likelihood_hyper, levels, False, choose_mask,
-                       live_count=c.get("live_count") if lazy else None)
+                       live_count=c.get("live_count") if route.rate_lazy else None, levels_fused=route.levels_fused)
     return (feat_after_Q, grid_scaling_after_Q, grid_offsets_after_Q) + tuple(rates)
 
 
@@ -1172,7 +1233,7 @@ def multi_scale_generating_visible(pc, anchor, hyper, feat, grid_offsets, grid_s
             draw = True
         else:
             choose_mask = draw_choose_mask(anchor, mask_anchor_bool, False)
-    c, feat_p, scal_p, off_p, likelihood_hyper, levels = context_model_coding_order(
+    c, feat_p, scal_p, off_p, likelihood_hyper, levels, route = context_model_coding_order(
         pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, training, keep_stats=predict_bpp,
         choose_mask=choose_mask, draw_choose=draw, begun=begun, allow_rate_lazy=True)
     if draw:
@@ -1193,12 +1254,11 @@ def multi_scale_generating_visible(pc, anchor, hyper, feat, grid_offsets, grid_s
     # (binary_grid_masks may be a callable: the caller creates the mask's autograd node after the level loop's nodes)
     rate = lambda masks_chosen=None: tuple(rate_model(
         pc, anchor, binary_grid_masks() if callable(binary_grid_masks) else binary_grid_masks, mask_anchor_bool, likelihood_hyper,
-        levels, False, choose_mask, live_count=c.get("live_count"), masks_chosen_given=masks_chosen))
+        levels, False, choose_mask, live_count=c.get("live_count"), masks_chosen_given=masks_chosen,
+        levels_fused=route.levels_fused))
     # the rows whose mask weights the rate model will gather, when it is one list for all levels (the caller may gather them in
     # the same node as its own rows of the mask: _GatherUniquePair)
-    rate.chosen_rows = (levels[0]["chosen"][0] if (levels and all(L.get("fused") and L.get("chosen") is not None
-                                                                     and L["chosen"][0] is levels[0]["chosen"][0] for L in levels))
-                        else None)
+    rate.chosen_rows = levels[0]["chosen"][0] if (route.levels_fused and levels[0]["chosen"] is not None) else None
     if defer_rate:      # the caller enqueues the rate model where it fills a read-back bubble (renderer.py)
         return outs + (rate,)
     return outs + rate()

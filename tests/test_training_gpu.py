@@ -366,6 +366,53 @@ def test_early_launches_change_nothing_but_the_order():
         assert close(x, y)
 
 
+@pytest.mark.parametrize("knob_off", [None, "ROW_SOURCE", "LEVEL_FUSED", "RATE_FUSED", "RATE_SIDE", "FUSED_TRAINING", "EARLY_LEVELS"])
+def test_early_launch_and_level_loop_agree_on_the_route(monkeypatch, knob_off):
+    """The early launch (context_model._early_levels) and the level loop answer "is this the all-fused step?" from the same
+    predicates: on a cached plan they can only disagree over data.  Second step of a scene, launches counted:
+    * all knobs at their defaults: one early launch per non-empty level and no other launch of the level kernel — nothing is
+      launched twice — and the context model runs once;
+    * any one knob off: nothing is enqueued early and the context model still runs once (no _EarlyMismatch rerun), with finite,
+      non-zero results and gradients."""
+    from contextgs_amd import context_model as cm, ctx_ops
+    for knob in ("ROW_SOURCE", "LEVEL_FUSED", "RATE_FUSED", "RATE_SIDE", "FUSED_TRAINING", "EARLY_LEVELS"):
+        monkeypatch.setattr(cm, knob, knob != knob_off)
+    pc, cams, pipe, bg = _setup(N=12000, W=256, H=144, seed=7)
+    _ctx_step(pc, cams[0], pipe, bg)                     # builds the plan
+    seen = {"early": 0, "launch": 0, "mismatch": 0}
+    real_early, real_launch = ctx_ops.level_fused_launch, ctx_ops._LevelFused.launch
+
+    def early(*a, **k):
+        seen["early"] += 1
+        return real_early(*a, **k)
+
+    def launch(*a, **k):
+        seen["launch"] += 1
+        return real_launch(*a, **k)
+
+    def mismatch(self, *a):
+        seen["mismatch"] += 1
+        Exception.__init__(self, *a)
+    ctx_ops.level_fused_launch, ctx_ops._LevelFused.launch, cm._EarlyMismatch.__init__ = early, staticmethod(launch), mismatch
+    try:
+        pkg, loss = _ctx_step(pc, cams[1], pipe, bg)     # a step on the cached plan
+    finally:
+        ctx_ops.level_fused_launch, ctx_ops._LevelFused.launch = real_early, staticmethod(real_launch)
+        del cm._EarlyMismatch.__init__
+    levels = sum(1 for s in pc._level_cache["sizes"] if s > 0)
+    print(f"[route] {knob_off}: levels {levels}, early launches {seen['early']}, level-kernel launches {seen['launch']}, "
+          f"reruns {seen['mismatch']}")
+    assert levels >= 2 and seen["mismatch"] == 0
+    if knob_off is None:
+        assert seen["early"] == levels and seen["launch"] == levels
+    else:
+        assert seen["early"] == 0
+    assert math.isfinite(loss) and torch.isfinite(pkg["render"]).all() and float(pkg["bit_per_param"]) > 0
+    for name in ("_anchor", "_offset", "_mask", "_anchor_feat", "_scaling", "_hyper_latent"):
+        g = getattr(pc, name).grad
+        assert g is not None and torch.isfinite(g).all() and float(g.abs().sum()) > 0, name
+
+
 def test_hyper_latent_gradient_rows_written_by_the_levels_equal_the_gathered_blocks():
     """The fused levels' backward writes the hyper latents' gradient rows straight into one buffer in parameter order
     (ctx_ops.HyperDirect, cgs_ctx_level_bwd2) instead of handing one strided block per level to the hyper prior's backward, which
