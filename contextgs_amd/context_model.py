@@ -479,10 +479,13 @@ def gather_unique_pair_attach(x, idx_a, vals_a, idx_b):
 
 class _JoinRows(torch.autograd.Function):
     """The row slices `parts` (consecutive, covering `whole`) were written in place by the fused kernels:
-    return `whole` as their concatenation without copying; the backward hands each part a view of the gradient."""
+    return `whole` as their concatenation without copying; the backward hands each part a view of the gradient.
+    row_src: the step's ctx_ops.RowSource, whose record the backward notes the gradient in (a context level may add its prefix
+    gradient into the rows in front of its own: ctx_ops.JoinedGrads) — or None (no fused level node: nothing is noted)."""
 
     @staticmethod
-    def forward(ctx, whole, *parts):
+    def forward(ctx, row_src, whole, *parts):
+        ctx.joined = None if row_src is None else row_src.joined
         ctx.sizes = [int(p.shape[0]) for p in parts]
         assert sum(ctx.sizes) == whole.shape[0]
         ctx.set_materialize_grads(False)     # (a context level that summed its prefix gradient in place returns none: no zero tensor for it)
@@ -491,10 +494,11 @@ class _JoinRows(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         if g is None:
-            return (None,) * (1 + len(ctx.sizes))
+            return (None,) * (2 + len(ctx.sizes))
         g = g.contiguous()
-        _ctx.note_joined_grad(g)        # (a context level may add its prefix gradient into the rows in front of its own: ctx_ops._grad_prefix)
-        return (None, *torch.split(g, ctx.sizes))
+        if ctx.joined is not None:
+            ctx.joined.note(g)
+        return (None, None, *torch.split(g, ctx.sizes))
 
 
 def _rowcat_ok(x):
@@ -812,7 +816,6 @@ def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
     likelihood_hyper [N-ordered], levels, route) where `levels` holds, per coded level, the slices the rate model
     needs (only when keep_stats)."""
     K = pc.n_offsets
-    _ctx._JOINED_GRADS.clear()
     if pc.level_scale is None:                                                         # :1559
         sel = anchor[mask_anchor_bool] if mask_anchor_bool is not None else anchor
         pc.level_scale = find_divide_scale(pc, sel, pc.target_ratio, pc.level_num)
@@ -917,10 +920,10 @@ def _coding_order_impl(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
         row_off += sizes[j]
         if i != 0:
             in_big = joined and tier in ("kernel", "launches")
-            ctx_src = _next_context(c, i, feat_q, scal_q, (big[0], big[1], row_off) if in_big else None)
+            ctx_src = _next_context(c, i, feat_q, scal_q, (big[0], big[1], row_off, row_src) if in_big else None)
     if joined:
-        return (c, _JoinRows.apply(big[0], *feat_q), _JoinRows.apply(big[1], *scal_q),
-                _JoinRows.apply(big[2], *off_q).view(-1, K, 3), likelihood_hyper, levels, route)
+        return (c, _JoinRows.apply(row_src, big[0], *feat_q), _JoinRows.apply(row_src, big[1], *scal_q),
+                _JoinRows.apply(row_src, big[2], *off_q).view(-1, K, 3), likelihood_hyper, levels, route)
     cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
     return c, cat(feat_q), cat(scal_q), cat(off_q).view(-1, K, 3), likelihood_hyper, levels, route
 
@@ -931,8 +934,8 @@ def _next_context(c, i, feat_q, scal_q, joined=None):
     if len(feat_q) == 1:
         base_f, base_s = feat_q[0], scal_q[0]
     elif joined is not None:            # the prefix already lies contiguously in the level output buffers
-        big_f, big_s, rows = joined
-        base_f, base_s = _JoinRows.apply(big_f[:rows], *feat_q), _JoinRows.apply(big_s[:rows], *scal_q)
+        big_f, big_s, rows, row_src = joined
+        base_f, base_s = _JoinRows.apply(row_src, big_f[:rows], *feat_q), _JoinRows.apply(row_src, big_s[:rows], *scal_q)
     else:
         base_f, base_s = torch.cat(feat_q, dim=0), torch.cat(scal_q, dim=0)
     return c["ctx_idx"][i], c["ctx_pos"][i], base_f, base_s, c["ctx_csr"][i]

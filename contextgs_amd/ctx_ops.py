@@ -13,6 +13,7 @@ import itertools
 import threading
 import weakref
 
+import collections
 import os
 
 import torch
@@ -35,6 +36,11 @@ def _ints(v):
     return (C.c_int * len(v))(*v)
 
 
+def _u8(t):
+    """A bool / uint8 row mask as the contiguous uint8 tensor the kernels read (None stays None)."""
+    return None if t is None else (t if t.dtype == torch.uint8 else t.view(torch.uint8)).contiguous()
+
+
 class _RowCat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec, *srcs):
@@ -42,8 +48,7 @@ class _RowCat(torch.autograd.Function):
         srcs = [_c(s) for s in srcs]
         _lib.require_device(*srcs)
         idxs = [sp[0] for sp in spec]
-        masks = ctx.masks = [None if sp[2] is None else (sp[2] if sp[2].dtype == torch.uint8 else sp[2].view(torch.uint8)).contiguous()
-                             for sp in spec]
+        masks = ctx.masks = [_u8(sp[2]) for sp in spec]
         n = next((i.shape[0] for i in idxs if i is not None), srcs[0].shape[0])
         for s, i in zip(srcs, idxs):
             if i is None and s.shape[0] != n:
@@ -181,7 +186,113 @@ class HyperDirect:
         return buf, done
 
 
-class RowSource:
+# ---- gradients handed between nodes outside autograd: one ledger per step ("Hand-overs between nodes") ----------------
+# A backward that adds into a tensor another node owns returns None for it.  Every such route has ONE predicate that answers "may
+# this level add in place?" (the A/B knob and the preconditions) and one fallback that returns a gradient tensor for autograd to sum:
+#   parameter rows    RowSource.grad_buffers()                      always in place (the RowSource path has no other form)
+#   shared anchor     _anchor_shared() -> RowSource.anchor_*        else a zero-filled [N, 3] per level
+#   coded prefix      _prefix_inplace() -> JoinedGrads.prefix()     else a [prefix, w] tensor per level
+#   rate gradients    RateSide.give() / take()                      else N-row tensors through autograd (no RateSide)
+#   hyper rows        _hyper_rows_direct() -> HyperDirect.buffer()  else the hyper columns of dX, a strided slice
+ANCHOR_SHARED = os.environ.get("CGS_ANCHOR_SHARED", "1") != "0"      # A/B knob: 0 = one zero-filled [N,3] anchor gradient per level (rounds 5)
+HYPER_DIRECT = os.environ.get("CGS_HYPER_DIRECT", "1") != "0"        # A/B knob: 0 = the hyper latents' gradient leaves the levels as column slices of dX (gather_rows_segmented)
+PREFIX_INPLACE = os.environ.get("CGS_PREFIX_INPLACE", "1") != "0"    # A/B knob: 0 = the coded prefix's gradient as its own tensors, summed by autograd
+
+
+class JoinedGrads:
+    """The gradients context_model._JoinRows' backward split into per-level row slices during ONE step's backward (needs no device).
+
+    The coded prefix a context level reads IS the earlier levels' outputs, and their gradient from the joined tensor lies in the
+    same buffer right in front of this level's rows: the level's backward adds the parents' sums THERE (cgs_ctx_gather_bwd_acc
+    bits 1 / 2) and returns no gradient for the prefix.  Autograd still runs the earlier levels' nodes after this one (the edges
+    exist), they find the sums in their own slice.  Before: a [prefix, 50] + [prefix, 6] tensor per context level and six add
+    launches by the engine per step (profiles/r06_launch_attribution.txt).
+
+    The record holds the noted tensors themselves until the step's token node clears it, and a lookup matches a part against a
+    tensor it still holds by storage and offset — never an address alone, which the allocator may have handed to another step's
+    gradient since.  It heals itself: a later level that could not add in place returns a real prefix gradient, the engine then
+    SUMS two gradients for the earlier level's output into a fresh tensor, that tensor is in no record, and the earlier level
+    falls back too."""
+
+    def __init__(self):
+        self.noted = []
+
+    def note(self, g):
+        if g.dim() == 2 and g.dtype == _f32 and g.is_contiguous():
+            self.noted.append(g)
+
+    def clear(self):
+        self.noted = []
+
+    def prefix(self, part, n_prefix, w):
+        """`part` = rows [n_prefix, n_prefix + n) of a noted [rows, w] gradient -> that gradient's first n_prefix rows as a view,
+        else None."""
+        if (part is None or n_prefix <= 0 or part.dim() != 2 or part.shape[1] != w or part.dtype != _f32 or not part.is_contiguous()
+                or part.requires_grad):
+            return None
+        first, addr = part.storage_offset() - w * n_prefix, part.data_ptr() - 4 * w * n_prefix
+        for g in self.noted:
+            # (the address only narrows the search: what decides is the storage and offset of a tensor this record keeps alive)
+            if (g.data_ptr() == addr and g.shape[1] == w and g.storage_offset() == first and g.shape[0] >= n_prefix + part.shape[0]
+                    and g.untyped_storage().data_ptr() == part.untyped_storage().data_ptr()):
+                return torch.as_strided(part, (n_prefix, w), (w, 1), first)
+        return None
+
+
+class _AnchorLedger:
+    """ONE anchor-gradient buffer for the levels of a backward (round 6): every fused level gathers anchor rows (its own, or its
+    parents'), and as separate [N,3] outputs that was a zero fill per level + autograd's adds (3 fills + 2 adds of 12 MB at 1 M
+    anchors).  The levels that asked for the anchor gradient register in the forward; in the backward the first one to run creates
+    the zeroed buffer, each ADDS its rows, and the last one to release hands the buffer to autograd.  (Needs no device: the
+    counting half of RowSource.)"""
+
+    def __init__(self):
+        self.anchor_users = 0
+        self.anchor_acc = None
+
+    def anchor_register(self):
+        self.anchor_users += 1
+
+    def anchor_target(self, shape, device):
+        if self.anchor_acc is None:
+            self.anchor_acc = torch.zeros(shape, dtype=_f32, device=device)
+        return self.anchor_acc
+
+    def anchor_release(self):
+        """-> the shared buffer for the last registered level of this backward, None for the others."""
+        self.anchor_users -= 1
+        if self.anchor_users > 0:
+            return None
+        acc, self.anchor_acc = self.anchor_acc, None
+        return acc
+
+    def anchor_finish(self):
+        if self.anchor_users != 0 or self.anchor_acc is not None:
+            raise RuntimeError("RowSource: a level that registered for the shared anchor gradient did not release it "
+                               f"({self.anchor_users} registrations open, buffer {'left over' if self.anchor_acc is not None else 'handed on'})")
+
+
+def _anchor_shared(need_anchor_grad) -> bool:
+    """May this level add its anchor rows into the step's shared buffer?  (asked in the forward: the level registers)"""
+    return bool(ANCHOR_SHARED and need_anchor_grad)
+
+
+def _prefix_inplace(src, part, shape, need):
+    """May this level add the gradient of its coded prefix (`shape` = [prefix rows, w]) into the rows in front of its own gradient
+    `part`?  -> those rows as a view, or None: the caller then returns a [prefix, w] tensor of its own."""
+    return src.joined.prefix(part, int(shape[0]), int(shape[1])) if (PREFIX_INPLACE and need) else None
+
+
+def _hyper_rows_direct(hd, need, n, n_full, device):
+    """May this level write its hyper latents' gradient rows straight into the hyper prior's buffer?  Yes when its block of latents
+    came from training_step_forms(sizes=) (hd = block._cgs_hyp_direct) and the latents are indexed like the per-anchor tensors (rows
+    = coding permutation).  -> the [N, 12] buffer, or None: the gradient then leaves as the hyper columns of dX."""
+    if HYPER_DIRECT and hd is not None and need and hd[0].n == n_full and hd[0].c == 12 and hd[0].sizes[hd[1]] == n:
+        return hd[0].buffer(device)
+    return None
+
+
+class RowSource(_AnchorLedger):
     """The three per-anchor parameter tensors (features [N,D], scaling [N,S], offsets [N,K,3]) read THROUGH a row
     index by the level kernels, instead of being gathered into coding order first.
 
@@ -192,6 +303,8 @@ class RowSource:
     drops a full read+write pass over the tensors in each direction and the per-level gradient concatenation."""
 
     def __init__(self, feat, scal, off, complete: bool):
+        super().__init__()
+        self.joined = JoinedGrads()
         self.shapes = (feat.shape, scal.shape, off.shape)
         self.f, self.s = _c(feat.detach()), _c(scal.detach())
         self.s_orig = scal                      # the tensor the caller passed (rate_model checks WHOSE scaling it is)
@@ -200,13 +313,7 @@ class RowSource:
         self.complete = bool(complete)          # the levels' rows cover every row: no zero fill needed
         self.rows_read = self.rows_written = 0
         self.grads = None
-        # (round 6) ONE anchor-gradient buffer for the levels of a backward: every fused level gathers anchor rows (its own, or
-        # its parents'), and as separate [N,3] outputs that was a zero fill per level + autograd's adds (3 fills + 2 adds of
-        # 12 MB at 1 M anchors).  The levels that asked for the anchor gradient register in the forward; in the backward the first
-        # one to run creates the zeroed buffer, each ADDS its rows, and the last one hands the buffer to autograd.
-        self.anchor_users = 0
-        self.anchor_acc = None
-        self.sums = None            # device double [3]: sums of the values the levels read (RowSource.means())
+        self.sums = None           # device double [3]: sums of the values the levels read (RowSource.means())
         self.token = _RowSourceFn.apply(self, feat, scal, off)
 
     def sums_buffer(self):
@@ -255,17 +362,21 @@ class _RowSourceFn(torch.autograd.Function):
         # (a WEAK reference: `src` keeps this node's output — its token — so a strong one would be a cycle through the C++
         #  node, invisible to Python's collector; the level nodes that consumed the token hold `src` until the graph is freed)
         ctx.src_ref = weakref.ref(src)
+        ctx.joined = src.joined              # (holds gradient tensors only: no way back to this node)
         ctx.set_materialize_grads(False)     # the token's gradient carries nothing: no zeros(1) for it
         return feat.new_empty(1)             # (its VALUE is never read either: no fill launch)
 
     @staticmethod
     def backward(ctx, _g):
+        # the step's backward ends here (every level consumed the token): its hand-overs must be settled, its records go
+        ctx.joined.clear()
         src = ctx.src_ref()
         if src is None:                      # no level ever took the token: nothing was read, nothing to hand on
             return None, None, None, None
         if src.rows_written != src.rows_read:
             raise RuntimeError("RowSource: a level that read rows in the forward did not run its backward "
                                f"({src.rows_written} of {src.rows_read} rows have gradients)")
+        src.anchor_finish()
         gf, gs, go = src.grad_buffers()
         src.grads = None
         need = ctx.needs_input_grad
@@ -280,14 +391,52 @@ class RateSide:
     rows.  Instead of scattering the rate gradients into N-row zero buffers that autograd then adds to the dense
     ones (a fill and three full-size adds per level), _LevelRate leaves them COMPACT here and returns no gradient;
     the noise_quant backward — which autograd runs after every consumer of its outputs, so after _LevelRate — adds
-    row map[r] of them on the fly.  Needs the RowSource path (the kernel that scatters is the one that adds)."""
+    row map[r] of them on the fly.  Needs the RowSource path (the kernel that scatters is the one that adds).
+
+    Each transfer has one producer and one consumer:
+      lend()         level forward -> rate node, `rate_lazy` levels only (cgs_rate_sub_*): the level's input rows X and mlp_grid's
+                     weights; the rate node reads them with loan() in both directions
+      give()         rate node's backward -> (map, f, s, o, q); on lazy levels also the input-row gradient of the mean / scale
+                     branch dx [m, in] and its weight gradients dW = (dW1, db1, dW2, db2: the level kernel accumulates its own
+                     into them)
+      take()         the level's / noise_quant's backward <- (map, f, s, o, q)
+      take_branch()  the level's backward <- (dx, dW); ends the loan
+    Taking clears the record, so nothing of one backward is left for the next."""
+
+    _ABSENT = (None,) * 5
 
     def __init__(self):
-        self.map = self.f = self.s = self.o = self.q = None
-        # the fused rate-subset path (cgs_rate_sub_*, `rate_lazy` levels): forward -> rate node: the level's input rows and
-        # mlp_grid's weights; rate node's backward -> level node's backward: the input-row gradient of the mean / scale branch
-        # [m, in] and the weight gradients of that branch (dW1, db1, dW2, db2: the level kernel accumulates its own into them)
-        self.X = self.weights = self.dx = self.dW = None
+        self._loan = self._rate = self._branch = None
+
+    def lend(self, X, weights):
+        assert self._loan is None, "RateSide: this level's input rows were lent twice"
+        self._loan = (X, weights)
+
+    @property
+    def lazy(self) -> bool:
+        return self._loan is not None
+
+    def loan(self):
+        assert self._loan is not None, "RateSide: the level lent nothing (or its backward already took the loan back)"
+        return self._loan
+
+    def give(self, smap, f, s, o, q, dx=None, dW=None):
+        assert self._rate is None and self._branch is None, "RateSide: rate gradients given twice before the level took them"
+        self._rate = (smap, f, s, o, q)
+        if dW is not None:
+            self._branch = (dx, dW)
+
+    def take(self):
+        """(map, f, s, o, q), or five None when nothing was given or the arrays are empty: a level without a single chosen row has
+        an all -1 map and zero-row arrays — nothing to add, and empty tensors would reach the C entry point as NULL pointers."""
+        rate, self._rate = self._rate, None
+        return rate if (rate is not None and rate[1].numel() > 0) else self._ABSENT
+
+    def take_branch(self):
+        """(dx, dW) of a lazy level whose rate node's backward ran, else (None, None): the level then zero-fills its weight
+        gradients (no chosen row on the level, or a loss without the rate)."""
+        branch, self._branch, self._loan = self._branch, None, None
+        return branch if branch is not None else (None, None)
 
 
 class _NoiseQuant(torch.autograd.Function):
@@ -329,23 +478,17 @@ class _NoiseQuant(torch.autograd.Function):
         gf, gs, go, gQ = (None if t is None else _c(t) for t in (gf, gs, go, gQ))
         dq = torch.empty(n, 3, dtype=_f32, device=qadj.device) if (ctx.needs_input_grad[3] or src is not None) else None
         dx = src.grad_buffers() if src is not None else (None, None, None)
-        side = ctx.side if (ctx.side is not None and ctx.side.map is not None and src is not None) else None
-        # (a level without a single chosen row has an all -1 map and EMPTY side arrays: nothing to add, and empty tensors
-        #  would reach the C entry point as NULL pointers)
-        use_side = side is not None and side.f is not None and side.f.numel() > 0
-        sd = (side.map, side.f, side.s, side.o, side.q) if use_side else (None,) * 5
+        sd = ctx.side.take() if ctx.side is not None else (None,) * 5       # (a side needs src: noise_quant())
         if dq is not None:
             _lib.check(_lib.lib().cgs_noise_quant_bwd(
                 _lib.ptr(gf), _lib.ptr(gs), _lib.ptr(go), _lib.ptr(gQ), _lib.ptr(qadj), n, D, S, O, ctx.seed, ctx.q0[0],
                 ctx.q0[1], ctx.q0[2], _lib.ptr(dq), _lib.ptr(rows) if src is not None else None, _lib.ptr(dx[0]),
                 _lib.ptr(dx[1]), _lib.ptr(dx[2]), *[_lib.ptr(t) for t in sd], _lib.current_stream()), "cgs_noise_quant_bwd")
-        if side is not None:
-            side.map = side.f = side.s = side.o = side.q = None
         if src is not None:
             src.rows_written += n
-            # (no gradient VALUE for the token: it only ties _RowSourceFn into the graph, whose backward hands out the
-            #  buffers this kernel filled — a zeros(1) per level cost a fill and an add launch each)
-            return None, None, None, dq, None, None, None, None, None, None, None
+            gf = gs = go = None         # (the kernel scattered them into the RowSource's buffers)
+        # (no gradient VALUE for the token: it only ties _RowSourceFn into the graph, whose backward hands out the
+        #  buffers this kernel filled — a zeros(1) per level cost a fill and an add launch each)
         return gf, gs, go, dq, None, None, None, None, None, None, None
 
 
@@ -359,12 +502,94 @@ def noise_quant(xf, xs, xo, qadj, q0, seed=None, outs=None, src=None, rows=None,
                              tuple(float(v) for v in q0), outs, src, rows, None if src is None else src.token, side)
 
 
+# ---- the launches the rate nodes share (one node per level: _LevelRate + _RateFinish; one node for the step: _RateAll) -----------
+def _carve(n, widths, device, zero=False):
+    """[n, w] tensors for w in widths, side by side in ONE allocation (one fill when zero)."""
+    flat = (torch.zeros if zero else torch.empty)(n * sum(widths), dtype=_f32, device=device)
+    return [t.view(n, w) for t, w in zip(torch.split(flat, [n * w for w in widths]), widths)]
+
+
+def _sub_map(loc, n_level):
+    """int32 [n_level]: a level row's index in the chosen list `loc`, -1 elsewhere — where the step's bookkeeping kernel
+    (ctx_plan.hip, choose_rows' sub_map) did not leave one."""
+    m = torch.full((n_level,), -1, dtype=torch.int32, device=loc.device)
+    m[loc] = torch.arange(int(loc.shape[0]), dtype=torch.int32, device=loc.device)
+    return m
+
+
+def _level_rate_fwd(lv, masks_p, grows, x_means, use_clamp, K, sums_p, stream):
+    """masks_p / sums_p: device addresses of the level's mask-weight rows (or None) and of its float [3] sums."""
+    yf, ys, yo, Q, pred, loc = lv
+    _lib.check(_lib.lib().cgs_level_rate_fwd(
+        _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(loc), _lib.ptr(pred), masks_p, _lib.ptr(grows),
+        _lib.ptr(x_means), use_clamp, int(pred.shape[0]), int(yf.shape[1]), K, int(pred.shape[1]), sums_p, stream), "cgs_level_rate_fwd")
+
+
+def _level_rate_bwd(lv, masks_p, grows, x_means, use_clamp, K, g_p, d_masks_p, compact, stream):
+    """-> ([d_yf, d_ys, d_yo, dQ], d_pred).  Row-scattered gradients: one zero fill for the four N-row buffers — or, compact (with a
+    RateSide), [n_sub, .] arrays (every row written, no fill) that the level's backward adds in."""
+    yf, ys, yo, Q, pred, loc = lv
+    n_sub, D = int(pred.shape[0]), int(yf.shape[1])
+    d = _carve(n_sub if compact else int(yf.shape[0]), (D, 6, 3 * K, 3), yf.device, zero=not compact)
+    d_pred = torch.empty_like(pred)
+    _lib.check(_lib.lib().cgs_level_rate_bwd(
+        _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(loc), _lib.ptr(pred), masks_p, _lib.ptr(grows),
+        _lib.ptr(x_means), use_clamp, n_sub, D, K, int(pred.shape[1]), g_p, _lib.ptr(d_pred), *[_lib.ptr(t) for t in d], d_masks_p,
+        int(compact), stream), "cgs_level_rate_bwd")
+    return d, d_pred
+
+
+def _rate_sub_fwd(side, lv, masks_p, x_means, use_clamp, sums_p, stream):
+    """A rate_lazy level: the MLP's mean / scale branch + the rate terms of the chosen rows in one launch, from the loan."""
+    yf, ys, yo, Q, _pred, loc = lv
+    X, (W1, b1, W2, b2) = side.loan()
+    _lib.check(_lib.lib().cgs_rate_sub_fwd(
+        int(X.shape[1]), _lib.ptr(X), int(X.shape[0]), _lib.ptr(loc), int(loc.shape[0]), _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2),
+        _lib.ptr(b2), _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), masks_p, _lib.ptr(x_means), use_clamp, sums_p, stream),
+        "cgs_rate_sub_fwd")
+
+
+def _rate_sub_bwd(side, lv, masks_p, x_means, use_clamp, K, g_p, d_masks_p, stream):
+    """-> ([d_yf, d_ys, d_yo, dQ], dx [n_sub, in], (dW1, db1, dW2, db2)), all compact and fully written."""
+    Lc = _lib.lib()
+    yf, ys, yo, Q, _pred, loc = lv
+    X, W = side.loan()
+    n_sub, in_f, dev = int(loc.shape[0]), int(X.shape[1]), yf.device
+    *d, dx = _carve(n_sub, (int(yf.shape[1]), 6, 3 * K, 3, in_f), dev)
+    wflat = torch.empty(sum(w.numel() for w in W), dtype=_f32, device=dev)
+    dW = tuple(t.view(w.shape) for t, w in zip(torch.split(wflat, [w.numel() for w in W]), W))
+    ws = torch.empty(int(Lc.cgs_rate_sub_bwd_scratch_bytes(in_f, n_sub)), dtype=torch.uint8, device=dev)
+    _lib.check(Lc.cgs_rate_sub_bwd(
+        in_f, _lib.ptr(X), int(X.shape[0]), _lib.ptr(loc), n_sub, *[_lib.ptr(w) for w in W], _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo),
+        _lib.ptr(Q), masks_p, _lib.ptr(x_means), use_clamp, g_p, *[_lib.ptr(t) for t in d], _lib.ptr(dx), d_masks_p,
+        *[_lib.ptr(t) for t in dW], _lib.ptr(ws), ws.numel(), stream), "cgs_rate_sub_bwd")
+    return d, dx, dW
+
+
+def _rate_finish_fwd(table_p, levels, hsum, finish, device, stream):
+    """scene/gaussian_model.py:1687-1705 over a [levels, 3] table of bit sums -> (out [4], raw [2 + levels])."""
+    out = torch.empty(4, dtype=_f32, device=device)
+    raw = torch.empty(2 + levels, dtype=_f32, device=device)
+    _lib.check(_lib.lib().cgs_rate_finish_fwd(table_p, levels, _lib.ptr(_c(hsum)), *[float(v) for v in finish], _lib.ptr(out),
+                                              _lib.ptr(raw), stream), "cgs_rate_finish_fwd")
+    return out, raw
+
+
+def _rate_finish_bwd(gs, levels, finish, device, stream):
+    """gs: the gradient of out [4], or of its four entries (None = unread) -> (dS [levels, 3], dh [1])."""
+    dS = torch.empty(levels, 3, dtype=_f32, device=device)
+    dh = torch.empty(1, dtype=_f32, device=device)
+    entry = _lib.lib().cgs_rate_finish_bwd if len(gs) == 1 else _lib.lib().cgs_rate_finish_bwd4
+    _lib.check(entry(*[_lib.ptr(None if g is None else _c(g)) for g in gs], levels, *[float(v) for v in finish[:4]], _lib.ptr(dS),
+                     _lib.ptr(dh), stream), "cgs_rate_finish_bwd")
+    return dS, dh
+
+
 class _LevelRate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, yf, ys, yo, Q, pred, loc, masks, grows, x_means, use_clamp, K, side, out):
-        yf, ys, yo, Q, pred = _c(yf), _c(ys), _c(yo), _c(Q), _c(pred)
-        _lib.require_device(yf, pred)
-        n_sub, D = pred.shape[0], yf.shape[1]
+        lv = (_c(yf), _c(ys), _c(yo), _c(Q), _c(pred), loc)
+        _lib.require_device(lv[0], lv[4])
         # out: a ZEROED float [3] the caller owns (a row of the step's [levels, 3] table: one fill for all levels)
         if out is not None:     # an independent tensor object on the caller's storage (not an autograd view of it)
             sums = torch.empty(0, dtype=_f32, device=yf.device).set_(out.untyped_storage(), out.storage_offset(), (3,), (1,))
@@ -372,40 +597,25 @@ class _LevelRate(torch.autograd.Function):
             sums = torch.zeros(3, dtype=_f32, device=yf.device)
         masks = None if masks is None else _c(masks)
         x_means = None if x_means is None else _c(x_means)
-        _lib.check(_lib.lib().cgs_level_rate_fwd(
-            _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(loc), _lib.ptr(pred), _lib.ptr(masks),
-            _lib.ptr(grows), _lib.ptr(x_means), int(use_clamp), n_sub, D, K, pred.shape[1], _lib.ptr(sums),
-            _lib.current_stream()), "cgs_level_rate_fwd")
-        ctx.save_for_backward(yf, ys, yo, Q, pred, loc, masks, grows, x_means)
-        ctx.cfg = (int(use_clamp), n_sub, D, K)
+        _level_rate_fwd(lv, _lib.ptr(masks), grows, x_means, int(use_clamp), K, _lib.ptr(sums), _lib.current_stream())
+        ctx.save_for_backward(*lv, masks, grows, x_means)
+        ctx.cfg = (int(use_clamp), K)
         ctx.side = side
         return sums
 
     @staticmethod
     def backward(ctx, g):
-        yf, ys, yo, Q, pred, loc, masks, grows, x_means = ctx.saved_tensors
-        use_clamp, n_sub, D, K = ctx.cfg
-        n_l = yf.shape[0]
+        *lv, masks, grows, x_means = ctx.saved_tensors
+        use_clamp, K = ctx.cfg
+        loc = lv[5]
         side = ctx.side if loc is not None else None
-        # row-scattered gradients: one zero fill for the four N-row buffers — or, with a RateSide, compact
-        # [n_sub, .] arrays (every row written, no fill) that the level's noise_quant backward adds in
-        n_o = n_sub if side is not None else n_l
-        flat = (torch.empty if side is not None else torch.zeros)(n_o * (D + 6 + 3 * K + 3), dtype=_f32, device=yf.device)
-        d_yf, d_ys, d_yo, dQ = torch.split(flat, [n_o * D, n_o * 6, n_o * 3 * K, n_o * 3])
-        d_yf, d_ys, d_yo, dQ = d_yf.view(n_o, D), d_ys.view(n_o, 6), d_yo.view(n_o, 3 * K), dQ.view(n_o, 3)
-        d_pred = torch.empty_like(pred)
         d_masks = torch.zeros_like(masks) if (masks is not None and ctx.needs_input_grad[6]) else None
-        _lib.check(_lib.lib().cgs_level_rate_bwd(
-            _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(loc), _lib.ptr(pred), _lib.ptr(masks),
-            _lib.ptr(grows), _lib.ptr(x_means), use_clamp, n_sub, D, K, pred.shape[1], _lib.ptr(_c(g)), _lib.ptr(d_pred),
-            _lib.ptr(d_yf), _lib.ptr(d_ys), _lib.ptr(d_yo), _lib.ptr(dQ), _lib.ptr(d_masks), int(side is not None),
-            _lib.current_stream()), "cgs_level_rate_bwd")
+        d, d_pred = _level_rate_bwd(lv, _lib.ptr(masks), grows, x_means, use_clamp, K, _lib.ptr(_c(g)), _lib.ptr(d_masks),
+                                    side is not None, _lib.current_stream())
         if side is not None:
-            m = torch.full((n_l,), -1, dtype=torch.int32, device=yf.device)
-            m[loc] = torch.arange(n_sub, dtype=torch.int32, device=yf.device)
-            side.map, side.f, side.s, side.o, side.q = m, d_yf, d_ys, d_yo, dQ
-            return None, None, None, None, d_pred, None, d_masks, None, None, None, None, None, None
-        return d_yf, d_ys, d_yo, dQ, d_pred, None, d_masks, None, None, None, None, None, None
+            side.give(_sub_map(loc, int(lv[0].shape[0])), *d)
+            d = (None,) * 4
+        return (*d, d_pred, None, d_masks, None, None, None, None, None, None)
 
 
 def level_rate(yf, ys, yo, Q, pred, loc, masks, grows, x_means, use_clamp, K, side=None, out=None):
@@ -422,28 +632,18 @@ class _RateFinish(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hsum, cfg, *rows):
-        rate, n_f, n_s, n_o, dead = cfg
-        L = len(rows)
         base = rows[0]
         for j, r in enumerate(rows):
             if r.data_ptr() != base.data_ptr() + 12 * j:
                 raise ValueError("rate_finish: level sums must be consecutive rows of one table")
-        out = torch.empty(4, dtype=_f32, device=base.device)
-        raw = torch.empty(2 + L, dtype=_f32, device=base.device)
-        _lib.check(_lib.lib().cgs_rate_finish_fwd(_lib.ptr(base), L, _lib.ptr(_c(hsum)), float(rate), float(n_f), float(n_s),
-                                                  float(n_o), float(dead), _lib.ptr(out), _lib.ptr(raw),
-                                                  _lib.current_stream()), "cgs_rate_finish_fwd")
-        ctx.cfg, ctx.L = cfg, L
+        out, raw = _rate_finish_fwd(_lib.ptr(base), len(rows), hsum, cfg, base.device, _lib.current_stream())
+        ctx.cfg, ctx.L = cfg, len(rows)
         ctx.mark_non_differentiable(raw)
         return out, raw
 
     @staticmethod
     def backward(ctx, g, _g_raw):
-        rate, n_f, n_s, n_o, _dead = ctx.cfg
-        dS = torch.empty(ctx.L, 3, dtype=_f32, device=g.device)
-        dh = torch.empty(1, dtype=_f32, device=g.device)
-        _lib.check(_lib.lib().cgs_rate_finish_bwd(_lib.ptr(_c(g)), ctx.L, float(rate), float(n_f), float(n_s), float(n_o),
-                                                  _lib.ptr(dS), _lib.ptr(dh), _lib.current_stream()), "cgs_rate_finish_bwd")
+        dS, dh = _rate_finish_bwd((g,), ctx.L, ctx.cfg, g.device, _lib.current_stream())
         return (dh, None, *dS.unbind(0))
 
 
@@ -467,42 +667,27 @@ class _RateAll(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hsum, masks, x_means, meta, *lv):
-        Lc = _lib.lib()
         nl = len(lv) // 6
         K, use_clamp = int(meta["K"]), int(bool(meta["use_clamp"]))
         masks, x_means, hsum = _c(masks), _c(x_means), _c(hsum)
         lv = [t.contiguous() if k % 6 == 5 else _c(t) for k, t in enumerate(lv)]     # every 6th is loc (int64)
         _lib.require_device(masks, x_means, lv[0], lv[4])
-        dev = masks.device
         S = meta.get("sum_table")           # (zeroed with the row source's accumulator: RowSource.rate_sum_table)
         if S is None or tuple(S.shape) != (nl, 3):
-            S = torch.zeros(nl, 3, dtype=_f32, device=dev)
+            S = torch.zeros(nl, 3, dtype=_f32, device=masks.device)
         stream = _lib.current_stream()
+        # a rate_lazy level (its node lent X and the weights): MLP branch + rate terms in one launch
+        ctx.lazy = tuple(sd is not None and sd.lazy for sd in meta["sides"])
         for j in range(nl):
-            yf, ys, yo, Q, pred, loc = lv[6 * j:6 * j + 6]
-            lo, hi = meta["spans"][j]
-            side = meta["sides"][j]
-            if side is not None and side.X is not None:          # a rate_lazy level: MLP branch + rate terms in one launch
-                n_sub = int(loc.shape[0])
-                assert hi - lo == n_sub
-                if n_sub > 0:
-                    W1, b1, W2, b2 = side.weights
-                    _lib.check(Lc.cgs_rate_sub_fwd(
-                        int(side.X.shape[1]), _lib.ptr(side.X), int(side.X.shape[0]), _lib.ptr(loc), n_sub, _lib.ptr(W1), _lib.ptr(b1),
-                        _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), masks.data_ptr() + 4 * K * lo,
-                        _lib.ptr(x_means), use_clamp, S.data_ptr() + 12 * j, stream), "cgs_rate_sub_fwd")
-                continue
-            n_sub = int(pred.shape[0])
-            assert hi - lo == n_sub and int(loc.shape[0]) == n_sub
-            _lib.check(Lc.cgs_level_rate_fwd(
-                _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(loc), _lib.ptr(pred),
-                masks.data_ptr() + 4 * K * lo, None, _lib.ptr(x_means), use_clamp, n_sub, yf.shape[1], K, pred.shape[1],
-                S.data_ptr() + 12 * j, stream), "cgs_level_rate_fwd")
-        rate, n_f, n_s, n_o, dead = meta["finish"]
-        out = torch.empty(4, dtype=_f32, device=dev)
-        raw = torch.empty(2 + nl, dtype=_f32, device=dev)
-        _lib.check(Lc.cgs_rate_finish_fwd(_lib.ptr(S), nl, _lib.ptr(hsum), float(rate), float(n_f), float(n_s), float(n_o),
-                                          float(dead), _lib.ptr(out), _lib.ptr(raw), stream), "cgs_rate_finish_fwd")
+            lvj, (lo, hi) = lv[6 * j:6 * j + 6], meta["spans"][j]
+            n_sub = int(lvj[5].shape[0])
+            assert hi - lo == n_sub and (ctx.lazy[j] or int(lvj[4].shape[0]) == n_sub)
+            masks_p, sums_p = masks.data_ptr() + 4 * K * lo, S.data_ptr() + 12 * j
+            if not ctx.lazy[j]:
+                _level_rate_fwd(lvj, masks_p, None, x_means, use_clamp, K, sums_p, stream)
+            elif n_sub > 0:
+                _rate_sub_fwd(meta["sides"][j], lvj, masks_p, x_means, use_clamp, sums_p, stream)
+        out, raw = _rate_finish_fwd(_lib.ptr(S), nl, hsum, meta["finish"], masks.device, stream)
         ctx.save_for_backward(masks, x_means, *lv)
         ctx.meta = meta
         ctx.mark_non_differentiable(raw)
@@ -513,76 +698,31 @@ class _RateAll(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g0, g1, g2, g3, _g_raw):
-        Lc = _lib.lib()
-        masks, x_means = ctx.saved_tensors[:2]
-        lv = ctx.saved_tensors[2:]
-        meta = ctx.meta
-        nl = len(lv) // 6
+        masks, x_means, *lv = ctx.saved_tensors
+        meta, nl = ctx.meta, len(lv) // 6
         K, use_clamp = int(meta["K"]), int(bool(meta["use_clamp"]))
-        rate, n_f, n_s, n_o, _dead = meta["finish"]
-        dev = masks.device
         stream = _lib.current_stream()
-        dS = torch.empty(nl, 3, dtype=_f32, device=dev)
-        dh = torch.empty(1, dtype=_f32, device=dev)
-        g0, g1, g2, g3 = (None if t is None else _c(t) for t in (g0, g1, g2, g3))
-        _lib.check(Lc.cgs_rate_finish_bwd4(_lib.ptr(g0), _lib.ptr(g1), _lib.ptr(g2), _lib.ptr(g3), nl, float(rate), float(n_f),
-                                           float(n_s), float(n_o), _lib.ptr(dS), _lib.ptr(dh), stream), "cgs_rate_finish_bwd")
-        all_lazy = all(sd is not None and sd.X is not None for sd in meta["sides"])
+        dS, dh = _rate_finish_bwd((g0, g1, g2, g3), nl, meta["finish"], masks.device, stream)
         # (the level-rate kernels add into it; the fused rate-subset kernels write every row of their span)
-        d_masks = (torch.empty_like if all_lazy else torch.zeros_like)(masks) if ctx.needs_input_grad[1] else None
+        d_masks = (torch.empty_like if all(ctx.lazy) else torch.zeros_like)(masks) if ctx.needs_input_grad[1] else None
         grads = []
         for j in range(nl):
-            yf, ys, yo, Q, pred, loc = lv[6 * j:6 * j + 6]
-            lo, _hi = meta["spans"][j]
-            n_sub, n_l, D = int(pred.shape[0]), int(yf.shape[0]), int(yf.shape[1])
-            side = meta["sides"][j]
-            if side is not None and side.X is not None:
-                n_sub = int(loc.shape[0])
-                grads += [None, None, None, None, None, None]
-                if n_sub == 0:      # nothing chosen on this level: no side arrays, the level node zero-fills its weight gradients
-                    side.X = side.weights = None
-                    continue
-                X, (W1, b1, W2, b2) = side.X, side.weights
-                in_f = int(X.shape[1])
-                flat = torch.empty(n_sub * (D + 6 + 3 * K + 3 + in_f), dtype=_f32, device=dev)
-                d_yf, d_ys, d_yo, dQ, dx = torch.split(flat, [n_sub * D, n_sub * 6, n_sub * 3 * K, n_sub * 3, n_sub * in_f])
-                wflat = torch.empty(W1.numel() + b1.numel() + W2.numel() + b2.numel(), dtype=_f32, device=dev)
-                dW1, db1, dW2, db2 = (t.view(w.shape) for t, w in zip(torch.split(wflat, [W1.numel(), b1.numel(), W2.numel(), b2.numel()]),
-                                                                      (W1, b1, W2, b2)))
-                ws = torch.empty(int(Lc.cgs_rate_sub_bwd_scratch_bytes(in_f, n_sub)), dtype=torch.uint8, device=dev)
-                _lib.check(Lc.cgs_rate_sub_bwd(
-                    in_f, _lib.ptr(X), int(X.shape[0]), _lib.ptr(loc), n_sub, _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2),
-                    _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), masks.data_ptr() + 4 * K * lo, _lib.ptr(x_means), use_clamp,
-                    dS.data_ptr() + 12 * j, _lib.ptr(d_yf), _lib.ptr(d_ys), _lib.ptr(d_yo), _lib.ptr(dQ), _lib.ptr(dx),
-                    None if d_masks is None else d_masks.data_ptr() + 4 * K * lo, _lib.ptr(dW1), _lib.ptr(db1), _lib.ptr(dW2),
-                    _lib.ptr(db2), _lib.ptr(ws), ws.numel(), stream), "cgs_rate_sub_bwd")
-                mp = meta["maps"][j]
-                if mp is None:
-                    mp = torch.full((n_l,), -1, dtype=torch.int32, device=dev)
-                    mp[loc] = torch.arange(n_sub, dtype=torch.int32, device=dev)
-                side.map, side.f, side.s, side.o, side.q = mp, d_yf.view(n_sub, D), d_ys.view(n_sub, 6), d_yo.view(n_sub, 3 * K), dQ.view(n_sub, 3)
-                side.dx, side.dW = dx.view(n_sub, in_f), (dW1, db1, dW2, db2)
+            lvj, (lo, _hi), side, mp = lv[6 * j:6 * j + 6], meta["spans"][j], meta["sides"][j], meta["maps"][j]
+            loc, n_l = lvj[5], int(lvj[0].shape[0])
+            masks_p, g_p = masks.data_ptr() + 4 * K * lo, dS.data_ptr() + 12 * j
+            d_masks_p = None if d_masks is None else d_masks.data_ptr() + 4 * K * lo
+            if ctx.lazy[j]:
+                # (nothing chosen on this level: nothing is given, the level node zero-fills its weight gradients)
+                if int(loc.shape[0]) > 0:
+                    d, dx, dW = _rate_sub_bwd(side, lvj, masks_p, x_means, use_clamp, K, g_p, d_masks_p, stream)
+                    side.give(mp if mp is not None else _sub_map(loc, n_l), *d, dx=dx, dW=dW)
+                grads += [None] * 6
                 continue
-            n_o_rows = n_sub if side is not None else n_l
-            flat = (torch.empty if side is not None else torch.zeros)(n_o_rows * (D + 6 + 3 * K + 3), dtype=_f32, device=dev)
-            d_yf, d_ys, d_yo, dQ = torch.split(flat, [n_o_rows * D, n_o_rows * 6, n_o_rows * 3 * K, n_o_rows * 3])
-            d_yf, d_ys, d_yo, dQ = d_yf.view(n_o_rows, D), d_ys.view(n_o_rows, 6), d_yo.view(n_o_rows, 3 * K), dQ.view(n_o_rows, 3)
-            d_pred = torch.empty_like(pred)
-            _lib.check(Lc.cgs_level_rate_bwd(
-                _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(loc), _lib.ptr(pred),
-                masks.data_ptr() + 4 * K * lo, None, _lib.ptr(x_means), use_clamp, n_sub, D, K, pred.shape[1],
-                dS.data_ptr() + 12 * j, _lib.ptr(d_pred), _lib.ptr(d_yf), _lib.ptr(d_ys), _lib.ptr(d_yo), _lib.ptr(dQ),
-                None if d_masks is None else d_masks.data_ptr() + 4 * K * lo, int(side is not None), stream),
-                "cgs_level_rate_bwd")
+            d, d_pred = _level_rate_bwd(lvj, masks_p, None, x_means, use_clamp, K, g_p, d_masks_p, side is not None, stream)
             if side is not None:
-                m = meta["maps"][j]
-                if m is None:
-                    m = torch.full((n_l,), -1, dtype=torch.int32, device=dev)
-                    m[loc] = torch.arange(n_sub, dtype=torch.int32, device=dev)
-                side.map, side.f, side.s, side.o, side.q = m, d_yf, d_ys, d_yo, dQ
-                grads += [None, None, None, None, d_pred, None]
-            else:
-                grads += [d_yf, d_ys, d_yo, dQ, d_pred, None]
+                side.give(mp if mp is not None else _sub_map(loc, n_l), *d)
+                d = [None] * 4
+            grads += [*d, d_pred, None]
         return (dh, d_masks, None, None, *grads)
 
 
@@ -642,6 +782,13 @@ def ctx_assemble(anchor, base_f, base_s, own, idx, pos, csr):
     return _CtxAssemble.apply(anchor, base_f, base_s, own, idx, pos, csr)
 
 
+def _mask_ste_bwd(x, g):
+    d = torch.empty_like(x)
+    _lib.check(_lib.lib().cgs_mask_ste_bwd(_lib.ptr(x), _lib.ptr(_c(g)), x.numel(), _lib.ptr(d), _lib.current_stream()),
+               "cgs_mask_ste_bwd")
+    return d
+
+
 class _MaskSTE(torch.autograd.Function):
     """get_mask / get_mask_anchor of the model in one launch each way (cgs_mask_ste_*, csrc/mask.hip)."""
 
@@ -662,12 +809,7 @@ class _MaskSTE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_alive):
         (x,) = ctx.saved_tensors
-        if g is None:
-            return None
-        d = torch.empty_like(x)
-        _lib.check(_lib.lib().cgs_mask_ste_bwd(_lib.ptr(x), _lib.ptr(_c(g)), x.numel(), _lib.ptr(d), _lib.current_stream()),
-                   "cgs_mask_ste_bwd")
-        return d
+        return None if g is None else _mask_ste_bwd(x, g)
 
 
 class _MaskSTEAttach(torch.autograd.Function):
@@ -686,13 +828,7 @@ class _MaskSTEAttach(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
-        if g is None:
-            return None, None
-        x = _c(x)
-        d = torch.empty_like(x)
-        _lib.check(_lib.lib().cgs_mask_ste_bwd(_lib.ptr(x), _lib.ptr(_c(g)), x.numel(), _lib.ptr(d), _lib.current_stream()),
-                   "cgs_mask_ste_bwd")
-        return d, None
+        return (None if g is None else _mask_ste_bwd(_c(x), g)), None
 
 
 def mask_ste_values(logits):
@@ -748,8 +884,7 @@ def choose_rows_begin(perm, n, mask, given, seed, thresh, anchor, anchor_ref, ma
     the caller can enqueue more work (or reach a synchronisation it has to make anyway) before the counts are read."""
     L = _lib.lib()
     dev = (perm if perm is not None else anchor if anchor is not None else mask).device
-    as_u8 = lambda t: None if t is None else (t if t.dtype == torch.uint8 else t.view(torch.uint8)).contiguous()
-    mask_u8, given_u8, mref_u8 = as_u8(mask), as_u8(given), as_u8(mask_ref)
+    mask_u8, given_u8, mref_u8 = _u8(mask), _u8(given), _u8(mask_ref)
     nlev = len(bounds) - 1
     nblk = int(L.cgs_ctx_choose_blocks(n))
     flags = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
@@ -812,40 +947,12 @@ def choose_rows(perm, n, mask, given, seed, thresh, anchor, anchor_ref, mask_ref
 
 
 # ---- one launch per level and direction for the every-row half of the level loop (csrc/ctx_level.hip) ---------------
-ANCHOR_SHARED = os.environ.get("CGS_ANCHOR_SHARED", "1") != "0"      # A/B knob: 0 = one zero-filled [N,3] anchor gradient per level (rounds 5)
-HYPER_DIRECT = os.environ.get("CGS_HYPER_DIRECT", "1") != "0"        # A/B knob: 0 = the hyper latents' gradient leaves the levels as column slices of dX (gather_rows_segmented)
-PREFIX_INPLACE = os.environ.get("CGS_PREFIX_INPLACE", "1") != "0"    # A/B knob: 0 = the coded prefix's gradient as its own tensors, summed by autograd
 # A/B knob, default: the context levels' forward (in_dim 71) hands its hidden layer to the backward (cgs_ctx_level_fwd_h / _bwd_h,
 # +416 B per row kept between the two).  CGS_CTXL_KEEP_H=0: the backward recomputes it from X (cgs_ctx_level_bwd2).  The first level
 # (in_dim 15) always recomputes: its 28 layer-1 MFMAs per tile cost what the hand-over's bytes do — profiles/ctxl_hidden_handover.txt
 KEEP_H = os.environ.get("CGS_CTXL_KEEP_H", "1") != "0"
 
 
-_JOINED_GRADS = {}       # data pointer -> (rows, width) of the gradients _JoinRows' backward split this step (cleared per forward)
-
-
-def note_joined_grad(g):
-    """_JoinRows.backward: `g` [rows, w] is the gradient of level outputs lying side by side in coding order."""
-    if g is not None and g.dim() == 2 and g.dtype == _f32 and g.is_contiguous() and g.is_cuda:
-        _JOINED_GRADS[g.data_ptr()] = (int(g.shape[0]), int(g.shape[1]))
-
-
-def _grad_prefix(part, n_prefix):
-    """`part` = rows [n_prefix, n_prefix + n) of a gradient buffer _JoinRows' backward split (note_joined_grad) -> that buffer's
-    first n_prefix rows as a view, else None.
-
-    The coded prefix a context level reads IS the earlier levels' outputs, and their gradient from the joined tensor lies in
-    the same buffer right in front of this level's rows: the level's backward adds the parents' sums THERE
-    (cgs_ctx_gather_bwd_acc bits 1 / 2) and returns no gradient for the prefix.  Autograd still runs the earlier levels'
-    nodes after this one (the edges exist), they find the sums in their own slice.  Before: a [prefix, 50] + [prefix, 6]
-    tensor per context level and six add launches by the engine per step (profiles/r06_launch_attribution.txt)."""
-    if part is None or n_prefix <= 0 or part.dim() != 2 or part.dtype != _f32 or not part.is_contiguous() or part.requires_grad:
-        return None
-    w = int(part.shape[1])
-    rec = _JOINED_GRADS.get(part.data_ptr() - 4 * w * n_prefix)
-    if rec is None or rec[1] != w or rec[0] < n_prefix + int(part.shape[0]) or part.storage_offset() < w * n_prefix:
-        return None
-    return torch.as_strided(part, (n_prefix, w), (w, 1), part.storage_offset() - w * n_prefix)
 _LEVEL_DIMS = (50, 6, 30, 12, 100, 175)      # features, scaling, offsets, hyper, hidden, outputs of mlp_grid: the kernels' instance
 
 
@@ -862,6 +969,108 @@ def level_fused_supported(seq, anchor, hyp, src) -> bool:
                 and anchor.dtype == _f32 and anchor.is_cuda and anchor.dim() == 2 and anchor.shape[1] == 3)
 
 
+# What a level's node keeps of level_fused()'s arguments (a_mask: uint8 [N] or None).  `outs` and `pre` travel beside it: they are
+# the node's outputs.
+_LevelCfg = collections.namedtuple("_LevelCfg", "a_rows a_mask pos n_stat src rows seed q0 csr loc side rate_lazy hyp_direct need_grad",
+                                   defaults=(None, None, None, False, None, False))
+
+
+def _level_bwd_subset(ctx, saved, d_pred):
+    """Step 1, the rate subset's branch of mlp_grid: -> ((dW1, db1, dW2, db2) this module's weight gradients so far, dx_sub [m, in]
+    the branch's input-row gradient or None).  Its input gradient rides into the level kernel as compact rows."""
+    from . import mlp as _mlp
+    _X, x_sub, h_sub, W1, _b1, W2, _b2, _H = saved
+    n, in_f, hid, out, n_stat, m = ctx.dims
+    dev = W1.device
+    if ctx.lazy:
+        # the rate node's backward (cgs_rate_sub_bwd) already ran: its weight gradients are the start of this module's
+        # (no zero fill), its input-row gradient rides along
+        dx_sub, dW = ctx.cfg.side.take_branch()
+        if dW is not None:
+            return dW, dx_sub
+    dW = _mlp._zeros_views(dev, (hid, in_f), (hid,), (out, hid), (out,))      # one fill for the module
+    dx_sub = None
+    if (not ctx.lazy) and d_pred is not None and m > 0:
+        ws = _mlp._wgrad_workspace(dev)
+        dz1s = torch.empty(m, hid, dtype=_f32, device=dev)
+        dx_sub = torch.empty(m, in_f, dtype=_f32, device=dev)
+        _lib.check(_lib.lib().cgs_mlp2_backward(
+            in_f, hid, out, 0, _lib.ptr(x_sub), in_f, _lib.ptr(W1), None, _lib.ptr(W2), None, _lib.ptr(_c(d_pred)), out, _lib.ptr(h_sub),
+            _lib.ptr(dx_sub), in_f, 0, _lib.ptr(dz1s), None, *[_lib.ptr(t) for t in dW], m, _lib.ptr(ws), ws.numel(),
+            _lib.current_stream()), "cgs_mlp2_backward")
+    return dW, dx_sub
+
+
+def _level_bwd_launch(ctx, saved, grads, dW, dx_sub):
+    """Step 2, the level kernel: parameter-row gradients into the RowSource's buffers (rate gradients added from the RateSide),
+    mlp_grid's step-size branch.  -> (dX [n, in], d_hyp: the hyper latents' gradient for autograd, or None when it went direct)"""
+    L = _lib.lib()
+    X, _xs, _hs, W1, b1, W2, b2, H = saved
+    cfg = ctx.cfg
+    n, in_f, hid, _out, n_stat, m = ctx.dims
+    dev, stream = X.device, _lib.current_stream()
+    smap, *sd = cfg.side.take() if cfg.side is not None else RateSide._ABSENT
+    if smap is None and dx_sub is not None and not ctx.lazy:
+        # no rate side (gradients of y / Q came through autograd) but a subset branch: its rows still need a map
+        smap = _sub_map(cfg.loc, n)
+        z = torch.zeros(m, 50 + 6 + 30 + 3, dtype=_f32, device=dev)
+        sd = [t.contiguous() for t in torch.split(z, [50, 6, 30, 3], dim=1)]
+    dxf, dxs, dxo = cfg.src.grad_buffers()
+    dX = torch.empty(n, in_f, dtype=_f32, device=dev)
+    ws2 = torch.empty(int(L.cgs_ctx_level_bwd_scratch_bytes()), dtype=torch.uint8, device=dev)
+    d_hyp_rows = _hyper_rows_direct(cfg.hyp_direct, ctx.needs_input_grad[3], n, int(dxf.shape[0]), dev)
+    dW1, db1, dW2, db2 = dW
+    # with the forward's hidden layer when it was kept (the recompute's bits, a third fewer matrix products), else from X alone
+    bwd_args = (
+        in_f, _lib.ptr(X), _lib.ptr(W1), _lib.ptr(b1), W2.data_ptr() + 4 * n_stat * hid, b2.data_ptr() + 4 * n_stat,
+        *[_lib.ptr(t) for t in grads], n, cfg.seed, *cfg.q0, _lib.ptr(cfg.rows), int(dxf.shape[0]), _lib.ptr(dxf), _lib.ptr(dxs),
+        _lib.ptr(dxo), _lib.ptr(smap), int(sd[0].shape[0]) if sd[0] is not None else 0, *[_lib.ptr(t) for t in sd],
+        _lib.ptr(dx_sub), _lib.ptr(dX), _lib.ptr(d_hyp_rows), _lib.ptr(dW1), _lib.ptr(db1), dW2.data_ptr() + 4 * n_stat * hid,
+        db2.data_ptr() + 4 * n_stat)
+    # (an instrumented cgs_ctx_level_bwd2 — a caller that wrapped the entry to see the level backward start, as the multi-rank
+    #  sequence test does — is honoured: the recompute path, the same bits)
+    if H is not None and type(L.cgs_ctx_level_bwd2) is type(L.cgs_ctx_level_bwd_h):
+        _lib.check(L.cgs_ctx_level_bwd_h(*bwd_args, _lib.ptr(H), _lib.ptr(ws2), ws2.numel(), stream), "cgs_ctx_level_bwd_h")
+    else:
+        _lib.check(L.cgs_ctx_level_bwd2(*bwd_args, _lib.ptr(ws2), ws2.numel(), stream), "cgs_ctx_level_bwd")
+    cfg.src.rows_written += n
+    if d_hyp_rows is not None:
+        cfg.hyp_direct[0].done.add(cfg.hyp_direct[1])
+        return dX, None
+    return dX, dX[:, in_f - 12:] if ctx.needs_input_grad[3] else None      # a column slice: its consumer takes strided rows
+
+
+def _level_bwd_context_inputs(ctx, dX, d_anchor, gf, gs):
+    """Step 3, a context level (X = [anchor[a_rows] | base_f[pos] | base_s[pos] | hyper]): the parents' rows, summed over their
+    children without atomics.  -> (d_f, d_s) for autograd, None where the sums went into the earlier levels' own gradient rows."""
+    cfg, need = ctx.cfg, ctx.needs_input_grad
+    _a_shape, f_shape, s_shape = ctx.shapes
+    dev = dX.device
+    in_f_ = _prefix_inplace(cfg.src, gf, f_shape, need[1])
+    in_s_ = _prefix_inplace(cfg.src, gs, s_shape, need[2])
+    d_f = in_f_ if in_f_ is not None else (torch.empty(f_shape, dtype=_f32, device=dev) if need[1] else None)
+    d_s = in_s_ if in_s_ is not None else (torch.empty(s_shape, dtype=_f32, device=dev) if need[2] else None)
+    if d_anchor is not None or d_f is not None or d_s is not None:
+        offs, order, prow = cfg.csr
+        acc = int(ctx.share_anchor) | (2 if in_f_ is not None else 0) | (4 if in_s_ is not None else 0)
+        _lib.check(_lib.lib().cgs_ctx_gather_bwd_acc(
+            _lib.ptr(dX), int(dX.shape[1]), int(f_shape[0]), _lib.ptr(offs), _lib.ptr(order), _lib.ptr(prow), _lib.ptr(d_anchor),
+            _lib.ptr(d_f), _lib.ptr(d_s), 3, 50, 6, acc, _lib.current_stream()), "cgs_ctx_gather_bwd")
+    return None if in_f_ is not None else d_f, None if in_s_ is not None else d_s
+
+
+def _level_bwd_first_inputs(ctx, dX, d_anchor):
+    """Step 4, the first level (X = [anchor[a_rows] * mask | hyper]): the anchor rows."""
+    if d_anchor is None:
+        return
+    cfg = ctx.cfg
+    # (the hyper columns of dX leave as a strided slice: mode 0 = no store for that source)
+    # (shared buffer: these rows may carry an earlier level's sums — mode 2 adds; the rows are distinct, the atomics uncontended)
+    _lib.check(_lib.lib().cgs_rowcat_bwd_masked(
+        2, _ptrs([d_anchor, None]), _ptrs([cfg.a_rows, None]), _ptrs([cfg.a_mask, None]), _ints([3, 12]), _ints([3, 12]),
+        _ints([2 if ctx.share_anchor else 1, 0]), int(dX.shape[0]), _lib.ptr(dX), _lib.current_stream()), "cgs_rowcat_bwd")
+
+
 class _LevelFused(torch.autograd.Function):
     """One level of the training level loop (scene/gaussian_model.py:1594-1616) as ONE node and one launch per direction for
     the work that runs on every row: input-row assembly (:1596-1599 / :1711-1724), mlp_grid's hidden layer and three step-size
@@ -869,219 +1078,112 @@ class _LevelFused(torch.autograd.Function):
     cgs_ctx_level_bwd (weight gradients of that branch inside the backward kernel) — plus the mean / scale outputs on the rate
     subset `loc` (the same fused MLP kernels as mlp._LevelMLP, on rows of the X the level kernel wrote).
 
-    cfg: dict(a_rows, a_mask, pos, csr, loc, n_stat, src, rows, seed, q0, outs, side) — see level_fused()."""
+    cfg: a _LevelCfg; outs = (yf, ys, yo) the slices to write — see level_fused()."""
 
     @staticmethod
-    def launch(anchor, base_f, base_s, hyp, W1, b1, W2, b2, cfg):
+    def launch(anchor, base_f, base_s, hyp, W1, b1, W2, b2, cfg, outs):
         """The forward's launch on plain values (no autograd): (X, Q, (W1c, b1c, W2c, b2c), H) — H: the hidden layer's hand-over to
-        the backward (a private byte buffer; None when cfg["need_grad"] is false or KEEP_H is off).  Called by forward(), or EARLIER by
+        the backward (a private byte buffer; None when cfg.need_grad is false or KEEP_H is off).  Called by forward(), or EARLIER by
         level_fused_launch() — the level kernels of a step need nothing the host has to wait for, so context_model enqueues them in
-        front of the rate subset's read-back and hands the result to forward() through cfg["pre"]."""
+        front of the rate subset's read-back and hands the result to forward() as `pre`."""
         from . import mlp as _mlp
         L = _lib.lib()
         _mlp._drop_stale_deferred()
-        src, rows = cfg["src"], cfg["rows"]
+        src, rows, a_rows = cfg.src, cfg.rows, cfg.a_rows
         anchor_c, hyp_c = _c(anchor.detach()), _c(hyp.detach())
         W1c, b1c, W2c, b2c = (t.detach().contiguous() for t in (W1, b1, W2, b2))
         n, in_f = int(rows.shape[0]), int(W1c.shape[1])
-        hid, out, n_stat = int(W1c.shape[0]), int(W2c.shape[0]), int(cfg["n_stat"])
+        hid, out, n_stat = int(W1c.shape[0]), int(W2c.shape[0]), cfg.n_stat
         assert (hid, out, out - n_stat) == (100, 175, 3) and rows.dtype == torch.int64 and rows.is_contiguous()
         ctxlevel = base_f is not None
         assert in_f == (71 if ctxlevel else 15) and hyp_c.shape == (n, 12)
         bf = _c(base_f.detach()) if ctxlevel else None
         bs = _c(base_s.detach()) if ctxlevel else None
-        a_rows, pos, a_mask = cfg["a_rows"], cfg["pos"], cfg["a_mask"]
         assert a_rows.dtype == torch.int64 and a_rows.is_contiguous() and int(a_rows.shape[0]) == n
-        if a_mask is not None:
-            a_mask = (a_mask if a_mask.dtype == torch.uint8 else a_mask.view(torch.uint8)).contiguous()
         _lib.require_device(anchor_c, hyp_c, W1c, W2c, src.f)
         dev = anchor_c.device
         src.rows_read += n
-        yf, ys, yo = cfg["outs"]
+        yf, ys, yo = outs
         assert yf.shape == (n, 50) and ys.shape == (n, 6) and yo.shape == (n, 30)
         assert yf.is_contiguous() and ys.is_contiguous() and yo.is_contiguous()
         X = torch.empty(n, in_f, dtype=_f32, device=dev)
         Q = torch.empty(n, 3, dtype=_f32, device=dev)
         H = None
-        if KEEP_H and cfg.get("need_grad") and n > 0 and in_f == 71:
+        if KEEP_H and cfg.need_grad and n > 0 and in_f == 71:
             H = torch.empty(int(L.cgs_ctx_level_hidden_bytes(n)), dtype=torch.uint8, device=dev)
-        stream = _lib.current_stream()
-        seed, q0 = int(cfg["seed"]), cfg["q0"]
         _lib.check(L.cgs_ctx_level_fwd_h(
-            in_f, _lib.ptr(anchor_c), int(anchor_c.shape[0]), _lib.ptr(a_rows), _lib.ptr(a_mask), _lib.ptr(bf), _lib.ptr(bs),
-            int(bf.shape[0]) if ctxlevel else 0, _lib.ptr(pos), _lib.ptr(hyp_c), n, _lib.ptr(W1c), _lib.ptr(b1c), W2c.data_ptr() + 4 * n_stat * hid, b2c.data_ptr() + 4 * n_stat, _lib.ptr(src.f),
-            _lib.ptr(src.s), _lib.ptr(src.o), _lib.ptr(rows), seed, q0[0], q0[1], q0[2], _lib.ptr(X), _lib.ptr(yf), _lib.ptr(ys),
-            _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(src.sums_buffer()), _lib.ptr(H), stream), "cgs_ctx_level_fwd_h")
+            in_f, _lib.ptr(anchor_c), int(anchor_c.shape[0]), _lib.ptr(a_rows), _lib.ptr(cfg.a_mask), _lib.ptr(bf), _lib.ptr(bs),
+            int(bf.shape[0]) if ctxlevel else 0, _lib.ptr(cfg.pos), _lib.ptr(hyp_c), n, _lib.ptr(W1c), _lib.ptr(b1c), W2c.data_ptr() + 4 * n_stat * hid, b2c.data_ptr() + 4 * n_stat, _lib.ptr(src.f),
+            _lib.ptr(src.s), _lib.ptr(src.o), _lib.ptr(rows), cfg.seed, *cfg.q0, _lib.ptr(X), _lib.ptr(yf), _lib.ptr(ys),
+            _lib.ptr(yo), _lib.ptr(Q), _lib.ptr(src.sums_buffer()), _lib.ptr(H), _lib.current_stream()), "cgs_ctx_level_fwd_h")
         return X, Q, (W1c, b1c, W2c, b2c), H
 
     @staticmethod
-    def forward(ctx, anchor, base_f, base_s, hyp, W1, b1, W2, b2, _token, cfg):
-        from . import mlp as _mlp
-        L = _lib.lib()
-        src, rows, loc = cfg["src"], cfg["rows"], cfg["loc"]
-        pre = cfg.get("pre")
+    def forward(ctx, anchor, base_f, base_s, hyp, W1, b1, W2, b2, _token, cfg, outs, pre):
         if pre is None:
-            pre = _LevelFused.launch(anchor, base_f, base_s, hyp, W1, b1, W2, b2, dict(cfg, need_grad=any(ctx.needs_input_grad)))
+            pre = _LevelFused.launch(anchor, base_f, base_s, hyp, W1, b1, W2, b2,
+                                     cfg._replace(need_grad=any(ctx.needs_input_grad)), outs)
         X, Q, (W1c, b1c, W2c, b2c), H = pre
-        n, in_f = int(rows.shape[0]), int(W1c.shape[1])
-        hid, out, n_stat = int(W1c.shape[0]), int(W2c.shape[0]), int(cfg["n_stat"])
-        ctxlevel = base_f is not None
+        loc = cfg.loc
+        n, in_f = int(cfg.rows.shape[0]), int(W1c.shape[1])
+        hid, out = int(W1c.shape[0]), int(W2c.shape[0])
         dev = X.device
-        yf, ys, yo = cfg["outs"]
-        stream = _lib.current_stream()
         pred = x_sub = h_sub = None
-        m = 0
-        lazy = bool(cfg.get("rate_lazy")) and loc is not None and cfg["side"] is not None
+        m = 0 if loc is None else int(loc.shape[0])
+        lazy = cfg.rate_lazy and loc is not None and cfg.side is not None
         if lazy:
             # the mean / scale outputs of the chosen rows are formed inside the rate kernels (cgs_rate_sub_*): nothing here
-            m = int(loc.shape[0])
-            cfg["side"].X, cfg["side"].weights = X, (W1c, b1c, W2c, b2c)
+            cfg.side.lend(X, (W1c, b1c, W2c, b2c))
         elif loc is not None:
-            m = int(loc.shape[0])
             x_sub = gather_rows_nograd(X, loc)
             pred = torch.empty(m, out, dtype=_f32, device=dev)
             h_sub = torch.empty(m, hid, dtype=_f32, device=dev)
-            _lib.check(L.cgs_mlp2_forward(in_f, hid, out, 0, _lib.ptr(x_sub), in_f, _lib.ptr(W1c), _lib.ptr(b1c), _lib.ptr(W2c),
-                                          _lib.ptr(b2c), _lib.ptr(pred), out, _lib.ptr(h_sub), m, stream), "cgs_mlp2_forward")
+            _lib.check(_lib.lib().cgs_mlp2_forward(
+                in_f, hid, out, 0, _lib.ptr(x_sub), in_f, _lib.ptr(W1c), _lib.ptr(b1c), _lib.ptr(W2c), _lib.ptr(b2c), _lib.ptr(pred),
+                out, _lib.ptr(h_sub), m, _lib.current_stream()), "cgs_mlp2_forward")
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(X, x_sub, h_sub, W1c, b1c, W2c, b2c, H)      # (H is no output of this node: no cycle, see below)
-        # (without "outs": they are this node's OUTPUTS — an output kept on its own ctx is a reference cycle through the C++
-        #  node that Python's collector cannot see: every step's level nodes, RowSource and ~350 MB of level tensors stayed
+        # (`outs` and `pre` stay off ctx: they are this node's OUTPUTS — an output kept on its own ctx is a reference cycle through
+        #  the C++ node that Python's collector cannot see: every step's level nodes, RowSource and ~350 MB of level tensors stayed
         #  alive for the life of the process, found in round 5 when the device filled up — tools/leak_probe.py)
-        ctx.cfg, ctx.dims = {k: v for k, v in cfg.items() if k not in ("outs", "pre")}, (n, in_f, hid, out, n_stat, m)
-        ctx.lazy = lazy
+        ctx.cfg, ctx.dims, ctx.lazy = cfg, (n, in_f, hid, out, cfg.n_stat, m), lazy
         ctx.shapes = (tuple(anchor.shape), None if base_f is None else tuple(base_f.shape), None if base_s is None else tuple(base_s.shape))
-        ctx.share_anchor = bool(ANCHOR_SHARED and ctx.needs_input_grad[0])
+        ctx.share_anchor = _anchor_shared(ctx.needs_input_grad[0])
         if ctx.share_anchor:
-            src.anchor_users += 1
+            cfg.src.anchor_register()
         if pred is None:
             pred = torch.empty(0, out, dtype=_f32, device=dev)
-        return yf, ys, yo, Q, pred
+        return (*outs, Q, pred)
 
     @staticmethod
     def backward(ctx, gf, gs, go, gQ, d_pred):
-        from . import mlp as _mlp
-        L = _lib.lib()
-        X, x_sub, h_sub, W1, b1, W2, b2, H = ctx.saved_tensors
-        cfg = ctx.cfg
-        n, in_f, hid, out, n_stat, m = ctx.dims
-        src, rows, loc = cfg["src"], cfg["rows"], cfg["loc"]
-        dev = X.device
-        stream = _lib.current_stream()
+        src, need = ctx.cfg.src, ctx.needs_input_grad
         gf, gs, go, gQ = (None if t is None else _c(t) for t in (gf, gs, go, gQ))
-        side0 = cfg["side"]
-        dx_sub = None
-        if ctx.lazy and side0 is not None and side0.dW is not None:
-            # the rate node's backward (cgs_rate_sub_bwd) already ran: its weight gradients are the start of this module's
-            # (no zero fill), its input-row gradient rides into the level kernel as compact rows
-            (dW1, db1, dW2, db2), dx_sub = side0.dW, side0.dx
-            side0.dW = side0.dx = side0.X = side0.weights = None
+        saved = ctx.saved_tensors
+        dW, dx_sub = _level_bwd_subset(ctx, saved, d_pred)
+        dX, d_hyp = _level_bwd_launch(ctx, saved, (gf, gs, go, gQ), dW, dx_sub)
+        a_shape, f_shape, _s_shape = ctx.shapes
+        if ctx.share_anchor:
+            d_anchor = src.anchor_target(a_shape, dX.device)
         else:
-            dW1, db1, dW2, db2 = _mlp._zeros_views(dev, (hid, in_f), (hid,), (out, hid), (out,))      # one fill for the module
-        ws = None if ctx.lazy else _mlp._wgrad_workspace(dev)
-        # the rate subset's branch first: its input gradient rides into the level kernel as compact rows
-        if (not ctx.lazy) and d_pred is not None and m > 0:
-            d_pred = _c(d_pred)
-            dz1s = torch.empty(m, hid, dtype=_f32, device=dev)
-            dx_sub = torch.empty(m, in_f, dtype=_f32, device=dev)
-            _lib.check(L.cgs_mlp2_backward(in_f, hid, out, 0, _lib.ptr(x_sub), in_f, _lib.ptr(W1), None, _lib.ptr(W2), None,
-                                           _lib.ptr(d_pred), out, _lib.ptr(h_sub), _lib.ptr(dx_sub), in_f, 0, _lib.ptr(dz1s), None,
-                                           _lib.ptr(dW1), _lib.ptr(db1), _lib.ptr(dW2), _lib.ptr(db2), m, _lib.ptr(ws), ws.numel(),
-                                           stream), "cgs_mlp2_backward")
-        side = cfg["side"] if (cfg["side"] is not None and cfg["side"].map is not None) else None
-        use_side = side is not None and side.f is not None and side.f.numel() > 0
-        smap = None
-        if use_side:
-            smap, sd = side.map, (side.f, side.s, side.o, side.q)
-        elif dx_sub is not None and not ctx.lazy:
-            # no rate side (gradients of y / Q came through autograd) but a subset branch: its rows still need a map
-            smap = torch.full((n,), -1, dtype=torch.int32, device=dev)
-            smap[loc] = torch.arange(m, dtype=torch.int32, device=dev)
-            z = torch.zeros(m, 50 + 6 + 30 + 3, dtype=_f32, device=dev)
-            sd = tuple(t.contiguous() for t in torch.split(z, [50, 6, 30, 3], dim=1))
-        else:
-            sd = (None,) * 4
-        dxf, dxs, dxo = src.grad_buffers()
-        dX = torch.empty(n, in_f, dtype=_f32, device=dev)
-        ws2 = torch.empty(int(L.cgs_ctx_level_bwd_scratch_bytes()), dtype=torch.uint8, device=dev)
-        # the hyper latents' gradient rows straight into the hyper prior's buffer (HyperDirect), when this level's block of latents
-        # came from training_step_forms(sizes=) and the latents are indexed like the per-anchor tensors (rows = coding permutation)
-        hd, d_hyp_rows = cfg.get("hyp_direct"), None
-        if hd is not None and ctx.needs_input_grad[3] and hd[0].n == int(dxf.shape[0]) and hd[0].c == 12 and hd[0].sizes[hd[1]] == n:
-            d_hyp_rows = hd[0].buffer(dev)
-        # with the forward's hidden layer when it was kept (the recompute's bits, a third fewer matrix products), else from X alone
-        bwd_args = (
-            in_f, _lib.ptr(X), _lib.ptr(W1), _lib.ptr(b1), W2.data_ptr() + 4 * n_stat * hid, b2.data_ptr() + 4 * n_stat,
-            _lib.ptr(gf), _lib.ptr(gs), _lib.ptr(go), _lib.ptr(gQ), n, int(cfg["seed"]), cfg["q0"][0], cfg["q0"][1], cfg["q0"][2],
-            _lib.ptr(rows), int(dxf.shape[0]), _lib.ptr(dxf), _lib.ptr(dxs), _lib.ptr(dxo), _lib.ptr(smap),
-            int(sd[0].shape[0]) if sd[0] is not None else 0, *[_lib.ptr(t) for t in sd],
-            _lib.ptr(dx_sub), _lib.ptr(dX), _lib.ptr(d_hyp_rows), _lib.ptr(dW1), _lib.ptr(db1), dW2.data_ptr() + 4 * n_stat * hid,
-            db2.data_ptr() + 4 * n_stat)
-        # (an instrumented cgs_ctx_level_bwd2 — a caller that wrapped the entry to see the level backward start, as the multi-rank
-        #  sequence test does — is honoured: the recompute path, the same bits)
-        if H is not None and type(L.cgs_ctx_level_bwd2) is type(L.cgs_ctx_level_bwd_h):
-            _lib.check(L.cgs_ctx_level_bwd_h(*bwd_args, _lib.ptr(H), _lib.ptr(ws2), ws2.numel(), stream), "cgs_ctx_level_bwd_h")
-        else:
-            _lib.check(L.cgs_ctx_level_bwd2(*bwd_args, _lib.ptr(ws2), ws2.numel(), stream), "cgs_ctx_level_bwd")
-        if d_hyp_rows is not None:
-            hd[0].done.add(hd[1])
-        if side is not None:
-            side.map = side.f = side.s = side.o = side.q = None
-        src.rows_written += n
-        need = ctx.needs_input_grad
-        a_shape, f_shape, s_shape = ctx.shapes
-        shared = ctx.share_anchor and need[0]
-        if shared:
-            if src.anchor_acc is None:
-                src.anchor_acc = torch.zeros(a_shape, dtype=_f32, device=dev)
-            d_anchor = src.anchor_acc
-        else:
-            d_anchor = torch.zeros(a_shape, dtype=_f32, device=dev) if need[0] else None
+            d_anchor = torch.zeros(a_shape, dtype=_f32, device=dX.device) if need[0] else None
         d_f = d_s = None
-        if f_shape is not None:                  # context level: the parents' rows, summed over their children without atomics
-            offs, order, prow = cfg["csr"]
-            # the prefix rows' gradient buffers, when this level's own gradients are row slices right behind them (_grad_prefix)
-            in_f_ = _grad_prefix(gf, int(f_shape[0])) if (PREFIX_INPLACE and need[1] and f_shape[1] == 50) else None
-            in_s_ = _grad_prefix(gs, int(s_shape[0])) if (PREFIX_INPLACE and need[2] and s_shape[1] == 6) else None
-            d_f = in_f_ if in_f_ is not None else (torch.empty(f_shape, dtype=_f32, device=dev) if need[1] else None)
-            d_s = in_s_ if in_s_ is not None else (torch.empty(s_shape, dtype=_f32, device=dev) if need[2] else None)
-            if d_anchor is not None or d_f is not None or d_s is not None:
-                acc = int(shared) | (2 if in_f_ is not None else 0) | (4 if in_s_ is not None else 0)
-                _lib.check(L.cgs_ctx_gather_bwd_acc(_lib.ptr(dX), in_f, int(f_shape[0]), _lib.ptr(offs), _lib.ptr(order), _lib.ptr(prow),
-                                                    _lib.ptr(d_anchor), _lib.ptr(d_f), _lib.ptr(d_s), 3, 50, 6, acc, stream),
-                           "cgs_ctx_gather_bwd")
-            if in_f_ is not None:
-                d_f = None                  # (already summed into the earlier levels' slices)
-            if in_s_ is not None:
-                d_s = None
-            d_hyp = dX[:, 59:] if (need[3] and d_hyp_rows is None) else None          # a column slice: its consumer takes strided rows
-        else:                                    # first level: X = [anchor[a_rows] * mask | hyper]
-            d_hyp = dX[:, 3:] if (need[3] and d_hyp_rows is None) else None
-            if d_anchor is not None:
-                a_mask = cfg["a_mask"]
-                if a_mask is not None:
-                    a_mask = (a_mask if a_mask.dtype == torch.uint8 else a_mask.view(torch.uint8)).contiguous()
-                # (the hyper columns of dX leave as the strided slice above: mode 0 = no store for that source)
-                # (shared buffer: these rows may carry an earlier level's sums — mode 2 adds; the rows are distinct, the atomics uncontended)
-                _lib.check(L.cgs_rowcat_bwd_masked(2, _ptrs([d_anchor, None]), _ptrs([cfg["a_rows"], None]), _ptrs([a_mask, None]),
-                                                   _ints([3, 12]), _ints([3, 12]), _ints([2 if shared else 1, 0]), n, _lib.ptr(dX), stream),
-                           "cgs_rowcat_bwd")
-        if shared:
-            src.anchor_users -= 1
-            if src.anchor_users > 0:
-                d_anchor = None                 # a later level of this backward hands the shared buffer on
-            else:
-                src.anchor_acc = None
-        return d_anchor, d_f, d_s, d_hyp, dW1, db1, dW2, db2, None, None
+        if f_shape is not None:
+            d_f, d_s = _level_bwd_context_inputs(ctx, dX, d_anchor, gf, gs)
+        else:
+            _level_bwd_first_inputs(ctx, dX, d_anchor)
+        if ctx.share_anchor:
+            d_anchor = src.anchor_release()          # (None unless this is the last level of the backward: that one hands it on)
+        return (d_anchor, d_f, d_s, d_hyp, *dW, None, None, None, None)
 
 
 def level_fused_launch(anchor, base_f, base_s, hyp, seq, n_stat, a_rows, a_mask, pos, src, rows, outs, q0, seed):
     """The launch of level_fused() on plain values, for a caller that creates the node later: returns `pre` for level_fused(pre=)
     (same arguments, same seed).  base_f / base_s: the coded prefix's VALUES (the buffers the earlier levels' launches wrote)."""
     l1, l2 = seq[0], seq[2]
-    cfg = dict(a_rows=a_rows, a_mask=a_mask, pos=pos, n_stat=int(n_stat), src=src, rows=rows, seed=int(seed),
-               q0=tuple(float(v) for v in q0), outs=outs, need_grad=torch.is_grad_enabled())
-    return _LevelFused.launch(anchor, base_f, base_s, hyp, l1.weight, l1.bias, l2.weight, l2.bias, cfg)
+    cfg = _LevelCfg(a_rows=a_rows, a_mask=_u8(a_mask), pos=pos, n_stat=int(n_stat), src=src, rows=rows, seed=int(seed),
+                    q0=tuple(float(v) for v in q0), need_grad=torch.is_grad_enabled())
+    return _LevelFused.launch(anchor, base_f, base_s, hyp, l1.weight, l1.bias, l2.weight, l2.bias, cfg, outs)
 
 
 def level_fused(anchor, base_f, base_s, hyp, seq, n_stat, loc, a_rows, a_mask, pos, csr, src, rows, outs, side, q0, seed=None,
@@ -1095,7 +1197,7 @@ def level_fused(anchor, base_f, base_s, hyp, seq, n_stat, loc, a_rows, a_mask, p
     the fused rate kernels (cgs_rate_sub_*) from the X this node leaves on `side`; pred is then an empty tensor.
     Returns (yf, ys, yo, Q [n,3], pred [len(loc),175] or an empty tensor)."""
     l1, l2 = seq[0], seq[2]
-    cfg = dict(a_rows=a_rows, a_mask=a_mask, pos=pos, csr=csr, loc=loc, n_stat=int(n_stat), src=src, rows=rows,
-               seed=next_seed() if seed is None else int(seed), q0=tuple(float(v) for v in q0), outs=outs, side=side,
-               rate_lazy=bool(rate_lazy), pre=pre, hyp_direct=getattr(hyp, "_cgs_hyp_direct", None) if HYPER_DIRECT else None)
-    return _LevelFused.apply(anchor, base_f, base_s, hyp, l1.weight, l1.bias, l2.weight, l2.bias, src.token, cfg)
+    cfg = _LevelCfg(a_rows=a_rows, a_mask=_u8(a_mask), pos=pos, csr=csr, loc=loc, n_stat=int(n_stat), src=src, rows=rows,
+                    seed=next_seed() if seed is None else int(seed), q0=tuple(float(v) for v in q0), side=side,
+                    rate_lazy=bool(rate_lazy), hyp_direct=getattr(hyp, "_cgs_hyp_direct", None))
+    return _LevelFused.apply(anchor, base_f, base_s, hyp, l1.weight, l1.bias, l2.weight, l2.bias, src.token, cfg, outs, pre)

@@ -85,6 +85,111 @@ def test_fused_level_equals_the_separate_launches(N, seed, rate_side, monkeypatc
         assert frac <= 2e-3 and worst <= 2e-2, (name, frac, worst)
 
 
+def _forward(pc, seed, seed0, monkeypatch):
+    """The forward of one step on `pc`: rate subset and loss weights from `seed`, noise stream ids counted from seed0 -> loss"""
+    from contextgs_amd import context_model as cm
+    from contextgs_amd import ctx_ops
+    counter = itertools.count(seed0)
+    monkeypatch.setattr(ctx_ops, "next_seed", lambda: 0x1234567 * next(counter) + 99)
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    choose = (torch.rand(pc.get_anchor.shape[0], generator=g) < 0.15).cuda()
+    monkeypatch.setattr(cm, "choose_mask_provider", lambda anchor, mab: choose & mab if mab is not None else choose)
+    binary, mab = pc.get_mask_pair()
+    fq, sq, oq, bpp, bf, bs, bo, _each = cm.multi_scale_generating(pc, pc.get_anchor, pc._hyper_latent, pc._anchor_feat, pc._offset,
+                                                                   pc.get_scaling, binary, mab, training=True, predict_bpp=True)
+    rng = np.random.default_rng(seed + 5)
+    ws = [T(rng.normal(size=tuple(t.shape)).astype(np.float32)) for t in (fq, sq, oq)]
+    return sum((t * w).sum() for t, w in zip((fq, sq, oq), ws)) + 3000.0 * bpp + 200.0 * bf + 50.0 * bs + 70.0 * bo
+
+
+# the context model's backward is bit-repeatable for these (profiles/context_route.txt §4); latent_codec's parameters are summed
+# with float atomics
+_REPEATABLE = ("_anchor_feat", "_scaling", "_offset", "_hyper_latent", "_mask", "_anchor", "mlp_grid")
+
+
+def test_interleaved_steps_sum_the_same_gradients(monkeypatch):
+    """Two steps A and B (other rate subsets, other noise) accumulated before one optimizer step, their forwards and backwards in
+    three orders: every hand-over between nodes outside autograd belongs to ONE step (ctx_ops.RowSource and its records), so the
+    order changes nothing — and the in-place prefix route is still the one taken when two steps' graphs are alive at once."""
+    from contextgs_amd import ctx_ops
+    pc = _model(3000, 2)
+    hits = []
+    real = ctx_ops.JoinedGrads.prefix
+
+    def prefix(self, *a):
+        v = real(self, *a)
+        hits[-1] += v is not None
+        return v
+    monkeypatch.setattr(ctx_ops.JoinedGrads, "prefix", prefix)
+    _forward(pc, 2, 1, monkeypatch)                   # (builds the level plan: every order below runs on the cached one)
+    results = []
+    for order in ("AaBb", "ABab", "ABba"):            # capital = forward, small = backward
+        for p in pc.parameters():
+            p.grad = None
+        hits.append(0)
+        loss = {}
+        for s in order:
+            if s.isupper():
+                loss[s.lower()] = _forward(pc, 2 if s == "A" else 11, 1 if s == "A" else 1000, monkeypatch)
+            else:
+                loss.pop(s).backward()
+        results.append({n_: p.grad.detach().clone() for n_, p in pc.named_parameters() if p.grad is not None})
+    # two context levels per step look up the feature and the scaling prefix
+    assert hits == [4 * (gi.LEVELS - 1)] * 3, hits
+    first = results[0]
+    assert any(n_.startswith("latent_codec") for n_ in first) and all(any(n_.startswith(k) for n_ in first) for k in _REPEATABLE)
+    for other in results[1:]:
+        assert set(other) == set(first)
+        for name, a in first.items():
+            b = other[name]
+            if name.startswith(_REPEATABLE):
+                assert torch.equal(a, b), (name, float((a - b).abs().max()))
+            else:
+                assert float((a - b).abs().max()) <= 2e-5 * float(a.abs().max()) + 1e-12, name
+
+
+_ALL_ON = {}
+
+
+@pytest.mark.parametrize("knob", ["PREFIX_INPLACE", "ANCHOR_SHARED", "HYPER_DIRECT"])
+def test_each_fallback_alone_sums_the_same_gradients(knob, monkeypatch):
+    """Every in-place route has a fallback that returns a gradient tensor for autograd to sum (ctx_ops.PREFIX_INPLACE,
+    ANCHOR_SHARED, HYPER_DIRECT): the same forward, the same sums in another order backward.
+
+    The quantised tensors are compared bit for bit.  The four rate values can not be: the rate and hyper-bits kernels close their
+    sums with float atomics, and eight runs of this very step with NOTHING changed give two rate vectors one ulp apart (1.5e-7
+    relative), with every knob setting, before and after the ledger (profiles/ctx_ops_ledger.txt §3; profiles/context_route.txt
+    §4 measured 0 to 3 ulp).  They are sums of non-negative terms added in arrival order, one rounding per add: held to 4 ulp."""
+    from contextgs_amd import ctx_ops
+    assert ctx_ops.PREFIX_INPLACE and ctx_ops.ANCHOR_SHARED and ctx_ops.HYPER_DIRECT
+    if not _ALL_ON:
+        _ALL_ON.update(_run(3000, 2, True, monkeypatch))
+    monkeypatch.setattr(ctx_ops, knob, False)
+    off = _run(3000, 2, True, monkeypatch)
+    for k in ("fq", "sq", "oq"):
+        assert torch.equal(off[k], _ALL_ON[k]), k
+    print("rates", off["bits"].tolist(), _ALL_ON["bits"].tolist())
+    assert bool(((off["bits"] - _ALL_ON["bits"]).abs() <= 4 * 2.0 ** -23 * _ALL_ON["bits"].abs()).all()), (off["bits"], _ALL_ON["bits"])
+    assert set(off["grads"]) == set(_ALL_ON["grads"])
+    for name in sorted(_ALL_ON["grads"]):
+        frac, worst = _close(name, off["grads"][name], _ALL_ON["grads"][name], 1e-3, 2e-4)
+        assert frac <= 2e-3 and worst <= 2e-2, (name, frac, worst)
+
+
+def test_a_second_backward_of_one_step_raises(monkeypatch):
+    """A step's records are used up by its backward: running it again (retain_graph) must raise — RateSide's loan is gone, or the
+    RowSource counts more rows written than read — and hand the per-anchor parameters no gradient."""
+    pc = _model(3000, 2)
+    loss = _forward(pc, 2, 1, monkeypatch)
+    loss.backward(retain_graph=True)
+    assert pc._anchor_feat.grad is not None
+    for p in pc.parameters():
+        p.grad = None
+    with pytest.raises((RuntimeError, AssertionError)):
+        loss.backward()
+    assert pc._anchor_feat.grad is None and pc._scaling.grad is None and pc._offset.grad is None
+
+
 def test_fused_level_is_the_default_and_runs_the_level_kernels(monkeypatch):
     """The product path launches cgs_ctx_level_fwd / _bwd (not the round-4 launches) when nothing is overridden."""
     from contextgs_amd import context_model as cm
