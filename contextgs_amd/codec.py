@@ -93,7 +93,6 @@ def host_pool():
     device launches of the level loop."""
     global _POOL
     if _POOL is None:
-        import os
         from concurrent.futures import ThreadPoolExecutor
         _POOL = ThreadPoolExecutor(max_workers=max(2, min(32, os.cpu_count() or 2)), thread_name_prefix="cgs-codec")
     return _POOL
@@ -213,14 +212,11 @@ class BernoulliEncodeJob:
         if S <= 0:
             return
         assert int(off_h[-1]) == sym.numel() and int(off_h[0]) == 0
-        caps = ((off_h[1:] - off_h[:-1]) * 2 + 16 + 7) // 8 * 8
-        out_off_h = torch.zeros(S + 1, dtype=torch.int64)
-        out_off_h[1:] = torch.cumsum(caps, 0)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(self.stream):
-            off_d, out_off = off_h.to(dev, non_blocking=True), out_off_h.to(dev, non_blocking=True)
-            out = torch.empty(int(out_off_h[-1]) + 16, dtype=torch.uint8, device=dev)
-            self.st_len = st_len = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+            off_d = off_h.to(dev, non_blocking=True)
+            out_off_h, out_off, out, st_len = _slot_layout(off_h[1:] - off_h[:-1], _stream_slot_bytes, dev, non_blocking=True)
+            self.st_len = st_len
             raw = self.stream.cuda_stream
             _lib.check(L.cgs_bernoulli_ac_encode(_lib.ptr(sym), bernoulli_c1(p0), _lib.ptr(off_d), S, _lib.ptr(out),
                                                  _lib.ptr(out_off), _lib.ptr(st_len[1:]), _lib.ptr(st_len[:1]), raw),
@@ -259,22 +255,13 @@ def bernoulli_decode_packed(p0, stream_off, blob, lens, device=None):
     L = _lib.lib()
     off_h = torch.as_tensor(stream_off, dtype=torch.int64).cpu()
     S = int(off_h.numel()) - 1
-    if isinstance(blob, torch.Tensor) and blob.is_cuda:
-        dev, in_d = blob.device, blob
-    else:
-        dev = torch.device(device if device is not None else "cuda")
-        buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
-        in_d = torch.zeros(buf.size + 16, dtype=torch.uint8, device=dev)
-        if buf.size:
-            in_d[: buf.size].copy_(torch.from_numpy(np.ascontiguousarray(buf) if buf.flags.writeable else buf.copy()))
+    in_d, _ = _blob_on_device(blob, device if device is not None else "cuda")
+    dev = in_d.device
     n = int(off_h[-1]) if S >= 0 and off_h.numel() else 0
     out = torch.empty(n, dtype=torch.float32, device=dev)
     if S <= 0:
         return out
-    lens = np.asarray(lens, dtype=np.int64)
-    assert lens.shape[0] == S
-    in_off_h = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum(lens, out=in_off_h[1:])
+    in_off_h = _stream_starts(lens, S)
     assert int(in_off_h[-1]) <= int(in_d.numel()), "stream lengths exceed the blob"
     in_off, off_d = _upload_small([in_off_h, off_h], dev)
     _lib.check(L.cgs_bernoulli_ac_decode(bernoulli_c1(p0), _lib.ptr(off_d), S, _lib.ptr(in_d), _lib.ptr(in_off), _lib.ptr(out),
@@ -285,6 +272,48 @@ def bernoulli_decode_packed(p0, stream_off, blob, lens, device=None):
 # ---- batched device Gaussian codec ---------------------------------------------------------------
 def _f(t):
     return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
+
+
+def _blob_on_device(blob, device):
+    """bytes / uint8 ndarray / uint8 device tensor -> (uint8 device tensor, byte count), followed by >= 16 readable bytes."""
+    # (the decoders' word reads may run past the last stream.  StagedFiles hands its device slices out with that room behind
+    #  them, so a device tensor is taken as it is; a host blob goes into a zeroed buffer of its own on `device`)
+    if isinstance(blob, torch.Tensor) and blob.is_cuda:
+        return blob, int(blob.numel())
+    buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
+    in_d = torch.zeros(buf.size + 16, dtype=torch.uint8, device=torch.device(device))
+    if buf.size:
+        in_d[: buf.size].copy_(torch.from_numpy(np.ascontiguousarray(buf) if buf.flags.writeable else buf.copy()))
+    return in_d, int(buf.size)
+
+
+def _stream_starts(lens, S, what=None):
+    """Byte lengths of S streams packed back to back -> their int64 start offsets [S + 1]."""
+    lens = np.asarray(lens, dtype=np.int64)
+    assert lens.shape[0] == S, what
+    return np.concatenate([np.zeros(1, np.int64), np.cumsum(lens)])
+
+
+def _stream_slot_bytes(n_sym, sym_bytes=2):
+    """Slot of one serial stream of n_sym symbols (int or int64 tensor): at most sym_bytes each, the coder's closing bytes, 8-aligned."""
+    return (n_sym * sym_bytes + 16 + 7) // 8 * 8
+
+
+def _lane_block_slot_bytes(n_sym, sym_bytes=2):
+    """cgs_lanes_block_slot_bytes(n_sym, sym_bytes): the 128-byte header of a block and 64 lane slots of ceil(n_sym / 64) symbols."""
+    return 128 + 64 * _stream_slot_bytes((n_sym + 63) // 64, sym_bytes)
+
+
+def _slot_layout(lens_sym, slot_bytes, dev, non_blocking=False):
+    """Host int64 symbol counts [S], a capacity rule -> (out_off host int64 [S + 1], on the device, slot buffer, [status, len...])."""
+    # ([status, len_0 .. len_{S-1}] int32 in one zeroed buffer: ONE device-to-host read of it decides everything after the
+    #  launch.  Everything is enqueued under the caller's current stream.)
+    S = int(lens_sym.numel())
+    out_off_h = torch.zeros(S + 1, dtype=torch.int64)
+    out_off_h[1:] = torch.cumsum(slot_bytes(lens_sym), 0)
+    out = torch.empty(int(out_off_h[-1]) + 16, dtype=torch.uint8, device=dev)
+    out_off = out_off_h.to(dev, non_blocking=non_blocking)
+    return out_off_h, out_off, out, torch.zeros(S + 1, dtype=torch.int32, device=dev)
 
 
 _STAGE = {}
@@ -300,7 +329,6 @@ def _pinned_staging(nbytes: int, key: str = "bitstream") -> torch.Tensor:
 
 
 _STAGE_PIECE = 8 << 20
-_STAGE_READY = None
 
 
 class StageReady:
@@ -325,11 +353,6 @@ class StageReady:
         first, last = (a0 - self.base + lo) // _STAGE_PIECE, (a0 - self.base + hi - 1) // _STAGE_PIECE
         for i in range(first, min(last, len(self.events) - 1) + 1):
             self.events[i].synchronize()
-
-
-def stage_ready():
-    """The arrival tracker of the last staged download of this process, or None when it was waited for inline."""
-    return _STAGE_READY
 
 
 def to_host_pinned(t: torch.Tensor, key: str) -> np.ndarray:
@@ -400,7 +423,9 @@ def gaussian_encode_packed(x, mean, scale, Q, stream_off, q_div=1, staging=False
     blob = uint8 ndarray holding the S streams back to back (exactly the bytes of the reference's
     b"".join(chunk strings) file), lens int64[S], min/max int32[S] (host).
     lanes (container version 2): every [stream_off[s], stream_off[s+1]) is a BLOCK coded as 64 interleaved lane streams
-    behind a 128-byte header of their lengths (csrc/codec.hip, "Lane-parallel Gaussian codec")."""
+    behind a 128-byte header of their lengths (csrc/codec.hip, "Lane-parallel Gaussian codec").
+    deferred (with staging): the download is queued and NOT waited for, and a fifth item is returned: its StageReady, for
+    write_file(..., ready=) — or None when nothing is in flight."""
     L = _lib.lib()
     _lib.require_device(x, mean, scale, Q)
     x, mean, scale, Q = _f(x).reshape(-1), _f(mean).reshape(-1), _f(scale).reshape(-1), _f(Q).reshape(-1)
@@ -408,7 +433,8 @@ def gaussian_encode_packed(x, mean, scale, Q, stream_off, q_div=1, staging=False
     off = torch.as_tensor(stream_off, dtype=torch.int64)
     S = int(off.numel()) - 1
     if S <= 0:
-        return np.zeros(0, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int32)
+        empty = (np.zeros(0, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int32))
+        return empty + (None,) if deferred else empty
     off_h = off.cpu()
     off_d = off_h.to(dev)
     stream = _lib.current_stream()
@@ -416,17 +442,7 @@ def gaussian_encode_packed(x, mean, scale, Q, stream_off, q_div=1, staging=False
     mn, mx = mnmx[0], mnmx[1]
     _lib.check(L.cgs_gaussian_stream_minmax(_lib.ptr(x), _lib.ptr(Q), q_div, _lib.ptr(off_d), S, _lib.ptr(mn),
                                             _lib.ptr(mx), stream), "cgs_gaussian_stream_minmax")
-    lens_sym = (off_h[1:] - off_h[:-1])
-    if lanes:
-        caps = 128 + 64 * (((lens_sym + 63) // 64 * 2 + 16 + 7) // 8 * 8)        # cgs_lanes_block_slot_bytes
-    else:
-        caps = (lens_sym * 2 + 16 + 7) // 8 * 8
-    out_off_h = torch.zeros(S + 1, dtype=torch.int64)
-    out_off_h[1:] = torch.cumsum(caps, 0)
-    out = torch.empty(int(out_off_h[-1]) + 16, dtype=torch.uint8, device=dev)
-    out_off = out_off_h.to(dev)
-    # [status, len_0 .. len_{S-1}] in one buffer: ONE device->host read decides everything below
-    st_len = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    _, out_off, out, st_len = _slot_layout(off_h[1:] - off_h[:-1], _lane_block_slot_bytes if lanes else _stream_slot_bytes, dev)
     status, out_len = st_len[:1], st_len[1:]
     enc = L.cgs_gaussian_ac_encode_lanes if lanes else L.cgs_gaussian_ac_encode
     _lib.check(enc(_lib.ptr(x), _lib.ptr(mean), _lib.ptr(scale), _lib.ptr(Q), q_div,
@@ -450,13 +466,12 @@ def gaussian_encode_packed(x, mean, scale, Q, stream_off, q_div=1, staging=False
         _lib.check(L.cgs_streams_compact(_lib.ptr(out), _lib.ptr(out_off), _lib.ptr(out_len), _lib.ptr(dst_off), S,
                                          _lib.ptr(packed), stream), "cgs_streams_compact")
     nbytes = int(lens.sum())
-    global _STAGE_READY
-    _STAGE_READY = None
+    ready = None
     if staging and nbytes > 0:
         # pinned, reused staging buffer: ~25 GB/s instead of a pageable copy (~5 GB/s, 25 ms for a 1 M-anchor model).
         # The returned blob ALIASES it: valid until the next staging call (the container driver writes the files first).
-        # deferred: the download is queued in pieces with an event each and NOT waited for: write_file(..., ready=
-        # stage_ready()) lets the writer threads start on a piece the moment it has landed, so the ~5 ms of PCIe and the
+        # deferred: the download is queued in pieces with an event each and NOT waited for: write_file(..., ready=the
+        # returned tracker) lets the writer threads start on a piece the moment it has landed, so the ~5 ms of PCIe and the
         # ~5 ms of page-cache writes of a 1 M-anchor container overlap instead of adding up.
         mnmx_h = mnmx.cpu().numpy()                   # (before the big copies: this read drains the stream)
         stage = _pinned_staging(nbytes)
@@ -469,15 +484,14 @@ def gaussian_encode_packed(x, mean, scale, Q, stream_off, q_div=1, staging=False
             ev.record(cs)
             events.append(ev)
         ready = StageReady(stage.data_ptr(), nbytes, events, packed)
-        if deferred:
-            _STAGE_READY = ready
-        else:
+        if not deferred:
             ready.wait_all()
         blob = stage.numpy()[:nbytes]
     else:
         blob = packed.cpu().numpy()[:nbytes]
         mnmx_h = mnmx.cpu().numpy()
-    return blob, lens, mnmx_h[0], mnmx_h[1]
+    coded = (blob, lens, mnmx_h[0], mnmx_h[1])
+    return coded + (ready,) if deferred else coded
 
 
 def gaussian_encode_streams(x, mean, scale, Q, stream_off, q_div=1):
@@ -506,19 +520,15 @@ def _pack_flat(parts, dev):
     return flat, sizes
 
 
-def _expand_q(Q, q_div):
-    Q = _f(Q).reshape(-1)
-    return Q if q_div == 1 else Q.repeat_interleave(int(q_div))
-
-
 def gaussian_encode_groups(groups, staging=False, lanes=False, overlap=None, deferred=False):
     """groups = [(x, mean, scale, Q, stream_off, q_div), ...] -> [(blob, lens, min, max), ...] (see gaussian_encode_packed).
     staging: download through the module's reused pinned buffer; the blobs then alias it until the next staging call.
     All streams of all groups go through ONE coder launch: a stream is a serial chain on one wave, so the launch
-    lasts as long as its longest stream however many streams it holds."""
+    lasts as long as its longest stream however many streams it holds.
+    deferred: -> (that list, the download's StageReady or None), see gaussian_encode_packed."""
     groups = list(groups)
     if not groups:
-        return []
+        return ([], None) if deferred else []
     xs, ms, ss, qs, edges, counts, base = [], [], [], [], [torch.zeros(1, dtype=torch.int64)], [], 0
     dev = groups[0][0].device
     _lib.require_device(*[t for g_ in groups for t in g_[:4]])
@@ -544,11 +554,14 @@ def gaussian_encode_groups(groups, staging=False, lanes=False, overlap=None, def
         e0, e1 = int(E[s0]), int(E[s1])
         part = gaussian_encode_packed(X[e0:e1], M[e0:e1], Sc[e0:e1], Qe[e0:e1], E[s0:s1 + 1] - e0, 1, lanes=lanes)
         parts = D.gather_objects(part, dst=0)
+        ready = None                                  # (gathered blobs are host arrays of their own)
         if parts is None:
-            return None
+            return (None, None) if deferred else None
         blob, lens, mn, mx = (np.concatenate([p[i] for p in parts]) for i in range(4))
     else:
-        blob, lens, mn, mx = gaussian_encode_packed(X, M, Sc, Qe, E, 1, staging=staging, lanes=lanes, overlap=overlap, deferred=deferred)
+        blob, lens, mn, mx, *ready = gaussian_encode_packed(X, M, Sc, Qe, E, 1, staging=staging, lanes=lanes, overlap=overlap,
+                                                            deferred=deferred)
+        ready = ready[0] if deferred else None
         overlap = None
     if overlap is not None:
         overlap()
@@ -557,7 +570,7 @@ def gaussian_encode_groups(groups, staging=False, lanes=False, overlap=None, def
         nb = int(lens[s0:s0 + c].sum())
         out.append((blob[b0:b0 + nb], lens[s0:s0 + c], mn[s0:s0 + c], mx[s0:s0 + c]))
         s0 += c; b0 += nb
-    return out
+    return (out, ready) if deferred else out
 
 
 def gaussian_decode_packed(mean, scale, Q, stream_off, min_v, max_v, blob, lens, q_div=1, lanes=False):
@@ -572,20 +585,9 @@ def gaussian_decode_packed(mean, scale, Q, stream_off, min_v, max_v, blob, lens,
     x_out = torch.empty(mean.numel(), dtype=torch.float32, device=dev)
     if S <= 0:
         return x_out
-    lens = np.asarray(lens, dtype=np.int64)
-    assert lens.shape[0] == S
-    in_off_h = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum(lens, out=in_off_h[1:])
-    if isinstance(blob, torch.Tensor) and blob.is_cuda:
-        # already on the device (StagedFiles): a uint8 slice followed by >= 16 readable bytes of its storage
-        assert blob.dtype == torch.uint8 and blob.numel() == int(in_off_h[-1]), "stream lengths do not add up to the blob"
-        in_d = blob
-    else:
-        buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
-        assert buf.size == int(in_off_h[-1]), "stream lengths do not add up to the blob"
-        in_d = torch.empty(buf.size + 16, dtype=torch.uint8, device=dev)
-        if buf.size:
-            in_d[: buf.size].copy_(torch.from_numpy(np.ascontiguousarray(buf) if buf.flags.writeable else buf.copy()))
+    in_off_h = _stream_starts(lens, S)
+    in_d, nbytes = _blob_on_device(blob, dev)
+    assert in_d.dtype == torch.uint8 and nbytes == int(in_off_h[-1]), "stream lengths do not add up to the blob"
     in_off, mn, mx, off_d = _upload_small([in_off_h, np.asarray(min_v, dtype=np.int32), np.asarray(max_v, dtype=np.int32), off_h],
                                           dev)
     if lanes:
@@ -873,13 +875,8 @@ def table_encode_lanes(sym, cdf, cdf_len, offset, block):
     if S == 0:
         return np.zeros(0, np.uint8), np.zeros(0, np.int64)
     dev = sym.device
-    lens_sym = edges_h[1:] - edges_h[:-1]
-    caps = 128 + 64 * (((lens_sym + 63) // 64 * 6 + 16 + 7) // 8 * 8)                       # cgs_lanes_block_slot_bytes(n, 6)
-    out_off_h = torch.zeros(S + 1, dtype=torch.int64)
-    out_off_h[1:] = torch.cumsum(caps, 0)
-    edges, ch, out_off = edges_h.to(dev), ch_h.to(dev), out_off_h.to(dev)
-    out = torch.empty(int(out_off_h[-1]) + 16, dtype=torch.uint8, device=dev)
-    st_len = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    edges, ch = edges_h.to(dev), ch_h.to(dev)
+    _, out_off, out, st_len = _slot_layout(edges_h[1:] - edges_h[:-1], lambda n: _lane_block_slot_bytes(n, 6), dev)
     cdf = cdf.to(torch.int32).contiguous()
     cl, of = cdf_len.to(torch.int32).contiguous(), offset.to(torch.int32).contiguous()
     stream = _lib.current_stream()
@@ -908,17 +905,8 @@ def table_decode_lanes(blob, lens, C_, N, cdf, cdf_len, offset, medians, block):
     S = int(ch_h.numel())
     if S == 0:
         return out
-    lens = np.asarray(lens, dtype=np.int64)
-    assert lens.shape[0] == S, "hyper.b: block count does not match the header"
-    if isinstance(blob, torch.Tensor) and blob.is_cuda:
-        in_d = blob
-    else:
-        buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else blob
-        in_d = torch.zeros(buf.size + 16, dtype=torch.uint8, device=dev)
-        if buf.size:
-            in_d[: buf.size].copy_(torch.from_numpy(np.ascontiguousarray(buf) if buf.flags.writeable else buf.copy()))
-    in_off_h = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum(lens, out=in_off_h[1:])
+    in_off_h = _stream_starts(lens, S, "hyper.b: block count does not match the header")
+    in_d, _ = _blob_on_device(blob, dev)
     assert int(in_off_h[-1]) <= int(in_d.numel())
     # (every operand is held in a local until the launch is enqueued: a temporary's block goes back to the caching allocator the
     #  moment its pointer has been read, and the next temporary's upload would land in it ahead of the kernel)
@@ -1076,8 +1064,7 @@ def anchor_decode(stream, device=None):
         buf = np.frombuffer(stream, dtype=np.uint8) if not isinstance(stream, np.ndarray) else stream.reshape(-1).view(np.uint8)
         total = int(buf.size)
         h = _anchor_header(buf.tobytes(), total)
-        in_d = torch.zeros(total + 16, dtype=torch.uint8, device=dev)
-        in_d[:total].copy_(torch.from_numpy(buf.copy()))
+        in_d, _ = _blob_on_device(buf, dev)
     N, B, nb, n_cls, hdr = h["N"], h["B"], h["n_blocks"], h["n_cls"], h["header_bytes"]
     q = torch.empty(N, 3, dtype=torch.int32, device=dev)
     if N == 0:

@@ -21,6 +21,12 @@ Container version 3 (opt-in) is version 2 with the anchors coded: anchor.b (code
 classes through the table coder, raw low bits) replaces anchor.npy, and every per-anchor tensor is coded in that sorted order, so
 the decoded model's rows come back sorted by Morton key.
 
+Layout of the code: `ContainerLayout` is the one record of what a container version means.  Built when writing (requested version,
+module constants) or when reading (the header: `ContainerMeta` is meta.b by name), it alone says where streams and blocks are cut,
+which files are staged in which order and what the header's 15th item holds: both directions must agree on that byte for byte.
+`conduct_encoding` / `conduct_decoding` read top to bottom as the schedule: one function per stage, one `_Coding` object carrying the
+buffers; a stage that differs by version (masks, hyper, anchors, the offsets' launch) is listed per version in `_ENCODE` / `_DECODE`.
+
 Deliberate deviation: the reference's decoder raises IndexError when fewer
 than 10 000 anchors are valid (:1322-1331); this one decodes any size.
 """
@@ -29,6 +35,9 @@ from __future__ import annotations
 import os
 import re
 import time
+from collections import namedtuple
+from functools import partial
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -36,9 +45,8 @@ import torch.nn as nn
 
 from . import codec
 from . import dist as mgpu
-from .context_model import (context_rows, extract_context_feat, find_divide_scale, grid_mlp, level_plan, multi_scale_generating,
-                            split_prediction)
-from .encodings import Q_anchor, Quantize_anchor, STE_multistep, decoder, encoder
+from .context_model import context_rows, find_divide_scale, grid_mlp, level_plan, multi_scale_generating, split_prediction
+from .encodings import Q_anchor, Quantize_anchor, STE_multistep
 
 bit2MB_scale = 8 * 1024 * 1024
 MAX_BATCH = 1_000                                              # :1071
@@ -282,43 +290,141 @@ def estimate_final_bits(pc):                                   # :980-1004
 
 
 V2_BLOCK_MIN = 64 * 128                  # shortest block of the per-group policy: 128 symbols per lane stream
-V2_BLOCK_POLICY = 2                      # 0 / absent: every group in blocks of "block_symbols"; 1, 2: _block_for
+V2_BLOCK_POLICY = 2                      # 0 / absent: every group in blocks of "block_symbols"; 1, 2: ContainerLayout.block_symbols
 
 
-def _block_for(n_sym, policy=V2_BLOCK_POLICY, base=None):
-    """Symbols per block.  A coder launch lasts as long as its longest lane stream (block / 64 serial symbols), and the decoder's
-    three level launches depend on each other: the two small levels would occupy a few dozen waves for 512-symbol chains.
-    Policy 2 (what the encoder writes): ONE block size per LEVEL — n_sym = the level's feature symbols (anchors x 50), the same
-    size for its scaling and offset groups, which ride in the same launch — halved until the level's features make >= 256 blocks
-    (one wave per CU) or lane streams are 128 symbols long: at 1 M and at 500 k anchors the big level keeps 32 768-symbol
-    blocks, the middle one gets 16 384, the small one 8 192 (a block costs a 128-byte header and 64 stream ends, ~0.6 % of its
-    bytes at 32 768 symbols: +0.15 % of the container for the shorter blocks).
-    Policy 1 (containers written earlier in round 5; decoded, no longer written): per GROUP, n_sym = the group's own symbols,
-    halved until >= 1024 blocks.  Encoder and decoder derive the size from the counts in the header alone."""
-    base = V2_BLOCK if base is None else int(base)
-    if not policy:
-        return base
-    want = 1024 if int(policy) == 1 else 256
-    b = base
-    while b > V2_BLOCK_MIN and n_sym // b < want:
-        b //= 2
-    return b
+# ---- the header by name -------------------------------------------------------------------------------------------------------
+# meta.b: the reference's 14-item list (:1277) in its order, and the 15th item of container versions 2 and 3 (None: absent).
+# n_anchors counts every anchor of the model, valid or not; n_levels the valid ones per level, in the order the levels are coded;
+# the per-level dicts map a level to its per-stream (version 1) or per-block lists; bit_hyper is per hyper string / block.
+ContainerMeta = namedtuple("ContainerMeta", "n_anchors max_batch min_feat max_feat min_scaling max_scaling min_offsets max_offsets "
+                           "prob_masks bit_hyper bit_feat bit_scaling bit_offsets n_levels extra", defaults=[None])
 
 
-def _level_blocks(n_level, n_group, D, policy, base=None):
-    """Block size of a group of n_group symbols in a level of n_level anchors (see _block_for)."""
-    return _block_for(n_group if int(policy or 0) == 1 else n_level * D, policy, base)
+def _pack_meta(meta):
+    # ContainerMeta -> the list torch.save writes as meta.b.
+    return list(meta[:14]) + ([meta.extra] if meta.extra is not None else [])
 
 
-def _block_edges(n_sym, block=None):
-    """Element offsets of the version-2 blocks of a group of n_sym symbols."""
-    block = V2_BLOCK if block is None else int(block)
-    return torch.tensor(list(range(0, n_sym, block)) + [n_sym] if n_sym > 0 else [0], dtype=torch.int64)
+def _unpack_meta(items):
+    return ContainerMeta(*items[:14], items[14] if len(items) > 14 else None)
 
 
-def _chunk_rows(n, batch=MAX_BATCH):
-    edges = list(range(0, n, batch)) + [n]
-    return edges if n > 0 else [0]
+# ---- the layout: what a container version means -----------------------------------------------------------------------------
+def _edges(n, step):
+    # 0, step, 2 step, ..., n: the element offsets of the blocks (or chunks) of n symbols (or rows)
+    return torch.tensor(list(range(0, n, int(step))) + [n] if n > 0 else [0], dtype=torch.int64)
+
+
+class ContainerLayout(NamedTuple):
+    """How one container is cut.  Built in two places only: for_writing and from_header."""
+    # The encoder and the decoder answer every question about streams, blocks and files through it, with the same code.  Nothing
+    # outside this class looks at the version number; the stage functions further down are picked by it once per call.
+    version: int                         # as stored: 1, 2 or 3
+    max_batch: int                       # anchors per version-1 chunk stream (x 10: per hyper string)
+    mask_chunk: int                      # anchors per mask chunk stream
+    block: int                           # "block_symbols": the block size the policy starts from
+    policy: int                          # "block_policy"
+    hyper_block: int                     # anchors of one channel per hyper.b block
+    block_min: int                       # where the halving of block_symbols stops (not stored: both sides take the module's)
+
+    @staticmethod
+    def _check_version(version, unknown, role):
+        if version not in (1, 2, 3):
+            raise unknown
+        if version == 3 and mgpu.world() > 1:
+            raise NotImplementedError(f"container version 3 (anchors coded in Morton order) is {role} by one rank only")
+
+    @classmethod
+    def for_writing(cls, version=None):
+        # (the module's constants as they are at the call)
+        version = default_container_version() if version is None else int(version)
+        cls._check_version(version, ValueError(f"container version {version}: 1 (the reference's container), 2 or 3"), "written")
+        mask_chunk = V2_CHUNK["masks"] if version > 1 else MAX_BATCH
+        return cls(version, MAX_BATCH, mask_chunk, V2_BLOCK, V2_BLOCK_POLICY, V2_HYPER_BLOCK, V2_BLOCK_MIN)
+
+    @classmethod
+    def from_header(cls, meta):
+        # (meta: a ContainerMeta.  14 items are version 1; a 15th item without "block_policy" was cut by policy 0)
+        extra = meta.extra if meta.extra is not None else {}
+        version = int(extra.get("version", 1))
+        cls._check_version(version, RuntimeError(f"meta.b: container version {version} is newer than this decoder (1, 2, 3)"), "decoded")
+        max_batch, mask_chunk = int(meta.max_batch), int(extra["chunk"]["masks"] if version > 1 else meta.max_batch)
+        return cls(version, max_batch, mask_chunk, int(extra.get("block_symbols", V2_BLOCK)), int(extra.get("block_policy", 0)),
+                   int(extra.get("hyper_block", V2_HYPER_BLOCK)), V2_BLOCK_MIN)
+
+    # feat / scaling / offsets are blocks of 64 interleaved lane streams (else 1000-anchor chunk streams)
+    lanes = property(lambda self: self.version >= 2)
+    # masks and hyper latents go through the device coders (else: a serial host stream, host rANS strings)
+    device_coders = property(lambda self: self.version >= 2)
+    # anchor.b in Morton order (else anchor.npy in the model's order)
+    anchors_coded = property(lambda self: self.version == 3)
+
+    def block_symbols(self, n_level, n_group, D):
+        # Symbols per block of a group of n_group symbols in a level of n_level anchors with D features each.
+        # A coder launch lasts as long as its longest lane stream (block / 64 serial symbols), and the decoder's three level
+        # launches depend on each other: the two small levels would occupy a few dozen waves for 512-symbol chains.
+        # Policy 2 (what the encoder writes): ONE block size per LEVEL — from the level's feature symbols (anchors x D), the same
+        # size for its scaling and offset groups, which ride in the same launch — halved until the level's features make >= 256
+        # blocks (one wave per CU) or lane streams are 128 symbols long: at 1 M and at 500 k anchors the big level keeps
+        # 32 768-symbol blocks, the middle one gets 16 384, the small one 8 192 (a block costs a 128-byte header and 64 stream
+        # ends, ~0.6 % of its bytes at 32 768 symbols: +0.15 % of the container for the shorter blocks).
+        # Policy 1 (containers written earlier): per GROUP, from the group's own symbols, halved until >= 1024 blocks.
+        # Policy 0 / absent: every group in blocks of "block_symbols".  The size follows from the counts in the header alone.
+        if not self.policy:
+            return self.block
+        n_sym, want = (n_group, 1024) if self.policy == 1 else (n_level * D, 256)
+        b = self.block
+        while b > self.block_min and n_sym // b < want:
+            b //= 2
+        return b
+
+    def mask_edges(self, N_valid, K):
+        # Symbol edges of the mask streams of N_valid anchors with K offsets each (version 1: the one serial stream).
+        return _edges(N_valid, self.mask_chunk if self.device_coders else max(N_valid, 1)) * K
+
+    def group_edges(self, n_level, width, D):
+        # Symbol edges of a level's feature (width = D) or scaling (width = 6) group: n_level x width symbols.
+        if self.lanes:
+            return _edges(n_level * width, self.block_symbols(n_level, n_level * width, D))
+        return _edges(n_level, self.max_batch) * width
+
+    def offset_edges(self, n_level, D, live):
+        # Host symbol edges of a level's offsets group, which holds the live slots only.
+        # live: the running count of live slots in front of every anchor row and behind the last, int64 [n_level + 1] on any
+        # device (lane blocks need its last entry alone and take a plain count as well)
+        if self.lanes:
+            n_live = int(live[-1]) if isinstance(live, torch.Tensor) else int(live)
+            return _edges(n_live, self.block_symbols(n_level, n_live, D))
+        return live[_edges(n_level, self.max_batch).to(live.device)].cpu()
+
+    def staged_files(self, n_levels):
+        # (the files the decoder stages on the device, in the order the coder launches consume them; how many are read at once)
+        # Lane containers: masks first (their launch runs beside the prologue), then level by level incl. the offsets — version 3:
+        # anchor.b in front of them, because the anchors gate the level plan.  Version 1: its offsets are one launch at the end.
+        # Only the leading files start at once: the checkpoint is read first, on a quiet interpreter — beside eight reader threads
+        # that read took 4-8 ms instead of 0.3; the other files are released right after it, still early for the first level.
+        levels = list(reversed(range(n_levels)))
+        if not self.lanes:
+            return [f"{a}{l}.b" for l in levels for a in ("feat", "scaling")] + [f"offsets{l}.b" for l in levels], 0
+        lead = ["anchor.b"] if self.anchors_coded else []
+        return lead + ["masks.b", "hyper.b"] + [f"{a}{l}.b" for l in levels for a in ("feat", "scaling", "offsets")], len(lead) + 1
+
+    def stream_records(self, lens, mn, mx):
+        # A file's per-stream (bits, min, max) as the header stores them.
+        if self.lanes:   # arrays: thousands of blocks as Python ints cost the decoder's unpickling a garbage-collector pass
+            return lens * 8, mn.astype(np.int32), mx.astype(np.int32)
+        return (lens * 8).tolist(), mn.astype(np.int64).tolist(), mx.astype(np.int64).tolist()
+
+    def header_item(self, bit_masks, anchor_bytes):
+        # The 15th item of meta.b (None: version 1 keeps the reference's 14).
+        if not self.device_coders:
+            return None
+        item = {"version": 2, "block_symbols": self.block, "block_policy": self.policy, "hyper_block": self.hyper_block,
+                "chunk": {"masks": self.mask_chunk}, "bit_masks": bit_masks}
+        if self.anchors_coded:
+            item.update(version=3, anchor={"scheme": "morton-gap", "block": codec._ANCHOR_BLOCK, "bytes": anchor_bytes})
+        return item
 
 
 def _predict(pc, level, feat_in):
@@ -334,8 +440,8 @@ _SIDE = {}
 
 
 def _side_stream(dev, tag=""):
-    """One side stream per device (and purpose) for the life of the process (a fresh stream per container costs the caching
-    allocator a fresh pool, see codec.StagedFiles)."""
+    # one side stream per device (and purpose) for the life of the process (a fresh stream per container costs the caching
+    # allocator a fresh pool, see codec.StagedFiles)
     key = str(dev) + tag
     if key not in _SIDE:
         _SIDE[key] = torch.cuda.Stream(device=dev)
@@ -357,190 +463,292 @@ def _tracer(name):
     return mark
 
 
+# ---- what both directions share ---------------------------------------------------------------------------------------------
+class _Coding:
+    """What one conduct_encoding / conduct_decoding call hands from stage to stage."""
+    # the valid anchors' tensors as far as they are known (the encoder has anchors, hyper and masks from the start, the decoder
+    # fills them in): anchors [N_valid, 3] dequantised; hyper [N_valid, H] as the context MLP is fed it (the encoder's symbols,
+    # the decoder's rows); masks [N_valid, K, 1]; context: the rows gathered for the level about to be coded (None: the first)
+    anchors = hyper = masks = feat_after_Q = scaling_after_Q = offsets_after_Q = already_coded = None
+    context = inverse_indices = mapping = None
+    # the decoder's: the unpacked header, the codec.StagedFiles, anchor.npy on its way into pinned memory; version 1: the serial
+    # mask stream's host job, the main stream's event in front of the last level's launch; lane containers: the side stream's
+    # event behind the mask launch
+    meta = staged = anchor_job = mask_job = fork = masks_ready = None
+
+    def __init__(self, layout, directory, pc, **decoder):
+        self.layout, self.K, self.D = layout, pc.n_offsets, pc.feat_dim
+        self.path = lambda name: os.path.join(directory, name)
+        self.pending_offsets, self.live_ahead = [], {}
+        self.__dict__.update(decoder)
+
+
+def _skip(*args):
+    pass              # a stage this container version does not have
+
+
+def _plan_levels(pc, st, tr):
+    if pc.level_scale is None:
+        pc.level_scale = find_divide_scale(pc, st.anchors, pc.target_ratio, pc.level_num)
+    plan, st.inverse_indices, st.mapping = level_plan(pc, st.anchors, None)
+    tr("level plan built")
+    return plan
+
+
+def _predict_level(pc, st, level, orig, tr, mark_rows=False):
+    # a level's input rows — the anchors themselves for the first level, then the context gathered from the levels already
+    # coded; the hyper latents beside either — through the context MLP
+    feat_in = torch.cat([st.anchors[orig] if st.context is None else st.context, st.hyper[orig].float()], dim=1)
+    if mark_rows:
+        tr(f"level {level}: input rows assembled")
+    pred = _predict(pc, level, feat_in)
+    tr(f"level {level}: predicted (enqueued)")
+    return pred
+
+
+def _gather_next_context(pc, st, level, tr):
+    st.context = context_rows(pc, st.anchors, st.feat_after_Q, st.scaling_after_Q, st.already_coded, st.inverse_indices,
+                              st.mapping, level)
+    tr(f"level {level}: context of the next level gathered")
+
+
+def _live_mask(st, orig, n):
+    # [n, 3K] bool: the offset slots that are transmitted (:1222-1223).
+    return st.masks[orig].repeat(1, 1, 3).reshape(n, 3 * st.K).to(torch.bool)
+
+
+def _live_index(m30):
+    # ONE compaction index of the live slots for every operand of the offsets group (and the decoder's fill).
+    return torch.nonzero(m30.reshape(-1))[:, 0]
+
+
+def _live_running_count(m30):
+    cnt = torch.zeros(m30.shape[0] + 1, dtype=torch.int64, device=m30.device)
+    cnt[1:] = torch.cumsum(m30.sum(1), 0)
+    return cnt
+
+
+def _place_offsets(st, fills, values):
+    for (orig, n, live), off_vals in zip(fills, values):
+        off_dec = torch.zeros(n * 3 * st.K, device=off_vals.device)
+        off_dec.index_copy_(0, live, off_vals)
+        st.offsets_after_Q[orig] = off_dec.view(n, st.K, 3)
+
+
+# ---- encoder stages -----------------------------------------------------------------------------------------------------------
+def _anchors_in_model_order(pc, tr):
+    return pc.get_mask_anchor, None
+
+
+def _anchors_in_morton_order(pc, tr):
+    # version 3: the valid anchors in the stable ascending order of their Morton keys (an index selection; the model itself
+    # is neither permuted nor modified).  Everything after it is defined on whatever order this selection produces.
+    mask_anchor = pc.get_mask_anchor
+    q = Quantize_anchor.apply(pc._anchor[mask_anchor], pc.x_bound_min, pc.x_bound_max)[1]
+    anchor_order, anchor_stream = codec.anchor_encode(q.to(torch.int32))
+    tr("anchors ordered and coded (device)")
+    return torch.nonzero(mask_anchor.reshape(-1))[:, 0][anchor_order], anchor_stream
+
+
+def _mask_symbols(st):
+    return torch.floor(((st.masks * 2 - 1).view(-1) + 1) / 2)
+
+
+def _mask_stream_on_host(sym, prob):
+    return codec.bernoulli_encode_host(sym, prob), None
+
+
+def _encode_masks_host(st, prob_masks, tr):
+    # Version 1: ONE serial stream on a host thread -> a job whose result is (bytes, None).
+    mask_sym = codec.to_host_pinned(_mask_symbols(st).to(torch.int16), "mask symbols")
+    tr("mask symbols on the host")
+    return codec.host_pool().submit(_mask_stream_on_host, mask_sym, prob_masks)
+
+
+def _encode_masks_device(st, prob_masks, tr):
+    # lane containers: the same symbols as chunk streams, one device launch on a side stream beside everything that follows
+    # -> a job whose result is (uint8 array, per-stream byte lengths)
+    job = codec.BernoulliEncodeJob(_mask_symbols(st), prob_masks, st.layout.mask_edges(int(st.masks.shape[0]), st.K),
+                                   _side_stream(st.masks.device))
+    tr("mask chunk streams enqueued (device)")
+    return job
+
+
+def _write_anchor_npy(st, quantized_anchor, anchor_stream):
+    # -> (write jobs, bits)
+    anchor_u16 = quantized_anchor.cpu().numpy().astype(np.uint16)                           # :1100-1101
+    return [codec.host_pool().submit(np.save, st.path("anchor.npy"), anchor_u16)], anchor_u16.size * 16
+
+
+def _write_anchor_b(st, quantized_anchor, anchor_stream):
+    return codec.write_file(st.path("anchor.b"), anchor_stream), len(anchor_stream) * 8
+
+
+def _encode_hyper_rans(pc, st, hyper_latent, tr):
+    jobs = pc.latent_codec.compress_chunks(hyper_latent.t(), st.layout.max_batch * 10, lazy=True)
+    tr("hyper symbols on the host, rANS jobs submitted")
+    return jobs
+
+
+def _finish_hyper_rans(st, jobs, writes, tr):
+    # Version 1: 10 000-anchor rANS strings (:1082-1098) from host threads -> the header's bit list.
+    hyper_bytes = [j.result() for j in jobs]
+    tr("hyper rANS jobs done")
+    with open(st.path("hyper.b"), "wb") as f:
+        f.write(b"".join(hyper_bytes))
+    return [len(b) * 8 for b in hyper_bytes]
+
+
+def _encode_hyper_lanes(pc, st, hyper_latent, tr):
+    coded = pc.latent_codec.compress_lanes(hyper_latent.t().contiguous(), st.layout.hyper_block)
+    tr("hyper blocks coded (device) and on the host")
+    return coded
+
+
+def _finish_hyper_lanes(st, coded, writes, tr):
+    writes += codec.write_file(st.path("hyper.b"), coded[0])
+    return coded[1] * 8
+
+
+_EncodeStages = namedtuple("_EncodeStages", "select_anchors start_masks write_anchors start_hyper finish_hyper")
+_ENCODE = {1: _EncodeStages(_anchors_in_model_order, _encode_masks_host, _write_anchor_npy, _encode_hyper_rans, _finish_hyper_rans),
+           2: _EncodeStages(_anchors_in_model_order, _encode_masks_device, _write_anchor_npy, _encode_hyper_lanes, _finish_hyper_lanes),
+           3: _EncodeStages(_anchors_in_morton_order, _encode_masks_device, _write_anchor_b, _encode_hyper_lanes, _finish_hyper_lanes)}
+# the valid anchors' rows of the model, as the encoder codes them
+_Source = namedtuple("_Source", "quantized_anchor feat offsets scaling hyper_latent")
+
+
+def _gather_valid_anchors(pc, st, mask_anchor, tr):
+    # -> (_Source, level plan); st gets the anchors, the hyper symbols and the zeroed buffers of the level loop.
+    pc.latent_codec.update(force=True)
+    tr("tables updated")
+    st.anchors, quantized_anchor = Quantize_anchor.apply(pc._anchor[mask_anchor], pc.x_bound_min, pc.x_bound_max)
+    src = _Source(quantized_anchor, pc._anchor_feat[mask_anchor], pc._offset[mask_anchor], pc.get_scaling[mask_anchor],
+                  pc._hyper_latent[mask_anchor])
+    tr("valid anchors gathered")
+    # Q3: the encoder feeds integer SYMBOLS to the context MLP (:1040,1164)
+    st.hyper = pc.latent_codec.quantize(src.hyper_latent, "symbols", means=pc.latent_codec._get_medians().permute(1, 2, 0)[0])
+    plan = _plan_levels(pc, st, tr)
+    st.feat_after_Q = torch.zeros_like(src.feat)
+    st.scaling_after_Q = torch.zeros_like(src.scaling)
+    st.already_coded = torch.zeros(src.feat.shape[0], dtype=torch.bool, device=src.feat.device)
+    return src, plan
+
+
+def _encode_level(pc, st, src, level, orig, tr):
+    # Predict and quantise one level (:1112-1242) -> its feat / scaling / offsets groups for the coder launch.
+    n_l, K, D, layout = int(orig.shape[0]), st.K, st.D, st.layout
+    (mean_feat, scale_feat, mean_scaling, scale_scaling, mean_offsets, scale_offsets, Qf, Qs, Qo) = \
+        _predict_level(pc, st, level, orig, tr)
+    edges_f, edges_s = layout.group_edges(n_l, D, D), layout.group_edges(n_l, 6, D)
+    tr(f"level {level}: chunk rows")
+    feat_q = STE_multistep.apply(src.feat[orig], Qf.unsqueeze(1))
+    scal_q = STE_multistep.apply(src.scaling[orig], Qs.unsqueeze(1))
+    off_q = STE_multistep.apply(src.offsets[orig].reshape(n_l, 3 * K), Qo.unsqueeze(1))
+    tr(f"level {level}: quantised")
+    m30 = _live_mask(st, orig, n_l)
+    off_edges = layout.offset_edges(n_l, D, _live_running_count(m30))
+    tr(f"level {level}: offset stream edges on the host")
+    live = _live_index(m30)
+    pick = lambda t: t.reshape(-1).index_select(0, live)
+    groups = [(feat_q, mean_feat, scale_feat, Qf, edges_f, D),
+              (scal_q, mean_scaling, scale_scaling, Qs, edges_s, 6),
+              (pick(off_q), pick(mean_offsets), pick(scale_offsets), Qo.index_select(0, live // (3 * K)), off_edges, 1)]
+    tr(f"level {level}: groups built")
+
+    st.feat_after_Q[orig] = feat_q                                                       # :1240-1242
+    st.scaling_after_Q[orig] = scal_q
+    st.already_coded.index_fill_(0, orig, True)    # (x[idx] = True uploads its scalar through a blocking pageable copy)
+    if level != 0:
+        _gather_next_context(pc, st, level, tr)
+    return groups
+
+
+def _write_mlp(pc, st):
+    # mlp.pt on THIS thread while the coder launch runs (its small device-to-host copies on a side stream, not behind the
+    # launch).  A host thread of its own was tried: torch.save holds the GIL for milliseconds at a time and the level loop
+    # stretched from 8 to 10-35 ms waiting for it.
+    with torch.cuda.stream(_side_stream(st.masks.device, "mlp")):
+        save_mlp_checkpoints(pc, st.path("mlp.pt"))
+
+
+def _write_streams(st, tags, coded, ready, writes):
+    # Submit the file writes of the coded groups (:1235-1238) -> the header's {attribute: {level: list}} of bits, min, max.
+    bits, mins, maxs = ({"feat": {}, "scaling": {}, "offsets": {}} for _ in range(3))
+    for (name, level), (blob, lens, mn, mx) in zip(tags, coded):
+        writes += codec.write_file(st.path(f"{name}{level}.b"), blob, ready=ready)
+        bits[name][level], mins[name][level], maxs[name][level] = st.layout.stream_records(lens, mn, mx)
+    return bits, mins, maxs
+
+
+def _finish_masks(st, mask_job, tr):
+    # masks.b, written on this thread -> (its bits, the header's per-stream bits or None).
+    mask_bytes, mask_lens = mask_job.result()
+    tr("mask stream done")
+    with open(st.path("masks.b"), "wb") as f:
+        f.write(mask_bytes)
+    return len(mask_bytes) * 8, None if mask_lens is None else mask_lens * 8
+
+
+def _write_header(pc, st, meta, bit_anchor, bit_masks, seconds):
+    # meta.b (:1276-1277) -> the encoder's summary line.
+    torch.save(_pack_meta(meta), st.path("meta.b"))
+    total = lambda d: sum(int(np.sum(v)) for v in d.values())
+    sizes = {"meta": os.path.getsize(st.path("meta.b")) * 8, "hyper": int(np.sum(meta.bit_hyper)), "anchor": bit_anchor,
+             "feat": total(meta.bit_feat), "scaling": total(meta.bit_scaling), "offsets": total(meta.bit_offsets),
+             "masks": bit_masks, "MLPs": pc.get_mlp_size()[0]}
+    r = lambda v: round(v / bit2MB_scale, 4)
+    return ("\nEncoded sizes in MB: " + ", ".join(f"{k} {r(v)}" for k, v in sizes.items()) +
+            f", Total {r(sum(sizes.values()))}, EncTime {round(seconds, 4)}")
+
+
 @torch.no_grad()
 def conduct_encoding(pc, pre_path_name, container_version=None):   # :1007-1295
-    version = default_container_version() if container_version is None else int(container_version)
-    if version not in (1, 2, 3):
-        raise ValueError(f"container version {version}: 1 (the reference's container), 2 or 3")
-    if version == 3 and mgpu.world() > 1:
-        raise NotImplementedError("container version 3 (anchors coded in Morton order) is written by one rank only")
-    anchors_coded = version == 3
-    if anchors_coded:
-        version = 2                   # everything but the anchor file and the order of the rows is version 2
-    chunk = dict(V2_CHUNK) if version == 2 else {"masks": MAX_BATCH}
-    lanes = version == 2
+    layout = ContainerLayout.for_writing(container_version)
+    stages = _ENCODE[layout.version]
     torch.cuda.synchronize(); t1 = time.time()
     tr = _tracer("encode")
     print("Start encoding ...")
     root = mgpu.rank() == 0          # multi-GPU: every rank predicts/quantises, codes its block of streams; rank 0 writes
     os.makedirs(pre_path_name, exist_ok=True)
-    K, D = pc.n_offsets, pc.feat_dim
-    path = lambda name: os.path.join(pre_path_name, name)
+    st = _Coding(layout, pre_path_name, pc)
 
-    # the mask stream (:1265-1269) is ONE serial arithmetic-coded stream and the longest chain of the encoder (10 M symbols on
-    # a host thread): it is started FIRST, before the prior tables and the other per-anchor gathers
-    mask_anchor = pc.get_mask_anchor
-    if anchors_coded:
-        # version 3: the valid anchors in the stable ascending order of their Morton keys (an index selection; the model itself
-        # is neither permuted nor modified).  Everything below is defined on whatever order this selection produces.
-        _q = Quantize_anchor.apply(pc._anchor[mask_anchor], pc.x_bound_min, pc.x_bound_max)[1]
-        anchor_order, anchor_stream = codec.anchor_encode(_q.to(torch.int32))
-        mask_anchor = torch.nonzero(mask_anchor.reshape(-1))[:, 0][anchor_order]
-        tr("anchors ordered and coded (device)")
-    _mask = pc.get_mask[mask_anchor]
-    prob_masks = (_mask.sum() / _mask.numel()).item() if _mask.numel() else 0.5
-    if root and version == 2:
-        # version 2: the same symbols as 1000-anchor chunk streams, one device launch on a side stream beside everything below
-        mask_edges = torch.tensor(_chunk_rows(int(_mask.shape[0]), chunk["masks"]), dtype=torch.int64) * K
-        mask_job = codec.BernoulliEncodeJob(torch.floor(((_mask * 2 - 1).view(-1) + 1) / 2), prob_masks, mask_edges,
-                                            _side_stream(_mask.device))
-        tr("mask chunk streams enqueued (device)")
-    elif root:
-        mask_sym = codec.to_host_pinned(torch.floor(((_mask * 2 - 1).view(-1) + 1) / 2).to(torch.int16), "mask symbols")
-        tr("mask symbols on the host")
-        mask_job = codec.host_pool().submit(codec.bernoulli_encode_host, mask_sym, prob_masks)
-        # hyper: 10 000-anchor rANS chunks (:1082-1098), on host threads too — but submitted only AFTER the level loop
-        # has been enqueued: ~100 short jobs finishing on the pool make the main thread queue for the GIL, which
-        # stretched the 7 ms of launch code below to 38 ms when they ran beside it
-        hyper_jobs = None
-    pc.latent_codec.update(force=True)
-    tr("tables updated")
-    _anchor, quantized_anchor = Quantize_anchor.apply(pc._anchor[mask_anchor], pc.x_bound_min, pc.x_bound_max)
-    _feat = pc._anchor_feat[mask_anchor]
-    _grid_offsets = pc._offset[mask_anchor]
-    _scaling = pc.get_scaling[mask_anchor]
-    _hyper_latent = pc._hyper_latent[mask_anchor]
-    tr("valid anchors gathered")
+    # the mask stream (:1265-1269) is the longest chain of the version-1 encoder (ONE serial arithmetic-coded stream, 10 M
+    # symbols on a host thread): it is started FIRST, before the prior tables and the other per-anchor gathers
+    mask_anchor, anchor_stream = stages.select_anchors(pc, tr)
+    st.masks = pc.get_mask[mask_anchor]
+    prob_masks = (st.masks.sum() / st.masks.numel()).item() if st.masks.numel() else 0.5
+    mask_job = stages.start_masks(st, prob_masks, tr) if root else None
+    src, plan = _gather_valid_anchors(pc, st, mask_anchor, tr)
+    # file writes run on host threads while the device predicts / codes
+    writes, bit_anchor = stages.write_anchors(st, src.quantized_anchor, anchor_stream) if root else ([], 0)
 
-    # Q3: the encoder feeds integer SYMBOLS to the context MLP (:1040,1164)
-    hyper_feat = pc.latent_codec.quantize(_hyper_latent, "symbols", means=pc.latent_codec._get_medians().permute(1, 2, 0)[0])
-    if pc.level_scale is None:
-        pc.level_scale = find_divide_scale(pc, _anchor, pc.target_ratio, pc.level_num)
-    plan, inverse_indices_list, mapping_list = level_plan(pc, _anchor, None)
-
-    tr("level plan built")
-    feat_after_Q = torch.zeros_like(_feat)
-    grid_scaling_after_Q = torch.zeros_like(_scaling)
-    already_coded = torch.zeros(_feat.shape[0], dtype=torch.bool, device=_feat.device)
-    writes = []                       # file writes run on host threads while the device predicts / codes
-    if root and anchors_coded:
-        writes += codec.write_file(path("anchor.b"), anchor_stream)
-    elif root:
-        anchor_u16 = quantized_anchor.cpu().numpy().astype(np.uint16)                       # :1100-1101
-        writes.append(codec.host_pool().submit(np.save, path("anchor.npy"), anchor_u16))
-
-    N_levels_list, groups, tags = [], [], []
-    content_pre_gathered = None
-    for (level, to_code, orig, hybrid_anchor) in plan:                                   # :1112
-        n_l = int(orig.shape[0])
-        N_levels_list.append(n_l)
-        if content_pre_gathered is None:
-            feat_in = torch.cat([_anchor[orig], hyper_feat[orig].float()], dim=1)
-        else:
-            feat_in = torch.cat([content_pre_gathered, hyper_feat[orig].float()], dim=1)
-        (mean_feat, scale_feat, mean_scaling, scale_scaling, mean_offsets, scale_offsets, Qf, Qs, Qo) = \
-            _predict(pc, level, feat_in)
-        tr(f"level {level}: predicted (enqueued)")
-        rows = torch.tensor(_chunk_rows(n_l), dtype=torch.int64)
-
-        tr(f"level {level}: chunk rows")
-        feat_q = STE_multistep.apply(_feat[orig], Qf.unsqueeze(1))
-        scal_q = STE_multistep.apply(_scaling[orig], Qs.unsqueeze(1))
-        off_q = STE_multistep.apply(_grid_offsets[orig].reshape(n_l, 3 * K), Qo.unsqueeze(1))
-        tr(f"level {level}: quantised")
-        m30 = _mask[orig].repeat(1, 1, 3).reshape(n_l, 3 * K).to(torch.bool)              # :1222-1223
-        cnt = torch.zeros(n_l + 1, dtype=torch.int64, device=m30.device)
-        cnt[1:] = torch.cumsum(m30.sum(1), 0)
-        if lanes:      # version 2: blocks of V2_BLOCK symbols, whatever anchors they belong to
-            n_off = int(cnt[-1].item())
-            B_l = _level_blocks(n_l, n_l * D, D, V2_BLOCK_POLICY)          # one block size for the level's three groups
-            edges_f, edges_s = _block_edges(n_l * D, B_l), _block_edges(n_l * 6, B_l)
-            off_edges = _block_edges(n_off, B_l)
-        else:
-            edges_f, edges_s = rows * D, rows * 6
-            off_edges = cnt[rows.to(cnt.device)].cpu()
-        tr(f"level {level}: offset stream edges on the host")
-        live = torch.nonzero(m30.reshape(-1))[:, 0]              # ONE compaction index for the four operands
-        pick = lambda t: t.reshape(-1).index_select(0, live)
-
-        groups += [(feat_q, mean_feat, scale_feat, Qf, edges_f, D),
-                   (scal_q, mean_scaling, scale_scaling, Qs, edges_s, 6),
-                   (pick(off_q), pick(mean_offsets), pick(scale_offsets), Qo.index_select(0, live // (3 * K)),
-                    off_edges, 1)]
+    n_levels, groups, tags = [], [], []
+    for (level, _to_code, orig, _hybrid_anchor) in plan:                                 # :1112
+        n_levels.append(int(orig.shape[0]))
+        groups += _encode_level(pc, st, src, level, orig, tr)
         tags += [("feat", level), ("scaling", level), ("offsets", level)]
-        tr(f"level {level}: groups built")
-
-        feat_after_Q[orig] = feat_q                                                      # :1240-1242
-        grid_scaling_after_Q[orig] = scal_q
-        already_coded.index_fill_(0, orig, True)   # (x[idx] = True uploads its scalar through a blocking pageable copy)
-        if level != 0:
-            content_pre_gathered = context_rows(pc, _anchor, feat_after_Q, grid_scaling_after_Q, already_coded,
-                                                inverse_indices_list, mapping_list, level)
-            tr(f"level {level}: context of the next level gathered")
-
     tr("levels enqueued")
-    hyper_v2 = None
-    if root and version == 2:
-        hyper_v2 = pc.latent_codec.compress_lanes(_hyper_latent.t().contiguous(), V2_HYPER_BLOCK)
-        tr("hyper blocks coded (device) and on the host")
-    elif root:
-        hyper_jobs = pc.latent_codec.compress_chunks(_hyper_latent.t(), MAX_BATCH * 10, lazy=True)
-        tr("hyper symbols on the host, rANS jobs submitted")
+    # the hyper latents only AFTER the level loop has been enqueued: ~100 short rANS jobs finishing on the pool make the main
+    # thread queue for the GIL, which stretched the 7 ms of launch code above to 38 ms when they ran beside it
+    hyper_job = stages.start_hyper(pc, st, src.hyper_latent, tr) if root else None
     torch.cuda.synchronize(); t0 = time.time()
     tr("levels done on the device")
-    def write_mlp():
-        # mlp.pt on THIS thread while the coder launch runs (its small device-to-host copies on a side stream, not behind
-        # the launch).  A host thread of its own was tried: torch.save holds the GIL for milliseconds at a time and the level
-        # loop above stretched from 8 to 10-35 ms waiting for it.
-        if root:
-            with torch.cuda.stream(_side_stream(_mask.device, "mlp")):
-                save_mlp_checkpoints(pc, path("mlp.pt"))
-    coded = codec.gaussian_encode_groups(groups, staging=True, lanes=lanes, overlap=write_mlp, deferred=True)   # blobs alias the pinned buffer
-    ready = codec.stage_ready()          # the download is still in flight: the file writers below wait piece by piece
+    # ALL streams in one launch; the blobs alias the pinned buffer and their download is still in flight when this returns:
+    # the file writers wait for it piece by piece (`ready`)
+    coded, ready = codec.gaussian_encode_groups(groups, staging=True, lanes=layout.lanes, deferred=True,
+                                                overlap=partial(_write_mlp, pc, st) if root else None)
     tr("coder launch done, download queued")
     if not root:
         torch.cuda.synchronize()
         return mgpu.broadcast_object(None)            # the summary string of rank 0
 
-    bit_d = {"feat": {}, "scaling": {}, "offsets": {}}
-    min_d = {"feat": {}, "scaling": {}, "offsets": {}}
-    max_d = {"feat": {}, "scaling": {}, "offsets": {}}
-    for (name, level), (blob, lens, mn, mx) in zip(tags, coded):
-        writes += codec.write_file(path(f"{name}{level}.b"), blob, ready=ready)           # :1235-1238
-        if version == 2:      # arrays: thousands of blocks as Python ints cost the decoder's unpickling a garbage-collector pass
-            bit_d[name][level], min_d[name][level], max_d[name][level] = lens * 8, mn.astype(np.int32), mx.astype(np.int32)
-        else:
-            bit_d[name][level] = (lens * 8).tolist()
-            min_d[name][level] = mn.astype(np.int64).tolist()
-            max_d[name][level] = mx.astype(np.int64).tolist()
-
+    bits, mins, maxs = _write_streams(st, tags, coded, ready, writes)
     tr("file writes submitted")
     torch.cuda.synchronize(); t_codec = time.time() - t0
     tr("bitstream on the host")
-    if hyper_v2 is not None:
-        bit_hyper_list = hyper_v2[1] * 8
-        writes += codec.write_file(path("hyper.b"), hyper_v2[0])
-    else:
-        hyper_bytes = [j.result() for j in hyper_jobs]                                   # :1082-1098
-        tr("hyper rANS jobs done")
-        bit_hyper_list = [len(b) * 8 for b in hyper_bytes]
-        with open(path("hyper.b"), "wb") as f:
-            f.write(b"".join(hyper_bytes))
-    bit_anchor = len(anchor_stream) * 8 if anchors_coded else _anchor.numel() * 16
-    bit_hyper = int(np.sum(bit_hyper_list))
-    bit_feat = sum(int(np.sum(v)) for v in bit_d["feat"].values())
-    bit_scaling = sum(int(np.sum(v)) for v in bit_d["scaling"].values())
-    bit_offsets = sum(int(np.sum(v)) for v in bit_d["offsets"].values())
-
-    if version == 2:
-        mask_blob, mask_lens = mask_job.result()
-        mask_bytes = mask_blob.tobytes()
-    else:
-        mask_bytes = mask_job.result()
-    tr("mask stream done")
-    with open(path("masks.b"), "wb") as f:
-        f.write(mask_bytes)
-    bit_masks = len(mask_bytes) * 8
+    bit_hyper = stages.finish_hyper(st, hyper_job, writes, tr)
+    bit_masks, bit_mask_streams = _finish_masks(st, mask_job, tr)
     for w in writes:
         w.result()                    # every file is on disk before the encoder reports (and raises here if one failed)
     tr("files written")
@@ -548,25 +756,219 @@ def conduct_encoding(pc, pre_path_name, container_version=None):   # :1007-1295
     torch.cuda.synchronize(); t2 = time.time()
     print("encoding time:", t2 - t1)
     print("codec time:", t_codec)
+    meta = ContainerMeta(pc._anchor.shape[0], layout.max_batch, mins["feat"], maxs["feat"], mins["scaling"], maxs["scaling"],
+                         mins["offsets"], maxs["offsets"], prob_masks, bit_hyper, bits["feat"], bits["scaling"], bits["offsets"],
+                         n_levels, layout.header_item(bit_mask_streams, bit_anchor // 8))
+    return mgpu.broadcast_object(_write_header(pc, st, meta, bit_anchor, bit_masks, t2 - t1))
 
-    meta_path = path("meta.b")                                                            # :1276-1277
-    meta = [pc._anchor.shape[0], MAX_BATCH, min_d["feat"], max_d["feat"], min_d["scaling"], max_d["scaling"],
-            min_d["offsets"], max_d["offsets"], prob_masks, bit_hyper_list, bit_d["feat"], bit_d["scaling"],
-            bit_d["offsets"], N_levels_list]
-    if version == 2:
-        meta.append({"version": 2, "block_symbols": V2_BLOCK, "block_policy": V2_BLOCK_POLICY, "hyper_block": V2_HYPER_BLOCK, "chunk": chunk,
-                     "bit_masks": mask_lens * 8})
-        if anchors_coded:
-            meta[-1].update(version=3, anchor={"scheme": "morton-gap", "block": codec._ANCHOR_BLOCK, "bytes": len(anchor_stream)})
-    torch.save(meta, meta_path)
-    bit_meta = os.path.getsize(meta_path) * 8
-    mlp = pc.get_mlp_size()[0]
-    r = lambda v: round(v / bit2MB_scale, 4)
-    return mgpu.broadcast_object(
-            f"\nEncoded sizes in MB: meta {r(bit_meta)}, hyper {r(bit_hyper)}, anchor {r(bit_anchor)}, "
-            f"feat {r(bit_feat)}, scaling {r(bit_scaling)}, offsets {r(bit_offsets)}, masks {r(bit_masks)}, "
-            f"MLPs {r(mlp)}, Total {r(bit_meta + bit_hyper + bit_anchor + bit_feat + bit_scaling + bit_offsets + bit_masks + mlp)}, "
-            f"EncTime {round(t2 - t1, 4)}")
+
+# ---- decoder stages -----------------------------------------------------------------------------------------------------------
+def _read_anchor_npy(path):
+    # anchor.npy -> a pinned int32 tensor, or None: version 3 has anchor.b, staged and decoded on the device.
+    if not os.path.exists(path):
+        return None
+    a = np.load(path)
+    pinned = codec._pinned_staging(a.size * 4, "anchors")[:a.size * 4].view(torch.int32).view(a.shape)
+    np.copyto(pinned.numpy(), a, casting="unsafe")
+    return pinned
+
+
+def _stage_files(st, dev, tr):
+    # all coded streams: file -> pinned buffer -> device by the staging threads on a side stream; started before anything
+    # else is loaded (reading ~120 MB is the longest chain of the prologue)
+    names, start = st.layout.staged_files(len(st.meta.n_levels))
+    st.staged = codec.StagedFiles([st.path(f_) for f_ in names if os.path.exists(st.path(f_))], dev, start=start)
+    codec.decode_status(dev, reset=True)     # the lane decoders report a malformed block here (read once, after the last launch)
+    tr("file staging prepared")
+    # (whatever tensors a header holds — the reference stores its minima / maxima as device tensors — are only ever read as
+    #  Python numbers here: restoring them on the device would cost a copy each and a stream drain per .item())
+    tr("meta.b loaded")
+
+
+def _decode_group(st, name, level, mean, scale, Q, edges, q_div):
+    # a group of the decoder launch: the prediction, the cut, and what the header and the staged file hold for it
+    header = st.meta._asdict()
+    blob = st.staged.get(st.path(f"{name}{level}.b"))                                    # device bytes
+    lens = np.asarray(header["bit_" + name][level], dtype=np.int64) // 8
+    assert int(lens.sum()) == int(blob.numel())                                          # :1479-1481
+    return (mean, scale, Q, edges, header["min_" + name][level], header["max_" + name][level], blob, lens, q_div)
+
+
+def _masks_from_host_job(st, dev):
+    return torch.from_numpy(st.mask_job.result()).to(dev).to(torch.float32).view(-1, st.K, 1)
+
+
+def _submit_mask_job(st, N_valid, dev, tr):
+    # version 1: the mask stream (:1348-1353) is serial and only the offsets need it: a host thread decodes it meanwhile
+    st.mask_job = codec.host_pool().submit(codec.bernoulli_decode_host, np.fromfile(st.path("masks.b"), dtype=np.uint8),
+                                           N_valid * st.K, float(st.meta.prob_masks))
+    tr("mask job submitted")
+
+
+def _launch_masks(st, N_valid, dev, tr):
+    # lane containers: chunk streams, one device launch on the side stream.  It needs the header and masks.b only — staged by
+    # the time the checkpoint is unpickled — so its ~3 ms run beside the rest of the prologue, not in front of the first level.
+    side_stream = _side_stream(dev)
+    with torch.cuda.stream(side_stream):
+        mask_lens = np.asarray(st.meta.extra["bit_masks"], dtype=np.int64) // 8
+        blob = st.staged.get(st.path("masks.b"))
+        assert int(mask_lens.sum()) == int(blob.numel())
+        st.masks = codec.bernoulli_decode_packed(float(st.meta.prob_masks), st.layout.mask_edges(N_valid, st.K), blob,
+                                                 mask_lens).view(-1, st.K, 1)
+        st.masks_ready = side_stream.record_event()
+    tr("mask chunk streams: device launch enqueued")
+
+
+def _join_mask_launch(st, dev):
+    torch.cuda.current_stream().wait_event(st.masks_ready)
+    st.masks.record_stream(torch.cuda.current_stream())
+
+
+def _masks_of_a_model_without_levels(st, dev):
+    # no level at all (empty model): nothing has asked for the mask job's result
+    st.masks = st.masks if st.masks is not None else _masks_from_host_job(st, dev)
+
+
+def _anchors_from_npy(st, N_valid, dev, tr):
+    return st.anchor_job.result().to(dev, non_blocking=True)     # :1340-1342 (pinned: the copy is queued, not waited for)
+
+
+def _anchors_from_anchor_b(st, N_valid, dev, tr):
+    q = codec.anchor_decode(st.staged.get(st.path("anchor.b")))  # int32 [N_valid, 3], rows in Morton order
+    if int(q.shape[0]) != N_valid:
+        raise RuntimeError(f"anchor.b holds {int(q.shape[0])} anchors, meta.b's levels {N_valid}")
+    tr("anchor.b decoded (device)")
+    return q
+
+
+def _decode_hyper_rans(pc, st, N_valid, tr):
+    # version 1: the hyper strings are decoded by host threads (straight into a pinned [N_valid, H] buffer); the first level's
+    # prediction waits for them
+    with open(st.path("hyper.b"), "rb") as f:
+        hyper_stream = f.read()
+    ends = np.cumsum(np.asarray(st.meta.bit_hyper, dtype=np.int64) // 8).tolist()
+    per = st.layout.max_batch * 10                                                       # :1326-1336 (any N_valid, Q2)
+    sizes = [min(per, N_valid - s0) for s0 in range(0, N_valid, per)]
+    strings = [hyper_stream[e0:e1] for e0, e1 in zip([0] + ends, ends[:len(sizes)])]
+    job = pc.latent_codec.decompress_chunks_rows(strings, sizes)
+    tr("hyper rANS jobs submitted")
+    return job()
+
+
+def _decode_hyper_lanes(pc, st, N_valid, tr):
+    # lane-parallel table blocks, one device launch (EntropyBottleneck.decompress_lanes_rows)
+    rows = pc.latent_codec.decompress_lanes_rows(st.staged.get(st.path("hyper.b")), np.asarray(st.meta.bit_hyper, dtype=np.int64) // 8,
+                                                 N_valid, st.layout.hyper_block)
+    tr("hyper blocks: device launch enqueued")
+    return rows
+
+
+def _live_slots(st, level, orig, n, by_row=True):
+    # -> (host stream edges, live index) of a level's offsets from the decoded masks; by_row: the edges want every row's count.
+    m30 = _live_mask(st, orig, n)
+    live = _live_index(m30)
+    return st.layout.offset_edges(n, st.D, _live_running_count(m30) if by_row else int(live.numel())), live
+
+
+def _read_offset_edges_ahead(st, plan, tr):
+    # lane containers: the offsets' stream edges of EVERY level in one host read, before the first coder launch is queued (a
+    # read inside the level loop would drain the previous level's launch and leave the device idle while the next one is built)
+    _join_mask_launch(st, None)
+    for (level, _to_code, orig, _hybrid_anchor) in plan:
+        st.live_ahead[level] = _live_slots(st, level, orig, int(orig.shape[0]), by_row=False)
+    tr("offset blocks of all levels on the host")
+
+
+def _offset_groups(st, pending, live_slots):
+    # -> (the coder groups of the pending levels' offsets, where their values go).
+    groups, fills = [], []
+    for (level, orig, n, mean_o, scale_o, Qo) in pending:
+        off_edges, live = live_slots(st, level, orig, n)
+        groups.append(_decode_group(st, "offsets", level, mean_o.reshape(-1).index_select(0, live),
+                                    scale_o.reshape(-1).index_select(0, live), Qo.index_select(0, live // (3 * st.K)), off_edges, 1))
+        fills.append((orig, n, live))
+    return groups, fills
+
+
+def _offsets_ride_with_their_level(st, last):
+    # lane containers: the masks are on the device long before the first level is predicted, so a level's offsets ride in
+    # that level's launch (their streams are not longer than the feature streams beside them)
+    return _offset_groups(st, st.pending_offsets[-1:], lambda st, level, orig, n: st.live_ahead[level])
+
+
+def _fork_before_the_last_level(st, last):
+    if last:
+        st.fork = torch.cuda.current_stream().record_event()        # everything the offsets need exists before this point
+    return [], []
+
+
+def _launch_offsets_beside_the_last_level(st, last, dev, tr):
+    # version 1: the offsets of ALL levels as their own launch on a side stream, forked BEFORE the last feature launch: they
+    # need the mask stream (a serial host job of ~70 ms that ends about now), the features do not, and a coder launch keeps few
+    # SIMDs busy (one wave per stream), so the two launches run side by side instead of the last one waiting for the masks
+    if not last:
+        return
+    main, side_stream = torch.cuda.current_stream(), _side_stream(dev)
+    with torch.cuda.stream(side_stream):
+        side_stream.wait_event(st.fork)
+        tr("waiting for the mask stream")
+        st.masks = _masks_from_host_job(st, dev)
+        tr("mask stream decoded")
+        og, fills = _offset_groups(st, st.pending_offsets, _live_slots)
+        _place_offsets(st, fills, codec.gaussian_decode_groups(og, lanes=st.layout.lanes))
+        tr("offsets launch enqueued")
+    main.wait_stream(side_stream)
+
+
+# submit_masks: before the checkpoint is read, launch_masks: after it; level_offsets: in front of a level's launch -> (groups to
+# add to it, where their values go), offsets_launch: behind it
+_DecodeStages = namedtuple("_DecodeStages", "submit_masks launch_masks anchors hyper offset_edges_ahead level_offsets offsets_launch "
+                           "masks_joined status_check")
+_DECODE_V1 = _DecodeStages(_submit_mask_job, _skip, _anchors_from_npy, _decode_hyper_rans, _skip, _fork_before_the_last_level,
+                           _launch_offsets_beside_the_last_level, _masks_of_a_model_without_levels, _skip)
+_DECODE_V2 = _DecodeStages(_skip, _launch_masks, _anchors_from_npy, _decode_hyper_lanes, _read_offset_edges_ahead,
+                           _offsets_ride_with_their_level, _skip, _join_mask_launch, codec.decode_status_check)
+_DECODE = {1: _DECODE_V1, 2: _DECODE_V2, 3: _DECODE_V2._replace(anchors=_anchors_from_anchor_b)}
+
+
+def _decode_level(pc, st, stages, level, orig, last, dev, tr):
+    # One level: predict, ONE coder launch for its features and scaling (and whatever offsets the container version lets ride
+    # along), place the decoded rows, gather the next level's context.  Coder launches last as long as their LONGEST stream (a
+    # 1000-anchor feature chunk: 50 000 serial symbols at ~0.4 us each) however many streams they hold, so the fewer the better:
+    # version 1 codes the offsets of all levels in ONE more launch beside the last level's — 3 serial launches for 3 levels.
+    n_l, D, layout = int(orig.shape[0]), st.D, st.layout
+    (mean_feat, scale_feat, mean_scaling, scale_scaling, mean_offsets, scale_offsets, Qf, Qs, Qo) = \
+        _predict_level(pc, st, level, orig, tr, mark_rows=True)
+    st.pending_offsets.append((level, orig, n_l, mean_offsets, scale_offsets, Qo))
+    groups = [_decode_group(st, "feat", level, mean_feat, scale_feat, Qf, layout.group_edges(n_l, D, D), D),
+              _decode_group(st, "scaling", level, mean_scaling, scale_scaling, Qs, layout.group_edges(n_l, 6, D), 6)]
+    offset_groups, fills = stages.level_offsets(st, last)
+    decoded = codec.gaussian_decode_groups(groups + offset_groups, lanes=layout.lanes)
+    tr(f"level {level}: coder launch enqueued")
+    _place_offsets(st, fills, decoded[2:])
+    stages.offsets_launch(st, last, dev, tr)
+    tr(f"level {level}: offsets placed")
+    st.feat_after_Q[orig] = decoded[0].view(n_l, D)
+    st.scaling_after_Q[orig] = decoded[1].view(n_l, 6)
+    tr(f"level {level}: decoded rows placed")
+    if level != 0:
+        st.already_coded.index_fill_(0, orig, True)    # (x[idx] = True uploads its scalar through a blocking pageable copy)
+        _gather_next_context(pc, st, level, tr)
+
+
+def _install_decoded(pc, st, N_valid, dev):
+    # The decoded rows in front of zeroed rows for the anchors that were not valid (:1503-1533).
+    rows = {"_hyper_latent": st.hyper, "_anchor": st.anchors, "_anchor_feat": st.feat_after_Q, "_offset": st.offsets_after_Q,
+            "_scaling": st.scaling_after_Q, "_mask": st.masks}
+    full = {name: torch.zeros(st.meta.n_anchors, *r.shape[1:], device=dev) for name, r in rows.items()}
+    for name in ("_anchor", "_hyper_latent", "_anchor_feat", "_offset", "_scaling", "_mask"):
+        full[name][:N_valid] = rows[name]
+    for name, t in full.items():
+        setattr(pc, name, nn.Parameter(t))
+    pc.decoded_version = True
+    if hasattr(pc, "_level_cache"):
+        pc._level_cache = None
+    pc._anchor_q_cache = None
 
 
 @torch.no_grad()
@@ -574,267 +976,50 @@ def conduct_decoding(pc, pre_path_name):                       # :1299-1539
     torch.cuda.synchronize(); t1 = time.time()
     tr = _tracer("decode")
     print("Start decoding ...")
-    path = lambda name: os.path.join(pre_path_name, name)
     # anchor.npy (12 MB at 1 M anchors) is read and converted on a host thread while this one loads the header, the MLPs and
-    # the prior tables: the level plan — the first thing the device chain waits for — needs nothing else from the files
-    def read_anchors():
-        if not os.path.exists(path("anchor.npy")):
-            return None                                   # container version 3: anchor.b, staged and decoded on the device
-        a = np.load(path("anchor.npy"))
-        pinned = codec._pinned_staging(a.size * 4, "anchors")[:a.size * 4].view(torch.int32).view(a.shape)
-        np.copyto(pinned.numpy(), a, casting="unsafe")
-        return pinned
-    anchor_job = codec.host_pool().submit(read_anchors)
-    meta = read_mlp_checkpoint(path("meta.b"))        # (the same loader: nested lists / dicts of numbers, arrays, tensors)
+    # the prior tables: the level plan — the first thing the device chain waits for — needs nothing else from the files.
+    # (Submitted before the header says which container this is: a version-3 directory has no such file.)
+    anchor_job = codec.host_pool().submit(_read_anchor_npy, os.path.join(pre_path_name, "anchor.npy"))
+    meta = _unpack_meta(read_mlp_checkpoint(os.path.join(pre_path_name, "meta.b")))   # (the same loader: lists / dicts of numbers, arrays)
     tr("meta.b unpickled")
-    (N_full, max_batch, min_feat_d, max_feat_d, min_scaling_d, max_scaling_d, min_offsets_d, max_offsets_d, prob_masks,
-     bit_hyper_list, bit_feat_d, bit_scaling_d, bit_offsets_d, N_levels_list) = meta[:14]
-    extra = meta[14] if len(meta) > 14 else {"version": 1}
-    version = int(extra.get("version", 1))
-    if version not in (1, 2, 3):
-        raise RuntimeError(f"meta.b: container version {version} is newer than this decoder (1, 2, 3)")
-    if version == 3 and mgpu.world() > 1:
-        raise NotImplementedError("container version 3 (anchors coded in Morton order) is decoded by one rank only")
-    anchors_coded = version == 3
-    if anchors_coded:
-        version = 2                   # everything but the anchor file is version 2
-    # all coded streams: file -> pinned buffer -> device by the staging threads on a side stream, in the order the coder
-    # launches consume them; started before anything else is loaded (reading ~120 MB is the longest chain of the prologue)
+    layout = ContainerLayout.from_header(meta)
+    stages = _DECODE[layout.version]
+    st = _Coding(layout, pre_path_name, pc, meta=meta, anchor_job=anchor_job)
     dev = pc.x_bound_min.device
-    n_lv = len(N_levels_list)
-    if version == 2:       # masks first (their launch runs beside the prologue), then level by level incl. the offsets
-        # (version 3: anchor.b in front of them, because the anchors gate the level plan)
-        order = (["anchor.b"] if anchors_coded else []) + ["masks.b", "hyper.b"] + [f"{a}{l}.b" for l in reversed(range(n_lv)) for a in ("feat", "scaling", "offsets")]
-    else:
-        order = [f"{a}{l}.b" for l in reversed(range(n_lv)) for a in ("feat", "scaling")] + \
-                [f"offsets{l}.b" for l in reversed(range(n_lv))]
-    # (only masks.b starts now: the checkpoint is read first, on a quiet interpreter — beside eight reader threads that read
-    #  took 4-8 ms instead of 0.3; the other files are released right after it and are still early for the first level)
-    staged = codec.StagedFiles([path(f_) for f_ in order if os.path.exists(path(f_))], dev,
-                               start=(2 if anchors_coded else 1) if version == 2 else 0)
-    codec.decode_status(dev, reset=True)     # the lane decoders report a malformed block here (read once, after the last launch)
-    tr("file staging prepared")
-    chunk = extra["chunk"] if version == 2 else {"masks": max_batch}
-    lanes = version == 2
-    block = int(extra.get("block_symbols", V2_BLOCK))
-    policy = int(extra.get("block_policy", 0))
-    block_of = lambda n_level, n_group: _level_blocks(n_level, n_group, D, policy, block)
-    # (map_location: whatever tensors a header holds — the reference stores its minima / maxima as device tensors — are only
-    #  ever read as Python numbers here: restoring them on the device would cost a copy each and a stream drain per .item())
-    tr("meta.b loaded")
-    K, D, H = pc.n_offsets, pc.feat_dim, pc.feat_dim // pc.hyper_divisor
-    N_levels_list = list(reversed(N_levels_list))
-    N_valid = sum(N_levels_list)
-    # the mask stream (:1348-1353) is serial and only the offsets need it: decode it on a host thread meanwhile
-    # (version 2: chunk streams, decoded by one device launch as soon as masks.b is staged — see below)
-    mask_job = None
-    if version == 1:
-        mask_job = codec.host_pool().submit(codec.bernoulli_decode_host, np.fromfile(path("masks.b"), dtype=np.uint8),
-                                            N_valid * K, float(prob_masks))
-        tr("mask job submitted")
+    _stage_files(st, dev, tr)
+    n_levels = list(reversed(meta.n_levels))
+    N_valid = sum(n_levels)
+    stages.submit_masks(st, N_valid, dev, tr)
     # mlp.pt gates everything below (bounds -> anchors -> level plan; prior tables -> hyper launch) and unpickling it is the
-    # longest host step of the prologue (on a host thread it only moved the time: unpickling holds the GIL).  The mask launch
-    # needs the header and masks.b only — staged by the time the checkpoint is unpickled — so it is queued right after,
-    # and its ~3 ms run beside the rest of the prologue instead of in front of the first level.
-    ck = read_mlp_checkpoint(path("mlp.pt"))
+    # longest host step of the prologue (on a host thread it only moved the time: unpickling holds the GIL), so it is read on
+    # THIS thread, before the other files' reads are released
+    ck = read_mlp_checkpoint(st.path("mlp.pt"))
     tr("mlp.pt unpickled")
-    staged.release()
-    side_stream = _side_stream(dev)
-    masks_decoded, masks_ready = None, None
-    if version == 2:
-        with torch.cuda.stream(side_stream):
-            mask_edges = torch.tensor(_chunk_rows(N_valid, chunk["masks"]), dtype=torch.int64) * K
-            mask_lens = np.asarray(extra["bit_masks"], dtype=np.int64) // 8
-            blob = staged.get(path("masks.b"))
-            assert int(mask_lens.sum()) == int(blob.numel())
-            masks_decoded = codec.bernoulli_decode_packed(float(prob_masks), mask_edges, blob, mask_lens).view(-1, K, 1)
-            masks_ready = side_stream.record_event()
-        tr("mask chunk streams: device launch enqueued")
-    load_mlp_checkpoints(pc, path("mlp.pt"), ck=ck, tr=tr, stored_tables=version == 2)     # (incl. the hyper prior's CDF tables)
+    st.staged.release()
+    stages.launch_masks(st, N_valid, dev, tr)
+    load_mlp_checkpoints(pc, st.path("mlp.pt"), ck=ck, tr=tr, stored_tables=layout.device_coders)   # (incl. the hyper prior's CDF tables)
     # the level plan (sorts and compactions: milliseconds of device work) needs the anchors and the checkpoint's bounds only:
-    # queued now, it runs while the host goes on with the mask / hyper launches
-    if anchors_coded:
-        q = codec.anchor_decode(staged.get(path("anchor.b")))    # int32 [N_valid, 3], rows in Morton order
-        if int(q.shape[0]) != N_valid:
-            raise RuntimeError(f"anchor.b holds {int(q.shape[0])} anchors, meta.b's levels {N_valid}")
-        tr("anchor.b decoded (device)")
-    else:
-        q = anchor_job.result().to(dev, non_blocking=True)       # :1340-1342 (pinned: the copy is queued, not waited for)
-    interval = (pc.x_bound_max - pc.x_bound_min) * Q_anchor + 1e-6
-    anchor_decoded = q * interval + pc.x_bound_min
+    # queued now, it runs while the host goes on with the hyper launch
+    q = stages.anchors(st, N_valid, dev, tr)
+    st.anchors = q * ((pc.x_bound_max - pc.x_bound_min) * Q_anchor + 1e-6) + pc.x_bound_min
     tr("anchors on the device")
-    if pc.level_scale is None:
-        pc.level_scale = find_divide_scale(pc, anchor_decoded, pc.target_ratio, pc.level_num)
-    plan, inverse_indices_list, mapping_list = level_plan(pc, anchor_decoded, None)
-    tr("level plan built")
-    dev = pc.x_bound_min.device
-    if version == 2:
-        # version 2: lane-parallel table blocks, one device launch (EntropyBottleneck.decompress_lanes_rows)
-        hyper_rows = pc.latent_codec.decompress_lanes_rows(staged.get(path("hyper.b")), np.asarray(bit_hyper_list, dtype=np.int64) // 8,
-                                                           N_valid, int(extra.get("hyper_block", V2_HYPER_BLOCK)))
-        hyper_job = lambda: hyper_rows
-        tr("hyper blocks: device launch enqueued")
-    else:
-        # the hyper strings are decoded by host threads (straight into a pinned [N_valid, H] buffer) while this thread stages the
-        # files, loads the anchors and builds the level plan; submitted FIRST: the first level's prediction waits for them
-        with open(path("hyper.b"), "rb") as f:
-            hyper_stream = f.read()
-        pos, strings, sizes = 0, [], []
-        for s, s0 in enumerate(range(0, N_valid, max_batch * 10)):                           # :1326-1336 (any N_valid, Q2)
-            nb = bit_hyper_list[s] // 8
-            strings.append(hyper_stream[pos:pos + nb])
-            sizes.append(min(max_batch * 10, N_valid - s0))
-            pos += nb
-        hyper_job = pc.latent_codec.decompress_chunks_rows(strings, sizes)
-        tr("hyper rANS jobs submitted")
-
-    hyper_decoded = hyper_job()                                                          # [N_valid, H]
+    plan = _plan_levels(pc, st, tr)
+    st.hyper = stages.hyper(pc, st, N_valid, tr)                                         # [N_valid, H]
     tr("hyper latents decoded (host rANS) and on the device")
 
-    feat_after_Q = torch.zeros(N_valid, D, device=dev)
-    grid_scaling_after_Q = torch.zeros(N_valid, 6, device=dev)
-    grid_offset_after_Q = torch.zeros(N_valid, K, 3, device=dev)
-    already_coded = torch.zeros(N_valid, dtype=torch.bool, device=dev)
-    content_pre_gathered = None
-
-    def chunk_lens(name, level, bit_list):
-        blob = staged.get(path(f"{name}{level}.b"))                                      # device bytes
-        lens = np.asarray(bit_list, dtype=np.int64) // 8
-        assert int(lens.sum()) == int(blob.numel())                                      # :1479-1481
-        return blob, lens
-
-    # Coder launches last as long as their LONGEST stream (a 1000-anchor feature chunk: 50 000 serial symbols at ~0.4 us each) however
-    # many streams they hold, so the fewer the better: one per level for features + scaling — the offsets of a level
-    # need nothing but that level's prediction and the masks, so ALL of them go into ONE more launch, beside the last
-    # level's (see below): 3 serial launches for 3 levels.
-    pending_offsets = []
-
-    def live_slots(orig_, n_, rows_):
-        m30 = masks_decoded[orig_].repeat(1, 1, 3).reshape(n_, 3 * K).to(torch.bool)
-        live = torch.nonzero(m30.reshape(-1))[:, 0]              # ONE compaction index for the three operands and the fill
-        if rows_ is None:                                        # version 2: blocks of `block` live symbols
-            return _block_edges(int(live.numel()), block_of(n_, int(live.numel()))), live
-        cnt = torch.zeros(n_ + 1, dtype=torch.int64, device=dev)
-        cnt[1:] = torch.cumsum(m30.sum(1), 0)
-        return cnt[rows_.to(dev)], live
-
-    live_pre = {}
-    if version == 2:
-        # the offsets' stream edges of EVERY level in one host read, before the first coder launch is queued (a read inside
-        # the level loop would drain the previous level's launch and leave the device idle while the next one is built)
-        torch.cuda.current_stream().wait_event(masks_ready)
-        masks_decoded.record_stream(torch.cuda.current_stream())
-        for (level_, _tc, orig_, _h) in plan:
-            live_pre[level_] = live_slots(orig_, int(orig_.shape[0]), None)
-        tr("offset blocks of all levels on the host")
-
-    def offset_groups(pending):
-        groups, fills = [], []
-        for (level_, orig_, n_, rows_, mean_o, scale_o, Qo_) in pending:
-            if level_ in live_pre:
-                off_edges, live = live_pre[level_]
-            else:
-                off_edges, live = live_slots(orig_, n_, rows_)
-                off_edges = off_edges.cpu()
-            groups.append((mean_o.reshape(-1).index_select(0, live), scale_o.reshape(-1).index_select(0, live),
-                           Qo_.index_select(0, live // (3 * K)), off_edges,
-                           min_offsets_d[level_], max_offsets_d[level_],
-                           *chunk_lens("offsets", level_, bit_offsets_d[level_]), 1))
-            fills.append((orig_, n_, live))
-        return groups, fills
-
-    last_level = plan[-1][0] if plan else None
-    for (level, to_code, orig, hybrid_anchor) in plan:
-        n_l = int(orig.shape[0])
-        assert n_l == N_levels_list[level]
-        if content_pre_gathered is None:
-            feat_in = torch.cat([anchor_decoded[orig], hyper_decoded[orig].float()], dim=1)
-        else:
-            feat_in = torch.cat([content_pre_gathered, hyper_decoded[orig]], dim=1)
-        tr(f"level {level}: input rows assembled")
-        (mean_feat, scale_feat, mean_scaling, scale_scaling, mean_offsets, scale_offsets, Qf, Qs, Qo) = \
-            _predict(pc, level, feat_in)
-        tr(f"level {level}: predicted (enqueued)")
-        rows = torch.tensor(_chunk_rows(n_l, max_batch), dtype=torch.int64)
-        edges_f, edges_s = ((_block_edges(n_l * D, block_of(n_l, n_l * D)), _block_edges(n_l * 6, block_of(n_l, n_l * 6))) if lanes
-                            else (rows * D, rows * 6))
-        pending_offsets.append((level, orig, n_l, rows, mean_offsets, scale_offsets, Qo))
-        groups = [(mean_feat, scale_feat, Qf, edges_f, min_feat_d[level], max_feat_d[level],
-                   *chunk_lens("feat", level, bit_feat_d[level]), D),
-                  (mean_scaling, scale_scaling, Qs, edges_s, min_scaling_d[level], max_scaling_d[level],
-                   *chunk_lens("scaling", level, bit_scaling_d[level]), 6)]
-        fills = []
-        if version == 2:
-            # version 2: the masks are on the device long before the first level is predicted, so a level's offsets ride in
-            # that level's launch (their streams are not longer than the feature streams beside them)
-            og, fills = offset_groups(pending_offsets[-1:])
-            groups += og
-        elif level == last_level:
-            fork = torch.cuda.current_stream().record_event()       # everything the offsets need exists before this point
-        decoded = codec.gaussian_decode_groups(groups, lanes=lanes)
-        tr(f"level {level}: coder launch enqueued")
-        feat_dec, scal_dec = decoded[0], decoded[1]
-        for (orig_, n_, live), off_vals in zip(fills, decoded[2:]):
-            off_dec = torch.zeros(n_ * 3 * K, device=dev)
-            off_dec.index_copy_(0, live, off_vals)
-            grid_offset_after_Q[orig_] = off_dec.view(n_, K, 3)
-        if version == 1 and level == last_level:
-            # The offsets of ALL levels as their own launch on a side stream, forked BEFORE the last feature launch:
-            # they need the mask stream (a serial host job of ~70 ms that ends about now), the features do not, and a
-            # coder launch keeps few SIMDs busy (one wave per stream), so the two launches run side by side instead of
-            # the last one waiting for the masks.
-            main = torch.cuda.current_stream()
-            with torch.cuda.stream(side_stream):
-                side_stream.wait_event(fork)
-                tr("waiting for the mask stream")
-                masks_decoded = torch.from_numpy(mask_job.result()).to(dev).to(torch.float32).view(-1, K, 1)
-                tr("mask stream decoded")
-                og, fills = offset_groups(pending_offsets)
-                for (orig_, n_, live), off_vals in zip(fills, codec.gaussian_decode_groups(og)):
-                    off_dec = torch.zeros(n_ * 3 * K, device=dev)
-                    off_dec.index_copy_(0, live, off_vals)
-                    grid_offset_after_Q[orig_] = off_dec.view(n_, K, 3)
-                tr("offsets launch enqueued")
-            main.wait_stream(side_stream)
-
-        tr(f"level {level}: offsets placed")
-        feat_after_Q[orig] = feat_dec.view(n_l, D)
-        grid_scaling_after_Q[orig] = scal_dec.view(n_l, 6)
-        tr(f"level {level}: decoded rows placed")
-        if level != 0:
-            already_coded.index_fill_(0, orig, True)   # (x[idx] = True uploads its scalar through a blocking pageable copy)
-            content_pre_gathered = context_rows(pc, anchor_decoded, feat_after_Q, grid_scaling_after_Q, already_coded,
-                                                inverse_indices_list, mapping_list, level)
-            tr(f"level {level}: context of the next level gathered")
-    if masks_decoded is None:                    # no level at all (empty model)
-        masks_decoded = torch.from_numpy(mask_job.result()).to(dev).to(torch.float32).view(-1, K, 1)
-    if masks_ready is not None:
-        torch.cuda.current_stream().wait_event(masks_ready)
-        masks_decoded.record_stream(torch.cuda.current_stream())
+    st.feat_after_Q = torch.zeros(N_valid, st.D, device=dev)
+    st.scaling_after_Q = torch.zeros(N_valid, 6, device=dev)
+    st.offsets_after_Q = torch.zeros(N_valid, st.K, 3, device=dev)
+    st.already_coded = torch.zeros(N_valid, dtype=torch.bool, device=dev)
+    stages.offset_edges_ahead(st, plan, tr)
+    for (level, _to_code, orig, _hybrid_anchor) in plan:
+        assert int(orig.shape[0]) == n_levels[level]
+        _decode_level(pc, st, stages, level, orig, level == plan[-1][0], dev, tr)
+    stages.masks_joined(st, dev)
     tr("levels enqueued")
     torch.cuda.synchronize(); t2 = time.time()
     tr("device done")
-    if version == 2:
-        codec.decode_status_check(dev)           # (after the synchronize: no extra wait)
+    stages.status_check(dev)                     # (after the synchronize: no extra wait)
     print("decoding time:", t2 - t1)
-
-    z = lambda *s: torch.zeros(*s, device=dev)                                            # :1503-1533
-    _hyper, _anchor, _feat = z(N_full, H), z(N_full, 3), z(N_full, D)
-    _offset, _scaling, _mask = z(N_full, K, 3), z(N_full, 6), z(N_full, K, 1)
-    _anchor[:N_valid] = anchor_decoded
-    _hyper[:N_valid] = hyper_decoded
-    _feat[:N_valid] = feat_after_Q
-    _offset[:N_valid] = grid_offset_after_Q
-    _scaling[:N_valid] = grid_scaling_after_Q
-    _mask[:N_valid] = masks_decoded
-    pc._hyper_latent = nn.Parameter(_hyper)
-    pc._anchor_feat = nn.Parameter(_feat)
-    pc._offset = nn.Parameter(_offset)
-    pc.decoded_version = True
-    pc._anchor = nn.Parameter(_anchor)
-    pc._scaling = nn.Parameter(_scaling)
-    pc._mask = nn.Parameter(_mask)
-    if hasattr(pc, "_level_cache"):
-        pc._level_cache = None
-    pc._anchor_q_cache = None
+    _install_decoded(pc, st, N_valid, dev)
     return f"\nDecTime {round(t2 - t1, 4)}"

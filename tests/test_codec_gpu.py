@@ -299,14 +299,15 @@ def test_container_encode_decode_roundtrip(tmp_path, N, seed, version):
     else:
         # version 2: the same symbols cut into 1000-anchor chunk streams, each the oracle's stream for its symbols
         assert len(meta) == 15 and meta[14]["version"] == 2
-        from contextgs_amd.codec_driver import _level_blocks
+        from contextgs_amd.codec_driver import ContainerLayout, _unpack_meta
+        layout = ContainerLayout.from_header(_unpack_meta(meta))
         ck, K = meta[14]["chunk"], enc.n_offsets
         want = b"".join(ref.ac_encode([row] * len(sym[a:a + ck["masks"] * K]), sym[a:a + ck["masks"] * K])
                         for a in range(0, len(sym), ck["masks"] * K))
         assert masks_b == want and sum(meta[14]["bit_masks"]) == 8 * len(masks_b)
         # feat / scaling: ceil(symbols / block) blocks per level, each a 128-byte header + 64 lane streams
         for l, n_l in enumerate(reversed(meta[13])):
-            B_of = lambda n_sym: _level_blocks(n_l, n_sym, enc.feat_dim, int(meta[14].get("block_policy", 0)), int(meta[14]["block_symbols"]))
+            B_of = lambda n_sym: layout.block_symbols(n_l, n_sym, enc.feat_dim)
             assert (len(meta[10][l]) == -(-n_l * enc.feat_dim // B_of(n_l * enc.feat_dim))
                     and len(meta[11][l]) == -(-n_l * 6 // B_of(n_l * 6)))
             blob = open(os.path.join(d, f"feat{l}.b"), "rb").read()
@@ -315,6 +316,53 @@ def test_container_encode_decode_roundtrip(tmp_path, N, seed, version):
             for bits in meta[10][l]:
                 _split_block(blob[pos:pos + bits // 8])
                 pos += bits // 8
+
+
+def test_every_block_policy_round_trips(tmp_path, monkeypatch):
+    """Block policies 0 and 1 are no longer what the encoder writes by default, but containers cut by them exist: with the
+    policy patched in, version 2 of the golden model (N = 10000) decodes to exactly the encoder's quantised values under each
+    of the three.  The block sizes are patched down (4096 halving to 128) so that the policies really cut this small model
+    differently: with n anchors in the largest level (2622 <= n < 20972 for these sizes) policy 0 keeps 4096, policy 2 takes
+    the largest size that makes >= 256 feature blocks (>= 512), policy 1 a quarter of that or less for both groups."""
+    from container_digest import build_model
+    from contextgs_amd import codec_driver as cd
+    from contextgs_amd import context_model as cm
+    monkeypatch.setattr(cd, "V2_BLOCK", 4096)
+    monkeypatch.setattr(cd, "V2_BLOCK_MIN", 128)
+    enc = build_model(10000, 3)
+    with torch.no_grad():
+        m = enc.get_mask_anchor
+        nv = int(m.sum())
+        anchor, masks = enc.get_anchor[m], enc.get_mask[m]
+        f, s, o = cm.multi_scale_generating(enc, anchor, enc._hyper_latent[m], enc._anchor_feat[m], enc._offset[m],
+                                            enc.get_scaling[m], masks, None, predict_bpp=False, training=False)
+        hyper = torch.round(enc._hyper_latent[m])
+    blocks = {}
+    for policy in (0, 1, 2):
+        monkeypatch.setattr(cd, "V2_BLOCK_POLICY", policy)
+        d = str(tmp_path / f"policy{policy}")
+        cd.conduct_encoding(enc, d, container_version=2)
+        meta = cd._unpack_meta(torch.load(os.path.join(d, "meta.b"), weights_only=False))
+        assert meta.extra["block_policy"] == policy and meta.extra["block_symbols"] == 4096
+        big = max(range(len(meta.n_levels)), key=lambda l: list(reversed(meta.n_levels))[l])
+        blocks[policy] = (len(meta.bit_feat[big]), len(meta.bit_scaling[big]))
+        dec = build_model(10000, 3)
+        with torch.no_grad():           # scramble: everything must come from the files
+            dec._anchor_feat.zero_(); dec._offset.zero_(); dec._hyper_latent.zero_(); dec._scaling.zero_()
+            for p in dec.mlp_grid.parameters():
+                p.zero_()
+        info = dec.conduct_decoding(d)
+        assert "DecTime" in info and dec.decoded_version
+        with torch.no_grad():
+            assert torch.equal(dec._anchor[:nv], anchor)
+            assert torch.equal(dec._mask[:nv], masks)
+            assert torch.equal(dec._hyper_latent[:nv], hyper)
+            assert torch.equal(dec._anchor_feat[:nv], f)
+            assert torch.equal(dec._scaling[:nv], s)
+            assert torch.equal(dec._offset[:nv], o * masks)               # masked-out offsets are not transmitted
+            assert float(dec._anchor_feat[nv:].abs().sum()) == 0.0
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        assert blocks[a][0] != blocks[b][0] and blocks[a][1] != blocks[b][1], blocks
 
 
 @pytest.mark.parametrize("N", [3000, 10000])
@@ -401,8 +449,8 @@ def test_staged_files_hold_release_and_deferred_download(tmp_path):
     if edges[-1] != n:
         edges.append(n)
     ref = codec.gaussian_encode_packed(x, mean, scale, Q, torch.tensor(edges), lanes=True)
-    blob, lens, mn, mx = codec.gaussian_encode_packed(x, mean, scale, Q, torch.tensor(edges), staging=True, lanes=True, deferred=True)
-    ready = codec.stage_ready()
+    blob, lens, mn, mx, ready = codec.gaussian_encode_packed(x, mean, scale, Q, torch.tensor(edges), staging=True, lanes=True,
+                                                             deferred=True)
     assert ready is not None
     out = str(tmp_path / "coded.b")
     for j in codec.write_file(out, blob, piece=1 << 20, ready=ready):
