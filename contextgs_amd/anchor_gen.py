@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .mlp import _ptr_array, _zeros_views, anchor_mlp3_supported
+from .mlp import _ptr_array, _zeros_views, anchor_mlp3_params, anchor_mlp3_supported
 
 K_FUSED = 10
 # Which calls take the fused node ("all" | "nograd" | "off"; every setting computes the same function).  Measured on
@@ -134,7 +134,4 @@ def anchor_gen(feat_src, feat_row, anchor_vis, cam_center, gs_src, off_src, geo_
     """(xyz, color, opacity, scaling, rot, neural_opacity, selection_mask) of the visible anchors: anchor r has the
     MLP input [feat_src[feat_row[r]] | unit view vector | distance] and the geometry rows gs_src / off_src[geo_row[r]]
     (a row index of None = identity), masks [n, K] its offset mask."""
-    params = []
-    for s in (mo, mc, mv):
-        params += [s[0].weight, s[0].bias, s[2].weight, s[2].bias]
-    return _AnchorGen.apply(feat_src, feat_row, anchor_vis, cam_center, gs_src, off_src, geo_row, masks, *params)
+    return _AnchorGen.apply(feat_src, feat_row, anchor_vis, cam_center, gs_src, off_src, geo_row, masks, *anchor_mlp3_params(mo, mc, mv))

@@ -516,8 +516,11 @@ def gather_unique(x, idx, complete=False):
     return _GatherUnique.apply(x, idx, complete) if x.requires_grad else _index_rows(x, idx)
 
 
+gather_unique_values = _index_rows     # the rows of a detached x that gather_unique_attach / _pair_attach create their node around
+
+
 def gather_unique_attach(x, idx, values):
-    """The autograd node of gather_unique(x, idx) around rows that were gathered EARLIER (values = _index_rows(x.detach(), idx)):
+    """The autograd node of gather_unique(x, idx) around rows that were gathered EARLIER (values = gather_unique_values(x.detach(), idx)):
     the launch stays where it hides a host wait, the node is created where the backward should run it (see
     ctx_ops._MaskSTEAttach)."""
     return _GatherUnique.apply(x, idx, False, values) if x.requires_grad else values
@@ -682,6 +685,16 @@ def early_levels_begin(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask
     The result waits in begun["early"] for context_model_coding_order."""
     if EARLY_LEVELS and begun is not None and anchor.is_cuda and torch.is_grad_enabled():
         begun["early"] = _early_levels(pc, anchor, hyper, feat, grid_offsets, grid_scaling, mask_anchor_bool, begun)
+
+
+def early_visible_rows(begun, vis_idx):
+    """(the early levels' coded-feature buffer, the rows of the anchors vis_idx in it) or None: nothing was enqueued early."""
+    early = begun.get("early") if begun is not None else None
+    if early is None:
+        return None
+    pos = _index_rows(early["cache"]["inv_perm"], vis_idx)
+    begun["early_pos"] = (vis_idx, pos, early["cache"])      # (multi_scale_generating_visible hands the same tensor on)
+    return early["big"][0], pos
 
 
 def context_model_coding_order(*args, begun=None, **kwargs):
@@ -1242,7 +1255,7 @@ def multi_scale_generating_visible(pc, anchor, hyper, feat, grid_offsets, grid_s
     if draw:
         choose_mask = c.get("_choose_mask")
     if c["covers_all"]:
-        # (the renderer may have formed the rows already, for its early launch of the anchor MLPs: the same tensor is handed on)
+        # (early_visible_rows may have formed the rows already, for the early launch of the anchor MLPs: the same tensor is handed on)
         e_pos = begun.get("early_pos") if begun is not None else None
         pos = e_pos[1] if (e_pos is not None and e_pos[0] is vis_idx and e_pos[2] is c) else _index_rows(c["inv_perm"], vis_idx)
         lazy = defer_feat and feat_p.is_cuda and feat_p.dtype == torch.float32
@@ -1259,9 +1272,9 @@ def multi_scale_generating_visible(pc, anchor, hyper, feat, grid_offsets, grid_s
         pc, anchor, binary_grid_masks() if callable(binary_grid_masks) else binary_grid_masks, mask_anchor_bool, likelihood_hyper,
         levels, False, choose_mask, live_count=c.get("live_count"), masks_chosen_given=masks_chosen,
         levels_fused=route.levels_fused))
-    # the rows whose mask weights the rate model will gather, when it is one list for all levels (the caller may gather them in
-    # the same node as its own rows of the mask: _GatherUniquePair)
-    rate.chosen_rows = levels[0]["chosen"][0] if (route.levels_fused and levels[0]["chosen"] is not None) else None
     if defer_rate:      # the caller enqueues the rate model where it fills a read-back bubble (renderer.py)
-        return outs + (rate,)
+        # with the rows whose mask weights the rate model will gather, when it is one list for all levels (the caller may gather
+        # them in the same node as its own rows of the mask: _GatherUniquePair)
+        chosen_rows = levels[0]["chosen"][0] if (route.levels_fused and levels[0]["chosen"] is not None) else None
+        return outs + (rate, chosen_rows)
     return outs + rate()

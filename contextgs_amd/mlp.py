@@ -6,6 +6,7 @@ instance raise.
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import torch
@@ -345,6 +346,11 @@ def anchor_mlp3_supported(mo: nn.Sequential, mc: nn.Sequential, mv: nn.Sequentia
     return keys == [(54, 50, 10, 1), (54, 50, 30, 2), (54, 50, 70, 0)]
 
 
+def anchor_mlp3_params(mo: nn.Sequential, mc: nn.Sequential, mv: nn.Sequential):
+    """(W1, b1, W2, b2) x (opacity, color, cov): the flat parameter list of the anchor-MLP nodes."""
+    return [t for s in (mo, mc, mv) for t in (s[0].weight, s[0].bias, s[2].weight, s[2].bias)]
+
+
 def _m3_wgrad_job(x, ldx, hcat, dz1, dz2_op, dz2_color, g_cov, dW1cat, db1cat, dW2, db2, n, ws, params, wgrads):
     """The deferred weight-gradient launch of an anchor-MLP backward node (operands kept alive by the closure)."""
     def job():
@@ -429,6 +435,18 @@ M3_TILED = os.environ.get("CGS_M3_TILED", "1") != "0"
 _M3_REGATHER_MAX_ROWS = 4_000_000                                # the fused backward's row limit (32-bit buffer offsets)
 
 
+class _M3Launch(collections.namedtuple("_M3Launch", "feat_src src_row anchor_vis cam W1 W2 y hcat x keep_x need_grad deferred tiled")):
+    """What _AnchorMLP3Rows.launch enqueued: its operands as the kernel read them, its outputs and the settings it ran under."""
+
+    def fits(self, feat_src, src_row, anchor_vis, need_grad):
+        """An early launch is taken only if it ran on exactly these operands, under the settings the node has now."""
+        fs, av = feat_src.detach(), anchor_vis.detach()
+        return (self.src_row is src_row and self.need_grad == need_grad and self.deferred == _Deferred.on
+                and fs.dtype == torch.float32 and fs.is_contiguous() and av.dtype == torch.float32 and av.is_contiguous()
+                and (self.feat_src.data_ptr(), tuple(self.feat_src.shape), self.anchor_vis.data_ptr(), int(self.src_row.shape[0]))
+                == (fs.data_ptr(), tuple(fs.shape), av.data_ptr(), int(src_row.shape[0])))
+
+
 class _AnchorMLP3Rows(torch.autograd.Function):
     """The three anchor MLPs on rows assembled inside the kernel: [feat_src[src_row] | view direction | distance]
     (gaussian_renderer/__init__.py:106-127); backward scatters the feature gradient into the source rows and pulls the
@@ -436,7 +454,7 @@ class _AnchorMLP3Rows(torch.autograd.Function):
 
     @staticmethod
     def launch(feat_src, src_row, anchor_vis, cam, params, need_grad):
-        """The forward's launch on plain values: a dict forward() accepts as `pre`.  The renderer calls it EARLY — right after the
+        """The forward's launch on plain values: the record forward() accepts as `pre`.  The renderer calls it EARLY — right after the
         visible-anchor list is known, on the buffer the step's level kernels are writing — so that the 0.5 ms kernel is in the
         queue while the host creates the context model's autograd nodes (renderer.generate_neural_gaussians)."""
         L = _lib.lib()
@@ -464,32 +482,22 @@ class _AnchorMLP3Rows(torch.autograd.Function):
                                                     _lib.ptr(x), _ptr_array(W1), _ptr_array(b1), _ptr_array(W2), _ptr_array(b2),
                                                     _lib.ptr(y_op), _lib.ptr(y_color), _lib.ptr(y_cov), _lib.ptr(hcat), n, int(tiled),
                                                     _lib.current_stream()), "cgs_anchor_mlp3_forward_rows")
-        return dict(feat_src=feat_src, src_row=src_row, anchor_vis=anchor_vis, cam=cam, W1=W1, W2=W2, y=(y_op, y_color, y_cov), hcat=hcat,
-                    x=x, keep_x=keep_x, need_grad=need_grad, deferred=_Deferred.on, tiled=tiled,
-                    key=(feat_src.data_ptr(), tuple(feat_src.shape), anchor_vis.data_ptr(), n))
+        return _M3Launch(feat_src, src_row, anchor_vis, cam, W1, W2, (y_op, y_color, y_cov), hcat, x, keep_x, need_grad,
+                         _Deferred.on, tiled)
 
     @staticmethod
     def forward(ctx, feat_src, src_row, anchor_vis, cam, pre, *params):
         ctx.set_materialize_grads(False)
         need_grad = any(ctx.needs_input_grad)
-        if pre is not None:
-            # an early launch is taken only if it ran on exactly these operands (else: dropped, launched again)
-            fs_, av_ = feat_src.detach(), anchor_vis.detach()
-            if not (pre["src_row"] is src_row and pre["need_grad"] == need_grad and pre["deferred"] == _Deferred.on
-                    and fs_.dtype == torch.float32 and fs_.is_contiguous() and av_.dtype == torch.float32 and av_.is_contiguous()
-                    and pre["key"] == (fs_.data_ptr(), tuple(fs_.shape), av_.data_ptr(), int(src_row.shape[0]))):
-                pre = None
-        if pre is None:
+        if pre is None or not pre.fits(feat_src, src_row, anchor_vis, need_grad):      # (else: dropped, launched again)
             pre = _AnchorMLP3Rows.launch(feat_src, src_row, anchor_vis, cam, params, need_grad)
-        feat_src, anchor_vis, cam = pre["feat_src"], pre["anchor_vis"], pre["cam"]
-        W1, W2 = pre["W1"], pre["W2"]
-        y_op, y_color, y_cov = pre["y"]
-        hcat, x, keep_x = pre["hcat"], pre["x"], pre["keep_x"]
+        y_op, y_color, y_cov = pre.y
         if need_grad:
-            ctx.save_for_backward(x if keep_x else feat_src, src_row, anchor_vis, cam, y_op, y_color, hcat, *W1, *W2)
-            ctx.n_src = int(feat_src.shape[0])
-            ctx.keep_x = keep_x
-            ctx.tiled = bool(pre.get("tiled", False))
+            ctx.save_for_backward(pre.x if pre.keep_x else pre.feat_src, src_row, pre.anchor_vis, pre.cam, y_op, y_color, pre.hcat,
+                                  *pre.W1, *pre.W2)
+            ctx.n_src = int(pre.feat_src.shape[0])
+            ctx.keep_x = pre.keep_x
+            ctx.tiled = pre.tiled
         ctx.params = params
         return y_op, y_color, y_cov
 
@@ -543,24 +551,15 @@ class _AnchorMLP3Rows(torch.autograd.Function):
 def anchor_mlp3_rows(feat_src, src_row, anchor_vis, cam_center, mo: nn.Sequential, mc: nn.Sequential, mv: nn.Sequential, pre=None):
     """(mlp_opacity(x), mlp_color(x), mlp_cov(x)) with x[r] = [feat_src[src_row[r]] | unit view vector | distance] of
     anchor_vis[r] seen from cam_center, assembled inside the fused launch.  pre: anchor_mlp3_rows_launch() of the same operands."""
-    params = []
-    for s in (mo, mc, mv):
-        params += [s[0].weight, s[0].bias, s[2].weight, s[2].bias]
-    return _AnchorMLP3Rows.apply(feat_src, src_row, anchor_vis, cam_center, pre, *params)
+    return _AnchorMLP3Rows.apply(feat_src, src_row, anchor_vis, cam_center, pre, *anchor_mlp3_params(mo, mc, mv))
 
 
 def anchor_mlp3_rows_launch(feat_src, src_row, anchor_vis, cam_center, mo: nn.Sequential, mc: nn.Sequential, mv: nn.Sequential,
                             need_grad=True):
     """The launch of anchor_mlp3_rows() on plain values, ahead of the node (see _AnchorMLP3Rows.launch)."""
-    params = []
-    for s in (mo, mc, mv):
-        params += [s[0].weight, s[0].bias, s[2].weight, s[2].bias]
-    return _AnchorMLP3Rows.launch(feat_src, src_row, anchor_vis, cam_center, params, need_grad)
+    return _AnchorMLP3Rows.launch(feat_src, src_row, anchor_vis, cam_center, anchor_mlp3_params(mo, mc, mv), need_grad)
 
 
 def anchor_mlp3(x, mo: nn.Sequential, mc: nn.Sequential, mv: nn.Sequential):
     """(mlp_opacity(x), mlp_color(x), mlp_cov(x)) in one fused launch each way."""
-    params = []
-    for s in (mo, mc, mv):
-        params += [s[0].weight, s[0].bias, s[2].weight, s[2].bias]
-    return _AnchorMLP3.apply(x, *params)
+    return _AnchorMLP3.apply(x, *anchor_mlp3_params(mo, mc, mv))

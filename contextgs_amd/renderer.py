@@ -11,6 +11,7 @@ step); the context model of the training / eval phases is context_model.py.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -18,8 +19,9 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import _lib, anchor_gen, mlp
-from .context_model import LazyRows, begin_step, gather_unique, multi_scale_generating, multi_scale_generating_visible
+from . import _lib, anchor_gen, ctx_ops, mlp
+from .context_model import (LazyRows, begin_step, early_levels_begin, early_visible_rows, gather_unique, gather_unique_attach,
+                            gather_unique_pair_attach, gather_unique_values, multi_scale_generating_visible)
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, check_deterministic
 
 Q_FEAT, Q_SCALING, Q_OFFSETS = 1, 0.001, 0.2      # :40-42
@@ -111,6 +113,41 @@ class ExpandCount:
         return self.P
 
 
+def _expand_operands(anchor, gscaling, offsets, masks, op_raw, color_in, cov_in, K, pre):
+    """The expansion's seven operands as contiguous fp32 tensors, and their count launch `pre` (launched here when None)."""
+    _lib.require_device(anchor, gscaling, offsets, masks, op_raw, color_in, cov_in)
+    ops = tuple(_c(t) for t in (anchor, gscaling, offsets, masks, op_raw, color_in, cov_in))
+    if pre is None:
+        pre = ExpandCount(ops[4], ops[3], K)
+    assert pre.n == ops[0].shape[0] and pre.K == K
+    return ops, pre
+
+
+def _expand_backward(saved, n, K, src_row, g_xyz, g_color, g_opacity, g_scaling, g_rot, g_no, stream):
+    """cgs_expand_backward on the per-Gaussian gradients (g_no may be None) -> those of the expansion's seven operands."""
+    flags, pos, gscaling, offsets, op_raw, masks, cov_in = saved
+    dev = gscaling.device
+    e = lambda t: torch.empty_like(t)
+    d_anchor = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    d_op, d_mask = e(op_raw), e(masks)
+    if src_row is None:
+        d_gs, d_off = e(gscaling), e(offsets)
+    else:       # rows of the larger arrays that no visible anchor reads get a zero gradient (zero_unlisted_rows: only those
+        # rows are written, not a fill of the whole arrays); when src_row names every row there is nothing to zero
+        flat = torch.empty(gscaling.numel() + offsets.numel(), dtype=torch.float32, device=dev)
+        d_gs, d_off = flat[:gscaling.numel()].view_as(gscaling), flat[gscaling.numel():].view_as(offsets)
+        if n != gscaling.shape[0]:
+            ctx_ops.zero_unlisted_rows(src_row, gscaling.shape[0], [d_gs, d_off])
+    d_color = torch.empty(n, 3 * K, dtype=torch.float32, device=dev)
+    d_cov = e(cov_in)
+    _lib.check(_lib.lib().cgs_expand_backward(
+        n, K, _lib.ptr(flags), _lib.ptr(pos), _lib.ptr(gscaling), _lib.ptr(offsets), _lib.ptr(op_raw), _lib.ptr(masks),
+        _lib.ptr(cov_in), _lib.ptr(g_xyz), _lib.ptr(g_color), _lib.ptr(g_opacity), _lib.ptr(g_scaling), _lib.ptr(g_rot),
+        _lib.ptr(g_no), _lib.ptr(d_anchor), _lib.ptr(d_gs), _lib.ptr(d_off), _lib.ptr(d_op), _lib.ptr(d_mask),
+        _lib.ptr(d_color), _lib.ptr(d_cov), _lib.ptr(src_row), stream), "cgs_expand_backward")
+    return d_anchor, d_gs, d_off, d_mask, d_op, d_color, d_cov
+
+
 class _ExpandGaussians(torch.autograd.Function):
     """(anchor, grid_scaling, offsets, masks, mlp outputs) -> compacted Gaussians (:112-145)."""
 
@@ -120,72 +157,30 @@ class _ExpandGaussians(torch.autograd.Function):
         # their row src_row[n] (the visibility gather is done by the kernel)
         # pre: an ExpandCount already launched for (op_raw, masks) by the caller
         L = _lib.lib()
-        _lib.require_device(anchor, gscaling, offsets, masks, op_raw, color_in, cov_in)
-        anchor, gscaling, offsets = _c(anchor), _c(gscaling), _c(offsets)
-        masks, op_raw, color_in, cov_in = _c(masks), _c(op_raw), _c(color_in), _c(cov_in)
-        n = anchor.shape[0]
-        dev = anchor.device
-        stream = _lib.current_stream()
-        if pre is None:
-            pre = ExpandCount(op_raw, masks, K)
-        assert pre.n == n and pre.K == K
+        (anchor, gscaling, offsets, masks, op_raw, color_in, cov_in), pre = _expand_operands(
+            anchor, gscaling, offsets, masks, op_raw, color_in, cov_in, K, pre)
+        n, dev, stream = anchor.shape[0], anchor.device, _lib.current_stream()
         ctx.set_materialize_grads(False)        # an unused output (neural_opacity in most losses) arrives as None, not as zeros
         P = pre.wait()
         neural_opacity, mask_out, flags, pos = pre.neural_opacity, pre.mask_out, pre.flags, pre.pos
-        xyz = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        color = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        opacity = torch.empty(P, 1, dtype=torch.float32, device=dev)
-        scaling = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        rot = torch.empty(P, 4, dtype=torch.float32, device=dev)
+        xyz, color, opacity, scaling, rot = (torch.empty(P, w, dtype=torch.float32, device=dev) for w in (3, 3, 1, 3, 4))
         _lib.check(L.cgs_expand_write(n, K, _lib.ptr(flags), _lib.ptr(pos), _lib.ptr(anchor), _lib.ptr(gscaling),
                                       _lib.ptr(offsets), _lib.ptr(neural_opacity), _lib.ptr(color_in),
                                       _lib.ptr(cov_in), _lib.ptr(xyz), _lib.ptr(color), _lib.ptr(opacity),
                                       _lib.ptr(scaling), _lib.ptr(rot), _lib.ptr(src_row), stream), "cgs_expand_write")
-        ctx.K = K
-        ctx.n = n
-        ctx.P = P                   # the substitutes of absent output gradients are sized from this, not from g_xyz (ADVICE r3)
-        ctx.src_row = src_row
+        ctx.K, ctx.n, ctx.src_row = K, n, src_row
+        ctx.P = P                   # the substitutes of absent output gradients are sized from this, not from g_xyz
         ctx.save_for_backward(flags, pos, gscaling, offsets, op_raw, masks, cov_in)
         ctx.mark_non_differentiable(mask_out)
         return xyz, color, opacity, scaling, rot, neural_opacity, mask_out
 
     @staticmethod
     def backward(ctx, g_xyz, g_color, g_opacity, g_scaling, g_rot, g_no, _g_mask):
-        L = _lib.lib()
-        flags, pos, gscaling, offsets, op_raw, masks, cov_in = ctx.saved_tensors
-        K = ctx.K
-        n = ctx.n
-        src_row = ctx.src_row
-        dev = gscaling.device
-        P = ctx.P
-        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        g_xyz = _c(g_xyz) if g_xyz is not None else z(P, 3)
-        g_color = _c(g_color) if g_color is not None else z(P, 3)
-        g_opacity = _c(g_opacity) if g_opacity is not None else z(P, 1)
-        g_scaling = _c(g_scaling) if g_scaling is not None else z(P, 3)
-        g_rot = _c(g_rot) if g_rot is not None else z(P, 4)
+        saved, P = ctx.saved_tensors, ctx.P
+        grads = [_c(g) if g is not None else torch.zeros(P, w, dtype=torch.float32, device=saved[2].device)
+                 for g, w in zip((g_xyz, g_color, g_opacity, g_scaling, g_rot), (3, 3, 1, 3, 4))]
         g_no = _c(g_no) if g_no is not None else None
-        e = lambda t: torch.empty_like(t)
-        d_anchor = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        d_op, d_mask = e(op_raw), e(masks)
-        if src_row is None:
-            d_gs, d_off = e(gscaling), e(offsets)
-        else:       # rows of the larger arrays that no visible anchor reads get a zero gradient (zero_unlisted_rows: only those
-            # rows are written); when every anchor is visible (src_row names every row) there is nothing to zero
-            flat = torch.empty(gscaling.numel() + offsets.numel(), dtype=torch.float32, device=dev)
-            d_gs, d_off = flat[:gscaling.numel()].view_as(gscaling), flat[gscaling.numel():].view_as(offsets)
-            if n != gscaling.shape[0]:
-                from .ctx_ops import zero_unlisted_rows
-                zero_unlisted_rows(src_row, gscaling.shape[0], [d_gs, d_off])
-        d_color = torch.empty(n, 3 * K, dtype=torch.float32, device=dev)
-        d_cov = e(cov_in)
-        _lib.check(L.cgs_expand_backward(
-            n, K, _lib.ptr(flags), _lib.ptr(pos), _lib.ptr(gscaling), _lib.ptr(offsets), _lib.ptr(op_raw),
-            _lib.ptr(masks), _lib.ptr(cov_in), _lib.ptr(g_xyz), _lib.ptr(g_color), _lib.ptr(g_opacity),
-            _lib.ptr(g_scaling), _lib.ptr(g_rot), _lib.ptr(g_no), _lib.ptr(d_anchor), _lib.ptr(d_gs),
-            _lib.ptr(d_off), _lib.ptr(d_op), _lib.ptr(d_mask), _lib.ptr(d_color), _lib.ptr(d_cov),
-            _lib.ptr(src_row), _lib.current_stream()), "cgs_expand_backward")
-        return d_anchor, d_gs, d_off, d_mask, d_op, d_color, d_cov, None, None, None
+        return (*_expand_backward(saved, ctx.n, ctx.K, ctx.src_row, *grads, g_no, _lib.current_stream()), None, None, None)
 
 
 EARLY_MLP3 = os.environ.get("CGS_EARLY_MLP3", "1") != "0"            # A/B knob: 0 = the anchor MLPs are enqueued where their node is created
@@ -219,18 +214,13 @@ class _ExpandRasterize(torch.autograd.Function):
                 absgrad=False, deterministic=False):
         from . import rasterizer as rz
         L = _lib.lib()
-        _lib.require_device(anchor, gscaling, offsets, masks, op_raw, color_in, cov_in)
-        anchor, gscaling, offsets = _c(anchor), _c(gscaling), _c(offsets)
-        masks, op_raw, color_in, cov_in = _c(masks), _c(op_raw), _c(color_in), _c(cov_in)
-        n = anchor.shape[0]
-        dev = anchor.device
-        stream = _lib.current_stream()
-        assert pre.n == n and pre.K == K
+        (anchor, gscaling, offsets, masks, op_raw, color_in, cov_in), pre = _expand_operands(
+            anchor, gscaling, offsets, masks, op_raw, color_in, cov_in, K, pre)
+        n, dev, stream = anchor.shape[0], anchor.device, _lib.current_stream()
         ctx.set_materialize_grads(False)
         P = pre.wait()
         assert means2D.shape[0] == P and means2D.shape[1] == (4 if absgrad else 3)
-        ctx.absgrad = bool(absgrad)
-        ctx.deterministic = bool(deterministic)
+        ctx.absgrad, ctx.deterministic = bool(absgrad), bool(deterministic)
         neural_opacity, mask_out, flags, pos = pre.neural_opacity, pre.mask_out, pre.flags, pre.pos
         cfg = rz._Cfg(raster_settings)
         H, W = cfg.c.image_height, cfg.c.image_width
@@ -255,11 +245,10 @@ class _ExpandRasterize(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_img, _g_radii, g_scaling, g_no, _g_mask):
         from . import rasterizer as rz
-        L = _lib.lib()
-        (flags, pos, gscaling, offsets, op_raw, masks, cov_in, xyz, scaling, rot, radii, geom, binws, img) = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        xyz, scaling, rot, radii, geom, binws, img = saved[7:]
         cfg, K, n, src_row, P = ctx.cfg, ctx.K, ctx.n, ctx.src_row, ctx.P
-        dev = gscaling.device
-        stream = _lib.current_stream()
+        dev, stream = xyz.device, _lib.current_stream()
         # ---- the rasterizer's backward (rasterizer.launch_backward) into buffers that stay inside this node
         use_det = g_img is not None and P > 0 and ctx.deterministic
         # atomically accumulated: dL/d colour | opacity (the deterministic backward writes every row of both itself)
@@ -280,28 +269,9 @@ class _ExpandRasterize(torch.autograd.Function):
             rest.zero_()
         if g_scaling is not None:            # the loss reads `scaling` too (train.py:204): what autograd would have summed
             d_scales = d_scales + _c(g_scaling)
-        # ---- the expansion's backward (as _ExpandGaussians.backward)
         g_no = _c(g_no) if g_no is not None else None
-        e = lambda t: torch.empty_like(t)
-        d_anchor = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        d_op, d_mask = e(op_raw), e(masks)
-        if src_row is None:
-            d_gs, d_off = e(gscaling), e(offsets)
-        else:       # rows of the larger arrays that no visible anchor reads get zeros (ctx_ops.zero_unlisted_rows: only
-            #             THOSE rows are written, not a 144 MB fill); every row read -> nothing to zero
-            flat = torch.empty(gscaling.numel() + offsets.numel(), dtype=torch.float32, device=dev)
-            d_gs, d_off = flat[:gscaling.numel()].view_as(gscaling), flat[gscaling.numel():].view_as(offsets)
-            if n != gscaling.shape[0]:
-                from .ctx_ops import zero_unlisted_rows
-                zero_unlisted_rows(src_row, gscaling.shape[0], [d_gs, d_off])
-        d_color = torch.empty(n, 3 * K, dtype=torch.float32, device=dev)
-        d_cov = e(cov_in)
-        _lib.check(L.cgs_expand_backward(
-            n, K, _lib.ptr(flags), _lib.ptr(pos), _lib.ptr(gscaling), _lib.ptr(offsets), _lib.ptr(op_raw), _lib.ptr(masks),
-            _lib.ptr(cov_in), _lib.ptr(d_means3D), _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_scales), _lib.ptr(d_rots),
-            _lib.ptr(g_no), _lib.ptr(d_anchor), _lib.ptr(d_gs), _lib.ptr(d_off), _lib.ptr(d_op), _lib.ptr(d_mask),
-            _lib.ptr(d_color), _lib.ptr(d_cov), _lib.ptr(src_row), stream), "cgs_expand_backward")
-        return d_anchor, d_gs, d_off, d_mask, d_op, d_color, d_cov, d_means2D, None, None, None, None, None, None
+        return (*_expand_backward(saved[:7], n, K, src_row, d_means3D, d_colors, d_opac, d_scales, d_rots, g_no, stream),
+                d_means2D, None, None, None, None, None, None)
 
 
 def _anchor_mlps(pc, x):
@@ -381,186 +351,243 @@ def _generate_unfused(viewpoint_camera, pc, anchor, feat, grid_scaling, grid_off
         pre = ExpandCount(op_raw, masks2, K)
     if between is not None:
         between()
-    if (view is not None and FUSE_VIEW and pre is not None and anchor.is_cuda and grid_scaling.is_cuda
-            and grid_offsets.is_cuda and torch.is_grad_enabled()):
+    if view is not None and _fusable_on_device(pre, anchor, grid_scaling, grid_offsets):
         # the expansion and the rasterizer as one node (csrc/expand_raster.hip); the survivor count is read here, after
         # `between` has put the rate model in the queue, so that screenspace_points can be an INPUT of the node
         P = pre.wait()
         screenspace_points = _zero_points(torch.empty(P, 0, device=anchor.device), 4 if view.absgrad else 3)
-        if view.retain_grad:
-            try:
-                screenspace_points.retain_grad()
-            except Exception:
-                pass
+        _retain_grad(screenspace_points, view.retain_grad)
         image, radii, scaling, neural_opacity, mask = _ExpandRasterize.apply(
             anchor, grid_scaling, grid_offsets, masks2, op_raw, color_in, cov_in, screenspace_points, K, src_row, pre,
-            view.raster_settings, *((view.absgrad, True) if view.deterministic else (True,) if view.absgrad else ()))
+            view.raster_settings, view.absgrad, view.deterministic)
         view.done = (image, radii, screenspace_points)
         return None, None, None, scaling, None, neural_opacity, mask
     return _ExpandGaussians.apply(anchor, grid_scaling, grid_offsets, masks2, op_raw, color_in, cov_in, K, src_row, pre)
 
 
+def _fusable_on_device(pre, anchor, grid_scaling, grid_offsets):
+    # what _view_fusion cannot know up front: the expansion's count is in flight and its operands are on the device
+    return pre is not None and anchor.is_cuda and grid_scaling.is_cuda and grid_offsets.is_cuda
+
+
+_GenPlan = collections.namedtuple("_GenPlan", "phase predict_rate update_bound")
+
+
+def _gen_plan(is_training, step, decoded_version):
+    """What a call runs, from plain values (the one place that compares `step` with a number).  phase: "plain" (raw parameters),
+    "noise" (:54-58) or "context" (:63 in training, :83 in eval); predict_rate; update_bound: update_anchor_bound() runs (:60)."""
+    context = (is_training and step > 10000) or (not is_training and not decoded_version)
+    phase = "context" if context else "noise" if (is_training and 3000 < step <= 10000) else "plain"
+    return _GenPlan(phase, bool(is_training and context), bool(is_training and step == 10000))
+
+
+class _DeferredMask:
+    """The offset mask of a step that trains it on the device: `values` at once, the autograd node when node() is first called."""
+    # the level plan needs the anchor mask, but the node is attached after the level loop's (ctx_ops._MaskSTEAttach: `_mask`'s
+    # gradient is then final BEFORE the level kernels run in the backward); visible_values: the visible anchors' rows of `values`
+
+    def __init__(self, param, values):
+        self.param, self.values, self.visible_values, self._node = param, values, None, None
+
+    def node(self):
+        if self._node is None:
+            self._node = ctx_ops.mask_ste_attach(self.param, self.values)
+        return self._node
+
+
+class _ViewStep:
+    """One call of generate_neural_gaussians: what its stages hand to each other."""
+
+    def __init__(self, camera, pc, plan, is_training, visible_mask, view):
+        self.camera, self.pc, self.plan, self.is_training, self.visible_mask = camera, pc, plan, is_training, visible_mask
+        self.view = view                            # a ViewFusion: the fused expand + raster node may be taken
+        self.full_anchor = self.vis_pending = self.vis_idx = self.anchor = None     # (anchor: the visible rows of full_anchor)
+        # the offset mask of all anchors (a tensor, or the node() of `mask`, the _DeferredMask) and "any offset alive" of it
+        self.binary_all = self.mask_anchor_bool = self.mask = None
+        # context_model.begin_step's handle, get_scaling as the early levels read it, mlp.anchor_mlp3_rows_launch's record
+        self.begun = self.scaling_all = self.mlp_pre = None
+        self.feat = self.grid_scaling = self.grid_offsets = self.masks = None    # the expansion's inputs (tensors or LazyRows)
+        self.rate = self.chosen_rows = self.masks_chosen = None     # the deferred rate model, the mask rows it reads, those rows gathered
+        self.rates = (None,) * 5                    # bit_per_param, bit_per_feat / scaling / offsets_param, bpp_per_level
+
+    def run_rate(self):
+        if self.rate is not None:
+            self.rates = self.rate(self.masks_chosen)
+
+
+def _begin_context(s):
+    # everything of the context model that does not depend on the visible set is enqueued BEFORE the read-back of the visible
+    # count: the GPU works through it while the host waits, and the context model's own count read-back finds its data there
+    if s.plan.phase != "context":
+        return
+    pc = s.pc
+    if (s.is_training and hasattr(pc, "get_mask_pair") and not pc.decoded_version and pc._mask.is_cuda and pc._mask.requires_grad
+            and torch.is_grad_enabled()):
+        values, s.mask_anchor_bool = ctx_ops.mask_ste_values(pc._mask)
+        s.mask = _DeferredMask(pc._mask, values)
+        s.binary_all = s.mask.node
+    elif hasattr(pc, "get_mask_pair"):
+        s.binary_all, s.mask_anchor_bool = pc.get_mask_pair()
+    else:                                   # the reference's own GaussianModel
+        s.binary_all = pc.get_mask
+        s.mask_anchor_bool = s.binary_all.detach().sum(dim=1)[:, 0] > 0
+    s.begun = begin_step(pc, s.full_anchor, s.mask_anchor_bool, s.is_training)
+    if s.begun is not None and s.is_training:
+        # the step's level kernels depend on nothing the host still has to read (not on the view either): 0.4 ms of device
+        # work behind which the read-backs below and the small launches between them disappear (context_model._early_levels)
+        s.scaling_all = pc.get_scaling
+        early_levels_begin(pc, s.full_anchor, pc._hyper_latent, pc._anchor_feat, pc._offset, s.scaling_all, s.mask_anchor_bool,
+                           s.begun)
+
+
+def _note_touched_rows(s):
+    # multi-GPU: the per-anchor gradients of this view only reach the visible anchors unless the context model runs over all
+    # of them (dist.GradientSync(sparse="auto") exchanges the union of the ranks' rows instead of dense tensors)
+    if s.is_training:
+        from . import dist
+        dist.note_touched_rows(None if s.plan.phase == "context" else s.visible_mask, int(s.vis_idx.shape[0]))
+
+
+def _launch_early_mlps(s):
+    # The three anchor MLPs, enqueued on the buffer the level kernels (already in the queue) are writing: their operands are
+    # all known here, and the host has ~0.3 ms of node creation in front of it (hyper step, level nodes, the mask's node) during
+    # which the device would finish the level kernels and idle (profiles/r06_gpu_idle_gaps.txt).  The node is created later, by
+    # _generate_unfused, around this launch; if the step turns out different (the plan was rebuilt, another expansion path), the
+    # launch is dropped and repeated there (mlp._M3Launch.fits).
+    pc = s.pc
+    mlps = (pc.get_opacity_mlp, pc.get_color_mlp, pc.get_cov_mlp)
+    if not (s.begun is not None and s.is_training and EARLY_MLP3 and torch.is_grad_enabled()
+            and mlp.anchor_mlp3_supported(*mlps) and pc._anchor_feat.shape[1] == 50
+            and not anchor_gen.supported(*mlps, pc.n_offsets, s.full_anchor)):
+        return
+    early = early_visible_rows(s.begun, s.vis_idx)
+    if early is not None:
+        s.mlp_pre = mlp.anchor_mlp3_rows_launch(*early, s.anchor.detach(), s.camera.camera_center, *mlps)
+
+
+def _gather_mask_rows(s):
+    # enqueued in front of the context model's count read-back: the host falls behind the device while it waits there, and a
+    # gather the device still has queued covers part of the catch-up
+    if s.mask is not None:
+        s.mask.visible_values = gather_unique_values(s.mask.values, s.vis_idx)
+    elif s.binary_all is not None:
+        s.masks = gather_unique(s.binary_all, s.vis_idx)
+
+
+def _gather_raw_inputs(s):
+    if s.plan.phase == "context":
+        return
+    pc, noise = s.pc, s.plan.phase == "noise"
+    sel = lambda t: gather_unique(t, s.vis_idx)
+    # raw features of the visible anchors: left as (source, rows) when nothing is added to them, so that the anchor-MLP kernel
+    # gathers them itself
+    feat = LazyRows(pc._anchor_feat, s.vis_idx) if (not noise and pc._anchor_feat.is_cuda) else sel(pc._anchor_feat)
+    grid_offsets = sel(pc._offset)
+    grid_scaling = sel(pc.get_scaling)
+    s.masks = sel(pc.get_mask)
+    if noise:                                                                           # :54-58
+        if feat.is_cuda and grid_offsets.dim() == 3:
+            # x + U(-1/2, 1/2) Q for the three tensors in ONE launch (the level kernel of the context model with a zero step-size
+            # adjustment: Q = q0 (1 + tanh 0) = q0) instead of three uniform_ / mul / add chains over [n,50], [n,6], [n,30]; the
+            # build's counter-based generator instead of torch's Philox stream (same distribution, DESIGN.md section 2),
+            # backward = identity
+            n_vis = feat.shape[0]
+            zero_adj = torch.zeros(n_vis, 3, dtype=torch.float32, device=feat.device)
+            off_flat = grid_offsets.reshape(n_vis, grid_offsets.shape[1] * grid_offsets.shape[2])    # (explicit: n_vis may be 0)
+            feat, grid_scaling, off2, _q = ctx_ops.noise_quant(feat, grid_scaling, off_flat, zero_adj,
+                                                               (Q_FEAT, Q_SCALING, Q_OFFSETS))
+            grid_offsets = off2.view(grid_offsets.shape)
+        else:
+            feat = feat + torch.empty_like(feat).uniform_(-0.5, 0.5) * Q_FEAT
+            grid_scaling = grid_scaling + torch.empty_like(grid_scaling).uniform_(-0.5, 0.5) * Q_SCALING
+            grid_offsets = grid_offsets + torch.empty_like(grid_offsets).uniform_(-0.5, 0.5) * Q_OFFSETS
+    s.feat, s.grid_scaling, s.grid_offsets = feat, grid_scaling, grid_offsets
+
+
+def _run_context_model(s):                                                              # :63-81 (train) / :83-101 (eval)
+    if s.plan.phase != "context":
+        return
+    pc = s.pc
+    # (get_mask_anchor, scene/gaussian_model.py:302-310, is "any offset alive" of the SAME mask values: both came from one
+    # evaluation in _begin_context instead of running the sigmoid / threshold / STE chain twice)
+    res = multi_scale_generating_visible(pc, s.full_anchor, pc._hyper_latent, pc._anchor_feat, pc._offset,
+                                         s.scaling_all if s.scaling_all is not None else pc.get_scaling, s.binary_all,
+                                         s.mask_anchor_bool, s.vis_idx, training=s.is_training,
+                                         predict_bpp=s.plan.predict_rate, defer_feat=True, begun=s.begun, defer_rate=True)
+    s.feat, s.grid_scaling, s.grid_offsets = res[:3]
+    if s.plan.predict_rate:     # the rate model (:1657-1707) is enqueued behind the expansion's count (_expand)
+        s.rate, s.chosen_rows = res[3:]
+
+
+def _attach_mask(s):
+    if s.mask is None:
+        return
+    if s.chosen_rows is not None and s.chosen_rows.is_cuda:
+        # the visible rows (for the expansion) and the rate subset's rows of the mask weights through ONE node: one gradient
+        # buffer instead of two and the engine's add (context_model._GatherUniquePair)
+        s.masks, s.masks_chosen = gather_unique_pair_attach(s.mask.node(), s.vis_idx, s.mask.visible_values, s.chosen_rows)
+    else:
+        s.masks = gather_unique_attach(s.mask.node(), s.vis_idx, s.mask.visible_values)
+
+
+def _expand(s):
+    K = s.pc.n_offsets
+    out = _generate_fused(s.camera, s.pc, s.anchor, s.feat, s.grid_scaling, s.grid_offsets, s.masks, K)
+    if out is not None:
+        s.run_rate()
+        return out
+    # the rate model goes into the queue between the expansion's count launch and the read of that count
+    return _generate_unfused(s.camera, s.pc, s.anchor, s.feat, s.grid_scaling, s.grid_offsets, s.masks, K, between=s.run_rate,
+                             view=s.view, mlp_pre=s.mlp_pre)
+
+
+def _side_outputs(s, mask, rows, slots):
+    K = s.pc.n_offsets
+    if rows is not None:        # the visible anchor index once per offset, then through the expansion's selection mask
+        rows.append(s.vis_idx.repeat_interleave(K)[mask.reshape(-1)])
+    if slots is not None:       # a * K + k of every (visible anchor, offset), then through the same mask
+        ak = s.vis_idx.to(torch.int32)[:, None] * K + torch.arange(K, dtype=torch.int32, device=s.vis_idx.device)
+        slots.append(ak.reshape(-1)[mask.reshape(-1)])
+
+
 def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, step=0, _view=None,
                               _rows=None, _slots=None):   # :25-150
+    """The stages in launch order; a stage that does not belong to the plan's phase returns at once."""
     # _rows: a list that receives, for every Gaussian produced, the row of its anchor in pc.get_anchor (render(anchor_features=))
     # _slots: likewise, int32 a * K + k for offset k of anchor a (render(contrib=))
-    time_sub = 0
     if visible_mask is None:
         visible_mask = torch.ones(pc.get_anchor.shape[0], dtype=torch.bool, device=pc.get_anchor.device)
-
-    bit_per_param = bit_per_anchor_param = bit_per_feat_param = None
-    bit_per_scaling_param = bit_per_offsets_param = bpp_per_level = None
-
-    # the visible-anchor list is ENQUEUED first and read after everything below that does not need it (:44-50)
-    vis_pending = VisibleList(visible_mask) if visible_mask.is_cuda else None
-    full_anchor = pc.get_anchor                      # one Quantize_anchor launch per call (the reference re-derives
-    use_context = (is_training and step > 10000) or (not is_training and not pc.decoded_version)   # it ~5x)
-    begun = binary_all = mask_anchor_bool = rate_thunk = late_mask = scaling_all = None
-    if use_context:
-        # everything of the context model that does not depend on the visible set is enqueued BEFORE the read-back of
-        # the visible count below (the accessors, the step's bookkeeping kernel): the GPU works through it while the
-        # host waits, and the context model's own count read-back finds its data already there
-        late_mask = None
-        if (is_training and hasattr(pc, "get_mask_pair") and not pc.decoded_version and pc._mask.is_cuda and pc._mask.requires_grad
-                and torch.is_grad_enabled()):
-            # the mask VALUES now (the level plan needs the anchor mask), its autograd nodes after the level loop's
-            # (ctx_ops._MaskSTEAttach: `_mask`'s gradient is then final BEFORE the level kernels run in the backward)
-            from . import ctx_ops as _ctx_ops
-            binary_vals, mask_anchor_bool = _ctx_ops.mask_ste_values(pc._mask)
-            late_mask = {"vals": binary_vals, "node": None}
-
-            def binary_all():
-                if late_mask["node"] is None:
-                    late_mask["node"] = _ctx_ops.mask_ste_attach(pc._mask, late_mask["vals"])
-                return late_mask["node"]
-        elif hasattr(pc, "get_mask_pair"):
-            binary_all, mask_anchor_bool = pc.get_mask_pair()
-        else:                                   # the reference's own GaussianModel
-            binary_all = pc.get_mask
-            mask_anchor_bool = binary_all.detach().sum(dim=1)[:, 0] > 0
-        begun = begin_step(pc, full_anchor, mask_anchor_bool, is_training)
-        if begun is not None and is_training:
-            # the level kernels of the step's context model depend on nothing the host still has to read (not on the view either):
-            # they go into the queue here, 0.4 ms of device work behind which the read-backs below and the small launches between
-            # them disappear (context_model._early_levels)
-            from .context_model import early_levels_begin
-            scaling_all = pc.get_scaling
-            early_levels_begin(pc, full_anchor, pc._hyper_latent, pc._anchor_feat, pc._offset, scaling_all, mask_anchor_bool, begun)
-    # visible rows are distinct anchors: gather by index with a sort-free scatter backward (the reference's
-    # boolean-mask indexing, :44-50, backpropagates through index_put_(accumulate) = a device sort per tensor)
-    vis_idx = vis_pending.wait() if vis_pending is not None else torch.nonzero(visible_mask)[:, 0]
-    if is_training:
-        # multi-GPU: the per-anchor gradients of this view only reach the visible anchors unless the context model runs over all
-        # of them (dist.GradientSync(sparse="auto") exchanges the union of the ranks' rows instead of dense tensors)
-        from . import dist as _dist
-        _dist.note_touched_rows(None if use_context else visible_mask, int(vis_idx.shape[0]))
-    sel = lambda t: gather_unique(t, vis_idx)
-    anchor = sel(full_anchor)
-    early = begun.get("early") if begun is not None else None
-    if early is not None and is_training and EARLY_MLP3 and torch.is_grad_enabled():
-        # The three anchor MLPs of the view, enqueued NOW on the buffer the level kernels (already in the queue) are writing:
-        # their operands — the coded features in coding order, the visible anchors' rows of it, the camera — are all known here,
-        # and the host has ~0.3 ms of node creation in front of it (hyper step, three level nodes, the mask's node) during which
-        # the device would finish the level kernels and idle (profiles/r06_gpu_idle_gaps.txt).  The node is created later, by
-        # _generate_unfused, around this launch (mlp.anchor_mlp3_rows(pre=)); if the step turns out different (the plan was
-        # rebuilt, another expansion path), the launch is dropped and repeated there.
-        mo_, mc_, mv_ = pc.get_opacity_mlp, pc.get_color_mlp, pc.get_cov_mlp
-        if (mlp.anchor_mlp3_supported(mo_, mc_, mv_) and early["big"][0].shape[1] == 50
-                and not anchor_gen.supported(mo_, mc_, mv_, pc.n_offsets, full_anchor)):
-            from .context_model import _index_rows
-            pos_e = _index_rows(early["cache"]["inv_perm"], vis_idx)
-            begun["early_pos"] = (vis_idx, pos_e, early["cache"])      # (multi_scale_generating_visible hands the same rows on)
-            early["mlp3"] = mlp.anchor_mlp3_rows_launch(early["big"][0], pos_e, anchor.detach(), viewpoint_camera.camera_center,
-                                                        mo_, mc_, mv_)
-    if use_context:
-        # enqueued here, in front of the context model's count read-back: the host falls behind the device while it
-        # waits there, and a gather the device still has queued covers part of the catch-up
-        if late_mask is not None:
-            from .context_model import _index_rows
-            late_mask["vis_vals"] = _index_rows(late_mask["vals"], vis_idx)
-            binary_grid_masks = None
-        else:
-            binary_grid_masks = sel(binary_all)
-    if not use_context:
-        # raw features of the visible anchors: left as (source, rows) when nothing is added to them, so that the
-        # anchor-MLP kernel gathers them itself
-        plain = not (is_training and 3000 < step <= 10000)
-        feat = LazyRows(pc._anchor_feat, vis_idx) if (plain and pc._anchor_feat.is_cuda) else sel(pc._anchor_feat)
-        grid_offsets = sel(pc._offset)
-        grid_scaling = sel(pc.get_scaling)
-        binary_grid_masks = sel(pc.get_mask)
-        if is_training and 3000 < step <= 10000:                                        # :54-58
-            if feat.is_cuda and grid_offsets.dim() == 3:
-                # x + U(-1/2, 1/2) Q for the three tensors in ONE launch (the level kernel of the context model with a
-                # zero step-size adjustment: Q = q0 (1 + tanh 0) = q0) instead of three uniform_ / mul / add chains over
-                # [n,50], [n,6], [n,30]; the build's counter-based generator instead of torch's Philox stream (same
-                # distribution), backward = identity
-                from . import ctx_ops as _ctx
-                n_vis = feat.shape[0]
-                zero_adj = torch.zeros(n_vis, 3, dtype=torch.float32, device=feat.device)
-                off_flat = grid_offsets.reshape(n_vis, grid_offsets.shape[1] * grid_offsets.shape[2])    # (explicit: n_vis may be 0)
-                feat, grid_scaling, off2, _q = _ctx.noise_quant(feat, grid_scaling, off_flat, zero_adj,
-                                                                (Q_FEAT, Q_SCALING, Q_OFFSETS))
-                grid_offsets = off2.view(grid_offsets.shape)
-            else:
-                feat = feat + torch.empty_like(feat).uniform_(-0.5, 0.5) * Q_FEAT
-                grid_scaling = grid_scaling + torch.empty_like(grid_scaling).uniform_(-0.5, 0.5) * Q_SCALING
-                grid_offsets = grid_offsets + torch.empty_like(grid_offsets).uniform_(-0.5, 0.5) * Q_OFFSETS
-    if is_training and step == 10000:                                                   # :60-61
+    s = _ViewStep(viewpoint_camera, pc, _gen_plan(is_training, step, pc.decoded_version), is_training, visible_mask,
+                  _view if is_training else None)
+    # the visible-anchor list is ENQUEUED first and read after everything that does not need it (:44-50)
+    s.vis_pending = VisibleList(visible_mask) if visible_mask.is_cuda else None
+    s.full_anchor = pc.get_anchor       # one Quantize_anchor launch per call (the reference re-derives it ~5x)
+    _begin_context(s)
+    # visible rows are distinct anchors: gather by index with a sort-free scatter backward (the reference's boolean-mask
+    # indexing, :44-50, backpropagates through index_put_(accumulate) = a device sort per tensor)
+    s.vis_idx = s.vis_pending.wait() if s.vis_pending is not None else torch.nonzero(visible_mask)[:, 0]
+    _note_touched_rows(s)
+    s.anchor = gather_unique(s.full_anchor, s.vis_idx)
+    _launch_early_mlps(s)
+    _gather_mask_rows(s)
+    _gather_raw_inputs(s)
+    if s.plan.update_bound:                                                             # :60-61
         pc.update_anchor_bound()
-    if use_context:                                                                     # :63-81 (train) / :83-101 (eval)
-        # (get_mask_anchor, scene/gaussian_model.py:302-310, is "any offset alive" of the SAME mask values: both came
-        # from one evaluation above instead of running the sigmoid / threshold / STE chain twice)
-        res = multi_scale_generating_visible(pc, full_anchor, pc._hyper_latent, pc._anchor_feat, pc._offset,
-                                             scaling_all if scaling_all is not None else pc.get_scaling, binary_all,
-                                             mask_anchor_bool, vis_idx,
-                                             training=is_training, predict_bpp=is_training, defer_feat=True,
-                                             begun=begun, defer_rate=True)
-        feat, grid_scaling, grid_offsets = res[:3]
-        if is_training:
-            rate_thunk = res[3]         # the rate model (:1657-1707) is enqueued behind the expansion's count (see below)
-        if late_mask is not None:       # the level loop's nodes exist: now the mask's
-            from .context_model import gather_unique_attach, gather_unique_pair_attach
-            chosen = getattr(rate_thunk, "chosen_rows", None) if rate_thunk is not None else None
-            if chosen is not None and chosen.is_cuda:
-                # the visible rows (for the expansion) and the rate subset's rows of the mask weights through ONE node: one
-                # gradient buffer instead of two and the engine's add (context_model._GatherUniquePair)
-                binary_grid_masks, m_chosen = gather_unique_pair_attach(binary_all(), vis_idx, late_mask["vis_vals"], chosen)
-                rate_thunk = (lambda f, m: (lambda: f(m)))(rate_thunk, m_chosen)
-            else:
-                binary_grid_masks = gather_unique_attach(binary_all(), vis_idx, late_mask["vis_vals"])
-
-    K = pc.n_offsets
-    rate_out = []
-    run_rate = (lambda: rate_out.extend(rate_thunk())) if rate_thunk is not None else None
-    out = _generate_fused(viewpoint_camera, pc, anchor, feat, grid_scaling, grid_offsets, binary_grid_masks, K)
-    if out is None:
-        out = _generate_unfused(viewpoint_camera, pc, anchor, feat, grid_scaling, grid_offsets, binary_grid_masks, K,
-                                between=run_rate, view=_view if is_training else None,
-                                mlp_pre=early.get("mlp3") if early is not None else None)
-    elif run_rate is not None:
-        run_rate()
-    if rate_out:
-        bit_per_param, bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level = rate_out
-    xyz, color, opacity, scaling, rot, neural_opacity, mask = out
-    if _rows is not None:       # the visible anchor index once per offset, then through the expansion's selection mask
-        _rows.append(vis_idx.repeat_interleave(K)[mask.reshape(-1)])
-    if _slots is not None:      # a * K + k of every (visible anchor, offset), then through the same mask
-        ak = vis_idx.to(torch.int32)[:, None] * K + torch.arange(K, dtype=torch.int32, device=vis_idx.device)
-        _slots.append(ak.reshape(-1)[mask.reshape(-1)])
-
+    _run_context_model(s)
+    _attach_mask(s)
+    xyz, color, opacity, scaling, rot, neural_opacity, mask = _expand(s)
+    _side_outputs(s, mask, _rows, _slots)
     if is_training:                                                                      # :147-150
-        return (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, 16, bit_per_feat_param,
-                bit_per_scaling_param, bit_per_offsets_param, bpp_per_level)
-    return xyz, color, opacity, scaling, rot, time_sub
+        return (xyz, color, opacity, scaling, rot, neural_opacity, mask, s.rates[0], 16, *s.rates[1:])
+    return xyz, color, opacity, scaling, rot, 0
 
 
 class _ZeroPoints(torch.autograd.Function):
     """The reference's `screenspace_points` (gaussian_renderer/__init__.py:168: a zero [P,3] non-leaf tensor whose .grad
     receives the 2-D position gradients): a FRESH zero tensor per view, as in the reference — independent storage, so a caller
-    that writes into one view's tensor does not touch another's (rounds 3-4 handed every view a slice of one pooled zero
-    buffer, "read-only by contract") — wrapped in an autograd node so that it is a non-leaf tensor that requires
-    grad without the reference's `+ 0` launch.  One fill of 12 B per Gaussian per view ([P,4], 16 B, with render(absgrad=True))."""
+    that writes into one view's tensor does not touch another's — wrapped in an autograd node so that it is a non-leaf tensor
+    that requires grad without the reference's `+ 0` launch.  One fill of 12 B per Gaussian per view ([P,4], 16 B, with
+    render(absgrad=True))."""
 
     @staticmethod
     def forward(ctx, like, token, cols=3):
@@ -581,6 +608,14 @@ def _zero_points(xyz, cols=3):
     return _ZeroPoints.apply(xyz.detach(), tok, cols)
 
 
+def _retain_grad(points, wanted):
+    if wanted:
+        try:
+            points.retain_grad()
+        except Exception:
+            pass
+
+
 def _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier):
     return GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
@@ -589,6 +624,26 @@ def _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier):
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=1, campos=viewpoint_camera.camera_center,
         prefiltered=False, debug=bool(getattr(pipe, "debug", False)),
         antialiasing=bool(getattr(pipe, "antialiasing", False)))
+
+
+def _view_fusion(is_training, return_aux, return_geometry, antialiasing, cam_grad, anchor_features, contrib,
+                 raster_settings=None, retain_grad=False, absgrad=False, deterministic=False):
+    """The ViewFusion of a view that may take the fused expand + raster node, None of one that may not (render()'s docstring)."""
+    if (not is_training or return_aux or return_geometry or antialiasing or cam_grad or anchor_features is not None
+            or contrib is not None or not FUSE_VIEW or not torch.is_grad_enabled()):
+        return None
+    return ViewFusion(raster_settings, retain_grad, absgrad, deterministic)
+
+
+_RATE_KEYS = ("bit_per_param", "bit_per_anchor_param", "bit_per_feat_param", "bit_per_scaling_param", "bit_per_offsets_param",
+              "bpp_per_level")
+
+
+def _training_result(image, radii, points, scaling, rest):
+    """render()'s dict of a training call (:209-222); rest: what generate_neural_gaussians returns behind `rot`."""
+    neural_opacity, mask, *rates = rest
+    return {"render": image, "viewspace_points": points, "visibility_filter": radii > 0, "radii": radii,
+            "selection_mask": mask, "neural_opacity": neural_opacity, "scaling": scaling, **dict(zip(_RATE_KEYS, rates))}
 
 
 class _DetachedCamera:
@@ -653,7 +708,6 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     deterministic = check_deterministic(deterministic, return_aux, anchor_features, contrib, return_geometry)
     return_geometry = bool(return_geometry)
     is_training = pc.get_color_mlp.training
-    view = None
     cam_grad = torch.is_grad_enabled() and any(
         isinstance(t, torch.Tensor) and t.requires_grad for t in (
             viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center))
@@ -676,65 +730,41 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         slots = []
     else:
         contrib = None
-    if is_training:
-        # the expansion may run fused with the rasterizer's per-Gaussian stages (then `view.done` holds the rendered view
-        # and xyz / color / opacity / rot are None: they never existed as tensors)
-        view = ViewFusion(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier), retain_grad, absgrad,
-                          deterministic)
-        (xyz, color, opacity, scaling, rot, neural_opacity, mask, bit_per_param, bit_per_anchor_param,
-         bit_per_feat_param, bit_per_scaling_param, bit_per_offsets_param, bpp_per_level) = \
-            generate_neural_gaussians(gen_camera, pc, visible_mask, is_training=True, step=step,
-                                      _view=None if (return_aux or return_geometry or view.raster_settings.antialiasing
-                                                     or cam_grad or rows is not None or slots is not None) else view,
-                                      _rows=rows, _slots=slots)
-        if view.done is not None:
-            rendered_image, radii, screenspace_points = view.done
-            return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-                    "radii": radii, "selection_mask": mask, "neural_opacity": neural_opacity, "scaling": scaling,
-                    "bit_per_param": bit_per_param, "bit_per_anchor_param": bit_per_anchor_param,
-                    "bit_per_feat_param": bit_per_feat_param, "bit_per_scaling_param": bit_per_scaling_param,
-                    "bit_per_offsets_param": bit_per_offsets_param, "bpp_per_level": bpp_per_level}
-    else:
-        xyz, color, opacity, scaling, rot, time_sub = generate_neural_gaussians(
-            gen_camera, pc, visible_mask, is_training=False, step=step, _rows=rows, _slots=slots)
+    side = return_aux or return_geometry or rows is not None or slots is not None        # the rasterizer returns a third value
+    settings = _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier)
+    view = _view_fusion(is_training, return_aux, return_geometry, settings.antialiasing, cam_grad, anchor_features, contrib,
+                        settings, retain_grad, absgrad, deterministic)
+    xyz, color, opacity, scaling, rot, *rest = generate_neural_gaussians(
+        gen_camera, pc, visible_mask, is_training=is_training, step=step, _view=view, _rows=rows, _slots=slots)
+    if view is not None and view.done is not None:
+        # (xyz / color / opacity / rot are None: they never existed as tensors)
+        return _training_result(*view.done, scaling, rest)
 
     screenspace_points = _zero_points(xyz, 4 if absgrad else 3)       # :168 `torch.zeros_like(xyz, requires_grad=True) + 0`
-    if retain_grad:
-        try:
-            screenspace_points.retain_grad()
-        except Exception:
-            pass
-
-    rasterizer = GaussianRasterizer(_raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier))
-    abs_kw = dict(absgrad=True) if absgrad else {}
-    abs_kw.update(deterministic=deterministic)      # (resolved above: the rasterizer does not read the environment again)
-    if return_aux or return_geometry or rows is not None or slots is not None:
-        features = anchor_features.index_select(0, rows[0]) if rows is not None else None      # plumbing: plain torch
-        more = dict(contrib=contrib, contrib_slots=slots[0]) if slots is not None else {}
-        more.update(abs_kw)
+    _retain_grad(screenspace_points, retain_grad)
+    rasterizer = GaussianRasterizer(settings)
+    more = dict(absgrad=True) if absgrad else {}
+    more.update(deterministic=deterministic)      # (resolved above: the rasterizer does not read the environment again)
+    if side:
+        if slots is not None:
+            more.update(contrib=contrib, contrib_slots=slots[0])
         if return_geometry:
             more.update(return_geometry=True)
-        rendered_image, radii, aux = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
-                                                opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None,
-                                                features=features, return_aux=return_aux, **more)
-        if slots is not None:       # a Gaussian index means nothing outside this call: one gather to slot ids, -1 kept
-            tid = aux["top_id"].long()
-            table = torch.cat([slots[0], slots[0].new_full((1,), -1)])      # (index -1 reads the appended -1)
-            aux["top_id"] = table[tid]
-    else:
-        rendered_image, radii = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
-                                           opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None, **abs_kw)
+        more.update(features=anchor_features.index_select(0, rows[0]) if rows is not None else None,      # plumbing: plain torch
+                    return_aux=return_aux)
+    rendered_image, radii, *aux = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
+                                             opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None, **more)
+    if slots is not None:       # a Gaussian index means nothing outside this call: one gather to slot ids, -1 kept
+        tid = aux[0]["top_id"].long()
+        table = torch.cat([slots[0], slots[0].new_full((1,), -1)])      # (index -1 reads the appended -1)
+        aux[0]["top_id"] = table[tid]
     if is_training:
-        out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-               "radii": radii, "selection_mask": mask, "neural_opacity": neural_opacity, "scaling": scaling,
-               "bit_per_param": bit_per_param, "bit_per_anchor_param": bit_per_anchor_param,
-               "bit_per_feat_param": bit_per_feat_param, "bit_per_scaling_param": bit_per_scaling_param,
-               "bit_per_offsets_param": bit_per_offsets_param, "bpp_per_level": bpp_per_level}
+        out = _training_result(rendered_image, radii, screenspace_points, scaling, rest)
     else:
         out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-               "radii": radii, "time_sub": time_sub}
-    if return_aux or return_geometry or rows is not None or slots is not None:
-        out.update(aux)
+               "radii": radii, "time_sub": rest[0]}
+    if side:
+        out.update(aux[0])
     return out
 
 
