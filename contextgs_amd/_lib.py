@@ -115,6 +115,13 @@ SIGNATURES = {
     "cgs_raster_camera_backward": (c_int, [C.POINTER(RasterCfg), c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, C.c_uint32,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # normal maps (csrc/normal_maps.hip): cfg, P, means3D, scales, rotations | H, W, tanfovx, tanfovy, eps
+    "cgs_gaussian_normals_fwd": (c_int, [C.POINTER(RasterCfg), c_int64] + [c_void_p] * 5),
+    "cgs_gaussian_normals_bwd": (c_int, [C.POINTER(RasterCfg), c_int64] + [c_void_p] * 6),
+    "cgs_depth_normals_fwd": (c_int, [c_int32, c_int32, c_float, c_float, c_float] + [c_void_p] * 3),
+    "cgs_depth_normals_bwd": (c_int, [c_int32, c_int32, c_float, c_float, c_float] + [c_void_p] * 4),
+    "cgs_normal_consistency_fwd": (c_int, [c_int32, c_int32, c_float, c_float, c_float] + [c_void_p] * 5),
+    "cgs_normal_consistency_bwd": (c_int, [c_int32, c_int32, c_float, c_float, c_float] + [c_void_p] * 7),
     "cgs_filter_cov": (c_int,[C.POINTER(RasterCfg), c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cgs_raster_preprocess_wait": (c_int, [C.c_uint64, C.POINTER(c_int64)]),
     "cgs_raster_preprocess_wait2": (c_int, [C.c_uint64, C.POINTER(c_int64), C.POINTER(c_int)]),

@@ -1121,3 +1121,98 @@ extern "C" int cgs_raster_stats(const cgs_raster_cfg *cfg, void *img_ws, size_t 
     }
     return cgs_launch_stats(cfg, im, stats_out, (hipStream_t)stream);
 }
+
+// ---- normal maps and the normal-consistency regulariser (csrc/normal_maps.hip) ------------------------------------------------
+int cgs_launch_gaussian_normals_fwd(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *scales,
+                                    const float *rotations, float *out, hipStream_t stream);
+int cgs_launch_gaussian_normals_bwd(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *scales,
+                                    const float *rotations, const float *dL_dout, float *dL_drotations, hipStream_t stream);
+int cgs_launch_depth_normals_fwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps, const float *depth, float *out,
+                                 hipStream_t stream);
+int cgs_launch_depth_normals_bwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps, const float *depth,
+                                 const float *dL_dout, float *dL_ddepth, hipStream_t stream);
+int cgs_launch_normal_consistency_fwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps, const float *normals,
+                                      const float *depth, const float *weight, float *out, hipStream_t stream);
+int cgs_launch_normal_consistency_bwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps, const float *normals,
+                                      const float *depth, const float *weight, const float *dL_dE, float *dL_dnormals,
+                                      float *dL_ddepth, hipStream_t stream);
+
+// The per-Gaussian entry points read cfg->viewmatrix only.  P == 0: CGS_OK, nothing enqueued, no pointer looked at.
+static int check_gaussian_normals(const char *fn, const cgs_raster_cfg *cfg, int64_t P) {
+    if (!cfg) { cgs_set_error("%s: cfg is NULL", fn); return CGS_ERR_ARG; }
+    if (P < 0) { cgs_set_error("%s: P < 0", fn); return CGS_ERR_ARG; }
+    if (P >= (1ll << 31) * 256) { cgs_set_error("%s: P = %lld is beyond one launch", fn, (long long)P); return CGS_ERR_ARG; }
+    if (!cfg->viewmatrix) { cgs_set_error("%s: cfg->viewmatrix is NULL", fn); return CGS_ERR_ARG; }
+    return CGS_OK;
+}
+
+extern "C" int cgs_gaussian_normals_fwd(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *scales,
+                                        const float *rotations, float *out_normals, void *stream) {
+    const char *fn = "cgs_gaussian_normals_fwd";
+    int rc = check_gaussian_normals(fn, cfg, P);
+    if (rc) return rc;
+    if (P > 0 && (!means3D || !scales || !rotations || !out_normals)) { cgs_set_error("%s: NULL input or output", fn); return CGS_ERR_ARG; }
+    return cgs_launch_gaussian_normals_fwd(cfg, P, means3D, scales, rotations, out_normals, (hipStream_t)stream);
+}
+
+extern "C" int cgs_gaussian_normals_bwd(const cgs_raster_cfg *cfg, int64_t P, const float *means3D, const float *scales,
+                                        const float *rotations, const float *dL_dnormals, float *dL_drotations, void *stream) {
+    const char *fn = "cgs_gaussian_normals_bwd";
+    int rc = check_gaussian_normals(fn, cfg, P);
+    if (rc) return rc;
+    if (P > 0 && (!means3D || !scales || !rotations || !dL_dnormals || !dL_drotations)) {
+        cgs_set_error("%s: NULL input or output", fn);
+        return CGS_ERR_ARG;
+    }
+    return cgs_launch_gaussian_normals_bwd(cfg, P, means3D, scales, rotations, dL_dnormals, dL_drotations, (hipStream_t)stream);
+}
+
+// The per-pixel entry points take the five numbers they read instead of a cgs_raster_cfg.
+static int check_normal_view(const char *fn, int32_t H, int32_t W, float tanfovx, float tanfovy, float eps) {
+    if (H < 1 || W < 1 || H > 65535 || W > 65535) { cgs_set_error("%s: image size %dx%d outside 1..65535", fn, W, H); return CGS_ERR_ARG; }
+    if (!(tanfovx > 0.f) || !(tanfovy > 0.f) || !(tanfovx < 1e30f) || !(tanfovy < 1e30f)) {
+        cgs_set_error("%s: tanfovx, tanfovy = %g, %g must be positive and finite", fn, (double)tanfovx, (double)tanfovy);
+        return CGS_ERR_ARG;
+    }
+    if (!(eps >= 0.f) || !(eps < 1e30f)) { cgs_set_error("%s: eps = %g must be >= 0 and finite", fn, (double)eps); return CGS_ERR_ARG; }
+    return CGS_OK;
+}
+
+extern "C" int cgs_depth_normals_fwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps, const float *depth,
+                                     float *out_normals, void *stream) {
+    const char *fn = "cgs_depth_normals_fwd";
+    int rc = check_normal_view(fn, H, W, tanfovx, tanfovy, eps);
+    if (rc) return rc;
+    if (!depth || !out_normals) { cgs_set_error("%s: NULL input or output", fn); return CGS_ERR_ARG; }
+    return cgs_launch_depth_normals_fwd(H, W, tanfovx, tanfovy, eps, depth, out_normals, (hipStream_t)stream);
+}
+
+extern "C" int cgs_depth_normals_bwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps, const float *depth,
+                                     const float *dL_dnormals, float *dL_ddepth, void *stream) {
+    const char *fn = "cgs_depth_normals_bwd";
+    int rc = check_normal_view(fn, H, W, tanfovx, tanfovy, eps);
+    if (rc) return rc;
+    if (!depth || !dL_dnormals || !dL_ddepth) { cgs_set_error("%s: NULL input or output", fn); return CGS_ERR_ARG; }
+    return cgs_launch_depth_normals_bwd(H, W, tanfovx, tanfovy, eps, depth, dL_dnormals, dL_ddepth, (hipStream_t)stream);
+}
+
+extern "C" int cgs_normal_consistency_fwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps, const float *normals,
+                                          const float *depth, const float *weight, float *out_error, void *stream) {
+    const char *fn = "cgs_normal_consistency_fwd";
+    int rc = check_normal_view(fn, H, W, tanfovx, tanfovy, eps);
+    if (rc) return rc;
+    if (!normals || !depth || !out_error) { cgs_set_error("%s: NULL input or output (only weight may be NULL)", fn); return CGS_ERR_ARG; }
+    return cgs_launch_normal_consistency_fwd(H, W, tanfovx, tanfovy, eps, normals, depth, weight, out_error, (hipStream_t)stream);
+}
+
+extern "C" int cgs_normal_consistency_bwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps, const float *normals,
+                                          const float *depth, const float *weight, const float *dL_derror, float *dL_dnormals,
+                                          float *dL_ddepth, void *stream) {
+    const char *fn = "cgs_normal_consistency_bwd";
+    int rc = check_normal_view(fn, H, W, tanfovx, tanfovy, eps);
+    if (rc) return rc;
+    if (!normals || !depth || !dL_derror) { cgs_set_error("%s: NULL input (only weight may be NULL)", fn); return CGS_ERR_ARG; }
+    if (!dL_dnormals && !dL_ddepth) { cgs_set_error("%s: no output given (dL_dnormals and dL_ddepth are both NULL)", fn); return CGS_ERR_ARG; }
+    return cgs_launch_normal_consistency_bwd(H, W, tanfovx, tanfovy, eps, normals, depth, weight, dL_derror, dL_dnormals, dL_ddepth,
+                                             (hipStream_t)stream);
+}

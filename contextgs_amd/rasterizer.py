@@ -157,6 +157,24 @@ maps got a gradient; when neither did, no geometry backward kernel runs and the 
 keyword.  Float atomics like the other side passes: not bit-reproducible.  Without the keyword the call enqueues exactly what it
 did before.
 
+`forward(..., return_normals=True)` returns the rendered normal map, `extras["normals"]` float32 [3,H,W]:
+
+  normals[c, p] = sum_i w_i n_i[c]
+
+over the colour blend's own contributors and weights and a zero background, with n_i = gaussian_normals(means3D, scales,
+rotations, raster_settings)[i] (contextgs_amd/normals.py, csrc/normal_maps.hip): the axis of Gaussian i's smallest scale, from
+the NORMALISED quaternion, in CAMERA space (the view space of `viewmatrix`: x right, y down, z forward) and turned AWAY from
+the camera (n_i . t_i >= 0), the hemisphere of the reference's computeNormalsFromPosCam_Batched and of
+normals.depth_normals, the opposite of 2DGS's convention.  The map is not normalised: its length is at most alpha; divide by
+alpha for a unit-ish normal.  The three columns are appended to the feature matrix of the feature walk above and split off
+its output: no second blend kernel runs.  Gradients flow as for `features` (means2D, opacities, means3D, scales, rotations
+through the weights), plus gaussian_normals' own backward into `rotations`.  The keyword combines with return_aux,
+return_geometry, contrib, absgrad, antialiasing, SH colours and user `features` of at most CGS_RASTER_MAX_FEATURES - 3 = 29
+columns.  ValueError before a device is touched: cov3D_precomp (no axes to read), more than 29 feature columns,
+deterministic=True (as for `features`), and a `viewmatrix` that requires a gradient (n_i's own dependence on the camera is not
+differentiated; a silently partial camera gradient is worse than a refusal).  Without the keyword the call enqueues exactly
+what it did before.  normals.normal_consistency(extras["normals"], depth, raster_settings, weight=alpha) is the regulariser.
+
 `forward(..., deterministic=True)` makes the backward bit-reproducible.  The forward already is (no atomics in the blend, a
 stable depth sort, binnings that leave the same lists); the default backward sums every Gaussian's partial gradients with float
 atomics, in LDS inside a tile and in global memory across tiles, in the order of arrival.  With the flag the backward is
@@ -167,7 +185,7 @@ Gaussian's slots in an order that depends on its tile count only.  Every gradien
 from call to call for the same input bits, library build and device model, whichever binning ran, with or without pair-count
 speculation, whatever else the device does; the values are the default backward's up to the order of the sums.  All four
 argument forms, antialiasing, absgrad and camera gradients are covered; the forward is untouched.  NOT covered, and refused with
-ValueError before a device is touched: return_aux, features, contrib and return_geometry (the map, feature and geometry blends'
+ValueError before a device is touched: return_aux, features, contrib, return_normals and return_geometry (the map, feature and geometry blends'
 backward and GaussianContrib.weight are separate kernels that sum with float atomics).  `deterministic=None` (the default) reads the
 environment variable CGS_RASTER_DETERMINISTIC (1 = on), so that a training script that never heard of the keyword can be
 switched; without the flag the call enqueues exactly what it did before.  The mode costs a workspace of 48 bytes per
@@ -370,7 +388,8 @@ def check_absgrad(means2D, absgrad, P) -> None:
         raise ValueError(f"means2D is {shape}: four columns are the layout of absgrad=True, which was not given")
 
 
-def check_deterministic(deterministic, return_aux=False, features=None, contrib=None, return_geometry=False) -> bool:
+def check_deterministic(deterministic, return_aux=False, features=None, contrib=None, return_geometry=False,
+                        return_normals=False) -> bool:
     """The resolved `deterministic` flag (None: the environment variable CGS_RASTER_DETERMINISTIC, 1 = on).  With the flag on,
     the keywords whose backward or accumulation still sums with float atomics are refused; no device is touched.  With the flag
     off nothing is checked."""
@@ -386,7 +405,26 @@ def check_deterministic(deterministic, return_aux=False, features=None, contrib=
     if return_geometry:
         raise ValueError("deterministic=True does not cover return_geometry: the distortion / median-depth blend's backward sums "
                          "with float atomics (not covered: return_aux, features, contrib, return_geometry)")
+    if return_normals:
+        raise ValueError("deterministic=True does not cover return_normals: the normal map is three more columns of the feature "
+                         "blend, whose backward sums with float atomics (not covered: return_aux, features, contrib, "
+                         "return_geometry, return_normals)")
     return True
+
+
+def check_normals(return_normals, features, cov3D_precomp, viewmatrix) -> None:
+    """Rules of `return_normals`, on shapes and flags only: no device is touched."""
+    if not return_normals:
+        return
+    if cov3D_precomp is not None:
+        raise ValueError("return_normals=True needs scales and rotations: a cov3D_precomp has no axes to read a normal from")
+    if features is not None and features.shape[1] > CGS_RASTER_MAX_FEATURES - 3:
+        raise ValueError(f"return_normals=True takes three of the {CGS_RASTER_MAX_FEATURES} feature channels: features has "
+                         f"{features.shape[1]} columns, more than {CGS_RASTER_MAX_FEATURES - 3}")
+    if isinstance(viewmatrix, torch.Tensor) and viewmatrix.requires_grad:
+        raise ValueError("return_normals=True with a viewmatrix that requires a gradient: the normals' own dependence on the "
+                         "camera is not differentiated, and a silently partial camera gradient is worse than a refusal "
+                         "(pass viewmatrix.detach(), or render the normals in a second call)")
 
 
 class GaussianContrib:
@@ -711,18 +749,26 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, features=None, return_aux=False, contrib=None, contrib_slots=None, absgrad=False,
-                deterministic=None, return_geometry=False):
+                deterministic=None, return_geometry=False, return_normals=False):
         """(color [3,H,W], radii int32 [P]); with return_aux=True, features [P,C] and / or contrib a third value, the dict of
         {"depth", "invdepth", "alpha"}, float32 [1,H,W] each, {"features"}, float32 [C,H,W], and / or {"contrib", "top_id",
         "top_weight", "count"} (see the module docstring).  absgrad=True: means2D is [P,4] and its gradient's columns 2:4 are
         the sums over the pixels of the absolute per-pixel gradients of the colour image (module docstring).
         deterministic=True (None: CGS_RASTER_DETERMINISTIC=1): a bit-reproducible backward without float atomics; not with
         return_aux, features, contrib or return_geometry (module docstring).  return_geometry=True: the dict gains
-        {"distortion", "median_depth"}, float32 [1,H,W], and {"median_id"}, int32 [H,W] (module docstring)."""
-        deterministic = check_deterministic(deterministic, return_aux, features, contrib, return_geometry)
+        {"distortion", "median_depth"}, float32 [1,H,W], and {"median_id"}, int32 [H,W] (module docstring).
+        return_normals=True: the dict gains {"normals"}, float32 [3,H,W], the blend of the Gaussians' camera-space normals
+        (module docstring); scales / rotations only, not with deterministic=True or a viewmatrix that requires a gradient."""
+        deterministic = check_deterministic(deterministic, return_aux, features, contrib, return_geometry, return_normals)
         check_forms(shs, colors_precomp, scales, rotations, cov3D_precomp, self.raster_settings.sh_degree)
         check_absgrad(means2D, absgrad, means3D.shape[0])
         check_features(features, means3D.shape[0])
+        check_normals(return_normals, features, cov3D_precomp, self.raster_settings.viewmatrix)
+        user_features = features
+        if return_normals:      # three more columns of the ONE feature walk: no second blend
+            from .normals import gaussian_normals      # (here, not at the top: normals.py imports _Cfg and _f32c from this module)
+            nrm = gaussian_normals(means3D, scales, rotations, self.raster_settings)
+            features = nrm if features is None else torch.cat([features.to(nrm.dtype), nrm], dim=1)
         if contrib is False:
             contrib = None
         check_contrib(contrib, contrib_slots, means3D)
@@ -744,6 +790,8 @@ class GaussianRasterizer(nn.Module):
         if return_geometry:
             k = 2 + (3 if return_aux else 0) + (3 if contrib is not None else 0)
             extras.update(distortion=out[k], median_depth=out[k + 1], median_id=out[k + 2])
-        if features is not None:
-            extras["features"] = out[-1]
+        if user_features is not None:
+            extras["features"] = out[-1][:-3] if return_normals else out[-1]
+        if return_normals:
+            extras["normals"] = out[-1][-3:]
         return out[0], out[1], extras

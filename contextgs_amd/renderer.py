@@ -627,10 +627,10 @@ def _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier):
 
 
 def _view_fusion(is_training, return_aux, return_geometry, antialiasing, cam_grad, anchor_features, contrib,
-                 raster_settings=None, retain_grad=False, absgrad=False, deterministic=False):
+                 raster_settings=None, retain_grad=False, absgrad=False, deterministic=False, return_normals=False):
     """The ViewFusion of a view that may take the fused expand + raster node, None of one that may not (render()'s docstring)."""
-    if (not is_training or return_aux or return_geometry or antialiasing or cam_grad or anchor_features is not None
-            or contrib is not None or not FUSE_VIEW or not torch.is_grad_enabled()):
+    if (not is_training or return_aux or return_geometry or return_normals or antialiasing or cam_grad
+            or anchor_features is not None or contrib is not None or not FUSE_VIEW or not torch.is_grad_enabled()):
         return None
     return ViewFusion(raster_settings, retain_grad, absgrad, deterministic)
 
@@ -662,7 +662,7 @@ class _DetachedCamera:
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False,
            step=0, *, return_aux=False, anchor_features=None, contrib=None, absgrad=False, deterministic=None,
-           return_geometry=False):   # :155-229
+           return_geometry=False, return_normals=False):   # :155-229
     """Render the scene.  Background tensor (bg_color) must be on the GPU.
 
     return_aux=True: the dict also holds the rasterizer's "depth", "invdepth" and "alpha" maps ([1,H,W] each, see
@@ -687,6 +687,12 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     (rasterizer.py has the definitions and the gradients).  In training mode such a call takes the unfused path, as return_aux
     does.
 
+    return_normals=True: the dict also holds "normals" [3,H,W], the rasterizer's blend of the neural Gaussians' camera-space
+    normals (the axis of each one's smallest scale, turned away from the camera; rasterizer.py and normals.py have the
+    definition), for normals.normal_consistency.  It takes three of the 32 feature channels, so it composes with
+    `anchor_features` of at most 29 columns.  In training mode such a call takes the unfused path, as anchor_features does; not
+    with a camera whose world_view_transform requires a gradient (ValueError).
+
     absgrad=True: "viewspace_points" is created [P,4] and its gradient holds the signed 2-D position gradient in columns 0:2,
     as without the flag, and in columns 2:4 the sums over the pixels of the ABSOLUTE per-pixel gradients of the colour image
     (AbsGS's densification statistic; contextgs_amd/rasterizer.py has the definition and what it excludes).  Training-mode
@@ -697,7 +703,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     without float atomics and its gradients are bit-reproducible (contextgs_amd/rasterizer.py has the contract).  Training-mode
     calls stay on the fused expand + raster node, whose backward launch is then cgs_raster_backward_det; every other path hands
     the keyword to the rasterizer; fused and unfused give the same bits.  Not covered, ValueError before a device is touched:
-    return_aux, anchor_features, contrib, return_geometry.  The rasterizer's gradients only: other launches of a training step still sum with
+    return_aux, anchor_features, contrib, return_geometry, return_normals.  The rasterizer's gradients only: other launches of a training step still sum with
     float atomics (DESIGN.md section 8 lists them).
 
     A camera whose `world_view_transform`, `full_proj_transform` or `camera_center` requires a gradient (a trainable pose,
@@ -705,8 +711,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     tensors through the rasterizer (rasterizer.py: the projection, the covariance chain, the depth of the maps).  Not
     differentiated with respect to the camera: the anchor MLPs' input (anchor - camera_center), which is evaluated on the
     detached position, and the fused expand + raster node, which such a call never takes."""
-    deterministic = check_deterministic(deterministic, return_aux, anchor_features, contrib, return_geometry)
-    return_geometry = bool(return_geometry)
+    deterministic = check_deterministic(deterministic, return_aux, anchor_features, contrib, return_geometry, return_normals)
+    return_geometry, return_normals = bool(return_geometry), bool(return_normals)
     is_training = pc.get_color_mlp.training
     cam_grad = torch.is_grad_enabled() and any(
         isinstance(t, torch.Tensor) and t.requires_grad for t in (
@@ -730,10 +736,10 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         slots = []
     else:
         contrib = None
-    side = return_aux or return_geometry or rows is not None or slots is not None        # the rasterizer returns a third value
+    side = return_aux or return_geometry or return_normals or rows is not None or slots is not None   # the rasterizer returns a third value
     settings = _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier)
     view = _view_fusion(is_training, return_aux, return_geometry, settings.antialiasing, cam_grad, anchor_features, contrib,
-                        settings, retain_grad, absgrad, deterministic)
+                        settings, retain_grad, absgrad, deterministic, return_normals)
     xyz, color, opacity, scaling, rot, *rest = generate_neural_gaussians(
         gen_camera, pc, visible_mask, is_training=is_training, step=step, _view=view, _rows=rows, _slots=slots)
     if view is not None and view.done is not None:
@@ -750,6 +756,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
             more.update(contrib=contrib, contrib_slots=slots[0])
         if return_geometry:
             more.update(return_geometry=True)
+        if return_normals:
+            more.update(return_normals=True)
         more.update(features=anchor_features.index_select(0, rows[0]) if rows is not None else None,      # plumbing: plain torch
                     return_aux=return_aux)
     rendered_image, radii, *aux = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,

@@ -580,6 +580,63 @@ int cgs_raster_camera_backward(const cgs_raster_cfg *cfg, int64_t P,
                                float *dL_dcampos, void *work, size_t work_bytes,
                                void *stream);
 
+/* ---- normal maps and the normal-consistency regulariser (csrc/normal_maps.hip) ----
+ * Everything is in CAMERA space, the view space of cfg->viewmatrix V in the row-vector convention: t = [x y z 1] V, x right,
+ * y down, z forward.  Normals point AWAY from the camera (n . t >= 0), the hemisphere of the reference's
+ * utils/visualize_utils.py computeNormalsFromPosCam_Batched: a fronto-parallel plane has the normal (0, 0, +1).  This is the
+ * opposite of 2DGS's convention; what counts is that the two normals below agree with each other.
+ *
+ * Per-Gaussian normals, cgs_gaussian_normals_fwd: out_normals [P, 3].  For Gaussian i
+ *   k   = the index of the smallest of scales[i, 0..2], ties to the lowest index (cfg->scale_modifier does not matter);
+ *   n_w = column k of R(q / |q|), R as the rasterizer builds it from (r, x, y, z); the quaternion is normalised HERE (the
+ *         rasterizer uses it as given), so the result has unit length; the zero quaternion reads as the identity;
+ *   n_v = n_w V[:3,:3];   t = [means3D[i], 1] V;   out = s n_v with s = +1 if n_v . t >= 0, else -1.
+ * cgs_gaussian_normals_bwd: dL_drotations [P, 4] from dL_dnormals [P, 3], through the column and through q / |q|:
+ *   dL/dq = (g - q^ (q^ . g)) / |q|, g = dL/dq^ of s V[:3,:3] dL_dnormals.  Every row is written; one thread owns a row (no
+ * atomics).  Nothing else gets a gradient: scales only pick k, means3D only picks s, the camera is a constant.
+ * Only cfg->viewmatrix (and cfg->debug) is read.  P == 0: CGS_OK, nothing enqueued.  CGS_ERR_ARG with a message that names
+ * the function: cfg NULL, cfg->viewmatrix NULL, P < 0, a NULL input or output with P > 0.
+ *
+ * Normals of a depth map, cgs_depth_normals_fwd: out_normals [3, H, W] from depth [H, W].  With fx = W / (2 tanfovx),
+ * fy = H / (2 tanfovy), integer pixel coordinates (u, v) and the principal point (W/2, H/2):
+ *   p(v, u) = (d (u - W/2) / fx, d (v - H/2) / fy, d),   d = depth[v, u],   rows and columns replicated at the edges;
+ *   d0 = p(v+1, u) - p(v-1, u),   d1 = p(v, u+1) - p(v, u-1),   n = d0 x d1,   N = -n / (|n| + eps).
+ * Where |n| + eps = 0, N = 0; where |n| = 0 the gradient through the norm is 0 (undrawn regions, an image one pixel wide or
+ * high).  eps = 1e-5 is the reference's visualisation constant; eps = 0 gives unit normals.
+ * cgs_depth_normals_bwd: dL_ddepth [H, W] from dL_dnormals [3, H, W], as a gather: each pixel sums, in a fixed order, the
+ * shares of the (up to four) neighbouring stencils and replicated copies that read it, recomputing their cross products:
+ *   dL/dn = -G / (|n| + eps) + n (G . n) / (|n| (|n| + eps)^2),   dL/dd0 = d1 x dL/dn,   dL/dd1 = dL/dn x d0,
+ *   dL/dd = dL/dp . ((u - W/2) / fx, (v - H/2) / fy, 1).   No atomics: bit-reproducible.
+ *
+ * The fused regulariser, cgs_normal_consistency_fwd: out_error [H, W],
+ *   E = 1 - m sum_c normals[c] N[c],
+ * normals [3, H, W] any map (the rendered normal map), N the depth normals above computed on the fly and never stored, m the
+ * optional weight [H, W] (NULL: 1), which is not differentiated.  cgs_normal_consistency_bwd: from dL_derror [H, W],
+ *   dL_dnormals [3, H, W] = -m dL_derror N   and   dL_ddepth [H, W] by the gather above with G = -m dL_derror normals.
+ * Either of the two may be NULL (not computed), not both.
+ *
+ * The four per-pixel entry points take H, W, tanfovx, tanfovy and eps instead of a cgs_raster_cfg.  CGS_ERR_ARG with a message
+ * that names the function: H or W outside 1..65535, tanfovx or tanfovy not positive and finite, eps negative or not finite, a
+ * NULL pointer other than weight (and than one of cgs_normal_consistency_bwd's two outputs). */
+int cgs_gaussian_normals_fwd(const cgs_raster_cfg *cfg, int64_t P, const float *means3D,
+                             const float *scales, const float *rotations,
+                             float *out_normals, void *stream);
+int cgs_gaussian_normals_bwd(const cgs_raster_cfg *cfg, int64_t P, const float *means3D,
+                             const float *scales, const float *rotations,
+                             const float *dL_dnormals, float *dL_drotations, void *stream);
+int cgs_depth_normals_fwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps,
+                          const float *depth, float *out_normals, void *stream);
+int cgs_depth_normals_bwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps,
+                          const float *depth, const float *dL_dnormals, float *dL_ddepth,
+                          void *stream);
+int cgs_normal_consistency_fwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps,
+                               const float *normals, const float *depth, const float *weight,
+                               float *out_error, void *stream);
+int cgs_normal_consistency_bwd(int32_t H, int32_t W, float tanfovx, float tanfovy, float eps,
+                               const float *normals, const float *depth, const float *weight,
+                               const float *dL_derror, float *dL_dnormals, float *dL_ddepth,
+                               void *stream);
+
 /* ---- the anchor expansion fused with the rasterizer's preprocess stage (csrc/expand_raster.hip) ----
  * Training path of render(): gaussian_renderer/__init__.py:130-145 (generate_neural_gaussians' tail) feeding :179-205.
  * cgs_raster_preprocess_expand_launch = cgs_raster_preprocess_launch whose Gaussians are the surviving slots of

@@ -1,0 +1,407 @@
+"""GPU checks of the normal maps and the normal-consistency regulariser (csrc/normal_maps.hip, contextgs_amd/normals.py,
+`return_normals=True`) against the fp64 restatement of tests/normals_ref.py.
+
+Inputs are those of tests/normals_ref.py (pixel_inputs, gaussian_inputs, plane_scene): tests/test_normals.py runs the fp32
+restatement against the fp64 one on exactly them at HALF of every cap below, and the hemisphere scene on the raster oracle, so
+the caps are conditions, not measurements.  Tolerances (the project's own, copies of tests/test_raster_geom_gpu.py): maps, RMSE
+<= 1e-5 of the map's maximum and at most a 1e-4 share of values beyond 2e-5; gradients, at most a 2e-3 share of entries beyond
+2e-4 of the tensor's maximum.  Per-Gaussian rows whose fp64 |n^ . t^| < 1e-4 (the sign could fall either way) are left out of
+the comparison, at most 1 % of the rows.  References are computed once and shared; nobody writes into them."""
+import functools
+import itertools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import normals_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+TX, TY = ref.TAN
+BG = (0.1, 0.25, 0.4)
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _cu(a, grad=False):
+    return torch.tensor(a, device="cuda", requires_grad=grad)
+
+
+def _settings(H, W, tanfovx=TX, tanfovy=TY, view=None, proj=None, aa=False):
+    from contextgs_amd.rasterizer import GaussianRasterizationSettings
+    eye = torch.eye(4, device="cuda")
+    return GaussianRasterizationSettings(
+        image_height=H, image_width=W, tanfovx=tanfovx, tanfovy=tanfovy, bg=torch.tensor(BG, dtype=torch.float32, device="cuda"),
+        scale_modifier=1.0, viewmatrix=eye if view is None else view, projmatrix=eye if proj is None else proj, sh_degree=1,
+        campos=torch.zeros(3, device="cuda"), prefiltered=False, debug=False, antialiasing=aa)
+
+
+def _cam_settings(cam, aa=False):
+    c = cam.to_torch("cuda")
+    rs = _settings(cam.image_height, cam.image_width, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5),
+                   c.world_view_transform, c.full_proj_transform, aa)
+    return rs._replace(campos=c.camera_center)
+
+
+# ---- (1) per-Gaussian normals ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("P", [0, 1, 200, 257])
+def test_gaussian_normals_match_fp64(P):
+    from contextgs_amd.normals import gaussian_normals
+    V = ref.view_matrix()
+    x = ref.gaussian_inputs(P, seed=P)
+    rs = _settings(24, 40, view=_cu(V))
+    m, s, q = _cu(x["means3D"], True), _cu(x["scales"], True), _cu(x["rotations"], True)
+    n = gaussian_normals(m, s, q, rs)
+    assert n.shape == (P, 3) and n.dtype == torch.float32
+    (n * _cu(x["g"])).sum().backward()
+    torch.cuda.synchronize()
+    assert m.grad is None and s.grad is None and q.grad.shape == (P, 4)       # the gradient reaches the rotations only
+    if P == 0:
+        return
+    want = ref.gaussian_normals(x["means3D"], x["scales"], x["rotations"], V)
+    ok = want["margin"] >= 1e-4
+    print(f"[allowance] P = {P}: {int((~ok).sum())} rows within 1e-4 of a sign change")
+    assert (~ok).sum() <= 0.01 * P
+    assert torch.isfinite(n).all() and torch.isfinite(q.grad).all()
+    assert float((n.detach().norm(dim=1) - 1).abs().max()) < 1e-5                    # quaternions of length 0.3..3: unit normals
+    ref.check_map(_np(n)[ok], want["n"][ok], f"gaussian normals, P = {P}")
+    ref.check_grad(_np(q.grad)[ok], ref.gaussian_normals_bwd(x["means3D"], x["scales"], x["rotations"], V, x["g"])[ok],
+                   f"dL/drotations, P = {P}")
+    n2 = gaussian_normals(m.detach(), s.detach(), q.detach(), rs)
+    assert torch.equal(n2, n.detach())
+
+
+def test_gaussian_normals_edge_rows():
+    """Equal scales pick the lowest index; the zero quaternion reads as the identity and gets a zero gradient; a [P,4] view that
+    starts in the middle of a buffer is read where it is."""
+    from contextgs_amd.normals import gaussian_normals
+    rs = _settings(24, 40)                                                   # the identity view: camera space = world space
+    m = _cu(np.array([[0, 0, 2], [0, 0, 2], [0, 0, -2], [0.5, 0, 2]], np.float32))
+    s = _cu(np.array([[1, 1, 1], [2, 1, 1], [3, 2, 1], [1, 2, 3]], np.float32))
+    buf = torch.zeros(1 + 16, device="cuda")
+    buf[1:] = _cu(np.array([[1, 0, 0, 0], [2, 0, 0, 0], [0.5, 0, 0, 0], [0, 0, 0, 0]], np.float32)).reshape(-1)
+    q = buf[1:].view(4, 4).requires_grad_()
+    n = gaussian_normals(m, s, q, rs)
+    n.sum().backward()
+    torch.cuda.synchronize()
+    # axes x, y, z, x of the identity; turned so that n . t >= 0 (row 2 is behind the camera: -z)
+    assert _np(n).tolist() == [[1, 0, 0], [0, 1, 0], [0, 0, -1], [1, 0, 0]]
+    assert torch.isfinite(q.grad).all() and bool((q.grad[3] == 0).all())
+
+
+# ---- (3), (4) per pixel --------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _pixel_ref(kind, H, W, eps, weighted):
+    """The fp64 results of one case, computed once."""
+    x = ref.pixel_inputs(kind, H, W)
+    w = x["weight"] if weighted else None
+    dn, dd = ref.normal_consistency_bwd(x["normals"], x["depth"], TX, TY, w, eps, x["gE"])
+    return {"N": ref.depth_normals(x["depth"], TX, TY, eps), "dN": ref.depth_normals_bwd(x["depth"], TX, TY, eps, x["gN"]),
+            "E": ref.normal_consistency(x["normals"], x["depth"], TX, TY, w, eps), "dn": dn, "dd": dd}
+
+
+def _run_pixels(x, H, W, eps, weighted, flat_depth=False):
+    """{"N", "dN", "E", "dn", "dd"} from the device; the backward of each runs twice and must give the same bits."""
+    from contextgs_amd.normals import depth_normals, normal_consistency
+    rs = _settings(H, W)
+    out = {}
+    for rep in range(2):
+        d = _cu(x["depth"][0] if flat_depth else x["depth"], True)
+        N = depth_normals(d, rs, eps=eps)
+        (N * _cu(x["gN"])).sum().backward()
+        d2, nm = _cu(x["depth"], True), _cu(x["normals"], True)
+        w = _cu(x["weight"], True) if weighted else None
+        E = normal_consistency(nm, d2, rs, weight=w, eps=eps)
+        (E * _cu(x["gE"])).sum().backward()
+        torch.cuda.synchronize()
+        assert N.shape == (3, H, W) and E.shape == (1, H, W) and d.grad.shape == d.shape and nm.grad.shape == (3, H, W)
+        assert w is None or w.grad is None                                   # the weight is not differentiated
+        got = {"N": N.detach(), "dN": d.grad.reshape(H, W), "E": E.detach()[0], "dn": nm.grad, "dd": d2.grad[0]}
+        for k, v in got.items():
+            assert torch.isfinite(v).all(), k
+            if rep:
+                assert torch.equal(v, out[k]), f"{k}: two runs differ"
+        out = got
+    return out
+
+
+@pytest.mark.parametrize("kind", ["smooth", "rough"])
+@pytest.mark.parametrize("H, W", ref.SHAPES)
+def test_depth_normals_and_consistency_match_fp64(H, W, kind):
+    x = ref.pixel_inputs(kind, H, W)
+    assert (x["depth"][0][ref.HOLE] == 0).all()                               # the undrawn region is part of every case
+    for eps, weighted in itertools.product((0.0, 1e-5), (False, True)):
+        what = f"{H}x{W} {kind} eps {eps:g}{' weighted' if weighted else ''}"
+        got = _run_pixels(x, H, W, eps, weighted, flat_depth=weighted)
+        want = _pixel_ref(kind, H, W, eps, weighted)
+        ref.check_map(_np(got["N"]), want["N"], f"depth normals {what}")
+        ref.check_grad(_np(got["dN"]), want["dN"], f"dL/ddepth of the normals {what}")
+        ref.check_map(_np(got["E"]), want["E"], f"E {what}")
+        ref.check_grad(_np(got["dn"]), want["dn"], f"dL/dnormals {what}")
+        ref.check_grad(_np(got["dd"]), want["dd"], f"dL/ddepth of E {what}")
+        inside = (slice(None), slice(6, 8), slice(11, 19))                   # deep inside the hole: no normal, no gradient
+        assert bool((got["N"][inside] == 0).all()) and bool((got["dn"][inside] == 0).all())
+        if eps == 0.0:
+            ln = got["N"].norm(dim=0)
+            assert bool(((ln - 1).abs() < 1e-5)[ln > 0].all())                # unit normals wherever there is one
+
+
+def test_constant_depth_gives_plus_z():
+    from contextgs_amd.normals import depth_normals
+    N = depth_normals(_cu(ref.depth_case("constant", 24, 40)), _settings(24, 40))
+    assert bool((N[:2] == 0).all()) and bool(((N[2] - 1).abs() < 1e-6).all())
+
+
+@pytest.mark.parametrize("H, W", ref.THIN)
+def test_one_pixel_wide_or_high_is_exactly_zero(H, W):
+    x = ref.pixel_inputs("rough", H, W)
+    for eps, weighted in itertools.product((0.0, 1e-5), (False, True)):
+        got = _run_pixels(x, H, W, eps, weighted)
+        assert bool((got["N"] == 0).all()) and bool((got["dN"] == 0).all())
+        assert bool((got["E"] == 1).all()) and bool((got["dn"] == 0).all()) and bool((got["dd"] == 0).all())
+
+
+def test_fused_loss_equals_the_composition():
+    """normal_consistency against 1 - m <normals, depth_normals(depth)> composed in torch from the same kernel's output."""
+    from contextgs_amd.normals import depth_normals, normal_consistency
+    H, W = 48, 64
+    x = ref.pixel_inputs("rough", H, W)
+    rs = _settings(H, W)
+    d, nm = _cu(x["depth"], True), _cu(x["normals"], True)
+    E = normal_consistency(nm, d, rs, weight=_cu(x["weight"]))
+    (E * _cu(x["gE"])).sum().backward()
+    d2, nm2 = _cu(x["depth"], True), _cu(x["normals"], True)
+    E2 = 1 - _cu(x["weight"]) * (nm2 * depth_normals(d2, rs)).sum(0, keepdim=True)
+    (E2 * _cu(x["gE"])).sum().backward()
+    torch.cuda.synchronize()
+    ref.check_map(_np(E), _np(E2), "fused E vs composed")
+    ref.check_grad(_np(nm.grad), _np(nm2.grad), "fused dL/dnormals vs composed")
+    ref.check_grad(_np(d.grad), _np(d2.grad), "fused dL/ddepth vs composed")
+
+
+def test_loss_backward_computes_only_the_gradients_asked_for():
+    """A detached `depth` or `normals` gets None, and the other gradient has the bits of the call in which both asked."""
+    from contextgs_amd.normals import normal_consistency
+    H, W = 17, 33
+    x = ref.pixel_inputs("rough", H, W)
+    rs = _settings(H, W)
+    got = {}
+    for need_n, need_d in ((True, True), (True, False), (False, True)):
+        nm, d = _cu(x["normals"], need_n), _cu(x["depth"], need_d)
+        (normal_consistency(nm, d, rs, weight=_cu(x["weight"])) * _cu(x["gE"])).sum().backward()
+        torch.cuda.synchronize()
+        got[need_n, need_d] = (nm.grad, d.grad)
+    assert got[True, False][1] is None and got[False, True][0] is None
+    assert torch.equal(got[True, False][0], got[True, True][0]) and torch.equal(got[False, True][1], got[True, True][1])
+    E = normal_consistency(_cu(x["normals"]), _cu(x["depth"]), rs)
+    assert not E.requires_grad
+
+
+# ---- (2) the rendered normal map -----------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _scene(P, W, H, seed, extent=1.0, srange=(0.005, 0.05), eye=(0.4, -2.2, 0.6)):
+    """The `ragged` and `single` scenes of tests/test_raster_geom_gpu.py, restated."""
+    from contextgs_amd.synth import look_at_camera, random_gaussians
+    cam = look_at_camera(eye, (0, 0, 0), W, H, fovx_deg=60.0)
+    g = random_gaussians(P, seed=seed, extent=extent, scale_lo=srange[0], scale_hi=srange[1])
+    if P >= 20:     # some Gaussians behind the near plane
+        e = np.array([0.4, -2.2, 0.6], dtype=np.float32)
+        g["means3D"][::20] = e + 0.3 * (e - g["means3D"][::20])
+    return cam, g
+
+
+def _named_scene(name):
+    return _scene(200, 40, 24, 3, 1.0, (0.02, 0.12)) if name == "ragged" else _scene(1, 64, 48, 1)
+
+
+def _raster(rs, g, C, composed, seed=0, **kw):
+    """One forward + backward with user features of C columns (0: none), either with return_normals=True or with the normals
+    appended to the features by hand.  The loss weights every channel of every output with fixed random numbers."""
+    from contextgs_amd.normals import gaussian_normals
+    from contextgs_amd.rasterizer import GaussianRasterizer
+    P = g["means3D"].shape[0]
+    H, W = rs.image_height, rs.image_width
+    rng = np.random.default_rng(seed)
+    t = {k: _cu(v, True) for k, v in g.items()}
+    m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
+    F = _cu(rng.normal(size=(P, C)).astype(np.float32), True) if C else None
+    wts = _cu(rng.normal(size=(C + 3, H, W)).astype(np.float32))
+    wc = _cu(rng.normal(size=(3, H, W)).astype(np.float32))
+    args = dict(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"], scales=t["scales"],
+                rotations=t["rotations"], **kw)
+    if composed:
+        nrm = gaussian_normals(t["means3D"], t["scales"], t["rotations"], rs)
+        color, radii, ex = GaussianRasterizer(rs)(features=nrm if F is None else torch.cat([F, nrm], dim=1), **args)
+        fmap = ex["features"]
+        user, normals = fmap[:-3], fmap[-3:]
+    else:
+        color, radii, ex = GaussianRasterizer(rs)(features=F, return_normals=True, **args)
+        assert ("features" in ex) == bool(C)
+        user, normals = (ex["features"] if C else torch.zeros(0, H, W, device="cuda")), ex["normals"]
+    assert normals.shape == (3, H, W) and user.shape == (C, H, W)
+    loss = (color * wc).sum() + (normals * wts[C:]).sum() + ((user * wts[:C]).sum() if C else 0.0)
+    loss.backward()
+    torch.cuda.synchronize()
+    grads = {k: v.grad for k, v in t.items()}
+    grads["means2D"] = m2.grad
+    if C:
+        grads["features"] = F.grad
+    return {"color": color.detach(), "radii": radii, "normals": normals.detach(), "user": user.detach(), "extras": ex,
+            "grads": grads}
+
+
+@pytest.mark.parametrize("C", [0, 1, 29])
+@pytest.mark.parametrize("name", ["ragged", "single"])
+def test_rendered_normals_equal_the_feature_composition(name, C):
+    cam, g = _named_scene(name)
+    rs = _cam_settings(cam)
+    more = dict(return_aux=True, return_geometry=True) if C == 1 else dict(return_aux=(C == 29))
+    a = _raster(rs, g, C, composed=False, **more)
+    b = _raster(rs, g, C, composed=True, **more)
+    assert torch.equal(a["normals"], b["normals"]) and torch.equal(a["user"], b["user"])      # bit for bit
+    assert torch.equal(a["color"], b["color"]) and torch.equal(a["radii"], b["radii"])
+    assert float(a["normals"].abs().max()) > 0
+    if more.get("return_aux"):
+        ex = a["extras"]
+        assert torch.equal(ex["alpha"], b["extras"]["alpha"])
+        assert bool((a["normals"].norm(dim=0) <= ex["alpha"][0] + 1e-5).all())                # unnormalised: at most alpha long
+    if more.get("return_geometry"):
+        assert torch.equal(a["extras"]["median_id"], b["extras"]["median_id"])
+    for k in b["grads"]:
+        ref.check_grad(_np(a["grads"][k]), _np(b["grads"][k]), f"d{k} {name} C = {C}: return_normals vs composed")
+    assert float(a["grads"]["rotations"].abs().max()) > 0
+
+
+def test_rendered_normals_match_the_fp64_blend_of_restated_normals(oracle64):
+    """Independent of the feature path: the oracle blends the restated fp64 per-Gaussian normals as colours."""
+    cam, g = _named_scene("ragged")
+    a = _raster(_cam_settings(cam), g, 0, composed=False)
+    V = np.asarray(cam.world_view_transform, np.float32)
+    f = ref.gaussian_normals(g["means3D"], g["scales"], g["rotations"], V)
+    assert (f["margin"] >= 1e-4).all()
+    want = oracle64.render(cam.oracle_dict(bg=(0.0, 0.0, 0.0)), g["means3D"], f["n"], g["opacities"], g["scales"],
+                           g["rotations"])["color"]
+    ref.check_map(_np(a["normals"]), want, "rendered normals vs the oracle's blend")
+
+
+def test_return_normals_with_antialiasing_shs_contrib_and_absgrad():
+    from contextgs_amd.rasterizer import GaussianRasterizer
+    cam, g = _named_scene("ragged")
+    P = g["means3D"].shape[0]
+    rs = _cam_settings(cam, aa=True)
+    t = {k: _cu(v, True) for k, v in g.items()}
+    sh = _cu(np.random.default_rng(5).normal(size=(P, 4, 3)).astype(np.float32) * 0.3, True)
+    m2 = torch.zeros(P, 4, device="cuda", requires_grad=True)
+    color, radii, ex = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], shs=sh,
+                                              scales=t["scales"], rotations=t["rotations"], return_normals=True, contrib=True,
+                                              absgrad=True)
+    assert set(ex) >= {"normals", "contrib", "top_id"} and "features" not in ex and ex["normals"].shape == (3, 24, 40)
+    (ex["normals"].sum() + color.sum()).backward()
+    torch.cuda.synchronize()
+    for k in ("means3D", "opacities", "scales", "rotations"):
+        assert torch.isfinite(t[k].grad).all() and float(t[k].grad.abs().sum()) > 0, k
+    assert m2.grad.shape == (P, 4) and torch.isfinite(sh.grad).all()
+    plain = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], shs=sh, scales=t["scales"],
+                                   rotations=t["rotations"], absgrad=True)
+    assert len(plain) == 2 and torch.equal(plain[0], color)                    # without the keyword the call is unchanged
+
+
+def test_no_gaussians():
+    from contextgs_amd.rasterizer import GaussianRasterizer
+    cam, g = _named_scene("ragged")
+    e = {k: _cu(v[:0], True) for k, v in g.items()}
+    color, radii, ex = GaussianRasterizer(_cam_settings(cam))(
+        means3D=e["means3D"], means2D=torch.zeros(0, 3, device="cuda"), opacities=e["opacities"], colors_precomp=e["colors"],
+        scales=e["scales"], rotations=e["rotations"], return_normals=True)
+    assert ex["normals"].shape == (3, 24, 40) and bool((ex["normals"] == 0).all())
+
+
+# ---- the hemispheres agree -----------------------------------------------------------------------------------------------------
+def test_rendered_normals_and_depth_normals_share_a_hemisphere():
+    """What the parts cannot show alone: on a tilted plane of flat, randomly flipped Gaussians the rendered normals and the
+    normals of the rendered depth point the same way (tests/test_normals.py confirms the +1 on the oracle)."""
+    from contextgs_amd.normals import depth_normals, normal_consistency
+    from contextgs_amd.rasterizer import GaussianRasterizer
+    cam, g = ref.plane_scene()
+    H, W = cam.image_height, cam.image_width
+    assert (H, W) == (48, 64)
+    rs = _cam_settings(cam)
+    t = {k: _cu(v) for k, v in g.items()}
+    P = g["means3D"].shape[0]
+    color, radii, ex = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=torch.zeros(P, 3, device="cuda"),
+                                              opacities=t["opacities"], colors_precomp=t["colors"], scales=t["scales"],
+                                              rotations=t["rotations"], return_aux=True, return_normals=True)
+    alpha = ex["alpha"]
+    depth_p = ex["depth"] / alpha.clamp_min(1e-6)
+    N = depth_normals(depth_p, rs)
+    cos = (ex["normals"] * N).sum(0) / alpha[0].clamp_min(1e-6)
+    mask = alpha[0] > 0.9
+    mask[:4] = mask[-4:] = False
+    mask[:, :4] = mask[:, -4:] = False
+    mean = float(cos[mask].mean())
+    print(f"[hemisphere] mean cosine {mean:.4f} over {int(mask.sum())} pixels")
+    assert int(mask.sum()) > 1500 and mean > 0.5
+    want, _ = ref.hemisphere_agreement(_np(ex["normals"]), _np(ex["depth"]), _np(alpha), math.tan(cam.FoVx * 0.5),
+                                       math.tan(cam.FoVy * 0.5))
+    assert abs(mean - want) < 1e-3
+    # the plane recedes to the right: both normals are near (-sin 30, 0, +cos 30)
+    mid = (slice(None), slice(20, 28), slice(28, 36))
+    for v in (N[mid].mean(dim=(1, 2)), (ex["normals"] / alpha.clamp_min(1e-6))[mid].mean(dim=(1, 2))):
+        assert abs(float(v[0]) + 0.5) < 0.1 and abs(float(v[1])) < 0.1 and abs(float(v[2]) - 0.866) < 0.1, v
+    E = normal_consistency(ex["normals"], depth_p, rs, weight=alpha)
+    assert float(E[0][mask].mean()) < 0.1                                     # the regulariser is near its minimum here
+
+
+# ---- render() ----------------------------------------------------------------------------------------------------------------
+def _model(N=20000, W=320, H=180):
+    from contextgs_amd.synth import SynthPipe, make_scene, orbit_cameras
+    pc = make_scene(N, seed=0)
+    cams = [c.to_torch("cuda") for c in orbit_cameras(4, W, H)]
+    return pc, cams, SynthPipe(), torch.zeros(3, device="cuda")
+
+
+def _render(pc, cam, pipe, bg, **kw):
+    from contextgs_amd import ctx_ops
+    from contextgs_amd.renderer import prefilter_voxel, render
+    torch.manual_seed(0)
+    ctx_ops._seed_counter = itertools.count(1)       # the same noise streams in every call
+    vis = prefilter_voxel(cam, pc, pipe, bg)
+    return render(cam, pc, pipe, bg, visible_mask=vis, step=1000, **kw)
+
+
+def test_render_returns_the_normals_and_the_backward_reaches_the_anchors():
+    from contextgs_amd.normals import normal_consistency
+    from contextgs_amd.renderer import _raster_settings
+    pc, cams, pipe, bg = _model()
+    cam = cams[1]
+    pc.train(True)
+    with torch.enable_grad():
+        plain = _render(pc, cam, pipe, bg)
+        pkg = _render(pc, cam, pipe, bg, return_aux=True, return_normals=True)
+        A = torch.randn(pc.get_anchor.shape[0], 2, device="cuda", requires_grad=True)
+        both = _render(pc, cam, pipe, bg, return_normals=True, anchor_features=A)
+    assert torch.equal(pkg["render"].detach(), plain["render"].detach()) and torch.equal(pkg["radii"], plain["radii"])
+    assert pkg["normals"].shape == (3, 180, 320) and "features" not in pkg
+    assert both["features"].shape == (2, 180, 320)
+    ref.check_map(_np(both["normals"]), _np(pkg["normals"]), "normals next to anchor_features vs alone")
+    assert float(pkg["normals"].detach().abs().max()) > 0
+    assert bool((pkg["normals"].detach().norm(dim=0) <= pkg["alpha"][0].detach() + 1e-5).all())
+    for _, p in pc.named_parameters():
+        p.grad = None
+    settings = _raster_settings(cam, pipe, bg, 1.0)
+    depth_p = pkg["depth"] / pkg["alpha"].clamp_min(1e-6)
+    normal_consistency(pkg["normals"], depth_p, settings, weight=pkg["alpha"].detach()).mean().backward()
+    torch.cuda.synchronize()
+    for name in ("_anchor", "_offset", "_anchor_feat", "_scaling"):
+        gr = getattr(pc, name).grad
+        assert gr is not None and torch.isfinite(gr).all() and float(gr.abs().sum()) > 0, name
+    with pytest.raises(ValueError, match="more than 29"):
+        _render(pc, cam, pipe, bg, return_normals=True, anchor_features=torch.zeros(pc.get_anchor.shape[0], 30, device="cuda"))
+    pc.train(False)
+    with torch.no_grad():
+        ev = _render(pc, cam, pipe, bg, return_normals=True)
+    assert ev["normals"].shape == (3, 180, 320) and torch.isfinite(ev["normals"]).all()
