@@ -59,6 +59,13 @@ class AdamTensor(C.Structure):
     ]
 
 
+class RateSubLevel(C.Structure):
+    """struct cgs_rate_sub_level — one level of a cgs_rate_sub_fwd_multi / _bwd_multi call (ctx_ops.py)."""
+    _fields_ = [("in_dim", c_int32), ("use_clamp", c_int32), ("n", c_int64), ("m", c_int64)] + [
+        (k, c_void_p) for k in ("X", "loc", "W1", "b1", "W2", "b2", "yf", "ys", "yo", "Q", "masks", "x_means", "sums3", "g_sums3",
+                                "side_f", "side_s", "side_o", "side_Q", "dx_sub", "d_masks", "dW1", "db1", "dW2", "db2")]
+
+
 # The eight cgs_raster_backward* signatures (include/cgs.h), from their common pieces: cfg, P, R | the inputs | the three
 # workspaces, pointer and bytes each | dL_dout [| the three map gradients] | the output gradients | scratch, its bytes, the stream
 # [| opts [| features, C, dL_dfeatures_map, dL_dfeatures [| moments, median_id, dL_ddistortion, dL_dmedian_depth]] or
@@ -235,6 +242,12 @@ SIGNATURES = {
     "cgs_rate_sub_bwd_scratch_bytes": (c_size_t, [c_int, c_int64]),
     "cgs_rate_sub_bwd": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64] + [c_void_p] * 10 + [c_int] + [c_void_p] * 12 +
                          [c_size_t, c_void_p]),
+    "cgs_rate_sub_fwd_multi": (c_int, [c_int, C.POINTER(RateSubLevel), c_void_p]),
+    "cgs_rate_sub_bwd_multi_scratch_bytes": (c_size_t, [c_int, C.POINTER(RateSubLevel)]),
+    "cgs_rate_sub_bwd_multi": (c_int, [c_int, C.POINTER(RateSubLevel), c_void_p, c_size_t, c_void_p]),
+    "cgs_rate_sub_group_begin": (c_int, []),
+    "cgs_rate_sub_group_end": (c_int, [c_int]),
+    "cgs_rate_sub_partition": (c_int, [c_int, C.POINTER(c_int), C.POINTER(c_int64), c_int, C.POINTER(c_int), C.POINTER(c_int)]),
     "cgs_eb_likelihood_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "cgs_eb_likelihood_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "cgs_ac_max_bytes": (c_size_t, [c_int64]),

@@ -243,3 +243,6 @@ int cgs_launch_wgrad_multi(const CgsWgProduct *prods, int nprod, int64_t n, int 
                            size_t scratch_bytes, hipStream_t s);
 int cgs_launch_wgrad_reduce(const float *partial, int blocks, const CgsWgProduct *prods, int nprod, hipStream_t s);
 int cgs_launch_wgrad_reduce_assign(const float *partial, int blocks, const CgsWgProduct *prods, int nprod, hipStream_t s);
+#define CGS_WG_REDUCE_MAX_SETS 8
+struct CgsWgReduceSet { const float *partial; int blocks; const CgsWgProduct *prods; int nprod; };
+int cgs_launch_wgrad_reduce_assign_sets(const CgsWgReduceSet *sets, int nsets, hipStream_t s);

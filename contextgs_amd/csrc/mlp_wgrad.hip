@@ -381,11 +381,11 @@ __global__ void __launch_bounds__(1024)
     for (int i = tid; i < a.E; i += 1024) dst[i] = img[i];
 }
 
-__global__ void __launch_bounds__(256)
-    wgrad_multi_reduce_kernel(const float *__restrict__ partial, int blocks, int E, WgmProducts pr, int assign) {
-    __shared__ float s[4][64];
+// (the body: workgroup `bx` of the (E + 63) / 64 that sum one set of images; s = the workgroup's [4][64] LDS patch)
+__device__ __forceinline__ void wgrad_multi_reduce_body(const float *__restrict__ partial, int blocks, int E, const WgmProducts &pr,
+                                                        int assign, int bx, float (*s)[64]) {
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + tx;
+    const int e = bx * 64 + tx;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     if (e < E) {
         int b = ty;
@@ -415,6 +415,32 @@ __global__ void __launch_bounds__(256)
         if (le < dadb) dW[le] = assign ? t : dW[le] + t;
         else if (db) db[le - dadb] = assign ? t : db[le - dadb] + t;
     }
+}
+
+__global__ void __launch_bounds__(256)
+    wgrad_multi_reduce_kernel(const float *__restrict__ partial, int blocks, int E, WgmProducts pr, int assign) {
+    __shared__ float s[4][64];
+    wgrad_multi_reduce_body(partial, blocks, E, pr, assign, (int)blockIdx.x, s);
+}
+
+// The same over several independent sets of images (the levels of the rate subset, rate_sub.hip) in ONE launch: the grids of
+// the sets one after the other, every set summed exactly as a launch of its own would.
+struct WgrSet {
+    const float *partial;
+    int blocks, E;
+    WgmProducts pr;
+};
+struct WgrSets {
+    WgrSet s[CGS_WG_REDUCE_MAX_SETS];
+    int first_block[CGS_WG_REDUCE_MAX_SETS + 1];
+    int nsets;
+};
+__global__ void __launch_bounds__(256) wgrad_multi_reduce_sets_kernel(WgrSets t, int assign) {
+    __shared__ float s[4][64];
+    const int bx = (int)blockIdx.x;
+    int k = 0;
+    for (int q = 1; q < CGS_WG_REDUCE_MAX_SETS; ++q) k += (q < t.nsets && bx >= t.first_block[q]) ? 1 : 0;
+    wgrad_multi_reduce_body(t.s[k].partial, t.s[k].blocks, t.s[k].E, t.s[k].pr, assign, bx - t.first_block[k], s);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -620,9 +646,8 @@ int cgs_launch_wgrad_reduce(const float *partial, int blocks, const CgsWgProduct
 int cgs_launch_wgrad_reduce_assign(const float *partial, int blocks, const CgsWgProduct *prods, int nprod, hipStream_t s) {
     return wgrad_reduce_launch(partial, blocks, prods, nprod, 1, s);
 }
-static int wgrad_reduce_launch(const float *partial, int blocks, const CgsWgProduct *prods, int nprod, int assign, hipStream_t s) {
-    if (nprod <= 0 || nprod > WGM_MAX_PROD || blocks <= 0) { cgs_set_error("wgrad_reduce: bad args"); return CGS_ERR_ARG; }
-    WgmProducts pr;
+// the products' table of a set of images and its length E
+static int wgrad_reduce_table(const CgsWgProduct *prods, int nprod, WgmProducts &pr) {
     int E = 0;
     for (int k = 0; k < nprod; ++k) {
         pr.dW[k] = prods[k].dW; pr.db[k] = prods[k].db; pr.off[k] = E; pr.dadb[k] = prods[k].DA * prods[k].DB;
@@ -631,7 +656,33 @@ static int wgrad_reduce_launch(const float *partial, int blocks, const CgsWgProd
     for (int k = nprod; k < WGM_MAX_PROD; ++k) { pr.dW[k] = nullptr; pr.db[k] = nullptr; pr.off[k] = E; pr.dadb[k] = 0; }
     pr.off[WGM_MAX_PROD] = E;
     pr.nprod = nprod;
+    return E;
+}
+static int wgrad_reduce_launch(const float *partial, int blocks, const CgsWgProduct *prods, int nprod, int assign, hipStream_t s) {
+    if (nprod <= 0 || nprod > WGM_MAX_PROD || blocks <= 0) { cgs_set_error("wgrad_reduce: bad args"); return CGS_ERR_ARG; }
+    WgmProducts pr;
+    const int E = wgrad_reduce_table(prods, nprod, pr);
     hipLaunchKernelGGL(wgrad_multi_reduce_kernel, dim3((unsigned)((E + 63) / 64)), dim3(256), 0, s, partial, blocks, E, pr, assign);
+    CGS_CHECK_HIP(hipGetLastError());
+    return CGS_OK;
+}
+// cgs_launch_wgrad_reduce_assign for `nsets` sets of images at once (one set alone takes the launch above)
+int cgs_launch_wgrad_reduce_assign_sets(const CgsWgReduceSet *sets, int nsets, hipStream_t s) {
+    if (nsets <= 0 || nsets > CGS_WG_REDUCE_MAX_SETS) { cgs_set_error("wgrad_reduce: bad args"); return CGS_ERR_ARG; }
+    if (nsets == 1) return wgrad_reduce_launch(sets[0].partial, sets[0].blocks, sets[0].prods, sets[0].nprod, 1, s);
+    WgrSets t = {};
+    int grid = 0;
+    for (int k = 0; k < nsets; ++k) {
+        if (sets[k].nprod <= 0 || sets[k].nprod > WGM_MAX_PROD || sets[k].blocks <= 0) { cgs_set_error("wgrad_reduce: bad args"); return CGS_ERR_ARG; }
+        t.s[k].partial = sets[k].partial;
+        t.s[k].blocks = sets[k].blocks;
+        t.s[k].E = wgrad_reduce_table(sets[k].prods, sets[k].nprod, t.s[k].pr);
+        t.first_block[k] = grid;
+        grid += (t.s[k].E + 63) / 64;
+    }
+    for (int k = nsets; k <= CGS_WG_REDUCE_MAX_SETS; ++k) t.first_block[k] = grid;
+    t.nsets = nsets;
+    hipLaunchKernelGGL(wgrad_multi_reduce_sets_kernel, dim3((unsigned)grid), dim3(256), 0, s, t, 1);
     CGS_CHECK_HIP(hipGetLastError());
     return CGS_OK;
 }

@@ -4,18 +4,25 @@
 // i.e. ~8 launches per level and direction that hand ~3.5 KB per chosen row to each other through HBM
 // (scene/gaussian_model.py:1600-1608 on the chosen rows, :1658-1694, utils/entropy_models.py:30-50).
 //
-//   rs_main_kernel<IN, false>   forward: X rows through `loc`, hidden layer, the 172 mean / scale outputs of mlp_grid, the three
+//   rs_main_body<IN, false>     forward: X rows through `loc`, hidden layer, the 172 mean / scale outputs of mlp_grid, the three
 //                               Entropy_gaussian terms of every element against the level's noisy values, the three bit sums.
 //                               NOTHING is written but the sums: the [m,175] prediction never exists in memory.
-//   rs_main_kernel<IN, true>    backward, data half: the forward is recomputed (same MFMA chains = same bits), d bits / d(mean,
+//   rs_main_body<IN, true>      backward, data half: the forward is recomputed (same MFMA chains = same bits), d bits / d(mean,
 //                               scale, x, Q, mask weight) formed in registers, dH = W2^T dZ2, dZ1, dX = W1^T dZ1 on the matrix
 //                               cores; writes the compact side arrays (gradients of the noisy values / step sizes / input row that
 //                               cgs_ctx_level_bwd adds in) and the operands of the weight gradients as 16-row tiles in COLUMN-major
 //                               order ([tile][column][16 rows]): the layout whose fragments are one 16-byte load per lane.
-//   rs_wgrad_kernel<IN>         dW2 = dZ2^T [H | 1], dW1 = dZ1^T [X | 1] with the ROW index as the MFMA contraction: the 119 output
+//   rs_wgrad_body<IN>           dW2 = dZ2^T [H | 1], dW1 = dZ1^T [X | 1] with the ROW index as the MFMA contraction: the 119 output
 //                               tiles are split over the eight waves of a workgroup (60-80 accumulator registers each, two waves per
 //                               SIMD), every operand fragment is ONE coalesced 1 KB wave load, no LDS, no atomics; per-workgroup
 //                               images are summed in block order by wgrad_multi_reduce_kernel (bit-reproducible).
+//
+// The bodies run inside GROUPED kernels, one launch per stage for all levels of a step (rs_main_multi_kernel<BWD>,
+// rs_wgrad_multi_kernel, one reduction over all levels' images): no level's rate kernels depend on another level's, and the
+// small levels alone fill a fraction of the device — level by level, every launch paid its own weight-staging prologue and its
+// own tail on mostly idle compute units.  A workgroup belongs to ONE level (a range of the grid, cgs_rate_sub_partition for
+// rs_main, the level's own grid for rs_wgrad), so every per-row result, every per-workgroup image and the block-order sums
+// have the bits of a launch per level; a single level is the same code with L = 1.
 //
 // Output tiles of the second layer are PERMUTED so that the mean and the scale of an element sit in the same lane and register
 // slot of two neighbouring tiles, and so that a lane's four elements are one 16-byte piece of the level's noisy values in the
@@ -72,8 +79,8 @@ struct RsArgs {
     const float *masks;                      // [m, 10] mask weights of the chosen rows (may be NULL = ones)
     const float *x_means;                    // [3] clamp centres (use_clamp)
     int64_t n, m;
-    int use_clamp;
-    float *sums;                             // forward: [3] accumulated into
+    int use_clamp, in_dim;                   // in_dim 71 / 15: which body a grouped kernel's workgroup runs
+    float *sums;                            // forward: [3] accumulated into
     const float *g_sums;                     // backward: [3] upstream gradient of the three sums
     float *side_f, *side_s, *side_o, *side_Q;        // [m,50] [m,6] [m,30] [m,3]
     float *dx_sub;                           // [m, IN]
@@ -88,15 +95,21 @@ struct RsOps {             // the global operands of one 16-row tile, fetched on
     f32x4 q3, mk4, mk5;
 };
 
+// The LDS of a workgroup, carved by the body: the images of W2 ([o'][h]) and W1 ([h][k], at most 112 x 84 floats), the two
+// biases and the waves' partial sums.  ONE buffer of the grouped kernel: static arrays in its two inlined bodies would add up.
+#define RS_LDS_W1 (RS_OP * RS_SA)
+#define RS_LDS_B1 (RS_LDS_W1 + CL_HP * ClShape<71>::SB)
+#define RS_LDS_B2 (RS_LDS_B1 + CL_HP)
+#define RS_LDS_PART (RS_LDS_B2 + RS_OP)
+#define RS_LDS_FLOATS (RS_LDS_PART + 3 * (RS_WAVES_F > RS_WAVES_B ? RS_WAVES_F : RS_WAVES_B))
+
+// Workgroup `block` of the `nblocks` that share ONE level's tiles (the grouped kernels below give every level its own range
+// of the grid): the level's weights are staged once and kept, its 16-row tiles go round the level's waves.
 template <int IN, bool BWD>
-__global__ void __launch_bounds__((BWD ? RS_WAVES_B : RS_WAVES_F) * 64) rs_main_kernel(RsArgs a) {
+__device__ __forceinline__ void rs_main_body(const RsArgs &a, float *lds, int block, int nblocks) {
     constexpr int RS_WAVES = BWD ? RS_WAVES_B : RS_WAVES_F;
     constexpr int NTI = ClShape<IN>::NTI, XP = ClShape<IN>::XP, SB = ClShape<IN>::SB;
-    __shared__ __attribute__((aligned(16))) float W2n[RS_OP * RS_SA];      // [o'][h]
-    __shared__ __attribute__((aligned(16))) float W1n[CL_HP * SB];         // [h][k]
-    __shared__ float b1s[CL_HP];
-    __shared__ float b2p[RS_OP];
-    __shared__ float part[RS_WAVES][3];
+    float *W2n = lds, *W1n = lds + RS_LDS_W1, *b1s = lds + RS_LDS_B1, *b2p = lds + RS_LDS_B2, *part = lds + RS_LDS_PART;
     const int tid = threadIdx.x, nthr = RS_WAVES * 64;
     // The weights are read in THEIR order (coalesced 16-byte loads, nothing between a load and the next: all of a thread's loads
     // are in flight together) and scattered into the LDS images; walking the images and gathering cost ~15 us per launch — 43
@@ -144,7 +157,9 @@ __global__ void __launch_bounds__((BWD ? RS_WAVES_B : RS_WAVES_F) * 64) rs_main_
     }
     __syncthreads();
 
-    const int lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
+    // (the wave index as a scalar: the tile counters then live in scalar registers — with both bodies in one kernel the
+    //  backward is two vector registers short of keeping them per lane without spilling)
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, c = lane & 15;
     const int64_t m = a.m, ntiles = (m + 15) / 16;
     const uint64_t nb = (uint64_t)a.n, mb = (uint64_t)m, tb = (uint64_t)ntiles * 64;
     const ClBuf bX = cl_buf(a.X, nb * IN * 4), bLoc = cl_buf(a.loc, mb * 8), bQ = cl_buf(a.Q, nb * 12),
@@ -168,8 +183,8 @@ __global__ void __launch_bounds__((BWD ? RS_WAVES_B : RS_WAVES_F) * 64) rs_main_
         op.mk5 = cl_l64(bM, cl_sel(v && has_masks, (uint32_t)s * (RS_K * 4) + (uint32_t)lo5 * 4));
     };
 
-    const int64_t tstride = (int64_t)gridDim.x * RS_WAVES;
-    int64_t tile = (int64_t)blockIdx.x * RS_WAVES + wave;
+    const int64_t tstride = (int64_t)nblocks * RS_WAVES;
+    int64_t tile = (int64_t)block * RS_WAVES + wave;
     float accb[3] = {0.f, 0.f, 0.f};
     RsOps<IN> opn;
     int64_t rn;
@@ -440,15 +455,42 @@ __global__ void __launch_bounds__((BWD ? RS_WAVES_B : RS_WAVES_F) * 64) rs_main_
             float v = accb[k];
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-            if (lane == 0) part[wave][k] = v;
+            if (lane == 0) part[3 * wave + k] = v;
         }
         __syncthreads();
         if (tid < 3) {
             float v = 0.f;
-            for (int w = 0; w < RS_WAVES; ++w) v += part[w][tid];
+            for (int w = 0; w < RS_WAVES; ++w) v += part[3 * w + tid];
             atomicAdd(&a.sums[tid], v);
         }
     }
+}
+
+// All levels in one launch: workgroup blockIdx.x belongs to the level whose range of the grid holds it (first_block: the
+// exclusive prefix of the levels' workgroup counts, cgs_rate_sub_partition).  The branch on the level's input width is uniform
+// per workgroup, so the barriers of the bodies stay legal.
+#define RS_MAX_LEVELS 8
+struct RsMulti {
+    RsArgs lv[RS_MAX_LEVELS];
+    int first_block[RS_MAX_LEVELS + 1];
+    int L;
+};
+
+template <class T>
+__device__ __forceinline__ int rs_level_of(const T &t, int bx) {
+    int level = 0;
+#pragma unroll
+    for (int l = 1; l < RS_MAX_LEVELS; ++l) level += (l < t.L && bx >= t.first_block[l]) ? 1 : 0;
+    return level;
+}
+
+template <bool BWD>
+__global__ void __launch_bounds__((BWD ? RS_WAVES_B : RS_WAVES_F) * 64) rs_main_multi_kernel(RsMulti t) {
+    __shared__ __attribute__((aligned(16))) float lds[RS_LDS_FLOATS];
+    const int bx = (int)blockIdx.x, level = rs_level_of(t, bx);
+    const int block = bx - t.first_block[level], nblocks = t.first_block[level + 1] - t.first_block[level];
+    if (t.lv[level].in_dim == 71) rs_main_body<71, BWD>(t.lv[level], lds, block, nblocks);
+    else rs_main_body<15, BWD>(t.lv[level], lds, block, nblocks);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -459,7 +501,8 @@ __global__ void __launch_bounds__((BWD ? RS_WAVES_B : RS_WAVES_F) * 64) rs_main_
 struct RwArgs {
     const float *dZ2t, *Ht, *dZ1t, *Xt;
     int64_t ntiles, tiles_per_block;
-    float *partial;                          // [gridDim.x][E], E = 100 IN + 100 + 175 * 100 + 175
+    float *partial;                          // [the level's workgroups][E], E = 100 IN + 100 + 175 * 100 + 175
+    int in_dim;
 };
 
 template <int NA, int NB>
@@ -506,15 +549,16 @@ __device__ __forceinline__ void rw_accumulate(ClBuf A, int colsA, int a0, ClBuf 
     }
 }
 
+// workgroup `block` of ONE level's own grid (rw_blocks): tiles [block, block + 1) * tiles_per_block into image `block`
 template <int IN>
-__global__ void __launch_bounds__(RW_WAVES * 64) rs_wgrad_kernel(RwArgs a) {
+__device__ __forceinline__ void rs_wgrad_body(const RwArgs &a, int block) {
     constexpr int NTI = ClShape<IN>::NTI, XP = ClShape<IN>::XP;
     constexpr int E1 = CL_HID * IN + CL_HID, E = E1 + RS_OUT * CL_HID + RS_OUT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-    const int64_t t0 = (int64_t)blockIdx.x * a.tiles_per_block;
+    const int64_t t0 = (int64_t)block * a.tiles_per_block;
     const int64_t t1 = t0 + a.tiles_per_block < a.ntiles ? t0 + a.tiles_per_block : a.ntiles;
     const uint64_t tb = (uint64_t)a.ntiles * 64;
-    float *img = a.partial + (int64_t)blockIdx.x * E;
+    float *img = a.partial + (int64_t)block * E;
     float *img1 = img, *imgb1 = img + CL_HID * IN, *img2 = img + E1, *imgb2 = img2 + RS_OUT * CL_HID;
     if (wave < 6) {
         // dW2[o'][h] for the permuted tiles u = 2 wave, 2 wave + 1 (one element block: its means and its scales)
@@ -567,6 +611,21 @@ __global__ void __launch_bounds__(RW_WAVES * 64) rs_wgrad_kernel(RwArgs a) {
     }
 }
 
+// The levels' own grids one after the other (the host puts the small ones first: the large level's workgroups start as the
+// small ones drain): a level's workgroups, their tiles and their images are those of a launch of its own.
+struct RwMulti {
+    RwArgs lv[RS_MAX_LEVELS];
+    int first_block[RS_MAX_LEVELS + 1];
+    int L;
+};
+
+__global__ void __launch_bounds__(RW_WAVES * 64) rs_wgrad_multi_kernel(RwMulti t) {
+    const int bx = (int)blockIdx.x, level = rs_level_of(t, bx);
+    const int block = bx - t.first_block[level];
+    if (t.lv[level].in_dim == 71) rs_wgrad_body<71>(t.lv[level], block);
+    else rs_wgrad_body<15>(t.lv[level], block);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 static int rs_cus() {
     static int cus = 0;
@@ -581,45 +640,155 @@ static int rs_cus() {
 
 static bool rs_fits(int64_t rows, int64_t row_bytes) { return rows >= 0 && (uint64_t)rows * (uint64_t)row_bytes < CL_MAX_BYTES; }
 
-static int rs_check(const char *what, int in_dim, const float *X, int64_t n, const int64_t *loc, int64_t m, const float *W1,
-                    const float *b1, const float *W2, const float *b2, const float *yf, const float *ys, const float *yo,
-                    const float *Q, const float *x_means, int use_clamp) {
-    if (n < 0 || m < 0 || (in_dim != 71 && in_dim != 15)) { cgs_set_error("%s: bad args (in_dim 71 or 15)", what); return CGS_ERR_ARG; }
-    if (m == 0) return CGS_OK;
-    if (!X || !loc || !W1 || !b1 || !W2 || !b2 || !yf || !ys || !yo || !Q || (use_clamp && !x_means)) { cgs_set_error("%s: NULL", what); return CGS_ERR_ARG; }
-    const int64_t ntiles = (m + 15) / 16;
-    if (!rs_fits(n, in_dim * 4) || !rs_fits(n, CL_D * 4) || !rs_fits(m, CL_D * 4) || !rs_fits(ntiles * 16, RS_OP * 4)) {
-        cgs_set_error("%s: an operand exceeds 4 GB (n %lld, m %lld)", what, (long long)n, (long long)m);
+static int rs_check(const char *what, const cgs_rate_sub_level &v) {
+    if (v.n < 0 || v.m < 0 || (v.in_dim != 71 && v.in_dim != 15)) { cgs_set_error("%s: bad args (in_dim 71 or 15)", what); return CGS_ERR_ARG; }
+    if (v.m == 0) return CGS_OK;
+    if (!v.X || !v.loc || !v.W1 || !v.b1 || !v.W2 || !v.b2 || !v.yf || !v.ys || !v.yo || !v.Q || (v.use_clamp && !v.x_means)) {
+        cgs_set_error("%s: NULL", what);
+        return CGS_ERR_ARG;
+    }
+    const int64_t ntiles = (v.m + 15) / 16;
+    if (!rs_fits(v.n, v.in_dim * 4) || !rs_fits(v.n, CL_D * 4) || !rs_fits(v.m, CL_D * 4) || !rs_fits(ntiles * 16, RS_OP * 4)) {
+        cgs_set_error("%s: an operand exceeds 4 GB (n %lld, m %lld)", what, (long long)v.n, (long long)v.m);
         return CGS_ERR_ARG;
     }
     return CGS_OK;
 }
 
-static int64_t rs_grid(int64_t m, int waves) {
-    const int64_t tiles = (m + 15) / 16, want = (tiles + waves - 1) / waves;
-    return want < rs_cus() ? want : rs_cus();
+// MFMAs of the forward per 16-row tile (layer 1: 28 per input tile, layer 2: 336): 476 / 364 for in_dim 71 / 15; the backward
+// issues exactly twice as many of either, so one weight serves both directions
+static int64_t rs_cost(int in_dim) { return 4 * CL_NT1 * ((in_dim + 15) / 16) + 4 * CL_NT1 * RS_NT2; }
+
+// The workgroups of one rs_main launch over L levels of m[l] chosen rows on a device of C compute units: a workgroup stages
+// ONE level's weights and takes eight of its tiles per pass.  blocks[l]: 0 for an empty level, else at least 1 and at most
+// ceil(tiles / 8); the C workgroups (one per compute unit: the weights fill its LDS) go to the levels in proportion to
+// tiles * cost — every further workgroup to the level whose workgroups carry the most.  first_block [L + 1]: the exclusive
+// prefix of blocks.  The total is at most max(C, levels with rows).
+extern "C" int cgs_rate_sub_partition(int L, const int *in_dim, const int64_t *m, int C, int *blocks, int *first_block) {
+    if (L < 0 || L > RS_MAX_LEVELS || C < 1 || (L > 0 && (!in_dim || !m || !blocks)) || !first_block) {
+        cgs_set_error("rate_sub_partition: bad args (at most %d levels)", RS_MAX_LEVELS);
+        return CGS_ERR_ARG;
+    }
+    int64_t cap[RS_MAX_LEVELS], load[RS_MAX_LEVELS];
+    int total = 0;
+    for (int l = 0; l < L; ++l) {
+        if (m[l] < 0 || (in_dim[l] != 71 && in_dim[l] != 15)) { cgs_set_error("rate_sub_partition: bad args (in_dim 71 or 15)"); return CGS_ERR_ARG; }
+        const int64_t tiles = (m[l] + 15) / 16;
+        if (tiles > ((int64_t)1 << 40)) { cgs_set_error("rate_sub_partition: bad args (m %lld)", (long long)m[l]); return CGS_ERR_ARG; }
+        cap[l] = (tiles + 7) / 8;
+        load[l] = tiles * rs_cost(in_dim[l]);
+        blocks[l] = tiles > 0 ? 1 : 0;
+        total += blocks[l];
+    }
+    for (; total < C; ++total) {
+        int best = -1;
+        for (int l = 0; l < L; ++l) {
+            if (blocks[l] == 0 || blocks[l] >= cap[l]) continue;
+            // load / blocks, compared without a division (< 2^62: tiles <= 2^40, cost < 2^9, blocks <= C)
+            if (best < 0 || load[l] * blocks[best] > load[best] * blocks[l]) best = l;
+        }
+        if (best < 0) break;
+        ++blocks[best];
+    }
+    first_block[0] = 0;
+    for (int l = 0; l < L; ++l) first_block[l + 1] = first_block[l] + blocks[l];
+    return CGS_OK;
 }
 
-// Bits of the rate subset of one level (scene/gaussian_model.py:1658-1669 on rows loc[0..m) of the level): sums3 [3] +=
-// (feat, scaling, offsets * mask weight) bits.  X [n, in_dim]: the level's input rows as cgs_ctx_level_fwd wrote them; W1 / b1 /
-// W2 / b2: mlp_grid[level] ([100, in_dim], [100], [175, 100], [175]); yf / ys / yo / Q: the level's noisy values and step sizes
-// [n, .]; masks [m, 10]: the mask weights of the chosen rows (NULL = ones); x_means [3]: clamp centres when use_clamp.
+static void rs_fill(RsArgs &a, const cgs_rate_sub_level &v) {
+    a = RsArgs{};
+    a.X = v.X; a.loc = v.loc; a.W1 = v.W1; a.b1 = v.b1; a.W2 = v.W2; a.b2 = v.b2; a.yf = v.yf; a.ys = v.ys; a.yo = v.yo; a.Q = v.Q;
+    a.masks = v.masks; a.x_means = v.use_clamp ? v.x_means : nullptr; a.n = v.n; a.m = v.m; a.use_clamp = v.use_clamp ? 1 : 0;
+    a.in_dim = v.in_dim;
+}
+
+// one rs_main launch over the levels of t (all with rows): the partition, then the grid
+template <bool BWD>
+static int rs_main_launch(RsMulti &t, hipStream_t stream) {
+    int in_dim[RS_MAX_LEVELS], blocks[RS_MAX_LEVELS];
+    int64_t m[RS_MAX_LEVELS];
+    for (int l = 0; l < t.L; ++l) { in_dim[l] = t.lv[l].in_dim; m[l] = t.lv[l].m; }
+    int rc = cgs_rate_sub_partition(t.L, in_dim, m, rs_cus(), blocks, t.first_block);
+    if (rc) return rc;
+    for (int l = t.L; l < RS_MAX_LEVELS; ++l) t.first_block[l + 1] = t.first_block[t.L];
+    constexpr int waves = BWD ? RS_WAVES_B : RS_WAVES_F;
+    hipLaunchKernelGGL((rs_main_multi_kernel<BWD>), dim3((unsigned)t.first_block[t.L]), dim3(waves * 64), 0, stream, t);
+    CGS_CHECK_HIP(hipGetLastError());
+    return CGS_OK;
+}
+
+// ---- grouping the single-level calls, as ncclGroupStart / ncclGroupEnd group collectives: between cgs_rate_sub_group_begin()
+// and cgs_rate_sub_group_end() of the calling thread, cgs_rate_sub_fwd / cgs_rate_sub_bwd check their arguments and are
+// RECORDED; the end issues them as ONE grouped call (what cgs_rate_sub_fwd_multi / _bwd_multi do with an array of records).
+// The call sites of a step stay one per level — each with the buffers and the scratch it allocated — and the launches are shared.
+struct RsGroup {
+    bool open, failed;
+    int bwd, L;                              // bwd: -1 until the first call is recorded
+    cgs_rate_sub_level lv[RS_MAX_LEVELS];
+    void *scratch[RS_MAX_LEVELS];
+    void *stream;
+};
+static thread_local RsGroup rs_group;
+
+static int rs_group_record(int bwd, const cgs_rate_sub_level &v, void *scratch, void *stream) {
+    RsGroup &g = rs_group;
+    if (g.L >= RS_MAX_LEVELS || (g.L > 0 && (g.bwd != bwd || g.stream != stream))) {
+        g.failed = true;
+        cgs_set_error("rate_sub group: at most %d calls, all forward or all backward, on one stream", RS_MAX_LEVELS);
+        return CGS_ERR_ARG;
+    }
+    g.bwd = bwd; g.stream = stream; g.lv[g.L] = v; g.scratch[g.L] = scratch;
+    ++g.L;
+    return CGS_OK;
+}
+
+static int rs_fwd_check(const cgs_rate_sub_level &v) {
+    int rc = rs_check("rate_sub_fwd", v);
+    if (rc || v.m == 0) return rc;
+    if (!v.sums3) { cgs_set_error("rate_sub_fwd: NULL"); return CGS_ERR_ARG; }
+    return CGS_OK;
+}
+
+// the forward of the (checked) levels in one launch; a level with m == 0 takes no part
+static int rs_fwd_run(int L, const cgs_rate_sub_level *levels, hipStream_t stream) {
+    RsMulti t = {};
+    for (int l = 0; l < L; ++l) {
+        if (levels[l].m == 0) continue;
+        RsArgs &a = t.lv[t.L++];
+        rs_fill(a, levels[l]);
+        a.sums = levels[l].sums3;
+    }
+    if (t.L == 0) return CGS_OK;
+    CgsProfScope prof(CGS_PROF_RATE_FWD, stream);
+    return rs_main_launch<false>(t, stream);
+}
+
+// Bits of the rate subsets of L levels (scene/gaussian_model.py:1658-1669 on rows loc[0..m) of each level) in ONE launch:
+// sums3 [3] of every level += (feat, scaling, offsets * mask weight) bits.  Per level — X [n, in_dim]: the level's input rows
+// as cgs_ctx_level_fwd wrote them; W1 / b1 / W2 / b2: mlp_grid[level] ([100, in_dim], [100], [175, 100], [175]); yf / ys / yo /
+// Q: the level's noisy values and step sizes [n, .]; masks [m, 10]: the mask weights of the chosen rows (NULL = ones); x_means
+// [3]: clamp centres when use_clamp.  A level with m == 0 takes no part.
+extern "C" int cgs_rate_sub_fwd_multi(int L, const cgs_rate_sub_level *levels, void *stream) {
+    if (L < 0 || L > RS_MAX_LEVELS || (L > 0 && !levels)) { cgs_set_error("rate_sub_fwd: bad args (at most %d levels)", RS_MAX_LEVELS); return CGS_ERR_ARG; }
+    for (int l = 0; l < L; ++l) {
+        int rc = rs_fwd_check(levels[l]);
+        if (rc) return rc;
+    }
+    return rs_fwd_run(L, levels, (hipStream_t)stream);
+}
+
+// one level: the L = 1 case, or a record of the open group
 extern "C" int cgs_rate_sub_fwd(int in_dim, const float *X, int64_t n, const int64_t *loc, int64_t m, const float *W1,
                                 const float *b1, const float *W2, const float *b2, const float *yf, const float *ys,
                                 const float *yo, const float *Q, const float *masks, const float *x_means, int use_clamp,
                                 float *sums3, void *stream) {
-    int rc = rs_check("rate_sub_fwd", in_dim, X, n, loc, m, W1, b1, W2, b2, yf, ys, yo, Q, x_means, use_clamp);
+    cgs_rate_sub_level v = {};
+    v.in_dim = in_dim; v.use_clamp = use_clamp; v.n = n; v.m = m; v.X = X; v.loc = loc; v.W1 = W1; v.b1 = b1; v.W2 = W2; v.b2 = b2;
+    v.yf = yf; v.ys = ys; v.yo = yo; v.Q = Q; v.masks = masks; v.x_means = x_means; v.sums3 = sums3;
+    int rc = rs_fwd_check(v);
     if (rc || m == 0) return rc;
-    if (!sums3) { cgs_set_error("rate_sub_fwd: NULL"); return CGS_ERR_ARG; }
-    RsArgs a = {};
-    a.X = X; a.loc = loc; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.yf = yf; a.ys = ys; a.yo = yo; a.Q = Q; a.masks = masks;
-    a.x_means = use_clamp ? x_means : nullptr; a.n = n; a.m = m; a.use_clamp = use_clamp ? 1 : 0; a.sums = sums3;
-    const unsigned grid = (unsigned)rs_grid(m, RS_WAVES_F);
-    CgsProfScope prof(CGS_PROF_RATE_FWD, (hipStream_t)stream);
-    if (in_dim == 71) hipLaunchKernelGGL((rs_main_kernel<71, false>), dim3(grid), dim3(RS_WAVES_F * 64), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((rs_main_kernel<15, false>), dim3(grid), dim3(RS_WAVES_F * 64), 0, (hipStream_t)stream, a);
-    CGS_CHECK_HIP(hipGetLastError());
-    return CGS_OK;
+    if (rs_group.open) return rs_group_record(0, v, nullptr, stream);
+    return rs_fwd_run(1, &v, (hipStream_t)stream);
 }
 
 static int64_t rw_blocks(int64_t ntiles) {
@@ -636,49 +805,143 @@ extern "C" size_t cgs_rate_sub_bwd_scratch_bytes(int in_dim, int64_t m) {
     return (size_t)(ntiles * 16 * (RS_OP + 2 * CL_HP + xp) + rw_blocks(ntiles) * E) * sizeof(float);
 }
 
-// Backward of cgs_rate_sub_fwd.  g_sums3 [3] (device): upstream gradient of the three sums.  Writes the compact side arrays
-// side_f [m,50] / side_s [m,6] / side_o [m,30] / side_Q [m,3] (row s = gradient of the noisy values / step sizes of level row
-// loc[s]: the side arrays of cgs_ctx_level_bwd), dx_sub [m, in_dim] (gradient of the input row through the mean / scale branch),
-// d_masks [m,10] (may be NULL; every row written), and ASSIGNS dW1 [100, in_dim], db1 [100], dW2 [175, 100], db2 [175] (the
-// three step-size rows of dW2 / db2 are zeros: cgs_ctx_level_bwd accumulates them).  scratch >= cgs_rate_sub_bwd_scratch_bytes().
+// the scratch of the levels one after the other, each level's piece (cgs_rate_sub_bwd_scratch_bytes) starting on a 256-byte
+// boundary: where the piece of the next level with rows starts, given where the one before ended
+static size_t rs_scratch_start(size_t end) { return (end + 255) / 256 * 256; }
+
+extern "C" size_t cgs_rate_sub_bwd_multi_scratch_bytes(int L, const cgs_rate_sub_level *levels) {
+    size_t end = 0;
+    for (int l = 0; l < L && levels; ++l) {
+        const size_t piece = cgs_rate_sub_bwd_scratch_bytes(levels[l].in_dim, levels[l].m);
+        if (piece) end = rs_scratch_start(end) + piece;
+    }
+    return end;
+}
+
+static int rs_bwd_check(const cgs_rate_sub_level &v, const void *scratch) {
+    int rc = rs_check("rate_sub_bwd", v);
+    if (rc || v.m == 0) return rc;
+    if (!v.g_sums3 || !v.side_f || !v.side_s || !v.side_o || !v.side_Q || !v.dx_sub || !v.dW1 || !v.db1 || !v.dW2 || !v.db2 || !scratch) {
+        cgs_set_error("rate_sub_bwd: NULL");
+        return CGS_ERR_ARG;
+    }
+    return CGS_OK;
+}
+
+// The backward of the (checked) levels, scratch[l] >= cgs_rate_sub_bwd_scratch_bytes() of level l, in three launches whatever
+// L: the data half, the weight gradients' images (every level its own grid and tiles per workgroup, small levels first) and
+// their sums, in block order per level.  A level with m == 0 takes no part.
+static int rs_bwd_run(int L, const cgs_rate_sub_level *levels, void *const *scratch, hipStream_t stream) {
+    RsMulti t = {};
+    RwArgs w[RS_MAX_LEVELS];
+    CgsWgProduct prods[RS_MAX_LEVELS][2];
+    int wgrid[RS_MAX_LEVELS];
+    for (int l = 0; l < L; ++l) {
+        const cgs_rate_sub_level &v = levels[l];
+        if (v.m == 0) continue;
+        const int k = t.L++;
+        const int64_t ntiles = (v.m + 15) / 16, xp = v.in_dim == 71 ? 80 : 16;
+        RsArgs &a = t.lv[k];
+        rs_fill(a, v);
+        a.g_sums = v.g_sums3;
+        a.side_f = v.side_f; a.side_s = v.side_s; a.side_o = v.side_o; a.side_Q = v.side_Q; a.dx_sub = v.dx_sub;
+        a.d_masks = v.masks ? v.d_masks : nullptr;
+        a.dZ2t = (float *)scratch[l]; a.Ht = a.dZ2t + ntiles * 16 * RS_OP; a.dZ1t = a.Ht + ntiles * 16 * CL_HP;
+        a.Xt = a.dZ1t + ntiles * 16 * CL_HP;
+        RwArgs &r = w[k];
+        r.dZ2t = a.dZ2t; r.Ht = a.Ht; r.dZ1t = a.dZ1t; r.Xt = a.Xt; r.ntiles = ntiles; r.partial = a.Xt + ntiles * 16 * xp;
+        r.in_dim = v.in_dim;
+        const int64_t blocks = rw_blocks(ntiles);
+        r.tiles_per_block = (ntiles + blocks - 1) / blocks;
+        wgrid[k] = (int)((ntiles + r.tiles_per_block - 1) / r.tiles_per_block);
+        prods[k][0] = CgsWgProduct{nullptr, 0, CL_HID, nullptr, 0, v.in_dim, v.dW1, v.db1};
+        prods[k][1] = CgsWgProduct{nullptr, 0, RS_OUT, nullptr, 0, CL_HID, v.dW2, v.db2};
+    }
+    if (t.L == 0) return CGS_OK;
+    {
+        CgsProfScope prof(CGS_PROF_RATE_BWD, stream);
+        int rc = rs_main_launch<true>(t, stream);
+        if (rc) return rc;
+    }
+    CgsProfScope prof(CGS_PROF_LMLP_WGRAD, stream);
+    // small grids first (a stable insertion sort of at most eight)
+    int order[RS_MAX_LEVELS];
+    for (int k = 0; k < t.L; ++k) {
+        int i = k;
+        for (; i > 0 && wgrid[order[i - 1]] > wgrid[k]; --i) order[i] = order[i - 1];
+        order[i] = k;
+    }
+    RwMulti wm = {};
+    CgsWgReduceSet sets[RS_MAX_LEVELS];
+    for (int i = 0; i < t.L; ++i) {
+        const int k = order[i];
+        wm.lv[i] = w[k];
+        wm.first_block[i + 1] = wm.first_block[i] + wgrid[k];
+        sets[i] = CgsWgReduceSet{w[k].partial, wgrid[k], prods[k], 2};
+    }
+    for (int i = t.L; i < RS_MAX_LEVELS; ++i) wm.first_block[i + 1] = wm.first_block[t.L];
+    wm.L = t.L;
+    hipLaunchKernelGGL(rs_wgrad_multi_kernel, dim3((unsigned)wm.first_block[t.L]), dim3(RW_WAVES * 64), 0, stream, wm);
+    CGS_CHECK_HIP(hipGetLastError());
+    return cgs_launch_wgrad_reduce_assign_sets(sets, t.L, stream);
+}
+
+// Backward of cgs_rate_sub_fwd_multi.  Per level — g_sums3 [3] (device): upstream gradient of the three sums; writes the
+// compact side arrays side_f [m,50] / side_s [m,6] / side_o [m,30] / side_Q [m,3] (row s = gradient of the noisy values / step
+// sizes of level row loc[s]: the side arrays of cgs_ctx_level_bwd), dx_sub [m, in_dim] (gradient of the input row through the
+// mean / scale branch), d_masks [m,10] (may be NULL; every row written), and ASSIGNS dW1 [100, in_dim], db1 [100], dW2 [175,
+// 100], db2 [175] (the three step-size rows of dW2 / db2 are zeros: cgs_ctx_level_bwd accumulates them).  A level with m == 0
+// takes no part: nothing of it is written (the caller zero-fills its weight gradients).  scratch >=
+// cgs_rate_sub_bwd_multi_scratch_bytes().
+extern "C" int cgs_rate_sub_bwd_multi(int L, const cgs_rate_sub_level *levels, void *scratch, size_t scratch_bytes, void *stream) {
+    if (L < 0 || L > RS_MAX_LEVELS || (L > 0 && !levels)) { cgs_set_error("rate_sub_bwd: bad args (at most %d levels)", RS_MAX_LEVELS); return CGS_ERR_ARG; }
+    void *piece[RS_MAX_LEVELS] = {};
+    size_t end = 0;
+    for (int l = 0; l < L; ++l) {
+        const cgs_rate_sub_level &v = levels[l];
+        int rc = rs_bwd_check(v, scratch);
+        if (rc) return rc;
+        if (v.m == 0) continue;
+        const size_t start = rs_scratch_start(end);
+        end = start + cgs_rate_sub_bwd_scratch_bytes(v.in_dim, v.m);
+        if (end > scratch_bytes) { cgs_set_error("rate_sub_bwd: scratch too small"); return CGS_ERR_WORKSPACE; }
+        piece[l] = (char *)scratch + start;
+    }
+    return rs_bwd_run(L, levels, piece, (hipStream_t)stream);
+}
+
+// one level: the L = 1 case, or a record of the open group
 extern "C" int cgs_rate_sub_bwd(int in_dim, const float *X, int64_t n, const int64_t *loc, int64_t m, const float *W1,
                                 const float *b1, const float *W2, const float *b2, const float *yf, const float *ys,
                                 const float *yo, const float *Q, const float *masks, const float *x_means, int use_clamp,
                                 const float *g_sums3, float *side_f, float *side_s, float *side_o, float *side_Q, float *dx_sub,
                                 float *d_masks, float *dW1, float *db1, float *dW2, float *db2, void *scratch, size_t scratch_bytes,
                                 void *stream) {
-    int rc = rs_check("rate_sub_bwd", in_dim, X, n, loc, m, W1, b1, W2, b2, yf, ys, yo, Q, x_means, use_clamp);
+    cgs_rate_sub_level v = {};
+    v.in_dim = in_dim; v.use_clamp = use_clamp; v.n = n; v.m = m; v.X = X; v.loc = loc; v.W1 = W1; v.b1 = b1; v.W2 = W2; v.b2 = b2;
+    v.yf = yf; v.ys = ys; v.yo = yo; v.Q = Q; v.masks = masks; v.x_means = x_means; v.g_sums3 = g_sums3;
+    v.side_f = side_f; v.side_s = side_s; v.side_o = side_o; v.side_Q = side_Q; v.dx_sub = dx_sub; v.d_masks = d_masks;
+    v.dW1 = dW1; v.db1 = db1; v.dW2 = dW2; v.db2 = db2;
+    int rc = rs_bwd_check(v, scratch);
     if (rc) return rc;
     if (m == 0) { cgs_set_error("rate_sub_bwd: m == 0 (the caller zero-fills the weight gradients of an empty subset)"); return CGS_ERR_ARG; }
-    if (!g_sums3 || !side_f || !side_s || !side_o || !side_Q || !dx_sub || !dW1 || !db1 || !dW2 || !db2 || !scratch) {
-        cgs_set_error("rate_sub_bwd: NULL");
-        return CGS_ERR_ARG;
-    }
     if (scratch_bytes < cgs_rate_sub_bwd_scratch_bytes(in_dim, m)) { cgs_set_error("rate_sub_bwd: scratch too small"); return CGS_ERR_WORKSPACE; }
-    const int64_t ntiles = (m + 15) / 16, xp = in_dim == 71 ? 80 : 16;
-    float *ws = (float *)scratch;
-    RsArgs a = {};
-    a.X = X; a.loc = loc; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.yf = yf; a.ys = ys; a.yo = yo; a.Q = Q; a.masks = masks;
-    a.x_means = use_clamp ? x_means : nullptr; a.n = n; a.m = m; a.use_clamp = use_clamp ? 1 : 0; a.g_sums = g_sums3;
-    a.side_f = side_f; a.side_s = side_s; a.side_o = side_o; a.side_Q = side_Q; a.dx_sub = dx_sub; a.d_masks = masks ? d_masks : nullptr;
-    a.dZ2t = ws; a.Ht = a.dZ2t + ntiles * 16 * RS_OP; a.dZ1t = a.Ht + ntiles * 16 * CL_HP; a.Xt = a.dZ1t + ntiles * 16 * CL_HP;
-    float *partial = a.Xt + ntiles * 16 * xp;
-    const unsigned grid = (unsigned)rs_grid(m, RS_WAVES_B);
-    {
-        CgsProfScope prof(CGS_PROF_RATE_BWD, (hipStream_t)stream);
-        if (in_dim == 71) hipLaunchKernelGGL((rs_main_kernel<71, true>), dim3(grid), dim3(RS_WAVES_B * 64), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((rs_main_kernel<15, true>), dim3(grid), dim3(RS_WAVES_B * 64), 0, (hipStream_t)stream, a);
-        CGS_CHECK_HIP(hipGetLastError());
-    }
-    CgsProfScope prof(CGS_PROF_LMLP_WGRAD, (hipStream_t)stream);
-    RwArgs w;
-    w.dZ2t = a.dZ2t; w.Ht = a.Ht; w.dZ1t = a.dZ1t; w.Xt = a.Xt; w.ntiles = ntiles; w.partial = partial;
-    const int64_t blocks = rw_blocks(ntiles);
-    w.tiles_per_block = (ntiles + blocks - 1) / blocks;
-    const unsigned wgrid = (unsigned)((ntiles + w.tiles_per_block - 1) / w.tiles_per_block);
-    if (in_dim == 71) hipLaunchKernelGGL((rs_wgrad_kernel<71>), dim3(wgrid), dim3(RW_WAVES * 64), 0, (hipStream_t)stream, w);
-    else hipLaunchKernelGGL((rs_wgrad_kernel<15>), dim3(wgrid), dim3(RW_WAVES * 64), 0, (hipStream_t)stream, w);
-    CGS_CHECK_HIP(hipGetLastError());
-    const CgsWgProduct prods[2] = {{nullptr, 0, CL_HID, nullptr, 0, in_dim, dW1, db1}, {nullptr, 0, RS_OUT, nullptr, 0, CL_HID, dW2, db2}};
-    return cgs_launch_wgrad_reduce_assign(partial, (int)wgrid, prods, 2, (hipStream_t)stream);
+    if (rs_group.open) return rs_group_record(1, v, scratch, stream);
+    return rs_bwd_run(1, &v, &scratch, (hipStream_t)stream);
+}
+
+extern "C" int cgs_rate_sub_group_begin(void) {
+    if (rs_group.open) { cgs_set_error("rate_sub group: already open on this thread"); return CGS_ERR_ARG; }
+    rs_group.open = true; rs_group.failed = false; rs_group.bwd = -1; rs_group.L = 0;
+    return CGS_OK;
+}
+
+// launch != 0: issue the recorded calls (an error while recording: nothing is issued, CGS_ERR_ARG); 0: drop them
+extern "C" int cgs_rate_sub_group_end(int launch) {
+    RsGroup &g = rs_group;
+    if (!g.open) { cgs_set_error("rate_sub group: not open on this thread"); return CGS_ERR_ARG; }
+    g.open = false;
+    if (!launch || g.L == 0) return CGS_OK;
+    if (g.failed) { cgs_set_error("rate_sub group: a call of the group was refused"); return CGS_ERR_ARG; }
+    return g.bwd ? rs_bwd_run(g.L, g.lv, g.scratch, (hipStream_t)g.stream) : rs_fwd_run(g.L, g.lv, (hipStream_t)g.stream);
 }

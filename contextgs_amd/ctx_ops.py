@@ -8,6 +8,7 @@ parity reference of tests/test_ctx_ops_gpu.py.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import itertools
 import threading
@@ -549,21 +550,54 @@ def _rate_sub_fwd(side, lv, masks_p, x_means, use_clamp, sums_p, stream):
         "cgs_rate_sub_fwd")
 
 
-def _rate_sub_bwd(side, lv, masks_p, x_means, use_clamp, K, g_p, d_masks_p, stream):
-    """-> ([d_yf, d_ys, d_yo, dQ], dx [n_sub, in], (dW1, db1, dW2, db2)), all compact and fully written."""
-    Lc = _lib.lib()
+def _rate_sub_bwd_buffers(levels, K):
+    """The outputs and the scratch of cgs_rate_sub_bwd for several levels [(side, lv)] from three allocations (every row and every
+    weight gradient is written: no fill) -> per level ([d_yf, d_ys, d_yo, dQ], dx [n_sub, in], (dW1, db1, dW2, db2), scratch)."""
+    Lc, dev = _lib.lib(), levels[0][1][0].device
+    shapes = []
+    for side, lv in levels:
+        X, W = side.loan()
+        n_sub, in_f = int(lv[5].shape[0]), int(X.shape[1])
+        ws = int(Lc.cgs_rate_sub_bwd_scratch_bytes(in_f, n_sub))
+        shapes.append((n_sub, (int(lv[0].shape[1]), 6, 3 * K, 3, in_f), W, (ws + 255) // 256 * 256))
+    rows = torch.split(torch.empty(sum(n * sum(ws_) for n, ws_, _, _ in shapes), dtype=_f32, device=dev),
+                       [n * w for n, ws_, _, _ in shapes for w in ws_])
+    wg = torch.split(torch.empty(sum(w.numel() for _, _, W, _ in shapes for w in W), dtype=_f32, device=dev),
+                     [w.numel() for _, _, W, _ in shapes for w in W])
+    scr = torch.split(torch.empty(sum(b for *_, b in shapes), dtype=torch.uint8, device=dev), [b for *_, b in shapes])
+    out = []
+    for j, (n, widths, W, _) in enumerate(shapes):
+        *d, dx = [t.view(n, w) for t, w in zip(rows[5 * j:5 * j + 5], widths)]
+        out.append((d, dx, tuple(t.view(w.shape) for t, w in zip(wg[4 * j:4 * j + 4], W)), scr[j]))
+    return out
+
+
+def _rate_sub_bwd(side, lv, masks_p, x_means, use_clamp, g_p, d_masks_p, bufs, stream):
+    """Fills bufs (one entry of _rate_sub_bwd_buffers) -> ([d_yf, d_ys, d_yo, dQ], dx [n_sub, in], (dW1, db1, dW2, db2)), all
+    compact and fully written."""
     yf, ys, yo, Q, _pred, loc = lv
     X, W = side.loan()
-    n_sub, in_f, dev = int(loc.shape[0]), int(X.shape[1]), yf.device
-    *d, dx = _carve(n_sub, (int(yf.shape[1]), 6, 3 * K, 3, in_f), dev)
-    wflat = torch.empty(sum(w.numel() for w in W), dtype=_f32, device=dev)
-    dW = tuple(t.view(w.shape) for t, w in zip(torch.split(wflat, [w.numel() for w in W]), W))
-    ws = torch.empty(int(Lc.cgs_rate_sub_bwd_scratch_bytes(in_f, n_sub)), dtype=torch.uint8, device=dev)
-    _lib.check(Lc.cgs_rate_sub_bwd(
-        in_f, _lib.ptr(X), int(X.shape[0]), _lib.ptr(loc), n_sub, *[_lib.ptr(w) for w in W], _lib.ptr(yf), _lib.ptr(ys), _lib.ptr(yo),
-        _lib.ptr(Q), masks_p, _lib.ptr(x_means), use_clamp, g_p, *[_lib.ptr(t) for t in d], _lib.ptr(dx), d_masks_p,
-        *[_lib.ptr(t) for t in dW], _lib.ptr(ws), ws.numel(), stream), "cgs_rate_sub_bwd")
+    d, dx, dW, ws = bufs
+    _lib.check(_lib.lib().cgs_rate_sub_bwd(
+        int(X.shape[1]), _lib.ptr(X), int(X.shape[0]), _lib.ptr(loc), int(loc.shape[0]), *[_lib.ptr(w) for w in W], _lib.ptr(yf),
+        _lib.ptr(ys), _lib.ptr(yo), _lib.ptr(Q), masks_p, _lib.ptr(x_means), use_clamp, g_p, *[_lib.ptr(t) for t in d], _lib.ptr(dx),
+        d_masks_p, *[_lib.ptr(t) for t in dW], _lib.ptr(ws), ws.numel(), stream), "cgs_rate_sub_bwd")
     return d, dx, dW
+
+
+@contextlib.contextmanager
+def _rate_sub_group():
+    """The cgs_rate_sub_fwd / cgs_rate_sub_bwd calls inside are recorded and leave as ONE grouped call at the end (include/cgs.h):
+    no level's rate kernels depend on another level's, and a launch per level leaves most of the device idle on the small ones."""
+    Lc = _lib.lib()
+    _lib.check(Lc.cgs_rate_sub_group_begin(), "cgs_rate_sub_group_begin")
+    done = False
+    try:
+        yield
+        done = True
+    finally:
+        rc = Lc.cgs_rate_sub_group_end(int(done))
+    _lib.check(rc, "cgs_rate_sub_group_end")
 
 
 def _rate_finish_fwd(table_p, levels, hsum, finish, device, stream):
@@ -655,7 +689,8 @@ def rate_finish(level_sums, hsum, rate, n_feat, n_scaling, n_offsets, dead_frac)
 
 class _RateAll(torch.autograd.Function):
     """The rate of ALL levels plus the scalar tail as one autograd node (scene/gaussian_model.py:1658-1705 on the
-    fused path): per level one cgs_level_rate_* launch, then cgs_rate_finish_*.  Compared with one node per level +
+    fused path): per level one cgs_level_rate_* launch — the rate_lazy levels' cgs_rate_sub_* calls as one group, a launch
+    per stage for all of them — then cgs_rate_finish_*.  Compared with one node per level +
     one for the tail: one zero fill for the [levels,3] sum table (forward) and one for the mask-weight gradient of all
     chosen rows (backward), no per-level slice nodes, and the level-row -> chosen-index maps come from the step's
     bookkeeping kernel (ctx_plan.hip) instead of a fill + arange + scatter per level.
@@ -678,15 +713,16 @@ class _RateAll(torch.autograd.Function):
         stream = _lib.current_stream()
         # a rate_lazy level (its node lent X and the weights): MLP branch + rate terms in one launch
         ctx.lazy = tuple(sd is not None and sd.lazy for sd in meta["sides"])
-        for j in range(nl):
-            lvj, (lo, hi) = lv[6 * j:6 * j + 6], meta["spans"][j]
-            n_sub = int(lvj[5].shape[0])
-            assert hi - lo == n_sub and (ctx.lazy[j] or int(lvj[4].shape[0]) == n_sub)
-            masks_p, sums_p = masks.data_ptr() + 4 * K * lo, S.data_ptr() + 12 * j
-            if not ctx.lazy[j]:
-                _level_rate_fwd(lvj, masks_p, None, x_means, use_clamp, K, sums_p, stream)
-            elif n_sub > 0:
-                _rate_sub_fwd(meta["sides"][j], lvj, masks_p, x_means, use_clamp, sums_p, stream)
+        with _rate_sub_group():              # the lazy levels' launches leave together
+            for j in range(nl):
+                lvj, (lo, hi) = lv[6 * j:6 * j + 6], meta["spans"][j]
+                n_sub = int(lvj[5].shape[0])
+                assert hi - lo == n_sub and (ctx.lazy[j] or int(lvj[4].shape[0]) == n_sub)
+                masks_p, sums_p = masks.data_ptr() + 4 * K * lo, S.data_ptr() + 12 * j
+                if not ctx.lazy[j]:
+                    _level_rate_fwd(lvj, masks_p, None, x_means, use_clamp, K, sums_p, stream)
+                elif n_sub > 0:
+                    _rate_sub_fwd(meta["sides"][j], lvj, masks_p, x_means, use_clamp, sums_p, stream)
         out, raw = _rate_finish_fwd(_lib.ptr(S), nl, hsum, meta["finish"], masks.device, stream)
         ctx.save_for_backward(masks, x_means, *lv)
         ctx.meta = meta
@@ -706,23 +742,26 @@ class _RateAll(torch.autograd.Function):
         # (the level-rate kernels add into it; the fused rate-subset kernels write every row of their span)
         d_masks = (torch.empty_like if all(ctx.lazy) else torch.zeros_like)(masks) if ctx.needs_input_grad[1] else None
         grads = []
-        for j in range(nl):
-            lvj, (lo, _hi), side, mp = lv[6 * j:6 * j + 6], meta["spans"][j], meta["sides"][j], meta["maps"][j]
-            loc, n_l = lvj[5], int(lvj[0].shape[0])
-            masks_p, g_p = masks.data_ptr() + 4 * K * lo, dS.data_ptr() + 12 * j
-            d_masks_p = None if d_masks is None else d_masks.data_ptr() + 4 * K * lo
-            if ctx.lazy[j]:
-                # (nothing chosen on this level: nothing is given, the level node zero-fills its weight gradients)
-                if int(loc.shape[0]) > 0:
-                    d, dx, dW = _rate_sub_bwd(side, lvj, masks_p, x_means, use_clamp, K, g_p, d_masks_p, stream)
-                    side.give(mp if mp is not None else _sub_map(loc, n_l), *d, dx=dx, dW=dW)
-                grads += [None] * 6
-                continue
-            d, d_pred = _level_rate_bwd(lvj, masks_p, None, x_means, use_clamp, K, g_p, d_masks_p, side is not None, stream)
-            if side is not None:
-                side.give(mp if mp is not None else _sub_map(loc, n_l), *d)
-                d = [None] * 4
-            grads += [*d, d_pred, None]
+        # (nothing chosen on a lazy level: nothing is given, the level node zero-fills its weight gradients)
+        sub = [j for j in range(nl) if ctx.lazy[j] and int(lv[6 * j + 5].shape[0]) > 0]
+        bufs = dict(zip(sub, _rate_sub_bwd_buffers([(meta["sides"][j], lv[6 * j:6 * j + 6]) for j in sub], K))) if sub else {}
+        with _rate_sub_group():
+            for j in range(nl):
+                lvj, (lo, _hi), side, mp = lv[6 * j:6 * j + 6], meta["spans"][j], meta["sides"][j], meta["maps"][j]
+                loc, n_l = lvj[5], int(lvj[0].shape[0])
+                masks_p, g_p = masks.data_ptr() + 4 * K * lo, dS.data_ptr() + 12 * j
+                d_masks_p = None if d_masks is None else d_masks.data_ptr() + 4 * K * lo
+                if ctx.lazy[j]:
+                    if j in bufs:
+                        d, dx, dW = _rate_sub_bwd(side, lvj, masks_p, x_means, use_clamp, g_p, d_masks_p, bufs[j], stream)
+                        side.give(mp if mp is not None else _sub_map(loc, n_l), *d, dx=dx, dW=dW)
+                    grads += [None] * 6
+                    continue
+                d, d_pred = _level_rate_bwd(lvj, masks_p, None, x_means, use_clamp, K, g_p, d_masks_p, side is not None, stream)
+                if side is not None:
+                    side.give(mp if mp is not None else _sub_map(loc, n_l), *d)
+                    d = [None] * 4
+                grads += [*d, d_pred, None]
         return (dh, d_masks, None, None, *grads)
 
 

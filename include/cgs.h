@@ -1027,6 +1027,43 @@ int cgs_rate_sub_bwd(int in_dim, const float *X, int64_t n, const int64_t *loc, 
                      float *side_Q, float *dx_sub, float *d_masks, float *dW1, float *db1,
                      float *dW2, float *db2, void *scratch, size_t scratch_bytes, void *stream);
 
+/* The same for up to 8 levels in ONE launch per stage (forward; backward: data half, weight-gradient
+ * images, their sums): no level's rate kernels depend on another level's, and the small levels
+ * alone leave most of the device idle.  A record holds the arguments of cgs_rate_sub_fwd (up to
+ * sums3) and of cgs_rate_sub_bwd (g_sums3 and the outputs; unused by the forward); the checks of
+ * the single-level calls apply per level, a level with m == 0 takes no part and nothing of it is
+ * written.  Every per-row and per-level result has the bits of the single-level call, which IS
+ * the L = 1 case; the forward's sums are closed by float atomics either way.
+ * scratch >= cgs_rate_sub_bwd_multi_scratch_bytes(L, levels) (reads in_dim and m only).
+ * cgs_rate_sub_partition: the workgroups of the forward / data-half launch, no kernel involved —
+ * blocks [L]: 0 for m == 0, else 1 .. ceil(ceil(m / 16) / 8), the C compute units shared out in
+ * proportion to tiles x matrix instructions per tile; first_block [L + 1]: their exclusive prefix;
+ * the total is at most max(C, levels with rows). */
+typedef struct cgs_rate_sub_level {
+    int32_t in_dim, use_clamp;
+    int64_t n, m;
+    const float *X;
+    const int64_t *loc;
+    const float *W1, *b1, *W2, *b2, *yf, *ys, *yo, *Q, *masks, *x_means;
+    float *sums3;
+    const float *g_sums3;
+    float *side_f, *side_s, *side_o, *side_Q, *dx_sub, *d_masks, *dW1, *db1, *dW2, *db2;
+} cgs_rate_sub_level;
+int cgs_rate_sub_fwd_multi(int L, const cgs_rate_sub_level *levels, void *stream);
+size_t cgs_rate_sub_bwd_multi_scratch_bytes(int L, const cgs_rate_sub_level *levels);
+int cgs_rate_sub_bwd_multi(int L, const cgs_rate_sub_level *levels, void *scratch,
+                           size_t scratch_bytes, void *stream);
+int cgs_rate_sub_partition(int L, const int *in_dim, const int64_t *m, int C, int *blocks,
+                           int *first_block);
+/* The same grouping for callers that keep one call site per level (the training step: every
+ * level's node owns the buffers of its call), as ncclGroupStart / ncclGroupEnd: between begin and
+ * end of the calling thread, cgs_rate_sub_fwd / cgs_rate_sub_bwd check their arguments and are
+ * recorded — at most 8 calls, all forward or all backward, one stream, each backward call with
+ * scratch of its own — and cgs_rate_sub_group_end(1) issues them as one grouped call;
+ * cgs_rate_sub_group_end(0) drops them (the caller failed in between). */
+int cgs_rate_sub_group_begin(void);
+int cgs_rate_sub_group_end(int launch);
+
 /* One launch per level and direction for the every-row half of the level loop, training path (round 5, csrc/ctx_level.hip;
  * scene/gaussian_model.py:1594-1616 and its autograd) — replaces cgs_rowcat_fwd + cgs_mlp2_forward(., 100, 3) +
  * cgs_noise_quant_fwd, and cgs_noise_quant_bwd + cgs_mlp2_backward(., 100, 3) + the first layer's cgs_mlp2_wgrad.
