@@ -26,6 +26,10 @@
 // operands are in flight while this tile is in the matrix pipe (the first version used predicated global loads, whose
 // exec-mask joins drained the load queue three times per prefetch; profiles/r05_ctx_level.txt).
 //
+// The noise takes a 32-bit element index (ctx_noise_k32; the bound is asserted next to cl_fits): fp32 MFMAs and VALU instructions do
+// not overlap on gfx950, so the 64-bit index arithmetic of 26 values per lane and tile was added time, and its registers had pushed
+// the forward's HS instance into scratch (profiles/ctxl_lean.txt).
+//
 // The mean / scale outputs of mlp_grid on the ~15 % rate subset and the rate terms stay in their own (small) launches.
 #include "cgs_internal.h"
 #include "mlp_frag.h"
@@ -163,25 +167,25 @@ __device__ __forceinline__ void cl_qadj(const float *__restrict__ W2qs, const fl
 // the noise of the lane's pieces of level row r (same element -> value map as noise_quant_*_kernel: element r * W + column of
 // tensor 0 / 1 / 2); pieces / values the lane does not own get 0
 __device__ __forceinline__ void cl_row_noise(ClRow &u, uint32_t kf, uint32_t ks, uint32_t ko, int64_t r, int g) {
-    const uint64_t ef = (uint64_t)r * CL_D, es = (uint64_t)r * CL_S, eo = (uint64_t)r * CL_O;
+    const uint32_t ef = (uint32_t)r * CL_D, es = (uint32_t)r * CL_S, eo = (uint32_t)r * CL_O;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) u.F[i][j] = ctx_noise_k(kf, ef + 16 * i + 4 * g + j);
-    const float n48 = ctx_noise_k(kf, ef + 48), n49 = ctx_noise_k(kf, ef + 49);
+        for (int j = 0; j < 4; ++j) u.F[i][j] = ctx_noise_k32(kf, ef + 16 * i + 4 * g + j);
+    const float n48 = ctx_noise_k32(kf, ef + 48), n49 = ctx_noise_k32(kf, ef + 49);
     u.F[3] = g == 0 ? (f32x4){n48, n49, 0.f, 0.f} : (f32x4){0.f, 0.f, 0.f, 0.f};
     // scaling: g 1 -> columns 0..3, g 2 -> columns 4, 5
     const int s0 = g == 2 ? 4 : 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float v = ctx_noise_k(ks, es + s0 + j);
+        const float v = ctx_noise_k32(ks, es + s0 + j);
         u.S[j] = (g == 1 || (g == 2 && j < 2)) ? v : 0.f;
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) u.O[0][j] = ctx_noise_k(ko, eo + 4 * g + j);
+    for (int j = 0; j < 4; ++j) u.O[0][j] = ctx_noise_k32(ko, eo + 4 * g + j);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float v = ctx_noise_k(ko, eo + 16 + 4 * g + j);
+        const float v = ctx_noise_k32(ko, eo + 16 + 4 * g + j);
         u.O[1][j] = (g == 3 && j >= 2) ? 0.f : v;
     }
 }
@@ -392,20 +396,20 @@ struct ClbOps {            // the global operands of one 16-row tile, fetched on
 __device__ __forceinline__ void clb_dx_and_sums(const ClRow &dy, const ClRow &sd, const ClRowBufs &B, uint32_t srow, uint32_t kf,
                                                 uint32_t ks, uint32_t ko, int64_t r, int g, bool on, float &af, float &as, float &ao) {
     const uint32_t of = srow * (CL_D * 4), os = srow * (CL_S * 4), oo = srow * (CL_O * 4);
-    const uint64_t ef = (uint64_t)r * CL_D, es = (uint64_t)r * CL_S, eo = (uint64_t)r * CL_O;
+    const uint32_t ef = (uint32_t)r * CL_D, es = (uint32_t)r * CL_S, eo = (uint32_t)r * CL_O;
     af = as = ao = 0.f;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const f32x4 v = dy.F[i] + sd.F[i];
         cl_s128(B.f, cl_sel(on, of + (uint32_t)(16 * i + 4 * g) * 4), v);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) af = fmaf(v[j], ctx_noise_k(kf, ef + 16 * i + 4 * g + j), af);
+        for (int j = 0; j < 4; ++j) af = fmaf(v[j], ctx_noise_k32(kf, ef + 16 * i + 4 * g + j), af);
     }
     {       // columns 48, 49: lane g == 0 only (the other lanes' pieces are zeros, their store goes nowhere)
         const f32x4 v = dy.F[3] + sd.F[3];
         cl_s64(B.f, cl_sel(on && g == 0, of + 48 * 4), v);
-        af = fmaf(v[0], ctx_noise_k(kf, ef + 48), af);
-        af = fmaf(v[1], ctx_noise_k(kf, ef + 49), af);
+        af = fmaf(v[0], ctx_noise_k32(kf, ef + 48), af);
+        af = fmaf(v[1], ctx_noise_k32(kf, ef + 49), af);
     }
     {       // scaling: g 1 -> columns 0..3, g 2 -> columns 4, 5 ([2], [3] of that piece belong to the next row)
         f32x4 v = dy.S + sd.S;
@@ -414,13 +418,13 @@ __device__ __forceinline__ void clb_dx_and_sums(const ClRow &dy, const ClRow &sd
         cl_s64(B.s, cl_sel(on && g == 2, os + 16), v);
         const int s0 = g == 2 ? 4 : 0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) as = fmaf(v[j], ctx_noise_k(ks, es + s0 + j), as);      // lanes g 0, 3: v = 0
+        for (int j = 0; j < 4; ++j) as = fmaf(v[j], ctx_noise_k32(ks, es + s0 + j), as);      // lanes g 0, 3: v = 0
     }
     {
         const f32x4 v = dy.O[0] + sd.O[0];
         cl_s128(B.o, cl_sel(on, oo + (uint32_t)(4 * g) * 4), v);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ao = fmaf(v[j], ctx_noise_k(ko, eo + 4 * g + j), ao);
+        for (int j = 0; j < 4; ++j) ao = fmaf(v[j], ctx_noise_k32(ko, eo + 4 * g + j), ao);
     }
     {
         f32x4 v = dy.O[1] + sd.O[1];
@@ -428,7 +432,7 @@ __device__ __forceinline__ void clb_dx_and_sums(const ClRow &dy, const ClRow &sd
         cl_s128(B.o, cl_sel(on && g != 3, oo + (uint32_t)(16 + 4 * g) * 4), v);
         cl_s64(B.o, cl_sel(on && g == 3, oo + 28 * 4), v);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ao = fmaf(v[j], ctx_noise_k(ko, eo + 16 + 4 * g + j), ao);
+        for (int j = 0; j < 4; ++j) ao = fmaf(v[j], ctx_noise_k32(ko, eo + 16 + 4 * g + j), ao);
     }
     af += __shfl_xor(af, 16); as += __shfl_xor(as, 16); ao += __shfl_xor(ao, 16);
     af += __shfl_xor(af, 32); as += __shfl_xor(as, 32); ao += __shfl_xor(ao, 32);
@@ -721,6 +725,9 @@ static int cl_cus() {
 }
 
 static bool cl_fits(int64_t rows, int64_t row_bytes) { return rows >= 0 && (uint64_t)rows * (uint64_t)row_bytes < CL_MAX_BYTES; }
+// ctx_noise_k32 (the kernels' 32-bit element indices r * width + column) rests on this bound: both launchers require
+// cl_fits(n, CL_D * 4), so n * CL_D < CL_MAX_BYTES / 4 <= 2^30, and CL_D is the widest of the three noisy tensors
+static_assert(CL_MAX_BYTES <= (1ull << 32) && CL_S <= CL_D && CL_O <= CL_D, "ctx_noise_k32: element indices must stay below 2^32");
 
 // Forward of one level, every row (see the head of this file).  in_dim 71: context level — X[r] = [anchor[a_rows[r]] |
 // base_f[pos[r]] | base_s[pos[r]] | hyp[r]]; in_dim 15: first level — X[r] = [anchor[a_rows[r]] (* a_mask) | hyp[r]].

@@ -22,6 +22,14 @@ __device__ __forceinline__ float ctx_noise_k(uint32_t key, uint64_t elem) {
     const uint32_t h = ctx_mix32((uint32_t)elem + key + (uint32_t)(elem >> 32) * 0x632BE5ABu);
     return (float)(h >> 8) * (1.0f / 16777216.0f) - 0.5f;
 }
+// The same value for an element index below 2^32 (elem_hi == 0: the third term above vanishes), without the 64-bit index
+// arithmetic and the quarter-rate multiply by a high word that is always zero.  The fused level kernels use it: their launchers
+// refuse any operand of CL_MAX_BYTES (< 2^32) bytes or more, so rows * width * 4 < 2^32 and every element index rows * width + column
+// they form is below 2^30 (ctx_level.hip asserts the tie next to cl_fits).  ctx.hip keeps the 64-bit form.
+__device__ __forceinline__ float ctx_noise_k32(uint32_t key, uint32_t elem) {
+    const uint32_t h = ctx_mix32(elem + key);
+    return (float)(h >> 8) * (1.0f / 16777216.0f) - 0.5f;
+}
 __device__ __forceinline__ float ctx_noise(uint64_t seed, uint32_t tensor, uint64_t elem) {
     return ctx_noise_k(ctx_noise_key(seed, tensor), elem);
 }
