@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera
+from raster_units_ref import geom64 as _geom64, t_no_termination as _t_no_termination
 
 pytestmark = pytest.mark.gpu
 
@@ -79,63 +80,7 @@ def _gaussians(means, scales, quats, opac, colors):
                 opacities=f(np.asarray(opac).reshape(-1, 1)))
 
 
-def _geom64(cam, g):
-    """fp64 restatement of the preprocess (oracle/raster_ref.c preprocess_one): pixel centre, depth, dilated 2-D covariance,
-    and the extents of the alpha >= 1/255 ellipse the GPU preprocess packs (box hx, hy; diagonals hu, hv)."""
-    o = cam.oracle_dict()
-    V, Pm = o["view"].astype(np.float64).reshape(4, 4), o["proj"].astype(np.float64).reshape(4, 4)
-    p = g["means3D"].astype(np.float64)
-    hom = np.c_[p, np.ones(len(p))]
-    t, h = hom @ V, hom @ Pm
-    pw = 1.0 / (h[:, 3] + 1e-7)
-    W, H = cam.image_width, cam.image_height
-    px, py = ((h[:, 0] * pw + 1) * W - 1) * 0.5, ((h[:, 1] * pw + 1) * H - 1) * 0.5
-    q = g["rotations"].astype(np.float64)
-    r, x, y, z = q.T
-    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
-                  2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
-                  2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
-    M = R * g["scales"].astype(np.float64)[:, None, :]
-    S3 = M @ M.transpose(0, 2, 1)
-    tz = t[:, 2]
-    limx, limy = 1.3 * o["tanfovx"], 1.3 * o["tanfovy"]
-    tx = np.clip(t[:, 0] / tz, -limx, limx) * tz
-    ty = np.clip(t[:, 1] / tz, -limy, limy) * tz
-    fx, fy = W / (2 * o["tanfovx"]), H / (2 * o["tanfovy"])
-    J = np.zeros((len(p), 2, 3))
-    J[:, 0, 0], J[:, 0, 2] = fx / tz, -fx * tx / tz ** 2
-    J[:, 1, 1], J[:, 1, 2] = fy / tz, -fy * ty / tz ** 2
-    A = J @ V[:3, :3].T
-    cov = A @ S3 @ A.transpose(0, 2, 1)
-    a, b, c = cov[:, 0, 0] + 0.3, cov[:, 0, 1], cov[:, 1, 1] + 0.3
-    det = a * c - b * b
-    mid = 0.5 * (a + c)
-    disc = np.sqrt(np.maximum(0.1, (0.5 * (a - c)) ** 2 + b * b))
-    op = g["opacities"].reshape(-1).astype(np.float64)
-    tau2 = 2 * np.log(np.maximum(255 * op, 1.0))
-    return dict(px=px, py=py, z=tz, a=a, b=b, c=c, det=det, ratio=(mid + disc) / np.maximum(mid - disc, 1e-30),
-                tau2=tau2, hx=np.sqrt(tau2 * a), hy=np.sqrt(tau2 * c), hu=np.sqrt(tau2 * np.maximum(a + c + 2 * b, 0)),
-                hv=np.sqrt(tau2 * np.maximum(a + c - 2 * b, 0)), radius=np.ceil(3 * np.sqrt(mid + disc)))
-
-
-def _t_no_termination(cam, g, geo, radii):
-    """Per pixel: the product of (1 - alpha) over EVERY Gaussian that reaches it (fp64, no early termination; order does not
-    matter).  Where it is below 1e-4 the blend must have stopped early."""
-    W, H = cam.image_width, cam.image_height
-    ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
-    logT = np.zeros((H, W))
-    live = np.nonzero(radii > 0)[0]
-    op = g["opacities"].reshape(-1).astype(np.float64)
-    for s in range(0, len(live), 256):
-        i = live[s:s + 256]
-        dx, dy = geo["px"][i, None, None] - xs, geo["py"][i, None, None] - ys
-        det = geo["det"][i, None, None]
-        ca, cb, cc = geo["c"][i, None, None] / det, -geo["b"][i, None, None] / det, geo["a"][i, None, None] / det
-        power = -0.5 * (ca * dx * dx + cc * dy * dy) - cb * dx * dy
-        alpha = np.minimum(0.99, op[i, None, None] * np.exp(np.minimum(power, 0.0)))
-        alpha[(power > 0) | (alpha < 1 / 255)] = 0.0
-        logT += np.log1p(-alpha).sum(0)
-    return np.exp(logT)
+# (the fp64 restatement of the preprocess and of the dense alpha: tests/raster_units_ref.py)
 
 
 def _tile_counts(cam, geo, radii):
