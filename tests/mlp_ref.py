@@ -15,6 +15,7 @@ stages by their absolute matrices (all in fp64, nothing taken from a kernel):
   y          none: U(z2);   tanh: U(z2) + u |y|;   sigmoid: U(z2) / 4 + u (y (1 - y) (|z2| + 1) + y)
              (|z2|: the rounding of z log2(e) inside the hardware exponential, amplified by the argument)
   dz2        |dy| (|d act'/dy| U(y) + u |act'|) + u |dz2|        (no activation: dz2 is dy itself, U = 0)
+             + |act'| U(dy) where the cotangent carries an error unit of its own (`dy_unit`; default: dy is exact)
   dh         U(dz2) |W2| + u |dz2| |W2|
   dz1        U(dh) under the gate
   dx         U(dz1) |W1| + u |dz1| |W1|
@@ -98,7 +99,7 @@ def act_fwd(z, act):
 class Ref:
     """values[k], units[k] for k in QUANTITIES (numpy float64), from float32 (or exact double) operands."""
 
-    def __init__(self, x, W1, b1, W2, b2, act, dy):
+    def __init__(self, x, W1, b1, W2, b2, act, dy, dy_unit=None):
         x, W1, b1, W2, b2, dy = (_f64(a) for a in (x, W1, b1, W2, b2, dy))
         aW1, aW2 = np.abs(W1), np.abs(W2)
         self.act, self.n = act, x.shape[0]
@@ -122,6 +123,8 @@ class Ref:
             Uy, g, dg = Uz2, np.ones_like(y), np.zeros_like(y)
         dz2 = dy * g
         Udz2 = np.zeros_like(dz2) if act == ACT_NONE else np.abs(dy) * (dg * Uy + U * np.abs(g)) + U * np.abs(dz2) + FLOOR
+        if dy_unit is not None:                                          # (a cotangent that is itself a computed quantity)
+            Udz2 = Udz2 + np.abs(g) * _f64(dy_unit)
         dh = dz2 @ W2
         Udh = Udz2 @ aW2 + U * (np.abs(dz2) @ aW2) + FLOOR
         dz1 = np.where(gate, dh, 0.0)

@@ -3,8 +3,9 @@ tanh of the step-size outputs per 16-row tile, cgs_ctx_level_bwd_h reads them in
 
 The reference is the recompute path — cgs_ctx_level_fwd / cgs_ctx_level_bwd2, whose kernels this change leaves as they were — and
 the statement is bit equality: the hand-over carries the very registers the recompute forms, and every product and sum behind them
-is the same instruction sequence.  (The recompute path itself is judged against torch in tests/test_ctx_level_gpu.py; the operands
-here are built like that file's C-ABI test, whose builder is inline there, so only its helpers are imported.)
+is the same instruction sequence.  (The recompute path itself is judged per element against float64 in
+tests/test_ctx_level_fp64_gpu.py, on every trip of the tile loops; the operands here are built like the C-ABI test of
+tests/test_ctx_level_gpu.py, whose builder is inline there, so only its helpers are imported.)
 
 Row counts: every wave of the backward's grid (one workgroup of 4 waves per CU) with zero, one and two tiles, and a ragged last tile.
 """
