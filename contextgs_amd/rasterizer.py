@@ -193,6 +193,7 @@ switched; without the flag the call enqueues exactly what it did before.  The mo
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import NamedTuple, Optional
@@ -490,12 +491,103 @@ def check_contrib(contrib, contrib_slots, means3D) -> None:
         raise ValueError("contrib needs at least one row with contrib_slots")
 
 
-def launch_backward(cfg, P, R, inputs, D, M, workspaces, g, maps, grads, stream, opts=0, absgrad=False, deterministic=False,
+class RasterRequest(NamedTuple):
+    """What a call wants besides colour and radii (module docstring): the one non-tensor argument of _RasterizeGaussians besides
+    the settings.  `contrib`: the GaussianContrib accumulated into (None: off); `normals`: how many trailing columns of the
+    node's `features` are the Gaussians' normals (0 or 3)."""
+    aux: bool = False
+    contrib: Optional["GaussianContrib"] = None
+    contrib_slots: Optional[torch.Tensor] = None
+    absgrad: bool = False
+    deterministic: bool = False
+    geometry: bool = False
+    normals: int = 0
+
+    def flags(self) -> "RasterRequest":
+        """The request without its objects (contrib: True or None), as the node keeps it for the backward."""
+        return self._replace(contrib=None if self.contrib is None else True, contrib_slots=None)
+
+    def keywords(self) -> dict:
+        """The request as keywords of GaussianRasterizer.forward."""
+        return dict(return_aux=self.aux, contrib=self.contrib, contrib_slots=self.contrib_slots, absgrad=self.absgrad,
+                    deterministic=self.deterministic, return_geometry=self.geometry, return_normals=bool(self.normals))
+
+
+AUX_MAPS = ("depth", "invdepth", "alpha")
+CONTRIB_MAPS = ("top_id", "top_weight", "count")
+GEOMETRY_MAPS = ("distortion", "median_depth", "median_id")
+NON_DIFFERENTIABLE = frozenset(("radii", "top_id", "top_weight", "count", "median_id"))
+# the inputs of _RasterizeGaussians.forward behind ctx: the backward's return, ctx.needs_input_grad by name
+INPUT_NAMES = ("request", "means3D", "means2D", "shs", "colors", "opacities", "scales", "rotations", "cov3D", "raster_settings",
+               "viewmatrix", "projmatrix", "campos", "features")
+
+
+def output_names(request: RasterRequest, has_features: bool) -> tuple:
+    """The node's outputs in order, for the forward's return, the backward's incoming gradients and the caller's extras."""
+    return (("color", "radii") + (AUX_MAPS if request.aux else ()) + (CONTRIB_MAPS if request.contrib is not None else ())
+            + (GEOMETRY_MAPS if request.geometry else ()) + (("features",) if has_features else ()))
+
+
+def named_extras(request: RasterRequest, has_user_features: bool, out: dict) -> dict:
+    """GaussianRasterizer.forward's third value from the node's outputs by name.  The one place that knows that the normals
+    are the three trailing channels of the feature map."""
+    extras = {}
+    for k, v in out.items():
+        if k == CONTRIB_MAPS[0]:
+            extras["contrib"] = request.contrib
+        if k not in ("color", "radii", "features"):
+            extras[k] = v
+    if has_user_features:
+        extras["features"] = out["features"][:-request.normals] if request.normals else out["features"]
+    if request.normals:
+        extras["normals"] = out["features"][-request.normals:]
+    return extras
+
+
+class _KeptView(NamedTuple):
+    """The render of a view that bin_and_blend kept: what every further walk of its lists and its backward are pointed at.
+    R: the pair count the binning workspace was carved with."""
+    cfg: _Cfg
+    P: int
+    R: int
+    geom: torch.Tensor
+    binws: Optional[torch.Tensor]
+    img: torch.Tensor
+
+    def args(self) -> tuple:
+        """cfg, P, R and the three workspaces, pointer and bytes each: the nine leading arguments of cgs_raster_render_aux,
+        _render_features, _render_geom and cgs_raster_contrib (include/cgs.h)."""
+        p = _lib.ptr
+        return (self.cfg.ref, self.P, self.R, p(self.geom), self.geom.numel(), p(self.binws),
+                self.binws.numel() if self.binws is not None else 0, p(self.img), self.img.numel())
+
+
+# the gradient buffers of a cgs_raster_backward* call, carved from two allocations (`rest` is the whole second one)
+_BackwardBuffers = collections.namedtuple("_BackwardBuffers", "rest means3D means2D colors opac scales rots cov")
+
+
+def carve_backward_buffers(P, m2, dev, cov_form=False, zero_acc=True, rows=None, opac_shape=None) -> _BackwardBuffers:
+    """For both autograd nodes.  One allocation for what the blends accumulate atomically, dL/dcolors (read by the SH backward)
+    | dL/dopacities: zero-filled, or left empty for the deterministic backward, which writes every row of both itself.  One for
+    what the preprocess backward writes for EVERY Gaussian (zeros for culled ones): dL/dmeans3D | dL/dmeans2D [P, m2] |
+    dL/dscales | dL/drotations, or | dL/dcov3D with `cov_form`.  rows: the rows allocated (default P)."""
+    rows = P if rows is None else rows
+    acc = (torch.zeros if zero_acc else torch.empty)(rows * 4, dtype=torch.float32, device=dev)
+    rest = torch.empty(rows * (3 + m2 + (6 if cov_form else 7)), dtype=torch.float32, device=dev)
+    at = (3 + m2) * P
+    return _BackwardBuffers(
+        rest, rest[:3 * P].view(P, 3), rest[3 * P:at].view(P, m2), acc[:3 * P].view(P, 3),
+        acc[3 * P:4 * P].view(opac_shape or (P, 1)),
+        None if cov_form else rest[at:at + 3 * P].view(P, 3), None if cov_form else rest[at + 3 * P:at + 7 * P].view(P, 4),
+        rest[at:at + 6 * P].view(P, 6) if cov_form else None)
+
+
+def launch_backward(view, inputs, D, M, g, maps, grads, stream, opts=0, absgrad=False, deterministic=False,
                     features=None, geometry=None):
     """The one cgs_raster_backward* call of a view, for both autograd nodes (_RasterizeGaussians, renderer._ExpandRasterize).
-    inputs: (means3D, colors, shs, opacities, scales, rotations, cov3D, radii), None for what the form does not have;
-    workspaces: (geom, binning or None, img) and R the count the binning workspace was carved with; g, maps: the upstream
-    gradients of the colour image and of the depth / inverse-depth / alpha maps (None: no gradient); grads: (dL_dmeans3D,
+    view: the _KeptView; inputs: (means3D, colors, shs, opacities, scales, rotations, cov3D, radii), None for what the form does
+    not have; g, maps: the upstream gradients of the colour image and of the depth / inverse-depth / alpha maps (None: no
+    gradient); grads: (dL_dmeans3D,
     dL_dmeans2D [P, 4 with absgrad else 3], dL_dcolors, dL_dopacities, dL_dshs, dL_dscales, dL_drotations, dL_dcov3D), the
     caller's buffers (dL_dcolors / dL_dopacities zero-filled unless `deterministic`); features: (features, the feature map's
     gradient, dL_dfeatures zero-filled) or None; geometry: (moments, median_id, the distortion map's gradient, the median-depth
@@ -507,8 +599,7 @@ def launch_backward(cfg, P, R, inputs, D, M, workspaces, g, maps, grads, stream,
     L = _lib.lib()
     p = _lib.ptr
     means3D, colors, shs, opac, scales, rots, cov, radii = inputs
-    geom, binws, img = workspaces
-    dev = means3D.device
+    P, dev = view.P, means3D.device
     feat, g_fmap, d_feat = features if features is not None else (None, None, None)
     m2 = 4 if absgrad else 3        # columns of dL/dmeans2D
     map_ptrs = tuple(p(t) for t in maps)
@@ -528,12 +619,12 @@ def launch_backward(cfg, P, R, inputs, D, M, workspaces, g, maps, grads, stream,
         name, scratch_bytes, map_ptrs, tail, cam_opts = "cgs_raster_backward_ex", L.cgs_raster_bwd_scratch_bytes(P), (), (), 0
     scratch = _workspace(scratch_bytes, dev)
     if deterministic:
-        det_ws = _workspace(L.cgs_raster_bwd_det_bytes(P, R, m2), dev)
+        det_ws = _workspace(L.cgs_raster_bwd_det_bytes(P, view.R, m2), dev)
         tail = (opts, m2, p(det_ws), det_ws.numel())
+    kept = view.args()
     _lib.check(getattr(L, name)(
-        cfg.ref, P, R, p(means3D), p(colors), p(shs), D, M, p(opac), p(scales), p(rots), p(cov), p(radii), p(geom), geom.numel(),
-        p(binws), binws.numel() if binws is not None else 0, p(img), img.numel(), p(g), *map_ptrs, *(p(t) for t in grads),
-        p(scratch), scratch.numel(), stream, *tail), name)
+        *kept[:3], p(means3D), p(colors), p(shs), D, M, p(opac), p(scales), p(rots), p(cov), p(radii), *kept[3:],
+        p(g), *map_ptrs, *(p(t) for t in grads), p(scratch), scratch.numel(), stream, *tail), name)
     return scratch, cam_opts
 
 
@@ -556,15 +647,18 @@ class _RasterizeGaussians(torch.autograd.Function):
     cgs_raster_backward_det: no float atomics, bit-reproducible gradients (module docstring).
     With `geometry` one more walk gives the distortion and median-depth maps and the non-differentiable median_id behind the
     contrib maps (cgs_raster_render_geom); its moments and median_id are saved, and when one of the two maps got a gradient the
-    backward is cgs_raster_backward_geom (module docstring)."""
+    backward is cgs_raster_backward_geom (module docstring).
+    `aux`, `contrib` (with `contrib_slots`), `absgrad`, `deterministic` and `geometry` are fields of `request`, a RasterRequest,
+    of which the node keeps the flags only.  Nothing here counts positions: the outputs, and the gradients that come back for
+    them, go by output_names(); the gradients returned, and ctx.needs_input_grad, by INPUT_NAMES."""
 
     @staticmethod
-    def forward(ctx, aux, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings,
-                viewmatrix, projmatrix, campos, features=None, contrib=None, contrib_slots=None, absgrad=False,
-                deterministic=False, geometry=False):
+    def forward(ctx, request, means3D, means2D, shs, colors, opacities, scales, rotations, cov3D, raster_settings,
+                viewmatrix, projmatrix, campos, features):
         # viewmatrix / projmatrix / campos: the settings' three camera tensors once more, as inputs of the node so that autograd
         # can hand them a gradient; the forward reads them through _Cfg as before
         L = _lib.lib()
+        contrib, contrib_slots = request.contrib, request.contrib_slots
         _lib.require_device(means3D, shs, colors, opacities, scales, rotations, cov3D, features, contrib_slots,
                             *(contrib.tensors() if isinstance(contrib, GaussianContrib) else ()))
         means3D, shs, colors, opac, scales, rots, cov, feat = (
@@ -591,109 +685,89 @@ class _RasterizeGaussians(torch.autograd.Function):
             _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(geom), geom.numel(), _lib.ptr(radii), stream, C.byref(ticket), opts),
             "cgs_raster_preprocess_launch_opt")
         binws, bin_R, _num_rendered = bin_and_blend(cfg, P, geom, img, color, stream, ticket)
-        outs = (color, radii)
-        nondiff = (radii,)
-        if aux:     # behind the render bin_and_blend kept (a voided speculative render has been redone by now)
-            maps = [torch.empty(1, H, W, dtype=torch.float32, device=dev) for _ in range(3)]
-            _lib.check(L.cgs_raster_render_aux(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
-                                               binws.numel(), _lib.ptr(img), img.numel(), _lib.ptr(maps[0]),
-                                               _lib.ptr(maps[1]), _lib.ptr(maps[2]), stream), "cgs_raster_render_aux")
-            outs += tuple(maps)
-        if contrib is not None:     # likewise; accumulates into the caller's object, every pixel of the maps is written
-            top_id = torch.empty(H, W, dtype=torch.int32, device=dev)
-            top_w = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-            count = torch.empty(H, W, dtype=torch.int32, device=dev)
+        # every further walk runs behind the render bin_and_blend kept (a voided speculative render has been redone by now) and
+        # writes every pixel of its maps
+        kept = _KeptView(cfg, P, bin_R, geom, binws, img).args()
+        new = lambda *shape, dtype=torch.float32, make=torch.empty: make(*shape, dtype=dtype, device=dev)
+        out = {"color": color, "radii": radii}
+        if request.aux:
+            out.update((n, new(1, H, W)) for n in AUX_MAPS)
+            _lib.check(L.cgs_raster_render_aux(*kept, *(_lib.ptr(out[n]) for n in AUX_MAPS), stream), "cgs_raster_render_aux")
+        if contrib is not None:     # accumulates into the caller's object
+            out.update(top_id=new(H, W, dtype=torch.int32), top_weight=new(1, H, W), count=new(H, W, dtype=torch.int32))
             # (P == 0: no row can be touched, and an empty slot table has no pointer to tell it from an absent one)
             accs = [_lib.ptr(t) for t in contrib.tensors()] if P > 0 else [None] * 4
-            _lib.check(L.cgs_raster_contrib(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws), binws.numel(),
-                                            _lib.ptr(img), img.numel(), _lib.ptr(contrib_slots) if P > 0 else None,
-                                            len(contrib) if P > 0 else 0, *accs, _lib.ptr(top_id), _lib.ptr(top_w),
-                                            _lib.ptr(count), stream), "cgs_raster_contrib")
+            _lib.check(L.cgs_raster_contrib(*kept, _lib.ptr(contrib_slots) if P > 0 else None, len(contrib) if P > 0 else 0,
+                                            *accs, *(_lib.ptr(out[n]) for n in CONTRIB_MAPS), stream), "cgs_raster_contrib")
             contrib.views += 1
-            outs += (top_id, top_w, count)
-            nondiff += (top_id, top_w, count)
         geom_saved = ()
-        if geometry:    # likewise; every pixel is written (P == 0: the call enqueues nothing, the fills below stand)
-            new = torch.empty if P > 0 else torch.zeros
-            gmaps = [new(1, H, W, dtype=torch.float32, device=dev) for _ in range(2)]
-            med_id = new(H, W, dtype=torch.int32, device=dev) if P > 0 else torch.full((H, W), -1, dtype=torch.int32, device=dev)
-            moments = new(2, H, W, dtype=torch.float32, device=dev)
-            _lib.check(L.cgs_raster_render_geom(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws), binws.numel(),
-                                                _lib.ptr(img), img.numel(), _lib.ptr(gmaps[0]), _lib.ptr(gmaps[1]),
-                                                _lib.ptr(med_id), _lib.ptr(moments), stream), "cgs_raster_render_geom")
-            ctx.geom_at = len(outs) - 2       # where the two maps' gradients sit in the backward's *grad_rest
-            outs += (gmaps[0], gmaps[1], med_id)
-            nondiff += (med_id,)
-            geom_saved = (moments, med_id)
-        if feat is not None:    # likewise; every pixel is written
-            fmap = torch.empty(feat.shape[1], H, W, dtype=torch.float32, device=dev)
-            _lib.check(L.cgs_raster_render_features(cfg.ref, P, bin_R, _lib.ptr(geom), geom.numel(), _lib.ptr(binws),
-                                                    binws.numel(), _lib.ptr(img), img.numel(), _lib.ptr(feat), feat.shape[1],
-                                                    _lib.ptr(fmap), stream), "cgs_raster_render_features")
-            outs += (fmap,)
-        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M, ctx.opts, ctx.aux = cfg, bin_R, D, M, opts, bool(aux)
-        ctx.absgrad = bool(absgrad)
-        ctx.deterministic = bool(deterministic)
-        ctx.geometry = bool(geometry)
+        if request.geometry:    # (P == 0: the call enqueues nothing, the fills below stand)
+            make = torch.empty if P > 0 else torch.zeros
+            out.update(distortion=new(1, H, W, make=make), median_depth=new(1, H, W, make=make))
+            out["median_id"] = (new(H, W, dtype=torch.int32) if P > 0
+                                else torch.full((H, W), -1, dtype=torch.int32, device=dev))
+            moments = new(2, H, W, make=make)
+            _lib.check(L.cgs_raster_render_geom(*kept, *(_lib.ptr(out[n]) for n in GEOMETRY_MAPS), _lib.ptr(moments), stream),
+                       "cgs_raster_render_geom")
+            geom_saved = (moments, out["median_id"])
+        if feat is not None:
+            out["features"] = new(feat.shape[1], H, W)
+            _lib.check(L.cgs_raster_render_features(*kept, _lib.ptr(feat), feat.shape[1], _lib.ptr(out["features"]), stream),
+                       "cgs_raster_render_features")
+        ctx.cfg, ctx.num_rendered, ctx.D, ctx.M, ctx.opts, ctx.request = cfg, bin_R, D, M, opts, request.flags()
         ctx.save_for_backward(means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat, *geom_saved)
-        ctx.mark_non_differentiable(*nondiff)      # ONE call: torch keeps only the last call's arguments
-        return outs
+        names = output_names(request, feat is not None)
+        ctx.mark_non_differentiable(*(out[n] for n in names if n in NON_DIFFERENTIABLE))      # ONE call: torch keeps only the last
+        return tuple(out[n] for n in names)
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, *grad_rest):
+    def backward(ctx, *grad_outputs):
         L = _lib.lib()
         means3D, shs, colors, opac, scales, rots, cov, radii, geom, binws, img, feat, *geom_saved = ctx.saved_tensors
-        grad_maps = grad_rest[:3] if ctx.aux else ()
-        g_geom = [None if t is None else _f32c(t) for t in grad_rest[ctx.geom_at:ctx.geom_at + 2]] if ctx.geometry else []
+        req = ctx.request
+        g = {k: None if t is None else _f32c(t) for k, t in zip(output_names(req, feat is not None), grad_outputs)}
+        maps = [g.get(k) for k in AUX_MAPS]
+        g_geom = [g.get("distortion"), g.get("median_depth")]
         with_geom = any(t is not None for t in g_geom)       # (neither map got a gradient: the backward of a call without them)
-        g_fmap = _f32c(grad_rest[-1]) if (feat is not None and grad_rest[-1] is not None) else None
-        cfg = ctx.cfg
-        P = means3D.shape[0]
-        dev = means3D.device
-        g, *maps = (None if t is None else _f32c(t) for t in (grad_color, *grad_maps, None, None, None)[:4])
-        if g is None and g_fmap is None and all(t is None for t in maps) and not with_geom:
-            return (None,) * 19
-        # the blends accumulate dL/dcolor (read by the SH backward) and dL/dopacity atomically: one zero fill for both; the
-        # other arrays are written for EVERY Gaussian by the preprocess backward (zeros for culled ones).  The deterministic
-        # backward writes every row of both itself.
-        acc = (torch.empty if ctx.deterministic else torch.zeros)(P * 4, dtype=torch.float32, device=dev)
-        d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:].view(opac.shape)
-        m2 = 4 if (ctx.absgrad or with_geom) else 3     # columns of dL/dmeans2D (cgs_raster_backward_geom: always four)
-        rest = torch.empty(P * (3 + m2 + (7 if cov is None else 6)), dtype=torch.float32, device=dev)
-        d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:(3 + m2) * P].view(P, m2)
-        d_scales = rest[(3 + m2) * P:(6 + m2) * P].view(P, 3) if cov is None else None
-        d_rots = rest[(6 + m2) * P:].view(P, 4) if cov is None else None
-        d_cov = rest[(3 + m2) * P:].view(P, 6) if cov is not None else None
+        with_feat = g.get("features") is not None
+        grads = dict.fromkeys(INPUT_NAMES)
+        if g["color"] is None and not with_feat and all(t is None for t in maps) and not with_geom:
+            return tuple(grads.values())
+        view = _KeptView(ctx.cfg, means3D.shape[0], ctx.num_rendered, geom, binws, img)
+        P, dev = view.P, means3D.device
+        m2 = 4 if (req.absgrad or with_geom) else 3     # columns of dL/dmeans2D (cgs_raster_backward_geom: always four)
+        b = carve_backward_buffers(P, m2, dev, cov is not None, not req.deterministic, opac_shape=opac.shape)
         d_shs = torch.empty_like(shs) if shs is not None else None      # of its own: aligned as shs is (vector stores)
-        with_feat = g_fmap is not None
         d_feat = torch.zeros_like(feat) if with_feat else None          # accumulated atomically, like dL/dcolor
         stream = _lib.current_stream()
         scratch, cam_opts = launch_backward(
-            cfg, P, ctx.num_rendered, (means3D, colors, shs, opac, scales, rots, cov, radii), ctx.D, ctx.M, (geom, binws, img),
-            g, maps, (d_means3D, d_means2D, d_colors, d_opac, d_shs, d_scales, d_rots, d_cov), stream, ctx.opts, ctx.absgrad,
-            ctx.deterministic, (feat, g_fmap, d_feat) if with_feat else None, (*geom_saved, *g_geom) if with_geom else None)
+            view, (means3D, colors, shs, opac, scales, rots, cov, radii), ctx.D, ctx.M, g["color"], maps,
+            (b.means3D, b.means2D, b.colors, b.opac, d_shs, b.scales, b.rots, b.cov), stream, ctx.opts, req.absgrad,
+            req.deterministic, (feat, g["features"], d_feat) if with_feat else None,
+            (*geom_saved, *g_geom) if with_geom else None)
         # the camera: only when one of its tensors asks (campos without shs is unused: None), behind the backward above while
         # its scratch and its dL_dcolors / dL_dopacities are intact
-        need_v, need_p, need_c = ctx.needs_input_grad[10:13]
-        need_c = need_c and shs is not None
-        d_view = d_proj = d_campos = None
-        if need_v or need_p or need_c:
+        need = dict(zip(INPUT_NAMES, ctx.needs_input_grad))
+        need["campos"] = need["campos"] and shs is not None
+        if need["viewmatrix"] or need["projmatrix"] or need["campos"]:
             cam = torch.empty(35, dtype=torch.float32, device=dev)
-            d_view = cam[:16].view(4, 4) if need_v else None
-            d_proj = cam[16:32].view(4, 4) if need_p else None
-            d_campos = cam[32:] if need_c else None
+            grads.update(viewmatrix=cam[:16].view(4, 4) if need["viewmatrix"] else None,
+                         projmatrix=cam[16:32].view(4, 4) if need["projmatrix"] else None,
+                         campos=cam[32:] if need["campos"] else None)
             work = _workspace(L.cgs_raster_camera_bytes(P), dev)
             _lib.check(L.cgs_raster_camera_backward(
-                cfg.ref, P, _lib.ptr(means3D), _lib.ptr(shs) if need_c else None, ctx.D, ctx.M, _lib.ptr(opac), _lib.ptr(scales),
-                _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(scratch), scratch.numel(), _lib.ptr(d_colors),
-                _lib.ptr(d_opac), cam_opts, _lib.ptr(d_view), _lib.ptr(d_proj),
-                _lib.ptr(d_campos), _lib.ptr(work), work.numel(), stream), "cgs_raster_camera_backward")
-        if g is None:       # the maps and the features send no gradient to the colour inputs
-            d_shs = d_colors = None
-        if with_geom and not ctx.absgrad:       # means2D is [P, 3]: the signed columns and the zero every [P, 3] backward writes
+                view.cfg.ref, P, _lib.ptr(means3D), _lib.ptr(shs) if need["campos"] else None, ctx.D, ctx.M, _lib.ptr(opac),
+                _lib.ptr(scales), _lib.ptr(rots), _lib.ptr(cov), _lib.ptr(radii), _lib.ptr(scratch), scratch.numel(),
+                _lib.ptr(b.colors), _lib.ptr(b.opac), cam_opts, _lib.ptr(grads["viewmatrix"]), _lib.ptr(grads["projmatrix"]),
+                _lib.ptr(grads["campos"]), _lib.ptr(work), work.numel(), stream), "cgs_raster_camera_backward")
+        d_means2D = b.means2D
+        if with_geom and not req.absgrad:       # means2D is [P, 3]: the signed columns and the zero every [P, 3] backward writes
             d_means2D = torch.nn.functional.pad(d_means2D[:, :2], (0, 1))
-        return (None, d_means3D, d_means2D, d_shs, d_colors if colors is not None else None, d_opac, d_scales, d_rots,
-                d_cov, None, d_view, d_proj, d_campos, d_feat, None, None, None, None, None)
+        grads.update(means3D=b.means3D, means2D=d_means2D, opacities=b.opac, scales=b.scales, rotations=b.rots, cov3D=b.cov,
+                     features=d_feat)
+        if g["color"] is not None:       # the maps and the features send no gradient to the colour inputs
+            grads.update(shs=d_shs, colors=b.colors if colors is not None else None)
+        return tuple(grads.values())
 
 
 def _camera_inputs(rs):
@@ -703,8 +777,8 @@ def _camera_inputs(rs):
 
 
 def rasterize_gaussians(means3D, means2D, colors_precomp, opacities, scales, rotations, raster_settings):
-    return _RasterizeGaussians.apply(False, means3D, means2D, None, colors_precomp, opacities, scales, rotations, None,
-                                     raster_settings, *_camera_inputs(raster_settings))
+    return _RasterizeGaussians.apply(RasterRequest(), means3D, means2D, None, colors_precomp, opacities, scales, rotations, None,
+                                     raster_settings, *_camera_inputs(raster_settings), None)
 
 
 def raster_stats(raster_settings: GaussianRasterizationSettings, img_ws: torch.Tensor) -> torch.Tensor:
@@ -774,24 +848,11 @@ class GaussianRasterizer(nn.Module):
         check_contrib(contrib, contrib_slots, means3D)
         if contrib is True:
             contrib = GaussianContrib.zeros(means3D.shape[0], means3D.device)
-        out = _RasterizeGaussians.apply(bool(return_aux), means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                        cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings), features,
-                                        contrib, contrib_slots,
-                                        *((bool(absgrad), False, True) if return_geometry else (bool(absgrad), True) if deterministic
-                                          else (True,) if absgrad else ()))
-        if not return_aux and features is None and contrib is None and not return_geometry:
+        request = RasterRequest(bool(return_aux), contrib, contrib_slots, bool(absgrad), deterministic, bool(return_geometry),
+                                3 if return_normals else 0)
+        out = _RasterizeGaussians.apply(request, means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                        cov3D_precomp, self.raster_settings, *_camera_inputs(self.raster_settings), features)
+        names = output_names(request, features is not None)
+        if len(names) == 2:
             return out
-        extras = {}
-        if return_aux:
-            extras.update(depth=out[2], invdepth=out[3], alpha=out[4])
-        if contrib is not None:
-            k = 5 if return_aux else 2
-            extras.update(contrib=contrib, top_id=out[k], top_weight=out[k + 1], count=out[k + 2])
-        if return_geometry:
-            k = 2 + (3 if return_aux else 0) + (3 if contrib is not None else 0)
-            extras.update(distortion=out[k], median_depth=out[k + 1], median_id=out[k + 2])
-        if user_features is not None:
-            extras["features"] = out[-1][:-3] if return_normals else out[-1]
-        if return_normals:
-            extras["normals"] = out[-1][-3:]
-        return out[0], out[1], extras
+        return out[0], out[1], named_extras(request, user_features is not None, dict(zip(names, out)))

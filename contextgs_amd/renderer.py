@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from . import _lib, anchor_gen, ctx_ops, mlp
 from .context_model import (LazyRows, begin_step, early_levels_begin, early_visible_rows, gather_unique, gather_unique_attach,
                             gather_unique_pair_attach, gather_unique_values, multi_scale_generating_visible)
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, check_deterministic
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, RasterRequest, check_deterministic
 
 Q_FEAT, Q_SCALING, Q_OFFSETS = 1, 0.001, 0.2      # :40-42
 
@@ -249,29 +249,26 @@ class _ExpandRasterize(torch.autograd.Function):
         xyz, scaling, rot, radii, geom, binws, img = saved[7:]
         cfg, K, n, src_row, P = ctx.cfg, ctx.K, ctx.n, ctx.src_row, ctx.P
         dev, stream = xyz.device, _lib.current_stream()
-        # ---- the rasterizer's backward (rasterizer.launch_backward) into buffers that stay inside this node
-        use_det = g_img is not None and P > 0 and ctx.deterministic
-        # atomically accumulated: dL/d colour | opacity (the deterministic backward writes every row of both itself)
-        acc = (torch.empty if use_det else torch.zeros)(max(P, 1) * 4, dtype=torch.float32, device=dev)
-        d_colors, d_opac = acc[:3 * P].view(P, 3), acc[3 * P:4 * P].view(P, 1)
-        m2 = 4 if ctx.absgrad else 3        # columns of dL/dmeans2D
-        rest = torch.empty(max(P, 1) * (10 + m2), dtype=torch.float32, device=dev)
-        d_means3D, d_means2D = rest[:3 * P].view(P, 3), rest[3 * P:(3 + m2) * P].view(P, m2)
-        d_scales, d_rots = rest[(3 + m2) * P:(6 + m2) * P].view(P, 3), rest[(6 + m2) * P:(10 + m2) * P].view(P, 4)
-        if g_img is not None and P > 0:
+        # ---- the rasterizer's backward (rasterizer.launch_backward) into buffers that stay inside this node: the unfused
+        # node's carve, at least one row allocated, and zero-filled unless the deterministic backward runs
+        launch = g_img is not None and P > 0
+        b = rz.carve_backward_buffers(P, 4 if ctx.absgrad else 3, dev, zero_acc=not (launch and ctx.deterministic),
+                                      rows=max(P, 1))
+        if launch:
             # the plain form's arguments; the colours never existed as a tensor and the backward of this form does not read
             # them (the pointer only says "colours, not SH": include/cgs.h), so the gradient buffer stands in
-            rz.launch_backward(cfg, P, ctx.num_rendered, (xyz, d_colors, None, None, scaling, rot, None, radii), 0, 0,
-                               (geom, binws, img), rz._f32c(g_img), (None, None, None),
-                               (d_means3D, d_means2D, d_colors, d_opac, None, d_scales, d_rots, None), stream, 0, ctx.absgrad,
+            rz.launch_backward(rz._KeptView(cfg, P, ctx.num_rendered, geom, binws, img),
+                               (xyz, b.colors, None, None, scaling, rot, None, radii), 0, 0, rz._f32c(g_img), (None, None, None),
+                               (b.means3D, b.means2D, b.colors, b.opac, None, b.scales, b.rots, None), stream, 0, ctx.absgrad,
                                ctx.deterministic)
         else:
-            rest.zero_()
+            b.rest.zero_()
+        d_scales = b.scales
         if g_scaling is not None:            # the loss reads `scaling` too (train.py:204): what autograd would have summed
             d_scales = d_scales + _c(g_scaling)
         g_no = _c(g_no) if g_no is not None else None
-        return (*_expand_backward(saved[:7], n, K, src_row, d_means3D, d_colors, d_opac, d_scales, d_rots, g_no, stream),
-                d_means2D, None, None, None, None, None, None)
+        return (*_expand_backward(saved[:7], n, K, src_row, b.means3D, b.colors, b.opac, d_scales, b.rots, g_no, stream),
+                b.means2D, None, None, None, None, None, None)
 
 
 def _anchor_mlps(pc, x):
@@ -736,7 +733,10 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         slots = []
     else:
         contrib = None
-    side = return_aux or return_geometry or return_normals or rows is not None or slots is not None   # the rasterizer returns a third value
+    # what the rasterizer is asked for (deterministic: resolved above, the rasterizer does not read the environment again);
+    # the slot table follows once the view's Gaussians exist
+    request = RasterRequest(bool(return_aux), contrib, None, bool(absgrad), deterministic, return_geometry,
+                            3 if return_normals else 0)
     settings = _raster_settings(viewpoint_camera, pipe, bg_color, scaling_modifier)
     view = _view_fusion(is_training, return_aux, return_geometry, settings.antialiasing, cam_grad, anchor_features, contrib,
                         settings, retain_grad, absgrad, deterministic, return_normals)
@@ -749,19 +749,12 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     screenspace_points = _zero_points(xyz, 4 if absgrad else 3)       # :168 `torch.zeros_like(xyz, requires_grad=True) + 0`
     _retain_grad(screenspace_points, retain_grad)
     rasterizer = GaussianRasterizer(settings)
-    more = dict(absgrad=True) if absgrad else {}
-    more.update(deterministic=deterministic)      # (resolved above: the rasterizer does not read the environment again)
-    if side:
-        if slots is not None:
-            more.update(contrib=contrib, contrib_slots=slots[0])
-        if return_geometry:
-            more.update(return_geometry=True)
-        if return_normals:
-            more.update(return_normals=True)
-        more.update(features=anchor_features.index_select(0, rows[0]) if rows is not None else None,      # plumbing: plain torch
-                    return_aux=return_aux)
-    rendered_image, radii, *aux = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
-                                             opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None, **more)
+    if slots is not None:
+        request = request._replace(contrib_slots=slots[0])
+    rendered_image, radii, *aux = rasterizer(
+        means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color, opacities=opacity, scales=scaling,
+        rotations=rot, cov3D_precomp=None, **request.keywords(),
+        features=anchor_features.index_select(0, rows[0]) if rows is not None else None)      # plumbing: plain torch
     if slots is not None:       # a Gaussian index means nothing outside this call: one gather to slot ids, -1 kept
         tid = aux[0]["top_id"].long()
         table = torch.cat([slots[0], slots[0].new_full((1,), -1)])      # (index -1 reads the appended -1)
@@ -771,7 +764,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     else:
         out = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
                "radii": radii, "time_sub": rest[0]}
-    if side:
+    if aux:     # the rasterizer returned a third value
         out.update(aux[0])
     return out
 

@@ -113,11 +113,11 @@ def test_check_deterministic_reads_the_environment(monkeypatch):
 
 def test_keyword_surfaces():
     from contextgs_amd import renderer
-    from contextgs_amd.rasterizer import GaussianRasterizer, _RasterizeGaussians
+    from contextgs_amd.rasterizer import GaussianRasterizer, RasterRequest
     assert inspect.signature(GaussianRasterizer.forward).parameters["deterministic"].default is None
     p = inspect.signature(renderer.render).parameters["deterministic"]
     assert p.default is None and p.kind is inspect.Parameter.KEYWORD_ONLY
-    assert inspect.signature(_RasterizeGaussians.forward).parameters["deterministic"].default is False
+    assert RasterRequest._field_defaults["deterministic"] is False
     assert inspect.signature(renderer.ViewFusion.__init__).parameters["deterministic"].default is False
 
 

@@ -213,12 +213,12 @@ def test_check_deterministic_old_call_forms_are_unchanged(monkeypatch):
 def test_keyword_surfaces():
     from contextgs_amd import renderer
     from contextgs_amd.dropin import diff_gaussian_rasterization as shim
-    from contextgs_amd.rasterizer import GaussianRasterizer, _RasterizeGaussians
+    from contextgs_amd.rasterizer import GaussianRasterizer, RasterRequest
     assert inspect.signature(GaussianRasterizer.forward).parameters["return_geometry"].default is False
     assert inspect.signature(shim.GaussianRasterizer.forward).parameters["return_geometry"].default is False
     p = inspect.signature(renderer.render).parameters["return_geometry"]
     assert p.default is False and p.kind is inspect.Parameter.KEYWORD_ONLY
-    assert inspect.signature(_RasterizeGaussians.forward).parameters["geometry"].default is False
+    assert RasterRequest._field_defaults["geometry"] is False
     for needle in ("return_geometry", "distortion[p]", "median_depth[p]", "median_id[p]"):
         import contextgs_amd.rasterizer as rz
         assert needle in rz.__doc__, needle
