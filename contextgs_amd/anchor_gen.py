@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .mlp import _ptr_array, _zeros_views, anchor_mlp3_params, anchor_mlp3_supported
+from .mlp import _anchor_wgrad_views, _f32c, _m3_split, _ptr_array, anchor_mlp3_params, anchor_mlp3_supported
 
 K_FUSED = 10
 # Which calls take the fused node ("all" | "nograd" | "off"; every setting computes the same function).  Measured on
@@ -22,10 +22,6 @@ K_FUSED = 10
 MODE = os.environ.get("CGS_ANCHOR_GEN", "nograd")
 ENABLED = MODE != "off"
 FUSED_WGRAD = os.environ.get("CGS_ANCHOR_GEN_WGRAD", "0") != "0"
-
-
-def _f32c(t):
-    return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
 
 
 def supported(mo: nn.Sequential, mc: nn.Sequential, mv: nn.Sequential, K: int, *tensors) -> bool:
@@ -51,8 +47,7 @@ class _AnchorGen(torch.autograd.Function):
         assert masks.numel() == n * K_FUSED and off_src.numel() == gs_src.shape[0] * 3 * K_FUSED
         for r, src in ((feat_row, feat_src), (geo_row, gs_src)):
             assert (r is None and src.shape[0] == n) or (r is not None and r.dtype == torch.int64 and r.numel() == n)
-        p = [t.detach().contiguous() for t in params]
-        W1, b1, W2, b2 = p[0::4], p[1::4], p[2::4], p[3::4]
+        W1, b1, W2, b2 = _m3_split(params)
         dev = feat_src.device
         need_grad = any(ctx.needs_input_grad)
         stream = _lib.current_stream()
@@ -109,8 +104,7 @@ class _AnchorGen(torch.autograd.Function):
         d_gs, d_off = flat[:gs_src.numel()].view_as(gs_src), flat[gs_src.numel():].view(ctx.off_shape)
         d_anchor = torch.empty(n, 3, dtype=torch.float32, device=dev)
         d_mask = torch.empty_like(masks)
-        views = _zeros_views(dev, (150, 54), (150,), *[tuple(w.shape) for w in W2], *[(w.shape[0],) for w in W2])
-        dW1cat, db1cat, dW2, db2 = views[0], views[1], list(views[2:5]), list(views[5:8])
+        dW1cat, db1cat, dW2, db2, wgrads = _anchor_wgrad_views(dev, W2, 150, 50)
         fused = 1 if FUSED_WGRAD else 0
         ws = torch.empty(int(L.cgs_anchor_gen_bwd_scratch_bytes(n, fused)), dtype=torch.uint8, device=dev)
         _lib.check(L.cgs_anchor_gen_backward(
@@ -124,9 +118,7 @@ class _AnchorGen(torch.autograd.Function):
         need = ctx.needs_input_grad
         grads = [d_feat if need[0] else None, None, d_anchor if need[2] else None, None, d_gs if need[4] else None,
                  d_off if need[5] else None, None, d_mask if need[7] else None]
-        for i in range(3):
-            grads += [dW1cat[50 * i:50 * (i + 1)], db1cat[50 * i:50 * (i + 1)], dW2[i], db2[i]]
-        return tuple(grads)
+        return tuple(grads + wgrads)
 
 
 def anchor_gen(feat_src, feat_row, anchor_vis, cam_center, gs_src, off_src, geo_row, masks,

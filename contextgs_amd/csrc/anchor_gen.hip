@@ -689,20 +689,9 @@ __global__ void __launch_bounds__(WAVES * 64) ag_bwd_kernel(AgBwdArgs a) {
 }
 
 // ---- host side of the C-ABI --------------------------------------------------------------------
-static int ag_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 static int ag_grid(int64_t tiles, int waves) {
     const int64_t want = (tiles + waves - 1) / waves;
-    return (int)(want < ag_cus() ? want : ag_cus());
+    return (int)(want < cgs_num_cus() ? want : cgs_num_cus());
 }
 
 // Opacity head, mask, survivor bookkeeping.  base16 [ceil(n/16) + 1]: exclusive prefix of the survivor counts per
@@ -772,10 +761,10 @@ extern "C" int cgs_anchor_gen_write(const float *feat_src, const int64_t *feat_r
 }
 
 extern "C" size_t cgs_anchor_gen_bwd_scratch_bytes(int64_t n, int fused) {
-    const size_t part = (size_t)ag_cus() * AG_E * sizeof(float) + 256;
+    const size_t part = (size_t)cgs_num_cus() * AG_E * sizeof(float) + 256;
     if (fused) return part;
     // X [n,54], Hcat [n,150], dZ1cat [n,150], dZ2 [n,10+30+70] + the two-pass weight-gradient partials
-    return (size_t)n * (54 + 150 + 150 + 110) * sizeof(float) + 8 * 256 + cgs_wgrad_scratch_bytes_for(ag_cus());
+    return (size_t)n * (54 + 150 + 150 + 110) * sizeof(float) + 8 * 256 + cgs_wgrad_scratch_bytes_for(cgs_num_cus());
 }
 
 
@@ -840,7 +829,7 @@ extern "C" int cgs_anchor_gen_backward(const float *feat_src, const int64_t *fea
     a.dZ2_op = cv.take<float>((size_t)n * 10);
     a.dZ2_col = cv.take<float>((size_t)n * 30);
     a.dZ2_cov = cv.take<float>((size_t)n * 70);
-    const size_t wbytes = cgs_wgrad_scratch_bytes_for(ag_cus());
+    const size_t wbytes = cgs_wgrad_scratch_bytes_for(cgs_num_cus());
     void *wscratch = cv.take<char>(wbytes);
     if (!cv.ok) { cgs_set_error("anchor_gen_backward: scratch too small"); return CGS_ERR_WORKSPACE; }
     {
@@ -853,5 +842,5 @@ extern "C" int cgs_anchor_gen_backward(const float *feat_src, const int64_t *fea
                                    {a.dZ2_op, 10, 10, a.Hcat, 150, 50, dW2[0], db2[0]},
                                    {a.dZ2_col, 30, 30, a.Hcat + 50, 150, 50, dW2[1], db2[1]},
                                    {a.dZ2_cov, 70, 70, a.Hcat + 100, 150, 50, dW2[2], db2[2]}};
-    return cgs_launch_wgrad_multi(prods, 4, n, ag_cus(), wscratch, wbytes, stream);
+    return cgs_launch_wgrad_multi(prods, 4, n, cgs_num_cus(), wscratch, wbytes, stream);
 }

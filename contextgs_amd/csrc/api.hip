@@ -14,6 +14,17 @@ void cgs_set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
+int cgs_num_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t p;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
+        if (cus <= 0) cus = 256;
+    }
+    return cus;
+}
+
 extern "C" const char *cgs_last_error(void) { return g_err; }
 extern "C" int cgs_version(void) { return CGS_VERSION; }
 #ifndef CGS_SOURCE_DIGEST

@@ -11,6 +11,7 @@
 
 void cgs_set_error(const char *fmt, ...);
 uint64_t cgs_new_ticket(int kind);      // api.hip: tickets of the *_launch / *_wait pairs (kind: 1 raster, 2 expand, 3 nonzero)
+int cgs_num_cus();                      // api.hip: compute units of the device (cached; 256 if the query fails): grid and scratch sizes
 
 #define CGS_CHECK_HIP(expr)                                                   \
     do {                                                                      \

@@ -713,17 +713,6 @@ ctxl_bwd_kernel(typename std::conditional<HS, ClBwdArgsH, ClBwdArgs>::type a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
-static int cl_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 static bool cl_fits(int64_t rows, int64_t row_bytes) { return rows >= 0 && (uint64_t)rows * (uint64_t)row_bytes < CL_MAX_BYTES; }
 // ctx_noise_k32 (the kernels' 32-bit element indices r * width + column) rests on this bound: both launchers require
 // cl_fits(n, CL_D * 4), so n * CL_D < CL_MAX_BYTES / 4 <= 2^30, and CL_D is the widest of the three noisy tensors
@@ -762,7 +751,7 @@ extern "C" int cgs_ctx_level_fwd_h(int in_dim, const float *anchor, int64_t n_an
     a.q0f = q0f; a.q0s = q0s; a.q0o = q0o;
     a.X = X; a.yf = yf; a.ys = ys; a.yo = yo; a.Q = Q; a.sums = sums3; a.H = H;
     const int64_t tiles = (n + 15) / 16, want = (tiles + CLF_WAVES - 1) / CLF_WAVES;
-    const int64_t cap = (int64_t)CLF_GRID * cl_cus();
+    const int64_t cap = (int64_t)CLF_GRID * cgs_num_cus();
     const unsigned grid = (unsigned)(want < cap ? want : cap);
     CgsProfScope prof(CGS_PROF_CTX_FWD, (hipStream_t)stream);
     const dim3 gr(grid), bl(CLF_WAVES * 64);
@@ -785,7 +774,7 @@ extern "C" int cgs_ctx_level_fwd(int in_dim, const float *anchor, int64_t n_anch
                                rows, seed, q0f, q0s, q0o, X, yf, ys, yo, Q, sums3, nullptr, stream);
 }
 
-extern "C" size_t cgs_ctx_level_bwd_scratch_bytes(void) { return (size_t)cl_cus() * (CL_HID * 71 + CL_HID + 3 * CL_HID + 3) * sizeof(float); }
+extern "C" size_t cgs_ctx_level_bwd_scratch_bytes(void) { return (size_t)cgs_num_cus() * (CL_HID * 71 + CL_HID + 3 * CL_HID + 3) * sizeof(float); }
 
 // Backward of cgs_ctx_level_fwd.  dxf / dxs / dxo: the FULL-size parameter gradients [n_anchor, .], rows rows[r] are
 // overwritten with dy[r] (+ the rate subset's compact gradient row side_map[r] when >= 0; the side arrays have m_side rows).
@@ -853,7 +842,7 @@ extern "C" int cgs_ctx_level_bwd_h(int in_dim, const float *X, const float *W1, 
     }
     const int E = CL_HID * in_dim + CL_HID + 3 * CL_HID + 3;
     const int64_t tiles = (n + 15) / 16, want = (tiles + CLB_WAVES - 1) / CLB_WAVES;
-    int64_t grid = want < cl_cus() ? want : cl_cus();
+    int64_t grid = want < cgs_num_cus() ? want : cgs_num_cus();
     if ((size_t)grid * E * sizeof(float) > scratch_bytes) { cgs_set_error("ctx_level_bwd: scratch too small"); return CGS_ERR_WORKSPACE; }
     ClBwdArgsH a;
     const bool side = side_map != nullptr && m_side > 0;

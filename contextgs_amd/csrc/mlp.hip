@@ -259,17 +259,6 @@ __global__ void __launch_bounds__(WAVES * 64)
 
 // ------------------------------------------------------------------------------------------
 
-static int num_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 template <int IN, int HID, int OUT, int ACT>
 static int launch_fwd(const float *X, int64_t ldx, const float *W1, const float *b1, const float *W2, const float *b2,
                       float *Y, int64_t ldy, float *H, int64_t n, hipStream_t s) {
@@ -277,7 +266,7 @@ static int launch_fwd(const float *X, int64_t ldx, const float *W1, const float 
     constexpr int RT = M2_RT, WAVES = M2_WAVES;
     const int64_t tiles = (n + 16 * RT - 1) / (16 * RT);
     const int64_t want = (tiles + WAVES - 1) / WAVES;
-    const int grid = (int)(want < num_cus() ? want : num_cus());
+    const int grid = (int)(want < cgs_num_cus() ? want : cgs_num_cus());
     hipLaunchKernelGGL((mlp2_fwd_kernel<IN, HID, OUT, ACT, RT, WAVES>), dim3(grid), dim3(WAVES * 64), 0, s, X, ldx, W1, b1, W2,
                        b2, Y, ldy, H, n);
     CGS_CHECK_HIP(hipGetLastError());
@@ -292,7 +281,7 @@ static int launch_bwd(const float *dY, const float *Y, int64_t ldy, const float 
     constexpr int RT = M2_RT, WAVES = M2_WAVES;
     const int64_t tiles = (n + 16 * RT - 1) / (16 * RT);
     const int64_t want = (tiles + WAVES - 1) / WAVES;
-    const int grid = (int)(want < num_cus() ? want : num_cus());
+    const int grid = (int)(want < cgs_num_cus() ? want : cgs_num_cus());
     hipLaunchKernelGGL((mlp2_bwd_kernel<IN, HID, OUT, ACT, RT, WAVES>), dim3(grid), dim3(WAVES * 64), 0, s, dY, Y, ldy, H, W1,
                        W2, dX, lddx, acc, dZ2, dZ1, n, dx_rows);
     CGS_CHECK_HIP(hipGetLastError());
@@ -378,13 +367,13 @@ static int mlp2_backward_impl(int in, int hid, int out, int act, const float *X,
         {
             CgsProfScope prof(CGS_PROF_LMLP_BWD, stream);
             rc = cgs_launch_mlp2_bwd_recompute(in, hid, out, X, ldx, W1, b1, W2, dY, ldy, dX, lddx, accumulate_dx, dZ1, dW2,
-                                               db2, n, num_cus(), scratch, scratch_bytes, stream);
+                                               db2, n, cgs_num_cus(), scratch, scratch_bytes, stream);
         }
         if (rc == -1) { cgs_set_error("mlp2_backward: no recompute instance for %d -> %d -> %d", in, hid, out); return CGS_ERR_ARG; }
         if (rc || data_only) return rc;
         CgsProfScope prof(CGS_PROF_LMLP_WGRAD, stream);
         const CgsWgProduct prod = {dZ1, hid, hid, X, ldx, in, dW1, db1};
-        return cgs_launch_wgrad_multi(&prod, 1, n, num_cus(), scratch, scratch_bytes, stream);
+        return cgs_launch_wgrad_multi(&prod, 1, n, cgs_num_cus(), scratch, scratch_bytes, stream);
     }
     {
         CgsProfScope prof(CGS_PROF_LMLP_BWD, stream);
@@ -403,7 +392,7 @@ static int mlp2_backward_impl(int in, int hid, int out, int act, const float *X,
     const float *P2 = (act == ACT_NONE || !dZ2) ? dY : dZ2;
     const int64_t ldp2 = (act == ACT_NONE || !dZ2) ? ldy : out;
     const CgsWgProduct prods[2] = {{P2, ldp2, out, H, hid, hid, dW2, db2}, {dZ1, hid, hid, X, ldx, in, dW1, db1}};
-    return cgs_launch_wgrad_multi(prods, 2, n, num_cus(), scratch, scratch_bytes, stream);
+    return cgs_launch_wgrad_multi(prods, 2, n, cgs_num_cus(), scratch, scratch_bytes, stream);
 }
 
 // The weight-gradient products of cgs_mlp2_backward as a call of their own (after a backward with dW1 == NULL):
@@ -419,11 +408,11 @@ extern "C" int cgs_mlp2_wgrad(int in, int hid, int out, const float *X, int64_t 
     CgsProfScope prof(CGS_PROF_LMLP_WGRAD, stream);
     if (!H) {
         const CgsWgProduct prod = {dZ1, hid, hid, X, ldx, in, dW1, db1};
-        return cgs_launch_wgrad_multi(&prod, 1, n, num_cus(), scratch, scratch_bytes, stream);
+        return cgs_launch_wgrad_multi(&prod, 1, n, cgs_num_cus(), scratch, scratch_bytes, stream);
     }
     const CgsWgProduct prods[2] = {{dZ2, lddz2, out, H, hid, hid, dW2, db2}, {dZ1, hid, hid, X, ldx, in, dW1, db1}};
-    return cgs_launch_wgrad_multi(prods, 2, n, num_cus(), scratch, scratch_bytes, stream);
+    return cgs_launch_wgrad_multi(prods, 2, n, cgs_num_cus(), scratch, scratch_bytes, stream);
 }
 
 // Workspace for the atomics-free weight-gradient reduction of cgs_mlp2_backward / cgs_anchor_mlp3_backward.
-extern "C" size_t cgs_mlp_wgrad_scratch_bytes(void) { return cgs_wgrad_scratch_bytes_for(num_cus()); }
+extern "C" size_t cgs_mlp_wgrad_scratch_bytes(void) { return cgs_wgrad_scratch_bytes_for(cgs_num_cus()); }

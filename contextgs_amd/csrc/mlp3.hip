@@ -850,18 +850,6 @@ __global__ void __launch_bounds__(M3W_WAVES * 64) __attribute__((amdgpu_waves_pe
     for (int i = tid; i < M3W_E; i += nthr) dstp[i] = lds[i];
 }
 
-
-static int m3_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 // Row strides (floats) of the buffers the forward / backward hand to each other: out4 = {Hcat row stride (150: head h in
 // columns 50 h ..), X_out row stride of the ROWS variant (54), dZ1cat row stride (192), dZ1cat column pitch of a head (64:
 // head h in columns 64 h .. 64 h + 49; dW1cat [192, 54] and db1cat [192] use the same row numbering)}.
@@ -894,7 +882,7 @@ extern "C" int cgs_anchor_mlp3_forward(const float *X, int64_t ldx, const float 
         for (int i = 0; i < 3; ++i) h[i].Y = ys[i] + r0 * (i == 0 ? 10 : (i == 1 ? 30 : 70));
         const int64_t tiles = (m + 16 * RT - 1) / (16 * RT);
         const int64_t want = (tiles + WAVES - 1) / WAVES;
-        const int grid = (int)(want < m3_cus() ? want : m3_cus());
+        const int grid = (int)(want < cgs_num_cus() ? want : cgs_num_cus());
         hipLaunchKernelGGL((mlp3_fwd_kernel<10, 1, 30, 2, 70, 0, RT, WAVES, false>), dim3(grid), dim3(WAVES * 64), 0, (hipStream_t)stream,
                            X + r0 * ldx, ldx, h[0], h[1], h[2], Hcat ? Hcat + r0 * M3_HLD : nullptr, m, M3Rows{});
     }
@@ -945,7 +933,7 @@ extern "C" int cgs_anchor_mlp3_forward_rows_t(const float *feat_src, const int64
         for (int i = 0; i < 3; ++i) h[i].Y = ys[i] + r0 * (i == 0 ? 10 : (i == 1 ? 30 : 70));
         const int64_t tiles = (m + 16 * RT - 1) / (16 * RT);
         const int64_t want = (tiles + WAVES - 1) / WAVES;
-        const int grid = (int)(want < m3_cus() ? want : m3_cus());
+        const int grid = (int)(want < cgs_num_cus() ? want : cgs_num_cus());
         M3Rows R{feat_src, src_row + r0, anchor_vis + 3 * r0, cam3, X_out ? X_out + r0 * M3_XLD : nullptr, nullptr, nullptr};
         if (tiled)
             hipLaunchKernelGGL((mlp3_fwd_kernel<10, 1, 30, 2, 70, 0, RT, WAVES, true, true>), dim3(grid), dim3(WAVES * 64), 0, (hipStream_t)stream,
@@ -1051,7 +1039,7 @@ static int m3_backward(const float *X, int64_t ldx, const float *const *W1, cons
         // data AND weight gradients in one launch (mlp3_bwd_wg_kernel): dZ1cat / dZ2_* stay untouched
         const int64_t tiles16 = (n + 15) / 16;
         const int64_t wantw = (tiles16 + M3W_WAVES - 1) / M3W_WAVES;
-        const int gridw = (int)(wantw < m3_cus() ? wantw : m3_cus());
+        const int gridw = (int)(wantw < cgs_num_cus() ? wantw : cgs_num_cus());
         if (scratch && scratch_bytes >= (size_t)gridw * M3W_E * sizeof(float)) {
             {
                 CgsProfScope prof(CGS_PROF_MLP_BWD, stream);
@@ -1085,7 +1073,7 @@ static int m3_backward(const float *X, int64_t ldx, const float *const *W1, cons
     }
     const int64_t tiles = (n + 16 * RT - 1) / (16 * RT);
     const int64_t want = (tiles + WAVES - 1) / WAVES;
-    const int grid = (int)(want < m3_cus() ? want : m3_cus());
+    const int grid = (int)(want < cgs_num_cus() ? want : cgs_num_cus());
     {
         CgsProfScope prof(CGS_PROF_MLP_BWD, stream);
         if (rows)
@@ -1123,5 +1111,5 @@ extern "C" int cgs_anchor_mlp3_wgrad(const float *X, int64_t ldx, const float *H
         {dZ2_op, 10, 10, Hcat, M3_HLD, M3_HID, dW2[0], db2[0]},
         {dZ2_color, 30, 30, Hcat + M3_HPITCH, M3_HLD, M3_HID, dW2[1], db2[1]},
         {dY_cov, 70, 70, Hcat + 2 * M3_HPITCH, M3_HLD, M3_HID, dW2[2], db2[2]}};
-    return cgs_launch_wgrad_multi(prods, 4, n, m3_cus(), scratch, scratch_bytes, stream);
+    return cgs_launch_wgrad_multi(prods, 4, n, cgs_num_cus(), scratch, scratch_bytes, stream);
 }

@@ -627,17 +627,6 @@ __global__ void __launch_bounds__(RW_WAVES * 64) rs_wgrad_multi_kernel(RwMulti t
 }
 
 // ------------------------------------------------------------------------------------------------------------
-static int rs_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 static bool rs_fits(int64_t rows, int64_t row_bytes) { return rows >= 0 && (uint64_t)rows * (uint64_t)row_bytes < CL_MAX_BYTES; }
 
 static int rs_check(const char *what, const cgs_rate_sub_level &v) {
@@ -708,7 +697,7 @@ static int rs_main_launch(RsMulti &t, hipStream_t stream) {
     int in_dim[RS_MAX_LEVELS], blocks[RS_MAX_LEVELS];
     int64_t m[RS_MAX_LEVELS];
     for (int l = 0; l < t.L; ++l) { in_dim[l] = t.lv[l].in_dim; m[l] = t.lv[l].m; }
-    int rc = cgs_rate_sub_partition(t.L, in_dim, m, rs_cus(), blocks, t.first_block);
+    int rc = cgs_rate_sub_partition(t.L, in_dim, m, cgs_num_cus(), blocks, t.first_block);
     if (rc) return rc;
     for (int l = t.L; l < RS_MAX_LEVELS; ++l) t.first_block[l + 1] = t.first_block[t.L];
     constexpr int waves = BWD ? RS_WAVES_B : RS_WAVES_F;
@@ -794,7 +783,7 @@ extern "C" int cgs_rate_sub_fwd(int in_dim, const float *X, int64_t n, const int
 static int64_t rw_blocks(int64_t ntiles) {
     // a workgroup writes (and the reduction reads) a ~100 KB image whatever its rows: at least 8 tiles each
     int64_t blocks = (ntiles + 7) / 8;
-    if (blocks > rs_cus()) blocks = rs_cus();
+    if (blocks > cgs_num_cus()) blocks = cgs_num_cus();
     return blocks < 1 ? 1 : blocks;
 }
 

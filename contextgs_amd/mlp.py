@@ -19,6 +19,11 @@ _RECOMPUTE = {(71, 100, 3, 0), (15, 100, 3, 0)}
 RECOMPUTE_HIDDEN = os.environ.get("CGS_MLP_RECOMPUTE", "1") != "0"      # tuning / A-B knob
 
 
+def _f32c(t):
+    """t as a contiguous float32 tensor (t itself when it is one)."""
+    return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
+
+
 def _zeros_views(dev, *shapes):
     """Zero-initialised tensors of the given shapes carved from ONE buffer (one fill launch)."""
     sizes = [int(torch.Size(s).numel()) for s in shapes]
@@ -114,6 +119,41 @@ def _accumulate(params, grads):
             _Deferred.staged[id(p)] = (p, g if have is None else have[1].add_(g))
 
 
+class _WeightGrads:
+    """The weight-gradient hand-off of ONE backward node: whether its products are launched inline, by the node's own C call, or
+    left for the end of the backward.  `also` is the node's own condition on top of _can_defer(params).  The decision and the
+    hand-off (ptr, leave) never touch the library."""
+
+    def __init__(self, params, also=True):
+        self.params = params
+        self.deferred = bool(_can_defer(params) and also)
+
+    def ptr(self, t, keep=False):
+        """The gradient pointer (of a tensor, or the pointer array of a list of them) for the node's C call: NULL when the product
+        is left for later, unless the kernel accumulates it by itself anyway (keep)."""
+        if self.deferred and not keep:
+            return None
+        return _ptr_array(t) if isinstance(t, (list, tuple)) else _lib.ptr(t)
+
+    def leave(self, grads, launch):
+        """What the node returns for its parameters.  Inline: `grads`, already written.  Deferred: a None for each, and one queued
+        job that runs launch() (which keeps its operands alive) and then stages `grads` for the parameters' .grad."""
+        if not self.deferred:
+            return grads
+        params = self.params
+
+        def job():
+            launch()
+            _accumulate(params, grads)
+        _defer(job)
+        return (None,) * len(grads)
+
+    @staticmethod
+    def buffers(dev, *shapes):
+        """(zeroed gradient tensors of the given shapes: one fill, the reduction workspace of the weight-gradient launch)"""
+        return _zeros_views(dev, *shapes), _wgrad_workspace(dev)
+
+
 _SUPPORTED = {(54, 50, 10, 1), (54, 50, 30, 2), (54, 50, 70, 0), (71, 100, 175, 0), (15, 100, 175, 0), (71, 100, 3, 0),
               (15, 100, 3, 0)}
 
@@ -138,7 +178,7 @@ class _MLP2(torch.autograd.Function):
         L = _lib.lib()
         _drop_stale_deferred()
         _lib.require_device(x, W1, W2)
-        x = x.contiguous() if x.dtype == torch.float32 else x.float().contiguous()
+        x = _f32c(x)
         W1c, b1c, W2c, b2c = (t.detach().contiguous() for t in (W1, b1, W2, b2))
         n, in_f = x.shape
         hid, out = W1c.shape[0], W2c.shape[0]
@@ -167,32 +207,25 @@ class _MLP2(torch.autograd.Function):
         n, in_f = x.shape
         hid, out = W1.shape[0], W2.shape[0]
         dev = x.device
-        dy = dy.contiguous() if dy.dtype == torch.float32 else dy.float().contiguous()
+        dy = _f32c(dy)
         need_dx = ctx.needs_input_grad[0]
         dx = torch.empty(n, in_f, dtype=torch.float32, device=dev) if need_dx else None
         dz1 = torch.empty(n, hid, dtype=torch.float32, device=dev)
         dz2 = torch.empty(n, out, dtype=torch.float32, device=dev) if act != 0 else None
-        dW1, db1, dW2, db2 = _zeros_views(dev, (hid, in_f), (hid,), (out, hid), (out,))   # one fill for the four
-        ws = _wgrad_workspace(dev)
-        defer = _can_defer(ctx.params) and n > 0
-        inside = defer and h is None          # the recomputing kernel accumulates the second layer itself
-        wg = lambda t, keep: _lib.ptr(t) if (not defer or keep) else None
+        wg = _WeightGrads(ctx.params, n > 0)
+        (dW1, db1, dW2, db2), ws = wg.buffers(dev, (hid, in_f), (hid,), (out, hid), (out,))   # one fill for the four
+        inside = wg.deferred and h is None    # the recomputing kernel accumulates the second layer itself
         _lib.check(L.cgs_mlp2_backward(in_f, hid, out, act, _lib.ptr(x), in_f, _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(y),
                                        _lib.ptr(dy), out, _lib.ptr(h), _lib.ptr(dx), in_f, 0, _lib.ptr(dz1), _lib.ptr(dz2),
-                                       wg(dW1, False), wg(db1, False), wg(dW2, inside), wg(db2, inside), n,
+                                       wg.ptr(dW1), wg.ptr(db1), wg.ptr(dW2, inside), wg.ptr(db2, inside), n,
                                        _lib.ptr(ws), ws.numel(), _lib.current_stream()), "cgs_mlp2_backward")
-        if not defer:
-            return dx, dW1, db1, dW2, db2, None
         p2 = dz2 if dz2 is not None else dy
-        params = ctx.params
 
-        def job():
+        def launch():
             _lib.check(L.cgs_mlp2_wgrad(in_f, hid, out, _lib.ptr(x), in_f, _lib.ptr(h), _lib.ptr(p2), out, _lib.ptr(dz1),
                                         _lib.ptr(dW1), _lib.ptr(db1), _lib.ptr(dW2), _lib.ptr(db2), n, _lib.ptr(ws), ws.numel(),
                                         _lib.current_stream()), "cgs_mlp2_wgrad")
-            _accumulate(params, (dW1, db1, dW2, db2))
-        _defer(job)
-        return dx, None, None, None, None, None
+        return (dx, *wg.leave((dW1, db1, dW2, db2), launch), None)
 
 
 class _LevelMLP(torch.autograd.Function):
@@ -208,7 +241,7 @@ class _LevelMLP(torch.autograd.Function):
         L = _lib.lib()
         _drop_stale_deferred()
         _lib.require_device(x, W1, W2, loc)
-        x = x.contiguous() if x.dtype == torch.float32 else x.float().contiguous()
+        x = _f32c(x)
         W1c, b1c, W2c, b2c = (t.detach().contiguous() for t in (W1, b1, W2, b2))
         n, in_f = x.shape
         hid, out = W1c.shape[0], W2c.shape[0]
@@ -240,30 +273,27 @@ class _LevelMLP(torch.autograd.Function):
         hid, out = W1.shape[0], W2.shape[0]
         nq, m = out - n_stat, int(loc.shape[0])
         dev = x.device
-        f32c = lambda t: t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
         need_dx = ctx.needs_input_grad[0]
         stream = _lib.current_stream()
-        dW1, db1, dW2, db2 = _zeros_views(dev, (hid, in_f), (hid,), (out, hid), (out,))   # one fill for the module
-        ws = _wgrad_workspace(dev)
+        wg = _WeightGrads(ctx.params)       # (no size condition: each branch guards its own launch)
+        (dW1, db1, dW2, db2), ws = wg.buffers(dev, (hid, in_f), (hid,), (out, hid), (out,))   # one fill for the module
         dx = None
-        defer = _can_defer(ctx.params)
-        wg = lambda t: None if defer else _lib.ptr(t)
         jobs = []
         if d_q is not None:
             dx = torch.empty(n, in_f, dtype=torch.float32, device=dev) if need_dx else None
             dz1 = torch.empty(n, hid, dtype=torch.float32, device=dev)
-            d_q = f32c(d_q)
+            d_q = _f32c(d_q)
             # (recomputing kernel: the step-size rows of the second layer are accumulated inside it, deferred or not)
             _lib.check(L.cgs_mlp2_backward(in_f, hid, nq, 0, _lib.ptr(x), in_f, _lib.ptr(W1), _lib.ptr(b1),
                                            W2.data_ptr() + 4 * n_stat * hid, None, _lib.ptr(d_q), nq, None, _lib.ptr(dx), in_f, 0,
-                                           _lib.ptr(dz1), None, wg(dW1), wg(db1), dW2.data_ptr() + 4 * n_stat * hid,
+                                           _lib.ptr(dz1), None, wg.ptr(dW1), wg.ptr(db1), dW2.data_ptr() + 4 * n_stat * hid,
                                            db2.data_ptr() + 4 * n_stat, n, _lib.ptr(ws), ws.numel(), stream), "cgs_mlp2_backward")
-            if defer and n > 0:
+            if wg.deferred and n > 0:
                 jobs.append(lambda: _lib.check(L.cgs_mlp2_wgrad(
                     in_f, hid, nq, _lib.ptr(x), in_f, None, None, 0, _lib.ptr(dz1), _lib.ptr(dW1), _lib.ptr(db1), None, None, n,
                     _lib.ptr(ws), ws.numel(), _lib.current_stream()), "cgs_mlp2_wgrad"))
         if d_pred is not None and m > 0:
-            d_pred = f32c(d_pred)
+            d_pred = _f32c(d_pred)
             dz1s = torch.empty(m, hid, dtype=torch.float32, device=dev)
             if need_dx and dx is None:
                 dx = torch.zeros(n, in_f, dtype=torch.float32, device=dev)
@@ -271,23 +301,14 @@ class _LevelMLP(torch.autograd.Function):
             # (cgs_mlp2_backward_rows): no [m, in] temporary, no index_add_ launch
             _lib.check(L.cgs_mlp2_backward_rows(in_f, hid, out, 0, _lib.ptr(x_sub), in_f, _lib.ptr(W1), None, _lib.ptr(W2), None,
                                                 _lib.ptr(d_pred), out, _lib.ptr(h_sub), _lib.ptr(dx) if need_dx else None, in_f, 1,
-                                                _lib.ptr(loc), _lib.ptr(dz1s), None, wg(dW1), wg(db1), wg(dW2),
-                                                wg(db2), m, _lib.ptr(ws), ws.numel(), stream), "cgs_mlp2_backward_rows")
-            if defer:
+                                                _lib.ptr(loc), _lib.ptr(dz1s), None, wg.ptr(dW1), wg.ptr(db1), wg.ptr(dW2),
+                                                wg.ptr(db2), m, _lib.ptr(ws), ws.numel(), stream), "cgs_mlp2_backward_rows")
+            if wg.deferred:
                 jobs.append(lambda: _lib.check(L.cgs_mlp2_wgrad(
                     in_f, hid, out, _lib.ptr(x_sub), in_f, _lib.ptr(h_sub), _lib.ptr(d_pred), out, _lib.ptr(dz1s), _lib.ptr(dW1),
                     _lib.ptr(db1), _lib.ptr(dW2), _lib.ptr(db2), m, _lib.ptr(ws), ws.numel(), _lib.current_stream()),
                     "cgs_mlp2_wgrad"))
-        if not defer:
-            return dx, None, dW1, db1, dW2, db2, None
-        params = ctx.params
-
-        def job():
-            for j in jobs:
-                j()
-            _accumulate(params, (dW1, db1, dW2, db2))
-        _defer(job)
-        return dx, None, None, None, None, None, None
+        return (dx, None, *wg.leave((dW1, db1, dW2, db2), lambda: [j() for j in jobs]), None)
 
 
 def level_mlp(x: torch.Tensor, loc: torch.Tensor, seq: nn.Sequential, n_stat: int):
@@ -310,10 +331,7 @@ def mlp2_weights(x: torch.Tensor, W1, b1, W2, b2, act: int = 0) -> torch.Tensor:
 def mlp2(x: torch.Tensor, seq: nn.Sequential) -> torch.Tensor:
     """seq(x) for a supported Sequential(Linear, ReLU, Linear[, act])."""
     l1, l2, act = _describe(seq)
-    key = (l1.in_features, l1.out_features, l2.out_features, act)
-    if key not in _SUPPORTED:
-        raise NotImplementedError(f"no fused MLP kernel for {key}; instantiate it in csrc/mlp.hip")
-    return _MLP2.apply(x, l1.weight, l1.bias, l2.weight, l2.bias, act)
+    return mlp2_weights(x, l1.weight, l1.bias, l2.weight, l2.bias, act)
 
 
 # ---- the three anchor MLPs in one launch (csrc/mlp3.hip) ---------------------------------------------
@@ -351,15 +369,49 @@ def anchor_mlp3_params(mo: nn.Sequential, mc: nn.Sequential, mv: nn.Sequential):
     return [t for s in (mo, mc, mv) for t in (s[0].weight, s[0].bias, s[2].weight, s[2].bias)]
 
 
-def _m3_wgrad_job(x, ldx, hcat, dz1, dz2_op, dz2_color, g_cov, dW1cat, db1cat, dW2, db2, n, ws, params, wgrads):
+def _m3_split(params):
+    """The flat parameter tuple as detached contiguous lists (W1, b1, W2, b2), one entry per head."""
+    p = [t.detach().contiguous() for t in params]
+    return p[0::4], p[1::4], p[2::4], p[3::4]
+
+
+def _m3_outputs(n, dev):
+    """(y_op, y_color, y_cov), to be written by the forward kernel."""
+    return [torch.empty(n, w, dtype=torch.float32, device=dev) for w in (10, 30, 70)]
+
+
+def _m3_grads_in(grads, n, dev):
+    """The incoming gradients of the three outputs as contiguous float32, zeros for an output nothing read."""
+    return [torch.zeros(n, w, dtype=torch.float32, device=dev) if g is None else _f32c(g) for g, w in zip(grads, (10, 30, 70))]
+
+
+def _anchor_wgrad_views(dev, W2, rows, pitch):
+    """The weight-gradient buffers of the three anchor heads, zeroed by ONE fill: (dW1cat [rows, 54], db1cat [rows] with head i
+    at rows pitch * i .. + 50, [dW2], [db2], the twelve gradients in anchor_mlp3_params order: views of the former)."""
+    views = _zeros_views(dev, (rows, 54), (rows,), *[tuple(w.shape) for w in W2], *[(w.shape[0],) for w in W2])
+    dW1cat, db1cat, dW2, db2 = views[0], views[1], list(views[2:5]), list(views[5:8])
+    wgrads = [t for i in range(3) for t in (dW1cat[pitch * i:pitch * i + 50], db1cat[pitch * i:pitch * i + 50], dW2[i], db2[i])]
+    return dW1cat, db1cat, dW2, db2, wgrads
+
+
+def _m3_backward_buffers(dev, n, W2):
+    """What both anchor-MLP backwards hand their kernel besides the operands: (dz1, dz2_op, dz2_color, the heads' gradient
+    buffers of _anchor_wgrad_views, the reduction workspace)."""
+    _hld, _xld, gld, hp = _m3_layout()
+    dz1 = torch.empty(n, gld, dtype=torch.float32, device=dev)
+    dz2_op = torch.empty(n, 10, dtype=torch.float32, device=dev)
+    dz2_color = torch.empty(n, 30, dtype=torch.float32, device=dev)
+    return dz1, dz2_op, dz2_color, _anchor_wgrad_views(dev, W2, gld, hp), _wgrad_workspace(dev)
+
+
+def _m3_wgrad_job(x, hcat, dz1, dz2_op, dz2_color, g_cov, dW1cat, db1cat, dW2, db2, n, ws):
     """The deferred weight-gradient launch of an anchor-MLP backward node (operands kept alive by the closure)."""
-    def job():
+    def launch():
         _lib.check(_lib.lib().cgs_anchor_mlp3_wgrad(
-            _lib.ptr(x), ldx, _lib.ptr(hcat), _lib.ptr(dz1), _lib.ptr(dz2_op), _lib.ptr(dz2_color), _lib.ptr(g_cov),
+            _lib.ptr(x), x.shape[1], _lib.ptr(hcat), _lib.ptr(dz1), _lib.ptr(dz2_op), _lib.ptr(dz2_color), _lib.ptr(g_cov),
             _lib.ptr(dW1cat), _lib.ptr(db1cat), _ptr_array(dW2), _ptr_array(db2), n, _lib.ptr(ws), ws.numel(),
             _lib.current_stream()), "cgs_anchor_mlp3_wgrad")
-        _accumulate(params, wgrads)
-    return job
+    return launch
 
 
 class _AnchorMLP3(torch.autograd.Function):
@@ -369,15 +421,12 @@ class _AnchorMLP3(torch.autograd.Function):
         L = _lib.lib()
         _drop_stale_deferred()
         _lib.require_device(x)
-        x = x.contiguous() if x.dtype == torch.float32 else x.float().contiguous()
-        p = [t.detach().contiguous() for t in params]
-        W1, b1, W2, b2 = p[0::4], p[1::4], p[2::4], p[3::4]
+        x = _f32c(x)
+        W1, b1, W2, b2 = _m3_split(params)
         n = x.shape[0]
         dev = x.device
         need_grad = any(ctx.needs_input_grad)
-        y_op = torch.empty(n, 10, dtype=torch.float32, device=dev)
-        y_color = torch.empty(n, 30, dtype=torch.float32, device=dev)
-        y_cov = torch.empty(n, 70, dtype=torch.float32, device=dev)
+        y_op, y_color, y_cov = _m3_outputs(n, dev)
         hcat = torch.empty(n, _m3_layout()[0], dtype=torch.float32, device=dev) if need_grad else None
         _lib.check(L.cgs_anchor_mlp3_forward(_lib.ptr(x), x.shape[1], _ptr_array(W1), _ptr_array(b1), _ptr_array(W2),
                                              _ptr_array(b2), _lib.ptr(y_op), _lib.ptr(y_color), _lib.ptr(y_cov),
@@ -395,33 +444,17 @@ class _AnchorMLP3(torch.autograd.Function):
         W1, W2 = list(saved[4:7]), list(saved[7:10])
         n = x.shape[0]
         dev = x.device
-        z = lambda t, shape: torch.zeros(shape, dtype=torch.float32, device=dev) if t is None else (
-            t.contiguous() if t.dtype == torch.float32 else t.float().contiguous())
-        g_op, g_color, g_cov = z(g_op, (n, 10)), z(g_color, (n, 30)), z(g_cov, (n, 70))
+        g_op, g_color, g_cov = _m3_grads_in((g_op, g_color, g_cov), n, dev)
         need_dx = ctx.needs_input_grad[0]
         dx = torch.empty(n, x.shape[1], dtype=torch.float32, device=dev) if need_dx else None
-        _hld, _xld, gld, hp = _m3_layout()
-        dz1 = torch.empty(n, gld, dtype=torch.float32, device=dev)
-        dz2_op = torch.empty(n, 10, dtype=torch.float32, device=dev)
-        dz2_color = torch.empty(n, 30, dtype=torch.float32, device=dev)
-        views = _zeros_views(dev, (gld, 54), (gld,), *[tuple(w.shape) for w in W2], *[(w.shape[0],) for w in W2])
-        dW1cat, db1cat, dW2, db2 = views[0], views[1], list(views[2:5]), list(views[5:8])
-        ws = _wgrad_workspace(dev)
-        defer = _can_defer(ctx.params) and n > 0
+        dz1, dz2_op, dz2_color, (dW1cat, db1cat, dW2, db2, wgrads), ws = _m3_backward_buffers(dev, n, W2)
+        wg = _WeightGrads(ctx.params, n > 0)
         _lib.check(L.cgs_anchor_mlp3_backward(
             _lib.ptr(x), x.shape[1], _ptr_array(W1), _ptr_array(W2), _lib.ptr(y_op), _lib.ptr(y_color), _lib.ptr(g_op),
             _lib.ptr(g_color), _lib.ptr(g_cov), _lib.ptr(hcat), _lib.ptr(dx), x.shape[1], _lib.ptr(dz1), _lib.ptr(dz2_op),
-            _lib.ptr(dz2_color), None if defer else _lib.ptr(dW1cat), None if defer else _lib.ptr(db1cat),
-            None if defer else _ptr_array(dW2), None if defer else _ptr_array(db2), n,
+            _lib.ptr(dz2_color), wg.ptr(dW1cat), wg.ptr(db1cat), wg.ptr(dW2), wg.ptr(db2), n,
             _lib.ptr(ws), ws.numel(), _lib.current_stream()), "cgs_anchor_mlp3_backward")
-        wgrads = []
-        for i in range(3):
-            wgrads += [dW1cat[hp * i:hp * i + 50], db1cat[hp * i:hp * i + 50], dW2[i], db2[i]]
-        if not defer:
-            return (dx, *wgrads)
-        _defer(_m3_wgrad_job(x, x.shape[1], hcat, dz1, dz2_op, dz2_color, g_cov, dW1cat, db1cat, dW2, db2, n, ws, ctx.params,
-                             wgrads))
-        return (dx,) + (None,) * 12
+        return (dx, *wg.leave(wgrads, _m3_wgrad_job(x, hcat, dz1, dz2_op, dz2_color, g_cov, dW1cat, db1cat, dW2, db2, n, ws)))
 
 
 # A/B knob, default: the forward KEEPS its assembled rows.  CGS_M3_KEEP_X=0: it does not (forward 480 -> 438 us at 1 M anchors:
@@ -459,17 +492,13 @@ class _AnchorMLP3Rows(torch.autograd.Function):
         queue while the host creates the context model's autograd nodes (renderer.generate_neural_gaussians)."""
         L = _lib.lib()
         _drop_stale_deferred()
-        f32c = lambda t: t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
-        feat_src, anchor_vis, cam = f32c(feat_src.detach()), f32c(anchor_vis.detach()), f32c(cam.detach()).reshape(-1)
+        feat_src, anchor_vis, cam = _f32c(feat_src.detach()), _f32c(anchor_vis.detach()), _f32c(cam.detach()).reshape(-1)
         _lib.require_device(feat_src, anchor_vis, cam, src_row)
         assert feat_src.dim() == 2 and feat_src.shape[1] == 50 and cam.numel() == 3 and src_row.dtype == torch.int64
-        p = [t.detach().contiguous() for t in params]
-        W1, b1, W2, b2 = p[0::4], p[1::4], p[2::4], p[3::4]
+        W1, b1, W2, b2 = _m3_split(params)
         n = int(src_row.shape[0])
         dev = feat_src.device
-        y_op = torch.empty(n, 10, dtype=torch.float32, device=dev)
-        y_color = torch.empty(n, 30, dtype=torch.float32, device=dev)
-        y_cov = torch.empty(n, 70, dtype=torch.float32, device=dev)
+        y_op, y_color, y_cov = _m3_outputs(n, dev)
         hld, xld, _gld, _gp = _m3_layout()
         tiled = bool(M3_TILED and need_grad and not _Deferred.on and 0 < n <= _M3_REGATHER_MAX_ROWS)
         n_buf = (n + 15) // 16 * 16 if tiled else n           # (whole 16-row tiles)
@@ -512,9 +541,7 @@ class _AnchorMLP3Rows(torch.autograd.Function):
         W1, W2 = list(saved[7:10]), list(saved[10:13])
         n = int(src_row.shape[0])
         dev = hcat.device
-        z = lambda t, shape: torch.zeros(shape, dtype=torch.float32, device=dev) if t is None else (
-            t.contiguous() if t.dtype == torch.float32 else t.float().contiguous())
-        g_op, g_color, g_cov = z(g_op, (n, 10)), z(g_color, (n, 30)), z(g_cov, (n, 70))
+        g_op, g_color, g_cov = _m3_grads_in((g_op, g_color, g_cov), n, dev)
         # rows of the source no visible anchor reads keep a zero gradient (ctx_ops.zero_unlisted_rows writes only those rows —
         # a 200 MB fill at 1 M anchors otherwise); when every row is read there is nothing to zero
         d_src = torch.empty(ctx.n_src, 50, dtype=torch.float32, device=dev)
@@ -522,30 +549,16 @@ class _AnchorMLP3Rows(torch.autograd.Function):
             from .ctx_ops import zero_unlisted_rows
             zero_unlisted_rows(src_row, ctx.n_src, [d_src])
         d_anchor = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        _hld, _xld, gld, hp = _m3_layout()
-        dz1 = torch.empty(n, gld, dtype=torch.float32, device=dev)
-        dz2_op = torch.empty(n, 10, dtype=torch.float32, device=dev)
-        dz2_color = torch.empty(n, 30, dtype=torch.float32, device=dev)
-        views = _zeros_views(dev, (gld, 54), (gld,), *[tuple(w.shape) for w in W2], *[(w.shape[0],) for w in W2])
-        dW1cat, db1cat, dW2, db2 = views[0], views[1], list(views[2:5]), list(views[5:8])
-        ws = _wgrad_workspace(dev)
+        dz1, dz2_op, dz2_color, (dW1cat, db1cat, dW2, db2, wgrads), ws = _m3_backward_buffers(dev, n, W2)
         # (the tiled hand-over is read by the fused data + weight-gradient kernel only: never deferred)
-        defer = _can_defer(ctx.params) and n > 0 and x is not None and not ctx.tiled
+        wg = _WeightGrads(ctx.params, n > 0 and x is not None and not ctx.tiled)
         _lib.check(L.cgs_anchor_mlp3_backward_rows_t(
             _lib.ptr(x), _lib.ptr(feat_src), _lib.ptr(src_row), _lib.ptr(anchor_vis), _lib.ptr(cam), _ptr_array(W1), _ptr_array(W2), _lib.ptr(y_op),
             _lib.ptr(y_color), _lib.ptr(g_op), _lib.ptr(g_color), _lib.ptr(g_cov), _lib.ptr(hcat), _lib.ptr(d_src),
-            _lib.ptr(d_anchor), _lib.ptr(dz1), _lib.ptr(dz2_op), _lib.ptr(dz2_color), None if defer else _lib.ptr(dW1cat),
-            None if defer else _lib.ptr(db1cat), None if defer else _ptr_array(dW2), None if defer else _ptr_array(db2), n,
-            int(ctx.tiled), _lib.ptr(ws), ws.numel(), _lib.current_stream()), "cgs_anchor_mlp3_backward_rows")
-        grads = [d_src if ctx.needs_input_grad[0] else None, None, d_anchor if ctx.needs_input_grad[2] else None, None, None]
-        wgrads = []
-        for i in range(3):
-            wgrads += [dW1cat[hp * i:hp * i + 50], db1cat[hp * i:hp * i + 50], dW2[i], db2[i]]
-        if not defer:
-            return tuple(grads + wgrads)
-        _defer(_m3_wgrad_job(x, x.shape[1], hcat, dz1, dz2_op, dz2_color, g_cov, dW1cat, db1cat, dW2, db2, n, ws, ctx.params,
-                             wgrads))
-        return tuple(grads) + (None,) * 12
+            _lib.ptr(d_anchor), _lib.ptr(dz1), _lib.ptr(dz2_op), _lib.ptr(dz2_color), wg.ptr(dW1cat), wg.ptr(db1cat), wg.ptr(dW2),
+            wg.ptr(db2), n, int(ctx.tiled), _lib.ptr(ws), ws.numel(), _lib.current_stream()), "cgs_anchor_mlp3_backward_rows")
+        return (d_src if ctx.needs_input_grad[0] else None, None, d_anchor if ctx.needs_input_grad[2] else None, None, None,
+                *wg.leave(wgrads, _m3_wgrad_job(x, hcat, dz1, dz2_op, dz2_color, g_cov, dW1cat, db1cat, dW2, db2, n, ws)))
 
 
 def anchor_mlp3_rows(feat_src, src_row, anchor_vis, cam_center, mo: nn.Sequential, mc: nn.Sequential, mv: nn.Sequential, pre=None):
