@@ -10,22 +10,15 @@ c3: ~500 k anchors, 1920x1080, 3-level context entropy encode + decode: every de
     quantised value bit for bit, and the decoded model renders the encoder-side image.
 c5: ~3 M anchors, rate sweep (feature spread as the lambda proxy), encode -> files -> decode round trip.
 """
-import math
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from raster_harness import settings
+
 pytestmark = pytest.mark.gpu
-
-
-def _settings(cam, bg):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=1.0, viewmatrix=cam.world_view_transform,
-        projmatrix=cam.full_proj_transform, sh_degree=1, campos=cam.camera_center, prefiltered=False, debug=False)
 
 
 def test_c1_10k_anchors_256x256_vs_oracle(oracle32):
@@ -66,7 +59,7 @@ def test_c1_10k_anchors_256x256_vs_oracle(oracle32):
                 assert np.allclose(f(a), b, rtol=1e-4, atol=3e-6)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        img, radii = GaussianRasterizer(_settings(cam, bg))(
+        img, radii = GaussianRasterizer(settings(cam_np, bg=bg))(
             means3D=xyz, means2D=torch.zeros_like(xyz), shs=None, colors_precomp=color, opacities=opacity, scales=scaling,
             rotations=rot, cov3D_precomp=None)
         torch.cuda.synchronize()
@@ -121,7 +114,7 @@ def test_c2_100k_anchors_800x800_forward_backward_vs_oracles(oracle32):
     # a4/a5: rasterizer forward + backward on these P Gaussians at 800x800 against the C oracle
     leaves = [t.detach().clone().requires_grad_(True) for t in (xyz, color, opacity, scaling, rot)]
     m2d = torch.zeros_like(leaves[0], requires_grad=True)
-    img, radii = GaussianRasterizer(_settings(cam, bg))(
+    img, radii = GaussianRasterizer(settings(cam_np, bg=bg))(
         means3D=leaves[0], means2D=m2d, shs=None, colors_precomp=leaves[1], opacities=leaves[2], scales=leaves[3],
         rotations=leaves[4], cov3D_precomp=None)
     w = np.random.default_rng(2).normal(size=(3, H, W)).astype(np.float32)

@@ -185,7 +185,7 @@ def test_hemispheres_agree_on_the_oracle(oracle64):
 
 
 # ---- the C-ABI ---------------------------------------------------------------------------------------------------------------
-def _cfg(view=P1):
+def _view_cfg(view=P1):
     from contextgs_amd import _lib
     return _lib.RasterCfg(image_height=16, image_width=16, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
                           debug=0, viewmatrix=view, projmatrix=P1, campos=P1, bg=P1)
@@ -217,18 +217,18 @@ def test_gaussian_normals_argument_errors():
         full = [P1] * n_ptr
         rc, msg = _call(fn, None, 1, *full, None)
         assert rc == CGS_ERR_ARG and "cfg is NULL" in msg and fn in msg, msg
-        rc, msg = _call(fn, C.byref(_cfg()), -1, *full, None)
+        rc, msg = _call(fn, C.byref(_view_cfg()), -1, *full, None)
         assert rc == CGS_ERR_ARG and "P < 0" in msg and fn in msg, msg
-        rc, msg = _call(fn, C.byref(_cfg()), 1 << 39, *full, None)
+        rc, msg = _call(fn, C.byref(_view_cfg()), 1 << 39, *full, None)
         assert rc == CGS_ERR_ARG and "beyond one launch" in msg and fn in msg, msg
-        rc, msg = _call(fn, C.byref(_cfg(view=None)), 1, *full, None)
+        rc, msg = _call(fn, C.byref(_view_cfg(view=None)), 1, *full, None)
         assert rc == CGS_ERR_ARG and "viewmatrix is NULL" in msg and fn in msg, msg
         for i in range(n_ptr):
             args = list(full)
             args[i] = None
-            rc, msg = _call(fn, C.byref(_cfg()), 1, *args, None)
+            rc, msg = _call(fn, C.byref(_view_cfg()), 1, *args, None)
             assert rc == CGS_ERR_ARG and "NULL" in msg and fn in msg, (i, msg)
-        rc, msg = _call(fn, C.byref(_cfg()), 0, *([None] * n_ptr), None)         # nothing to do, nothing enqueued
+        rc, msg = _call(fn, C.byref(_view_cfg()), 0, *([None] * n_ptr), None)         # nothing to do, nothing enqueued
         assert rc == CGS_OK, msg
 
 

@@ -3,7 +3,7 @@
 
 Inputs are those of tests/normals_ref.py (pixel_inputs, gaussian_inputs, plane_scene): tests/test_normals.py runs the fp32
 restatement against the fp64 one on exactly them at HALF of every cap below, and the hemisphere scene on the raster oracle, so
-the caps are conditions, not measurements.  Tolerances (the project's own, copies of tests/test_raster_geom_gpu.py): maps, RMSE
+the caps are conditions, not measurements.  Tolerances (the project's own, those of tests/raster_harness.py): maps, RMSE
 <= 1e-5 of the map's maximum and at most a 1e-4 share of values beyond 2e-5; gradients, at most a 2e-3 share of entries beyond
 2e-4 of the tensor's maximum.  Per-Gaussian rows whose fp64 |n^ . t^| < 1e-4 (the sign could fall either way) are left out of
 the comparison, at most 1 % of the rows.  References are computed once and shared; nobody writes into them."""
@@ -16,11 +16,11 @@ import pytest
 import torch
 
 import normals_ref as ref
+from raster_harness import BG, model, named_scene, settings
 
 pytestmark = pytest.mark.gpu
 
 TX, TY = ref.TAN
-BG = (0.1, 0.25, 0.4)
 
 
 def _np(t):
@@ -31,20 +31,14 @@ def _cu(a, grad=False):
     return torch.tensor(a, device="cuda", requires_grad=grad)
 
 
-def _settings(H, W, tanfovx=TX, tanfovy=TY, view=None, proj=None, aa=False):
+def _eye_settings(H, W, view=None):
+    """Settings without a camera object: the inputs of tests/normals_ref.py come with a view matrix (default: identity) only."""
     from contextgs_amd.rasterizer import GaussianRasterizationSettings
     eye = torch.eye(4, device="cuda")
     return GaussianRasterizationSettings(
-        image_height=H, image_width=W, tanfovx=tanfovx, tanfovy=tanfovy, bg=torch.tensor(BG, dtype=torch.float32, device="cuda"),
-        scale_modifier=1.0, viewmatrix=eye if view is None else view, projmatrix=eye if proj is None else proj, sh_degree=1,
-        campos=torch.zeros(3, device="cuda"), prefiltered=False, debug=False, antialiasing=aa)
-
-
-def _cam_settings(cam, aa=False):
-    c = cam.to_torch("cuda")
-    rs = _settings(cam.image_height, cam.image_width, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5),
-                   c.world_view_transform, c.full_proj_transform, aa)
-    return rs._replace(campos=c.camera_center)
+        image_height=H, image_width=W, tanfovx=TX, tanfovy=TY, bg=torch.tensor(BG, dtype=torch.float32, device="cuda"),
+        scale_modifier=1.0, viewmatrix=eye if view is None else view, projmatrix=eye, sh_degree=1,
+        campos=torch.zeros(3, device="cuda"), prefiltered=False, debug=False, antialiasing=False)
 
 
 # ---- (1) per-Gaussian normals ------------------------------------------------------------------------------------------------
@@ -53,7 +47,7 @@ def test_gaussian_normals_match_fp64(P):
     from contextgs_amd.normals import gaussian_normals
     V = ref.view_matrix()
     x = ref.gaussian_inputs(P, seed=P)
-    rs = _settings(24, 40, view=_cu(V))
+    rs = _eye_settings(24, 40, view=_cu(V))
     m, s, q = _cu(x["means3D"], True), _cu(x["scales"], True), _cu(x["rotations"], True)
     n = gaussian_normals(m, s, q, rs)
     assert n.shape == (P, 3) and n.dtype == torch.float32
@@ -79,7 +73,7 @@ def test_gaussian_normals_edge_rows():
     """Equal scales pick the lowest index; the zero quaternion reads as the identity and gets a zero gradient; a [P,4] view that
     starts in the middle of a buffer is read where it is."""
     from contextgs_amd.normals import gaussian_normals
-    rs = _settings(24, 40)                                                   # the identity view: camera space = world space
+    rs = _eye_settings(24, 40)                                                   # the identity view: camera space = world space
     m = _cu(np.array([[0, 0, 2], [0, 0, 2], [0, 0, -2], [0.5, 0, 2]], np.float32))
     s = _cu(np.array([[1, 1, 1], [2, 1, 1], [3, 2, 1], [1, 2, 3]], np.float32))
     buf = torch.zeros(1 + 16, device="cuda")
@@ -107,7 +101,7 @@ def _pixel_ref(kind, H, W, eps, weighted):
 def _run_pixels(x, H, W, eps, weighted, flat_depth=False):
     """{"N", "dN", "E", "dn", "dd"} from the device; the backward of each runs twice and must give the same bits."""
     from contextgs_amd.normals import depth_normals, normal_consistency
-    rs = _settings(H, W)
+    rs = _eye_settings(H, W)
     out = {}
     for rep in range(2):
         d = _cu(x["depth"][0] if flat_depth else x["depth"], True)
@@ -152,7 +146,7 @@ def test_depth_normals_and_consistency_match_fp64(H, W, kind):
 
 def test_constant_depth_gives_plus_z():
     from contextgs_amd.normals import depth_normals
-    N = depth_normals(_cu(ref.depth_case("constant", 24, 40)), _settings(24, 40))
+    N = depth_normals(_cu(ref.depth_case("constant", 24, 40)), _eye_settings(24, 40))
     assert bool((N[:2] == 0).all()) and bool(((N[2] - 1).abs() < 1e-6).all())
 
 
@@ -170,7 +164,7 @@ def test_fused_loss_equals_the_composition():
     from contextgs_amd.normals import depth_normals, normal_consistency
     H, W = 48, 64
     x = ref.pixel_inputs("rough", H, W)
-    rs = _settings(H, W)
+    rs = _eye_settings(H, W)
     d, nm = _cu(x["depth"], True), _cu(x["normals"], True)
     E = normal_consistency(nm, d, rs, weight=_cu(x["weight"]))
     (E * _cu(x["gE"])).sum().backward()
@@ -188,7 +182,7 @@ def test_loss_backward_computes_only_the_gradients_asked_for():
     from contextgs_amd.normals import normal_consistency
     H, W = 17, 33
     x = ref.pixel_inputs("rough", H, W)
-    rs = _settings(H, W)
+    rs = _eye_settings(H, W)
     got = {}
     for need_n, need_d in ((True, True), (True, False), (False, True)):
         nm, d = _cu(x["normals"], need_n), _cu(x["depth"], need_d)
@@ -202,22 +196,6 @@ def test_loss_backward_computes_only_the_gradients_asked_for():
 
 
 # ---- (2) the rendered normal map -----------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _scene(P, W, H, seed, extent=1.0, srange=(0.005, 0.05), eye=(0.4, -2.2, 0.6)):
-    """The `ragged` and `single` scenes of tests/test_raster_geom_gpu.py, restated."""
-    from contextgs_amd.synth import look_at_camera, random_gaussians
-    cam = look_at_camera(eye, (0, 0, 0), W, H, fovx_deg=60.0)
-    g = random_gaussians(P, seed=seed, extent=extent, scale_lo=srange[0], scale_hi=srange[1])
-    if P >= 20:     # some Gaussians behind the near plane
-        e = np.array([0.4, -2.2, 0.6], dtype=np.float32)
-        g["means3D"][::20] = e + 0.3 * (e - g["means3D"][::20])
-    return cam, g
-
-
-def _named_scene(name):
-    return _scene(200, 40, 24, 3, 1.0, (0.02, 0.12)) if name == "ragged" else _scene(1, 64, 48, 1)
-
-
 def _raster(rs, g, C, composed, seed=0, **kw):
     """One forward + backward with user features of C columns (0: none), either with return_normals=True or with the normals
     appended to the features by hand.  The loss weights every channel of every output with fixed random numbers."""
@@ -257,8 +235,8 @@ def _raster(rs, g, C, composed, seed=0, **kw):
 @pytest.mark.parametrize("C", [0, 1, 29])
 @pytest.mark.parametrize("name", ["ragged", "single"])
 def test_rendered_normals_equal_the_feature_composition(name, C):
-    cam, g = _named_scene(name)
-    rs = _cam_settings(cam)
+    cam, g = named_scene(name)
+    rs = settings(cam)
     more = dict(return_aux=True, return_geometry=True) if C == 1 else dict(return_aux=(C == 29))
     a = _raster(rs, g, C, composed=False, **more)
     b = _raster(rs, g, C, composed=True, **more)
@@ -278,8 +256,8 @@ def test_rendered_normals_equal_the_feature_composition(name, C):
 
 def test_rendered_normals_match_the_fp64_blend_of_restated_normals(oracle64):
     """Independent of the feature path: the oracle blends the restated fp64 per-Gaussian normals as colours."""
-    cam, g = _named_scene("ragged")
-    a = _raster(_cam_settings(cam), g, 0, composed=False)
+    cam, g = named_scene("ragged")
+    a = _raster(settings(cam), g, 0, composed=False)
     V = np.asarray(cam.world_view_transform, np.float32)
     f = ref.gaussian_normals(g["means3D"], g["scales"], g["rotations"], V)
     assert (f["margin"] >= 1e-4).all()
@@ -290,9 +268,9 @@ def test_rendered_normals_match_the_fp64_blend_of_restated_normals(oracle64):
 
 def test_return_normals_with_antialiasing_shs_contrib_and_absgrad():
     from contextgs_amd.rasterizer import GaussianRasterizer
-    cam, g = _named_scene("ragged")
+    cam, g = named_scene("ragged")
     P = g["means3D"].shape[0]
-    rs = _cam_settings(cam, aa=True)
+    rs = settings(cam, aa=True)
     t = {k: _cu(v, True) for k, v in g.items()}
     sh = _cu(np.random.default_rng(5).normal(size=(P, 4, 3)).astype(np.float32) * 0.3, True)
     m2 = torch.zeros(P, 4, device="cuda", requires_grad=True)
@@ -312,9 +290,9 @@ def test_return_normals_with_antialiasing_shs_contrib_and_absgrad():
 
 def test_no_gaussians():
     from contextgs_amd.rasterizer import GaussianRasterizer
-    cam, g = _named_scene("ragged")
+    cam, g = named_scene("ragged")
     e = {k: _cu(v[:0], True) for k, v in g.items()}
-    color, radii, ex = GaussianRasterizer(_cam_settings(cam))(
+    color, radii, ex = GaussianRasterizer(settings(cam))(
         means3D=e["means3D"], means2D=torch.zeros(0, 3, device="cuda"), opacities=e["opacities"], colors_precomp=e["colors"],
         scales=e["scales"], rotations=e["rotations"], return_normals=True)
     assert ex["normals"].shape == (3, 24, 40) and bool((ex["normals"] == 0).all())
@@ -329,7 +307,7 @@ def test_rendered_normals_and_depth_normals_share_a_hemisphere():
     cam, g = ref.plane_scene()
     H, W = cam.image_height, cam.image_width
     assert (H, W) == (48, 64)
-    rs = _cam_settings(cam)
+    rs = settings(cam)
     t = {k: _cu(v) for k, v in g.items()}
     P = g["means3D"].shape[0]
     color, radii, ex = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=torch.zeros(P, 3, device="cuda"),
@@ -357,13 +335,6 @@ def test_rendered_normals_and_depth_normals_share_a_hemisphere():
 
 
 # ---- render() ----------------------------------------------------------------------------------------------------------------
-def _model(N=20000, W=320, H=180):
-    from contextgs_amd.synth import SynthPipe, make_scene, orbit_cameras
-    pc = make_scene(N, seed=0)
-    cams = [c.to_torch("cuda") for c in orbit_cameras(4, W, H)]
-    return pc, cams, SynthPipe(), torch.zeros(3, device="cuda")
-
-
 def _render(pc, cam, pipe, bg, **kw):
     from contextgs_amd import ctx_ops
     from contextgs_amd.renderer import prefilter_voxel, render
@@ -376,7 +347,7 @@ def _render(pc, cam, pipe, bg, **kw):
 def test_render_returns_the_normals_and_the_backward_reaches_the_anchors():
     from contextgs_amd.normals import normal_consistency
     from contextgs_amd.renderer import _raster_settings
-    pc, cams, pipe, bg = _model()
+    pc, cams, pipe, bg = model()
     cam = cams[1]
     pc.train(True)
     with torch.enable_grad():

@@ -10,6 +10,8 @@ import types
 import pytest
 import torch
 
+from raster_harness import fake_cfg
+
 CGS_OK = 0
 CGS_ERR_ARG = 1
 CGS_ERR_WORKSPACE = 3
@@ -18,19 +20,12 @@ NEW_SYMBOLS = ("cgs_raster_backward_abs", "cgs_raster_bwd_abs_scratch_bytes", "c
 P1 = C.c_void_p(4096)      # a non-NULL stand-in: the checks only look at which pointers are given
 
 
-def _cfg(H=16, W=16):
-    from contextgs_amd import _lib
-    fake = C.c_void_p(256)     # never dereferenced: every call below fails its argument checks first
-    return _lib.RasterCfg(image_height=H, image_width=W, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
-                          debug=0, viewmatrix=fake, projmatrix=fake, campos=fake, bg=fake)
-
-
 def _backward_abs(P=1, R=0, geom=P1, img=P1, scratch=P1, scratch_bytes=1 << 40, features=P1, Cn=5, g_map=P1, d_feat=P1, m2=P1,
                   opts=0):
     """colours + scales / rotations, every other pointer given"""
     from contextgs_amd import _lib
     L = _lib.lib()
-    rc = L.cgs_raster_backward_abs(C.byref(_cfg()), P, R, P1, P1, None, 0, 0, P1, P1, P1, None, P1, geom, 1 << 30, None, 0, img,
+    rc = L.cgs_raster_backward_abs(C.byref(fake_cfg()), P, R, P1, P1, None, 0, 0, P1, P1, P1, None, P1, geom, 1 << 30, None, 0, img,
                                    1 << 30, None, None, None, None, P1, m2, P1, P1, None, P1, P1, None, scratch, scratch_bytes,
                                    None, opts, features, Cn, g_map, d_feat)
     return rc, L.cgs_last_error().decode()

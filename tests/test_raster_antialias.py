@@ -6,23 +6,18 @@ import math
 import pytest
 import torch
 
+from raster_harness import fake_cfg
+
 CGS_ERR_ARG = 1
 CGS_RASTER_ANTIALIAS = 1
 P1 = C.c_void_p(4096)      # a non-NULL stand-in: the checks only look at which pointers are given
-
-
-def _cfg(campos=True):
-    from contextgs_amd import _lib
-    fake = C.c_void_p(256)     # never dereferenced: every call below fails its argument checks first
-    return _lib.RasterCfg(image_height=16, image_width=16, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
-                          debug=0, viewmatrix=fake, projmatrix=fake, campos=fake if campos else None, bg=fake)
 
 
 def _launch_opt(opts, P=1, colors=P1, shs=None, D=0, M=0, scales=P1, rotations=P1, cov3D=None, cfg=None):
     from contextgs_amd import _lib
     L = _lib.lib()
     ticket = C.c_uint64(7)
-    rc = L.cgs_raster_preprocess_launch_opt(C.byref(cfg or _cfg()), P, P1, colors, shs, D, M, P1, scales, rotations, cov3D, P1,
+    rc = L.cgs_raster_preprocess_launch_opt(C.byref(cfg or fake_cfg()), P, P1, colors, shs, D, M, P1, scales, rotations, cov3D, P1,
                                             1 << 30, P1, None, C.byref(ticket), opts)
     return rc, L.cgs_last_error().decode(), ticket.value
 
@@ -32,8 +27,8 @@ def _backward_opt(opts, P=1, colors=P1, shs=None, D=0, M=0, scales=P1, rotations
     L = _lib.lib()
     o = dict(means3D=P1, means2D=P1, colors=P1, opac=P1, shs=None, scales=P1, rots=P1, cov=None)
     o.update(outs or {})
-    rc = L.cgs_raster_backward_opt(C.byref(_cfg()), P, 0, P1, colors, shs, D, M, opac, scales, rotations, cov3D, P1, P1, 1 << 30,
-                                   None, 0, P1, 1 << 30, P1, None, None, None, o["means3D"], o["means2D"], o["colors"],
+    rc = L.cgs_raster_backward_opt(C.byref(fake_cfg()), P, 0, P1, colors, shs, D, M, opac, scales, rotations, cov3D, P1, P1,
+                                   1 << 30, None, 0, P1, 1 << 30, P1, None, None, None, o["means3D"], o["means2D"], o["colors"],
                                    o["opac"], o["shs"], o["scales"], o["rots"], o["cov"], P1, 1 << 40, None, opts)
     return rc, L.cgs_last_error().decode()
 
@@ -111,7 +106,7 @@ def test_backward_without_antialiasing_does_not_need_opacities():
 
 
 def test_sh_without_campos():
-    rc, msg, _ = _launch_opt(CGS_RASTER_ANTIALIAS, colors=None, shs=P1, D=1, M=4, cfg=_cfg(campos=False))
+    rc, msg, _ = _launch_opt(CGS_RASTER_ANTIALIAS, colors=None, shs=P1, D=1, M=4, cfg=fake_cfg(campos=False))
     assert rc == CGS_ERR_ARG and "campos" in msg
 
 

@@ -14,120 +14,27 @@ import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera, random_gaussians
+from raster_harness import BG, R_MIN, check_image, close, h_torch, leaf, model, scene, settings, shs, sigma_rs
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(1, 64, 48), (64, 128, 96), (4000, 256, 256), (30000, 800, 800), (200000, 1920, 1080)]   # test_raster_sh_cov_gpu
 FORMS = ["colors+scales", "shs+scales", "colors+cov", "shs+cov"]
-BG = (0.1, 0.25, 0.4)
 MAPS = ("depth", "invdepth", "alpha")
-R_MIN = 2.5e-5
 
 
-def _scene(P, W, H, seed, extent=1.0, srange=(0.005, 0.05)):
-    cam = look_at_camera((0.4, -2.2, 0.6), (0, 0, 0), W, H, fovx_deg=60.0)
-    g = random_gaussians(P, seed=seed, extent=extent, scale_lo=srange[0], scale_hi=srange[1])
-    if P >= 20:     # some Gaussians behind the near plane
-        eye = np.array([0.4, -2.2, 0.6], dtype=np.float32)
-        g["means3D"][::20] = eye + 0.3 * (eye - g["means3D"][::20])
-    return cam, g
-
-
-def _settings(cam, aa, bg=BG, D=2):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    c = cam.to_torch("cuda")
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.tensor(bg, dtype=torch.float32, device="cuda"), scale_modifier=1.0,
-        viewmatrix=c.world_view_transform, projmatrix=c.full_proj_transform, sh_degree=D, campos=c.camera_center,
-        prefiltered=False, debug=False, antialiasing=aa)
-
-
-def _leaf(a):
-    return torch.tensor(a, device="cuda", requires_grad=True)
-
-
-# ---- the torch restatement (fp64) ---------------------------------------------------------------------------------------
-def quat_to_rot(q):
-    r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]      # used as given, like the kernels
-    return torch.stack([
-        1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
-        2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
-        2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).view(-1, 3, 3)
-
-
-def sigma_rs(scales, rotations, scale_modifier=1.0):
-    L = quat_to_rot(rotations.double()) * (scale_modifier * scales.double())[:, None, :]
-    return L @ L.transpose(1, 2)
-
-
+# ---- the torch restatement (fp64): h_torch, sigma_rs of tests/raster_harness.py and ------------------------------------
 def sigma_cov6(cov6):
     c = cov6.double()
     return torch.stack([c[:, 0], c[:, 1], c[:, 2], c[:, 1], c[:, 3], c[:, 4], c[:, 2], c[:, 4], c[:, 5]], 1).view(-1, 3, 3)
-
-
-def cov2d_torch(means3D, Sigma, rs):
-    """J W Sigma W^T J^T before the dilation, with cgs_jacobian's 1.3 tanfov clamp (fp64)."""
-    V = rs.viewmatrix.double()
-    m = means3D.double()
-    t = m @ V[:3, :3] + V[3, :3]
-    tx, ty, tz = t[:, 0], t[:, 1], t[:, 2]
-    limx, limy = 1.3 * rs.tanfovx, 1.3 * rs.tanfovy
-    tx = torch.clamp(tx / tz, -limx, limx) * tz
-    ty = torch.clamp(ty / tz, -limy, limy) * tz
-    fx = rs.image_width / (2 * rs.tanfovx)
-    fy = rs.image_height / (2 * rs.tanfovy)
-    z0 = torch.zeros_like(tz)
-    J = torch.stack([fx / tz, z0, -fx * tx / (tz * tz), z0, fy / tz, -fy * ty / (tz * tz)], 1).view(-1, 2, 3)
-    A = J @ V[:3, :3].T
-    return A @ Sigma @ A.transpose(1, 2)
-
-
-def h_torch(means3D, Sigma, rs):
-    c2 = cov2d_torch(means3D, Sigma, rs)
-    a, b, c = c2[:, 0, 0], c2[:, 0, 1], c2[:, 1, 1]
-    d0 = a * c - b * b
-    d1 = (a + 0.3) * (c + 0.3) - b * b
-    return torch.sqrt(torch.clamp_min(d0 / d1, R_MIN)), d0 / d1
-
-
-# ---- checks -------------------------------------------------------------------------------------------------------------
-def _check_image(a, b, rmse_max, what):
-    d = (a - b).abs().cpu().numpy()
-    rmse = float(np.sqrt((d ** 2).mean()))
-    frac = float((d > 2e-5).sum()) / d.size
-    print(f"[allowance] {what}: rmse {rmse:.2e}, {frac:.2e} of values beyond 2e-5, max {float(d.max()):.2e}")
-    assert rmse <= rmse_max, (what, rmse)
-    assert frac <= 1e-4, (what, frac, d.max())
-    assert d.max() <= 1.0 / 255 + 1e-4, (what, d.max())
-
-
-def _close(a, b, what, tol=2e-4, rows=None, allow_frac=1e-4):
-    """max |a - b| <= tol * max |b| on every row but at most allow_frac of them: op_eff comes from fp32 h on one side and
-    fp64 h on the other, and a last-ulp difference can flip an alpha >= 1/255 decision on a pixel."""
-    a, b = a.detach().float().cpu(), b.detach().float().cpu()
-    if rows is not None:
-        a, b = a[rows], b[rows]
-    if not a.numel():
-        return
-    scale = max(float(b.abs().max()), 1e-12)
-    row_err = (a - b).abs().reshape(a.shape[0], -1).amax(dim=1) / scale
-    n_bad = int((row_err > tol).sum())
-    print(f"[allowance] {what}: {n_bad} of {a.shape[0]} rows beyond {tol:g}, max {float(row_err.max()):.2e}")
-    assert n_bad <= int(allow_frac * a.shape[0]), (what, n_bad, float(row_err.max()))
-
-
-def _shs(P, M, seed):
-    rng = np.random.default_rng(seed + 1000)
-    return rng.normal(0.0, 0.25, size=(P, M, 3)).astype(np.float32)
 
 
 def _run(form, g, sh, rs, aa_ref, w, aux):
     """One render + backward in `form`.  aa_ref: the AA-off call with opacities o * h_torch (autograd through h_torch)."""
     from contextgs_amd.rasterizer import GaussianRasterizer
     P = g["means3D"].shape[0]
-    t = {k: _leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
-    t["shs"] = _leaf(sh)
+    t = {k: leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
+    t["shs"] = leaf(sh)
     m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
     cov6 = None
     if "cov" in form:
@@ -165,22 +72,22 @@ def _run(form, g, sh, rs, aa_ref, w, aux):
 @pytest.mark.parametrize("P, W, H, aux", [c + (False,) for c in CASES] + [c + (True,) for c in CASES[2:]])
 @pytest.mark.parametrize("form", FORMS)
 def test_matches_the_aa_off_path_with_h_in_torch(P, W, H, aux, form):
-    cam, g = _scene(P, W, H, seed=P + 5)
-    sh = _shs(P, 9, seed=P)
+    cam, g = scene(P, W, H, seed=P + 5)
+    sh = shs(P, 9, seed=P, clamp_dc=False)
     rng = np.random.default_rng(7)
     w = {k: torch.tensor(rng.normal(size=(3 if k == "color" else 1, H, W)).astype(np.float32), device="cuda")
          for k in ("color",) + MAPS}
-    new = _run(form, g, sh, _settings(cam, True), False, w, aux)
-    ref = _run(form, g, sh, _settings(cam, False), True, w, aux)
+    new = _run(form, g, sh, settings(cam, aa=True, D=2), False, w, aux)
+    ref = _run(form, g, sh, settings(cam, aa=False, D=2), True, w, aux)
     assert torch.equal(new["radii"], ref["radii"])
-    _check_image(new["color"], ref["color"], 1e-5, f"image {form} P={P}")
+    check_image(new["color"], ref["color"], 1e-5, f"image {form} P={P}")
     for k in MAPS if aux else ():
         scale = max(float(ref[k].abs().max()), 1e-12)
-        _check_image(new[k] / scale, ref[k] / scale, 1e-5, f"{k} {form} P={P}")
+        check_image(new[k] / scale, ref[k] / scale, 1e-5, f"{k} {form} P={P}")
     keys = ["means3D", "opacities", "m2"] + (["shs"] if "shs" in form else ["colors"]) + \
         (["scales", "rotations"])       # cov form: through cov6_torch to the same leaves
     for k in keys:
-        _close(new[k], ref[k], f"d{k} {form} aux={aux} P={P}")
+        close(new[k], ref[k], f"d{k} {form} aux={aux} P={P}", allow_frac=1e-4)
     if P >= 4000:
         vis = new["radii"] > 0
         assert float(new["opacities"][vis].abs().sum()) > 0
@@ -190,10 +97,10 @@ def test_matches_the_aa_off_path_with_h_in_torch(P, W, H, aux, form):
 @pytest.mark.parametrize("P, W, H", CASES[1:4])
 def test_matches_the_oracle_with_the_h_chain(oracle32, P, W, H):
     from contextgs_amd.rasterizer import GaussianRasterizer
-    cam, g = _scene(P, W, H, seed=P + 13)
-    rs = _settings(cam, True)
+    cam, g = scene(P, W, H, seed=P + 13)
+    rs = settings(cam, aa=True, D=2)
     gC = np.random.default_rng(P).normal(size=(3, H, W)).astype(np.float32)
-    t = {k: _leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
+    t = {k: leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
     m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
     color, radii = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"],
                                           colors_precomp=t["colors"], scales=t["scales"], rotations=t["rotations"])
@@ -210,12 +117,12 @@ def test_matches_the_oracle_with_the_h_chain(oracle32, P, W, H):
     geff = torch.tensor(ref["dL_dopacities"], device="cuda", dtype=torch.float64)
     (geff * o * h).sum().backward()
     assert np.array_equal(radii.cpu().numpy(), ref["radii"])
-    _check_image(color.detach(), torch.tensor(ref["color"], device="cuda"), 1e-5, f"oracle image P={P}")
-    _close(t["opacities"].grad, (torch.tensor(ref["dL_dopacities"]) * h.detach().float().cpu())[:, None],
+    check_image(color.detach(), torch.tensor(ref["color"], device="cuda"), 1e-5, f"oracle image P={P}")
+    close(t["opacities"].grad, (torch.tensor(ref["dL_dopacities"]) * h.detach().float().cpu())[:, None],
            f"oracle dopacities P={P}", allow_frac=2e-3)
     for k, name in (("means3D", "dL_dmeans3D"), ("scales", "dL_dscales"), ("rotations", "dL_drotations")):
-        _close(t[k].grad, torch.tensor(ref[name]) + q[k].grad.float().cpu(), f"oracle d{k} P={P}", allow_frac=2e-3)
-    _close(m2.grad, torch.tensor(ref["dL_dmeans2D"]), f"oracle dmeans2D P={P}", allow_frac=2e-3)
+        close(t[k].grad, torch.tensor(ref[name]) + q[k].grad.float().cpu(), f"oracle d{k} P={P}", allow_frac=2e-3)
+    close(m2.grad, torch.tensor(ref["dL_dmeans2D"]), f"oracle dmeans2D P={P}", allow_frac=2e-3)
 
 
 # ---- the clamp ----------------------------------------------------------------------------------------------------------
@@ -229,7 +136,7 @@ def _record_opacity(P):
 def test_clamp_regime():
     from contextgs_amd.rasterizer import GaussianRasterizer
     P, W, H = 3000, 256, 256
-    cam, g = _scene(P, W, H, seed=41)
+    cam, g = scene(P, W, H, seed=41)
     g["means3D"][::20] = g["means3D"][1::20]       # every Gaussian in front of the camera
     rng = np.random.default_rng(41)
     k = np.arange(P)
@@ -238,12 +145,12 @@ def test_clamp_regime():
     g["scales"][k % 3 == 1, 1:] = 1e-7
     g["opacities"][:] = rng.uniform(0.85, 1.0, size=(P, 1)).astype(np.float32)
     g["opacities"][k % 6 == 0] = 0.5             # points at 0.5: op_eff = 0.0025 < 1/255
-    rs_on, rs_off = _settings(cam, True), _settings(cam, False)
+    rs_on, rs_off = settings(cam, aa=True, D=2), settings(cam, aa=False, D=2)
     w = torch.tensor(rng.normal(size=(3, H, W)).astype(np.float32), device="cuda")
 
     def run(rs, op):
-        t = {k: _leaf(g[k]) for k in ("means3D", "scales", "rotations", "colors")}
-        t["opacities"] = _leaf(op)
+        t = {k: leaf(g[k]) for k in ("means3D", "scales", "rotations", "colors")}
+        t["opacities"] = leaf(op)
         color, radii = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=torch.zeros(P, 3, device="cuda"),
                                               opacities=t["opacities"], colors_precomp=t["colors"], scales=t["scales"],
                                               rotations=t["rotations"])
@@ -267,11 +174,11 @@ def test_clamp_regime():
     keep = ~clamped.numpy()
     op_ref[keep] = op_rec.numpy()[keep][:, None]     # the others at the kernel's own op_eff
     c_ref, _, g_ref = run(rs_off, op_ref)
-    _check_image(c_on, c_ref, 1e-5, "clamp image")
+    check_image(c_on, c_ref, 1e-5, "clamp image")
     rows = clamped
     for k in ("means3D", "scales", "rotations"):
-        _close(g_on[k], g_ref[k], f"clamp d{k}", rows=rows)
-    _close(g_on["opacities"], g_ref["opacities"] * 0.005, "clamp dopacities", rows=rows)
+        close(g_on[k], g_ref[k], f"clamp d{k}", rows=rows, allow_frac=1e-4)
+    close(g_on["opacities"], g_ref["opacities"] * 0.005, "clamp dopacities", rows=rows, allow_frac=1e-4)
     faint = clamped & (o * 0.005 < 1.0 / 255)
     assert int(faint.sum()) > 0
     for k in g_on:
@@ -291,7 +198,7 @@ def test_needles_h_against_fp64(form):
     g["scales"] = np.stack([long, long / ratio, long / ratio * rng.uniform(0.5, 2.0, size=P)], 1).astype(np.float32)
     q = rng.normal(size=(P, 4))
     g["rotations"] = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)     # oblique
-    rs = _settings(cam, True)
+    rs = settings(cam, aa=True, D=2)
     t = {k: torch.tensor(g[k], device="cuda") for k in g}
     kw = dict(means3D=t["means3D"], means2D=torch.zeros(P, 3, device="cuda"), opacities=t["opacities"],
               colors_precomp=t["colors"])
@@ -339,7 +246,7 @@ def test_antialiasing_keeps_brightness_across_resolutions():
         cam, g = _sparse_field(W)
         t = {k: torch.tensor(v, device="cuda") for k, v in g.items()}
         with torch.no_grad():
-            color, _ = GaussianRasterizer(_settings(cam, aa, bg=(0.0, 0.0, 0.0)))(
+            color, _ = GaussianRasterizer(settings(cam, aa=aa, D=2, bg=(0.0, 0.0, 0.0)))(
                 means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"],
                 colors_precomp=t["colors"], scales=t["scales"], rotations=t["rotations"])
         mean[(aa, W)] = float(color.mean())
@@ -354,13 +261,6 @@ def test_antialiasing_keeps_brightness_across_resolutions():
 
 
 # ---- render() -----------------------------------------------------------------------------------------------------------
-def _model(N=20000, W=320, H=180):
-    from contextgs_amd.synth import SynthPipe, make_scene, orbit_cameras
-    pc = make_scene(N, seed=0)
-    cams = [c.to_torch("cuda") for c in orbit_cameras(4, W, H)]
-    return pc, cams, SynthPipe(), torch.zeros(3, device="cuda")
-
-
 def _seeded(pc, cam, pipe, bg):
     from contextgs_amd import ctx_ops
     from contextgs_amd.renderer import prefilter_voxel
@@ -380,7 +280,7 @@ class _AAPipe:
 def test_render_with_pipe_antialiasing(training):
     from contextgs_amd.rasterizer import GaussianRasterizer
     from contextgs_amd.renderer import _raster_settings, generate_neural_gaussians, render
-    pc, cams, pipe, bg = _model()
+    pc, cams, pipe, bg = model()
     assert not hasattr(pipe, "antialiasing")
     pc.train(training)
     cam = cams[1]
@@ -414,7 +314,7 @@ def test_render_with_pipe_antialiasing(training):
 
 def test_pipe_without_the_attribute_renders_as_before():
     from contextgs_amd.renderer import render
-    pc, cams, pipe, bg = _model()
+    pc, cams, pipe, bg = model()
     pc.train(False)
 
     class _Off(_AAPipe):

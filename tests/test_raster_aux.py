@@ -8,18 +8,13 @@ import math
 import pytest
 import torch
 
+from raster_harness import fake_cfg
+
 CGS_ERR_ARG = 1
 CGS_ERR_WORKSPACE = 3
 
 NEW_SYMBOLS = ("cgs_raster_render_aux", "cgs_raster_backward_aux", "cgs_raster_bwd_aux_scratch_bytes")
 P1 = C.c_void_p(4096)      # a non-NULL stand-in: the checks only look at which pointers are given
-
-
-def _cfg(campos=True, H=16, W=16):
-    from contextgs_amd import _lib
-    fake = C.c_void_p(256)     # never dereferenced: every call below fails its argument checks first
-    return _lib.RasterCfg(image_height=H, image_width=W, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
-                          debug=0, viewmatrix=fake, projmatrix=fake, campos=fake if campos else None, bg=fake)
 
 
 def _render_aux(cfg, P=1, R=1, geom=P1, bin_ws=P1, img=P1, depth=P1, invdepth=P1, alpha=P1):
@@ -55,14 +50,14 @@ def test_new_symbols_resolve():
 
 def test_render_aux_argument_errors():
     assert _render_aux(None)[0] == CGS_ERR_ARG
-    rc, msg = _render_aux(_cfg(H=0))
+    rc, msg = _render_aux(fake_cfg(H=0))
     assert rc == CGS_ERR_ARG and "image size" in msg
     for kw in (dict(depth=None), dict(invdepth=None), dict(alpha=None), dict(img=None), dict(geom=None), dict(bin_ws=None)):
-        rc, msg = _render_aux(_cfg(), **kw)
+        rc, msg = _render_aux(fake_cfg(), **kw)
         assert rc == CGS_ERR_ARG and "NULL" in msg, (kw, msg)
-    rc, msg = _render_aux(_cfg(), P=-1)
+    rc, msg = _render_aux(fake_cfg(), P=-1)
     assert rc == CGS_ERR_ARG and "P < 0" in msg
-    rc, msg = _render_aux(_cfg(), R=-1)
+    rc, msg = _render_aux(fake_cfg(), R=-1)
     assert rc == CGS_ERR_ARG
 
 
@@ -80,18 +75,19 @@ def test_render_aux_argument_errors():
     (dict(colors=P1, scales=P1, rotations=P1, outs=dict(scales=P1, rots=P1), scratch=None), "NULL input"),
 ])
 def test_backward_aux_argument_errors(kw, needle):
-    rc, msg = _backward_aux(_cfg(), **kw)
+    rc, msg = _backward_aux(fake_cfg(), **kw)
     assert rc == CGS_ERR_ARG, (rc, msg)
     assert needle in msg, msg
 
 
 def test_backward_aux_small_scratch_is_a_workspace_error():
-    rc, msg = _backward_aux(_cfg(), P=1000, colors=P1, scales=P1, rotations=P1, outs=dict(scales=P1, rots=P1), scratch_bytes=16)
+    rc, msg = _backward_aux(fake_cfg(), P=1000, colors=P1, scales=P1, rotations=P1, outs=dict(scales=P1, rots=P1), scratch_bytes=16)
     assert rc == CGS_ERR_WORKSPACE and "scratch" in msg
 
 
 def test_backward_aux_sh_without_campos():
-    rc, msg = _backward_aux(_cfg(campos=False), shs=P1, D=1, M=4, scales=P1, rotations=P1, outs=dict(shs=P1, scales=P1, rots=P1))
+    rc, msg = _backward_aux(fake_cfg(campos=False), shs=P1, D=1, M=4, scales=P1, rotations=P1,
+                            outs=dict(shs=P1, scales=P1, rots=P1))
     assert rc == CGS_ERR_ARG and "campos" in msg
 
 

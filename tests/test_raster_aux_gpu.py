@@ -7,114 +7,38 @@ tests/test_raster_gpu.py: images by RMSE <= 1e-5 plus a max-abs allowance on a 1
 maximum), gradients 2e-4 of each tensor's maximum with a 2e-3 fraction allowance.
 """
 import itertools
-import math
 
 import numpy as np
 import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera, random_gaussians
+from raster_harness import (BG, aux_colors, check_grad, check_map, cov6_torch, leaf, model, run, scene, settings, sh_eval_torch,
+                            shs, view_z)
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(1, 64, 48), (64, 128, 96), (4000, 256, 256), (30000, 800, 800), (200000, 1920, 1080)]   # test_raster_sh_cov_gpu
-BG = (0.1, 0.25, 0.4)
 MAPS = ("depth", "invdepth", "alpha")
 
 
-def _scene(P, W, H, seed, extent=1.0, srange=(0.005, 0.05)):
-    cam = look_at_camera((0.4, -2.2, 0.6), (0, 0, 0), W, H, fovx_deg=60.0)
-    g = random_gaussians(P, seed=seed, extent=extent, scale_lo=srange[0], scale_hi=srange[1])
-    if P >= 20:     # some Gaussians behind the near plane
-        eye = np.array([0.4, -2.2, 0.6], dtype=np.float32)
-        g["means3D"][::20] = eye + 0.3 * (eye - g["means3D"][::20])
-    return cam, g
-
-
-def _view_z(cam, means3D):
-    """z of p_view = [x y z 1] @ V in fp32, in the kernels' order of operations."""
-    V = np.asarray(cam.world_view_transform.detach().cpu().numpy() if hasattr(cam.world_view_transform, "detach")
-                   else cam.world_view_transform, dtype=np.float32).reshape(4, 4)
-    m = means3D.astype(np.float32)
-    return ((V[0, 2] * m[:, 0] + V[1, 2] * m[:, 1]) + V[2, 2] * m[:, 2]) + V[3, 2], V[:3, 2].copy()
-
-
-def _aux_colors(z):
-    ok = z > 0.2            # the near cull: other Gaussians never reach a list
-    zs = np.where(ok, z, 1.0).astype(np.float32)
-    return np.stack([np.where(ok, zs, 0), np.where(ok, np.float32(1.0) / zs, 0), np.where(ok, 1.0, 0)], 1).astype(np.float32)
-
-
-def _settings(cam, bg=BG, D=1, debug=False):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    c = cam.to_torch("cuda")
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.tensor(bg, dtype=torch.float32, device="cuda"), scale_modifier=1.0,
-        viewmatrix=c.world_view_transform, projmatrix=c.full_proj_transform, sh_degree=D, campos=c.camera_center,
-        prefiltered=False, debug=debug)
-
-
-def _leaf(a):
-    return torch.tensor(a, device="cuda", requires_grad=True)
-
-
-def _run(rs, g, return_aux=True, loss_w=None, colors=None):
-    """Forward (and backward of sum(out * w) over the entries of loss_w: keys color / depth / invdepth / alpha)."""
-    from contextgs_amd.rasterizer import GaussianRasterizer
-    P = g["means3D"].shape[0]
-    t = {k: _leaf(v) for k, v in g.items()}
-    if colors is not None:
-        t["colors"] = _leaf(colors)
-    m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
-    res = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"],
-                                 scales=t["scales"], rotations=t["rotations"], return_aux=return_aux)
-    out = {"color": res[0], "radii": res[1]}
-    if return_aux:
-        out.update(res[2])
-    if loss_w:
-        sum(((out[k] * w).sum() for k, w in loss_w.items())).backward()
-    torch.cuda.synchronize()
-    o = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in out.items()}
-    o["grad"] = {k: (None if v.grad is None else v.grad.detach()) for k, v in t.items()}
-    o["grad"]["means2D"] = m2.grad
-    return o
-
-
-def _check_map(a, b, what):
-    a = a.detach().float().cpu().numpy().reshape(-1)
-    b = np.asarray(b, dtype=np.float32).reshape(-1)
-    scale = max(float(np.abs(b).max()), 1e-12)
-    d = np.abs(a - b) / scale
-    rmse = float(np.sqrt((d ** 2).mean()))
-    n_out = int((d > 2e-5).sum())
-    print(f"[allowance] {what}: rmse {rmse:.2e}, {n_out} of {d.size} values beyond 2e-5 of the max {scale:.3g}, worst {d.max():.2e}")
-    assert rmse <= 1e-5, (what, rmse)
-    assert n_out <= 1e-4 * d.size, (what, n_out, float(d.max()))
-
-
-def _check_grad(a, b, what, allow_frac=2e-3, tol=2e-4):
-    a = a.detach().float().cpu().numpy().reshape(a.shape[0], -1) if torch.is_tensor(a) else a
-    b = np.asarray(b, dtype=np.float32).reshape(a.shape)
-    scale = max(1e-6, float(np.abs(b).max()))
-    err = np.abs(a - b) / scale
-    n_out = int((err > tol).sum())
-    print(f"[allowance] {what}: {n_out} of {err.size} entries beyond {tol:g} of the maximum, worst {err.max():.2e}")
-    assert n_out <= allow_frac * err.size, (what, n_out, float(err.max()))
+def _run(rs, g, return_aux=True, **kw):
+    """raster_harness.run with the maps asked for unless the caller says otherwise."""
+    return run(rs, g, return_aux=return_aux, **kw)
 
 
 def _oracle_aux(oracle, cam, g, z, dl=None):
-    return oracle.render(cam.oracle_dict(bg=(0.0, 0.0, 0.0)), g["means3D"], _aux_colors(z), g["opacities"], g["scales"],
+    return oracle.render(cam.oracle_dict(bg=(0.0, 0.0, 0.0)), g["means3D"], aux_colors(z), g["opacities"], g["scales"],
                          g["rotations"], dL_dout=dl)
 
 
 # ---- forward ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("P, W, H", CASES)
 def test_forward_maps_match_the_oracle(oracle32, P, W, H):
-    cam, g = _scene(P, W, H, seed=P)
-    z, _ = _view_z(cam, g["means3D"])
+    cam, g = scene(P, W, H, seed=P)
+    z, _ = view_z(cam, g["means3D"])
     ref = _oracle_aux(oracle32, cam, g, z)
-    rs = _settings(cam, debug=(P == 1))          # the smallest case with a synchronised check after every kernel
+    rs = settings(cam, debug=(P == 1))          # the smallest case with a synchronised check after every kernel
     out = _run(rs, g)
     plain = _run(rs, g, return_aux=False)
     # no interference: the colour image and radii are those of the plain call, bit for bit
@@ -122,10 +46,10 @@ def test_forward_maps_match_the_oracle(oracle32, P, W, H):
     assert (out["radii"].cpu().numpy() == ref["radii"]).all()
     for k in MAPS:
         assert out[k].shape == (1, H, W) and out[k].dtype == torch.float32
-    _check_map(out["depth"], ref["color"][0], f"depth P={P}")
-    _check_map(out["invdepth"], ref["color"][1], f"invdepth P={P}")
-    _check_map(out["alpha"], ref["color"][2], f"alpha (sum w) P={P}")
-    _check_map(out["alpha"], 1.0 - ref["final_T"], f"alpha (1 - T) P={P}")
+    check_map(out["depth"], ref["color"][0], f"depth P={P}")
+    check_map(out["invdepth"], ref["color"][1], f"invdepth P={P}")
+    check_map(out["alpha"], ref["color"][2], f"alpha (sum w) P={P}")
+    check_map(out["alpha"], 1.0 - ref["final_T"], f"alpha (1 - T) P={P}")
     alpha = out["alpha"].cpu().numpy()[0]
     assert (alpha <= 1.0).all() and (alpha >= 0.0).all()
     assert (out["depth"].cpu().numpy() >= 0).all()
@@ -140,13 +64,13 @@ LOSSES = [("depth",), ("invdepth",), ("alpha",), ("color", "depth", "invdepth", 
 @pytest.mark.parametrize("P, W, H, seed, extent, srange", BWD_CASES)
 @pytest.mark.parametrize("keys", LOSSES, ids=["+".join(k) for k in LOSSES])
 def test_backward_matches_the_oracle(oracle32, P, W, H, seed, extent, srange, keys):
-    cam, g = _scene(P, W, H, seed=seed, extent=extent, srange=srange)
-    z, dz = _view_z(cam, g["means3D"])
+    cam, g = scene(P, W, H, seed=seed, extent=extent, srange=srange)
+    z, dz = view_z(cam, g["means3D"])
     rng = np.random.default_rng(seed + 17)
     gC = rng.normal(size=(3, H, W)).astype(np.float32)
     gm = {k: rng.normal(size=(1, H, W)).astype(np.float32) for k in MAPS}
     loss_w = {k: torch.tensor(gC if k == "color" else gm[k], device="cuda") for k in keys}
-    out = _run(_settings(cam), g, loss_w=loss_w)
+    out = _run(settings(cam), g, loss_w=loss_w)
 
     names = ["dL_dmeans3D", "dL_dmeans2D", "dL_dopacities", "dL_dscales", "dL_drotations"]
     exp = {k: 0.0 for k in names}
@@ -166,9 +90,9 @@ def test_backward_matches_the_oracle(oracle32, P, W, H, seed, extent, srange, ke
     gr = out["grad"]
     for k, t in (("dL_dmeans3D", "means3D"), ("dL_dmeans2D", "means2D"), ("dL_dopacities", "opacities"),
                  ("dL_dscales", "scales"), ("dL_drotations", "rotations")):
-        _check_grad(gr[t], exp[k], f"{k} P={P} {'+'.join(keys)}")
+        check_grad(gr[t], exp[k], f"{k} P={P} {'+'.join(keys)}")
     if "color" in keys:
-        _check_grad(gr["colors"], rc["dL_dcolors"], f"dL_dcolors P={P}")
+        check_grad(gr["colors"], rc["dL_dcolors"], f"dL_dcolors P={P}")
     else:
         assert gr["colors"] is None          # the maps send nothing to the colour input
     assert float(gr["means3D"].abs().sum()) > 0
@@ -179,19 +103,18 @@ def test_backward_matches_the_oracle(oracle32, P, W, H, seed, extent, srange, ke
 @pytest.mark.parametrize("form", ["shs+scales", "shs+cov", "colors+cov"])
 def test_all_forms_match_colors_precomp_scales_rotations(P, W, H, form):
     from contextgs_amd.rasterizer import GaussianRasterizer
-    from test_raster_sh_cov_gpu import _shs, cov6_torch, sh_eval_torch
     D, M = 2, 9
-    cam, g = _scene(P, W, H, seed=P + 3)
-    sh = _shs(P, M, seed=P)
-    rs = _settings(cam, D=D)
+    cam, g = scene(P, W, H, seed=P + 3)
+    sh = shs(P, M, seed=P)
+    rs = settings(cam, D=D)
     campos = rs.campos.float()
     rng = np.random.default_rng(5)
     w = {k: torch.tensor(rng.normal(size=(3 if k == "color" else 1, H, W)).astype(np.float32), device="cuda")
          for k in ("color",) + MAPS}
 
     def run(use_shs, use_cov):
-        t = {k: _leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
-        t["shs"] = _leaf(sh)
+        t = {k: leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
+        t["shs"] = leaf(sh)
         m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
         kw = dict(means3D=t["means3D"], means2D=m2, opacities=t["opacities"])
         if use_shs:
@@ -214,12 +137,12 @@ def test_all_forms_match_colors_precomp_scales_rotations(P, W, H, form):
     same = (ref["radii"] == new["radii"]).cpu()
     assert float(same.float().mean()) >= 1 - 1e-4
     for k in ("color",) + MAPS:
-        _check_map(new[k], ref[k].cpu().numpy(), f"{k} {form} P={P}")
+        check_map(new[k], ref[k].cpu().numpy(), f"{k} {form} P={P}")
     rows = same.numpy()
     allow = 1e-4 if "cov" in form else 0.0
     for k in ("means3D", "opacities", "scales", "rotations", "m2") + (("shs",) if "shs" in form else ("colors",)):
         a, b = new[k].cpu().numpy(), ref[k].cpu().numpy()
-        _check_grad(a[rows].reshape(int(rows.sum()), -1), b[rows].reshape(int(rows.sum()), -1), f"d{k} {form} P={P}",
+        check_grad(a[rows].reshape(int(rows.sum()), -1), b[rows].reshape(int(rows.sum()), -1), f"d{k} {form} P={P}",
                     allow_frac=max(allow, 2e-3))
 
 
@@ -230,30 +153,30 @@ def test_saturated_stack_reaches_termination(oracle32):
     rng = np.random.default_rng(11)
     g = random_gaussians(P, seed=11, extent=0.2, scale_lo=0.15, scale_hi=0.4)
     g["opacities"][:] = rng.uniform(0.9, 0.999, size=g["opacities"].shape).astype(np.float32)
-    z, _ = _view_z(cam, g["means3D"])
+    z, _ = view_z(cam, g["means3D"])
     ref = _oracle_aux(oracle32, cam, g, z)
     assert float(ref["final_T"].min()) < 1e-3         # the stack saturates: pixels stopped on the 1e-4 test
-    out = _run(_settings(cam), g)
+    out = _run(settings(cam), g)
     alpha = out["alpha"].cpu().numpy()[0]
     assert np.abs(alpha - (1.0 - ref["final_T"])).max() <= 1e-6
     assert (alpha <= 1.0).all()
-    _check_map(out["depth"], ref["color"][0], "depth saturated")
-    _check_map(out["invdepth"], ref["color"][1], "invdepth saturated")
+    check_map(out["depth"], ref["color"][0], "depth saturated")
+    check_map(out["invdepth"], ref["color"][1], "invdepth saturated")
 
 
 def test_ragged_image(oracle32):
     P, W, H = 5000, 257, 255
-    cam, g = _scene(P, W, H, seed=4)
-    z, dz = _view_z(cam, g["means3D"])
+    cam, g = scene(P, W, H, seed=4)
+    z, dz = view_z(cam, g["means3D"])
     ref = _oracle_aux(oracle32, cam, g, z)
-    out = _run(_settings(cam), g)
+    out = _run(settings(cam), g)
     for i, k in enumerate(MAPS):
-        _check_map(out[k], ref["color"][i], f"{k} 257x255")
+        check_map(out[k], ref["color"][i], f"{k} 257x255")
 
 
 def test_empty_views_give_zero_maps():
     cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), 80, 64, fovx_deg=50.0)
-    rs = _settings(cam)
+    rs = settings(cam)
     g = random_gaussians(64, seed=6)
     g["means3D"][:, 1] -= 20.0                        # everything behind the camera
     for gg in (g, {k: v[:0] for k, v in g.items()}):
@@ -267,16 +190,16 @@ def test_empty_views_give_zero_maps():
 def test_forward_after_a_voided_speculative_render(oracle32):
     from contextgs_amd import rasterizer
     P, W, H = 20000, 320, 240
-    cam, g = _scene(P, W, H, seed=9)
-    z, _ = _view_z(cam, g["means3D"])
+    cam, g = scene(P, W, H, seed=9)
+    z, _ = view_z(cam, g["means3D"])
     ref = _oracle_aux(oracle32, cam, g, z)
-    rs = _settings(cam)
+    rs = settings(cam)
     rasterizer._pair_capacity[(H, W)] = 1 << 10       # far below the view's pair count: the speculative render is voided
     out = _run(rs, g)
     assert rasterizer.last_call["num_rendered"] > (1 << 10)
     assert rasterizer.last_call["bin_R"] == rasterizer.last_call["num_rendered"]     # re-rendered with the true count
     for i, k in enumerate(MAPS):
-        _check_map(out[k], ref["color"][i], f"{k} re-rendered")
+        check_map(out[k], ref["color"][i], f"{k} re-rendered")
     again = _run(rs, g)                                   # now with a capacity that holds: the speculative render stands
     for k in MAPS:
         assert torch.equal(again[k], out[k]), k
@@ -285,21 +208,21 @@ def test_forward_after_a_voided_speculative_render(oracle32):
 # ---- no interference ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("P, W, H", [(3000, 256, 256), (30000, 800, 800)])
 def test_colour_only_loss_with_aux_requested_matches_the_plain_call(P, W, H):
-    cam, g = _scene(P, W, H, seed=21)
+    cam, g = scene(P, W, H, seed=21)
     w = torch.tensor(np.random.default_rng(3).normal(size=(3, H, W)).astype(np.float32), device="cuda")
-    a = _run(_settings(cam), g, return_aux=False, loss_w={"color": w})
-    b = _run(_settings(cam), g, return_aux=True, loss_w={"color": w})
+    a = _run(settings(cam), g, return_aux=False, loss_w={"color": w})
+    b = _run(settings(cam), g, return_aux=True, loss_w={"color": w})
     assert torch.equal(a["color"], b["color"])
     for k in ("means3D", "means2D", "colors", "opacities", "scales", "rotations"):
-        _check_grad(b["grad"][k], a["grad"][k].cpu().numpy(), f"d{k} colour-only P={P}")
+        check_grad(b["grad"][k], a["grad"][k].cpu().numpy(), f"d{k} colour-only P={P}")
 
 
 @pytest.mark.parametrize("P, W, H", [(4000, 256, 256), (200000, 1920, 1080)])
 def test_maps_equal_the_colour_blend_of_z(P, W, H):
-    cam, g = _scene(P, W, H, seed=31)
-    z, _ = _view_z(cam, g["means3D"])
-    out = _run(_settings(cam), g)
-    blend = _run(_settings(cam, bg=(0.0, 0.0, 0.0)), g, return_aux=False, colors=_aux_colors(z))["color"]
+    cam, g = scene(P, W, H, seed=31)
+    z, _ = view_z(cam, g["means3D"])
+    out = _run(settings(cam), g)
+    blend = _run(settings(cam, bg=(0.0, 0.0, 0.0)), g, return_aux=False, colors=aux_colors(z))["color"]
     for i, k in enumerate(MAPS):
         ref = blend[i:i + 1]
         scale = max(float(ref.abs().max()), 1e-12)
@@ -307,11 +230,6 @@ def test_maps_equal_the_colour_blend_of_z(P, W, H):
 
 
 # ---- render() -----------------------------------------------------------------------------------------------------------
-def _model(N=20000, W=320, H=180):
-    from contextgs_amd.synth import SynthPipe, make_scene, orbit_cameras
-    pc = make_scene(N, seed=0)
-    cams = [c.to_torch("cuda") for c in orbit_cameras(4, W, H)]
-    return pc, cams, SynthPipe(), torch.zeros(3, device="cuda")
 
 
 def _render(pc, cam, pipe, bg, **kw):
@@ -325,7 +243,7 @@ def _render(pc, cam, pipe, bg, **kw):
 
 @pytest.mark.parametrize("training", [False, True])
 def test_render_returns_the_maps(training):
-    pc, cams, pipe, bg = _model()
+    pc, cams, pipe, bg = model()
     pc.train(training)
     ctx = torch.enable_grad() if training else torch.no_grad()
     with ctx:

@@ -12,30 +12,12 @@ import ctypes as C
 
 import pytest
 
+from raster_backward_entries import ENTRIES, MAPS
+
 CGS_OK, CGS_ERR_ARG, CGS_ERR_WORKSPACE = 0, 1, 3
 P1 = 4096       # a non-NULL stand-in: the checks only look at which pointers are given
 BIG = 1 << 40
 
-COMMON = ["cfg", "P", "R", "means3D", "colors", "shs", "sh_degree", "sh_coeffs", "opacities", "scales", "rotations", "cov3D",
-          "radii", "geom_ws", "geom_bytes", "bin_ws", "bin_bytes", "img_ws", "img_bytes", "dL_dout"]
-MAPS = ["dL_ddepth", "dL_dinvdepth", "dL_dalpha"]
-GRADS = ["dL_dmeans3D", "dL_dmeans2D", "dL_dcolors", "dL_dopacities", "dL_dshs", "dL_dscales", "dL_drotations", "dL_dcov3D"]
-TAIL = ["scratch", "scratch_bytes", "stream"]
-FEAT = ["features", "C", "dL_dfeatures_map", "dL_dfeatures"]
-NO_FORMS = ("shs", "sh_degree", "sh_coeffs", "cov3D", "dL_dshs", "dL_dcov3D")
-ENTRIES = {     # name -> (argument names in order, the size query of its scratch, the query of the next smaller layout)
-    "cgs_raster_backward": ([a for a in COMMON + GRADS + TAIL if a not in NO_FORMS], "cgs_raster_bwd_scratch_bytes", None),
-    "cgs_raster_backward_ex": (COMMON + GRADS + TAIL, "cgs_raster_bwd_scratch_bytes", None),
-    "cgs_raster_backward_aux": (COMMON + MAPS + GRADS + TAIL, "cgs_raster_bwd_aux_scratch_bytes", "cgs_raster_bwd_scratch_bytes"),
-    "cgs_raster_backward_opt": (COMMON + MAPS + GRADS + TAIL + ["opts"], "cgs_raster_bwd_aux_scratch_bytes",
-                                "cgs_raster_bwd_scratch_bytes"),
-    "cgs_raster_backward_feat": (COMMON + MAPS + GRADS + TAIL + ["opts"] + FEAT, "cgs_raster_bwd_aux_scratch_bytes",
-                                 "cgs_raster_bwd_scratch_bytes"),
-    "cgs_raster_backward_abs": (COMMON + MAPS + GRADS + TAIL + ["opts"] + FEAT, "cgs_raster_bwd_abs_scratch_bytes",
-                                "cgs_raster_bwd_aux_scratch_bytes"),
-    "cgs_raster_backward_det": (COMMON + MAPS + GRADS + TAIL + ["opts", "means2D_cols", "det_ws", "det_bytes"],
-                                "cgs_raster_bwd_abs_scratch_bytes", "cgs_raster_bwd_aux_scratch_bytes"),
-}
 # one Gaussian, no pair, colours + scales / rotations, every pointer the form needs given
 BASE = dict(P=1, R=0, means3D=P1, colors=P1, shs=None, sh_degree=0, sh_coeffs=0, opacities=P1, scales=P1, rotations=P1, cov3D=None,
             radii=P1, geom_ws=P1, geom_bytes=BIG, bin_ws=None, bin_bytes=0, img_ws=P1, img_bytes=BIG, dL_dout=P1, dL_ddepth=None,

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera
-from test_raster_backward_checks import ENTRIES, MAPS
+from raster_backward_entries import ENTRIES, MAPS
 
 pytestmark = pytest.mark.gpu
 

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera
+from raster_harness import fake_cfg
 
 CGS_ERR_ARG = 1
 CGS_RASTER_ANTIALIAS = 1
@@ -15,19 +16,12 @@ P1 = C.c_void_p(4096)      # a non-NULL stand-in: the checks only look at which 
 BIG = 1 << 40
 
 
-def _cfg(campos=True):
-    from contextgs_amd import _lib
-    fake = C.c_void_p(256)     # never dereferenced: every call below fails its argument checks first
-    return _lib.RasterCfg(image_height=16, image_width=16, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
-                          debug=0, viewmatrix=fake, projmatrix=fake, campos=fake if campos else None, bg=fake)
-
-
 def _camera(opts=0, P=1, means3D=P1, shs=None, D=0, M=0, opac=None, scales=P1, rotations=P1, cov3D=None, radii=P1, scratch=P1,
             scratch_bytes=BIG, d_colors=None, d_opac=None, d_view=P1, d_proj=P1, d_campos=None, work=P1, work_bytes=BIG, cfg=None):
     from contextgs_amd import _lib
     L = _lib.lib()
-    rc = L.cgs_raster_camera_backward(C.byref(cfg or _cfg()), P, means3D, shs, D, M, opac, scales, rotations, cov3D, radii, scratch,
-                                      scratch_bytes, d_colors, d_opac, opts, d_view, d_proj, d_campos, work, work_bytes, None)
+    rc = L.cgs_raster_camera_backward(C.byref(cfg or fake_cfg()), P, means3D, shs, D, M, opac, scales, rotations, cov3D, radii,
+                                      scratch, scratch_bytes, d_colors, d_opac, opts, d_view, d_proj, d_campos, work, work_bytes, None)
     return rc, L.cgs_last_error().decode()
 
 
@@ -70,7 +64,7 @@ def test_unknown_option_bits_are_refused(opts):
 def test_argument_errors(kw, needle):
     kw = dict(kw)
     if kw.get("cfg") == "nocampos":
-        kw["cfg"] = _cfg(campos=False)
+        kw["cfg"] = fake_cfg(campos=False)
     rc, msg = _camera(**kw)
     assert rc == CGS_ERR_ARG and needle in msg, msg
     assert "cgs_raster_camera_backward" in msg

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera, random_gaussians
+from raster_harness import settings, sh_eval_torch, shs
 
 pytestmark = pytest.mark.gpu
 
@@ -73,17 +74,7 @@ def oracle_camera_fd(oracle, cam, g, w, eps):
     return out
 
 
-def _settings(cam, D=1, aa=False, view=None, proj=None, campos=None, bg=BG):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    c = cam.to_torch("cuda")
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.tensor(bg, dtype=torch.float32, device="cuda"), scale_modifier=1.0,
-        viewmatrix=c.world_view_transform if view is None else view, projmatrix=c.full_proj_transform if proj is None else proj,
-        sh_degree=D, campos=c.camera_center if campos is None else campos, prefiltered=False, debug=False, antialiasing=aa)
-
-
-def _leaf(a):
+def _leaf32(a):
     return torch.tensor(np.asarray(a, dtype=np.float32), device="cuda", requires_grad=True)
 
 
@@ -107,11 +98,11 @@ def test_every_entry_against_fp64_finite_differences(oracle64, name):
     _, res = oracle_loss(oracle64, cam, g, w, grads=True)
     c = cam.to_torch("cuda")
     V, PM = c.world_view_transform.clone().requires_grad_(True), c.full_proj_transform.clone().requires_grad_(True)
-    m3 = _leaf(g["means3D"])
+    m3 = _leaf32(g["means3D"])
     P = m3.shape[0]
-    color, radii = GaussianRasterizer(_settings(cam, view=V, proj=PM))(
-        means3D=m3, means2D=torch.zeros(P, 3, device="cuda", requires_grad=True), colors_precomp=_leaf(g["colors"]),
-        opacities=_leaf(g["opacities"]), scales=_leaf(g["scales"]), rotations=_leaf(g["rotations"]))
+    color, radii = GaussianRasterizer(settings(cam, bg=BG, view=V, proj=PM))(
+        means3D=m3, means2D=torch.zeros(P, 3, device="cuda", requires_grad=True), colors_precomp=_leaf32(g["colors"]),
+        opacities=_leaf32(g["opacities"]), scales=_leaf32(g["scales"]), rotations=_leaf32(g["rotations"]))
     (color * _const(w)).sum().backward()
     assert V.grad is not None and PM.grad is not None, "the camera tensors got no gradient"
     assert V.grad.shape == (4, 4) and PM.grad.shape == (4, 4)
@@ -212,7 +203,7 @@ def _identity_sides(cam, g, form, aa, loss, wc, wm):
                 dq = torch.cat([torch.ones(1, device="cuda"), 0.5 * theta[:3]])
                 dq = dq / dq.norm()
                 geo = dict(scales=s * torch.exp(theta[3]), rotations=_quat_mul(dq.expand(P, 4), q))
-        rs = _settings(cam, D=0, aa=aa, view=V, proj=PM)
+        rs = settings(cam, bg=BG, D=0, aa=aa, view=V, proj=PM)
         out, radii, aux = GaussianRasterizer(rs)(means3D=means, means2D=torch.zeros(P, 3, device="cuda"), opacities=op,
                                                  return_aux=True, **col, **geo)
         _loss(out, aux, wc, wm, loss).backward()
@@ -246,9 +237,8 @@ def test_identity_camera_side_equals_world_side(form, loss, aa):
 
 # ---- campos ----------------------------------------------------------------------------------------------------------------
 def _sh_scene(D, M, P=120_000, W=640, H=360):
-    from test_raster_sh_cov_gpu import _shs
     cam, g = _big_scene(P, W, H, seed=22)
-    return cam, g, _shs(P, M, 22)
+    return cam, g, shs(P, M, 22)
 
 
 @pytest.mark.parametrize("cov_form", [False, True])
@@ -258,7 +248,6 @@ def test_campos_against_torch_sh(D, M, cov_form):
     compares with, feeding colors_precomp; and dL/dcampos == -sum_i of the SH direction's share of dL/dmeans3D (the difference
     between dL/dmeans3D of the shs call and of the colors_precomp call with the same colours)."""
     from contextgs_amd.rasterizer import GaussianRasterizer
-    from test_raster_sh_cov_gpu import sh_eval_torch
     cam, g, sh = _sh_scene(D, M)
     P = sh.shape[0]
     s, q = _const(g["scales"]), _const(g["rotations"])
@@ -267,15 +256,15 @@ def test_campos_against_torch_sh(D, M, cov_form):
     c0 = cam.to_torch("cuda").camera_center
     zeros = lambda: torch.zeros(P, 3, device="cuda")
 
-    ca, ma, sha = c0.clone().requires_grad_(True), _leaf(g["means3D"]), _const(sh)
-    out, _ = GaussianRasterizer(_settings(cam, D=D, campos=ca))(means3D=ma, means2D=zeros(), shs=sha,
+    ca, ma, sha = c0.clone().requires_grad_(True), _leaf32(g["means3D"]), _const(sh)
+    out, _ = GaussianRasterizer(settings(cam, bg=BG, D=D, campos=ca))(means3D=ma, means2D=zeros(), shs=sha,
                                                                opacities=_const(g["opacities"]), **geo)
     (out * w).sum().backward()
     assert ca.grad is not None and ca.grad.shape == (3,)
 
-    cb, mb = c0.clone().requires_grad_(True), _leaf(g["means3D"])
+    cb, mb = c0.clone().requires_grad_(True), _leaf32(g["means3D"])
     colors = sh_eval_torch(sha, mb.detach(), cb, D)
-    out_b, _ = GaussianRasterizer(_settings(cam, D=D))(means3D=mb, means2D=zeros(), colors_precomp=colors,
+    out_b, _ = GaussianRasterizer(settings(cam, bg=BG, D=D))(means3D=mb, means2D=zeros(), colors_precomp=colors,
                                                        opacities=_const(g["opacities"]), **geo)
     (out_b * w).sum().backward()
     e_torch = _rel(ca.grad, cb.grad)
@@ -291,14 +280,14 @@ def test_campos_without_shs_and_degree_zero():
     from contextgs_amd.rasterizer import GaussianRasterizer
     cam, g, sh = _sh_scene(0, 1, P=5000, W=128, H=96)
     P = sh.shape[0]
-    kw = dict(means3D=_leaf(g["means3D"]), opacities=_const(g["opacities"]), scales=_const(g["scales"]),
+    kw = dict(means3D=_leaf32(g["means3D"]), opacities=_const(g["opacities"]), scales=_const(g["scales"]),
               rotations=_const(g["rotations"]))
     c = cam.to_torch("cuda").camera_center.clone().requires_grad_(True)
-    out, _ = GaussianRasterizer(_settings(cam, D=0, campos=c))(means2D=torch.zeros(P, 3, device="cuda"), shs=_const(sh), **kw)
+    out, _ = GaussianRasterizer(settings(cam, bg=BG, D=0, campos=c))(means2D=torch.zeros(P, 3, device="cuda"), shs=_const(sh), **kw)
     out.sum().backward()
     assert c.grad is not None and c.grad.shape == (3,) and not c.grad.any()      # degree 0 has no direction
     c2 = cam.to_torch("cuda").camera_center.clone().requires_grad_(True)
-    out, _ = GaussianRasterizer(_settings(cam, campos=c2))(means2D=torch.zeros(P, 3, device="cuda"),
+    out, _ = GaussianRasterizer(settings(cam, bg=BG, campos=c2))(means2D=torch.zeros(P, 3, device="cuda"),
                                                            colors_precomp=_const(g["colors"]), **kw)
     out.sum().backward()
     assert c2.grad is None                                                     # unused without shs
@@ -307,10 +296,10 @@ def test_campos_without_shs_and_degree_zero():
 # ---- structure ---------------------------------------------------------------------------------------------------------------
 def _plain_call(cam, g, w, view=None, proj=None, campos=None, aux=False, aa=False):
     from contextgs_amd.rasterizer import GaussianRasterizer
-    leaves = {k: _leaf(g[k]) for k in ("means3D", "colors", "opacities", "scales", "rotations")}
+    leaves = {k: _leaf32(g[k]) for k in ("means3D", "colors", "opacities", "scales", "rotations")}
     P = leaves["means3D"].shape[0]
     m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
-    res = GaussianRasterizer(_settings(cam, view=view, proj=proj, campos=campos, aa=aa))(
+    res = GaussianRasterizer(settings(cam, bg=BG, view=view, proj=proj, campos=campos, aa=aa))(
         means3D=leaves["means3D"], means2D=m2, colors_precomp=leaves["colors"], opacities=leaves["opacities"],
         scales=leaves["scales"], rotations=leaves["rotations"], return_aux=aux)
     (res[0] * w).sum().backward()
@@ -392,7 +381,7 @@ def test_degenerate_views_give_zero_gradients_of_the_right_shape(case):
     cp = c.camera_center.clone().requires_grad_(True)
     P = g["means3D"].shape[0]
     sh = torch.zeros(P, 4, 3, device="cuda")
-    out, radii = GaussianRasterizer(_settings(cam, view=V, proj=PM, campos=cp))(
+    out, radii = GaussianRasterizer(settings(cam, bg=BG, view=V, proj=PM, campos=cp))(
         means3D=_const(g["means3D"]).reshape(P, 3), means2D=torch.zeros(P, 3, device="cuda"), shs=sh,
         opacities=_const(g["opacities"]).reshape(P, 1), scales=_const(g["scales"]).reshape(P, 3),
         rotations=_const(g["rotations"]).reshape(P, 4))
@@ -413,7 +402,7 @@ def test_c_entry_point_is_bit_reproducible_on_a_frozen_scratch():
     cam, g = _big_scene(60_000, 640, 360)
     L = _lib.lib()
     c = cam.to_torch("cuda")
-    rs = _settings(cam)
+    rs = settings(cam, bg=BG)
     cfg = rasterizer._Cfg(rs)
     m, col, op, s, q = (_const(g[k]) for k in ("means3D", "colors", "opacities", "scales", "rotations"))
     P = m.shape[0]

@@ -11,23 +11,18 @@ import types
 import pytest
 import torch
 
+from raster_harness import fake_cfg
+
 CGS_ERR_ARG = 1
 CGS_ERR_WORKSPACE = 3
 
 P1 = C.c_void_p(4096)      # a non-NULL stand-in: the checks only look at which pointers are given
 
 
-def _cfg(H=16, W=16):
-    from contextgs_amd import _lib
-    fake = C.c_void_p(256)     # never dereferenced: every call below fails its argument checks first
-    return _lib.RasterCfg(image_height=H, image_width=W, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
-                          debug=0, viewmatrix=fake, projmatrix=fake, campos=fake, bg=fake)
-
-
 def _contrib(P=1, R=1, geom=P1, bin_ws=P1, img=P1, img_bytes=1 << 30, slot=None, n_slots=None, accs=(P1,) * 4, maps=(P1,) * 3):
     from contextgs_amd import _lib
     L = _lib.lib()
-    rc = L.cgs_raster_contrib(C.byref(_cfg()), P, R, geom, 1 << 30, bin_ws, 1 << 30, img, img_bytes, slot,
+    rc = L.cgs_raster_contrib(C.byref(fake_cfg()), P, R, geom, 1 << 30, bin_ws, 1 << 30, img, img_bytes, slot,
                               P if n_slots is None else n_slots, *accs, *maps, None)
     return rc, L.cgs_last_error().decode()
 

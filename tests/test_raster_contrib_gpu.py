@@ -6,9 +6,9 @@ Gaussian i, so a loop over all pixels of a tiny image gives the whole matrix w[i
 counts (w > 0), the per-pixel argmax and the top counts follow from it in numpy.  One call with dL_dout = ones gives
 sum_p w_i(p) for a scene of any size.
 
-Tolerances.  `weight` and `max_weight`: `_check_grad` of tests/test_raster_features_gpu.py (a copy): at most a 2e-3 share of
-entries beyond 2e-4 of the tensor's maximum.  `top_weight`: `_check_map` (a copy): RMSE <= 1e-5 of the map's maximum and at most
-a 1e-4 share of values beyond 2e-5.  `pixels`, `top_pixels`, `count` and `top_id` are discrete, and a pair whose alpha sits at
+Tolerances.  `weight` and `max_weight`: `check_grad` of tests/raster_harness.py: at most a 2e-3 share of entries beyond 2e-4
+of the tensor's maximum.  `top_weight`: `check_map`: RMSE <= 1e-5 of the map's maximum and at most a 1e-4 share of values
+beyond 2e-5.  `pixels`, `top_pixels`, `count` and `top_id` are discrete, and a pair whose alpha sits at
 1/255 or whose two largest weights nearly tie may fall either way in fp32, so: sum_i |pixels - ref| <= 1e-3 sum_i ref, the same
 for top_pixels; count equal on >= 99.8 % of the pixels and never off by more than 2; top_id equal on every pixel whose two
 largest reference weights differ by more than 1e-4 relative (and on every pixel without a contributor), and at most 1 % of the
@@ -19,56 +19,19 @@ another cap.  Sums that float atomics build in an unspecified order are compared
 non-negative fp32 addends, n 2^-24 relative, n counted from the call (`_sum_tol`).
 References are computed once per scene and shared; nobody writes into them.
 """
-import functools
 import itertools
-import math
 
 import numpy as np
 import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera, random_gaussians
+from raster_harness import (check_grad, check_map, cov6_torch, leaf, memo, model, named_scene, np_of, run, scene, settings,
+                            sh_eval_torch, shs)
 
 pytestmark = pytest.mark.gpu
 
-BG = (0.1, 0.25, 0.4)
 FIELDS = ("weight", "max_weight", "pixels", "top_pixels")
-
-
-# ---- scenes (constructions of tests/test_raster_features_gpu.py) -------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _scene(P, W, H, seed, extent=1.0, srange=(0.005, 0.05), eye=(0.4, -2.2, 0.6)):
-    cam = look_at_camera(eye, (0, 0, 0), W, H, fovx_deg=60.0)
-    g = random_gaussians(P, seed=seed, extent=extent, scale_lo=srange[0], scale_hi=srange[1])
-    if P >= 20:     # some Gaussians behind the near plane
-        e = np.array([0.4, -2.2, 0.6], dtype=np.float32)
-        g["means3D"][::20] = e + 0.3 * (e - g["means3D"][::20])
-    return cam, g
-
-
-@functools.lru_cache(maxsize=None)
-def _stack_scene(kind, W=16, H=16):
-    """saturated: 300 nearly opaque, wide Gaussians.  long: 700 faint, wide ones.  Both in front of a one-tile image."""
-    cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), W, H, fovx_deg=50.0)
-    if kind == "saturated":
-        rng = np.random.default_rng(11)
-        g = random_gaussians(300, seed=11, extent=0.2, scale_lo=0.15, scale_hi=0.4)
-        g["opacities"][:] = rng.uniform(0.9, 0.999, size=g["opacities"].shape).astype(np.float32)
-    else:
-        rng = np.random.default_rng(12)
-        g = random_gaussians(700, seed=12, extent=0.2, scale_lo=0.15, scale_hi=0.4)
-        g["opacities"][:] = rng.uniform(0.005, 0.02, size=g["opacities"].shape).astype(np.float32)
-    return cam, g
-
-
-def decomposed_scene(name):
-    if name == "ragged":        # 3 x 2 tiles, ragged right and bottom, some Gaussians behind the near plane
-        return _scene(200, 40, 24, 3, 1.0, (0.02, 0.12))
-    if name == "single":
-        return _scene(1, 64, 48, 1)
-    return _stack_scene(name)
-
-
 DECOMPOSED = ("ragged", "long", "saturated", "single")
 
 
@@ -104,99 +67,31 @@ def stats_of(w, H, W):
             "w1": w1, "w2": w2}
 
 
-_REFS = {}
-
-
-def _ref(key, make):
-    """References are computed once and shared; nobody writes into them."""
-    if key not in _REFS:
-        _REFS[key] = make()
-    return _REFS[key]
-
-
-def _np(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def _check_map(a, b, what, cap=1.0):
-    a = _np(a).astype(np.float32).reshape(-1)
-    b = np.asarray(b, dtype=np.float32).reshape(-1)
-    scale = max(float(np.abs(b).max()), 1e-12)
-    d = np.abs(a - b) / scale
-    rmse = float(np.sqrt((d ** 2).mean()))
-    n_out = int((d > 2e-5).sum())
-    print(f"[allowance] {what}: rmse {rmse:.2e}, {n_out} of {d.size} values beyond 2e-5 of the max {scale:.3g}, worst {d.max():.2e}")
-    assert rmse <= 1e-5 * cap, (what, rmse)
-    assert n_out <= 1e-4 * cap * d.size, (what, n_out, float(d.max()))
-
-
-def _check_grad(a, b, what, allow_frac=2e-3, tol=2e-4):
-    a = _np(a).astype(np.float32)
-    a = a.reshape(a.shape[0], -1)
-    b = np.asarray(b, dtype=np.float32).reshape(a.shape)
-    scale = max(1e-6, float(np.abs(b).max()))
-    err = np.abs(a - b) / scale
-    n_out = int((err > tol).sum())
-    print(f"[allowance] {what}: {n_out} of {err.size} entries beyond {tol:g} of the maximum, worst {err.max():.2e}")
-    assert n_out <= allow_frac * err.size, (what, n_out, float(err.max()))
-
-
 def _check_stats(got, ref, what, cap=1.0):
     """`got`: the seven results as arrays; `ref`: stats_of() of the fp64 decomposition.  cap = 0.5: the fp32 oracle's own test."""
-    _check_grad(got["weight"], ref["weight"], f"weight {what}", allow_frac=2e-3 * cap)
-    _check_grad(got["max_weight"], ref["max_weight"], f"max_weight {what}", allow_frac=2e-3 * cap)
-    _check_map(got["top_weight"], ref["top_weight"], f"top_weight {what}", cap=cap)
+    check_grad(got["weight"], ref["weight"], f"weight {what}", allow_frac=2e-3 * cap)
+    check_grad(got["max_weight"], ref["max_weight"], f"max_weight {what}", allow_frac=2e-3 * cap)
+    check_map(got["top_weight"], ref["top_weight"], f"top_weight {what}", cap=cap)
     for k in ("pixels", "top_pixels"):
-        a, b = _np(got[k]).astype(np.int64), ref[k]
+        a, b = np_of(got[k]).astype(np.int64), ref[k]
         off, tot = int(np.abs(a - b).sum()), int(b.sum())
         print(f"[allowance] {k} {what}: sum |got - ref| = {off} of {tot}")
         assert off <= 1e-3 * cap * tot, (k, what, off, tot)
-    a, b = _np(got["count"]).astype(np.int64), ref["count"]
+    a, b = np_of(got["count"]).astype(np.int64), ref["count"]
     diff = np.abs(a - b)
     print(f"[allowance] count {what}: {int((diff != 0).sum())} of {diff.size} pixels differ, worst {int(diff.max())}")
     assert (diff == 0).mean() >= 1 - 2e-3 * cap and diff.max() <= 2, (what, int((diff != 0).sum()), int(diff.max()))
     decided = ((ref["w1"] - ref["w2"]) > 1e-4 * ref["w1"]) | (ref["w1"] == 0)
     print(f"[allowance] top_id {what}: {int((~decided).sum())} of {decided.size} pixels are near ties")
     assert (~decided).mean() <= 1e-2 * cap, (what, int((~decided).sum()))
-    a, b = _np(got["top_id"]).reshape(-1), ref["top_id"].reshape(-1)
+    a, b = np_of(got["top_id"]).reshape(-1), ref["top_id"].reshape(-1)
     assert (a[decided] == b[decided]).all(), (what, int((a[decided] != b[decided]).sum()))
 
 
 # ---- running the rasterizer --------------------------------------------------------------------------------------------------
-def _settings(cam, bg=BG, D=1, debug=False, aa=False):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    c = cam.to_torch("cuda")
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.tensor(bg, dtype=torch.float32, device="cuda"), scale_modifier=1.0,
-        viewmatrix=c.world_view_transform, projmatrix=c.full_proj_transform, sh_degree=D, campos=c.camera_center,
-        prefiltered=False, debug=debug, antialiasing=aa)
-
-
-def _leaf(a):
-    return torch.tensor(a, device="cuda", requires_grad=True)
-
-
-def _run(rs, g, contrib=None, slots=None, F=None, return_aux=False, loss_w=None):
-    """Forward (and backward of sum(out * w) over the entries of loss_w)."""
-    from contextgs_amd.rasterizer import GaussianRasterizer
-    P = g["means3D"].shape[0]
-    t = {k: _leaf(v) for k, v in g.items()}
-    if F is not None:
-        t["features"] = _leaf(F)
-    m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
-    res = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"],
-                                 scales=t["scales"], rotations=t["rotations"], features=t.get("features"), return_aux=return_aux,
-                                 contrib=contrib, contrib_slots=slots)
-    out = {"color": res[0], "radii": res[1]}
-    if len(res) > 2:
-        out.update(res[2])
-    if loss_w:
-        sum(((out[k] * torch.as_tensor(w, device="cuda")).sum() for k, w in loss_w.items())).backward()
-    torch.cuda.synchronize()
-    o = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in out.items()}
-    o["grad"] = {k: (None if v.grad is None else v.grad.detach()) for k, v in t.items()}
-    o["grad"]["means2D"] = m2.grad
+def _run(rs, g, contrib=None, slots=None, F=None, **kw):
+    """raster_harness.run with the accumulators' four fields next to the maps."""
+    o = run(rs, g, features=F, contrib=contrib, contrib_slots=slots, **kw)
     if "contrib" in o:
         o.update({k: getattr(o["contrib"], k) for k in FIELDS})
     return o
@@ -230,10 +125,10 @@ def _tiles(cam):
 # ---- the decomposed scenes ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", DECOMPOSED)
 def test_matches_the_fp64_decomposition(oracle64, name):
-    cam, g = decomposed_scene(name)
+    cam, g = named_scene(name)
     P, H, W = g["means3D"].shape[0], cam.image_height, cam.image_width
-    dec = _ref(("dec", name), lambda: decompose(oracle64, cam, g))
-    ref = _ref(("stats", name), lambda: stats_of(dec["w"], H, W))
+    dec = memo(("contrib", "dec", name), lambda: decompose(oracle64, cam, g))
+    ref = memo(("contrib", "stats", name), lambda: stats_of(dec["w"], H, W))
     if name == "long":
         assert int(dec["stats"][0]) / _tiles(cam) > 512        # more than two 256-entry batches in the tile
         assert int(dec["stats"][1]) / _tiles(cam) > 256        # and the walk goes beyond the first
@@ -241,7 +136,7 @@ def test_matches_the_fp64_decomposition(oracle64, name):
         assert float(dec["final_T"].min()) < 1e-3              # pixels stop early: later entries must count nothing
     if name == "single":
         assert int(ref["pixels"][0]) > 0
-    rs = _settings(cam, debug=(name == "single"))
+    rs = settings(cam, debug=(name == "single"))
     out = _run(rs, g, contrib=True)
     plain = _run(rs, g)
     assert torch.equal(out["color"], plain["color"]) and torch.equal(out["radii"], plain["radii"])
@@ -256,7 +151,7 @@ LARGE = (4000, 256, 256, 4000)
 
 
 def _large_ref(oracle64):
-    cam, g = _scene(*LARGE)
+    cam, g = scene(*LARGE)
     P, H, W = g["means3D"].shape[0], cam.image_height, cam.image_width
 
     def make():
@@ -264,20 +159,20 @@ def _large_ref(oracle64):
         d[0] = 1.0
         return oracle64.render(cam.oracle_dict(bg=(0.0, 0.0, 0.0)), g["means3D"], np.ones((P, 3), np.float32), g["opacities"],
                                g["scales"], g["rotations"], dL_dout=d)["dL_dcolors"][:, 0].copy()
-    return _ref(("large",), make)
+    return memo(("contrib", "large",), make)
 
 
 def test_larger_scene(oracle64):
-    cam, g = _scene(*LARGE)
+    cam, g = scene(*LARGE)
     P, H, W = g["means3D"].shape[0], cam.image_height, cam.image_width
-    rs = _settings(cam)
+    rs = settings(cam)
     out = _run(rs, g, contrib=True, return_aux=True)
     plain = _run(rs, g)
     assert torch.equal(out["color"], plain["color"]) and torch.equal(out["radii"], plain["radii"])
     _check_shapes(out, P, H, W)
-    _check_grad(out["weight"], _large_ref(oracle64), "weight vs the fp64 oracle's dL_dcolors[:, 0]")
+    check_grad(out["weight"], _large_ref(oracle64), "weight vs the fp64 oracle's dL_dcolors[:, 0]")
     feat = _run(rs, g, F=np.ones((P, 1), np.float32), loss_w={"features": np.ones((1, H, W), np.float32)})
-    _check_grad(out["weight"], feat["grad"]["features"].cpu().numpy(), "weight vs the gradient of features = ones")
+    check_grad(out["weight"], feat["grad"]["features"].cpu().numpy(), "weight vs the gradient of features = ones")
     total, want = float(out["weight"].double().sum()), float(out["alpha"].double().sum())
     print(f"[contrib] sum of weight {total:.6f} vs sum of the alpha map {want:.6f}")
     assert abs(total - want) <= 1e-4 * want
@@ -295,9 +190,9 @@ def test_larger_scene(oracle64):
 # ---- accumulation ------------------------------------------------------------------------------------------------------------
 def test_two_calls_into_one_accumulator():
     from contextgs_amd.rasterizer import GaussianContrib
-    cam, g = _scene(*LARGE)
+    cam, g = scene(*LARGE)
     P = g["means3D"].shape[0]
-    rs = _settings(cam)
+    rs = settings(cam)
     one = _run(rs, g, contrib=True)
     acc = GaussianContrib.zeros(P, "cuda")
     _run(rs, g, contrib=acc)
@@ -315,14 +210,14 @@ def test_two_calls_into_one_accumulator():
 def test_maximum_over_two_cameras():
     from contextgs_amd.rasterizer import GaussianContrib
     P, W, H, seed = 2000, 128, 96, 7
-    cam_a, g = _scene(P, W, H, seed)
-    cam_b, _ = _scene(P, W, H, seed, eye=(-1.5, -1.8, 0.9))
-    a = _run(_settings(cam_a), g, contrib=True)
-    b = _run(_settings(cam_b), g, contrib=True)
+    cam_a, g = scene(P, W, H, seed)
+    cam_b, _ = scene(P, W, H, seed, eye=(-1.5, -1.8, 0.9))
+    a = _run(settings(cam_a), g, contrib=True)
+    b = _run(settings(cam_b), g, contrib=True)
     assert not torch.equal(a["pixels"], b["pixels"])
     acc = GaussianContrib.zeros(P, "cuda")
-    _run(_settings(cam_a), g, contrib=acc)
-    _run(_settings(cam_b), g, contrib=acc)
+    _run(settings(cam_a), g, contrib=acc)
+    _run(settings(cam_b), g, contrib=acc)
     assert torch.equal(acc.max_weight, torch.maximum(a["max_weight"], b["max_weight"]))
     assert torch.equal(acc.pixels, a["pixels"] + b["pixels"]) and torch.equal(acc.top_pixels, a["top_pixels"] + b["top_pixels"])
     want = a["weight"] + b["weight"]
@@ -332,9 +227,9 @@ def test_maximum_over_two_cameras():
 def test_slot_tables():
     from contextgs_amd import rasterizer
     from contextgs_amd.rasterizer import GaussianContrib
-    cam, g = _scene(*LARGE)
+    cam, g = scene(*LARGE)
     P = g["means3D"].shape[0]
-    rs = _settings(cam)
+    rs = settings(cam)
     one = _run(rs, g, contrib=True)
     pairs = int(rasterizer.last_call["num_rendered"])
     row_tol = _sum_tol(2 * _row_addends(cam))       # one call on either side
@@ -378,11 +273,10 @@ def test_slot_tables():
 @pytest.mark.parametrize("form", ["shs+scales", "shs+cov", "colors+cov"])
 def test_all_forms_match_colors_precomp_scales_rotations(form):
     from contextgs_amd.rasterizer import GaussianRasterizer
-    from test_raster_sh_cov_gpu import _shs, cov6_torch, sh_eval_torch
     P, W, H, D, M = 4000, 256, 256, 2, 9
-    cam, g = _scene(P, W, H, P + 3)
-    sh = _shs(P, M, seed=P)
-    rs = _settings(cam, D=D)
+    cam, g = scene(P, W, H, P + 3)
+    sh = shs(P, M, seed=P)
+    rs = settings(cam, D=D)
     campos = rs.campos.float()
 
     def run(use_shs, use_cov):
@@ -410,10 +304,10 @@ def test_all_forms_match_colors_precomp_scales_rotations(form):
     _check_shapes(new, P, H, W)
     rows = same.cpu().numpy()
     for k in ("weight", "max_weight"):
-        _check_grad(_np(new[k])[rows], _np(ref[k])[rows], f"{k} {form}")
-    _check_map(new["top_weight"], _np(ref["top_weight"]), f"top_weight {form}")
+        check_grad(np_of(new[k])[rows], np_of(ref[k])[rows], f"{k} {form}")
+    check_map(new["top_weight"], np_of(ref["top_weight"]), f"top_weight {form}")
     for k in ("pixels", "top_pixels"):       # the discrete results under the caps of the decomposed scenes
-        a, b = _np(new[k])[rows], _np(ref[k])[rows]
+        a, b = np_of(new[k])[rows], np_of(ref[k])[rows]
         assert int(np.abs(a - b).sum()) <= 1e-3 * int(b.sum()), (k, form)
     diff = (new["count"] - ref["count"]).abs()
     assert float((diff == 0).float().mean()) >= 1 - 2e-3 and int(diff.max()) <= 2
@@ -423,9 +317,9 @@ def test_all_forms_match_colors_precomp_scales_rotations(form):
 # ---- antialiasing ------------------------------------------------------------------------------------------------------------
 def test_antialiasing_reads_the_compensated_opacity():
     P, W, H = 2000, 128, 96
-    cam, g = _scene(P, W, H, 7)
-    aa = _run(_settings(cam, aa=True), g, contrib=True, return_aux=True)
-    no = _run(_settings(cam), g, contrib=True)
+    cam, g = scene(P, W, H, 7)
+    aa = _run(settings(cam, aa=True), g, contrib=True, return_aux=True)
+    no = _run(settings(cam), g, contrib=True)
     assert not torch.equal(aa["weight"], no["weight"]) and not torch.equal(aa["top_weight"], no["top_weight"])
     _check_shapes(aa, P, H, W)
     total, want = float(aa["weight"].double().sum()), float(aa["alpha"].double().sum())
@@ -440,9 +334,9 @@ def test_maps_are_the_same_bits_without_the_accumulators(name):
     reduction) against a maps-only call on the same workspaces (the instance without it; only the C entry point can ask for
     that): bit-identical.  Ragged tiles (40x24), and more than two 256-entry batches in a tile."""
     from contextgs_amd import _lib, rasterizer
-    cam, g = decomposed_scene(name)
+    cam, g = named_scene(name)
     P, H, W = g["means3D"].shape[0], cam.image_height, cam.image_width
-    out = _run(_settings(cam), g, contrib=True)
+    out = _run(settings(cam), g, contrib=True)
     assert int(out["count"].sum()) > 0 and int(out["pixels"].sum()) == int(out["count"].sum())
     lc = dict(rasterizer.last_call)
     geom, binws, img = lc["geom_ws"], lc["bin_ws"], lc["img_ws"]
@@ -463,7 +357,7 @@ def test_maps_are_the_same_bits_without_the_accumulators(name):
 def test_empty_view_and_no_gaussians():
     from contextgs_amd.rasterizer import GaussianContrib
     cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), 80, 64, fovx_deg=50.0)
-    rs = _settings(cam)
+    rs = settings(cam)
     g = random_gaussians(64, seed=6)
     g["means3D"][:, 1] -= 20.0                        # everything behind the camera
     for gg in (g, {k: v[:0] for k, v in g.items()}):
@@ -487,8 +381,8 @@ def test_empty_view_and_no_gaussians():
 def test_after_a_voided_speculative_render():
     from contextgs_amd import rasterizer
     P, W, H = 20000, 320, 240
-    cam, g = _scene(P, W, H, 9)
-    rs = _settings(cam)
+    cam, g = scene(P, W, H, 9)
+    rs = settings(cam)
     rasterizer._pair_capacity[(H, W)] = 1 << 10       # far below the view's pair count: the speculative render is voided
     out = _run(rs, g, contrib=True)
     assert rasterizer.last_call["num_rendered"] > (1 << 10)
@@ -508,8 +402,8 @@ def test_backward_with_contrib():
     bit-reproducible by construction; bit-equality is asserted for every gradient that two plain calls reproduce bit for bit,
     and all of them stay within `_check_grad`."""
     P, W, H = 3000, 256, 256
-    cam, g = _scene(P, W, H, 1, 1.0, (0.003, 0.04))
-    rs = _settings(cam)
+    cam, g = scene(P, W, H, 1, 1.0, (0.003, 0.04))
+    rs = settings(cam)
     gC = np.random.default_rng(18).normal(size=(3, H, W)).astype(np.float32)
     a = _run(rs, g, contrib=True, loss_w={"color": gC})
     b = _run(rs, g, loss_w={"color": gC})
@@ -522,32 +416,32 @@ def test_backward_with_contrib():
         print(f"[contrib] d{k}: two plain calls bit-equal: {fixed}; with contrib bit-equal: {torch.equal(a['grad'][k], b['grad'][k])}")
         if fixed:
             assert torch.equal(a["grad"][k], b["grad"][k]), k
-        _check_grad(a["grad"][k], b["grad"][k].cpu().numpy(), f"d{k} with contrib vs without")
+        check_grad(a["grad"][k], b["grad"][k].cpu().numpy(), f"d{k} with contrib vs without")
     # and with the maps and the features in the same call
     F = np.ones((P, 1), np.float32)
     c = _run(rs, g, contrib=True, F=F, return_aux=True, loss_w={"color": gC, "features": np.ones((1, H, W), np.float32)})
     for k in ("top_id", "count", "pixels", "max_weight"):
         assert torch.equal(c[k], a[k]), k
     assert c["features"].shape == (1, H, W) and c["depth"].shape == (1, H, W)
-    _check_grad(a["weight"], c["grad"]["features"].cpu().numpy(), "weight vs dL/dfeatures of the same call")
+    check_grad(a["weight"], c["grad"]["features"].cpu().numpy(), "weight vs dL/dfeatures of the same call")
 
 
 def _raw_call(g, **kw):
     """The node's raw outputs (nothing detached) of a call whose inputs all require a gradient."""
     from contextgs_amd.rasterizer import GaussianRasterizer
-    cam, _ = _scene(2000, 128, 96, 7)
+    cam, _ = scene(2000, 128, 96, 7)
     P = g["means3D"].shape[0]
-    t = {k: _leaf(v) for k, v in g.items()}
+    t = {k: leaf(v) for k, v in g.items()}
     m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
-    return GaussianRasterizer(_settings(cam))(means3D=t["means3D"], means2D=m2, opacities=t["opacities"],
+    return GaussianRasterizer(settings(cam))(means3D=t["means3D"], means2D=m2, opacities=t["opacities"],
                                               colors_precomp=t["colors"], scales=t["scales"], rotations=t["rotations"], **kw)
 
 
 @pytest.mark.parametrize("return_aux, with_features", [(False, False), (True, False), (False, True), (True, True)])
 def test_outputs_are_marked_non_differentiable(return_aux, with_features):
-    _, g = _scene(2000, 128, 96, 7)
+    _, g = scene(2000, 128, 96, 7)
     P = g["means3D"].shape[0]
-    kw = dict(features=_leaf(np.ones((P, 2), np.float32))) if with_features else {}
+    kw = dict(features=leaf(np.ones((P, 2), np.float32))) if with_features else {}
     color, radii, ex = _raw_call(g, contrib=True, return_aux=return_aux, **kw)
     assert color.requires_grad and color.grad_fn is not None
     for k in ("top_id", "top_weight", "count"):
@@ -561,7 +455,7 @@ def test_outputs_are_marked_non_differentiable(return_aux, with_features):
 
 
 def test_the_backward_saves_nothing_new():
-    _, g = _scene(2000, 128, 96, 7)
+    _, g = scene(2000, 128, 96, 7)
     plain = _raw_call(g)
     color, _, ex = _raw_call(g, contrib=True)
     saved_plain, saved = plain[0].grad_fn.saved_tensors, color.grad_fn.saved_tensors
@@ -577,13 +471,6 @@ def test_the_backward_saves_nothing_new():
 
 
 # ---- render() ----------------------------------------------------------------------------------------------------------------
-def _model(N=20000, W=320, H=180):
-    from contextgs_amd.synth import SynthPipe, make_scene, orbit_cameras
-    pc = make_scene(N, seed=0)
-    cams = [c.to_torch("cuda") for c in orbit_cameras(4, W, H)]
-    return pc, cams, SynthPipe(), torch.zeros(3, device="cuda")
-
-
 def _render(pc, cam, pipe, bg, **kw):
     from contextgs_amd import ctx_ops
     from contextgs_amd.renderer import prefilter_voxel, render
@@ -597,7 +484,7 @@ def _render(pc, cam, pipe, bg, **kw):
 def test_render_accumulates_per_anchor_and_offset(training):
     from contextgs_amd.densify import anchor_importance
     from contextgs_amd.rasterizer import GaussianContrib
-    pc, cams, pipe, bg = _model()
+    pc, cams, pipe, bg = model()
     pc.train(training)
     N, K = pc.get_anchor.shape[0], pc.n_offsets
     with (torch.enable_grad() if training else torch.no_grad()):

@@ -7,6 +7,8 @@ import inspect
 import pytest
 import torch
 
+from raster_harness import fake_cfg
+
 CGS_OK = 0
 CGS_ERR_ARG = 1
 CGS_ERR_WORKSPACE = 3
@@ -15,19 +17,12 @@ NEW_SYMBOLS = ("cgs_raster_backward_det", "cgs_raster_bwd_det_bytes")
 P1 = C.c_void_p(4096)      # a non-NULL stand-in: the checks only look at which pointers are given
 
 
-def _cfg(H=16, W=16):
-    from contextgs_amd import _lib
-    fake = C.c_void_p(256)     # never dereferenced: every call below fails its argument checks first
-    return _lib.RasterCfg(image_height=H, image_width=W, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
-                          debug=0, viewmatrix=fake, projmatrix=fake, campos=fake, bg=fake)
-
-
 def _backward_det(P=1, R=0, geom=P1, img=P1, scratch=P1, scratch_bytes=1 << 40, d_depth=None, d_invdepth=None, d_alpha=None,
                   opts=0, cols=3, det_ws=P1, det_bytes=1 << 40):
     """colours + scales / rotations, every other pointer given"""
     from contextgs_amd import _lib
     L = _lib.lib()
-    rc = L.cgs_raster_backward_det(C.byref(_cfg()), P, R, P1, P1, None, 0, 0, P1, P1, P1, None, P1, geom, 1 << 30,
+    rc = L.cgs_raster_backward_det(C.byref(fake_cfg()), P, R, P1, P1, None, 0, 0, P1, P1, P1, None, P1, geom, 1 << 30,
                                    P1 if R else None, 1 << 40 if R else 0, img, 1 << 30, None, d_depth, d_invdepth, d_alpha,
                                    P1, P1, P1, P1, None, P1, P1, None, scratch, scratch_bytes, None, opts, cols, det_ws, det_bytes)
     return rc, L.cgs_last_error().decode()

@@ -3,14 +3,13 @@ csrc/raster_blend_rows.hip and det_sum_kernel).
 
 Two kinds of assertion.  Equality: gradients of two runs on the same input bits are torch.equal, whatever varied between them
 (fresh leaves and workspaces, the binning, a speculative pair capacity, the fused or the unfused node).  Values: the flag's
-gradients against the UNCHANGED fp32 oracle and against the default (float-atomic) path, with `_check_grad` of
-tests/test_raster_features_gpu.py (at most a 2e-3 share of entries beyond 2e-4 of the tensor's maximum; on the CPU, on all five
+gradients against the UNCHANGED fp32 oracle and against the default (float-atomic) path, with `check_grad` of
+tests/raster_harness.py (at most a 2e-3 share of entries beyond 2e-4 of the tensor's maximum; on the CPU, on all five
 scenes, the fp32 oracle against the fp64 oracle leaves no entry of any of the six gradient tensors beyond it, worst 1.3e-5).
 
-Scenes: the constructions of tests/test_raster_absgrad_gpu.py plus `giant` (64 Gaussians of which 47 have a radius beyond the
+Scenes: those of tests/test_raster_absgrad_gpu.py plus `giant` (64 Gaussians of which 47 have a radius beyond the
 width of the 416 x 320 image, hundreds of tiles each: the per-Gaussian sum kernel's wave path with several passes), bg = (0.1, 0.25, 0.4), normal loss
 weights from default_rng(5).  The oracle's backward of a scene is computed once and shared."""
-import functools
 import itertools
 
 import numpy as np
@@ -18,10 +17,11 @@ import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera, random_gaussians
-from test_raster_absgrad_gpu import BG, GRAD_TOL, _check_grad, _leaf, _loss_weights, _model, _scene, _settings, _stack_scene
+from raster_harness import BG, check_grad, cov6_torch, leaf, loss_weights, memo, model, run, scene, settings, shs, stack_scene
 
 pytestmark = pytest.mark.gpu
 
+GRAD_TOL = 2e-4         # tests/test_raster_camera_gpu.py: of the tensor's maximum
 GRADS = (("dL_dmeans3D", "means3D"), ("dL_dmeans2D", "means2D"), ("dL_dopacities", "opacities"), ("dL_dscales", "scales"),
          ("dL_drotations", "rotations"), ("dL_dcolors", "colors"))
 SCENES = ("s300", "sat", "long", "wide", "giant")
@@ -34,42 +34,28 @@ def _giant():
     return cam, g
 
 
-@functools.lru_cache(maxsize=None)
 def _named(name):
-    return {"s300": lambda: _scene(300, 40, 24, 7, srange=(0.01, 0.12)),     # 565 pairs, near-plane culls
-            "sat": lambda: _stack_scene("saturated", 32, 16),                # every pixel stops early, occluded Gaussians
-            "long": lambda: _stack_scene("long", 24, 16),                    # 700-entry lists, three staged batches
-            "wide": lambda: _scene(2000, 128, 96, 7),                        # 48 tiles, thousands of pairs
+    return {"s300": lambda: scene(300, 40, 24, 7, srange=(0.01, 0.12)),     # 565 pairs, near-plane culls
+            "sat": lambda: stack_scene("saturated", 32, 16),                # every pixel stops early, occluded Gaussians
+            "long": lambda: stack_scene("long", 24, 16),                    # 700-entry lists, three staged batches
+            "wide": lambda: scene(2000, 128, 96, 7),                        # 48 tiles, thousands of pairs
             "giant": _giant}[name]()
-
-
-_REFS = {}
 
 
 def _ref(oracle, name):
     """The fp32 oracle's forward and backward of a scene: computed once, nobody writes into it."""
-    if name not in _REFS:
+    def make():
         cam, g = _named(name)
-        w = _loss_weights(cam.image_height, cam.image_width)
-        _REFS[name] = oracle.render(cam.oracle_dict(bg=BG), g["means3D"], g["colors"], g["opacities"], g["scales"], g["rotations"],
-                                    dL_dout=w)
-    return _REFS[name]
+        w = loss_weights(cam.image_height, cam.image_width)
+        return oracle.render(cam.oracle_dict(bg=BG), g["means3D"], g["colors"], g["opacities"], g["scales"], g["rotations"],
+                             dL_dout=w)
+    return memo(("deterministic", name), make)
 
 
 def _run(rs, g, w, deterministic=True, absgrad=False):
     """Forward + backward of sum(color * w) on fresh leaves (and, the allocator willing, fresh workspaces)."""
-    from contextgs_amd.rasterizer import GaussianRasterizer
-    P = g["means3D"].shape[0]
-    t = {k: _leaf(v) for k, v in g.items()}
-    m2 = torch.zeros(P, 4 if absgrad else 3, device="cuda", requires_grad=True)
-    color, radii = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"],
-                                          scales=t["scales"], rotations=t["rotations"], deterministic=deterministic,
-                                          **(dict(absgrad=True) if absgrad else {}))
-    (color * torch.as_tensor(w, device="cuda")).sum().backward()
-    torch.cuda.synchronize()
-    grad = {k: v.grad.detach() for k, v in t.items()}
-    grad["means2D"] = m2.grad
-    return dict(color=color.detach(), radii=radii, grad=grad, leaves=t)
+    return run(rs, g, loss_w={"color": w}, means2D_cols=4 if absgrad else 3, deterministic=deterministic,
+               **(dict(absgrad=True) if absgrad else {}))
 
 
 def _assert_same_bits(a, b, what):
@@ -79,7 +65,7 @@ def _assert_same_bits(a, b, what):
 
 def _scene_run(name, **kw):
     cam, g = _named(name)
-    return _run(_settings(cam), g, _loss_weights(cam.image_height, cam.image_width), **kw)
+    return _run(settings(cam), g, loss_weights(cam.image_height, cam.image_width), **kw)
 
 
 # ---- 1: run-to-run equality ----------------------------------------------------------------------------------------------------
@@ -110,8 +96,8 @@ def test_matches_the_oracle_and_the_default_path(oracle32, name):
         a = det["grad"][tname]
         assert float(np.abs(ref[k]).max()) > 0
         r = ref[k].reshape(ref[k].shape[0], -1)[:, :a.reshape(a.shape[0], -1).shape[1]]
-        _check_grad(a, r, f"{k} {name} vs oracle32")
-        _check_grad(a, plain["grad"][tname].cpu().numpy(), f"{k} {name} vs the default path")
+        check_grad(a, r, f"{k} {name} vs oracle32")
+        check_grad(a, plain["grad"][tname].cpu().numpy(), f"{k} {name} vs the default path")
     culled = det["radii"] <= 0
     for _, tname in GRADS:
         assert bool((det["grad"][tname][culled] == 0).all()), tname
@@ -175,16 +161,15 @@ def test_binning_and_pair_count_do_not_change_a_bit(name, restore_bin_mode):
                                       for f in ("shs+scales", "shs+cov", "colors+cov")])
 def test_every_form_with_and_without_antialiasing(form, aa):
     from contextgs_amd.rasterizer import GaussianRasterizer
-    from test_raster_sh_cov_gpu import _shs, cov6_torch
     P, W, H, D, M = 2000, 128, 96, 2, 9
-    cam, g = _scene(P, W, H, P + 3)
-    sh = _shs(P, M, seed=P)
-    rs = _settings(cam, D=D, aa=aa)
-    w = torch.tensor(_loss_weights(H, W), device="cuda")
+    cam, g = scene(P, W, H, P + 3)
+    sh = shs(P, M, seed=P)
+    rs = settings(cam, D=D, aa=aa)
+    w = torch.tensor(loss_weights(H, W), device="cuda")
 
     def run(deterministic):
-        t = {k: _leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
-        t["shs"] = _leaf(sh)
+        t = {k: leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
+        t["shs"] = leaf(sh)
         m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
         kw = dict(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], deterministic=deterministic)
         used = ["means3D", "opacities"]
@@ -215,7 +200,7 @@ def test_every_form_with_and_without_antialiasing(form, aa):
     for k in a:
         assert torch.equal(a[k], b[k]), (form, aa, k)
         assert float(ref[k].abs().max()) > 0, k
-        _check_grad(a[k], ref[k].cpu().numpy(), f"{k} {form}{' aa' if aa else ''} vs the default path")
+        check_grad(a[k], ref[k].cpu().numpy(), f"{k} {form}{' aa' if aa else ''} vs the default path")
 
 
 # ---- 5: absgrad ------------------------------------------------------------------------------------------------------------------
@@ -229,8 +214,8 @@ def test_absgrad_columns(name):
     assert m2.shape == (P, 4)
     _assert_same_bits(a, b, f"{name} absgrad")
     assert float(ref["grad"]["means2D"][:, 2:4].max()) > 0
-    _check_grad(m2[:, 2:4], ref["grad"]["means2D"][:, 2:4].cpu().numpy(), f"absolute columns {name} vs the default path")
-    _check_grad(m2[:, 0:2], ref["grad"]["means2D"][:, 0:2].cpu().numpy(), f"signed columns {name} vs the default path")
+    check_grad(m2[:, 2:4], ref["grad"]["means2D"][:, 2:4].cpu().numpy(), f"absolute columns {name} vs the default path")
+    check_grad(m2[:, 0:2], ref["grad"]["means2D"][:, 0:2].cpu().numpy(), f"signed columns {name} vs the default path")
     assert bool((m2[:, 2:4] >= 0).all())
     # the other gradients are those of the flag without absgrad, bit for bit (the same sums in the same order)
     plain = _scene_run(name)
@@ -244,14 +229,14 @@ def test_absgrad_columns(name):
 def test_camera_gradients():
     from contextgs_amd.rasterizer import GaussianRasterizer
     P, W, H = 2000, 160, 120
-    cam, g = _scene(P, W, H, 13)
-    w = torch.tensor(_loss_weights(H, W), device="cuda")
+    cam, g = scene(P, W, H, 13)
+    w = torch.tensor(loss_weights(H, W), device="cuda")
     c = cam.to_torch("cuda")
 
     def run(deterministic):
         V, PM = c.world_view_transform.clone().requires_grad_(True), c.full_proj_transform.clone().requires_grad_(True)
-        rs = _settings(cam, view=V, proj=PM)
-        t = {k: _leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
+        rs = settings(cam, view=V, proj=PM)
+        t = {k: leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
         m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
         img, _ = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"],
                                         scales=t["scales"], rotations=t["rotations"], deterministic=deterministic)
@@ -277,8 +262,8 @@ def test_poisoned_workspaces_change_nothing():
     cam, g = _named("s300")
     H, W = cam.image_height, cam.image_width
     P = g["means3D"].shape[0]
-    w = torch.tensor(_loss_weights(H, W), device="cuda")
-    node = _run(_settings(cam), g, w)
+    w = torch.tensor(loss_weights(H, W), device="cuda")
+    node = _run(settings(cam), g, w)
     lc = dict(rz.last_call)
     t = node["leaves"]
     R = int(lc["bin_R"])
@@ -332,7 +317,7 @@ def _train_view(pc, cam, pipe, bg, fuse, **kw):
 
 
 def test_render_and_the_fused_node():
-    pc, cams, pipe, bg = _model()
+    pc, cams, pipe, bg = model()
     pc.train()
     a = _train_view(pc, cams[1], pipe, bg, True, deterministic=True)
     b = _train_view(pc, cams[1], pipe, bg, True, deterministic=True)
@@ -343,7 +328,7 @@ def test_render_and_the_fused_node():
     assert torch.equal(a["render"], b["render"]) and torch.equal(a["render"], u["render"]) and torch.equal(a["render"], plain["render"])
     assert torch.equal(ga, gb)
     assert torch.equal(ga, gu)          # same records and same lists in, same bits out
-    _check_grad(ga, gp.cpu().numpy(), "viewspace_points.grad, with vs without the flag")
+    check_grad(ga, gp.cpu().numpy(), "viewspace_points.grad, with vs without the flag")
     same = sorted(n for n in a["param_grads"] if n in b["param_grads"] and torch.equal(a["param_grads"][n], b["param_grads"][n]))
     other = sorted(set(a["param_grads"]) - set(same))
     print(f"[deterministic] fused training view, parameter gradients bit-equal between two calls: {same}; not: {other} "
@@ -359,7 +344,7 @@ def test_refusals():
     cam, g = _named("s300")
     H, W = cam.image_height, cam.image_width
     P = g["means3D"].shape[0]
-    rs = _settings(cam)
+    rs = settings(cam)
     t = {k: torch.tensor(v, device="cuda") for k, v in g.items()}
     args = dict(means3D=t["means3D"], means2D=torch.zeros(P, 3, device="cuda"), opacities=t["opacities"], colors_precomp=t["colors"],
                 scales=t["scales"], rotations=t["rotations"], deterministic=True)
@@ -368,7 +353,7 @@ def test_refusals():
         with pytest.raises(ValueError, match=name):
             GaussianRasterizer(rs)(**args, **kw)
     # the C level, on a real view's workspaces
-    w = torch.tensor(_loss_weights(H, W), device="cuda")
+    w = torch.tensor(loss_weights(H, W), device="cuda")
     node = _run(rs, g, w)
     lc = dict(rz.last_call)
     R = int(lc["bin_R"])
@@ -399,7 +384,7 @@ def test_refusals():
 
 def test_empty_inputs_give_zero_gradients():
     cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), 80, 64, fovx_deg=50.0)
-    rs = _settings(cam)
+    rs = settings(cam)
     g = random_gaussians(64, seed=6)
     g["means3D"][:, 1] -= 20.0                        # everything behind the camera
     for gg in (g, {k: v[:0] for k, v in g.items()}):

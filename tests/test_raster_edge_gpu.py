@@ -5,23 +5,17 @@ on one pixel.  Finite image, backward runs, finite gradients - and the same imag
 (oracle/raster_ref.c) under the tolerances of tests/test_raster_gpu.py: radii bit-exact; image RMSE <= 1e-5, at most 1e-4 of
 the values beyond 2e-5, max-abs <= 1/255 + 1e-4; gradients within 2e-4 of each tensor's maximum on all but 2e-3 of the
 entries, median <= 1e-6.  float64 and non-contiguous inputs are compared on their fp32-cast, contiguous values."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
-from contextgs_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+from contextgs_amd.rasterizer import GaussianRasterizer
 from contextgs_amd.synth import orbit_cameras
+from raster_harness import settings
 
 pytestmark = pytest.mark.gpu
 
 
-def settings(W, H):
-    cam = orbit_cameras(2, W, H)[0].to_torch("cuda")
-    return cam, GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5),
-        bg=torch.tensor([0.1, 0.2, 0.3], device="cuda"), scale_modifier=1.0, viewmatrix=cam.world_view_transform,
-        projmatrix=cam.full_proj_transform, sh_degree=1, campos=cam.camera_center, prefiltered=False, debug=False)
 def _check_image(a, b, what):
     d = np.abs(a - b)
     rmse = float(np.sqrt((d ** 2).mean()))
@@ -67,7 +61,7 @@ def oracle_check(cam, inputs, img, radii, grads, what):
 
 
 def go(P, W, H, scale=0.05, dtype=torch.float32, noncontig=False, op=0.8, pos_scale=0.5, name=""):
-    cam, rs = settings(W, H)
+    rs = settings(orbit_cameras(2, W, H)[0], bg=(0.1, 0.2, 0.3))
     g = torch.Generator(device="cuda").manual_seed(P + W)
     xyz = (torch.randn(P, 3, device="cuda", generator=g) * pos_scale).to(dtype).requires_grad_(True)
     col = torch.rand(P, 3, device="cuda", generator=g).to(dtype).requires_grad_(True)

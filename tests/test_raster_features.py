@@ -9,6 +9,8 @@ import math
 import pytest
 import torch
 
+from raster_harness import fake_cfg
+
 CGS_ERR_ARG = 1
 CGS_ERR_WORKSPACE = 3
 
@@ -16,17 +18,10 @@ NEW_SYMBOLS = ("cgs_raster_render_features", "cgs_raster_backward_feat")
 P1 = C.c_void_p(4096)      # a non-NULL stand-in: the checks only look at which pointers are given
 
 
-def _cfg(H=16, W=16):
-    from contextgs_amd import _lib
-    fake = C.c_void_p(256)     # never dereferenced: every call below fails its argument checks first
-    return _lib.RasterCfg(image_height=H, image_width=W, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
-                          debug=0, viewmatrix=fake, projmatrix=fake, campos=fake, bg=fake)
-
-
 def _render_features(P=1, R=1, geom=P1, bin_ws=P1, img=P1, img_bytes=1 << 30, features=P1, Cn=5, out=P1):
     from contextgs_amd import _lib
     L = _lib.lib()
-    rc = L.cgs_raster_render_features(C.byref(_cfg()), P, R, geom, 1 << 30, bin_ws, 1 << 30, img, img_bytes, features, Cn, out,
+    rc = L.cgs_raster_render_features(C.byref(fake_cfg()), P, R, geom, 1 << 30, bin_ws, 1 << 30, img, img_bytes, features, Cn, out,
                                       None)
     return rc, L.cgs_last_error().decode()
 
@@ -35,9 +30,9 @@ def _backward_feat(P=1, R=0, geom=P1, img=P1, scratch=P1, scratch_bytes=1 << 40,
     """colours + scales / rotations, every other pointer given"""
     from contextgs_amd import _lib
     L = _lib.lib()
-    rc = L.cgs_raster_backward_feat(C.byref(_cfg()), P, R, P1, P1, None, 0, 0, P1, P1, P1, None, P1, geom, 1 << 30, None, 0, img,
-                                    1 << 30, None, None, None, None, P1, P1, P1, P1, None, P1, P1, None, scratch, scratch_bytes,
-                                    None, 0, features, Cn, g_map, d_feat)
+    rc = L.cgs_raster_backward_feat(C.byref(fake_cfg()), P, R, P1, P1, None, 0, 0, P1, P1, P1, None, P1, geom, 1 << 30, None, 0,
+                                    img, 1 << 30, None, None, None, None, P1, P1, P1, P1, None, P1, P1, None, scratch,
+                                    scratch_bytes, None, 0, features, Cn, g_map, d_feat)
     return rc, L.cgs_last_error().decode()
 
 
@@ -82,7 +77,7 @@ def test_backward_feat_argument_errors():
     assert rc == CGS_ERR_WORKSPACE and "scratch" in msg
     from contextgs_amd import _lib
     L = _lib.lib()        # an unknown option bit, as cgs_raster_backward_opt
-    rc = L.cgs_raster_backward_feat(C.byref(_cfg()), 1, 0, P1, P1, None, 0, 0, P1, P1, P1, None, P1, P1, 1 << 30, None, 0, P1,
+    rc = L.cgs_raster_backward_feat(C.byref(fake_cfg()), 1, 0, P1, P1, None, 0, 0, P1, P1, P1, None, P1, P1, 1 << 30, None, 0, P1,
                                     1 << 30, None, None, None, None, P1, P1, P1, P1, None, P1, P1, None, P1, 1 << 40, None, 4,
                                     P1, 5, P1, P1)
     assert rc == CGS_ERR_ARG and "cgs_raster_backward_feat" in L.cgs_last_error().decode()

@@ -4,59 +4,31 @@ The feature map is the colour blend of the table's columns with a zero backgroun
 columns at a time as `colors` (the last group zero-padded) with bg = 0: `color` of a group is that group of the map,
 `dL_dcolors` that group of dL/dfeatures, and the geometry gradients are the sum over the groups (plus the ordinary colour run
 and the maps' run of tests/test_raster_aux_gpu.py when those are in the loss).  Tolerances are those of
-tests/test_raster_aux_gpu.py, unchanged (`_check_map`, `_check_grad` are copies): maps RMSE <= 1e-5 of the map's maximum and at
-most a 1e-4 share of values beyond 2e-5; gradients at most a 2e-3 share of entries beyond 2e-4 of the tensor's maximum.
+tests/test_raster_aux_gpu.py, unchanged (`check_map`, `check_grad` of tests/raster_harness.py): maps RMSE <= 1e-5 of the map's
+maximum and at most a 1e-4 share of values beyond 2e-5; gradients at most a 2e-3 share of entries beyond 2e-4 of the tensor's
+maximum.
 
 Scenes.  Every scene below with an oracle comparison was first run on the CPU with the fp32 oracle against the fp64 oracle
 under the same two checks, and kept only because the fp32 oracle alone stays within HALF of those shares there (map RMSE
 <= 5e-6 and a <= 5e-5 share beyond 2e-5; gradients a <= 1e-3 share beyond 2e-4), at every C the test uses.
 References are computed once per (scene, C) and shared between the tests and loss sets that need them.
 """
-import functools
 import itertools
-import math
 
 import numpy as np
 import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera, random_gaussians
+from raster_harness import (BG, aux_colors, check_grad, check_map, cov6_torch, leaf, memo, model, run, scene, settings,
+                            sh_eval_torch, shs, stack_scene, view_z)
 
 pytestmark = pytest.mark.gpu
 
-BG = (0.1, 0.25, 0.4)
 MAPS = ("depth", "invdepth", "alpha")
 GEOM = (("dL_dmeans3D", "means3D"), ("dL_dmeans2D", "means2D"), ("dL_dopacities", "opacities"), ("dL_dscales", "scales"),
         ("dL_drotations", "rotations"))
 CMAX = 32
-
-
-# ---- scenes (constructions of tests/test_raster_aux_gpu.py) -------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _scene(P, W, H, seed, extent=1.0, srange=(0.005, 0.05)):
-    cam = look_at_camera((0.4, -2.2, 0.6), (0, 0, 0), W, H, fovx_deg=60.0)
-    g = random_gaussians(P, seed=seed, extent=extent, scale_lo=srange[0], scale_hi=srange[1])
-    if P >= 20:     # some Gaussians behind the near plane
-        eye = np.array([0.4, -2.2, 0.6], dtype=np.float32)
-        g["means3D"][::20] = eye + 0.3 * (eye - g["means3D"][::20])
-    return cam, g
-
-
-@functools.lru_cache(maxsize=None)
-def _stack_scene(kind):
-    """saturated: the scene of test_saturated_stack_reaches_termination.  long: 700 faint, wide Gaussians in front of a 64x48
-    image, more than two 256-entry batches per tile and no pixel stopped early."""
-    W, H = 64, 48
-    cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), W, H, fovx_deg=50.0)
-    if kind == "saturated":
-        rng = np.random.default_rng(11)
-        g = random_gaussians(300, seed=11, extent=0.2, scale_lo=0.15, scale_hi=0.4)
-        g["opacities"][:] = rng.uniform(0.9, 0.999, size=g["opacities"].shape).astype(np.float32)
-    else:
-        rng = np.random.default_rng(12)
-        g = random_gaussians(700, seed=12, extent=0.2, scale_lo=0.15, scale_hi=0.4)
-        g["opacities"][:] = rng.uniform(0.005, 0.02, size=g["opacities"].shape).astype(np.float32)
-    return cam, g
 
 
 def _table(P, seed, C=CMAX):
@@ -66,19 +38,6 @@ def _table(P, seed, C=CMAX):
 
 def _weights(H, W, seed, C=CMAX):
     return np.random.default_rng(2000 + seed).normal(size=(CMAX, H, W)).astype(np.float32)[:C].copy()
-
-
-def _view_z(cam, means3D):
-    V = np.asarray(cam.world_view_transform.detach().cpu().numpy() if hasattr(cam.world_view_transform, "detach")
-                   else cam.world_view_transform, dtype=np.float32).reshape(4, 4)
-    m = means3D.astype(np.float32)
-    return ((V[0, 2] * m[:, 0] + V[1, 2] * m[:, 1]) + V[2, 2] * m[:, 2]) + V[3, 2], V[:3, 2].copy()
-
-
-def _aux_colors(z):
-    ok = z > 0.2
-    zs = np.where(ok, z, 1.0).astype(np.float32)
-    return np.stack([np.where(ok, zs, 0), np.where(ok, np.float32(1.0) / zs, 0), np.where(ok, 1.0, 0)], 1).astype(np.float32)
 
 
 # ---- the oracle, three columns at a time ---------------------------------------------------------------------------------------
@@ -107,92 +66,28 @@ def oracle_features(oracle, cam, g, F, dl=None):
     return out
 
 
-_REFS = {}
-
-
-def _ref(oracle, key, make):
-    """References are computed once and shared; nobody writes into them."""
-    if key not in _REFS:
-        _REFS[key] = make()
-    return _REFS[key]
-
-
 def _fwd_ref(oracle, name, cam, g, seed):
     P = g["means3D"].shape[0]
-    return _ref(oracle, ("fwd", name), lambda: oracle_features(oracle, cam, g, _table(P, seed)))
+    return memo(("features", "fwd", name), lambda: oracle_features(oracle, cam, g, _table(P, seed)))
 
 
 def _bwd_ref(oracle, name, cam, g, seed, C):
     P = g["means3D"].shape[0]
     H, W = cam.image_height, cam.image_width
-    return _ref(oracle, ("bwd", name, C), lambda: oracle_features(oracle, cam, g, _table(P, seed, C), dl=_weights(H, W, seed, C)))
+    return memo(("features", "bwd", name, C),
+                lambda: oracle_features(oracle, cam, g, _table(P, seed, C), dl=_weights(H, W, seed, C)))
 
 
 # ---- running the rasterizer ---------------------------------------------------------------------------------------------------
-def _settings(cam, bg=BG, D=1, debug=False, aa=False, view=None, proj=None):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    c = cam.to_torch("cuda")
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.tensor(bg, dtype=torch.float32, device="cuda"), scale_modifier=1.0,
-        viewmatrix=c.world_view_transform if view is None else view, projmatrix=c.full_proj_transform if proj is None else proj,
-        sh_degree=D, campos=c.camera_center, prefiltered=False, debug=debug, antialiasing=aa)
-
-
-def _leaf(a):
-    return torch.tensor(a, device="cuda", requires_grad=True)
-
-
-def _run(rs, g, F=None, return_aux=False, loss_w=None, colors=None):
-    """Forward (and backward of sum(out * w) over the entries of loss_w: keys color / depth / invdepth / alpha / features)."""
-    from contextgs_amd.rasterizer import GaussianRasterizer
-    P = g["means3D"].shape[0]
-    t = {k: _leaf(v) for k, v in g.items()}
-    if colors is not None:
-        t["colors"] = _leaf(colors)
-    if F is not None:
-        t["features"] = _leaf(F)
-    m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
-    res = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"],
-                                 scales=t["scales"], rotations=t["rotations"], features=t.get("features"), return_aux=return_aux)
-    out = {"color": res[0], "radii": res[1]}
-    if len(res) > 2:
-        out.update(res[2])
-    if loss_w:
-        sum(((out[k] * torch.as_tensor(w, device="cuda")).sum() for k, w in loss_w.items())).backward()
-    torch.cuda.synchronize()
-    o = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in out.items()}
-    o["grad"] = {k: (None if v.grad is None else v.grad.detach()) for k, v in t.items()}
-    o["grad"]["means2D"] = m2.grad
-    return o
-
-
-def _check_map(a, b, what):
-    a = a.detach().float().cpu().numpy().reshape(-1)
-    b = np.asarray(b, dtype=np.float32).reshape(-1)
-    scale = max(float(np.abs(b).max()), 1e-12)
-    d = np.abs(a - b) / scale
-    rmse = float(np.sqrt((d ** 2).mean()))
-    n_out = int((d > 2e-5).sum())
-    print(f"[allowance] {what}: rmse {rmse:.2e}, {n_out} of {d.size} values beyond 2e-5 of the max {scale:.3g}, worst {d.max():.2e}")
-    assert rmse <= 1e-5, (what, rmse)
-    assert n_out <= 1e-4 * d.size, (what, n_out, float(d.max()))
-
-
-def _check_grad(a, b, what, allow_frac=2e-3, tol=2e-4):
-    a = a.detach().float().cpu().numpy().reshape(a.shape[0], -1) if torch.is_tensor(a) else a
-    b = np.asarray(b, dtype=np.float32).reshape(a.shape)
-    scale = max(1e-6, float(np.abs(b).max()))
-    err = np.abs(a - b) / scale
-    n_out = int((err > tol).sum())
-    print(f"[allowance] {what}: {n_out} of {err.size} entries beyond {tol:g} of the maximum, worst {err.max():.2e}")
-    assert n_out <= allow_frac * err.size, (what, n_out, float(err.max()))
+def _run(rs, g, F=None, **kw):
+    """raster_harness.run with the feature table F."""
+    return run(rs, g, features=F, **kw)
 
 
 def _check_all_grads(out, exp, ref_f, what):
     for k, t in GEOM:
-        _check_grad(out["grad"][t], exp[k], f"{k} {what}")
-    _check_grad(out["grad"]["features"], ref_f["dL_dfeatures"], f"dL_dfeatures {what}")
+        check_grad(out["grad"][t], exp[k], f"{k} {what}")
+    check_grad(out["grad"]["features"], ref_f["dL_dfeatures"], f"dL_dfeatures {what}")
 
 
 # ---- forward ------------------------------------------------------------------------------------------------------------------
@@ -202,9 +97,9 @@ FWD_CASES = [(1, 64, 48), (64, 128, 96), (4000, 256, 256)]
 @pytest.mark.parametrize("P, W, H", FWD_CASES)
 @pytest.mark.parametrize("C", [1, 3, 5, 8, 17, 32])
 def test_forward_matches_the_oracle(oracle32, P, W, H, C):
-    cam, g = _scene(P, W, H, P)
+    cam, g = scene(P, W, H, P)
     ref = _fwd_ref(oracle32, f"scene{P}", cam, g, P)
-    rs = _settings(cam, debug=(P == 1))          # the smallest case with a synchronised check after every kernel
+    rs = settings(cam, debug=(P == 1))          # the smallest case with a synchronised check after every kernel
     out = _run(rs, g, F=_table(P, P, C))
     plain = _run(rs, g)
     # no interference: the colour image and radii are those of the plain call, bit for bit
@@ -215,7 +110,7 @@ def test_forward_matches_the_oracle(oracle32, P, W, H, C):
     for c in range(C):      # per channel, each against the whole map's maximum
         a = out["features"][c].cpu().numpy()
         assert np.abs(a - ref["map"][c]).max() <= 1e-3 * max(scale, 1e-12), c      # (a wrong channel is off by order 1)
-    _check_map(out["features"], ref["map"][:C], f"features P={P} C={C}")
+    check_map(out["features"], ref["map"][:C], f"features P={P} C={C}")
 
 
 # ---- backward -----------------------------------------------------------------------------------------------------------------
@@ -224,34 +119,35 @@ LOSSES = [("features",), ("color", "features"), ("color", "depth", "invdepth", "
 
 
 def _colour_ref(oracle, name, cam, g, gC):
-    return _ref(oracle, ("colour", name), lambda: oracle.render(cam.oracle_dict(bg=BG), g["means3D"], g["colors"], g["opacities"],
-                                                                g["scales"], g["rotations"], dL_dout=gC))
+    return memo(("features", "colour", name),
+                lambda: oracle.render(cam.oracle_dict(bg=BG), g["means3D"], g["colors"], g["opacities"], g["scales"], g["rotations"],
+                                      dL_dout=gC))
 
 
 def _aux_ref(oracle, name, cam, g, gm):
     def make():
-        z, dz = _view_z(cam, g["means3D"])
-        ra = oracle.render(cam.oracle_dict(bg=(0.0, 0.0, 0.0)), g["means3D"], _aux_colors(z), g["opacities"], g["scales"],
+        z, dz = view_z(cam, g["means3D"])
+        ra = oracle.render(cam.oracle_dict(bg=(0.0, 0.0, 0.0)), g["means3D"], aux_colors(z), g["opacities"], g["scales"],
                            g["rotations"], dL_dout=np.concatenate([gm[k] for k in MAPS], 0))
         zs = np.where(z > 0.2, z, 1.0).astype(np.float32)
         ra = dict(ra)
         ra["dL_dmeans3D"] = ra["dL_dmeans3D"] + (ra["dL_dcolors"][:, 0] - ra["dL_dcolors"][:, 1] / (zs * zs))[:, None] * dz[None, :]
         return ra
-    return _ref(oracle, ("aux", name), make)
+    return memo(("features", "aux", name), make)
 
 
 @pytest.mark.parametrize("P, W, H, seed, extent, srange", BWD_CASES)
 @pytest.mark.parametrize("C", [1, 5, 32])
 @pytest.mark.parametrize("keys", LOSSES, ids=["+".join(k) for k in LOSSES])
 def test_backward_matches_the_oracle(oracle32, P, W, H, seed, extent, srange, C, keys):
-    cam, g = _scene(P, W, H, seed, extent, srange)
+    cam, g = scene(P, W, H, seed, extent, srange)
     name = f"bwd{P}"
     rf = _bwd_ref(oracle32, name, cam, g, seed, C)
     rng = np.random.default_rng(seed + 17)
     gC = rng.normal(size=(3, H, W)).astype(np.float32)
     gm = {k: rng.normal(size=(1, H, W)).astype(np.float32) for k in MAPS}
     loss_w = {k: (_weights(H, W, seed, C) if k == "features" else gC if k == "color" else gm[k]) for k in keys}
-    out = _run(_settings(cam), g, F=_table(P, seed, C), return_aux="depth" in keys, loss_w=loss_w)
+    out = _run(settings(cam), g, F=_table(P, seed, C), return_aux="depth" in keys, loss_w=loss_w)
 
     exp = {k: rf[k] for k, _ in GEOM}
     if "color" in keys:
@@ -262,7 +158,7 @@ def test_backward_matches_the_oracle(oracle32, P, W, H, seed, extent, srange, C,
         exp = {k: exp[k] + ra[k] for k in exp}
     _check_all_grads(out, exp, rf, f"P={P} C={C} {'+'.join(keys)}")
     if "color" in keys:
-        _check_grad(out["grad"]["colors"], rc["dL_dcolors"], f"dL_dcolors P={P}")
+        check_grad(out["grad"]["colors"], rc["dL_dcolors"], f"dL_dcolors P={P}")
     else:
         assert out["grad"]["colors"] is None          # the features send nothing to the colour input
     assert float(out["grad"]["means3D"].abs().sum()) > 0
@@ -275,41 +171,41 @@ def test_lists_longer_than_one_staged_batch(oracle32):
     stats[0] / stats[1] is near 1 in any scene).  The kernels walk up to the last visited entry (464 per tile here, no pixel
     stopped early): also asserted to lie beyond the first batch."""
     C = 5
-    cam, g = _stack_scene("long")
+    cam, g = stack_scene("long", 64, 48)
     P, H, W = g["means3D"].shape[0], cam.image_height, cam.image_width
     tiles = ((H + 15) // 16) * ((W + 15) // 16)
     rf = _bwd_ref(oracle32, "long", cam, g, 12, C)
     assert float(rf["final_T"].min()) > 1e-4                       # no pixel stopped early
     assert int(rf["stats"][0]) / tiles > 512                       # more than two 256-entry batches per tile
     assert int(rf["stats"][1]) / tiles > 256                       # and the walk goes beyond the first
-    out = _run(_settings(cam), g, F=_table(P, 12, C), loss_w={"features": _weights(H, W, 12, C)})
-    _check_map(out["features"], rf["map"], "features, long lists")
+    out = _run(settings(cam), g, F=_table(P, 12, C), loss_w={"features": _weights(H, W, 12, C)})
+    check_map(out["features"], rf["map"], "features, long lists")
     _check_all_grads(out, rf, rf, "long lists")
 
 
 def test_saturated_stack(oracle32):
-    cam, g = _stack_scene("saturated")
-    ref = _ref(oracle32, ("fwd", "saturated"), lambda: oracle_features(oracle32, cam, g, g["colors"]))
+    cam, g = stack_scene("saturated", 64, 48)
+    ref = memo(("features", "fwd", "saturated"), lambda: oracle_features(oracle32, cam, g, g["colors"]))
     assert float(ref["final_T"].min()) < 1e-3         # the stack saturates: pixels stopped on the 1e-4 test
-    out = _run(_settings(cam, bg=(0.0, 0.0, 0.0)), g, F=g["colors"])
-    _check_map(out["features"], ref["map"], "features saturated")
+    out = _run(settings(cam, bg=(0.0, 0.0, 0.0)), g, F=g["colors"])
+    check_map(out["features"], ref["map"], "features saturated")
     scale = float(out["color"].abs().max())
     assert float((out["features"] - out["color"]).abs().max()) <= 1e-6 * scale
 
 
 def test_ragged_image(oracle32):
     P, W, H, C = 500, 65, 47, 5
-    cam, g = _scene(P, W, H, 4)
+    cam, g = scene(P, W, H, 4)
     rf = _bwd_ref(oracle32, "ragged", cam, g, 4, C)
-    out = _run(_settings(cam), g, F=_table(P, 4, C), loss_w={"features": _weights(H, W, 4, C)})
-    _check_map(out["features"], rf["map"], "features 65x47")
+    out = _run(settings(cam), g, F=_table(P, 4, C), loss_w={"features": _weights(H, W, 4, C)})
+    check_map(out["features"], rf["map"], "features 65x47")
     _check_all_grads(out, rf, rf, "65x47")
 
 
 def test_empty_inputs_give_zero_maps_and_gradients():
     C = 4
     cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), 80, 64, fovx_deg=50.0)
-    rs = _settings(cam)
+    rs = settings(cam)
     g = random_gaussians(64, seed=6)
     g["means3D"][:, 1] -= 20.0                        # everything behind the camera
     for gg in (g, {k: v[:0] for k, v in g.items()}):
@@ -324,29 +220,29 @@ def test_empty_inputs_give_zero_maps_and_gradients():
 def test_forward_after_a_voided_speculative_render(oracle32):
     from contextgs_amd import rasterizer
     P, W, H, C = 20000, 320, 240, 5
-    cam, g = _scene(P, W, H, 9)
+    cam, g = scene(P, W, H, 9)
     F = _table(P, 9, C)
     ref = oracle_features(oracle32, cam, g, F)
-    rs = _settings(cam)
+    rs = settings(cam)
     rasterizer._pair_capacity[(H, W)] = 1 << 10       # far below the view's pair count: the speculative render is voided
     out = _run(rs, g, F=F)
     assert rasterizer.last_call["num_rendered"] > (1 << 10)
     assert rasterizer.last_call["bin_R"] == rasterizer.last_call["num_rendered"]     # re-rendered with the true count
-    _check_map(out["features"], ref["map"], "features re-rendered")
+    check_map(out["features"], ref["map"], "features re-rendered")
     again = _run(rs, g, F=F)                              # now with a capacity that holds: the speculative render stands
     assert torch.equal(again["features"], out["features"])
 
 
 # ---- one walk for every instance ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("scene", ["ragged 40x24", "long lists"])
-def test_a_channel_is_the_same_bits_in_every_instance(scene):
+@pytest.mark.parametrize("which", ["ragged 40x24", "long lists"])
+def test_a_channel_is_the_same_bits_in_every_instance(which):
     """One fixed column, blended as channel 0 of tables with C = 1, 5, 9, 17 (the 4-, 8-, 16- and 32-channel instances of the
     forward kernel) whose other columns are random: channel 0 of the four maps is bit-identical, because every instance walks
     the same entries in the same order and adds with the same fmaf.  Ragged tiles (40x24 = 3 x 2 tiles, cut right and bottom),
     and the scene with more than two 256-entry batches per tile."""
-    cam, g = _scene(200, 40, 24, 3, 1.0, (0.02, 0.12)) if scene.startswith("ragged") else _stack_scene("long")
+    cam, g = scene(200, 40, 24, 3, 1.0, (0.02, 0.12)) if which.startswith("ragged") else stack_scene("long", 64, 48)
     P = g["means3D"].shape[0]
-    rs = _settings(cam)
+    rs = settings(cam)
     f = _table(P, 77, 1)
     maps = {}
     for C in (1, 5, 9, 17):
@@ -362,19 +258,18 @@ def test_a_channel_is_the_same_bits_in_every_instance(scene):
 @pytest.mark.parametrize("form", ["shs+scales", "shs+cov", "colors+cov"])
 def test_all_forms_match_colors_precomp_scales_rotations(form):
     from contextgs_amd.rasterizer import GaussianRasterizer
-    from test_raster_sh_cov_gpu import _shs, cov6_torch, sh_eval_torch
     P, W, H, C, D, M = 4000, 256, 256, 5, 2, 9
-    cam, g = _scene(P, W, H, P + 3)
-    sh = _shs(P, M, seed=P)
-    rs = _settings(cam, D=D)
+    cam, g = scene(P, W, H, P + 3)
+    sh = shs(P, M, seed=P)
+    rs = settings(cam, D=D)
     campos = rs.campos.float()
     F = _table(P, 5, C)
     w = {"color": torch.tensor(np.random.default_rng(5).normal(size=(3, H, W)).astype(np.float32), device="cuda"),
          "features": torch.tensor(_weights(H, W, 5, C), device="cuda")}
 
     def run(use_shs, use_cov):
-        t = {k: _leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
-        t["shs"], t["features"] = _leaf(sh), _leaf(F)
+        t = {k: leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations", "colors")}
+        t["shs"], t["features"] = leaf(sh), leaf(F)
         m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
         kw = dict(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], features=t["features"])
         if use_shs:
@@ -397,33 +292,33 @@ def test_all_forms_match_colors_precomp_scales_rotations(form):
     same = (ref["radii"] == new["radii"]).cpu()
     assert float(same.float().mean()) >= 1 - 1e-4
     for k in ("color", "fmap"):
-        _check_map(new[k], ref[k].cpu().numpy(), f"{k} {form}")
+        check_map(new[k], ref[k].cpu().numpy(), f"{k} {form}")
     rows = same.numpy()
     allow = 1e-4 if "cov" in form else 0.0
     for k in ("means3D", "opacities", "scales", "rotations", "m2", "features") + (("shs",) if "shs" in form else ("colors",)):
         a, b = new[k].cpu().numpy(), ref[k].cpu().numpy()
-        _check_grad(a[rows].reshape(int(rows.sum()), -1), b[rows].reshape(int(rows.sum()), -1), f"d{k} {form}",
+        check_grad(a[rows].reshape(int(rows.sum()), -1), b[rows].reshape(int(rows.sum()), -1), f"d{k} {form}",
                     allow_frac=max(allow, 2e-3))
 
 
 # ---- antialiasing -------------------------------------------------------------------------------------------------------------
 def test_antialiasing_reads_the_compensated_opacity():
     P, W, H, C = 2000, 128, 96, 5
-    cam, g = _scene(P, W, H, 7)
-    rs = _settings(cam, aa=True)
+    cam, g = scene(P, W, H, 7)
+    rs = settings(cam, aa=True)
     F = _table(P, 7, C)
     F[:, 2] = 1.0                                   # a column of ones blends to the alpha map
     out = _run(rs, g, F=F, return_aux=True)
-    _check_map(out["features"][2], out["alpha"].cpu().numpy(), "ones column vs alpha, antialiasing, C=5")
+    check_map(out["features"][2], out["alpha"].cpu().numpy(), "ones column vs alpha, antialiasing, C=5")
     ones = np.ones((P, 1), np.float32)
     w = _weights(H, W, 7, 1)
     a = _run(rs, g, F=ones, return_aux=True, loss_w={"features": w})
     b = _run(rs, g, F=ones, return_aux=True, loss_w={"alpha": w})
-    _check_map(a["features"], a["alpha"].cpu().numpy(), "ones [P,1] vs alpha, antialiasing")
-    _check_grad(a["grad"]["opacities"], b["grad"]["opacities"].cpu().numpy(), "dL_dopacities features vs alpha, antialiasing")
+    check_map(a["features"], a["alpha"].cpu().numpy(), "ones [P,1] vs alpha, antialiasing")
+    check_grad(a["grad"]["opacities"], b["grad"]["opacities"].cpu().numpy(), "dL_dopacities features vs alpha, antialiasing")
     for k in ("means3D", "scales", "rotations", "means2D"):
-        _check_grad(a["grad"][k], b["grad"][k].cpu().numpy(), f"d{k} features vs alpha, antialiasing")
-    no_aa = _run(_settings(cam), g, F=ones)
+        check_grad(a["grad"][k], b["grad"][k].cpu().numpy(), f"d{k} features vs alpha, antialiasing")
+    no_aa = _run(settings(cam), g, F=ones)
     assert not torch.equal(no_aa["features"], a["features"])
 
 
@@ -432,22 +327,22 @@ def test_camera_gradients_equal_those_of_the_colour_blend_of_the_table():
     from contextgs_amd.rasterizer import GaussianRasterizer
     GRAD_TOL = 2e-4         # tests/test_raster_camera_gpu.py: of the tensor's maximum
     P, W, H, C = 2000, 160, 120, 3
-    cam, g = _scene(P, W, H, 13)
+    cam, g = scene(P, W, H, 13)
     F = _table(P, 13, C)
     w = torch.tensor(_weights(H, W, 13, C), device="cuda")
     c = cam.to_torch("cuda")
 
     def run(as_features):
         V, PM = c.world_view_transform.clone().requires_grad_(True), c.full_proj_transform.clone().requires_grad_(True)
-        rs = _settings(cam, bg=(0.0, 0.0, 0.0), view=V, proj=PM)
-        t = {k: _leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations")}
+        rs = settings(cam, bg=(0.0, 0.0, 0.0), view=V, proj=PM)
+        t = {k: leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations")}
         kw = dict(means3D=t["means3D"], means2D=torch.zeros(P, 3, device="cuda", requires_grad=True), opacities=t["opacities"],
                   scales=t["scales"], rotations=t["rotations"])
         if as_features:
-            _, _, ex = GaussianRasterizer(rs)(colors_precomp=_leaf(g["colors"]), features=_leaf(F), **kw)
+            _, _, ex = GaussianRasterizer(rs)(colors_precomp=leaf(g["colors"]), features=leaf(F), **kw)
             img = ex["features"]
         else:
-            img, _ = GaussianRasterizer(rs)(colors_precomp=_leaf(F), **kw)
+            img, _ = GaussianRasterizer(rs)(colors_precomp=leaf(F), **kw)
         (img * w).sum().backward()
         torch.cuda.synchronize()
         return V.grad, PM.grad
@@ -461,13 +356,6 @@ def test_camera_gradients_equal_those_of_the_colour_blend_of_the_table():
 
 
 # ---- render() -----------------------------------------------------------------------------------------------------------------
-def _model(N=20000, W=320, H=180):
-    from contextgs_amd.synth import SynthPipe, make_scene, orbit_cameras
-    pc = make_scene(N, seed=0)
-    cams = [c.to_torch("cuda") for c in orbit_cameras(4, W, H)]
-    return pc, cams, SynthPipe(), torch.zeros(3, device="cuda")
-
-
 def _render(pc, cam, pipe, bg, **kw):
     from contextgs_amd import ctx_ops
     from contextgs_amd.renderer import prefilter_voxel, render
@@ -479,7 +367,7 @@ def _render(pc, cam, pipe, bg, **kw):
 
 @pytest.mark.parametrize("training", [False, True])
 def test_render_blends_anchor_features(training):
-    pc, cams, pipe, bg = _model()
+    pc, cams, pipe, bg = model()
     pc.train(training)
     N = pc.get_anchor.shape[0]
     af = torch.ones(N, 1, device="cuda", requires_grad=training)
@@ -492,7 +380,7 @@ def test_render_blends_anchor_features(training):
     assert pkg["features"].shape == (1, 180, 320) and pkg["features"].dtype == torch.float32
     assert torch.equal(pkg["render"].detach(), plain["render"].detach())
     assert torch.equal(pkg["radii"], plain["radii"])
-    _check_map(pkg["features"], aux["alpha"].detach().cpu().numpy(), f"render() features of ones vs alpha, training={training}")
+    check_map(pkg["features"], aux["alpha"].detach().cpu().numpy(), f"render() features of ones vs alpha, training={training}")
     assert float(pkg["features"].max()) > 0.5
     if training:
         pkg["features"].sum().backward()

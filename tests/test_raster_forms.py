@@ -7,17 +7,11 @@ import math
 import pytest
 import torch
 
+from raster_harness import fake_cfg
+
 CGS_ERR_ARG = 1
 
 NEW_SYMBOLS = ("cgs_raster_preprocess_launch_ex", "cgs_raster_backward_ex", "cgs_filter_cov")
-
-
-def _cfg(campos=True):
-    from contextgs_amd import _lib
-    # the pointers are never dereferenced: every call below fails its argument checks first
-    fake = C.c_void_p(256)
-    return _lib.RasterCfg(image_height=16, image_width=16, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
-                          debug=0, viewmatrix=fake, projmatrix=fake, campos=fake if campos else None, bg=fake)
 
 
 def _launch_ex(cfg, P=1, colors=None, shs=None, D=0, M=0, scales=None, rotations=None, cov3D=None):
@@ -63,20 +57,20 @@ P1 = C.c_void_p(4096)      # a non-NULL stand-in: the form checks only look at w
     (dict(shs=P1, D=0, M=17, cov3D=P1), "17 SH coefficients"),
 ])
 def test_argument_errors_return_err_arg(call, kw, needle):
-    out = call(_cfg(), **kw)
+    out = call(fake_cfg(), **kw)
     assert out[0] == CGS_ERR_ARG, out
     assert needle in out[1], out[1]
 
 
 def test_sh_without_campos_is_an_argument_error():
-    rc, msg, _ = _launch_ex(_cfg(campos=False), shs=P1, D=1, M=4, scales=P1, rotations=P1)
+    rc, msg, _ = _launch_ex(fake_cfg(campos=False), shs=P1, D=1, M=4, scales=P1, rotations=P1)
     assert rc == CGS_ERR_ARG and "campos" in msg
-    rc, msg = _backward_ex(_cfg(campos=False), shs=P1, D=1, M=4, scales=P1, rotations=P1)
+    rc, msg = _backward_ex(fake_cfg(campos=False), shs=P1, D=1, M=4, scales=P1, rotations=P1)
     assert rc == CGS_ERR_ARG and "campos" in msg
 
 
 def test_launch_ex_clears_the_ticket_on_an_argument_error():
-    rc, _, ticket = _launch_ex(_cfg(), shs=P1, D=3, M=4, cov3D=P1)
+    rc, _, ticket = _launch_ex(fake_cfg(), shs=P1, D=3, M=4, cov3D=P1)
     assert rc == CGS_ERR_ARG and ticket == 0
 
 
@@ -85,7 +79,7 @@ def test_filter_cov_argument_errors():
     L = _lib.lib()
     assert L.cgs_filter_cov(None, 10, None, None, None, None) == CGS_ERR_ARG
     assert b"cfg" in L.cgs_last_error()
-    cfg = _cfg()
+    cfg = fake_cfg()
     assert L.cgs_filter_cov(C.byref(cfg), 10, P1, None, P1, None) == CGS_ERR_ARG
     assert b"NULL" in L.cgs_last_error()
     assert L.cgs_filter_cov(C.byref(cfg), -1, P1, P1, P1, None) == CGS_ERR_ARG

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import raster_geom_ref as ref
+from raster_harness import fake_cfg
 
 CGS_OK = 0
 CGS_ERR_ARG = 1
@@ -88,18 +89,11 @@ def test_e_and_zterm_equal_central_differences():
 
 
 # ---- the C-ABI ---------------------------------------------------------------------------------------------------------------
-def _cfg(H=16, W=16):
-    from contextgs_amd import _lib
-    fake = C.c_void_p(256)     # never dereferenced: every call below fails its argument checks first
-    return _lib.RasterCfg(image_height=H, image_width=W, tanfovx=0.5, tanfovy=0.5, scale_modifier=1.0, prefiltered=0,
-                          debug=0, viewmatrix=fake, projmatrix=fake, campos=fake, bg=fake)
-
-
 def _render_geom(cfg=None, P=1, R=1, geom=P1, bin_ws=P1, img=P1, img_bytes=1 << 30, geom_bytes=1 << 30, bin_bytes=1 << 30,
                  dist=P1, med=P1, mid=P1, mom=P1):
     from contextgs_amd import _lib
     L = _lib.lib()
-    rc = L.cgs_raster_render_geom(C.byref(cfg or _cfg()), P, R, geom, geom_bytes, bin_ws, bin_bytes, img, img_bytes, dist, med,
+    rc = L.cgs_raster_render_geom(C.byref(cfg or fake_cfg()), P, R, geom, geom_bytes, bin_ws, bin_bytes, img, img_bytes, dist, med,
                                   mid, mom, None)
     return rc, L.cgs_last_error().decode()
 
@@ -109,7 +103,7 @@ def _backward_geom(P=1, R=0, geom=P1, img=P1, scratch=P1, scratch_bytes=1 << 40,
     """colours + scales / rotations, no features, every other pointer given"""
     from contextgs_amd import _lib
     L = _lib.lib()
-    rc = L.cgs_raster_backward_geom(C.byref(_cfg()), P, R, P1, P1, None, 0, 0, P1, P1, P1, None, P1, geom, 1 << 30, bin_ws,
+    rc = L.cgs_raster_backward_geom(C.byref(fake_cfg()), P, R, P1, P1, None, 0, 0, P1, P1, P1, None, P1, geom, 1 << 30, bin_ws,
                                     1 << 40 if bin_ws else 0, img, 1 << 30, None, None, None, None, P1, m2, P1, P1, None, P1, P1,
                                     None, scratch, scratch_bytes, None, opts, None, 0, None, None, moments, median_id, g_dist, g_med)
     return rc, L.cgs_last_error().decode()
@@ -136,7 +130,7 @@ def test_render_geom_argument_errors():
     for kw in (dict(P=-1), dict(R=-1)):
         rc, msg = _render_geom(**kw)
         assert rc == CGS_ERR_ARG and "P < 0 or R < 0" in msg and fn in msg, (kw, msg)
-    rc, msg = _render_geom(cfg=_cfg(H=0))
+    rc, msg = _render_geom(cfg=fake_cfg(H=0))
     assert rc == CGS_ERR_ARG and "image size" in msg
     for kw, needle in ((dict(img_bytes=16), "image workspace too small"), (dict(geom_bytes=16), "geometry workspace too small"),
                        (dict(bin_bytes=16), "binning workspace too small")):

@@ -1,21 +1,20 @@
 """GPU checks of the rasterizer's depth-distortion and median-depth maps (`return_geometry=True`, csrc/raster_geom_maps.hip)
 against the existing oracle, unchanged, used as a per-pixel decomposition (tests/raster_geom_ref.py has the reference).
 
-Scenes: the four decomposed scenes of tests/test_raster_contrib_gpu.py, restated: `ragged` (200 Gaussians at 40x24: 3x2 tiles,
-ragged right and bottom edges, some Gaussians behind the near plane), `single` (1 Gaussian at 64x48), `long` (700 faint
-Gaussians over one 16x16 tile: the lists cross the 256-entry batch boundary twice and no pixel stops early), `saturated` (300
-near-opaque Gaussians over one tile: early stops and the 0.99 cap).
+Scenes: the four named scenes of tests/raster_harness.py: `ragged` (200 Gaussians at 40x24: 3x2 tiles, ragged right and bottom
+edges, some Gaussians behind the near plane), `single` (1 Gaussian at 64x48), `long` (700 faint Gaussians over one 16x16 tile:
+the lists cross the 256-entry batch boundary twice and no pixel stops early), `saturated` (300 near-opaque Gaussians over one
+tile: early stops and the 0.99 cap).
 
-Tolerances.  `distortion`, `median_depth`: `_check_map` (a copy): RMSE <= 1e-5 of the map's maximum and at most a 1e-4 share
-of values beyond 2e-5.  `median_id` must be equal, and `median_depth` is compared, on every pixel whose reference margin to
-0.5 (raster_geom_ref.geom_maps) exceeds 1e-4; at most 1 % of the pixels may be excluded that way.  Gradients: `_check_grad` (a
-copy): at most a 2e-3 share of entries beyond 2e-4 of the tensor's maximum.  These caps are conditions, not measurements: every
+Tolerances.  `distortion`, `median_depth`: `check_map` of tests/raster_harness.py: RMSE <= 1e-5 of the map's maximum and at most
+a 1e-4 share of values beyond 2e-5.  `median_id` must be equal, and `median_depth` is compared, on every pixel whose reference
+margin to 0.5 (raster_geom_ref.geom_maps) exceeds 1e-4; at most 1 % of the pixels may be excluded that way.  Gradients:
+`check_grad`: at most a 2e-3 share of entries beyond 2e-4 of the tensor's maximum.  These caps are conditions, not measurements: every
 scene was first run on the CPU with the fp32 oracle's decomposition and gradients against the fp64 oracle's under the same
 checks at cap = 0.5 (`fp32_oracle_within_half_caps` below is that run), and kept only because the fp32 oracle alone stays
 within HALF of every cap; a scene that does not gets another seed, never another cap.
 References are computed once per scene and shared; nobody writes into them.
 """
-import functools
 import itertools
 import math
 
@@ -25,64 +24,19 @@ import torch
 
 import raster_geom_ref as ref
 from contextgs_amd.synth import look_at_camera, random_gaussians
+from raster_harness import BG, check_grad, check_map, cov6_torch, leaf, memo, model, named_scene, np_of, run, scene, settings, shs
 
 pytestmark = pytest.mark.gpu
 
-BG = (0.1, 0.25, 0.4)
 GRAD_TOL = 2e-4
 AUX = ("depth", "invdepth", "alpha")
-
-
-# ---- scenes (the decomposed scenes of tests/test_raster_contrib_gpu.py, restated) ----------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _scene(P, W, H, seed, extent=1.0, srange=(0.005, 0.05), eye=(0.4, -2.2, 0.6)):
-    cam = look_at_camera(eye, (0, 0, 0), W, H, fovx_deg=60.0)
-    g = random_gaussians(P, seed=seed, extent=extent, scale_lo=srange[0], scale_hi=srange[1])
-    if P >= 20:     # some Gaussians behind the near plane
-        e = np.array([0.4, -2.2, 0.6], dtype=np.float32)
-        g["means3D"][::20] = e + 0.3 * (e - g["means3D"][::20])
-    return cam, g
-
-
-@functools.lru_cache(maxsize=None)
-def _stack_scene(kind, W=16, H=16):
-    """saturated: 300 nearly opaque, wide Gaussians.  long: 700 faint, wide ones.  Both in front of a one-tile image."""
-    cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), W, H, fovx_deg=50.0)
-    if kind == "saturated":
-        rng = np.random.default_rng(11)
-        g = random_gaussians(300, seed=11, extent=0.2, scale_lo=0.15, scale_hi=0.4)
-        g["opacities"][:] = rng.uniform(0.9, 0.999, size=g["opacities"].shape).astype(np.float32)
-    else:
-        rng = np.random.default_rng(12)
-        g = random_gaussians(700, seed=12, extent=0.2, scale_lo=0.15, scale_hi=0.4)
-        g["opacities"][:] = rng.uniform(0.005, 0.02, size=g["opacities"].shape).astype(np.float32)
-    return cam, g
-
-
-def decomposed_scene(name):
-    if name == "ragged":
-        return _scene(200, 40, 24, 3, 1.0, (0.02, 0.12))
-    if name == "single":
-        return _scene(1, 64, 48, 1)
-    return _stack_scene(name)
-
-
 DECOMPOSED = ("ragged", "long", "saturated", "single")
 LOSSES = ("distortion", "median", "both", "everything")
-
-_REFS = {}
-
-
-def _ref(key, make):
-    """References are computed once and shared; nobody writes into them."""
-    if key not in _REFS:
-        _REFS[key] = make()
-    return _REFS[key]
 
 
 def _weights(name):
     """The upstream gradients of a scene: random normal, fixed per scene."""
-    cam, _ = decomposed_scene(name)
+    cam, _ = named_scene(name)
     H, W = cam.image_height, cam.image_width
     rng = np.random.default_rng(100 + DECOMPOSED.index(name))
     return {"distortion": rng.normal(size=(1, H, W)).astype(np.float32),
@@ -93,7 +47,7 @@ def _weights(name):
 
 def reference(oracle, name):
     """{"dec", "maps", "z", "grads": {"distortion", "median", "colour+aux"} -> per-input gradients} from one oracle."""
-    cam, g = decomposed_scene(name)
+    cam, g = named_scene(name)
     H, W = cam.image_height, cam.image_width
     wts = _weights(name)
     dec = ref.decompose(oracle, cam, g)
@@ -127,48 +81,21 @@ def grads_of(R, loss):
     return {k: sum(R["grads"][p][k] for p in parts) for k in ref.GRAD_KEYS}
 
 
-def _np(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def _check_map(a, b, what, cap=1.0):
-    a = _np(a).astype(np.float32).reshape(-1)
-    b = np.asarray(b, dtype=np.float32).reshape(-1)
-    scale = max(float(np.abs(b).max()), 1e-12)
-    d = np.abs(a - b) / scale
-    rmse = float(np.sqrt((d ** 2).mean()))
-    n_out = int((d > 2e-5).sum())
-    print(f"[allowance] {what}: rmse {rmse:.2e}, {n_out} of {d.size} values beyond 2e-5 of the max {scale:.3g}, worst {d.max():.2e}")
-    assert rmse <= 1e-5 * cap, (what, rmse)
-    assert n_out <= 1e-4 * cap * d.size, (what, n_out, float(d.max()))
-
-
-def _check_grad(a, b, what, allow_frac=2e-3, tol=2e-4):
-    a = _np(a).astype(np.float32)
-    a = a.reshape(a.shape[0], -1)
-    b = np.asarray(b, dtype=np.float32).reshape(a.shape)
-    scale = max(1e-6, float(np.abs(b).max()))
-    err = np.abs(a - b) / scale
-    n_out = int((err > tol).sum())
-    print(f"[allowance] {what}: {n_out} of {err.size} entries beyond {tol:g} of the maximum, worst {err.max():.2e}")
-    assert n_out <= allow_frac * err.size, (what, n_out, float(err.max()))
-
-
 def check_forward(got, maps, what, cap=1.0):
     """got: {"distortion", "median_depth", "median_id"} as arrays; maps: geom_maps() of the fp64 decomposition."""
-    _check_map(got["distortion"], maps["distortion"], f"distortion {what}", cap=cap)
+    check_map(got["distortion"], maps["distortion"], f"distortion {what}", cap=cap)
     decided = maps["margin"] > 1e-4
     print(f"[allowance] median {what}: {int((~decided).sum())} of {decided.size} pixels are within 1e-4 of the crossing")
     assert (~decided).mean() <= 1e-2 * cap, (what, int((~decided).sum()))
-    a, b = _np(got["median_id"]).reshape(-1), maps["median_id"].reshape(-1)
+    a, b = np_of(got["median_id"]).reshape(-1), maps["median_id"].reshape(-1)
     assert (a[decided] == b[decided]).all(), (what, int((a[decided] != b[decided]).sum()))
-    md = np.where(decided, _np(got["median_depth"]).reshape(-1), maps["median_depth"])
-    _check_map(md, maps["median_depth"], f"median_depth {what}", cap=cap)
+    md = np.where(decided, np_of(got["median_depth"]).reshape(-1), maps["median_depth"])
+    check_map(md, maps["median_depth"], f"median_depth {what}", cap=cap)
 
 
 def check_grads(got, want, what, cap=1.0):
     for k in ref.GRAD_KEYS:
-        _check_grad(np.asarray(got[k]).reshape(want[k].shape[0], -1), want[k], f"d{k} {what}", allow_frac=2e-3 * cap)
+        check_grad(np.asarray(got[k]).reshape(want[k].shape[0], -1), want[k], f"d{k} {what}", allow_frac=2e-3 * cap)
 
 
 def fp32_oracle_within_half_caps(oracle32, oracle64, name):
@@ -180,40 +107,10 @@ def fp32_oracle_within_half_caps(oracle32, oracle64, name):
 
 
 # ---- running the rasterizer --------------------------------------------------------------------------------------------------
-def _settings(cam, bg=BG, D=1, debug=False, aa=False, view=None, proj=None):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    c = cam.to_torch("cuda")
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.tensor(bg, dtype=torch.float32, device="cuda"), scale_modifier=1.0,
-        viewmatrix=c.world_view_transform if view is None else view,
-        projmatrix=c.full_proj_transform if proj is None else proj, sh_degree=D, campos=c.camera_center,
-        prefiltered=False, debug=debug, antialiasing=aa)
-
-
-def _leaf(a):
-    return torch.tensor(a, device="cuda", requires_grad=True)
-
-
-def _run(rs, g, loss_w=None, geometry=True, return_aux=False, absgrad=False, **kw):
-    """Forward (and backward of sum(out * w) over the entries of loss_w)."""
-    from contextgs_amd.rasterizer import GaussianRasterizer
-    P = g["means3D"].shape[0]
-    t = {k: _leaf(v) for k, v in g.items()}
-    m2 = torch.zeros(P, 4 if absgrad else 3, device="cuda", requires_grad=True)
+def _run(rs, g, geometry=True, absgrad=False, **kw):
+    """raster_harness.run with return_geometry=True unless `geometry` is False, and a [P,4] means2D with absgrad."""
     more = dict(return_geometry=True) if geometry else {}
-    res = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"],
-                                 scales=t["scales"], rotations=t["rotations"], return_aux=return_aux, absgrad=absgrad, **more, **kw)
-    out = {"color": res[0], "radii": res[1]}
-    if len(res) > 2:
-        out.update(res[2])
-    if loss_w:
-        sum(((out[k] * torch.as_tensor(w, device="cuda")).sum() for k, w in loss_w.items())).backward()
-    torch.cuda.synchronize()
-    o = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in out.items()}
-    o["grad"] = {k: (None if v.grad is None else v.grad.detach()) for k, v in t.items()}
-    o["grad"]["means2D"] = m2.grad
-    return o
+    return run(rs, g, means2D_cols=4 if absgrad else 3, absgrad=absgrad, **more, **kw)
 
 
 def _loss_w(name, loss):
@@ -235,16 +132,16 @@ def _check_shapes(out, P, H, W):
 # ---- forward -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", DECOMPOSED)
 def test_forward_matches_the_fp64_decomposition(oracle64, name):
-    cam, g = decomposed_scene(name)
+    cam, g = named_scene(name)
     P, H, W = g["means3D"].shape[0], cam.image_height, cam.image_width
-    R = _ref(("ref", name), lambda: reference(oracle64, name))
+    R = memo(("geom", "ref", name), lambda: reference(oracle64, name))
     dec = R["dec"]
     if name == "long":
         tiles = ((H + 15) // 16) * ((W + 15) // 16)
         assert int(dec["stats"][0]) / tiles > 512 and int(dec["stats"][1]) / tiles > 256     # beyond two 256-entry batches
     if name == "saturated":
         assert float(dec["final_T"].min()) < 1e-3              # pixels stop early: later entries must count nothing
-    rs = _settings(cam, debug=(name == "single"))
+    rs = settings(cam, debug=(name == "single"))
     out = _run(rs, g, return_aux=True)
     plain = _run(rs, g, geometry=False, return_aux=True)
     assert torch.equal(out["color"], plain["color"]) and torch.equal(out["radii"], plain["radii"])
@@ -265,13 +162,13 @@ def test_forward_matches_the_fp64_decomposition(oracle64, name):
 @pytest.mark.parametrize("loss", LOSSES)
 @pytest.mark.parametrize("name", DECOMPOSED)
 def test_backward_matches_the_reference(oracle64, name, loss):
-    cam, g = decomposed_scene(name)
-    R = _ref(("ref", name), lambda: reference(oracle64, name))
-    out = _run(_settings(cam), g, loss_w=_loss_w(name, loss), return_aux=(loss == "everything"))
+    cam, g = named_scene(name)
+    R = memo(("geom", "ref", name), lambda: reference(oracle64, name))
+    out = _run(settings(cam), g, loss_w=_loss_w(name, loss), return_aux=(loss == "everything"))
     want = grads_of(R, loss)
     if loss != "everything":
         assert out["grad"]["colors"] is None          # the new maps send nothing to the colour inputs
-    got = {k: _np(out["grad"][k]) for k in ref.GRAD_KEYS}
+    got = {k: np_of(out["grad"][k]) for k in ref.GRAD_KEYS}
     if name != "single" or loss == "everything":      # (one Gaussian: no distortion, and its opacity does not reach one half)
         assert max(float(np.abs(want[k]).max()) for k in ref.GRAD_KEYS) > 0
     check_grads(got, want, f"{name} {loss}")
@@ -279,55 +176,54 @@ def test_backward_matches_the_reference(oracle64, name, loss):
 
 def test_absgrad_takes_the_share_in_the_signed_columns_only(oracle64):
     name = "ragged"
-    cam, g = decomposed_scene(name)
-    R = _ref(("ref", name), lambda: reference(oracle64, name))
+    cam, g = named_scene(name)
+    R = memo(("geom", "ref", name), lambda: reference(oracle64, name))
     lw = _loss_w(name, "both")
-    out = _run(_settings(cam), g, loss_w=lw, absgrad=True)
-    m2 = _np(out["grad"]["means2D"])
+    out = _run(settings(cam), g, loss_w=lw, absgrad=True)
+    m2 = np_of(out["grad"]["means2D"])
     assert m2.shape == (g["means3D"].shape[0], 4) and (m2[:, 2:] == 0).all()      # the colour image got no gradient
     want = grads_of(R, "both")
-    _check_grad(m2[:, :2], want["means2D"][:, :2], "dmeans2D[:, :2] with absgrad")
+    check_grad(m2[:, :2], want["means2D"][:, :2], "dmeans2D[:, :2] with absgrad")
     lw = _loss_w(name, "everything")
-    out = _run(_settings(cam), g, loss_w=lw, absgrad=True, return_aux=True)
-    colour_only = _run(_settings(cam), g, loss_w={"color": lw["color"]}, absgrad=True, geometry=False)
-    _check_grad(_np(out["grad"]["means2D"])[:, 2:], _np(colour_only["grad"]["means2D"])[:, 2:], "absolute columns")
-    _check_grad(_np(out["grad"]["means2D"])[:, :2], grads_of(R, "everything")["means2D"][:, :2], "signed columns, everything")
+    out = _run(settings(cam), g, loss_w=lw, absgrad=True, return_aux=True)
+    colour_only = _run(settings(cam), g, loss_w={"color": lw["color"]}, absgrad=True, geometry=False)
+    check_grad(np_of(out["grad"]["means2D"])[:, 2:], np_of(colour_only["grad"]["means2D"])[:, 2:], "absolute columns")
+    check_grad(np_of(out["grad"]["means2D"])[:, :2], grads_of(R, "everything")["means2D"][:, :2], "signed columns, everything")
 
 
 def test_cov3D_and_shs_form_against_the_plain_form():
     """cov3D_precomp built from the same scales / rotations and SH colours: the maps do not depend on the colour, so maps and
     gradients are those of the plain form; dL/dcov3D_precomp is chained back to scales / rotations by torch."""
     from contextgs_amd.rasterizer import GaussianRasterizer
-    from test_raster_sh_cov_gpu import _shs, cov6_torch
     name = "ragged"
-    cam, g = decomposed_scene(name)
+    cam, g = named_scene(name)
     P = g["means3D"].shape[0]
     lw = _loss_w(name, "both")
-    rs = _settings(cam, D=2)
+    rs = settings(cam, D=2)
     plain = _run(rs, g, loss_w=lw)
-    t = {k: _leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations")}
-    sh = _leaf(_shs(P, 9, seed=5))
+    t = {k: leaf(g[k]) for k in ("means3D", "opacities", "scales", "rotations")}
+    sh = leaf(shs(P, 9, seed=5))
     m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
     color, radii, ex = GaussianRasterizer(rs)(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], shs=sh,
                                               cov3D_precomp=cov6_torch(t["scales"], t["rotations"], 1.0), return_geometry=True)
     sum((ex[k] * torch.as_tensor(w, device="cuda")).sum() for k, w in lw.items()).backward()
     torch.cuda.synchronize()
     assert torch.equal(radii, plain["radii"]) and sh.grad is None
-    _check_map(ex["distortion"], _np(plain["distortion"]), "distortion, shs + cov3D vs plain")
+    check_map(ex["distortion"], np_of(plain["distortion"]), "distortion, shs + cov3D vs plain")
     same = (ex["median_id"] == plain["median_id"])
     assert float(same.float().mean()) >= 0.99
-    _check_map(torch.where(same, ex["median_depth"][0], plain["median_depth"][0]), _np(plain["median_depth"]),
+    check_map(torch.where(same, ex["median_depth"][0], plain["median_depth"][0]), np_of(plain["median_depth"]),
                "median_depth, shs + cov3D vs plain")
     for k in ("means3D", "opacities", "scales", "rotations"):
-        _check_grad(t[k].grad, _np(plain["grad"][k]), f"d{k}, shs + cov3D vs plain")
-    _check_grad(m2.grad, _np(plain["grad"]["means2D"]), "dmeans2D, shs + cov3D vs plain")
+        check_grad(t[k].grad, np_of(plain["grad"][k]), f"d{k}, shs + cov3D vs plain")
+    check_grad(m2.grad, np_of(plain["grad"]["means2D"]), "dmeans2D, shs + cov3D vs plain")
 
 
 def test_antialiasing_against_opacities_premultiplied_by_h():
     """antialiasing=True against a plain call whose opacities are opacity * h, h computed in numpy fp64 (Gaussians large and
     small: h ranges well below 1).  Maps equal; dL/dopacity = h dL/d(opacity h); means2D gets nothing from h."""
     name = "ragged"
-    cam, g = decomposed_scene(name)
+    cam, g = named_scene(name)
     lw = _loss_w(name, "both")
     V = np.asarray(cam.world_view_transform, np.float32).astype(np.float64).reshape(4, 4)
     m, s, q = (g[k].astype(np.float64) for k in ("means3D", "scales", "rotations"))
@@ -348,18 +244,19 @@ def test_antialiasing_against_opacities_premultiplied_by_h():
     c2 = A @ Sigma @ A.transpose(0, 2, 1)
     a, b, c = c2[:, 0, 0], c2[:, 0, 1], c2[:, 1, 1]
     h = np.sqrt(np.maximum((a * c - b * b) / ((a + 0.3) * (c + 0.3) - b * b), 2.5e-5))
-    aa = _run(_settings(cam, aa=True), g, loss_w=lw)
+    aa = _run(settings(cam, aa=True), g, loss_w=lw)
     vis = aa["radii"].cpu().numpy() > 0
     assert float(h[vis].min()) < 0.5 and float(h[vis].max()) > 0.9           # h ~ 1 is not assumed
     g2 = dict(g)
     g2["opacities"] = (g["opacities"].astype(np.float64) * h[:, None]).astype(np.float32)
-    pre = _run(_settings(cam), g2, loss_w=lw)
-    _check_map(aa["distortion"], _np(pre["distortion"]), "distortion, antialiasing vs opacity * h")
+    pre = _run(settings(cam), g2, loss_w=lw)
+    check_map(aa["distortion"], np_of(pre["distortion"]), "distortion, antialiasing vs opacity * h")
     same = (aa["median_id"] == pre["median_id"])
     assert float(same.float().mean()) >= 0.99
-    _check_map(torch.where(same, aa["median_depth"], pre["median_depth"]), _np(pre["median_depth"]), "median_depth, antialiasing")
-    _check_grad(aa["grad"]["means2D"], _np(pre["grad"]["means2D"]), "dmeans2D, antialiasing vs opacity * h")
-    _check_grad(aa["grad"]["opacities"], _np(pre["grad"]["opacities"]) * h[:, None].astype(np.float32), "dopacities = h d(opacity h)")
+    check_map(torch.where(same, aa["median_depth"], pre["median_depth"]), np_of(pre["median_depth"]), "median_depth, antialiasing")
+    check_grad(aa["grad"]["means2D"], np_of(pre["grad"]["means2D"]), "dmeans2D, antialiasing vs opacity * h")
+    check_grad(aa["grad"]["opacities"], np_of(pre["grad"]["opacities"]) * h[:, None].astype(np.float32),
+               "dopacities = h d(opacity h)")
 
 
 # ---- the camera --------------------------------------------------------------------------------------------------------------
@@ -379,8 +276,8 @@ def test_viewmatrix_gradient_is_the_sum_the_per_gaussian_reference_implies(oracl
     The camera side is autograd through V = M V0, PM = M PM0 into the node's dL/dviewmatrix and dL/dprojmatrix."""
     from contextgs_amd.rasterizer import GaussianRasterizer
     name = "ragged"
-    cam, g = decomposed_scene(name)
-    R = _ref(("ref", name), lambda: reference(oracle64, name))
+    cam, g = named_scene(name)
+    R = memo(("geom", "ref", name), lambda: reference(oracle64, name))
     want = grads_of(R, "distortion")
     P = g["means3D"].shape[0]
     ref_k = float((g["means3D"].astype(np.float64) * want["means3D"]).sum() + (g["scales"].astype(np.float64) * want["scales"]).sum())
@@ -391,7 +288,7 @@ def test_viewmatrix_gradient_is_the_sum_the_per_gaussian_reference_implies(oracl
                     torch.cat([theta[1:], torch.ones(1, device="cuda")]).unsqueeze(0)], dim=0)
     V, PM = M4 @ c.world_view_transform, M4 @ c.full_proj_transform
     t = {k: torch.tensor(g[k], device="cuda") for k in ("means3D", "opacities", "scales", "rotations", "colors")}
-    color, radii, ex = GaussianRasterizer(_settings(cam, view=V, proj=PM))(
+    color, radii, ex = GaussianRasterizer(settings(cam, view=V, proj=PM))(
         means3D=t["means3D"], means2D=torch.zeros(P, 3, device="cuda"), opacities=t["opacities"], colors_precomp=t["colors"],
         scales=t["scales"], rotations=t["rotations"], return_geometry=True)
     (ex["distortion"] * torch.as_tensor(_weights(name)["distortion"], device="cuda")).sum().backward()
@@ -409,8 +306,8 @@ def test_without_a_gradient_on_the_new_maps_the_backward_is_the_old_one():
     the keyword.  The blend backward sums with float atomics, so bit-equality is asserted for every gradient that two plain
     calls reproduce bit for bit, and all of them stay within `_check_grad`."""
     P, W, H = 3000, 256, 256
-    cam, g = _scene(P, W, H, 1, 1.0, (0.003, 0.04))
-    rs = _settings(cam)
+    cam, g = scene(P, W, H, 1, 1.0, (0.003, 0.04))
+    rs = settings(cam)
     rng = np.random.default_rng(18)
     lw = {"color": rng.normal(size=(3, H, W)).astype(np.float32), "depth": rng.normal(size=(1, H, W)).astype(np.float32)}
     a = _run(rs, g, loss_w=lw, return_aux=True)
@@ -424,20 +321,20 @@ def test_without_a_gradient_on_the_new_maps_the_backward_is_the_old_one():
               f"{torch.equal(a['grad'][k], b['grad'][k])}")
         if fixed:
             assert torch.equal(a["grad"][k], b["grad"][k]), k
-        _check_grad(a["grad"][k], b["grad"][k].cpu().numpy(), f"d{k} with return_geometry vs without")
+        check_grad(a["grad"][k], b["grad"][k].cpu().numpy(), f"d{k} with return_geometry vs without")
     only = _run(rs, g, loss_w={"distortion": np.ones((1, H, W), np.float32)})
     assert only["grad"]["colors"] is None and float(only["grad"]["means3D"].abs().sum()) > 0
 
 
 def test_outputs_and_saved_tensors():
     from contextgs_amd.rasterizer import GaussianRasterizer
-    cam, g = _scene(2000, 128, 96, 7)
+    cam, g = scene(2000, 128, 96, 7)
     P = g["means3D"].shape[0]
-    t = {k: _leaf(v) for k, v in g.items()}
+    t = {k: leaf(v) for k, v in g.items()}
     m2 = torch.zeros(P, 3, device="cuda", requires_grad=True)
-    color, radii, ex = GaussianRasterizer(_settings(cam))(
+    color, radii, ex = GaussianRasterizer(settings(cam))(
         means3D=t["means3D"], means2D=m2, opacities=t["opacities"], colors_precomp=t["colors"], scales=t["scales"],
-        rotations=t["rotations"], return_geometry=True, return_aux=True, contrib=True, features=_leaf(np.ones((P, 2), np.float32)))
+        rotations=t["rotations"], return_geometry=True, return_aux=True, contrib=True, features=leaf(np.ones((P, 2), np.float32)))
     assert set(ex) >= {"distortion", "median_depth", "median_id", "depth", "top_id", "features"} and "moments" not in ex
     assert ex["median_id"].requires_grad is False and ex["median_id"].grad_fn is None
     for k in ("distortion", "median_depth", "depth", "features"):
@@ -449,7 +346,7 @@ def test_outputs_and_saved_tensors():
 
 def test_empty_view_and_no_gaussians():
     cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), 80, 64, fovx_deg=50.0)
-    rs = _settings(cam)
+    rs = settings(cam)
     g = random_gaussians(64, seed=6)
     g["means3D"][:, 1] -= 20.0                        # everything behind the camera
     for gg in (g, {k: v[:0] for k, v in g.items()}):
@@ -461,13 +358,6 @@ def test_empty_view_and_no_gaussians():
 
 
 # ---- render() ----------------------------------------------------------------------------------------------------------------
-def _model(N=20000, W=320, H=180):
-    from contextgs_amd.synth import SynthPipe, make_scene, orbit_cameras
-    pc = make_scene(N, seed=0)
-    cams = [c.to_torch("cuda") for c in orbit_cameras(4, W, H)]
-    return pc, cams, SynthPipe(), torch.zeros(3, device="cuda")
-
-
 def _render(pc, cam, pipe, bg, **kw):
     from contextgs_amd import ctx_ops
     from contextgs_amd.renderer import prefilter_voxel, render
@@ -478,7 +368,7 @@ def _render(pc, cam, pipe, bg, **kw):
 
 
 def test_render_returns_the_maps_and_the_backward_reaches_the_anchors():
-    pc, cams, pipe, bg = _model()
+    pc, cams, pipe, bg = model()
     pc.train(True)
     with torch.enable_grad():
         plain, _ = _render(pc, cams[1], pipe, bg)

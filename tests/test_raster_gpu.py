@@ -13,26 +13,16 @@ import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera, orbit_cameras, random_gaussians
+from raster_harness import settings
 
 pytestmark = pytest.mark.gpu
-
-
-def _settings(cam, bg, scale_modifier=1.0, debug=False):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    c = cam.to_torch("cuda")
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width,
-        tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5),
-        bg=torch.tensor(bg, dtype=torch.float32, device="cuda"), scale_modifier=scale_modifier,
-        viewmatrix=c.world_view_transform, projmatrix=c.full_proj_transform, sh_degree=1,
-        campos=c.camera_center, prefiltered=False, debug=debug)
 
 
 def _run_gpu(cam, g, bg, w=None, scale_modifier=1.0):
     from contextgs_amd.rasterizer import GaussianRasterizer
     t = {k: torch.tensor(v, device="cuda", requires_grad=(w is not None)) for k, v in g.items()}
     means2D = torch.zeros_like(t["means3D"], requires_grad=(w is not None))
-    rast = GaussianRasterizer(_settings(cam, bg, scale_modifier, debug=True))
+    rast = GaussianRasterizer(settings(cam, bg=bg, scale_modifier=scale_modifier, debug=True))
     color, radii = rast(means3D=t["means3D"], means2D=means2D, shs=None, colors_precomp=t["colors"],
                         opacities=t["opacities"], scales=t["scales"], rotations=t["rotations"], cov3D_precomp=None)
     out = {"color": color.detach().cpu().numpy(), "radii": radii.cpu().numpy()}
@@ -138,7 +128,7 @@ def test_scale_modifier_and_all_culled(oracle32):
 def test_empty_input():
     from contextgs_amd.rasterizer import GaussianRasterizer
     cam = look_at_camera((0.0, -3.0, 0.0), (0, 0, 0), 32, 32)
-    rast = GaussianRasterizer(_settings(cam, (0.5, 0.5, 0.5)))
+    rast = GaussianRasterizer(settings(cam, bg=(0.5, 0.5, 0.5)))
     z = lambda *s: torch.zeros(*s, device="cuda")
     color, radii = rast(means3D=z(0, 3), means2D=z(0, 3), shs=None, colors_precomp=z(0, 3), opacities=z(0, 1),
                         scales=z(0, 3), rotations=z(0, 4), cov3D_precomp=None)
@@ -151,7 +141,7 @@ def test_visible_filter_matches_oracle(oracle32):
     cam = orbit_cameras(4, 160, 90)[1]
     g = random_gaussians(50000, seed=7, extent=4.0)     # many outside the frustum / behind the camera
     ref = oracle32.visible_filter(cam.oracle_dict(), g["means3D"], g["scales"], g["rotations"])
-    rast = GaussianRasterizer(_settings(cam, (0, 0, 0)))
+    rast = GaussianRasterizer(settings(cam, bg=(0, 0, 0)))
     got = rast.visible_filter(*(torch.tensor(g[k], device="cuda") for k in ["means3D", "scales", "rotations"]))
     got = got.cpu().numpy()
     assert 0 < (ref > 0).sum() < ref.size
@@ -251,7 +241,7 @@ def test_a_depth_beyond_the_27_bit_range_falls_back_to_the_32_bit_sort():
     t["means3D"][:far, 2] = torch.linspace(20000.0, 60000.0, far, device="cuda").flip(0)      # NOT in index order
     t["scales"][:far] = 1500.0
     t["opacities"][:far] = 0.6
-    rast = GaussianRasterizer(_settings(cam, (0.1, 0.2, 0.3)))
+    rast = GaussianRasterizer(settings(cam, bg=(0.1, 0.2, 0.3)))
 
     def run():
         return rast(means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), shs=None, colors_precomp=t["colors"],
@@ -279,7 +269,7 @@ def test_full_hd_properties():
     cam = orbit_cameras(8, 1920, 1080)[3]
     g = random_gaussians(400_000, seed=11, extent=1.0, scale_lo=0.001, scale_hi=0.01)
     t = {k: torch.tensor(v, device="cuda") for k, v in g.items()}
-    rast = GaussianRasterizer(_settings(cam, (0.0, 0.0, 0.0)))
+    rast = GaussianRasterizer(settings(cam, bg=(0.0, 0.0, 0.0)))
 
     def run(colors):
         return rast(means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), shs=None, colors_precomp=colors,

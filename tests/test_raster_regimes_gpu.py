@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from contextgs_amd.synth import look_at_camera
+from raster_harness import cov6_torch, settings
 from raster_units_ref import geom64 as _geom64, t_no_termination as _t_no_termination
 
 pytestmark = pytest.mark.gpu
@@ -428,30 +429,6 @@ def _kw(g):
                 rots=g["rotations"])
 
 
-def _settings(cam):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    c = cam.to_torch("cuda")
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.tensor(BG, dtype=torch.float32, device="cuda"), scale_modifier=1.0,
-        viewmatrix=c.world_view_transform, projmatrix=c.full_proj_transform, sh_degree=1, campos=c.camera_center,
-        prefiltered=False, debug=True)
-
-
-def quat_to_rot(q):
-    r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-    return torch.stack([
-        1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
-        2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
-        2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).view(-1, 3, 3)
-
-
-def cov6_torch(scales, rotations):
-    L = quat_to_rot(rotations) * scales[:, None, :]
-    S = L @ L.transpose(1, 2)
-    return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], dim=1)
-
-
 def _run_gpu(cam, g, w=None, cov=False):
     """forward (+ backward with dL/dimage = w) through the drop-in GaussianRasterizer with the image size's pair capacity
     reset (the first view of a size sorts with the count known on the host); returns numpy arrays and the pair count"""
@@ -467,7 +444,7 @@ def _run_gpu(cam, g, w=None, cov=False):
         kw.update(scales=t["scales"], rotations=t["rotations"])
     rz._pair_capacity.pop((H, W), None)
     try:
-        color, radii = rz.GaussianRasterizer(_settings(cam))(**kw)
+        color, radii = rz.GaussianRasterizer(settings(cam, debug=True))(**kw)
         R = int(rz.last_call["num_rendered"])
         out = {"color": color.detach().cpu().numpy(), "radii": radii.cpu().numpy(), "R": R}
         if grad:

@@ -70,7 +70,6 @@ tests/test_raster_gpu.py::test_backward_matches_oracle and all of tests/test_ras
       pass are the cov3D_precomp tests, whose scale gradient goes through torch and not through that line.
       The regimes' test_backward_matches_oracle passes; test_raster_gpu.py's fails in 1 of its cases, the fp64 test in 5.
 """
-import math
 import types
 
 import numpy as np
@@ -78,6 +77,7 @@ import pytest
 import torch
 
 import raster_units_ref as ru
+from raster_harness import cov6_torch, settings
 from raster_units_ref import UNITS_KERNEL, UNITS_LITERAL
 
 pytestmark = pytest.mark.gpu
@@ -93,17 +93,6 @@ def bin_mode(request):
     _lib.check(L.cgs_debug_set_bin_mode(0), "cgs_debug_set_bin_mode")
 
 
-def _settings(sc):
-    from contextgs_amd.rasterizer import GaussianRasterizationSettings
-    cam = sc.cam
-    c = cam.to_torch("cuda")
-    return GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.tensor(sc.bg, dtype=torch.float32, device="cuda"), scale_modifier=1.0,
-        viewmatrix=c.world_view_transform, projmatrix=c.full_proj_transform, sh_degree=1, campos=c.camera_center,
-        prefiltered=False, debug=False)
-
-
 def _run(sc, w, deterministic=False, absgrad=False, cov=False):
     """Forward and the backward of sum(image * w) on fresh leaves, with the image size's pair capacity reset (the first view of
     a size sorts with the count known on the host) -> numpy arrays under the reference's names."""
@@ -117,13 +106,12 @@ def _run(sc, w, deterministic=False, absgrad=False, cov=False):
     if absgrad:
         kw["absgrad"] = True
     if cov:
-        from test_raster_regimes_gpu import cov6_torch
         kw["cov3D_precomp"] = cov6_torch(t["scales"], t["rotations"])
     else:
         kw.update(scales=t["scales"], rotations=t["rotations"])
     rz._pair_capacity.pop((H, W), None)
     try:
-        image, radii = rz.GaussianRasterizer(_settings(sc))(**kw)
+        image, radii = rz.GaussianRasterizer(settings(sc.cam, bg=sc.bg))(**kw)
         (image * torch.tensor(w, device="cuda")).sum().backward()
         torch.cuda.synchronize()
     finally:

@@ -37,7 +37,7 @@ def main():
         raise SystemExit("sh_raster_micro: needs the GPU")
     from contextgs_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer
     from contextgs_amd.synth import look_at_camera, random_gaussians
-    from test_raster_sh_cov_gpu import cov6_torch, sh_eval_torch
+    from raster_harness import cov6_torch, sh_eval_torch
 
     P, W, H, D, M = a.P, a.W, a.H, 3, 16
     cam = look_at_camera((0.4, -2.2, 0.6), (0, 0, 0), W, H, fovx_deg=60.0)
