@@ -316,6 +316,10 @@ SIGNATURES = {
     "cgs_l1_ssim_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cgs_l1_ssim_finish": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "cgs_l1_ssim_bwd_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cgs_l1_ssim_w_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cgs_l1_ssim_w_finish": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "cgs_l1_ssim_w_bwd": (c_int, [c_void_p] * 8 + [c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cgs_l1_ssim_w_dexposure": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "cgs_reg_partials": (c_size_t, [c_int64]),
     "cgs_scaling_reg_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "cgs_scaling_reg_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

@@ -312,6 +312,388 @@ extern "C" int cgs_l1_ssim_bwd_loss(const float *img, const float *gt, const flo
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// The same loss with a per-pixel weight w [H][W] (masks) and a per-view 3x4 exposure E (upstream 3DGS's affine colour transform)
+// built in:  x'_c = sum_k x_k E[k][c] + E[c][3] where the patch is loaded,  L1 = sum w |x' - y| / (C S),  SSIM = sum w ssim / (C S),
+// S = sum w.  The window statistics see every pixel; the weight multiplies the SSIM MAP — and the three derivative maps the
+// forward saves, so the backward filters them as the plain one does.  Neither x' nor G = dL/dx' goes to HBM: with E the
+// backward workgroup walks the three channels of its tile, keeps dx_k = sum_c E[k][c] G_c of its SS_CB outputs in registers and
+// leaves per-workgroup partials of the 12 sums of dE, which a single-workgroup launch adds in a fixed order (no float atomics).
+// The plain kernels above are not touched: these are separate kernels with the same tile, filter and tap order.  (One inlined
+// body for both was tried: the plain instances then compile to other code — backward 80 -> 126 VGPRs, 1547 -> 1278 instructions,
+// the forward's schedule moves — because `__restrict__` on an inlined function's parameters is not what it is on a kernel's;
+// profiles/loss_weighted.txt has the table that shows the plain instances unchanged.)
+// HBM per pixel and channel: forward 8 + 12 B plus 4 / C B of weight, and 16 + 12 B with E (the patch reads all three channels);
+// backward 20 + 4 B plus 4 / C B of weight, the same with E (x_0..2 are read once per pixel for the three channels).
+__device__ __forceinline__ float ssim_expose(float x0, float x1, float x2, const float *__restrict__ E, int c) {
+    return fmaf(x2, E[8 + c], fmaf(x1, E[4 + c], x0 * E[c])) + E[4 * c + 3];
+}
+
+template <bool EXPO>
+__global__ void __launch_bounds__(256)
+    l1_ssim_w_fwd_kernel(const float *__restrict__ img, const float *__restrict__ gt, const float *__restrict__ wgt /* [H][W] or null */,
+                         const float *__restrict__ expo /* [3][4], EXPO */, int H, int W, SsimWin win,
+                         float *__restrict__ maps /* [3][C][H][W] or null */, float *__restrict__ partials /* [..][3] */) {
+    __shared__ float sx[SS_PY][SS_P + 1], sy[SS_PY][SS_P + 1];
+    __shared__ float hq[5][SS_PY][SS_T + 1];
+    __shared__ float red[4];
+    const int c = blockIdx.z, C = gridDim.z;
+    const int x0 = blockIdx.x * SS_T, y0 = blockIdx.y * SS_TY;
+    const int tid = threadIdx.x;
+    const size_t plane = (size_t)H * W;
+    const float *xi = img + c * plane, *yi = gt + c * plane;
+    {
+        constexpr int NL = (SS_PY * SS_P + 255) / 256;      // (all loads before the first LDS store: see the plain forward)
+        float vx[NL], vy[NL];
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            const int i = tid + 256 * k;
+            const int py = i / SS_P, px = i - py * SS_P;
+            const int gy = y0 + py - SS_R, gx = x0 + px - SS_R;
+            const bool in = i < SS_PY * SS_P && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            const size_t o = in ? (size_t)gy * W + gx : 0;
+            if constexpr (EXPO) vx[k] = in ? ssim_expose(img[o], img[plane + o], img[2 * plane + o], expo, c) : 0.f;   // the padding of x' is zero, not the bias
+            else vx[k] = in ? xi[o] : 0.f;
+            vy[k] = in ? yi[o] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            const int i = tid + 256 * k;
+            if (i < SS_PY * SS_P) {
+                const int py = i / SS_P, px = i - py * SS_P;
+                sx[py][px] = vx[k];
+                sy[py][px] = vy[k];
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < SS_PY * SS_NG; i += 256) {
+        const int r = i / SS_NG, col = 4 * (i - r * SS_NG);
+        float xv[SS_K + 3], yv[SS_K + 3];
+#pragma unroll
+        for (int k = 0; k < SS_K + 3; ++k) { xv[k] = sx[r][col + k]; yv[k] = sy[r][col + k]; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
+#pragma unroll
+            for (int k = 0; k < SS_K; ++k) {
+                const float x = xv[j + k], y = yv[j + k], w = win.w[k];
+                a0 += w * x; a1 += w * y; a2 += w * (x * x); a3 += w * (y * y); a4 += w * (x * y);
+            }
+            hq[0][r][col + j] = a0; hq[1][r][col + j] = a1; hq[2][r][col + j] = a2; hq[3][r][col + j] = a3; hq[4][r][col + j] = a4;
+        }
+    }
+    __syncthreads();
+    const int lx = tid & (SS_T - 1), ly0 = SS_CB * (tid / SS_T);
+    float mu1[SS_CB], mu2[SS_CB], e11[SS_CB], e22[SS_CB], e12[SS_CB];
+    {
+        float v[5][SS_K + SS_CB - 1];
+#pragma unroll
+        for (int q = 0; q < 5; ++q)
+#pragma unroll
+            for (int k = 0; k < SS_K + SS_CB - 1; ++k) v[q][k] = hq[q][ly0 + k][lx];
+#pragma unroll
+        for (int j = 0; j < SS_CB; ++j) {
+            float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, b4 = 0.f;
+#pragma unroll
+            for (int k = 0; k < SS_K; ++k) {
+                const float w = win.w[k];
+                b0 += w * v[0][j + k]; b1 += w * v[1][j + k]; b2 += w * v[2][j + k]; b3 += w * v[3][j + k]; b4 += w * v[4][j + k];
+            }
+            mu1[j] = b0; mu2[j] = b1; e11[j] = b2; e22[j] = b3; e12[j] = b4;
+        }
+    }
+    float m = 0.f, l1 = 0.f, ws = 0.f;
+#pragma unroll
+    for (int j = 0; j < SS_CB; ++j) {
+        const int ly = ly0 + j, gx = x0 + lx, gy = y0 + ly;
+        if (gx < W && gy < H) {
+            const float wp = wgt ? wgt[(size_t)gy * W + gx] : 1.f;
+            const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+            const float mu1_sq = mu1[j] * mu1[j], mu2_sq = mu2[j] * mu2[j], mu12 = mu1[j] * mu2[j];
+            const float s1 = e11[j] - mu1_sq, s2 = e22[j] - mu2_sq, s12 = e12[j] - mu12;
+            const float a1 = 2.f * mu12 + C1, a2 = 2.f * s12 + C2, b1 = mu1_sq + mu2_sq + C1, b2 = s1 + s2 + C2;
+            m += wp * ((a1 * a2) / (b1 * b2));
+            l1 += wp * fabsf(sx[ly + SS_R][lx + SS_R] - sy[ly + SS_R][lx + SS_R]);
+            ws += wp;
+            if (maps) {
+                const float inv = 1.f / (b1 * b2);
+                const float dm_ds1 = -(a1 * a2) * inv / b2;
+                const float dm_ds12 = 2.f * a1 * inv;
+                const float dm_dmu1 = (2.f * mu2[j] * a2 * b1 - 2.f * mu1[j] * a1 * a2) * inv / b1
+                                      - 2.f * mu1[j] * dm_ds1 - mu2[j] * dm_ds12;
+                const size_t o = (size_t)c * plane + (size_t)gy * W + gx, cs = (size_t)C * plane;
+                maps[o] = wp * dm_dmu1;
+                maps[cs + o] = wp * dm_ds1;
+                maps[2 * cs + o] = wp * dm_ds12;
+            }
+        }
+    }
+    const float sl = block_sum_256(l1, red);
+    __syncthreads();
+    const float sm = block_sum_256(m, red);
+    __syncthreads();
+    const float sw = block_sum_256(ws, red);
+    if (tid == 0) {
+        const size_t b = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        partials[3 * b] = sl;
+        partials[3 * b + 1] = sm;
+        partials[3 * b + 2] = sw;
+    }
+}
+
+// out3 = (loss, L1, SSIM) and inv_cs = 1 / (C S) for the backward, from the [np][3] partials: the third column adds up to C S (each
+// channel's workgroups sum the weights of their tile).  S == 0 is decided here, on the device: (0, 0, 1) and inv_cs = 0, which
+// with the all-zero weighted maps makes every gradient an exact zero.
+__global__ void __launch_bounds__(256)
+    l1_ssim_w_finish_kernel(const float *__restrict__ partials, int64_t np, float lam, float *__restrict__ out3, float *__restrict__ inv_cs) {
+    __shared__ double sh[3][4];
+    double a = 0.0, b = 0.0, s = 0.0;
+    for (int64_t i = threadIdx.x; i < np; i += 256) { a += (double)partials[3 * i]; b += (double)partials[3 * i + 1]; s += (double)partials[3 * i + 2]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); s += __shfl_xor(s, o); }
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = a; sh[1][threadIdx.x >> 6] = b; sh[2][threadIdx.x >> 6] = s; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double cs = sh[2][0] + sh[2][1] + sh[2][2] + sh[2][3];
+        const bool any = cs > 0.0;
+        const double inv = any ? 1.0 / cs : 0.0;
+        const float l1 = any ? (float)((sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3]) * inv) : 0.f;
+        const float ss = any ? (float)((sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3]) * inv) : 1.f;
+        out3[0] = (1.f - lam) * l1 + lam * (1.f - ss);
+        out3[1] = l1;
+        out3[2] = ss;
+        inv_cs[0] = (float)inv;
+    }
+}
+
+// G_c = g0 inv_cs w sign(x'_c - y_c) + g1 inv_cs (conv(A_c) + 2 x'_c conv(B_c) + y_c conv(Cc_c)) with the WEIGHTED maps A, B, Cc.
+// Without E: one channel per workgroup, dimg = G.  With E: the workgroup walks c = 0, 1, 2 of its tile, dimg_k = sum_c E[k][c] G_c,
+// dE_part [tile][3][4] = this tile's sums of x_k G_c (columns 0..2) and of G_c (column 3, row c).
+// (three waves per SIMD asked for: left alone the EXPO instance takes 219 VGPRs, two workgroups per CU; so it takes 150 without
+// a spill and three fit, the 38 KB of LDS allow four)
+template <bool EXPO>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
+    l1_ssim_w_bwd_kernel(const float *__restrict__ img, const float *__restrict__ gt, const float *__restrict__ wgt,
+                         const float *__restrict__ expo, const float *__restrict__ maps, const float *__restrict__ inv_cs,
+                         const float *__restrict__ g, const float *__restrict__ g_loss, float lam, int C, int H, int W, SsimWin win,
+                         float *__restrict__ dimg /* may be null with EXPO */, float *__restrict__ dE_part /* EXPO, may be null */) {
+    const float gl = g_loss ? g_loss[0] : 0.f;
+    const float inv_n = inv_cs[0];
+    const float g0 = ((g ? g[0] : 0.f) + gl * (1.f - lam)) * inv_n, g1 = ((g ? g[1] : 0.f) - gl * lam) * inv_n;
+    __shared__ float sm[3][SS_PY][SS_P + 1];
+    __shared__ float hq[3][SS_PY][SS_T + 1];
+    __shared__ float red[4][4];
+    const int x0 = blockIdx.x * SS_T, y0 = blockIdx.y * SS_TY;
+    const int tid = threadIdx.x;
+    const size_t plane = (size_t)H * W, cs = (size_t)C * plane;
+    const int lx = tid & (SS_T - 1), ly0 = SS_CB * (tid / SS_T);
+    const int gx = x0 + lx;
+    // what the thread's SS_CB outputs need of the pixel itself, once for all channels
+    float wv[SS_CB], xs[EXPO ? 3 : 1][SS_CB], dx[EXPO ? 3 : 1][SS_CB];
+#pragma unroll
+    for (int j = 0; j < SS_CB; ++j) {
+        const int gy = y0 + ly0 + j;
+        const bool in = gx < W && gy < H;
+        const size_t o = in ? (size_t)gy * W + gx : 0;
+        wv[j] = in ? (wgt ? wgt[o] : 1.f) : 0.f;
+#pragma unroll
+        for (int k = 0; k < (EXPO ? 3 : 1); ++k) {
+            xs[k][j] = in ? img[(EXPO ? k : (int)blockIdx.z) * plane + o] : 0.f;
+            dx[k][j] = 0.f;
+        }
+    }
+    const int c_first = EXPO ? 0 : blockIdx.z, c_end = EXPO ? 3 : c_first + 1;
+#pragma unroll 1
+    for (int c = c_first; c < c_end; ++c) {
+        // (a second trip stores to sm after every thread has passed the barrier behind the row pass, and to hq after the barrier
+        // behind these stores, which a thread reaches only with its column pass done)
+        {
+            constexpr int NL = (SS_PY * SS_P + 255) / 256;
+            float vm[NL][3];
+#pragma unroll
+            for (int k = 0; k < NL; ++k) {
+                const int i = tid + 256 * k;
+                const int py = i / SS_P, px = i - py * SS_P;
+                const int qy = y0 + py - SS_R, qx = x0 + px - SS_R;
+                const bool in = i < SS_PY * SS_P && qy >= 0 && qy < H && qx >= 0 && qx < W;
+                const size_t o = in ? (size_t)c * plane + (size_t)qy * W + qx : 0;
+#pragma unroll
+                for (int q = 0; q < 3; ++q) vm[k][q] = in ? maps[q * cs + o] : 0.f;
+            }
+#pragma unroll
+            for (int k = 0; k < NL; ++k) {
+                const int i = tid + 256 * k;
+                if (i < SS_PY * SS_P) {
+                    const int py = i / SS_P, px = i - py * SS_P;
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) sm[q][py][px] = vm[k][q];
+                }
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < SS_PY * SS_NG; i += 256) {
+            const int r = i / SS_NG, col = 4 * (i - r * SS_NG);
+            float v[3][SS_K + 3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+                for (int k = 0; k < SS_K + 3; ++k) v[q][k] = sm[q][r][col + k];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+                for (int k = 0; k < SS_K; ++k) {
+                    const float w = win.w[k];
+                    a0 += w * v[0][j + k]; a1 += w * v[1][j + k]; a2 += w * v[2][j + k];
+                }
+                hq[0][r][col + j] = a0; hq[1][r][col + j] = a1; hq[2][r][col + j] = a2;
+            }
+        }
+        __syncthreads();
+        float v[3][SS_K + SS_CB - 1];
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+#pragma unroll
+            for (int k = 0; k < SS_K + SS_CB - 1; ++k) v[q][k] = hq[q][ly0 + k][lx];
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};       // this channel's column of dE: sum x_k G_c (k = 0..2), sum G_c
+#pragma unroll
+        for (int j = 0; j < SS_CB; ++j) {
+            float cA = 0.f, cB = 0.f, cC = 0.f;
+#pragma unroll
+            for (int k = 0; k < SS_K; ++k) {
+                const float w = win.w[k];
+                cA += w * v[0][j + k]; cB += w * v[1][j + k]; cC += w * v[2][j + k];
+            }
+            const int gy = y0 + ly0 + j;
+            if (gx < W && gy < H) {
+                const size_t o = (size_t)c * plane + (size_t)gy * W + gx;
+                const float y = gt[o];
+                float x;
+                if constexpr (EXPO) x = ssim_expose(xs[0][j], xs[1][j], xs[2][j], expo, c);
+                else x = xs[0][j];
+                const float d = x - y;
+                const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+                const float G = g0 * (wv[j] * sgn) + g1 * (cA + 2.f * x * cB + y * cC);
+                if constexpr (EXPO) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        dx[k][j] = fmaf(expo[4 * k + c], G, dx[k][j]);
+                        acc[k] = fmaf(xs[k][j], G, acc[k]);
+                    }
+                    acc[3] += G;
+                } else {
+                    dimg[o] = G;
+                }
+            }
+        }
+        if constexpr (EXPO) {
+            if (dE_part) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                    for (int o = 32; o >= 1; o >>= 1) acc[e] += __shfl_xor(acc[e], o);
+                    if ((tid & 63) == 0) red[e][tid >> 6] = acc[e];
+                }
+                __syncthreads();       // (the next store to red comes two barriers later)
+                if (tid < 4) {
+                    const size_t t = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+                    dE_part[12 * t + (tid < 3 ? 4 * tid + c : 4 * c + 3)] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+                }
+            }
+        }
+    }
+    if constexpr (EXPO) {
+        if (dimg) {
+#pragma unroll
+            for (int j = 0; j < SS_CB; ++j) {
+                const int gy = y0 + ly0 + j;
+                if (gx < W && gy < H) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) dimg[k * plane + (size_t)gy * W + gx] = dx[k][j];
+                }
+            }
+        }
+    }
+}
+
+// dE [3][4] from the per-tile partials [nt][12]: one workgroup, a fixed order, double accumulators
+__global__ void __launch_bounds__(256)
+    l1_ssim_w_dexpo_finish_kernel(const float *__restrict__ part, int64_t nt, float *__restrict__ dE) {
+    __shared__ double sh[12][4];
+    double a[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) a[e] = 0.0;
+    for (int64_t i = threadIdx.x; i < nt; i += 256) {
+#pragma unroll
+        for (int e = 0; e < 12; ++e) a[e] += (double)part[12 * i + e];
+    }
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a[e] += __shfl_xor(a[e], o);
+        if ((threadIdx.x & 63) == 0) sh[e][threadIdx.x >> 6] = a[e];
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) dE[threadIdx.x] = (float)((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]));
+}
+
+static int l1_ssim_w_check(const char *who, int C, int H, int W, const void *exposure) {
+    if (C < 1 || H < 1 || W < 1) { cgs_set_error("%s: bad shape", who); return CGS_ERR_ARG; }
+    if (exposure && C != 3) { cgs_set_error("%s: an exposure needs C == 3, got %d", who, C); return CGS_ERR_ARG; }
+    return CGS_OK;
+}
+
+extern "C" int cgs_l1_ssim_w_fwd(const float *img, const float *gt, const float *weight, const float *exposure, int C, int H, int W,
+                                 float *maps, float *partials, void *stream) {
+    if (int rc = l1_ssim_w_check("l1_ssim_w_fwd", C, H, W, exposure)) return rc;
+    if (!img || !gt || !partials) { cgs_set_error("l1_ssim_w_fwd: NULL"); return CGS_ERR_ARG; }
+    static const SsimWin win = ssim_window();
+    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_TY - 1) / SS_TY, C);
+    CgsProfScope prof(CGS_PROF_LOSS_FWD, (hipStream_t)stream);
+    if (exposure)
+        hipLaunchKernelGGL(l1_ssim_w_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, img, gt, weight, exposure, H, W, win, maps, partials);
+    else
+        hipLaunchKernelGGL(l1_ssim_w_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, img, gt, weight, exposure, H, W, win, maps, partials);
+    CGS_CHECK_HIP(hipGetLastError());
+    return CGS_OK;
+}
+
+extern "C" int cgs_l1_ssim_w_finish(const float *partials, int C, int H, int W, float lam, float *out3, float *inv_cs, void *stream) {
+    if (C < 1 || H < 1 || W < 1 || !partials || !out3 || !inv_cs) { cgs_set_error("l1_ssim_w_finish: bad args"); return CGS_ERR_ARG; }
+    hipLaunchKernelGGL(l1_ssim_w_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials,
+                       (int64_t)cgs_l1_ssim_partials(C, H, W), lam, out3, inv_cs);
+    CGS_CHECK_HIP(hipGetLastError());
+    return CGS_OK;
+}
+
+extern "C" int cgs_l1_ssim_w_bwd(const float *img, const float *gt, const float *weight, const float *exposure, const float *maps,
+                                 const float *inv_cs, const float *g_loss, const float *g2, float lam, int C, int H, int W,
+                                 float *dimg, float *dexposure_partials, void *stream) {
+    if (int rc = l1_ssim_w_check("l1_ssim_w_bwd", C, H, W, exposure)) return rc;
+    if (!img || !gt || !maps || !inv_cs || (!g_loss && !g2) || (!dimg && !dexposure_partials)) { cgs_set_error("l1_ssim_w_bwd: NULL"); return CGS_ERR_ARG; }
+    if (!exposure && (dexposure_partials || !dimg)) { cgs_set_error("l1_ssim_w_bwd: dexposure_partials without an exposure"); return CGS_ERR_ARG; }
+    static const SsimWin win = ssim_window();
+    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_TY - 1) / SS_TY, exposure ? 1 : C);
+    CgsProfScope prof(CGS_PROF_LOSS_BWD, (hipStream_t)stream);
+    if (exposure)
+        hipLaunchKernelGGL(l1_ssim_w_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, img, gt, weight, exposure, maps, inv_cs, g2, g_loss,
+                           lam, C, H, W, win, dimg, dexposure_partials);
+    else
+        hipLaunchKernelGGL(l1_ssim_w_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, img, gt, weight, exposure, maps, inv_cs, g2, g_loss,
+                           lam, C, H, W, win, dimg, dexposure_partials);
+    CGS_CHECK_HIP(hipGetLastError());
+    return CGS_OK;
+}
+
+extern "C" int cgs_l1_ssim_w_dexposure(const float *dexposure_partials, int H, int W, float *dexposure, void *stream) {
+    if (H < 1 || W < 1 || !dexposure_partials || !dexposure) { cgs_set_error("l1_ssim_w_dexposure: bad args"); return CGS_ERR_ARG; }
+    hipLaunchKernelGGL(l1_ssim_w_dexpo_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, dexposure_partials,
+                       (int64_t)cgs_l1_ssim_partials(1, H, W), dexposure);
+    CGS_CHECK_HIP(hipGetLastError());
+    return CGS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // The two regularisers of the training loss next to the image terms (train.py:203,209):
 //     scaling_reg = scaling.prod(dim=1).mean()                 scaling [P,3], the visible Gaussians' scales
 //     mask_reg    = torch.mean(torch.sigmoid(gaussians._mask))

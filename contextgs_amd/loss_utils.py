@@ -6,6 +6,29 @@ of five grouped conv2d + ~15 element-wise passes each way.  `l1_ssim(image, gt)`
 single launch; `ssim` / `l1_loss` keep the reference's signatures.  `scaling_reg` and `mask_reg` are the two
 regularisers train.py:203,209 adds to the image terms, one launch each way (torch's `prod` backward reads a zero
 count back on the host in the middle of every backward).  Device tensors only: there is no CPU path.
+
+`training_image_loss(image, gt, lambda_dssim, *, weight=None, exposure=None)` is train.py:199-204 as one node.  With both
+keywords None it is the plain node: the same three launches and kernels.  Otherwise, still one node (`cgs_l1_ssim_w_*`), with
+x = image, y = gt, both [C,H,W]:
+
+  exposure  E, a float [3,4] device tensor that may require grad (needs C == 3; contextgs_amd/exposure.py holds one per view):
+            the loss is computed on  x'_c(p) = sum_k x_k(p) E[k,c] + E[c,3]  — upstream 3DGS's convention,
+            matmul(image.permute(1,2,0), E[:3,:3]).permute(2,0,1) + E[:3,3,None,None].  Nothing is clamped.  Without it x' = x.
+  weight    w, [H,W] or [1,H,W] on the device, float32 / fp16 / bf16 / bool (converted to float32 once), shared by the channels
+            (a mask, or a soft per-pixel weight).  With S = sum_p w_p:
+                L1   = sum_{c,p} w_p |x'_c(p) - y_c(p)| / (C S)
+                SSIM = sum_{c,p} w_p ssim_c(p) / (C S)
+                loss = (1 - lambda) L1 + lambda (1 - SSIM)
+            ssim_c(p) is the SSIM map of (x', y) as ever: same window, zero padding and tap order.  A window's statistics see
+            every pixel, weighted or not — the weight applies to the MAP, not to the inputs — so a pixel of weight 0 within
+            five pixels of a weighted one does receive an SSIM gradient, and exactly none from L1.  A weighted mean keeps the
+            image term on one scale whatever the mask's area (it is added to lambda_e * bits).  Without it w = 1, S = H W.
+            S == 0 returns (0, 0, 1) and exact zero gradients, decided on the device.  Negative or non-finite weights are the
+            caller's error (checking would need a host read); a weight that requires grad raises NotImplementedError.
+  gradients with G_c(p) = dL/dx'_c(p):  dL/dx_k(p) = sum_c E[k,c] G_c(p),  dL/dE[k,c] = sum_p x_k(p) G_c(p),
+            dL/dE[c,3] = sum_p G_c(p); any of loss, L1, SSIM may have received a gradient.  Neither x' nor G is written to
+            memory; the 12 sums of dE are per-workgroup partials added in a fixed order by a single-workgroup launch (no float
+            atomics), so two runs are bit-identical.  Launches: forward 2, backward 1, or 2 when the exposure requires grad.
 """
 from __future__ import annotations
 
@@ -121,14 +144,106 @@ class _TrainImageLoss(torch.autograd.Function):
         return dimg, None, None
 
 
-def training_image_loss(image, gt, lambda_dssim: float = 0.2):
-    """((1 - lambda) L1 + lambda (1 - SSIM), L1, SSIM) of train.py:199-204 from one node (three launches per training step)."""
+class _TrainImageLossWeighted(torch.autograd.Function):
+    """_TrainImageLoss with a per-pixel weight and / or a per-view exposure (module docstring): still one node — the forward kernel
+    and its finish (which leaves 1 / (C S) on the device), one backward launch, and the 12 sums of dE from per-tile partials by a
+    single-workgroup launch when the exposure asks for a gradient.  `w` is float32 [H,W] or None, `E` float32 [3,4] or None."""
+
+    @staticmethod
+    def forward(ctx, img, gt, lam, w, E):
+        _refuse_target_grad(ctx, "training_image_loss")
+        _lib.require_device(img, gt, w, E)
+        x = img if (img.dtype == torch.float32 and img.is_contiguous()) else img.float().contiguous()
+        y = gt if (gt.dtype == torch.float32 and gt.is_contiguous()) else gt.float().contiguous()
+        e = None if E is None else (E if (E.dtype == torch.float32 and E.is_contiguous()) else E.float().contiguous())
+        C, H, W = x.shape
+        L = _lib.lib()
+        need_x, need_e = ctx.needs_input_grad[0], e is not None and ctx.needs_input_grad[4]
+        maps = torch.empty(3, C, H, W, dtype=torch.float32, device=x.device) if (need_x or need_e) else None
+        partials = torch.empty(int(L.cgs_l1_ssim_partials(C, H, W)), 3, dtype=torch.float32, device=x.device)
+        st = _lib.current_stream()
+        _lib.check(L.cgs_l1_ssim_w_fwd(_lib.ptr(x), _lib.ptr(y), _lib.ptr(w), _lib.ptr(e), C, H, W, _lib.ptr(maps), _lib.ptr(partials), st),
+                   "cgs_l1_ssim_w_fwd")
+        out3 = torch.empty(3, dtype=torch.float32, device=x.device)
+        inv_cs = torch.empty(1, dtype=torch.float32, device=x.device)
+        _lib.check(L.cgs_l1_ssim_w_finish(_lib.ptr(partials), C, H, W, float(lam), _lib.ptr(out3), _lib.ptr(inv_cs), st), "cgs_l1_ssim_w_finish")
+        if maps is not None:
+            ctx.save_for_backward(x, y, maps, inv_cs, w, e)
+        ctx.lam, ctx.need_x, ctx.need_e = float(lam), need_x, need_e
+        ctx.e_like = None if E is None else (E.shape, E.dtype)
+        ctx.set_materialize_grads(False)
+        return out3[0], out3[1], out3[2]
+
+    @staticmethod
+    def backward(ctx, g_loss, g_l1, g_ssim):
+        x, y, maps, inv_cs, w, e = ctx.saved_tensors
+        C, H, W = x.shape
+        g2 = None
+        if g_l1 is not None or g_ssim is not None:
+            z = torch.zeros((), dtype=torch.float32, device=x.device)
+            g2 = torch.stack([z if g_l1 is None else g_l1.float().reshape(()), z if g_ssim is None else g_ssim.float().reshape(())])
+        if g_loss is None and g2 is None:
+            return None, None, None, None, None
+        gl = None if g_loss is None else g_loss.float().reshape(1).contiguous()
+        L = _lib.lib()
+        st = _lib.current_stream()
+        dimg = torch.empty_like(x) if ctx.need_x else None
+        part = torch.empty(int(L.cgs_l1_ssim_partials(1, H, W)), 12, dtype=torch.float32, device=x.device) if ctx.need_e else None
+        _lib.check(L.cgs_l1_ssim_w_bwd(_lib.ptr(x), _lib.ptr(y), _lib.ptr(w), _lib.ptr(e), _lib.ptr(maps), _lib.ptr(inv_cs), _lib.ptr(gl),
+                                       _lib.ptr(g2), ctx.lam, C, H, W, _lib.ptr(dimg), _lib.ptr(part), st), "cgs_l1_ssim_w_bwd")
+        dE = None
+        if ctx.need_e:
+            dE = torch.empty(3, 4, dtype=torch.float32, device=x.device)
+            _lib.check(L.cgs_l1_ssim_w_dexposure(_lib.ptr(part), H, W, _lib.ptr(dE), st), "cgs_l1_ssim_w_dexposure")
+            dE = dE.reshape(ctx.e_like[0]).to(ctx.e_like[1])
+        return dimg, None, None, None, dE
+
+
+def _loss_weight(weight, H, W, image):
+    """The float32 contiguous [H,W] form of a [H,W] / [1,H,W] weight, checked without touching the device."""
+    if not isinstance(weight, torch.Tensor) or tuple(weight.shape) not in ((H, W), (1, H, W)):
+        raise ValueError(f"training_image_loss: weight must be a [{H},{W}] or [1,{H},{W}] tensor, got "
+                         f"{tuple(weight.shape) if isinstance(weight, torch.Tensor) else type(weight).__name__}")
+    if weight.requires_grad:
+        raise NotImplementedError("training_image_loss: `weight` requires grad, but the fused loss differentiates the image and the "
+                                  "exposure only; detach the weight")
+    if not (weight.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.bool)):
+        raise ValueError(f"training_image_loss: weight must be float32, float16, bfloat16 or bool, got {weight.dtype}")
+    if weight.device != image.device:
+        raise ValueError(f"training_image_loss: weight on {weight.device}, image on {image.device}")
+    return weight.reshape(H, W).to(torch.float32).contiguous()
+
+
+def _loss_exposure(exposure, C, image):
+    if not isinstance(exposure, torch.Tensor) or tuple(exposure.shape) != (3, 4) or not exposure.is_floating_point():
+        raise ValueError("training_image_loss: exposure must be a float [3,4] tensor (a 3x3 colour matrix and a bias column), got "
+                         f"{tuple(exposure.shape) if isinstance(exposure, torch.Tensor) else type(exposure).__name__}")
+    if C != 3:
+        raise ValueError(f"training_image_loss: an exposure needs a three-channel image, got C = {C}")
+    if exposure.device != image.device:
+        raise ValueError(f"training_image_loss: exposure on {exposure.device}, image on {image.device}")
+    return exposure
+
+
+def training_image_loss(image, gt, lambda_dssim: float = 0.2, *, weight=None, exposure=None):
+    """((1 - lambda) L1 + lambda (1 - SSIM), L1, SSIM) of train.py:199-204 from one node (three launches per training step).
+    `weight` ([H,W] or [1,H,W]: a mask or a soft per-pixel weight) and `exposure` (a [3,4] affine colour transform of the render,
+    which may require grad) are defined in the module docstring; without them the call is the plain node, launch for launch."""
     if image.dim() == 4 and image.shape[0] == 1:
         image, gt = image[0], gt[0]
-    if image.is_cuda and image.dim() == 3 and image.shape == gt.shape:
-        return _TrainImageLoss.apply(image, gt, float(lambda_dssim))
-    l1, s = l1_ssim(image, gt)
-    return (1.0 - lambda_dssim) * l1 + lambda_dssim * (1.0 - s), l1, s
+    if weight is None and exposure is None:
+        if image.is_cuda and image.dim() == 3 and image.shape == gt.shape:
+            return _TrainImageLoss.apply(image, gt, float(lambda_dssim))
+        l1, s = l1_ssim(image, gt)
+        return (1.0 - lambda_dssim) * l1 + lambda_dssim * (1.0 - s), l1, s
+    if image.dim() != 3 or image.shape != gt.shape:
+        raise ValueError("training_image_loss expects two [C,H,W] images of the same shape")
+    if image.device != gt.device:
+        raise ValueError(f"training_image_loss: image on {image.device}, gt on {gt.device}")
+    C, H, W = image.shape
+    w = None if weight is None else _loss_weight(weight, H, W, image)
+    E = None if exposure is None else _loss_exposure(exposure, C, image)
+    return _TrainImageLossWeighted.apply(image, gt, float(lambda_dssim), w, E)
 
 
 class _MeanReg(torch.autograd.Function):

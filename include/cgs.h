@@ -1648,6 +1648,31 @@ int cgs_l1_ssim_finish(const float *partials, int C, int H, int W, float lam, fl
 int cgs_l1_ssim_bwd_loss(const float *img, const float *gt, const float *maps, const float *g_loss,
                          const float *g2, float lam, int C, int H, int W, float *dimg, void *stream);
 
+/* The same loss with a per-pixel weight and a per-view exposure built in (masks; upstream 3DGS's 3x4 affine colour transform).
+ *   weight [H,W] fp32 or NULL (w = 1), shared by the channels; exposure E [3,4] fp32 or NULL (needs C == 3):
+ *   x'_c(p) = sum_k x_k(p) E[k][c] + E[c][3];  S = sum_p w_p;  L1 = sum w |x' - y| / (C S);  SSIM = sum w ssim(x', y) / (C S).
+ *   The window statistics see every pixel (zero padding of x' and y); the weight multiplies the SSIM map.
+ * cgs_l1_ssim_w_fwd: partials [cgs_l1_ssim_partials(C,H,W), 3] = per workgroup (sum w |x' - y|, sum w ssim, sum w) in the order
+ *   (channel, tile row, tile column) — the third column adds up to C S; maps [3,C,H,W] (may be NULL) = the three derivative
+ *   maps of (x', y) times w.  One launch.
+ * cgs_l1_ssim_w_finish: out3 = (loss, L1, SSIM) and inv_cs [1] = 1 / (C S), one single-workgroup launch in a fixed order.
+ *   S == 0 gives (0, 0, 1) and inv_cs = 0, decided on the device.
+ * cgs_l1_ssim_w_bwd: with G_c = d / d x'_c of (g_loss [1], g2 [2] as in cgs_l1_ssim_bwd_loss; either may be NULL, not both),
+ *   dimg_k = sum_c E[k][c] G_c (dimg = G without an exposure) and, when dexposure_partials is not NULL (it needs an
+ *   exposure), dexposure_partials [cgs_l1_ssim_partials(1,H,W), 3, 4] = per tile the sums of x_k G_c ([k][c]) and of G_c
+ *   ([c][3]).  dimg may be NULL when dexposure_partials is not.  inv_cs is cgs_l1_ssim_w_finish's.  One launch; neither x' nor G
+ *   is written to memory.
+ * cgs_l1_ssim_w_dexposure: dexposure [3,4] = the partials added in a fixed order (one workgroup, no atomics).
+ * All reject a NULL pointer they need, a shape below 1 and an exposure with C != 3 before anything is launched. */
+int cgs_l1_ssim_w_fwd(const float *img, const float *gt, const float *weight, const float *exposure, int C, int H,
+                      int W, float *maps, float *partials, void *stream);
+int cgs_l1_ssim_w_finish(const float *partials, int C, int H, int W, float lam, float *out3, float *inv_cs,
+                         void *stream);
+int cgs_l1_ssim_w_bwd(const float *img, const float *gt, const float *weight, const float *exposure,
+                      const float *maps, const float *inv_cs, const float *g_loss, const float *g2, float lam, int C,
+                      int H, int W, float *dimg, float *dexposure_partials, void *stream);
+int cgs_l1_ssim_w_dexposure(const float *dexposure_partials, int H, int W, float *dexposure, void *stream);
+
 /* sum_i img[i] * w[i] + lam * rate[0] (rate may be NULL) -> out [1], and its backward dimg = g[0] * w, drate[0] = g[0] * lam
  * (drate may be NULL): the linear objective a throughput measurement puts behind render() (train.py:206-209 with the image term
  * made linear), one launch each way, deterministic (per-workgroup partials in double, added in workgroup order).  scratch:
