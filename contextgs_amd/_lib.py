@@ -320,6 +320,13 @@ SIGNATURES = {
     "cgs_l1_ssim_w_finish": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "cgs_l1_ssim_w_bwd": (c_int, [c_void_p] * 8 + [c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cgs_l1_ssim_w_dexposure": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "cgs_bilagrid_slice_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "cgs_bilagrid_bwd_scratch_bytes": (c_size_t, [c_int] * 5),
+    "cgs_bilagrid_slice_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
+    "cgs_bilagrid_tv_scratch_bytes": (c_size_t, [c_int] * 4),
+    "cgs_bilagrid_tv_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cgs_bilagrid_tv_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cgs_reg_partials": (c_size_t, [c_int64]),
     "cgs_scaling_reg_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "cgs_scaling_reg_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

@@ -1673,6 +1673,36 @@ int cgs_l1_ssim_w_bwd(const float *img, const float *gt, const float *weight, co
                       int H, int W, float *dimg, float *dexposure_partials, void *stream);
 int cgs_l1_ssim_w_dexposure(const float *dexposure_partials, int H, int W, float *dexposure, void *stream);
 
+/* ---- per-view bilateral grids (Bilateral Guided Radiance Field Processing; contextgs_amd/bilagrid.py, csrc/bilagrid.hip) ----
+ * One view's grid G [12, L, Gh, Gw] fp32 holds a 3x4 affine colour map per node (channel 4 i + j = A[i][j]); img, out, dout and
+ * dimg are [3, H, W] fp32.  For pixel (y, x) with colour (r, g, b):
+ *   gx = (x + 0.5) / W * (Gw - 1), gy = (y + 0.5) / H * (Gh - 1), z = 0.299 r + 0.587 g + 0.114 b, gz = clamp(z (L - 1), 0, L - 1);
+ *   per axis of n nodes i0 = clamp(floor(g), 0, n - 1), i1 = min(i0 + 1, n - 1), f = g - i0, weights 1 - f on i0 and f on i1
+ *   (an axis of one node is legal);  A = sum over the 8 corners of wz wy wx G[:, zi, yi, xi];  out_i = sum_j A[i][j] rgb_j + A[i][3].
+ *   This is grid_sample(mode bilinear, align_corners, border padding) of the grid at (gx, gy, gz), then the affine map.
+ * cgs_bilagrid_slice_fwd: out, one launch.
+ * cgs_bilagrid_slice_bwd: with dA[i][j] = dout_i rgb_j (rgb_3 = 1):  dgrid[c, corner] = sum over the pixels of w_corner dA[c], and
+ *   dimg_j = sum_i A[i][j] dout_i + lum_j (L - 1) m sum_c dA[c] dA_c/dgz,  dA_c/dgz = sum over the xy corners of wy wx (G[c, z1] -
+ *   G[c, z0]),  m = 1 where 0 < z (L - 1) < L - 1 and 0 otherwise (a clamped guidance passes no gradient).  Either of dimg and
+ *   dgrid may be NULL, not both.  dgrid [12, L, Gh, Gw] is written in full (zeros where no pixel reaches a node; the caller does
+ *   not clear it) without float atomics: per-cell sums in `scratch` (cgs_bilagrid_bwd_scratch_bytes bytes, needed for dgrid
+ *   only), added per node in a fixed order, so two calls give the same bytes.  One launch for dimg, two for dgrid.
+ * cgs_bilagrid_tv_fwd: grids [N, 12, L, Gh, Gw];  out1 [1] = (1 / N) sum over the views and the axes (z, y, x) of (the sum of the
+ *   squared forward differences along the axis, all 12 channels) / (the number of such differences in one view); an axis of one
+ *   node adds nothing.  scratch: cgs_bilagrid_tv_scratch_bytes bytes (per-workgroup partials, added in order by a second launch).
+ * cgs_bilagrid_tv_bwd: dgrids = g[0] * d out1 / d grids, g [1] on the device; every element written, a gather of each node's up
+ *   to six neighbours, one launch.
+ * All reject a NULL pointer they need, a size below 1 and a short scratch before anything is launched; the size queries return
+ * 0 for a size below 1. */
+int cgs_bilagrid_slice_fwd(const float *grid, int L, int Gh, int Gw, const float *img, int H, int W, float *out,
+                           void *stream);
+size_t cgs_bilagrid_bwd_scratch_bytes(int L, int Gh, int Gw, int H, int W);
+int cgs_bilagrid_slice_bwd(const float *grid, int L, int Gh, int Gw, const float *img, const float *dout, int H, int W,
+                           float *dimg, float *dgrid, void *scratch, size_t scratch_bytes, void *stream);
+size_t cgs_bilagrid_tv_scratch_bytes(int N, int L, int Gh, int Gw);
+int cgs_bilagrid_tv_fwd(const float *grids, int N, int L, int Gh, int Gw, float *out1, void *scratch, void *stream);
+int cgs_bilagrid_tv_bwd(const float *grids, int N, int L, int Gh, int Gw, const float *g, float *dgrids, void *stream);
+
 /* sum_i img[i] * w[i] + lam * rate[0] (rate may be NULL) -> out [1], and its backward dimg = g[0] * w, drate[0] = g[0] * lam
  * (drate may be NULL): the linear objective a throughput measurement puts behind render() (train.py:206-209 with the image term
  * made linear), one launch each way, deterministic (per-workgroup partials in double, added in workgroup order).  scratch:
