@@ -1703,6 +1703,55 @@ size_t cgs_bilagrid_tv_scratch_bytes(int N, int L, int Gh, int Gw);
 int cgs_bilagrid_tv_fwd(const float *grids, int N, int L, int Gh, int Gw, float *out1, void *scratch, void *stream);
 int cgs_bilagrid_tv_bwd(const float *grids, int N, int L, int Gh, int Gw, const float *g, float *dgrids, void *stream);
 
+/* ---- monocular depth priors: aligned L1 / L2 and Pearson depth losses (contextgs_amd/depth_prior.py, csrc/depth_prior.hip) ----
+ * x (the rendered map, differentiated), y (the prior) [H*W] fp32; mask [H*W] or NULL: CGS_DP_MASK_FLOAT = fp32 weights m >= 0,
+ * CGS_DP_MASK_BYTE = one byte per pixel (m = 1 where the byte is not 0), CGS_DP_MASK_NONE = m = 1 (mask must be NULL).  n = H W.
+ * A pixel of m = 0 is selected out, not multiplied out: its x and y may be NaN or Inf, no result sees them and its gradient is +0.
+ *   Moments over the other pixels, in fp64 (a product of two fp32 values is exact there):
+ *     M = sum m, Sx = sum m x, Sy = sum m y, Sxx, Syy, Sxy;  Vx = M Sxx - Sx^2, Vy = M Syy - Sy^2, C = M Sxy - Sx Sy.
+ *   Least-squares map of the prior into the render's units: a = C / Vy, b = (Sx - a Sy) / M; Vy <= 1e-12 M Syy: a = 0, b = Sx / M
+ *     (M = 0: a = b = 0).
+ *   r = x - (a y + b);  L1 = sum m |r| / N, L2 = sum m r^2 / N;  N = M (CGS_DP_MEAN_MASK) or n (CGS_DP_MEAN_IMAGE); N = 0 or M = 0
+ *     gives 0.  d L / d x_p = g m_p w(r_p) / N with w = sign(r) (sign(0) = 0) or 2 r.  (a, b) are constants of the backward.
+ *   Pearson = 1 - rho, rho = C / sqrt(Vx Vy);  d / d x_p = -g m_p [(M y_p - Sy) / sqrt(Vx Vy) - rho (M x_p - Sx) / Vx];
+ *     Vx <= 1e-12 M Sxx or Vy <= 1e-12 M Syy (so also M = 0): the value is 1 and the gradient 0.
+ * cgs_depth_prior_fwd: out1 [1].  kind CGS_DP_L1 / _L2 / _PEARSON (align and mean_over are ignored for Pearson).  align
+ *   CGS_DP_ALIGN_GIVEN: (a, b) are the arguments a, b, or a_dev[0], b_dev[0] (device fp32) where those are not NULL;
+ *   CGS_DP_ALIGN_LSTSQ: the fit above, solved on the device.  coef: CGS_DEPTH_PRIOR_COEF_BYTES bytes, 8-byte aligned, written
+ *   by the call and read by the backward entries: fp64 (c0, c1, c2, scale, a, b, M, value), where t_p = c2 x_p + c1 y_p + c0 is r_p
+ *   (c2 = 1, c1 = -a, c0 = -b, scale = 1 / N) or the bracket of the Pearson gradient with its sign (scale = 1).  r_p is formed per
+ *   pixel in fp64 from these and rounded to fp32 once, with the result.  scratch: cgs_depth_prior_scratch_bytes(H, W) bytes,
+ *   8-byte aligned, per-workgroup partial sums that one workgroup adds in index order (no float atomics: two calls give the same
+ *   bytes, also with planes off their 16-byte alignment).  Launches: 2 (L2 and Pearson; L1 with a given map), 4 (L1 with the fit).
+ * cgs_depth_prior_bwd: dx [H*W] = g[0] * d out1 / d x, g [1] on the device, every element written; one launch.
+ * cgs_depth_prior_dab: dab2 [2] = g[0] * (d out1 / d a, d out1 / d b) of a GIVEN map: -(g / N) sum m w(r) y and -(g / N) sum m w(r);
+ *   two launches, the same scratch.
+ * cgs_depth_prior_scale_shift: ab2 [2] = the least-squares (a, b) as fp32; two launches.
+ * No entry synchronises with the host.  CGS_ERR_ARG (NULL planes, a mask that contradicts its type, H or W < 1, more than 2^30
+ * pixels, an unknown kind, mask type, align or mean_over, a misaligned coef or scratch) and CGS_ERR_WORKSPACE (a short scratch)
+ * are decided before anything is enqueued, with a message that names the function; the size query returns 0 for such a shape. */
+#define CGS_DP_L1 0
+#define CGS_DP_L2 1
+#define CGS_DP_PEARSON 2
+#define CGS_DP_MASK_NONE 0
+#define CGS_DP_MASK_FLOAT 1
+#define CGS_DP_MASK_BYTE 2
+#define CGS_DP_ALIGN_GIVEN 0
+#define CGS_DP_ALIGN_LSTSQ 1
+#define CGS_DP_MEAN_MASK 0
+#define CGS_DP_MEAN_IMAGE 1
+#define CGS_DEPTH_PRIOR_COEF_BYTES 64
+size_t cgs_depth_prior_scratch_bytes(int H, int W);
+int cgs_depth_prior_fwd(const float *x, const float *y, const void *mask, int mask_type, int H, int W, int kind, int align,
+                        int mean_over, double a, double b, const float *a_dev, const float *b_dev, float *out1, void *coef,
+                        void *scratch, size_t scratch_bytes, void *stream);
+int cgs_depth_prior_bwd(const float *x, const float *y, const void *mask, int mask_type, int H, int W, int kind,
+                        const void *coef, const float *g, float *dx, void *stream);
+int cgs_depth_prior_dab(const float *x, const float *y, const void *mask, int mask_type, int H, int W, int kind,
+                        const void *coef, const float *g, float *dab2, void *scratch, size_t scratch_bytes, void *stream);
+int cgs_depth_prior_scale_shift(const float *x, const float *y, const void *mask, int mask_type, int H, int W, float *ab2,
+                                void *scratch, size_t scratch_bytes, void *stream);
+
 /* sum_i img[i] * w[i] + lam * rate[0] (rate may be NULL) -> out [1], and its backward dimg = g[0] * w, drate[0] = g[0] * lam
  * (drate may be NULL): the linear objective a throughput measurement puts behind render() (train.py:206-209 with the image term
  * made linear), one launch each way, deterministic (per-workgroup partials in double, added in workgroup order).  scratch:
